@@ -11,6 +11,11 @@ The global grid is fixed (strong scaling): rank r owns the contiguous block of
 rows of init_row_decomposition (HypreSystem.cpp:525-544), i.e. z-slabs.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
+
+A plain run sets up, warms up, times --steps solves and prints the line.  Everything else the benchmark reports --
+per-kernel roofline figures (HIP events in the timed region and one extra solve), the error against x* = 1, the
+side-lines (cogmres, value dictionary off, non_galerkin_tol) and the CPU baseline -- runs only with --full.
+--dump-outputs DIR writes what the last timed step computed (bench.py dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -38,12 +43,18 @@ def parse():
     ap.add_argument("--tol", type=float, default=1e-8)
     ap.add_argument("--kdim", type=int, default=50)
     ap.add_argument("--max-iter", type=int, default=200)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline figures, the side-lines and the CPU "
+                         "baseline (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's solution (all of it, or a fixed seeded sample of "
+                         "rows on large grids), iteration count and final relative residual as DIR/<name>.npy")
     ap.add_argument("--cpu-n", type=int, default=int(os.environ.get("MI_BENCH_CPU_N", "-1")),
-                    help="grid side of the bounded CPU-baseline sample (0 = skip; default: 256 = BASELINE.json "
+                    help="--full: grid side of the bounded CPU-baseline sample (0 = skip; default: 256 = BASELINE.json "
                          "config 2 when the host has the memory, else 128)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-general", action="store_true",
-                    help="skip the general-operator leg (second setup with the value dictionary off + 3 solves)")
+                    help="--full: skip the general-operator leg (second setup with the value dictionary off + 3 solves)")
     ap.add_argument("--workload", choices=("laplace", "convdiff3"), default="laplace",
                     help="laplace = the headline (BASELINE.json configs 2/3: strong scaling of one n^3 grid); convdiff3 = "
                          "side-line for config 5: 3-component non-symmetric convection-diffusion system, BiCGSTAB + "
@@ -51,12 +62,12 @@ def parse():
     ap.add_argument("--segregated", type=int, default=0,
                     help="convdiff3: 1 = one solve per component (segregated_solve 1), 0 = one multivector solve")
     ap.add_argument("--sideline-non-galerkin", type=float, default=0.05,
-                    help="non_galerkin_tol of the side-line leg reported beside the headline at N = 1 (0 = skip)")
+                    help="--full: non_galerkin_tol of the side-line leg reported beside the headline at N = 1 (0 = skip)")
     ap.add_argument("--halo-transport", choices=("rccl", "ipc"), default=os.environ.get("MI_BENCH_HALO_TRANSPORT", "rccl"),
                     help="N > 1: how the halo updates travel -- rccl = ncclSend/ncclRecv groups (default), ipc = peer stores into "
                          "hipIpc-mapped mailboxes (HYPRE_MI_CommEnablePeerStoreExchange); reductions are RCCL either way")
     ap.add_argument("--ipc-sideline", action="store_true", default=os.environ.get("MI_BENCH_IPC_SIDELINE") == "1",
-                    help="N > 1: AFTER the headline line has been printed, repeat the solves on the peer-store transport and "
+                    help="--full, N > 1: AFTER the headline line has been printed, repeat the solves on the peer-store transport and "
                          "print the result as a second line tagged [sideline_peer_store].  Opt-in (ADVICE r3): that transport "
                          "has never run between separate devices, and a fault inside a peer store is not a Python exception")
     ap.add_argument("--no-ipc-sideline", action="store_true", help="(accepted for older command lines; the side-line is opt-in now)")
@@ -65,7 +76,43 @@ def parse():
     ap.add_argument("--amg", action="append", default=[], metavar="KEY=VALUE",
                     help="boomeramg_settings override for a side-line (e.g. --amg agg_num_levels=1); the headline "
                          "configuration is the one without overrides")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_MAX_VALUES = 1 << 22  # float64 values of the solution written by --dump-outputs: 32 MB, under the 64 MB bound
+
+
+def output_rows(n_global, ncomp=1):
+    """Global rows of the solution that --dump-outputs writes: all of them while ncomp * n_global <= DUMP_MAX_VALUES,
+    else a fixed seeded sample (sorted, distinct, the same in every run on the same grid)."""
+    cap = DUMP_MAX_VALUES // ncomp
+    if n_global <= cap:
+        return np.arange(n_global, dtype=np.int64)
+    return np.unique(np.random.default_rng(12345).integers(0, n_global, cap, dtype=np.int64))
+
+
+def dump_outputs(path, dist, rank, ilower, xs, n_global, scalars):
+    """What a caller of the timed path receives after its last step: the solution xs (this rank's rows from ilower;
+    shape (ncomp, rows)) at output_rows(), gathered on rank 0 in global row order, and the solver's scalars.
+    Written by rank 0 as path/x.npy (float64; shape (rows,) for one component) and path/<scalar>.npy."""
+    rows = output_rows(n_global, xs.shape[0])
+    mine = rows[(rows >= ilower) & (rows < ilower + xs.shape[1])]
+    part = np.ascontiguousarray(xs[:, mine - ilower], dtype=np.float64)
+    if dist is not None:
+        parts = [None] * dist.get_world_size() if rank == 0 else None
+        dist.gather_object(part, parts, dst=0)
+        if rank == 0:
+            part = np.concatenate(parts, axis=1)
+    if rank != 0:
+        return
+    assert part.shape[1] == rows.size, (part.shape, rows.size)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "x.npy"), part[0] if part.shape[0] == 1 else part)
+    for name, v in scalars.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.array([v], dtype=np.float64))
 
 
 def peer_store_sideline(mi, dist, torch, rank, world, one_solve, barrier, steps, head_iters, head_rel_res, head_s, ndof):
@@ -260,6 +307,9 @@ def run_convdiff3(args, mi, dist, rank, world, transport, rehearsal, torch):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     got = xv[0].get_all() if not args.segregated else np.stack([v.get() for v in xv])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dist, rank, ilower, got, ndof,
+                     {"iterations": bi.num_iterations, "final_rel_residual": bi.final_rel_res})
     err = float(np.abs(got - X).max())
     if dist is not None:
         e = torch.tensor([err], dtype=torch.float64, device="cpu")
@@ -550,8 +600,10 @@ def main():
     # HIP events in the timed region only around the dominant kernel (the level-0 SpMV of the GMRES loop, ~20 launches
     # per solve).  An event pair costs the queue ~10 us (profiles/r03_rank_size_proxy_256.txt: the gaps in front of every
     # timed launch); around the ~270 relaxation and Gram-Schmidt launches of a solve that is 0.5 % of a 512^3 solve on
-    # one GPU but ~3 % of the same solve on 8 -- those classes are timed in one extra solve AFTER the timed region
-    mi.profile_enable(mi.PROF_SPMV_L0, cap)
+    # one GPU but ~3 % of the same solve on 8 -- those classes are timed in one extra solve AFTER the timed region.
+    # --full only: a plain run times the solves alone
+    if args.full:
+        mi.profile_enable(mi.PROF_SPMV_L0, cap)
     comm_names = ("halo_exchange", "allreduce", "allgather", "matvec_overlapped", "gs_overlapped", "gs_in_order")
 
     def comm_counters():
@@ -576,10 +628,76 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    spmv_n, spmv_ms, spmv_min = mi.profile_get(mi.PROF_SPMV_L0)
-    spmv_kernel = mi.profile_kernel_name(mi.PROF_SPMV_L0)
     rel_res = gm.final_rel_res
     iters = gm.num_iterations
+    chunk = C.c_int()
+    mi.call("HYPRE_MI_GetGSChunk", C.byref(chunk))
+    xs = x.get() if (args.full or args.dump_outputs) else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dist, rank, mi.row_partition(ndof, world, rank)[0], xs[None, :], ndof,
+                     {"iterations": iters, "final_rel_residual": rel_res})
+
+    def headline():
+        """The fields of the result line that a plain run reports (rank 0)."""
+        out_ = {
+            "metric": "GMRES+AMG solve GDOF/s (N_global*iterations/t_solve; iterations/sec in iterations_per_s), %d^3 Laplacian" % n,
+            "value": ndof * iters_total / elapsed / 1e9,
+            "unit": "GDOF/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {
+                "workload": f"laplace_3d {n}^3 {args.stencil}-pt (N={ndof}), GMRES({args.kdim})+BoomerAMG "
+                            f"(PMIS, ext+i, C/F l1-hybrid-SGS chunk {chunk.value}, V(1,1)), tol {args.tol:g}, x0=0"
+                            + (f"; SIDE-LINE with boomeramg_settings overrides {amg_kw}" if amg_kw else ""),
+                "row_partition": f"{world} contiguous block-row slab(s)",
+                "transport": transport,
+            },
+            "iterations_per_solve": iters,
+            "iterations_per_s": iters_total / elapsed,
+            "final_rel_residual": rel_res,
+            "amg_levels": amg.num_levels,
+            "operator_complexity": amg.operator_complexity,
+            "setup_s": t_setup,
+            "build_s": t_build,
+        }
+        # what one solve asks of the interconnect, counted by the library on this rank inside the timed region
+        # (HYPRE_MI_GetCounter; VERDICT r3 item 6: a multi-GPU run should explain its own efficiency).  Per solve of m
+        # iterations: 3 + m + m(m+1)/2 scalar all-reduces (modified Gram-Schmidt: one per coefficient), <= 7 neighbour
+        # exchanges per distributed level and cycle + 1 per GMRES matvec, one all-gather per cycle (redundant tail).
+        m_it = iters
+        out_["comm_ops"] = {
+            "what": "collective operations of ONE solve on rank 0 (timed region / steps), from the library's counters",
+            **{k_: (c1[k_] - c0[k_]) / max(1, args.steps) for k_ in comm_names},
+            "host_synchronisations": m_it + 4,  # one per Arnoldi step (Hessenberg column), the norms of b, r0 and the final residual
+            "expected_allreduce": (3 + m_it + m_it * (m_it + 1) // 2) if world > 1 else 0,
+            "note": "halo_exchange counts neighbour exchanges (matvec + relaxation + transfer operators); matvec_overlapped / "
+                    "gs_overlapped went beside the diag-block kernel on the side stream, gs_in_order did not; all zero on one rank.  "
+                    "Kernel launches are not counted in-process: a rocprofv3 trace of this workload on one GPU has 1324 launches per "
+                    "solve, 440 of them shorter than 25 us (4.7 ms together), and 0.35 ms per solve outside kernels "
+                    "(RECORDED: profiles/r04_gaps_512.txt)",
+        }
+        if rehearsal:
+            out_["rehearsal"] = True
+        return out_
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        if dist is not None:
+            dist.barrier()
+            mi.call("HYPRE_MI_CommFinalize")
+            dist.destroy_process_group()
+        return
+
+    spmv_n, spmv_ms, spmv_min = mi.profile_get(mi.PROF_SPMV_L0)
+    spmv_kernel = mi.profile_kernel_name(mi.PROF_SPMV_L0)
     rel_n = rel_ms = rel_min = dot_n = dot_ms = axpy_n = axpy_ms = 0
     relax_kernel = ""
     extra_solves = 0
@@ -598,10 +716,7 @@ def main():
         mi.profile_enable(mi.PROF_DOT, 0)
         mi.profile_enable(mi.PROF_AXPY, 0)
         mi.profile_enable(mi.PROF_SPMV_L0, cap)  # (the general-operator leg below reads classes 0 and 1)
-    xs = x.get()
     err = float(np.abs(xs - 1.0).max()) if xs.size else 0.0
-    nlev = amg.num_levels
-    opcx = amg.operator_complexity
 
     # algorithmic bytes of one level-0 launch on this rank (DESIGN.md "Kernels")
     nr, nc, nnz = C.c_int(), C.c_int(), C.c_longlong()
@@ -680,59 +795,10 @@ def main():
                     "achieved": gs_bytes / (per_solve_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                     "frac": gs_bytes / (per_solve_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
                     "axpy_ms_per_solve": axpy_ms / extra_solves}
-        chunk = C.c_int()
-        mi.call("HYPRE_MI_GetGSChunk", C.byref(chunk))
-        out = {
-            "metric": "GMRES+AMG solve GDOF/s (N_global*iterations/t_solve; iterations/sec in iterations_per_s), %d^3 Laplacian" % n,
-            "value": ndof * iters_total / elapsed / 1e9,
-            "unit": "GDOF/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {
-                "workload": f"laplace_3d {n}^3 {args.stencil}-pt (N={ndof}), GMRES({args.kdim})+BoomerAMG "
-                            f"(PMIS, ext+i, C/F l1-hybrid-SGS chunk {chunk.value}, V(1,1)), tol {args.tol:g}, x0=0"
-                            + (f"; SIDE-LINE with boomeramg_settings overrides {amg_kw}" if amg_kw else ""),
-                "row_partition": f"{world} contiguous block-row slab(s)",
-                "transport": transport,
-            },
-            "iterations_per_solve": iters,
-            "iterations_per_s": iters_total / elapsed,
-            "final_rel_residual": rel_res,
-            "max_abs_error_vs_ones": err,
-            "amg_levels": nlev,
-            "operator_complexity": opcx,
-            "internal_locality_numbering": bool(mi.BoomerAMG.input_ordering(amg)[0]),
-            "setup_s": t_setup,
-            "build_s": t_build,
-            "roofline": roof,
-            "roofline_relax": roof_relax,
-            "gram_schmidt": gram,
-        }
-        # what one solve asks of the interconnect, counted by the library on this rank inside the timed region
-        # (HYPRE_MI_GetCounter; VERDICT r3 item 6: a multi-GPU run should explain its own efficiency).  Per solve of m
-        # iterations: 3 + m + m(m+1)/2 scalar all-reduces (modified Gram-Schmidt: one per coefficient), <= 7 neighbour
-        # exchanges per distributed level and cycle + 1 per GMRES matvec, one all-gather per cycle (redundant tail).
-        m_it = iters
-        out["comm_ops"] = {
-            "what": "collective operations of ONE solve on rank 0 (timed region / steps), from the library's counters",
-            **{k_: (c1[k_] - c0[k_]) / max(1, args.steps) for k_ in comm_names},
-            "host_synchronisations": m_it + 4,  # one per Arnoldi step (Hessenberg column), the norms of b, r0 and the final residual
-            "expected_allreduce": (3 + m_it + m_it * (m_it + 1) // 2) if world > 1 else 0,
-            "note": "halo_exchange counts neighbour exchanges (matvec + relaxation + transfer operators); matvec_overlapped / "
-                    "gs_overlapped went beside the diag-block kernel on the side stream, gs_in_order did not; all zero on one rank.  "
-                    "Kernel launches are not counted in-process: a rocprofv3 trace of this workload on one GPU has 1324 launches per "
-                    "solve, 440 of them shorter than 25 us (4.7 ms together), and 0.35 ms per solve outside kernels "
-                    "(RECORDED: profiles/r04_gaps_512.txt)",
-        }
-        if rehearsal:
-            out["rehearsal"] = True
+        out = headline()
+        out.update({"max_abs_error_vs_ones": err,
+                    "internal_locality_numbering": bool(mi.BoomerAMG.input_ordering(amg)[0]),
+                    "roofline": roof, "roofline_relax": roof_relax, "gram_schmidt": gram})
     # ---- side-line (N = 1): the reference's other Krylov choice on the SAME hierarchy, method: cogmres
     # (/root/reference/src/HypreSystem.cpp:372-388) -- GMRES with block classical Gram-Schmidt: one pass of inner products
     # and one block update per step instead of i dependent fused passes.  NOT the headline (the headline is method: gmres).

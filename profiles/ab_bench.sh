@@ -5,7 +5,7 @@ A=$1; B=$2; n=${3:-512}; rounds=${4:-2}
 for r in $(seq $rounds); do
   for v in A B; do
     lib=$A; [ $v = B ] && lib=$B
-    MI_HYPRE_LIB=$(realpath $lib) python3 bench.py --n $n --steps 4 --warmup 1 --no-cpu --no-general 2>/dev/null | python3 -c "
+    MI_HYPRE_LIB=$(realpath $lib) python3 bench.py --n $n --steps 4 --warmup 1 --full --no-cpu --no-general 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 g=d.get('gram_schmidt') or {}

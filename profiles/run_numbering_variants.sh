@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-.}"; REPO=$(pwd); export TMPDIR=/tmp
 out=$REPO/gpurun_out/numbering_variants.txt; : > $out
 run() {  # label, env...
   label=$1; shift
-  env "$@" python3 bench.py --steps 3 --warmup 1 --no-cpu --no-general --sideline-non-galerkin 0 2>/dev/null | python3 -c "
+  env "$@" python3 bench.py --steps 3 --warmup 1 --full --no-cpu --no-general --sideline-non-galerkin 0 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$label: ms/solve %.1f iters %d spmv_l0 %.3f ms relax_l0 %.3f ms setup %.1f s' % (d['ms_per_step'], d['iterations_per_solve'], d['roofline']['avg_ms'], d['roofline_relax']['avg_ms'], d['setup_s']))" >> $out

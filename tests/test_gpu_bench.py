@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -19,7 +20,7 @@ def _json_line(out):
 
 def test_bench_single_gpu_contract():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--grid", "64", "--cpu-n", "32"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
+                        "--grid", "64", "--cpu-n", "32", "--full"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
                        timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-3000:]
     j = _json_line(p.stdout)
@@ -57,6 +58,28 @@ def test_bench_single_gpu_contract():
     assert 5 <= j["iterations_per_solve"] <= 30 and j["final_rel_residual"] <= 1e-8
 
 
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """Without --full the line holds the headline only (no roofline, side-lines or CPU baseline); --steps sets the timed
+    steps; --dump-outputs writes the last timed step's solution and scalars."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--grid", "64", "--dump-outputs", str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                       text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stdout[-3000:]
+    j = _json_line(p.stdout)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config", "iterations_per_solve",
+              "final_rel_residual", "comm_ops"):
+        assert k in j, k
+    for k in ("roofline", "roofline_relax", "gram_schmidt", "roofline_general", "sideline_cogmres", "sideline_non_galerkin",
+              "cpu_baseline"):
+        assert k not in j, k
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["unit"] == "GDOF/s"
+    assert abs(j["value"] - 64 ** 3 * j["iterations_per_solve"] / (j["ms_per_step"] * 1e-3) / 1e9) <= 1e-9 * j["value"]
+    x = np.load(tmp_path / "x.npy")
+    assert x.dtype == np.float64 and x.shape == (64 ** 3,) and np.abs(x - 1.0).max() < 1e-5
+    assert np.load(tmp_path / "iterations.npy").tolist() == [j["iterations_per_solve"]]
+    assert np.load(tmp_path / "final_rel_residual.npy").tolist() == [j["final_rel_residual"]]
+
+
 def test_bench_two_ranks_rehearsal():
     env = dict(os.environ)
     env["MI_BENCH_SHARED_GPU"] = "1"
@@ -64,7 +87,7 @@ def test_bench_two_ranks_rehearsal():
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", "29791", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-           "--grid", "64", "--no-cpu", "--ipc-sideline"]
+           "--grid", "64", "--no-cpu", "--ipc-sideline", "--full"]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-3000:]
     j = _json_line(p.stdout)
@@ -84,9 +107,10 @@ def test_bench_two_ranks_rehearsal():
     assert "ipc-peer-store" in side["transport"] and side["ms_per_step"] > 0
 
 
-def test_bench_two_ranks_rehearsal_peer_store_halo():
+def test_bench_two_ranks_rehearsal_peer_store_halo(tmp_path):
     """The same rehearsal with the halo updates on the hipIpc peer-store transport (`--halo-transport ipc`; reductions stay
-    on the gloo callbacks here, on RCCL in a real multi-GPU run): same iteration count and residual as over the callbacks."""
+    on the gloo callbacks here, on RCCL in a real multi-GPU run): same iteration count and residual as over the callbacks,
+    and the same solution, gathered from both ranks by --dump-outputs."""
     env = dict(os.environ)
     env["MI_BENCH_SHARED_GPU"] = "1"
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -94,10 +118,12 @@ def test_bench_two_ranks_rehearsal_peer_store_halo():
     for port, extra in ((29793, []), (29795, ["--halo-transport", "ipc"])):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-               "--grid", "64", "--no-cpu"] + extra
+               "--grid", "64", "--no-cpu", "--dump-outputs", str(tmp_path / str(port))] + extra
         p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600, cwd=ROOT)
         assert p.returncode == 0, p.stdout[-3000:]
         res.append(_json_line(p.stdout))
     assert "hipIpc" in res[1]["config"]["transport"] and "hipIpc" not in res[0]["config"]["transport"]
     assert res[0]["iterations_per_solve"] == res[1]["iterations_per_solve"]
     assert res[0]["final_rel_residual"] == res[1]["final_rel_residual"]  # the transport moves the same bytes: bitwise
+    x0, x1 = np.load(tmp_path / "29793" / "x.npy"), np.load(tmp_path / "29795" / "x.npy")
+    assert x0.shape == (64 ** 3,) and np.abs(x0 - 1.0).max() < 1e-5 and np.array_equal(x0, x1)
