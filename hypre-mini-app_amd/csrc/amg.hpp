@@ -29,10 +29,14 @@ struct AmgParams {
   int agg_num_levels = 0, agg_interp_type = 4, agg_pmax_elmts = 0, keep_transpose = 0, rap2 = 0;
   double agg_trunc_factor = 0.0;
   int smooth_num_sweeps = 1;
-  // complex smoother on levels < smooth_num_levels (src/HypreSystem.cpp:235-320): 5 = ILU is implemented (block-Jacobi
-  // ILU(0), the IluSolver behind HYPRE_ILU); library defaults as in HYPRE
+  // complex smoother on levels < smooth_num_levels (src/HypreSystem.cpp:235-320): 5 = ILU (block-Jacobi ILU(k), the
+  // IluSolver behind HYPRE_ILU) and 4 = FSAI (static pattern, the FsaiSolver behind HYPRE_FSAI) are implemented; library
+  // defaults as in HYPRE
   int smooth_type = 6, smooth_num_levels = 0;
   int ilu_type = 0, ilu_level = 0, ilu_max_iter = 1, ilu_tri_solve = 1, ilu_lower_it = 5, ilu_upper_it = 5;
+  // smooth_type 4 = FSAI with the static pattern (algo type 3, the only one built), one step per sweep
+  int fsai_algo_type = 3, fsai_num_levels = 1, fsai_eig_max_iters = 5;
+  double fsai_threshold = 0.01;
   // non-Galerkin coarse operators (src/HypreSystem.cpp:161-176): drop tolerance for the coarse operator built FROM
   // level l (HYPRE's index): level_tol[l] when set (>= 0), else the global one; 0 = Galerkin
   double non_galerkin_tol = 0.0;
@@ -53,11 +57,13 @@ struct AmgParams {
   long long redundant_rows = -1;
 };
 
-struct IluSolver;
+struct SolverBase;
 
 struct AmgLevel {
   ParCSR *A = nullptr;
-  std::shared_ptr<IluSolver> smoother;  // complex smoother of this level (smooth_type 5 on levels < smooth_num_levels)
+  // complex smoother of this level on levels < smooth_num_levels: an IluSolver (smooth_type 5) or an FsaiSolver
+  // (smooth_type 4); level_ilu / level_fsai (solvers.hpp) give it by kind
+  std::shared_ptr<SolverBase> smoother;
   std::unique_ptr<ParCSR> A_own;
   int n = 0;
   HostCSR P, R;  // interpolation / restriction while the hierarchy is being built (moved into Pm / Rm)
@@ -223,6 +229,11 @@ struct BoomerAMG {
   void relax_pair(int level, int type, int first, const double *f, bool u_is_zero = false);
   void relax_sweeps(int level, int which, const double *f, bool u_is_zero = false);
   void cycle(int level, bool u_is_zero = false);
+  // complex smoothers of the levels < p.smooth_num_levels (end of setup_device); fsai_signature: the FSAI
+  // parameters they were built with -- a change after Setup rebuilds them before the next cycle
+  void build_smoothers();
+  std::vector<double> fsai_signature;
+  std::vector<double> current_fsai_signature() const;
   // cycle(level, true) never reads Lv.u before it has overwritten every row (one rank, Gauss-Seidel down sweep on
   // the zero-skipping kernels, or the dense coarsest solve): the caller need not zero-fill u first -- at 512^3 the
   // fills of a cycle are 1.6 GB of writes, 0.8 % of the solve, and one launch per level

@@ -1613,10 +1613,15 @@ void BoomerAMG::setup_host(ParCSR &A0) {
   if (p.interp_type != 0 && p.interp_type != 3 && p.interp_type != 4 && p.interp_type != 6)
     fail(4, "BoomerAMGSetup: interp_type " + std::to_string(p.interp_type) +
                 " is not implemented (0 classical modified, 3 direct, 4 multipass, 6 extended+i are); refusing to substitute another one");
-  if (p.smooth_num_levels > 0 && p.smooth_type != 5)
+  if (p.smooth_num_levels > 0 && p.smooth_type != 5 && p.smooth_type != 4)
     fail(4, "BoomerAMGSetup: smooth_type " + std::to_string(p.smooth_type) + " on " + std::to_string(p.smooth_num_levels) +
-                " level(s) is not implemented (5 = ILU is); refusing to smooth with something else");
-  if (p.smooth_num_levels > 0 && (p.ilu_type != 0 || p.ilu_level < 0))
+                " level(s) is not implemented (4 = FSAI and 5 = ILU are); refusing to smooth with something else");
+  if (p.smooth_num_levels > 0 && p.smooth_type == 4 && p.fsai_algo_type != 3)
+    fail(4, "BoomerAMGSetup: FSAI algo_type " + std::to_string(p.fsai_algo_type) +
+                " is not implemented (3 = static pattern is); refusing to substitute another one");
+  if (p.smooth_num_levels > 0 && p.smooth_type == 4 && (p.fsai_num_levels < 1 || p.fsai_num_levels > 3))
+    fail(4, "BoomerAMGSetup: FSAI num_levels " + std::to_string(p.fsai_num_levels) + " is not implemented (1, 2 and 3 are)");
+  if (p.smooth_num_levels > 0 && p.smooth_type == 5 && (p.ilu_type != 0 || p.ilu_level < 0))
     fail(4, "BoomerAMGSetup: ILU smoother type " + std::to_string(p.ilu_type) + " / level of fill " +
                 std::to_string(p.ilu_level) + " is not implemented (block-Jacobi ILU(k) = type 0, level k >= 0 is)");
   if (device_min_rows >= 0) dev_arena_hint((size_t)13 * 12 * (size_t)(A0.diag_nnz() + A0.offd.nnz()));
@@ -2408,6 +2413,47 @@ void BoomerAMG::build_replicated(ParCSR &A0) {
            t_phase[4]);
 }
 
+// complex smoother (smooth_type 5 = ILU, 4 = FSAI) on levels < smooth_num_levels, never on the last level (which is the
+// coarse solve, or the hand-over to the redundant tail): one block-Jacobi ILU(k) or FSAI of the level's diag block each
+void BoomerAMG::build_smoothers() {
+  Comm &comm = my_comm();
+  for (size_t li = 0; li < L.size(); li++) {
+    AmgLevel &Lv = L[li];
+    Lv.smoother.reset();
+    if ((p.smooth_type != 5 && p.smooth_type != 4) || (int)li >= p.smooth_num_levels || li + 1 >= L.size()) continue;
+    if (p.smooth_type == 4) {
+      auto fs = std::make_shared<FsaiSolver>();
+      fs->algo_type = p.fsai_algo_type;
+      fs->num_levels = p.fsai_num_levels;
+      fs->threshold = p.fsai_threshold;
+      fs->eig_max_iters = p.fsai_eig_max_iters;
+      fs->print_level = (p.print_level > 0 && comm.rank == 0) ? 1 : 0;
+      fs->setup(*Lv.A, comm, "BoomerAMGSetup: level " + std::to_string(li));
+      Lv.smoother = std::move(fs);
+      continue;
+    }
+    ensure_host((int)li);
+    auto ilu = std::make_shared<IluSolver>();
+    ilu->ilu_type = p.ilu_type;
+    ilu->level_of_fill = p.ilu_level;
+    ilu->tri_solve = p.ilu_tri_solve;
+    ilu->lower_it = p.ilu_lower_it;
+    ilu->upper_it = p.ilu_upper_it;
+    ilu->max_iter = p.ilu_max_iter;
+    ilu->tol = 0.0;
+    ilu->print_level = (p.print_level > 0 && comm.rank == 0) ? 1 : 0;
+    ilu->setup(*Lv.A);
+    Lv.smoother = std::move(ilu);
+  }
+  fsai_signature = current_fsai_signature();
+}
+
+std::vector<double> BoomerAMG::current_fsai_signature() const {
+  if (p.smooth_type != 4 || p.smooth_num_levels <= 0) return {};
+  return {(double)p.smooth_num_levels, (double)p.fsai_algo_type, (double)p.fsai_num_levels, p.fsai_threshold,
+          (double)p.fsai_eig_max_iters};
+}
+
 void BoomerAMG::setup_device() {
   TraceRange trace_setup("mi_hypre BoomerAMGSetup (solve-phase format)");
   MI_REQUIRE(host_ready, "BoomerAMG: setup_device before setup_host");
@@ -2531,25 +2577,7 @@ void BoomerAMG::setup_device() {
       zero_on_stream(Lv.snap.p, (size_t)Lv.n * sizeof(double));
     }
   }
-  // complex smoother (smooth_type 5 = ILU) on levels < smooth_num_levels, never on the last level (which is the
-  // coarse solve, or the hand-over to the redundant tail): one block-Jacobi ILU(0) of the level's diag block each
-  for (size_t li = 0; li < L.size(); li++) {
-    AmgLevel &Lv = L[li];
-    Lv.smoother.reset();
-    if (p.smooth_type != 5 || (int)li >= p.smooth_num_levels || li + 1 >= L.size()) continue;
-    ensure_host((int)li);
-    auto ilu = std::make_shared<IluSolver>();
-    ilu->ilu_type = p.ilu_type;
-    ilu->level_of_fill = p.ilu_level;
-    ilu->tri_solve = p.ilu_tri_solve;
-    ilu->lower_it = p.ilu_lower_it;
-    ilu->upper_it = p.ilu_upper_it;
-    ilu->max_iter = p.ilu_max_iter;
-    ilu->tol = 0.0;
-    ilu->print_level = (p.print_level > 0 && comm.rank == 0) ? 1 : 0;
-    ilu->setup(*Lv.A);
-    Lv.smoother = std::move(ilu);
-  }
+  build_smoothers();
   AmgLevel &Lc = L.back();
   if (Lc.dense) {
     const size_t width = (size_t)comm.size * (size_t)Lc.slot;

@@ -281,11 +281,27 @@ void BoomerAMG::relax_pair(int level, int type, int first, const double *f, bool
 void BoomerAMG::relax_sweeps(int level, int which, const double *f, bool u_is_zero) {
   const int type = p.relax_type[which];
   const bool has_cf = L[(size_t)level].has_cf;
-  if (L[(size_t)level].smoother && which != 2) {
+  if (FsaiSolver *fs = level_fsai(L[(size_t)level]); fs && which != 2) {
+    // FSAI (smooth_type 4): per sweep one step u += omega G^T G (f - A u), 3 launches; on a zero guess u = omega G^T G f
+    AmgLevel &Lv = L[(size_t)level];
+    Comm &comm = my_comm();
+    hipStream_t s = ctx().stream;
+    Lv.t_valid = false;
+    for (int sw = 0; sw < p.num_sweeps[which]; sw++) {
+      if (u_is_zero && sw == 0) {
+        fs->apply_add(f, Lv.u.p, true, k::prof_level(k::PROF_LVL_RELAX, level));
+      } else {
+        Lv.A->matvec(comm, -1.0, Lv.u.p, 1.0, f, Lv.tmp.p, s, k::prof_level(k::PROF_LVL_RELAX, level));
+        fs->apply_add(Lv.tmp.p, Lv.u.p, false, k::prof_level(k::PROF_LVL_RELAX, level));
+      }
+    }
+    return;
+  }
+  if (level_ilu(L[(size_t)level]) && which != 2) {
     // complex smoother (par_cycle.c: smooth_num_levels > level, smooth_type 5): per sweep ilu_max_iter times
     // u += (LU)^-1 (f - A u); on a zero guess the first residual is f itself
     AmgLevel &Lv = L[(size_t)level];
-    IluSolver &ilu = *Lv.smoother;
+    IluSolver &ilu = *level_ilu(Lv);
     Comm &comm = my_comm();
     hipStream_t s = ctx().stream;
     Lv.t_valid = false;
@@ -322,6 +338,7 @@ bool BoomerAMG::zero_cycle_ignores_u(int level) {
     if (tail) return false;
     return p.relax_type[2] == 9 && Lv.dense && p.num_sweeps[2] > 0;  // u = C^-1 f
   }
+  if (level_fsai(Lv)) return p.num_sweeps[0] >= 1;  // u = omega G^T G f overwrites every row
   if (Lv.smoother || p.num_sweeps[0] < 1 || zero_skip_mode() < 1) return false;
   const int type = p.relax_type[0];
   if (type == 9 || type == 11 || type == 12) return false;
@@ -339,6 +356,15 @@ bool BoomerAMG::zero_cycle_ignores_u(int level) {
 // one cycle on the level's own f (Lv.f) and u (Lv.u)
 void BoomerAMG::cycle(int level, bool u_is_zero) {
   const int nlev = (int)L.size();
+  if (level == 0 && fsai_signature != current_fsai_signature()) {
+    build_smoothers();  // an FSAI parameter changed after Setup: G and omega of another smoother
+    if (tail) {         // the redundant tail rebuilds its own at its next cycle
+      tail->p.fsai_algo_type = p.fsai_algo_type;
+      tail->p.fsai_num_levels = p.fsai_num_levels;
+      tail->p.fsai_threshold = p.fsai_threshold;
+      tail->p.fsai_eig_max_iters = p.fsai_eig_max_iters;
+    }
+  }
   if (level == 0 && collapsed_level >= 0 && collapsed_signature != cycle_signature())
     build_collapsed_tail();  // a cycle parameter changed after Setup: the tabulated maps are of another cycle
   AmgLevel &Lv = L[(size_t)level];
@@ -481,6 +507,7 @@ std::vector<double> BoomerAMG::cycle_signature() const {
   v.push_back(p.smooth_num_levels);
   v.push_back(p.smooth_num_sweeps);
   v.push_back(p.ilu_max_iter);
+  for (double x : current_fsai_signature()) v.push_back(x);
   return v;
 }
 

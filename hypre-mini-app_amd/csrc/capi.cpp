@@ -817,6 +817,15 @@ AMG_SET(ILUIterSetupTolerance, HYPRE_Real, (void)v)
 AMG_SET(ILUTriSolve, HYPRE_Int, p.ilu_tri_solve = v)
 AMG_SET(ILULowerJacobiIters, HYPRE_Int, p.ilu_lower_it = v)
 AMG_SET(ILUUpperJacobiIters, HYPRE_Int, p.ilu_upper_it = v)
+AMG_SET(FSAIAlgoType, HYPRE_Int, p.fsai_algo_type = v)  /* only 3 (static pattern) is built: others are refused at Setup */
+AMG_SET(FSAILocalSolveType, HYPRE_Int, (void)v)
+AMG_SET(FSAINumLevels, HYPRE_Int, p.fsai_num_levels = v)
+AMG_SET(FSAIThreshold, HYPRE_Real, if (v < 0.0) fail(HYPRE_ERROR_ARG, "fsai_threshold < 0"); p.fsai_threshold = v)
+AMG_SET(FSAIEigMaxIters, HYPRE_Int, if (v < 0) fail(HYPRE_ERROR_ARG, "fsai_eig_max_iters < 0"); p.fsai_eig_max_iters = v)
+AMG_SET(FSAIMaxSteps, HYPRE_Int, warn_ignored("fsai_max_steps", v))
+AMG_SET(FSAIMaxStepSize, HYPRE_Int, warn_ignored("fsai_max_step_size", v))
+AMG_SET(FSAIMaxNnzRow, HYPRE_Int, warn_ignored("fsai_max_nnz_row", v))
+AMG_SET(FSAIKapTolerance, HYPRE_Real, warn_ignored("fsai_kap_tolerance", v))
 #undef AMG_SET
 HYPRE_Int HYPRE_BoomerAMGSetLevelNonGalerkinTol(HYPRE_Solver solver, HYPRE_Real tol, HYPRE_Int level) {
   API_BEGIN
@@ -1083,6 +1092,61 @@ HYPRE_Int HYPRE_ILUSetTriSolve(HYPRE_Solver solver, HYPRE_Int v) {
   if (S(solver)->kind == SolverBase::K_ILU) ILU(solver)->tri_solve = v ? 1 : 0;
   API_END
 }
+
+// ------------------------------------------------------------------ FSAI (fsai.cpp)
+static FsaiSolver *FSAI(HYPRE_Solver s) {
+  SolverBase *b = S(s);
+  if (b->kind != SolverBase::K_FSAI) fail(HYPRE_ERROR_ARG, "handle is not an FSAI solver");
+  return static_cast<FsaiSolver *>(b);
+}
+HYPRE_Int HYPRE_FSAICreate(HYPRE_Solver *solver) {
+  API_BEGIN
+  if (!solver) fail(HYPRE_ERROR_ARG, "FSAICreate: NULL output");
+  *solver = reinterpret_cast<HYPRE_Solver>(static_cast<SolverBase *>(new FsaiSolver()));
+  API_END
+}
+HYPRE_Int HYPRE_FSAIDestroy(HYPRE_Solver solver) {
+  API_BEGIN
+  FSAI(solver);
+  delete S(solver);
+  API_END
+}
+HYPRE_Int HYPRE_FSAISetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector, HYPRE_ParVector) {
+  API_BEGIN
+  if (!A) fail(HYPRE_ERROR_ARG, "FSAISetup: NULL matrix");
+  FSAI(solver)->setup(*PM(A), current_comm(), "HYPRE_FSAISetup");
+  transport_gate(nullptr, "FSAISetup");
+  API_END
+}
+HYPRE_Int HYPRE_FSAISolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x) {
+  API_BEGIN
+  if (!A || !b || !x) fail(HYPRE_ERROR_ARG, "FSAISolve: NULL argument");
+  FSAI(solver)->solve(*PM(A), *PV(b), *PV(x));
+  transport_gate(PV(x), "FSAISolve");
+  API_END
+}
+#define FSAI_SET(NAME, TYPE, STMT)                            \
+  HYPRE_Int HYPRE_FSAISet##NAME(HYPRE_Solver solver, TYPE v) { \
+    API_BEGIN FsaiSolver *o = FSAI(solver);                   \
+    (void)o;                                                  \
+    STMT;                                                     \
+    API_END                                                   \
+  }
+FSAI_SET(AlgoType, HYPRE_Int, o->algo_type = v)  /* only 3 (static pattern) is built: others are refused at Setup */
+FSAI_SET(LocalSolveType, HYPRE_Int, (void)v)
+FSAI_SET(NumLevels, HYPRE_Int, o->num_levels = v)
+FSAI_SET(Threshold, HYPRE_Real, if (v < 0.0) fail(HYPRE_ERROR_ARG, "FSAI threshold < 0"); o->threshold = v)
+FSAI_SET(EigMaxIters, HYPRE_Int, if (v < 0) fail(HYPRE_ERROR_ARG, "FSAI eig_max_iters < 0"); o->eig_max_iters = v)
+FSAI_SET(Omega, HYPRE_Real, o->omega_user = v)
+FSAI_SET(MaxIterations, HYPRE_Int, if (v < 0) fail(HYPRE_ERROR_ARG, "FSAI max_iterations < 0"); o->max_iter = v)
+FSAI_SET(Tolerance, HYPRE_Real, o->tol = v)
+FSAI_SET(ZeroGuess, HYPRE_Int, o->zero_guess = v != 0)
+FSAI_SET(PrintLevel, HYPRE_Int, o->print_level = v)
+FSAI_SET(MaxSteps, HYPRE_Int, warn_ignored("fsai_max_steps", v))
+FSAI_SET(MaxStepSize, HYPRE_Int, warn_ignored("fsai_max_step_size", v))
+FSAI_SET(MaxNnzRow, HYPRE_Int, warn_ignored("fsai_max_nnz_row", v))
+FSAI_SET(KapTolerance, HYPRE_Real, warn_ignored("fsai_kap_tolerance", v))
+#undef FSAI_SET
 
 // ------------------------------------------------------------------ AMG internals used by the driver's level dump
 static thread_local std::vector<hypre_ParCSRMatrix *> g_level_ptrs;
@@ -1643,6 +1707,62 @@ HYPRE_Int HYPRE_MI_BoomerAMGRelaxLevel(HYPRE_Solver solver, HYPRE_Int level, HYP
   }
   a->amg.relax(level, relax_type, points, f.p);
   MI_HIP(hipStreamSynchronize(ctx().stream));
+  if (n) d2h(u_host, Lv.u.p, (size_t)n * sizeof(double), nullptr);
+  API_END
+}
+static FsaiSolver *level_fsai_or_null(HYPRE_Solver solver, int level) {
+  AmgSolver *a = AMG(solver);
+  if (!a->amg.is_setup) fail(HYPRE_ERROR_GENERIC, "GetLevelFSAI: AMG is not set up");
+  return level_fsai(level_ref(a, level));
+}
+HYPRE_Int HYPRE_MI_BoomerAMGGetLevelFSAISize(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int *nrows, HYPRE_BigInt *nnz) {
+  API_BEGIN
+  FsaiSolver *fs = level_fsai_or_null(solver, level);
+  *nrows = fs ? fs->G.nrows : 0;
+  *nnz = fs ? (HYPRE_BigInt)fs->G.nnz : 0;
+  API_END
+}
+HYPRE_Int HYPRE_MI_BoomerAMGGetLevelFSAI(HYPRE_Solver solver, HYPRE_Int level, HYPRE_BigInt *ia, HYPRE_Int *ja,
+                                         HYPRE_Complex *a, HYPRE_Real *omega) {
+  API_BEGIN
+  FsaiSolver *fs = level_fsai_or_null(solver, level);
+  if (!fs) fail(HYPRE_ERROR_ARG, "GetLevelFSAI: the level has no FSAI smoother");
+  const HostCSR &g = fs->host_G();
+  if (ia)
+    for (int i = 0; i <= g.nrows; i++) ia[i] = g.ia.empty() ? 0 : g.ia[(size_t)i];
+  if (ja && !g.ja.empty()) memcpy(ja, g.ja.data(), g.ja.size() * sizeof(int));
+  if (a && !g.a.empty()) memcpy(a, g.a.data(), g.a.size() * sizeof(double));
+  if (omega) *omega = fs->omega;
+  API_END
+}
+HYPRE_Int HYPRE_MI_BoomerAMGSmoothLevel(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int zero_guess,
+                                        const HYPRE_Real *f_host, HYPRE_Real *u_host) {
+  API_BEGIN
+  AmgSolver *a = AMG(solver);
+  if (!a->amg.is_setup) fail(HYPRE_ERROR_GENERIC, "SmoothLevel: AMG is not set up");
+  BoomerAMG *o = nullptr;
+  int loc = 0;
+  AmgLevel &Lv = level_ref(a, level, &o, &loc);
+  if (!Lv.smoother) fail(HYPRE_ERROR_ARG, "SmoothLevel: the level has no complex smoother");
+  const int n = Lv.n;
+  DVec<double> f((size_t)n);
+  hipStream_t s = ctx().stream;
+  if (n) {
+    f.upload(f_host, (size_t)n);
+    MI_HIP(hipStreamSynchronize(s));
+    MI_HIP(hipMemcpy(Lv.u.p, u_host, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+  }
+  // one sweep: num_sweeps[0] = 1 for the call
+  const int keep = o->p.num_sweeps[0];
+  o->p.num_sweeps[0] = 1;
+  try {
+    o->relax_sweeps(loc, 0, f.p, zero_guess != 0);
+  } catch (...) {
+    o->p.num_sweeps[0] = keep;
+    throw;
+  }
+  o->p.num_sweeps[0] = keep;
+  MI_HIP(hipStreamSynchronize(s));
   if (n) d2h(u_host, Lv.u.p, (size_t)n * sizeof(double), nullptr);
   API_END
 }

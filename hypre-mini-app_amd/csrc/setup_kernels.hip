@@ -556,6 +556,17 @@ constexpr int C_PT = 1, F_PT = -1, SF_PT = -3;
 __device__ __forceinline__ unsigned long long mulmod31(unsigned long long x, unsigned long long y) {
   return (x * y) % 2147483647ULL;  // both < 2^31: the product fits 64 bits
 }
+// element `index` (0-based) of the Park-Miller stream seeded with seed0: seed0 * 16807^(index+1) mod (2^31 - 1) -- the ONE
+// global stream of the PMIS measures (and of the FSAI power iteration's start vector)
+__device__ __forceinline__ int park_miller_element(int seed0, long long index) {
+  unsigned long long base = 16807ULL, acc = (unsigned long long)seed0, e = (unsigned long long)index + 1ULL;
+  while (e) {
+    if (e & 1ULL) acc = mulmod31(acc, base);
+    base = mulmod31(base, base);
+    e >>= 1;
+  }
+  return (int)acc;
+}
 
 __global__ __launch_bounds__(BLK) void pmis_init_k(int n, const long long *__restrict__ sia,
                                                    const int *__restrict__ incoming, int seed0,
@@ -564,13 +575,7 @@ __global__ __launch_bounds__(BLK) void pmis_init_k(int n, const long long *__res
   const long long i = bid() * BLK + threadIdx.x;
   if (i >= n) return;
   // element i of the Park-Miller stream: seed0 * 16807^(i+1) mod (2^31 - 1)
-  unsigned long long base = 16807ULL, acc = (unsigned long long)seed0, e = (unsigned long long)i + 1ULL;
-  while (e) {
-    if (e & 1ULL) acc = mulmod31(acc, base);
-    base = mulmod31(base, base);
-    e >>= 1;
-  }
-  const double m = (double)incoming[i] + (double)(int)acc / 2147483647;
+  const double m = (double)incoming[i] + (double)park_miller_element(seed0, i) / 2147483647;
   int c = 0;
   if (sia[i + 1] == sia[i])
     c = SF_PT;
@@ -2763,13 +2768,7 @@ __global__ __launch_bounds__(BLK) void pmisd_init_k(int n, int row0, long long g
   if (i >= n) return;
   const long long x = row0 + i;
   // element gid0 + i of the ONE global Park-Miller stream (see pmis_init_k)
-  unsigned long long base = 16807ULL, acc = (unsigned long long)seed0, e = (unsigned long long)(gid0 + i) + 1ULL;
-  while (e) {
-    if (e & 1ULL) acc = mulmod31(acc, base);
-    base = mulmod31(base, base);
-    e >>= 1;
-  }
-  const double m = (double)incoming[x] + (double)(int)acc / 2147483647;
+  const double m = (double)incoming[x] + (double)park_miller_element(seed0, gid0 + i) / 2147483647;
   int c = 0;
   if (sia[x + 1] == sia[x])
     c = SF_PT;
@@ -3095,6 +3094,243 @@ void mark_used_columns(const DCsr &A, DVec<unsigned char> &used, hipStream_t s) 
 }
 void add_to_ints(int *v, int n, int add, hipStream_t s) {
   if (n && add) add_const_k<<<grid_for(((long long)n + BLK - 1) / BLK), BLK, 0, s>>>(n, v, add);
+  MI_HIP(hipGetLastError());
+}
+
+
+// ---------------------------------------------------------------- FSAI with a static pattern (fsai.cpp)
+namespace {
+// filter = 1: row i keeps (i,i) -- inserted when B does not store it -- and every (i,j) with |b_ij| >= theta * max_{l != i}
+// |b_il|; filter = 0: every entry.  lower = 1: only j <= i.  Values 1.0 (a pattern whose products cannot cancel).
+// Count pass (oia == null: cnt[i]) and fill pass (oia: the scanned offsets).
+__global__ __launch_bounds__(BLK) void fsai_select_k(int n, const long long *__restrict__ ia, const int *__restrict__ ja,
+                                                     const double *__restrict__ a, double theta, int filter, int lower,
+                                                     const long long *__restrict__ oia, int *__restrict__ cnt,
+                                                     int *__restrict__ oja, double *__restrict__ oa) {
+  const long long i = bid() * BLK + threadIdx.x;
+  if (i >= n) return;
+  double mx = 0.0;
+  if (filter)
+    for (long long k = ia[i]; k < ia[i + 1]; k++)
+      if (ja[k] != (int)i) mx = fmax(mx, fabs(a[k]));
+  const double thr = theta * mx;
+  const long long o = oia ? oia[i] : 0;
+  int c = 0;
+  bool has_d = false;
+  for (long long k = ia[i]; k < ia[i + 1]; k++) {
+    const int j = ja[k];
+    if (filter && !has_d && j > (int)i) {
+      if (oia) oja[o + c] = (int)i, oa[o + c] = 1.0;
+      c++;
+      has_d = true;
+    }
+    if (lower && j > (int)i) break;
+    if (j == (int)i) has_d = true;
+    if (j == (int)i || !filter || fabs(a[k]) >= thr) {
+      if (oia) oja[o + c] = j, oa[o + c] = 1.0;
+      c++;
+    }
+  }
+  if (filter && !has_d) {
+    if (oia) oja[o + c] = (int)i, oa[o + c] = 1.0;
+    c++;
+  }
+  if (!oia) cnt[i] = c;
+}
+
+// largest row length, and the rows of every group-size class (<= 16, <= 32, <= 64 entries) in three lists; per wave one
+// atomic per class (ballot + rank inside the wave) and one for the maximum.  The lists' order is immaterial: every row
+// of G is computed on its own.
+__global__ __launch_bounds__(BLK) void fsai_classify_k(int n, const long long *__restrict__ ia, int *__restrict__ lists,
+                                                       int *__restrict__ counters) {
+  const long long i = bid() * BLK + threadIdx.x;
+  const int lane = (int)(threadIdx.x & 63);
+  const int m = (i < n) ? (int)(ia[i + 1] - ia[i]) : 0;
+  int mx = m;
+  for (int off = 32; off > 0; off >>= 1) mx = max(mx, __shfl_xor(mx, off, 64));
+  if (lane == 0 && mx > 0) atomicMax(&counters[3], mx);
+  const int c = (i >= n || m > 64) ? -1 : (m <= 16 ? 0 : (m <= 32 ? 1 : 2));
+  const unsigned long long below = (1ULL << lane) - 1ULL;
+  for (int q = 0; q < 3; q++) {
+    const unsigned long long mask = __ballot(c == q);
+    if (!mask) continue;
+    int base = 0;
+    const int leader = __ffsll((long long)mask) - 1;
+    if (lane == leader) base = atomicAdd(&counters[q], __popcll(mask));
+    base = __shfl(base, leader, 64);
+    if (c == q) lists[(long long)q * n + base + __popcll(mask & below)] = (int)i;
+  }
+}
+
+// One row of G per group of GS lanes (GS = 16, 32 or 64; 64 / GS rows per one-wave workgroup).  With P = P_i (m entries,
+// ascending, i last) and M = B[P, P], lane t holds row t of M^T in LDS (entry c = b(P_c, P_t), found by a binary search in
+// B's sorted row P_c) and the right-hand side e_last in column GS.  Gaussian elimination with partial pivoting: the pivot
+// of step k is the unused row with the largest |value| in column k, the lowest row on a tie; rows are not moved (pivot
+// order in piv).  Back substitution by columns, descending.  g = y / sqrt(y_last) goes to G's values on P's pattern.
+// status[i]: 0 ok, 1 singular (zero pivot), 2 y_last <= 0.  No atomics: every value is computed by one lane in a fixed
+// order, so G is bit-identical from run to run.
+template <int GS>
+__global__ __launch_bounds__(64) void fsai_local_solve_k(const int *__restrict__ rows, int nlist,
+                                                         const long long *__restrict__ Bia, const int *__restrict__ Bja,
+                                                         const double *__restrict__ Ba, const long long *__restrict__ Pia,
+                                                         const int *__restrict__ Pja, double *__restrict__ Ga,
+                                                         unsigned char *__restrict__ status) {
+  constexpr int RPB = 64 / GS, LD = GS + 1;
+  __shared__ double M[RPB][GS][LD];
+  __shared__ double y[RPB][GS];
+  __shared__ int piv[RPB][GS];
+  const int g = threadIdx.x / GS, t = threadIdx.x % GS;
+  const long long q = bid() * RPB + g;
+  int i = 0, m = 0;
+  long long p0 = 0;
+  if (q < nlist) {
+    i = rows[q];
+    p0 = Pia[i];
+    m = (int)(Pia[i + 1] - p0);
+  }
+  double *Mt = &M[g][t][0];
+  if (t < m) {
+    const int col = Pja[p0 + t];
+    for (int c = 0; c < m; c++) {
+      const int r = Pja[p0 + c];
+      long long lo = Bia[r];
+      const long long end = Bia[r + 1];
+      long long hi = end;
+      while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (Bja[mid] < col)
+          lo = mid + 1;
+        else
+          hi = mid;
+      }
+      Mt[c] = (lo < end && Bja[lo] == col) ? Ba[lo] : 0.0;
+    }
+    Mt[GS] = (t == m - 1) ? 1.0 : 0.0;
+  }
+  // trip counts: the largest m of the workgroup (one wave), so that every group reaches every barrier
+  int mb = m;
+  for (int off = 32; off > 0; off >>= 1) mb = max(mb, __shfl_xor(mb, off, 64));
+  __syncthreads();
+  bool used = false, singular = false;
+  int step = GS;  // the elimination step this lane's row was the pivot of
+  for (int k = 0; k < mb; k++) {
+    double v = (t < m && !used && k < m) ? fabs(Mt[k]) : -1.0;
+    int idx = t;
+    for (int off = GS / 2; off > 0; off >>= 1) {
+      const double ov = __shfl_xor(v, off, GS);
+      const int oi = __shfl_xor(idx, off, GS);
+      if (ov > v || (ov == v && oi < idx)) v = ov, idx = oi;
+    }
+    if (k < m && !singular) {
+      if (!(v > 0.0)) singular = true;
+      if (t == 0) piv[g][k] = idx;
+      if (t == idx) used = true, step = k;
+      if (!singular && t < m && !used) {
+        const double *Mp = &M[g][idx][0];
+        const double l = Mt[k] / Mp[k];
+        for (int c = k + 1; c < m; c++) Mt[c] = Mt[c] - l * Mp[c];
+        Mt[GS] = Mt[GS] - l * Mp[GS];
+      }
+    }
+    __syncthreads();
+  }
+  for (int c = mb - 1; c >= 0; c--) {
+    if (c < m && !singular && t == piv[g][c]) y[g][c] = Mt[GS] / Mt[c];
+    __syncthreads();
+    if (c < m && !singular && t < m && step < c) Mt[GS] = Mt[GS] - Mt[c] * y[g][c];
+  }
+  __syncthreads();
+  if (q >= nlist) return;
+  const double ylast = singular ? 0.0 : y[g][m - 1];
+  const bool ok = !singular && ylast > 0.0;
+  if (t < m) Ga[p0 + t] = ok ? y[g][t] / sqrt(ylast) : 0.0;
+  if (t == 0) status[i] = singular ? 1 : (ok ? 0 : 2);
+}
+
+__global__ __launch_bounds__(BLK) void fsai_first_bad_k(int n, const unsigned char *__restrict__ status, int *__restrict__ out) {
+  const long long i = bid() * BLK + threadIdx.x;
+  if (i < n && status[i]) atomicMin(out, (int)i);
+}
+
+__global__ __launch_bounds__(BLK) void fsai_random_k(int n, long long gid0, int seed0, double *__restrict__ v) {
+  const long long i = bid() * BLK + threadIdx.x;
+  if (i >= n) return;
+  v[i] = (double)park_miller_element(seed0, gid0 + i) / 2147483647;
+}
+}  // namespace
+
+void fsai_select(const DCsr &B, double theta, bool filter, bool lower, DCsr &S, hipStream_t s) {
+  const int n = B.nrows;
+  S.release();
+  S.nrows = n;
+  S.ncols = B.ncols;
+  S.ia.alloc((size_t)n + 1);
+  DVec<int> cnt((size_t)n);
+  const dim3 gr = grid_for(((long long)n + BLK - 1) / BLK);
+  if (n) fsai_select_k<<<gr, BLK, 0, s>>>(n, B.ia.p, B.ja.p, B.a.p, theta, filter, lower, nullptr, cnt.p, nullptr, nullptr);
+  exclusive_scan(cnt.p, S.ia.p, n, s);
+  long long nnz = 0;
+  d2h(&nnz, S.ia.p + n, sizeof(long long), s);
+  S.nnz = nnz;
+  S.ja.alloc((size_t)nnz);
+  S.a.alloc((size_t)nnz);
+  if (n) fsai_select_k<<<gr, BLK, 0, s>>>(n, B.ia.p, B.ja.p, B.a.p, theta, filter, lower, S.ia.p, nullptr, S.ja.p, S.a.p);
+  MI_HIP(hipGetLastError());
+}
+
+int fsai_local_solve(const DCsr &B, const DCsr &P, DCsr &G, int &max_row, int &bad_row, int &bad_kind, hipStream_t s) {
+  const int n = P.nrows;
+  bad_row = -1;
+  bad_kind = 0;
+  max_row = 0;
+  if (n == 0) {  // a rank without rows: an empty G with its one row pointer
+    G.release();
+    G.nrows = 0;
+    G.ncols = P.ncols;
+    G.ia.alloc(1);
+    MI_HIP(hipMemsetAsync(G.ia.p, 0, sizeof(long long), s));
+    G.ja.alloc(0);
+    G.a.alloc(0);
+    return 0;
+  }
+  const dim3 gr = grid_for(((long long)n + BLK - 1) / BLK);
+  DVec<int> lists((size_t)3 * n), cnt(4);
+  MI_HIP(hipMemsetAsync(cnt.p, 0, 4 * sizeof(int), s));
+  fsai_classify_k<<<gr, BLK, 0, s>>>(n, P.ia.p, lists.p, cnt.p);
+  int hc[4];
+  d2h(hc, cnt.p, sizeof(hc), s);
+  max_row = hc[3];
+  if (max_row > 64) return 1;
+  G.release();
+  G.nrows = P.nrows;
+  G.ncols = P.ncols;
+  G.nnz = P.nnz;
+  G.ia.alloc((size_t)n + 1);
+  G.ja.alloc((size_t)P.nnz);
+  G.a.alloc((size_t)P.nnz);
+  MI_HIP(hipMemcpyAsync(G.ia.p, P.ia.p, ((size_t)n + 1) * sizeof(long long), hipMemcpyDeviceToDevice, s));
+  if (P.nnz) MI_HIP(hipMemcpyAsync(G.ja.p, P.ja.p, (size_t)P.nnz * sizeof(int), hipMemcpyDeviceToDevice, s));
+  DVec<unsigned char> status((size_t)n);
+  if (hc[0]) fsai_local_solve_k<16><<<grid_for((hc[0] + 3) / 4), 64, 0, s>>>(lists.p, hc[0], B.ia.p, B.ja.p, B.a.p, P.ia.p, P.ja.p, G.a.p, status.p);
+  if (hc[1]) fsai_local_solve_k<32><<<grid_for((hc[1] + 1) / 2), 64, 0, s>>>(lists.p + n, hc[1], B.ia.p, B.ja.p, B.a.p, P.ia.p, P.ja.p, G.a.p, status.p);
+  if (hc[2]) fsai_local_solve_k<64><<<grid_for(hc[2]), 64, 0, s>>>(lists.p + 2LL * n, hc[2], B.ia.p, B.ja.p, B.a.p, P.ia.p, P.ja.p, G.a.p, status.p);
+  MI_HIP(hipGetLastError());
+  MI_HIP(hipMemsetAsync(cnt.p, 0x7f, sizeof(int), s));  // 0x7f7f7f7f: above every row
+  fsai_first_bad_k<<<gr, BLK, 0, s>>>(n, status.p, cnt.p);
+  int first = n;
+  d2h(&first, cnt.p, sizeof(int), s);
+  if (first < n) {
+    unsigned char k = 0;
+    d2h(&k, status.p + first, 1, s);
+    bad_row = first;
+    bad_kind = k;
+    return 2;
+  }
+  return 0;
+}
+
+void fsai_random_vector(int n, long long gid0, int seed, double *v, hipStream_t s) {
+  if (n) fsai_random_k<<<grid_for(((long long)n + BLK - 1) / BLK), BLK, 0, s>>>(n, gid0, seed, v);
   MI_HIP(hipGetLastError());
 }
 

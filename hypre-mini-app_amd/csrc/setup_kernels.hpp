@@ -132,6 +132,18 @@ void ilu_upper_level(const DCsr &LU, const long long *dpos, const int *rows, int
 void ilu_lower_jacobi(const DCsr &LU, const long long *dpos, const double *b, const double *in, double *out, hipStream_t s);
 void ilu_upper_jacobi(const DCsr &LU, const long long *dpos, const double *b, const double *in, double *out, hipStream_t s);
 
+// ---- FSAI with a static pattern (fsai.cpp), on a rank's diagonal block B (columns ascending in every row)
+// S = B's pattern, values 1.0: filter -- (i,i) (inserted when B does not store it) and every (i,j) with
+// |b_ij| >= theta * max_{l != i} |b_il|; no filter -- every entry; lower -- only the entries j <= i
+void fsai_select(const DCsr &B, double theta, bool filter, bool lower, DCsr &S, hipStream_t s);
+// G on the pattern P (rows ascending, the diagonal last): g_i = y / sqrt(y_last) with B[P_i, P_i]^T y = e_last by
+// Gaussian elimination with partial pivoting, one row per 16 / 32 / 64 lanes by |P_i|.  max_row = largest |P_i|.
+// Returns 0; 1 when max_row > 64 (G is not built); 2 when a row fails (bad_row = the first, bad_kind 1 singular,
+// 2 y_last <= 0)
+int fsai_local_solve(const DCsr &B, const DCsr &P, DCsr &G, int &max_row, int &bad_row, int &bad_kind, hipStream_t s);
+// v[i] = element gid0 + i of the global Park-Miller stream seeded with `seed` (the PMIS measures' stream) / (2^31 - 1)
+void fsai_random_vector(int n, long long gid0, int seed, double *v, hipStream_t s);
+
 // ---- distributed setup on the device (amg_setup_dist.cpp: BoomerAMG::build_distributed_device)
 // Column map between two extended index spaces [remote below | own range | remote above] (ascending global ids):
 // column c of the source becomes below[c] (c < nb_old), own_tab[c - nb_old] or own_new0 + (c - nb_old) (own range,

@@ -5,7 +5,7 @@
 namespace mi {
 
 struct SolverBase {
-  enum Kind { K_GMRES, K_BICGSTAB, K_PCG, K_AMG, K_ILU } kind;
+  enum Kind { K_GMRES, K_BICGSTAB, K_PCG, K_AMG, K_ILU, K_FSAI } kind;
   explicit SolverBase(Kind k) : kind(k) {}
   virtual ~SolverBase() {}
 };
@@ -99,5 +99,38 @@ struct IluSolver : SolverBase {
   void apply(const double *rhs, double *out);           // out = U^-1 L^-1 rhs
   int solve(ParCSR &A, ParVector &b, ParVector &x);     // x += M^-1 (b - A x), max_iter times or to tol
 };
+
+// HYPRE_FSAI with the static pattern (algo type 3): G lower triangular on the lower triangle of
+// the k-th power (k = num_levels) of the threshold-filtered graph of this rank's diagonal block, one dense local solve
+// per row; one step is x += omega G^T G (b - A x).  Also the complex smoother smooth_type 4 of BoomerAMG.
+struct FsaiSolver : SolverBase {
+  int algo_type = 3, num_levels = 1, eig_max_iters = 5, max_iter = 20, print_level = 0;
+  double threshold = 0.01, tol = 1e-6;
+  double omega_user = 0.0;  // > 0: HYPRE_FSAISetOmega, no eigenvalue estimate
+  bool zero_guess = false;
+  bool is_setup = false;
+  int n = 0, max_row = 0;
+  double omega = 1.0;
+  DevCSR G, Gt;
+  DVec<double> t, r;
+  HostCSR hG;  // host copy of G for the inspection API (on first use)
+  bool host_G_ok = false;
+  int num_iterations = 0;
+  double final_rel_res = 0.0;
+  FsaiSolver() : SolverBase(K_FSAI) {}
+  void setup(ParCSR &A, Comm &comm, const std::string &where);
+  // u += omega G^T G res (zero: u = omega G^T G res): two launches, the update fused into the G^T product
+  void apply_add(const double *res, double *u, bool zero, int prof = -1);
+  int solve(ParCSR &A, ParVector &b, ParVector &x);  // x += omega G^T G (b - A x), max_iter times or to tol
+  const HostCSR &host_G();
+};
+
+// the complex smoother of a level, by kind (null when the level has none or one of the other kind)
+inline IluSolver *level_ilu(const AmgLevel &Lv) {
+  return (Lv.smoother && Lv.smoother->kind == SolverBase::K_ILU) ? static_cast<IluSolver *>(Lv.smoother.get()) : nullptr;
+}
+inline FsaiSolver *level_fsai(const AmgLevel &Lv) {
+  return (Lv.smoother && Lv.smoother->kind == SolverBase::K_FSAI) ? static_cast<FsaiSolver *>(Lv.smoother.get()) : nullptr;
+}
 
 }  // namespace mi

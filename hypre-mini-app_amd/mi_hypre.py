@@ -277,6 +277,15 @@ class BoomerAMG:
                               ("ilu_tri_solve", "HYPRE_BoomerAMGSetILUTriSolve", int),
                               ("ilu_lower_jacobi_iters", "HYPRE_BoomerAMGSetILULowerJacobiIters", int),
                               ("ilu_upper_jacobi_iters", "HYPRE_BoomerAMGSetILUUpperJacobiIters", int),
+                              ("fsai_algo_type", "HYPRE_BoomerAMGSetFSAIAlgoType", int),
+                              ("fsai_local_solve_type", "HYPRE_BoomerAMGSetFSAILocalSolveType", int),
+                              ("fsai_num_levels", "HYPRE_BoomerAMGSetFSAINumLevels", int),
+                              ("fsai_threshold", "HYPRE_BoomerAMGSetFSAIThreshold", float),
+                              ("fsai_eig_max_iters", "HYPRE_BoomerAMGSetFSAIEigMaxIters", int),
+                              ("fsai_max_steps", "HYPRE_BoomerAMGSetFSAIMaxSteps", int),
+                              ("fsai_max_step_size", "HYPRE_BoomerAMGSetFSAIMaxStepSize", int),
+                              ("fsai_max_nnz_row", "HYPRE_BoomerAMGSetFSAIMaxNnzRow", int),
+                              ("fsai_kap_tolerance", "HYPRE_BoomerAMGSetFSAIKapTolerance", float),
                               ("true_pmax_elmts", "HYPRE_BoomerAMGSetPMaxElmts", int)):
             if key in cfg:
                 call(fn, s, conv(cfg[key]))
@@ -368,6 +377,38 @@ class BoomerAMG:
         call("HYPRE_MI_BoomerAMGRelaxLevel", self.h, level, relax_type, points, f, u)
         return u
 
+    def set_fsai(self, **kw):
+        """Change FSAI smoother parameters (fsai_* keys of the constructor), also after setup."""
+        names = {"fsai_algo_type": ("HYPRE_BoomerAMGSetFSAIAlgoType", int),
+                 "fsai_num_levels": ("HYPRE_BoomerAMGSetFSAINumLevels", int),
+                 "fsai_threshold": ("HYPRE_BoomerAMGSetFSAIThreshold", float),
+                 "fsai_eig_max_iters": ("HYPRE_BoomerAMGSetFSAIEigMaxIters", int)}
+        for k, v in kw.items():
+            fn, conv = names[k]
+            call(fn, self.h, conv(v))
+            self.cfg[k] = v
+
+    def level_fsai(self, level):
+        """(ia int64, ja int32, a f64, omega) of the level's FSAI factor G (GetLevelCSR numbering); None without one."""
+        nr, nnz = c_int(), c_big()
+        call("HYPRE_MI_BoomerAMGGetLevelFSAISize", self.h, level, C.byref(nr), C.byref(nnz))
+        if nr.value == 0 and nnz.value == 0:
+            return None
+        ia = np.zeros(nr.value + 1, dtype=np.int64)
+        ja = np.zeros(max(nnz.value, 1), dtype=np.int32)
+        a = np.zeros(max(nnz.value, 1), dtype=np.float64)
+        om = c_dbl()
+        call("HYPRE_MI_BoomerAMGGetLevelFSAI", self.h, level, ia, ja, a, C.byref(om))
+        return ia, ja[: nnz.value], a[: nnz.value], om.value
+
+    def smooth_level(self, level, f, u=None):
+        """One complex-smoother step of the level on host arrays; u None = zero guess."""
+        f = dbl(f)
+        zero = u is None
+        u = np.zeros_like(f) if zero else np.array(u, dtype=np.float64)
+        call("HYPRE_MI_BoomerAMGSmoothLevel", self.h, level, 1 if zero else 0, f, u)
+        return u
+
     def destroy(self):
         if self.h:
             call("HYPRE_BoomerAMGDestroy", self.h)
@@ -418,6 +459,43 @@ class ILU:
     def destroy(self):
         if self.h:
             call("HYPRE_ILUDestroy", self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+class FSAI:
+    """HYPRE_FSAI, static pattern (algo type 3): x += omega G^T G (b - A x); a preconditioner (set_precond) or a solver."""
+
+    def __init__(self, max_iterations=1, tolerance=0.0, zero_guess=1, algo_type=3, num_levels=1, threshold=0.01,
+                 eig_max_iters=5, omega=None, print_level=0):
+        self.h = vp()
+        call("HYPRE_FSAICreate", C.byref(self.h))
+        call("HYPRE_FSAISetAlgoType", self.h, int(algo_type))
+        call("HYPRE_FSAISetNumLevels", self.h, int(num_levels))
+        call("HYPRE_FSAISetThreshold", self.h, float(threshold))
+        call("HYPRE_FSAISetEigMaxIters", self.h, int(eig_max_iters))
+        if omega is not None:
+            call("HYPRE_FSAISetOmega", self.h, float(omega))
+        call("HYPRE_FSAISetMaxIterations", self.h, int(max_iterations))
+        call("HYPRE_FSAISetTolerance", self.h, float(tolerance))
+        call("HYPRE_FSAISetZeroGuess", self.h, int(zero_guess))
+        call("HYPRE_FSAISetPrintLevel", self.h, int(print_level))
+        self.solve_fn, self.setup_fn = "HYPRE_FSAISolve", "HYPRE_FSAISetup"
+
+    def setup(self, A):
+        call("HYPRE_FSAISetup", self.h, A.par, None, None)
+
+    def solve(self, A, b, x):
+        return call("HYPRE_FSAISolve", self.h, A.par, b.par, x.par)
+
+    def destroy(self):
+        if self.h:
+            call("HYPRE_FSAIDestroy", self.h)
             self.h = None
 
     def __del__(self):

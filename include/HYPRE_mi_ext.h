@@ -157,6 +157,15 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetLevelOffdColMap(HYPRE_Solver solver, HYPRE_Int le
 /* one relaxation call / one cycle on HOST arrays of the level's local length */
 HYPRE_Int HYPRE_MI_BoomerAMGRelaxLevel(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int relax_type, HYPRE_Int points,
                                        const HYPRE_Real *f_host, HYPRE_Real *u_host);
+/* FSAI smoother of a level (smooth_type 4, levels < smooth_num_levels): its G as CSR in GetLevelCSR's numbering (the
+ * rows and columns of the level's diag block), and omega.  Size: 0 x 0 and nnz 0 when the level has none */
+HYPRE_Int HYPRE_MI_BoomerAMGGetLevelFSAISize(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int *nrows, HYPRE_BigInt *nnz);
+HYPRE_Int HYPRE_MI_BoomerAMGGetLevelFSAI(HYPRE_Solver solver, HYPRE_Int level, HYPRE_BigInt *ia, HYPRE_Int *ja,
+                                         HYPRE_Complex *a, HYPRE_Real *omega);
+/* one complex-smoother step of a level on HOST arrays (the counterpart of RelaxLevel): u <- u + M (f - A u) with the
+ * level's smoother M; zero_guess != 0 takes u = 0 on entry (the mat-vec is skipped, as on a cycle's down leg) */
+HYPRE_Int HYPRE_MI_BoomerAMGSmoothLevel(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int zero_guess,
+                                        const HYPRE_Real *f_host, HYPRE_Real *u_host);
 
 /* ---- HIP-event timing of kernel classes on the library stream.
  * id: 0 level-0 SpMV of the Krylov loop, 1 level-0 relaxation, 2 dot, 3 axpy; per AMG level l < 16:

@@ -71,6 +71,18 @@ HYPRE_Int HYPRE_BoomerAMGSetILUIterSetupTolerance(HYPRE_Solver solver, HYPRE_Rea
 HYPRE_Int HYPRE_BoomerAMGSetILUTriSolve(HYPRE_Solver solver, HYPRE_Int v);              /* :311 */
 HYPRE_Int HYPRE_BoomerAMGSetILULowerJacobiIters(HYPRE_Solver solver, HYPRE_Int v);      /* :316 */
 HYPRE_Int HYPRE_BoomerAMGSetILUUpperJacobiIters(HYPRE_Solver solver, HYPRE_Int v);      /* :320 */
+/* FSAI smoother (smooth_type 4; names as remembered from HYPRE >= 2.25): only the static pattern, algo type 3, is built
+ * -- any other algo type is refused at Setup.  The adaptive-only settings are accepted and warned once (no effect on a
+ * static pattern); the local solve type is accepted and has no effect */
+HYPRE_Int HYPRE_BoomerAMGSetFSAIAlgoType(HYPRE_Solver solver, HYPRE_Int v);
+HYPRE_Int HYPRE_BoomerAMGSetFSAILocalSolveType(HYPRE_Solver solver, HYPRE_Int v);
+HYPRE_Int HYPRE_BoomerAMGSetFSAINumLevels(HYPRE_Solver solver, HYPRE_Int v);           /* 1, 2 or 3 */
+HYPRE_Int HYPRE_BoomerAMGSetFSAIThreshold(HYPRE_Solver solver, HYPRE_Real v);
+HYPRE_Int HYPRE_BoomerAMGSetFSAIEigMaxIters(HYPRE_Solver solver, HYPRE_Int v);
+HYPRE_Int HYPRE_BoomerAMGSetFSAIMaxSteps(HYPRE_Solver solver, HYPRE_Int v);            /* adaptive only */
+HYPRE_Int HYPRE_BoomerAMGSetFSAIMaxStepSize(HYPRE_Solver solver, HYPRE_Int v);         /* adaptive only */
+HYPRE_Int HYPRE_BoomerAMGSetFSAIMaxNnzRow(HYPRE_Solver solver, HYPRE_Int v);           /* adaptive only */
+HYPRE_Int HYPRE_BoomerAMGSetFSAIKapTolerance(HYPRE_Solver solver, HYPRE_Real v);       /* adaptive only */
 
 /* ---------------------------------------------------------------- ParCSR GMRES
  * src/HypreSystem.cpp:390-404; right-preconditioned restarted GMRES(k), MGS */
@@ -172,6 +184,29 @@ HYPRE_Int HYPRE_ILUSetIterativeSetupTolerance(HYPRE_Solver solver, HYPRE_Real v)
 HYPRE_Int HYPRE_ILUSetTriSolve(HYPRE_Solver solver, HYPRE_Int v);                       /* also called on an AMG handle, :306 */
 HYPRE_Int HYPRE_ILUSetLowerJacobiIters(HYPRE_Solver solver, HYPRE_Int v);
 HYPRE_Int HYPRE_ILUSetUpperJacobiIters(HYPRE_Solver solver, HYPRE_Int v);
+
+/* FSAI (factorized sparse approximate inverse; names as remembered from HYPRE >= 2.25): static pattern (algo type 3) on
+ * the rank's diagonal block, x += omega G^T G (b - A x) per iteration; omega = 1 / (power-iteration estimate of
+ * lambda_max(G A G^T)) unless SetOmega gives one.  Usable as a preconditioner through the Krylov SetPrecond calls
+ * (then: MaxIterations 1, Tolerance 0, ZeroGuess 1) */
+HYPRE_Int HYPRE_FSAICreate(HYPRE_Solver *solver);
+HYPRE_Int HYPRE_FSAIDestroy(HYPRE_Solver solver);
+HYPRE_Int HYPRE_FSAISetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_FSAISolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_FSAISetAlgoType(HYPRE_Solver solver, HYPRE_Int v);
+HYPRE_Int HYPRE_FSAISetLocalSolveType(HYPRE_Solver solver, HYPRE_Int v);
+HYPRE_Int HYPRE_FSAISetNumLevels(HYPRE_Solver solver, HYPRE_Int v);
+HYPRE_Int HYPRE_FSAISetThreshold(HYPRE_Solver solver, HYPRE_Real v);
+HYPRE_Int HYPRE_FSAISetEigMaxIters(HYPRE_Solver solver, HYPRE_Int v);
+HYPRE_Int HYPRE_FSAISetOmega(HYPRE_Solver solver, HYPRE_Real v);
+HYPRE_Int HYPRE_FSAISetMaxIterations(HYPRE_Solver solver, HYPRE_Int v);
+HYPRE_Int HYPRE_FSAISetTolerance(HYPRE_Solver solver, HYPRE_Real v);
+HYPRE_Int HYPRE_FSAISetZeroGuess(HYPRE_Solver solver, HYPRE_Int v);
+HYPRE_Int HYPRE_FSAISetPrintLevel(HYPRE_Solver solver, HYPRE_Int v);
+HYPRE_Int HYPRE_FSAISetMaxSteps(HYPRE_Solver solver, HYPRE_Int v);       /* adaptive only: accepted, no effect */
+HYPRE_Int HYPRE_FSAISetMaxStepSize(HYPRE_Solver solver, HYPRE_Int v);    /* adaptive only: accepted, no effect */
+HYPRE_Int HYPRE_FSAISetMaxNnzRow(HYPRE_Solver solver, HYPRE_Int v);      /* adaptive only: accepted, no effect */
+HYPRE_Int HYPRE_FSAISetKapTolerance(HYPRE_Solver solver, HYPRE_Real v);  /* adaptive only: accepted, no effect */
 
 #ifdef __cplusplus
 }
