@@ -34,6 +34,9 @@ struct AmgParams {
   // defaults as in HYPRE
   int smooth_type = 6, smooth_num_levels = 0;
   int ilu_type = 0, ilu_level = 0, ilu_max_iter = 1, ilu_tri_solve = 1, ilu_lower_it = 5, ilu_upper_it = 5;
+  // iterative ILU(0) setup of the ILU smoothers (IluSolver::iter_*; 0 = the exact factorisation)
+  int ilu_iter_type = 0, ilu_iter_option = 0, ilu_iter_max_iter = 100;
+  double ilu_iter_tol = 1e-3;
   // smooth_type 4 = FSAI with the static pattern (algo type 3, the only one built), one step per sweep
   int fsai_algo_type = 3, fsai_num_levels = 1, fsai_eig_max_iters = 5;
   double fsai_threshold = 0.01;
@@ -229,8 +232,8 @@ struct BoomerAMG {
   void relax_pair(int level, int type, int first, const double *f, bool u_is_zero = false);
   void relax_sweeps(int level, int which, const double *f, bool u_is_zero = false);
   void cycle(int level, bool u_is_zero = false);
-  // complex smoothers of the levels < p.smooth_num_levels (end of setup_device); fsai_signature: the FSAI
-  // parameters they were built with -- a change after Setup rebuilds them before the next cycle
+  // complex smoothers of the levels < p.smooth_num_levels (end of setup_device); fsai_signature: the FSAI and
+  // iterative-ILU parameters they were built with -- a change after Setup rebuilds them before the next cycle
   void build_smoothers();
   std::vector<double> fsai_signature;
   std::vector<double> current_fsai_signature() const;

@@ -1624,6 +1624,12 @@ void BoomerAMG::setup_host(ParCSR &A0) {
   if (p.smooth_num_levels > 0 && p.smooth_type == 5 && (p.ilu_type != 0 || p.ilu_level < 0))
     fail(4, "BoomerAMGSetup: ILU smoother type " + std::to_string(p.ilu_type) + " / level of fill " +
                 std::to_string(p.ilu_level) + " is not implemented (block-Jacobi ILU(k) = type 0, level k >= 0 is)");
+  if (p.smooth_num_levels > 0 && p.smooth_type == 5 && p.ilu_iter_type != 0 &&
+      (p.ilu_iter_type < 0 || p.ilu_iter_type > 4 || p.ilu_level != 0 || (p.ilu_iter_option & ~63) || p.ilu_iter_max_iter < 1))
+    fail(4, "BoomerAMGSetup: iterative ILU setup type " + std::to_string(p.ilu_iter_type) + " with level of fill " +
+                std::to_string(p.ilu_level) + ", option " + std::to_string(p.ilu_iter_option) + ", max iterations " +
+                std::to_string(p.ilu_iter_max_iter) +
+                " is not implemented (types 0 ... 4 with ILU(0), option bits 1 ... 32, max iterations >= 1 are)");
   if (device_min_rows >= 0) dev_arena_hint((size_t)13 * 12 * (size_t)(A0.diag_nnz() + A0.offd.nnz()));
   if (comm.size > 1) input_order.clear();
   if (comm.size > 1 && can_build_distributed()) {
@@ -2441,14 +2447,21 @@ void BoomerAMG::build_smoothers() {
     ilu->upper_it = p.ilu_upper_it;
     ilu->max_iter = p.ilu_max_iter;
     ilu->tol = 0.0;
+    ilu->iter_type = p.ilu_iter_type;
+    ilu->iter_option = p.ilu_iter_option;
+    ilu->iter_max_iter = p.ilu_iter_max_iter;
+    ilu->iter_tol = p.ilu_iter_tol;
     ilu->print_level = (p.print_level > 0 && comm.rank == 0) ? 1 : 0;
-    ilu->setup(*Lv.A);
+    ilu->setup(*Lv.A, comm);
     Lv.smoother = std::move(ilu);
   }
   fsai_signature = current_fsai_signature();
 }
 
 std::vector<double> BoomerAMG::current_fsai_signature() const {
+  if (p.smooth_type == 5 && p.smooth_num_levels > 0 && p.ilu_iter_type != 0)
+    return {(double)p.smooth_num_levels, (double)p.ilu_iter_type, (double)p.ilu_iter_option, (double)p.ilu_iter_max_iter,
+            p.ilu_iter_tol};
   if (p.smooth_type != 4 || p.smooth_num_levels <= 0) return {};
   return {(double)p.smooth_num_levels, (double)p.fsai_algo_type, (double)p.fsai_num_levels, p.fsai_threshold,
           (double)p.fsai_eig_max_iters};

@@ -357,12 +357,16 @@ bool BoomerAMG::zero_cycle_ignores_u(int level) {
 void BoomerAMG::cycle(int level, bool u_is_zero) {
   const int nlev = (int)L.size();
   if (level == 0 && fsai_signature != current_fsai_signature()) {
-    build_smoothers();  // an FSAI parameter changed after Setup: G and omega of another smoother
+    build_smoothers();  // an FSAI or iterative-ILU parameter changed after Setup: the smoothers are rebuilt
     if (tail) {         // the redundant tail rebuilds its own at its next cycle
       tail->p.fsai_algo_type = p.fsai_algo_type;
       tail->p.fsai_num_levels = p.fsai_num_levels;
       tail->p.fsai_threshold = p.fsai_threshold;
       tail->p.fsai_eig_max_iters = p.fsai_eig_max_iters;
+      tail->p.ilu_iter_type = p.ilu_iter_type;
+      tail->p.ilu_iter_option = p.ilu_iter_option;
+      tail->p.ilu_iter_max_iter = p.ilu_iter_max_iter;
+      tail->p.ilu_iter_tol = p.ilu_iter_tol;
     }
   }
   if (level == 0 && collapsed_level >= 0 && collapsed_signature != cycle_signature())

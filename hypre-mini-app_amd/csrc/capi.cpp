@@ -810,10 +810,10 @@ AMG_SET(ILULocalReordering, HYPRE_Int, if (v != 0) warn_ignored("ilu_reordering_
 AMG_SET(ILUMaxRowNnz, HYPRE_Int, warn_ignored("ilu_max_row_nnz", v))
 AMG_SET(ILUMaxIter, HYPRE_Int, if (v < 1) fail(HYPRE_ERROR_ARG, "ilu_max_iter < 1"); p.ilu_max_iter = v)
 AMG_SET(ILUDroptol, HYPRE_Real, if (v != 0.0) warn_ignored("ilu_droptol", v))
-AMG_SET(ILUIterSetupType, HYPRE_Int, if (v != 0) warn_ignored("iterative_ilu_algorithm_type", v))
-AMG_SET(ILUIterSetupOption, HYPRE_Int, (void)v)
-AMG_SET(ILUIterSetupMaxIter, HYPRE_Int, (void)v)
-AMG_SET(ILUIterSetupTolerance, HYPRE_Real, (void)v)
+AMG_SET(ILUIterSetupType, HYPRE_Int, p.ilu_iter_type = v)  /* 0 ... 4 with ILU(0); other combinations are refused at Setup */
+AMG_SET(ILUIterSetupOption, HYPRE_Int, p.ilu_iter_option = v)
+AMG_SET(ILUIterSetupMaxIter, HYPRE_Int, p.ilu_iter_max_iter = v)
+AMG_SET(ILUIterSetupTolerance, HYPRE_Real, p.ilu_iter_tol = v)
 AMG_SET(ILUTriSolve, HYPRE_Int, p.ilu_tri_solve = v)
 AMG_SET(ILULowerJacobiIters, HYPRE_Int, p.ilu_lower_it = v)
 AMG_SET(ILUUpperJacobiIters, HYPRE_Int, p.ilu_upper_it = v)
@@ -1045,7 +1045,7 @@ HYPRE_Int HYPRE_ILUDestroy(HYPRE_Solver solver) {
 HYPRE_Int HYPRE_ILUSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector, HYPRE_ParVector) {
   API_BEGIN
   if (!A) fail(HYPRE_ERROR_ARG, "ILUSetup: NULL matrix");
-  ILU(solver)->setup(*PM(A));
+  ILU(solver)->setup(*PM(A), current_comm());
   transport_gate(nullptr, "ILUSetup");
   API_END
 }
@@ -1079,10 +1079,10 @@ ILU_SET(PrintLevel, HYPRE_Int, o->print_level = v)
 ILU_SET(LevelOfFill, HYPRE_Int, o->level_of_fill = v)
 ILU_SET(MaxNnzPerRow, HYPRE_Int, (void)v)        /* ILUT only */
 ILU_SET(DropThreshold, HYPRE_Real, (void)v)      /* ILUT only */
-ILU_SET(IterativeSetupType, HYPRE_Int, if (v != 0) fail(HYPRE_ERROR_ARG, "ILU: iterative setup is not implemented"))
-ILU_SET(IterativeSetupOption, HYPRE_Int, (void)v)
-ILU_SET(IterativeSetupMaxIter, HYPRE_Int, (void)v)
-ILU_SET(IterativeSetupTolerance, HYPRE_Real, (void)v)
+ILU_SET(IterativeSetupType, HYPRE_Int, o->iter_type = v)  /* 0 ... 4 with ILU(0); other combinations are refused at Setup */
+ILU_SET(IterativeSetupOption, HYPRE_Int, o->iter_option = v)
+ILU_SET(IterativeSetupMaxIter, HYPRE_Int, o->iter_max_iter = v)
+ILU_SET(IterativeSetupTolerance, HYPRE_Real, o->iter_tol = v)
 ILU_SET(LowerJacobiIters, HYPRE_Int, o->lower_it = v)
 ILU_SET(UpperJacobiIters, HYPRE_Int, o->upper_it = v)
 #undef ILU_SET
@@ -1090,6 +1090,45 @@ ILU_SET(UpperJacobiIters, HYPRE_Int, o->upper_it = v)
 HYPRE_Int HYPRE_ILUSetTriSolve(HYPRE_Solver solver, HYPRE_Int v) {
   API_BEGIN
   if (S(solver)->kind == SolverBase::K_ILU) ILU(solver)->tri_solve = v ? 1 : 0;
+  API_END
+}
+HYPRE_Int HYPRE_MI_ILUGetIterativeSetupInfo(HYPRE_Solver solver, HYPRE_Int *sweeps, HYPRE_Real *correction,
+                                            HYPRE_Real *residual) {
+  API_BEGIN
+  IluSolver *o = ILU(solver);
+  if (sweeps) *sweeps = o->iter_sweeps;
+  if (correction) *correction = o->iter_correction;
+  if (residual) *residual = o->iter_residual;
+  API_END
+}
+HYPRE_Int HYPRE_MI_ILUGetIterativeSetupHistory(HYPRE_Solver solver, HYPRE_Int *ncorr, HYPRE_Real *corr, HYPRE_Int *nres,
+                                               HYPRE_Real *res) {
+  API_BEGIN
+  IluSolver *o = ILU(solver);
+  if (ncorr) *ncorr = (HYPRE_Int)o->iter_corr_hist.size();
+  if (nres) *nres = (HYPRE_Int)o->iter_res_hist.size();
+  if (corr && !o->iter_corr_hist.empty()) memcpy(corr, o->iter_corr_hist.data(), o->iter_corr_hist.size() * sizeof(double));
+  if (res && !o->iter_res_hist.empty()) memcpy(res, o->iter_res_hist.data(), o->iter_res_hist.size() * sizeof(double));
+  API_END
+}
+HYPRE_Int HYPRE_MI_ILUGetFactorsSize(HYPRE_Solver solver, HYPRE_Int *nrows, HYPRE_BigInt *nnz) {
+  API_BEGIN
+  IluSolver *o = ILU(solver);
+  if (!o->is_setup) fail(HYPRE_ERROR_GENERIC, "ILUGetFactors: the ILU is not set up");
+  *nrows = o->LU.nrows;
+  *nnz = (HYPRE_BigInt)o->LU.nnz;
+  API_END
+}
+HYPRE_Int HYPRE_MI_ILUGetFactors(HYPRE_Solver solver, HYPRE_BigInt *ia, HYPRE_Int *ja, HYPRE_Complex *a) {
+  API_BEGIN
+  IluSolver *o = ILU(solver);
+  if (!o->is_setup) fail(HYPRE_ERROR_GENERIC, "ILUGetFactors: the ILU is not set up");
+  HostCSR h;
+  o->LU.download(h, ctx().stream);
+  if (ia)
+    for (int i = 0; i <= h.nrows; i++) ia[i] = h.ia.empty() ? 0 : h.ia[(size_t)i];
+  if (ja && !h.ja.empty()) memcpy(ja, h.ja.data(), h.ja.size() * sizeof(int));
+  if (a && !h.a.empty()) memcpy(a, h.a.data(), h.a.size() * sizeof(double));
   API_END
 }
 

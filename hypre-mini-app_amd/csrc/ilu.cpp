@@ -2,9 +2,12 @@
 // `preconditioner: ilu` and `method: ilu` of the driver (src/HypreSystem.cpp:328-370, :457-497).
 // Every rank factorises its own diagonal block in place; rows are grouped into level sets (row i is one
 // level above the deepest row it depends on), which order both the factorisation and the substitutions:
-// one kernel launch per level set, every row of a set independent of the others.
+// one kernel launch per level set, every row of a set independent of the others.  For ILU(0) the factors can instead come
+// from fixed-point sweeps over all entries at once (the iterative setup, types 1-4; iterative_factor below).
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
+#include <cstring>
 
 #include "kernels.hpp"
 #include "solvers.hpp"
@@ -70,52 +73,77 @@ void ilu_symbolic(const HostCSR &B, int fill, HostCSR &F) {
 }
 }  // namespace
 
-void IluSolver::setup(ParCSR &A) {
+void IluSolver::setup(ParCSR &A, Comm &comm) {
   ensure_init();
   hipStream_t s = ctx().stream;
   if (ilu_type != 0 || level_of_fill < 0)
     fail(1, "HYPRE_ILU: this variant is not implemented -- only type 0 (block-Jacobi ILU(k)) is (got type " +
                 std::to_string(ilu_type) + ", fill " + std::to_string(level_of_fill) + ")");
+  if (iter_type != 0) {
+    if (iter_type < 0 || iter_type > 4)
+      fail(1, "HYPRE_ILU: iterative setup type " + std::to_string(iter_type) + " is not implemented (0 ... 4 are)");
+    if (level_of_fill != 0)
+      fail(1, "HYPRE_ILU: the iterative setup with level of fill " + std::to_string(level_of_fill) +
+                  " is not implemented (it exists for ILU(0) only)");
+    if (iter_option & ~63)
+      fail(1, "HYPRE_ILU: iterative setup option " + std::to_string(iter_option) +
+                  " is not implemented (bits 1, 2, 4, 8, 16, 32 are)");
+    if (iter_max_iter < 1) fail(1, "HYPRE_ILU: iterative setup max iterations must be >= 1");
+  }
   MI_REQUIRE(!A.host_diag_stale, "HYPRE_ILUSetup: the matrix has no host arrays");
+  is_setup = false;
   HostCSR filled;
   if (level_of_fill > 0) ilu_symbolic(A.diag, level_of_fill, filled);  // the factors live on the ILU(k) pattern
   const HostCSR &D = level_of_fill > 0 ? filled : A.diag;
   n = D.nrows;
+  // the Jacobi triangular solves of an iteratively built factor need no level set: no serial pass over the block
+  levels_built = iter_type == 0 || tri_solve != 0;
   // level sets of the lower and of the upper factor
-  std::vector<int> ll((size_t)n, 0), lu((size_t)n, 0);
   int nl = 0, nu = 0;
-  for (int i = 0; i < n; i++) {
-    int lv = 0;
-    for (int64_t k = D.ia[(size_t)i]; k < D.ia[(size_t)i + 1] && D.ja[(size_t)k] < i; k++)
-      lv = std::max(lv, ll[(size_t)D.ja[(size_t)k]] + 1);
-    ll[(size_t)i] = lv;
-    nl = std::max(nl, lv + 1);
+  if (levels_built) {
+    std::vector<int> ll((size_t)n, 0), lu((size_t)n, 0);
+    for (int i = 0; i < n; i++) {
+      int lv = 0;
+      for (int64_t k = D.ia[(size_t)i]; k < D.ia[(size_t)i + 1] && D.ja[(size_t)k] < i; k++)
+        lv = std::max(lv, ll[(size_t)D.ja[(size_t)k]] + 1);
+      ll[(size_t)i] = lv;
+      nl = std::max(nl, lv + 1);
+    }
+    for (int i = n - 1; i >= 0; i--) {
+      int lv = 0;
+      for (int64_t k = D.ia[(size_t)i + 1] - 1; k >= D.ia[(size_t)i] && D.ja[(size_t)k] > i; k--)
+        lv = std::max(lv, lu[(size_t)D.ja[(size_t)k]] + 1);
+      lu[(size_t)i] = lv;
+      nu = std::max(nu, lv + 1);
+    }
+    auto bucket = [&](const std::vector<int> &lev, int nlev, std::vector<int> &ptr, std::vector<int> &order) {
+      ptr.assign((size_t)nlev + 1, 0);
+      for (int i = 0; i < n; i++) ptr[(size_t)lev[(size_t)i] + 1]++;
+      for (int l = 0; l < nlev; l++) ptr[(size_t)l + 1] += ptr[(size_t)l];
+      order.resize((size_t)n);
+      std::vector<int> cur(ptr.begin(), ptr.end() - 1);
+      for (int i = 0; i < n; i++) order[(size_t)cur[(size_t)lev[(size_t)i]]++] = i;
+    };
+    std::vector<int> ol, ou;
+    bucket(ll, nl, lptr, ol);
+    bucket(lu, nu, uptr, ou);
+    order_l.upload(ol);
+    order_u.upload(ou);
+  } else {
+    lptr.clear();
+    uptr.clear();
+    order_l.release();
+    order_u.release();
   }
-  for (int i = n - 1; i >= 0; i--) {
-    int lv = 0;
-    for (int64_t k = D.ia[(size_t)i + 1] - 1; k >= D.ia[(size_t)i] && D.ja[(size_t)k] > i; k--)
-      lv = std::max(lv, lu[(size_t)D.ja[(size_t)k]] + 1);
-    lu[(size_t)i] = lv;
-    nu = std::max(nu, lv + 1);
-  }
-  auto bucket = [&](const std::vector<int> &lev, int nlev, std::vector<int> &ptr, std::vector<int> &order) {
-    ptr.assign((size_t)nlev + 1, 0);
-    for (int i = 0; i < n; i++) ptr[(size_t)lev[(size_t)i] + 1]++;
-    for (int l = 0; l < nlev; l++) ptr[(size_t)l + 1] += ptr[(size_t)l];
-    order.resize((size_t)n);
-    std::vector<int> cur(ptr.begin(), ptr.end() - 1);
-    for (int i = 0; i < n; i++) order[(size_t)cur[(size_t)lev[(size_t)i]]++] = i;
-  };
-  std::vector<int> ol, ou;
-  bucket(ll, nl, lptr, ol);
-  bucket(lu, nu, uptr, ou);
-  order_l.upload(ol);
-  order_u.upload(ou);
   LU.upload(D, s);
   dpos.alloc((size_t)n);
   sk::ilu_diag_positions(LU, dpos.p, s);
-  for (int l = 0; l < nl; l++)
-    sk::ilu_factor_level(LU, dpos.p, order_l.p + lptr[(size_t)l], lptr[(size_t)l + 1] - lptr[(size_t)l], s);
+  if (iter_type == 0) {
+    for (int l = 0; l < nl; l++)
+      sk::ilu_factor_level(LU, dpos.p, order_l.p + lptr[(size_t)l], lptr[(size_t)l + 1] - lptr[(size_t)l], s);
+  } else {
+    iterative_factor(comm, (long long)A.row_start);
+  }
   MI_HIP(hipGetLastError());
   y.alloc((size_t)n);
   t.alloc((size_t)n);
@@ -125,13 +153,117 @@ void IluSolver::setup(ParCSR &A) {
   zero_on_stream(t.p, (size_t)n * sizeof(double));
   MI_HIP(hipStreamSynchronize(s));
   is_setup = true;
-  if (print_level > 0 && current_comm().rank == 0)
+  if (print_level > 0 && comm.rank == 0 && levels_built)
     printf("mi_hypre ILU(%d): %d rows, %lld entries, %d lower / %d upper level sets, %s triangular solves\n", level_of_fill, n,
            (long long)LU.nnz, nl, nu, tri_solve ? "exact" : "Jacobi");
+  else if (print_level > 0 && comm.rank == 0)
+    printf("mi_hypre ILU(%d): %d rows, %lld entries, no level sets, Jacobi triangular solves\n", level_of_fill, n,
+           (long long)LU.nnz);
+}
+
+// Iterative ILU(0) setup (types 1-4): x_0, then at most iter_max_iter fixed-point sweeps on this
+// rank's block -- type 3 synchronous (two value buffers), 4 the same with the correction fused into the sweep, 1 and 2
+// asynchronous in place (1 on LU's own values, 2 on split L / U-by-column storage) -- then the values land in LU.
+// Norms are taken per sweep only when an option bit asks for them; each costs one small download.  One all-reduce at
+// the end: every rank learns of a failure anywhere, and rank 0 reports the largest sweeps and norms.
+void IluSolver::iterative_factor(Comm &comm, long long row0) {
+  hipStream_t s = ctx().stream;
+  const bool stop = iter_option & 2, want_c = stop || (iter_option & 4), want_r = iter_option & 8,
+             keep = iter_option & 16, verbose = (iter_option & 1) && print_level > 0 && comm.rank == 0;
+  iter_sweeps = 0;
+  iter_correction = iter_residual = -1.0;
+  iter_corr_hist.clear();
+  iter_res_hist.clear();
+  int err = 0;  // 1: zero pivot in bad_row, 2: too many entries for 32-bit slots
+  long long bad_row = -1;
+  if (LU.nnz > (long long)INT32_MAX - 2) err = 2;
+  sk::ItiluPlan P;
+  if (!err) {
+    const int r = sk::itilu_plan(LU, dpos.p, iter_type != 1, P, s);
+    if (r >= 0) err = 1, bad_row = r;
+  }
+  if (!err && P.nnz) {
+    DVec<unsigned long long> st(4);
+    auto as_double = [](unsigned long long b) {
+      double d;
+      memcpy(&d, &b, sizeof d);
+      return d;
+    };
+    auto reset_norms = [&]() { MI_HIP(hipMemsetAsync(st.p, 0, 3 * sizeof(unsigned long long), s)); };
+    MI_HIP(hipMemsetAsync(st.p + 3, 0xff, sizeof(unsigned long long), s));
+    double amax = 0.0;
+    if (want_r) {
+      reset_norms();
+      sk::itilu_abs_max(P, st.p, s);
+      unsigned long long b = 0;
+      d2h(&b, st.p, sizeof b, s);
+      amax = as_double(b);
+    }
+    DVec<double> xa, xb;
+    double *cur = LU.a.p, *nxt = nullptr;
+    if (iter_type != 1) {
+      xa.alloc((size_t)P.nnz);
+      cur = xa.p;
+    }
+    if (iter_type >= 3) {
+      xb.alloc((size_t)P.nnz);
+      nxt = xb.p;
+    }
+    sk::itilu_start(P, cur, st.p, s);
+    for (int m = 1; m <= iter_max_iter; m++) {
+      if (want_c || want_r) reset_norms();
+      if (iter_type >= 3) {
+        sk::itilu_sweep(P, cur, nxt, iter_type == 4, st.p, s);
+        if (iter_type == 3 && want_c) sk::itilu_correction(P, cur, nxt, st.p, s);
+        std::swap(cur, nxt);
+      } else {
+        sk::itilu_async_sweep(P, cur, want_c, st.p, s);
+      }
+      if (want_r) sk::itilu_residual(P, cur, st.p, s);
+      MI_HIP(hipGetLastError());
+      iter_sweeps = m;
+      if (!(want_c || want_r)) continue;
+      unsigned long long h[4];
+      d2h(h, st.p, sizeof h, s);
+      if (want_c) {
+        const double xm = as_double(h[1]);
+        iter_correction = xm > 0.0 ? as_double(h[0]) / xm : as_double(h[0]);
+        if (keep) iter_corr_hist.push_back(iter_correction);
+      }
+      if (want_r) {
+        iter_residual = amax > 0.0 ? as_double(h[2]) / amax : as_double(h[2]);
+        if (keep) iter_res_hist.push_back(iter_residual);
+      }
+      if (verbose)
+        printf("mi_hypre ILU iterative setup (type %d) sweep %d: correction %.6e, residual %.6e\n", iter_type, m,
+               iter_correction, iter_residual);
+      if (h[3] != ~0ull) break;  // a zero pivot: reported below
+      if (stop && iter_correction <= iter_tol) break;
+    }
+    unsigned long long piv = 0;
+    d2h(&piv, st.p + 3, sizeof piv, s);
+    if (piv != ~0ull) err = 1, bad_row = (long long)piv;
+    if (!err && iter_type != 1) sk::itilu_scatter(P, cur, LU, s);
+    MI_HIP(hipStreamSynchronize(s));  // the value buffers are released on return
+  }
+  double v[4] = {(double)err, (double)iter_sweeps, iter_correction, iter_residual};
+  comm.allreduce_host(v, 4, CommDType::F64, CommOp::MAX);
+  if (err == 1)
+    fail(1, "HYPRE_ILUSetup: iterative ILU(0) setup: zero pivot u_jj in row " + std::to_string(bad_row) +
+                " of this rank's block (global row " + std::to_string(row0 + bad_row) + ")");
+  if (err == 2)
+    fail(1, "HYPRE_ILUSetup: the iterative ILU(0) setup is not implemented for more than 2^31 - 3 entries per rank (" +
+                std::to_string((long long)LU.nnz) + ")");
+  if (v[0] > 0.0) fail(1, "HYPRE_ILUSetup: iterative ILU(0) setup failed on another rank");
+  if (print_level > 0 && comm.rank == 0)
+    printf("mi_hypre ILU iterative setup (type %d, option %d): %d sweeps (max over ranks), correction %.3e, residual "
+           "%.3e\n", iter_type, iter_option, (int)v[1], v[2], v[3]);
 }
 
 void IluSolver::apply(const double *rhs, double *out) {
   hipStream_t s = ctx().stream;
+  MI_REQUIRE(!tri_solve || levels_built,
+             "HYPRE_ILUSolve: exact triangular solves need the level sets, which a setup with trisolve 0 did not build");
   if (tri_solve) {
     const int nl = (int)lptr.size() - 1, nu = (int)uptr.size() - 1;
     for (int l = 0; l < nl; l++)
@@ -159,7 +291,7 @@ void IluSolver::apply(const double *rhs, double *out) {
 }
 
 int IluSolver::solve(ParCSR &A, ParVector &b, ParVector &x) {
-  if (!is_setup) setup(A);
+  if (!is_setup) setup(A, current_comm());
   MI_REQUIRE(b.n == n && x.n == n, "HYPRE_ILUSolve: vector size does not match the matrix");
   MI_REQUIRE(b.ncomp == x.ncomp, "HYPRE_ILUSolve: b and x differ in their number of components");
   Comm &comm = current_comm();

@@ -1619,6 +1619,238 @@ __global__ __launch_bounds__(BLK) void ilu_upper_jac_k(int n, const long long *_
   out[i] = (d >= 0) ? s / a[d] : s;
 }
 
+// ---------------------------------------------------------------- iterative ILU(0) setup (fixed-point sweeps)
+// Values live in slots (ItiluPlan, setup_kernels.hpp); every slot t owns one stored entry (i,j) of the pattern, the list
+// of its (l_ik, u_kj) slot pairs in ascending k, and dslot[t]: the slot of u_jj for an L entry, -1 for an off-diagonal
+// U entry, -(i + 2) for the diagonal of row i.  The norms are max-reductions of non-negative doubles, taken as atomic
+// maxima of their bit patterns (exact in any order); stat[3] is the smallest row whose pivot was found zero.
+__device__ __forceinline__ int itilu_row_of(const long long *__restrict__ ia, int n, long long e) {
+  int lo = 0, hi = n - 1;  // the row r with ia[r] <= e < ia[r + 1]
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (ia[mid] <= e) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// rows without a stored diagonal have a zero pivot; the L / U entry counts of every row
+__global__ __launch_bounds__(BLK) void itilu_rows_k(int n, const long long *__restrict__ ia,
+                                                    const long long *__restrict__ dpos, int *__restrict__ lcnt,
+                                                    int *__restrict__ ucnt, unsigned long long *__restrict__ bad_row) {
+  const long long i = bid() * BLK + threadIdx.x;
+  if (i >= n) return;
+  const long long d = dpos[i];
+  if (d < 0) {
+    atomicMin(bad_row, (unsigned long long)i);
+    lcnt[i] = ucnt[i] = 0;
+    return;
+  }
+  lcnt[i] = (int)(d - ia[i]);
+  ucnt[i] = (int)(ia[i + 1] - d);
+}
+
+// the L entries of every row in CSR order (perm[lptr[i] + q] = position), and the U part as a CSR whose values are the
+// positions (exact in a double below 2^53): its transpose lists U by (column, row)
+__global__ __launch_bounds__(BLK) void itilu_split_k(int n, const long long *__restrict__ ia, const int *__restrict__ ja,
+                                                     const long long *__restrict__ dpos, const long long *__restrict__ lptr,
+                                                     const long long *__restrict__ uptr, int *__restrict__ perm,
+                                                     int *__restrict__ uja, double *__restrict__ ua) {
+  const long long i = bid() * BLK + threadIdx.x;
+  if (i >= n) return;
+  const long long d = dpos[i];
+  if (d < 0) return;
+  long long o = lptr[i];
+  for (long long k = ia[i]; k < d; k++) perm[o++] = (int)k;
+  o = uptr[i];
+  for (long long k = d; k < ia[i + 1]; k++) {
+    uja[o] = ja[k];
+    ua[o++] = (double)k;
+  }
+}
+
+__global__ __launch_bounds__(BLK) void itilu_upos_k(long long nu, long long nl, const double *__restrict__ tpos,
+                                                    int *__restrict__ perm) {
+  const long long q = bid() * BLK + threadIdx.x;
+  if (q < nu) perm[nl + q] = (int)tpos[q];
+}
+
+__global__ __launch_bounds__(BLK) void itilu_inverse_k(long long nnz, const int *__restrict__ perm, int *__restrict__ inv) {
+  const long long t = bid() * BLK + threadIdx.x;
+  if (t < nnz) inv[perm[t]] = (int)t;
+}
+
+// FILL false: cnt[t] = number of pairs of slot t, a[t], dslot[t]; FILL true: the pairs at ptr[t]
+template <bool FILL>
+__global__ __launch_bounds__(BLK) void itilu_pairs_k(long long nnz, int n, const long long *__restrict__ ia,
+                                                     const int *__restrict__ ja, const double *__restrict__ aval,
+                                                     const long long *__restrict__ dpos, const int *__restrict__ perm,
+                                                     const int *__restrict__ inv, int *__restrict__ cnt,
+                                                     double *__restrict__ a, int *__restrict__ dslot,
+                                                     const long long *__restrict__ ptr, int *__restrict__ pl,
+                                                     int *__restrict__ pu) {
+  const long long t = bid() * BLK + threadIdx.x;
+  if (t >= nnz) return;
+  const long long e = perm ? perm[t] : t;
+  const int i = itilu_row_of(ia, n, e), j = ja[e];
+  const int m = i < j ? i : j;
+  long long o = FILL ? ptr[t] : 0;
+  int c = 0;
+  for (long long kk = ia[i]; kk < ia[i + 1]; kk++) {
+    const int k = ja[kk];
+    if (k >= m) break;
+    if (dpos[k] < 0) continue;
+    long long lo = dpos[k] + 1, hi = ia[k + 1];  // (k, j), j > k, by bisection in row k
+    while (lo < hi) {
+      const long long mid = (lo + hi) >> 1;
+      if (ja[mid] < j) lo = mid + 1;
+      else hi = mid;
+    }
+    if (lo < ia[k + 1] && ja[lo] == j) {
+      if (FILL) {
+        pl[o] = inv ? inv[kk] : (int)kk;
+        pu[o++] = inv ? inv[lo] : (int)lo;
+      }
+      c++;
+    }
+  }
+  if (!FILL) {
+    cnt[t] = c;
+    a[t] = aval[e];
+    const long long dj = dpos[j];
+    dslot[t] = (i > j) ? (dj < 0 ? -1 : (inv ? inv[dj] : (int)dj)) : (i == j ? -(i + 2) : -1);
+  }
+}
+
+__device__ __forceinline__ void itilu_block_max(double v, unsigned long long *out) {
+  __shared__ double sh[BLK];
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int d = BLK / 2; d > 0; d >>= 1) {
+    if (threadIdx.x < d) sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + d]);
+    __syncthreads();
+  }
+  // only a block that beats the maximum seen so far takes the atomic: one atomic per block on ONE address serialised
+  // the reduction (the fused type-4 sweep took 4x the time of the plain one at 256^3); a stale read costs an atomic
+  const unsigned long long bits = (unsigned long long)__double_as_longlong(sh[0]);
+  if (threadIdx.x == 0 && sh[0] > 0.0 && bits > __hip_atomic_load(out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+    atomicMax(out, bits);
+  __syncthreads();
+}
+
+// x0: L = strictly lower part of A with column j divided by a_jj, U = upper part of A
+__global__ __launch_bounds__(BLK) void itilu_start_k(long long nnz, const double *__restrict__ a,
+                                                     const int *__restrict__ dslot, double *__restrict__ x,
+                                                     unsigned long long *__restrict__ stat) {
+  const long long t = bid() * BLK + threadIdx.x;
+  if (t >= nnz) return;
+  const int d = dslot[t];
+  x[t] = d >= 0 ? a[t] / a[d] : a[t];
+  if (d <= -2 && a[t] == 0.0) atomicMin(&stat[3], (unsigned long long)(-d - 2));
+}
+
+// synchronous sweep: xn = F(xo), one thread per slot, the pairs in ascending k.  NORM (type 4, fused): also max|xn - xo|
+// and max|xn| into stat[0], stat[1]
+template <bool NORM>
+__global__ __launch_bounds__(BLK) void itilu_sweep_k(long long nnz, const double *__restrict__ a,
+                                                     const int *__restrict__ dslot, const long long *__restrict__ ptr,
+                                                     const int *__restrict__ pl, const int *__restrict__ pu,
+                                                     const double *__restrict__ xo, double *__restrict__ xn,
+                                                     unsigned long long *__restrict__ stat) {
+  const long long t = bid() * BLK + threadIdx.x;
+  double dx = 0.0, xm = 0.0;
+  if (t < nnz) {
+    double s = a[t];
+    for (long long p = ptr[t]; p < ptr[t + 1]; p++) s -= xo[pl[p]] * xo[pu[p]];
+    const int d = dslot[t];
+    if (d >= 0) s = s / xo[d];
+    xn[t] = s;
+    if (d <= -2 && s == 0.0) atomicMin(&stat[3], (unsigned long long)(-d - 2));
+    if (NORM) {
+      dx = fabs(s - xo[t]);
+      xm = fabs(s);
+    }
+  }
+  if (NORM) {
+    itilu_block_max(dx, &stat[0]);
+    itilu_block_max(xm, &stat[1]);
+  }
+}
+
+// correction of a synchronous sweep (type 3): max|xn - xo|, max|xn|
+__global__ __launch_bounds__(BLK) void itilu_correction_k(long long nnz, const double *__restrict__ xo,
+                                                          const double *__restrict__ xn,
+                                                          unsigned long long *__restrict__ stat) {
+  const long long t = bid() * BLK + threadIdx.x;
+  double dx = 0.0, xm = 0.0;
+  if (t < nnz) {
+    dx = fabs(xn[t] - xo[t]);
+    xm = fabs(xn[t]);
+  }
+  itilu_block_max(dx, &stat[0]);
+  itilu_block_max(xm, &stat[1]);
+}
+
+// asynchronous sweep in place (types 1 and 2): every value another thread may be writing is read and written with
+// relaxed agent-scope atomics (L2-served, no stale L1 line; other XCDs' values of this launch may still be old ones)
+template <bool NORM>
+__global__ __launch_bounds__(BLK) void itilu_async_k(long long nnz, const double *__restrict__ a,
+                                                     const int *__restrict__ dslot, const long long *__restrict__ ptr,
+                                                     const int *__restrict__ pl, const int *__restrict__ pu, double *x,
+                                                     unsigned long long *__restrict__ stat) {
+  const long long t = bid() * BLK + threadIdx.x;
+  double dx = 0.0, xm = 0.0;
+  if (t < nnz) {
+    double s = a[t];
+    for (long long p = ptr[t]; p < ptr[t + 1]; p++)
+      s -= __hip_atomic_load(x + pl[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) *
+           __hip_atomic_load(x + pu[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int d = dslot[t];
+    if (d >= 0) s = s / __hip_atomic_load(x + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const double old = __hip_atomic_load(x + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(x + t, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (d <= -2 && s == 0.0) atomicMin(&stat[3], (unsigned long long)(-d - 2));
+    if (NORM) {
+      dx = fabs(s - old);
+      xm = fabs(s);
+    }
+  }
+  if (NORM) {
+    itilu_block_max(dx, &stat[0]);
+    itilu_block_max(xm, &stat[1]);
+  }
+}
+
+// residual on the pattern: max |a_ij - (L U)_ij| into stat[2] (l_ii = 1: the last term is l_ij u_jj or u_ij)
+__global__ __launch_bounds__(BLK) void itilu_residual_k(long long nnz, const double *__restrict__ a,
+                                                        const int *__restrict__ dslot, const long long *__restrict__ ptr,
+                                                        const int *__restrict__ pl, const int *__restrict__ pu,
+                                                        const double *__restrict__ x,
+                                                        unsigned long long *__restrict__ stat) {
+  const long long t = bid() * BLK + threadIdx.x;
+  double r = 0.0;
+  if (t < nnz) {
+    double s = a[t];
+    for (long long p = ptr[t]; p < ptr[t + 1]; p++) s -= x[pl[p]] * x[pu[p]];
+    const int d = dslot[t];
+    s -= d >= 0 ? x[t] * x[d] : x[t];
+    r = fabs(s);
+  }
+  itilu_block_max(r, &stat[2]);
+}
+
+__global__ __launch_bounds__(BLK) void itilu_abs_max_k(long long nnz, const double *__restrict__ a,
+                                                       unsigned long long *__restrict__ stat) {
+  const long long t = bid() * BLK + threadIdx.x;
+  itilu_block_max(t < nnz ? fabs(a[t]) : 0.0, &stat[0]);
+}
+
+__global__ __launch_bounds__(BLK) void itilu_scatter_k(long long nnz, const int *__restrict__ perm,
+                                                       const double *__restrict__ x, double *__restrict__ lu) {
+  const long long t = bid() * BLK + threadIdx.x;
+  if (t < nnz) lu[perm[t]] = x[t];
+}
+
 // ---------------------------------------------------------------- zero-guess sub-operator
 // which entries of row i a first sweep on a zero guess can touch: the row's own chunk, and for an F row
 // (i >= nc) the C columns (< nc) the preceding C pass has just written
@@ -2669,6 +2901,98 @@ void ilu_upper_jacobi(const DCsr &LU, const long long *dpos, const double *b, co
                       hipStream_t s) {
   const int n = LU.nrows;
   if (n) ilu_upper_jac_k<<<(unsigned)((n + BLK - 1) / BLK), BLK, 0, s>>>(n, LU.ia.p, LU.ja.p, LU.a.p, dpos, b, in, out);
+}
+
+int itilu_plan(const DCsr &LU, const long long *dpos, bool split, ItiluPlan &P, hipStream_t s) {
+  const int n = LU.nrows;
+  const long long nnz = LU.nnz;
+  P.nnz = nnz;
+  P.npairs = 0;
+  P.perm.release();
+  if (nnz == 0) return -1;
+  DVec<unsigned long long> bad(1);
+  MI_HIP(hipMemsetAsync(bad.p, 0xff, sizeof(unsigned long long), s));
+  DVec<int> lcnt((size_t)n), ucnt((size_t)n);
+  itilu_rows_k<<<grid_for((n + BLK - 1) / BLK), BLK, 0, s>>>(n, LU.ia.p, dpos, lcnt.p, ucnt.p, bad.p);
+  unsigned long long b = 0;
+  d2h(&b, bad.p, sizeof(b), s);
+  if (b != ~0ull) return (int)b;
+  DVec<int> inv;
+  if (split) {  // slots: the L entries in CSR order, then the U entries by (column, row)
+    DVec<long long> lptr((size_t)n + 1), uptr((size_t)n + 1);
+    exclusive_scan(lcnt.p, lptr.p, n, s);
+    exclusive_scan(ucnt.p, uptr.p, n, s);
+    long long nl = 0;
+    d2h(&nl, lptr.p + n, sizeof(nl), s);
+    DCsr Up, Ut;
+    Up.nrows = Up.ncols = n;
+    Up.nnz = nnz - nl;
+    Up.ia = std::move(uptr);
+    Up.ja.alloc((size_t)Up.nnz);
+    Up.a.alloc((size_t)Up.nnz);
+    P.perm.alloc((size_t)nnz);
+    itilu_split_k<<<grid_for((n + BLK - 1) / BLK), BLK, 0, s>>>(n, LU.ia.p, LU.ja.p, dpos, lptr.p, Up.ia.p, P.perm.p,
+                                                                 Up.ja.p, Up.a.p);
+    transpose(Up, Ut, s);
+    if (Ut.nnz)
+      itilu_upos_k<<<grid_for((Ut.nnz + BLK - 1) / BLK), BLK, 0, s>>>(Ut.nnz, nl, Ut.a.p, P.perm.p);
+    inv.alloc((size_t)nnz);
+    itilu_inverse_k<<<grid_for((nnz + BLK - 1) / BLK), BLK, 0, s>>>(nnz, P.perm.p, inv.p);
+  }
+  DVec<int> cnt((size_t)nnz);
+  P.a.alloc((size_t)nnz);
+  P.dslot.alloc((size_t)nnz);
+  P.ptr.alloc((size_t)nnz + 1);
+  const dim3 g = grid_for((nnz + BLK - 1) / BLK);
+  itilu_pairs_k<false><<<g, BLK, 0, s>>>(nnz, n, LU.ia.p, LU.ja.p, LU.a.p, dpos, P.perm.p, inv.p, cnt.p, P.a.p,
+                                         P.dslot.p, nullptr, nullptr, nullptr);
+  exclusive_scan(cnt.p, P.ptr.p, nnz, s);
+  d2h(&P.npairs, P.ptr.p + nnz, sizeof(long long), s);
+  P.pl.alloc((size_t)P.npairs);
+  P.pu.alloc((size_t)P.npairs);
+  itilu_pairs_k<true><<<g, BLK, 0, s>>>(nnz, n, LU.ia.p, LU.ja.p, LU.a.p, dpos, P.perm.p, inv.p, nullptr, nullptr,
+                                        nullptr, P.ptr.p, P.pl.p, P.pu.p);
+  MI_HIP(hipGetLastError());
+  MI_HIP(hipStreamSynchronize(s));  // the temporaries are released on return
+  return -1;
+}
+void itilu_start(const ItiluPlan &P, double *x, unsigned long long *stat, hipStream_t s) {
+  if (P.nnz) itilu_start_k<<<grid_for((P.nnz + BLK - 1) / BLK), BLK, 0, s>>>(P.nnz, P.a.p, P.dslot.p, x, stat);
+}
+void itilu_sweep(const ItiluPlan &P, const double *xo, double *xn, bool fused_norm, unsigned long long *stat,
+                 hipStream_t s) {
+  if (!P.nnz) return;
+  const dim3 g = grid_for((P.nnz + BLK - 1) / BLK);
+  if (fused_norm)
+    itilu_sweep_k<true><<<g, BLK, 0, s>>>(P.nnz, P.a.p, P.dslot.p, P.ptr.p, P.pl.p, P.pu.p, xo, xn, stat);
+  else
+    itilu_sweep_k<false><<<g, BLK, 0, s>>>(P.nnz, P.a.p, P.dslot.p, P.ptr.p, P.pl.p, P.pu.p, xo, xn, stat);
+}
+void itilu_correction(const ItiluPlan &P, const double *xo, const double *xn, unsigned long long *stat, hipStream_t s) {
+  if (P.nnz) itilu_correction_k<<<grid_for((P.nnz + BLK - 1) / BLK), BLK, 0, s>>>(P.nnz, xo, xn, stat);
+}
+void itilu_async_sweep(const ItiluPlan &P, double *x, bool norm, unsigned long long *stat, hipStream_t s) {
+  if (!P.nnz) return;
+  const dim3 g = grid_for((P.nnz + BLK - 1) / BLK);
+  if (norm)
+    itilu_async_k<true><<<g, BLK, 0, s>>>(P.nnz, P.a.p, P.dslot.p, P.ptr.p, P.pl.p, P.pu.p, x, stat);
+  else
+    itilu_async_k<false><<<g, BLK, 0, s>>>(P.nnz, P.a.p, P.dslot.p, P.ptr.p, P.pl.p, P.pu.p, x, stat);
+}
+void itilu_residual(const ItiluPlan &P, const double *x, unsigned long long *stat, hipStream_t s) {
+  if (P.nnz)
+    itilu_residual_k<<<grid_for((P.nnz + BLK - 1) / BLK), BLK, 0, s>>>(P.nnz, P.a.p, P.dslot.p, P.ptr.p, P.pl.p,
+                                                                        P.pu.p, x, stat);
+}
+void itilu_abs_max(const ItiluPlan &P, unsigned long long *stat, hipStream_t s) {
+  if (P.nnz) itilu_abs_max_k<<<grid_for((P.nnz + BLK - 1) / BLK), BLK, 0, s>>>(P.nnz, P.a.p, stat);
+}
+void itilu_scatter(const ItiluPlan &P, const double *x, DCsr &LU, hipStream_t s) {
+  if (!P.nnz) return;
+  if (P.perm.p)
+    itilu_scatter_k<<<grid_for((P.nnz + BLK - 1) / BLK), BLK, 0, s>>>(P.nnz, P.perm.p, x, LU.a.p);
+  else if (x != LU.a.p)
+    MI_HIP(hipMemcpyAsync(LU.a.p, x, (size_t)P.nnz * sizeof(double), hipMemcpyDeviceToDevice, s));
 }
 
 // ---------------------------------------------------------------- distributed setup on the device

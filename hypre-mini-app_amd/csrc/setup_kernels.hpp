@@ -132,6 +132,41 @@ void ilu_upper_level(const DCsr &LU, const long long *dpos, const int *rows, int
 void ilu_lower_jacobi(const DCsr &LU, const long long *dpos, const double *b, const double *in, double *out, hipStream_t s);
 void ilu_upper_jacobi(const DCsr &LU, const long long *dpos, const double *b, const double *in, double *out, hipStream_t s);
 
+// ---- iterative ILU(0) setup (ilu.cpp; DESIGN.md section 3, "Iterative ILU(0) setup"): fixed-point sweeps on the
+// pattern S of LU.  Every stored entry (i,j) owns a value slot; the split layout (types 2-4) puts the L entries in CSR
+// order first and the U entries after them by (column, row), the in-place layout (type 1) is LU's own order.  The
+// pairs ((i,k), (k,j)) in S of every entry, k < min(i,j) ascending, are found once; a sweep gathers over them:
+//   s = a_ij; s -= l_ik * u_kj (ascending k); l_ij = s / u_jj (i > j) or u_ij = s (i <= j)
+// Slot and pair indices are 32-bit (the caller refuses nnz > INT_MAX).
+// stat[4] (device, unsigned 64-bit): [0] max|x_m - x_(m-1)|, [1] max|x_m|, [2] max|a - LU| on S (or max|a|, itilu_abs_max)
+// -- bit patterns of non-negative doubles, atomic maxima (exact in any order) -- and [3] the smallest row whose pivot
+// u_jj was zero (all ones: none).  The caller zeroes [0..2] and fills [3] with ones.
+struct ItiluPlan {
+  long long nnz = 0, npairs = 0;
+  DVec<int> perm;        // slot -> position in LU (empty: the identity)
+  DVec<double> a;        // a_ij by slot
+  DVec<int> dslot;       // L entry: slot of u_jj; off-diagonal U entry: -1; diagonal of row i: -(i + 2)
+  DVec<long long> ptr;   // pairs of slot t: [ptr[t], ptr[t + 1])
+  DVec<int> pl, pu;      // slots of l_ik and u_kj
+};
+// builds the plan; returns -1, or the first row without a stored diagonal (then nothing is built)
+int itilu_plan(const DCsr &LU, const long long *dpos, bool split, ItiluPlan &P, hipStream_t s);
+// x_0: L = strictly lower part of A with column j divided by a_jj, U = upper part of A (zero a_jj -> stat[3])
+void itilu_start(const ItiluPlan &P, double *x, unsigned long long *stat, hipStream_t s);
+// synchronous sweep xn = F(xo); fused_norm: the same launch also reduces stat[0], stat[1]
+void itilu_sweep(const ItiluPlan &P, const double *xo, double *xn, bool fused_norm, unsigned long long *stat,
+                 hipStream_t s);
+// stat[0], stat[1] of a synchronous sweep
+void itilu_correction(const ItiluPlan &P, const double *xo, const double *xn, unsigned long long *stat, hipStream_t s);
+// asynchronous sweep in place (relaxed agent-scope loads and stores); norm: stat[0], stat[1] against the value replaced
+void itilu_async_sweep(const ItiluPlan &P, double *x, bool norm, unsigned long long *stat, hipStream_t s);
+// stat[2] = max over S of |a_ij - (L U)_ij|
+void itilu_residual(const ItiluPlan &P, const double *x, unsigned long long *stat, hipStream_t s);
+// stat[0] = max |a_ij|
+void itilu_abs_max(const ItiluPlan &P, unsigned long long *stat, hipStream_t s);
+// LU.a[perm[t]] = x[t]
+void itilu_scatter(const ItiluPlan &P, const double *x, DCsr &LU, hipStream_t s);
+
 // ---- FSAI with a static pattern (fsai.cpp), on a rank's diagonal block B (columns ascending in every row)
 // S = B's pattern, values 1.0: filter -- (i,i) (inserted when B does not store it) and every (i,j) with
 // |b_ij| >= theta * max_{l != i} |b_il|; no filter -- every entry; lower -- only the entries j <= i

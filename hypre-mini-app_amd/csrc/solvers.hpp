@@ -81,10 +81,20 @@ struct PcgSolver : KrylovSolver {
 // HYPRE_ILU, type 0 (block Jacobi) with level of fill 0: ILU(0) of this rank's diagonal block, factorised and
 // applied on the device by level sets (src/HypreSystem.cpp:328-370 as preconditioner, :457-497 as solver).
 // tri_solve 1: exact substitutions (one launch per level set); 0: lower/upper Jacobi sweeps (HYPRE's GPU option)
+// iter_type 1-4 (fill 0 only): the factors come from fixed-point sweeps instead of the level-scheduled factorisation
+// ("Iterative ILU(0) setup"); with tri_solve 0 no level set is computed then
 struct IluSolver : SolverBase {
   int ilu_type = 0, level_of_fill = 0, max_iter = 20, print_level = 0, tri_solve = 1, lower_it = 5, upper_it = 5;
   double tol = 1e-7;
-  bool is_setup = false;
+  // iterative setup: algorithm type (0 = exact), option bits, sweep limit, tolerance of the correction (option bit 2)
+  int iter_type = 0, iter_option = 0, iter_max_iter = 100;
+  double iter_tol = 1e-3;
+  // what the last iterative setup did on this rank: sweeps run, the last correction / residual norm (-1: never
+  // computed), and their histories (option bit 16)
+  int iter_sweeps = 0;
+  double iter_correction = -1.0, iter_residual = -1.0;
+  std::vector<double> iter_corr_hist, iter_res_hist;
+  bool is_setup = false, levels_built = false;
   int n = 0;
   sk::DCsr LU;
   DVec<long long> dpos;
@@ -95,7 +105,9 @@ struct IluSolver : SolverBase {
   int num_iterations = 0;
   double final_rel_res = 0.0;
   IluSolver() : SolverBase(K_ILU) {}
-  void setup(ParCSR &A);
+  // every rank of comm calls it (the iterative setup agrees on failures and reports over comm)
+  void setup(ParCSR &A, Comm &comm);
+  void iterative_factor(Comm &comm, long long row0);
   void apply(const double *rhs, double *out);           // out = U^-1 L^-1 rhs
   int solve(ParCSR &A, ParVector &b, ParVector &x);     // x += M^-1 (b - A x), max_iter times or to tol
 };

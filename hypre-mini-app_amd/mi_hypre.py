@@ -277,6 +277,10 @@ class BoomerAMG:
                               ("ilu_tri_solve", "HYPRE_BoomerAMGSetILUTriSolve", int),
                               ("ilu_lower_jacobi_iters", "HYPRE_BoomerAMGSetILULowerJacobiIters", int),
                               ("ilu_upper_jacobi_iters", "HYPRE_BoomerAMGSetILUUpperJacobiIters", int),
+                              ("iterative_ilu_algorithm_type", "HYPRE_BoomerAMGSetILUIterSetupType", int),
+                              ("iterative_ilu_setup_option", "HYPRE_BoomerAMGSetILUIterSetupOption", int),
+                              ("iterative_ilu_max_iterations", "HYPRE_BoomerAMGSetILUIterSetupMaxIter", int),
+                              ("iterative_ilu_tolerance", "HYPRE_BoomerAMGSetILUIterSetupTolerance", float),
                               ("fsai_algo_type", "HYPRE_BoomerAMGSetFSAIAlgoType", int),
                               ("fsai_local_solve_type", "HYPRE_BoomerAMGSetFSAILocalSolveType", int),
                               ("fsai_num_levels", "HYPRE_BoomerAMGSetFSAINumLevels", int),
@@ -422,14 +426,20 @@ class BoomerAMG:
 
 
 class ILU:
-    """HYPRE_ILU: block-Jacobi ILU(0) (type 0, fill 0); usable as a preconditioner (set_precond) or a solver."""
+    """HYPRE_ILU: block-Jacobi ILU(k) (type 0); usable as a preconditioner (set_precond) or a solver.
+    iterative_algorithm_type 1-4 (fill 0): the factors come from fixed-point sweeps."""
 
     def __init__(self, max_iterations=1, tolerance=0.0, trisolve=1, lower_jacobi_iters=5, upper_jacobi_iters=5,
-                 print_level=0, ilu_type=0, fill=0):
+                 print_level=0, ilu_type=0, fill=0, iterative_algorithm_type=0, iterative_setup_option=0,
+                 iterative_max_iterations=100, iterative_tolerance=1e-3):
         self.h = vp()
         call("HYPRE_ILUCreate", C.byref(self.h))
         call("HYPRE_ILUSetType", self.h, ilu_type)
         call("HYPRE_ILUSetLevelOfFill", self.h, fill)
+        call("HYPRE_ILUSetIterativeSetupType", self.h, int(iterative_algorithm_type))
+        call("HYPRE_ILUSetIterativeSetupOption", self.h, int(iterative_setup_option))
+        call("HYPRE_ILUSetIterativeSetupMaxIter", self.h, int(iterative_max_iterations))
+        call("HYPRE_ILUSetIterativeSetupTolerance", self.h, float(iterative_tolerance))
         call("HYPRE_ILUSetMaxIter", self.h, max_iterations)
         call("HYPRE_ILUSetTol", self.h, float(tolerance))
         call("HYPRE_ILUSetTriSolve", self.h, trisolve)
@@ -455,6 +465,31 @@ class ILU:
         v = c_dbl()
         call("HYPRE_ILUGetFinalRelativeResidualNorm", self.h, C.byref(v))
         return v.value
+
+    def iterative_setup_info(self):
+        """(sweeps, last correction, last residual) of the last iterative setup on this rank; -1 = norm not computed."""
+        n, c, r = c_int(), c_dbl(), c_dbl()
+        call("HYPRE_MI_ILUGetIterativeSetupInfo", self.h, C.byref(n), C.byref(c), C.byref(r))
+        return n.value, c.value, r.value
+
+    def iterative_setup_history(self):
+        """(corrections, residuals) kept by option bit 16, one entry per sweep for each norm that was computed."""
+        nc, nr = c_int(), c_int()
+        call("HYPRE_MI_ILUGetIterativeSetupHistory", self.h, C.byref(nc), None, C.byref(nr), None)
+        c = np.zeros(max(nc.value, 1))
+        r = np.zeros(max(nr.value, 1))
+        call("HYPRE_MI_ILUGetIterativeSetupHistory", self.h, C.byref(nc), c, C.byref(nr), r)
+        return c[: nc.value], r[: nr.value]
+
+    def factors(self):
+        """(ia int64, ja int32, a f64): L (unit diagonal not stored) and U of this rank's block as one CSR."""
+        nr, nnz = c_int(), c_big()
+        call("HYPRE_MI_ILUGetFactorsSize", self.h, C.byref(nr), C.byref(nnz))
+        ia = np.zeros(nr.value + 1, dtype=np.int64)
+        ja = np.zeros(max(nnz.value, 1), dtype=np.int32)
+        a = np.zeros(max(nnz.value, 1), dtype=np.float64)
+        call("HYPRE_MI_ILUGetFactors", self.h, ia, ja, a)
+        return ia, ja[: nnz.value], a[: nnz.value]
 
     def destroy(self):
         if self.h:

@@ -162,6 +162,16 @@ HYPRE_Int HYPRE_MI_BoomerAMGRelaxLevel(HYPRE_Solver solver, HYPRE_Int level, HYP
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelFSAISize(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int *nrows, HYPRE_BigInt *nnz);
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelFSAI(HYPRE_Solver solver, HYPRE_Int level, HYPRE_BigInt *ia, HYPRE_Int *ja,
                                          HYPRE_Complex *a, HYPRE_Real *omega);
+/* HYPRE_ILU with the iterative setup (types 1-4): sweeps run by the last Setup on this rank and
+ * the last correction / residual norm (-1 when the option bits did not ask for it); the kept histories (option bit
+ * 16; null arrays: the lengths only); the factors L (unit, strictly lower) and U as one CSR of the rank's diagonal
+ * block (columns ascending) */
+HYPRE_Int HYPRE_MI_ILUGetIterativeSetupInfo(HYPRE_Solver solver, HYPRE_Int *sweeps, HYPRE_Real *correction,
+                                            HYPRE_Real *residual);
+HYPRE_Int HYPRE_MI_ILUGetIterativeSetupHistory(HYPRE_Solver solver, HYPRE_Int *ncorr, HYPRE_Real *corr, HYPRE_Int *nres,
+                                               HYPRE_Real *res);
+HYPRE_Int HYPRE_MI_ILUGetFactorsSize(HYPRE_Solver solver, HYPRE_Int *nrows, HYPRE_BigInt *nnz);
+HYPRE_Int HYPRE_MI_ILUGetFactors(HYPRE_Solver solver, HYPRE_BigInt *ia, HYPRE_Int *ja, HYPRE_Complex *a);
 /* one complex-smoother step of a level on HOST arrays (the counterpart of RelaxLevel): u <- u + M (f - A u) with the
  * level's smoother M; zero_guess != 0 takes u = 0 on entry (the mat-vec is skipped, as on a cycle's down leg) */
 HYPRE_Int HYPRE_MI_BoomerAMGSmoothLevel(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int zero_guess,

@@ -161,8 +161,8 @@ HYPRE_Int HYPRE_ParCSRCOGMRESGetNumIterations(HYPRE_Solver solver, HYPRE_Int *nu
 HYPRE_Int HYPRE_ParCSRCOGMRESGetFinalRelativeResidualNorm(HYPRE_Solver solver, HYPRE_Real *norm);
 
 /* ILU (src/HypreSystem.cpp:328-370, :457-497): type 0 (block Jacobi) with level of fill k >= 0 -- ILU(k) of the rank's
- * diagonal block, exact (level-scheduled) or Jacobi-iterated triangular solves; other types / fill levels and the
- * iterative setup report an error at Setup */
+ * diagonal block, exact (level-scheduled) or Jacobi-iterated triangular solves; for fill 0 also the iterative setup
+ * (SetIterativeSetupType 1-4: fixed-point sweeps); other types report an error at Setup */
 HYPRE_Int HYPRE_ILUCreate(HYPRE_Solver *solver);
 HYPRE_Int HYPRE_ILUGetNumIterations(HYPRE_Solver solver, HYPRE_Int *num_iterations);
 HYPRE_Int HYPRE_ILUGetFinalRelativeResidualNorm(HYPRE_Solver solver, HYPRE_Real *norm);
