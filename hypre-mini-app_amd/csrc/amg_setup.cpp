@@ -2512,11 +2512,10 @@ void BoomerAMG::setup_device() {
     // tile of R then gathers a thinned-out stretch of the fine vector, and every line of it is fetched by several
     // tiles (4x the vector's bytes at 512^3).  R is therefore stored with its rows in the order the coarse points
     // have on the FINE level (= the coarse level's ordering before its own C-first step) and writes through a row map.
-    static const bool natural_r = !(getenv("MI_HYPRE_NATURAL_R") && atoi(getenv("MI_HYPRE_NATURAL_R")) == 0);
     const bool r_on_device = Lv.Rm && Lv.oR.nrows == Lv.Rm->nrows && Lv.Rm->host_diag_stale;  // built there
     static const long long nat_min = getenv("MI_HYPRE_NATURAL_R_MIN_NNZ") ? atoll(getenv("MI_HYPRE_NATURAL_R_MIN_NNZ")) : 4000000;
     const bool r_large_host = Lv.Rm && !Lv.Rm->host_diag_stale && Lv.Rm->diag.nnz() >= nat_min;  // e.g. distributed setup
-    if (Lv.Rm && natural_r && li + 1 < L.size() && (r_on_device || r_large_host) &&
+    if (Lv.Rm && li + 1 < L.size() && (r_on_device || r_large_host) &&
         L[li + 1].perm.size() == (size_t)Lv.Rm->nrows && Lv.Rm->nrows > 0) {
       // L[li + 1].perm: stored position -> position before the C-first step; its inverse orders the rows of R
       DVec<int> dpos(L[li + 1].perm.size());
@@ -2624,9 +2623,7 @@ void BoomerAMG::setup_device() {
     const double tc0 = wall_time();
     build_collapsed_tail();
     if (timing && collapsed_level >= 0)
-      printf("   collapsed coarse tail: levels %d.. as one %d x %d map%s, %.3f s\n", collapsed_level, collapsed_n, collapsed_n,
-             collapsed_level2 >= 0 ? (", and levels " + std::to_string(collapsed_level2) + ".. as one " +
-                                      std::to_string(collapsed_n2) + " x " + std::to_string(collapsed_n2) + " map").c_str() : "",
+      printf("   collapsed coarse tail: levels %d.. as one %d x %d map, %.3f s\n", collapsed_level, collapsed_n, collapsed_n,
              wall_time() - tc0);
   }
   is_setup = true;
@@ -2639,22 +2636,6 @@ void BoomerAMG::setup_device() {
     printf("   device arena (since the process started): %.1f GiB mapped (peak %.1f), %.1f GiB in use (peak %.1f); %lld chunks mapped, %.2f s inside "
            "hipMemCreate/Map (grow-ahead thread), requests waited %.2f s for it; %lld stream drains before a reuse, %.2f s\n",
            mp / 1073741824.0, pm / 1073741824.0, iu / 1073741824.0, pu / 1073741824.0, gr, tg, tw, dr, td);
-    printf("   block-coded column lists (tiles that keep a 4-byte list / tiles; most 1024-id blocks in a tile):");
-    for (size_t li = 0; li < L.size() && li < 6; li++) {
-      const AmgLevel &Lv = L[li];
-      if (!Lv.A->d_diag.xcache) continue;
-      auto show = [](const char *nm, const DevCSR &M) {
-        printf(" %s %d/%d (%d)%s", nm, M.ucode_wide_tiles, M.nblocks, M.ucode_max_blocks, M.ucode.p ? "" : " off");
-      };
-      printf(" L%zu[", li);
-      show("A", Lv.A->d_diag);
-      if (Lv.has_Az) show("Az", Lv.Az);
-      if (Lv.has_Ar) show("Ar", Lv.Ar);
-      if (Lv.Pm && Lv.Pm->d_diag.xcache) show("P", Lv.Pm->d_diag);
-      if (Lv.Rm && Lv.Rm->d_diag.xcache) show("R", Lv.Rm->d_diag);
-      printf("]");
-    }
-    printf("\n");
     printf("   value dictionaries (1-byte value stream):");
     for (size_t li = 0; li < L.size(); li++) {
       const AmgLevel &Lv = L[li];

@@ -333,7 +333,7 @@ bool BoomerAMG::zero_cycle_ignores_u(int level) {
   if (!enabled || my_comm().size != 1) return false;  // N > 1: the second pass sends pre-sweep (zero) values of its halo rows
   const int nlev = (int)L.size();
   AmgLevel &Lv = L[(size_t)level];
-  if (level == collapsed_level || level == collapsed_level2) return true;  // u = B f
+  if (level == collapsed_level) return true;  // u = B f
   if (level == nlev - 1) {
     if (tail) return false;
     return p.relax_type[2] == 9 && Lv.dense && p.num_sweeps[2] > 0;  // u = C^-1 f
@@ -370,13 +370,9 @@ void BoomerAMG::cycle(int level, bool u_is_zero) {
     }
   }
   if (level == 0 && collapsed_level >= 0 && collapsed_signature != cycle_signature())
-    build_collapsed_tail();  // a cycle parameter changed after Setup: the tabulated maps are of another cycle
+    build_collapsed_tail();  // a cycle parameter changed after Setup: the tabulated map is of another cycle
   AmgLevel &Lv = L[(size_t)level];
-  if (level == collapsed_level2 && u_is_zero) {  // the tabulated map of this level's whole sub-cycle
-    k::dense_matvec_t(collapsed_Bt2.p, Lv.f.p, Lv.u.p, collapsed_n2, ctx().stream);
-    return;
-  }
-  if (level == collapsed_level && u_is_zero) {
+  if (level == collapsed_level && u_is_zero) {  // the tabulated map of this level's whole sub-cycle
     k::dense_matvec_t(collapsed_Bt.p, Lv.f.p, Lv.u.p, collapsed_n, ctx().stream);
     return;
   }
@@ -517,15 +513,10 @@ std::vector<double> BoomerAMG::cycle_signature() const {
 
 void BoomerAMG::build_collapsed_tail() {
   collapsed_signature = cycle_signature();
-  collapsed_level = collapsed_level2 = -1;
-  collapsed_n = collapsed_n2 = 0;
+  collapsed_level = -1;
+  collapsed_n = 0;
   collapsed_Bt.release();
-  collapsed_Bt2.release();
   static const long long max_rows = getenv("MI_HYPRE_DENSE_TAIL_ROWS") ? atoll(getenv("MI_HYPRE_DENSE_TAIL_ROWS")) : 1024;
-  // (the second stage is an option since the end of round 4: tabulating the 4275 columns of level 7 at 512^3 costs 0.29 s of
-  // a 2.9 s setup and saves ~9 short launches per cycle, which the solve does not show -- 669.1 / 670.6 ms without against
-  // 670.0 / 672.2 ms with, alternating runs on one box)
-  static const long long max_rows2 = getenv("MI_HYPRE_DENSE_TAIL_ROWS2") ? atoll(getenv("MI_HYPRE_DENSE_TAIL_ROWS2")) : 0;
   if (max_rows <= 0 || my_comm().size != 1 || tail) return;
   const int nlev = (int)L.size();
   int lt = -1;
@@ -540,15 +531,6 @@ void BoomerAMG::build_collapsed_tail() {
   collapsed_Bt = std::move(Bt);
   collapsed_n = L[(size_t)lt].n;
   collapsed_level = lt;
-  // second stage: the level above, through the map just built (one sub-cycle = its own ~9 launches + one dense
-  // product: tabulating ~4000 columns costs a few tenths of a second; 512^3: level 7, 4303 rows, 148 MB)
-  if (lt - 1 >= 1 && L[(size_t)lt - 1].n <= max_rows2) {
-    DVec<double> Bt2;
-    tabulate_cycle(lt - 1, Bt2);
-    collapsed_Bt2 = std::move(Bt2);
-    collapsed_n2 = L[(size_t)lt - 1].n;
-    collapsed_level2 = lt - 1;
-  }
 }
 
 // the stub level's right-hand side (this rank's slice) -> whole level on every rank -> one cycle of the

@@ -1638,7 +1638,7 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCSRSize(HYPRE_Solver solver, HYPRE_Int level
   if (which == 7) {  // x cache of the level operator: tiles, 0, total unique columns over the tiles
     *nrows = L.A->d_diag.nblocks;
     *ncols = 0;
-    *nnz = (HYPRE_BigInt)(L.A->d_diag.n_unique ? L.A->d_diag.n_unique : (long long)L.A->d_diag.ucols.n);
+    *nnz = (HYPRE_BigInt)L.A->d_diag.ucols.n;
     return 0;
   }
   const ParCSR *M = nullptr;

@@ -190,9 +190,7 @@ __global__ __launch_bounds__(BLOCK) void spmv_stream_xc(int nb, int xchunk, cons
                                                              const unsigned short *__restrict__ lcol,
                                                              const double *__restrict__ x, double *__restrict__ y,
                                                              EpiArgs e, const unsigned char *__restrict__ vidx,
-                                                             const double *__restrict__ vlut,
-                                                             const unsigned short *__restrict__ ucode,
-                                                             const int *__restrict__ ubase) {
+                                                             const double *__restrict__ vlut) {
   constexpr int TILE = 8 * BLOCK;  // TILE / TILE_WIDE
   __shared__ double prod[TILE];
   __shared__ double slut[VAL8 ? 256 : 1];
@@ -232,27 +230,14 @@ __global__ __launch_bounds__(BLOCK) void spmv_stream_xc(int nb, int xchunk, cons
   }
   constexpr int NU = TILE / BLOCK;
   int uc[NU];
-  int myblock = 0;
-  const bool coded = ucode && d1.w >= 0;  // (uniform per tile) a tile with more than 64 blocks keeps a 4-byte list, in the side list
-  if (ucode && !coded) ucols += (-d1.w - 1) - u0;
-  if (coded) {  // block-coded list: 6-bit selector of one of the tile's <= 64 column blocks + 10-bit offset
-    myblock = LIST_LOAD(ubase + d1.w + (tid & 63));  // (padded: the 64 ints behind any tile's first block exist)
 #pragma unroll
-    for (int q = 0; q < NU; q++) {
-      const int k = tid + q * BLOCK;
-      uc[q] = 0;
-      if (k < nu) uc[q] = LIST_LOAD(ucode + u0 + k);
-    }
-  } else {
-#pragma unroll
-    for (int q = 0; q < NU; q++) {
-      const int k = tid + q * BLOCK;
-      // (nothing that needs the loaded id inside the branch: written as a select, the compiler put the id's 64-bit
-      // extension there and with it a wait after every load -- up to eight SERIAL round trips per tile; check the ISA
-      // when this line changes: no s_waitcnt between the list loads)
-      uc[q] = 0;
-      if (!(MI_ABLATE & 2) && k < nu) uc[q] = LIST_LOAD(ucols + u0 + k);
-    }
+  for (int q = 0; q < NU; q++) {
+    const int k = tid + q * BLOCK;
+    // (nothing that needs the loaded id inside the branch: written as a select, the compiler put the id's 64-bit
+    // extension there and with it a wait after every load -- up to eight SERIAL round trips per tile; check the ISA
+    // when this line changes: no s_waitcnt between the list loads)
+    uc[q] = 0;
+    if (!(MI_ABLATE & 2) && k < nu) uc[q] = LIST_LOAD(ucols + u0 + k);
   }
   const long long base_al64 = base64 & ~1LL;
   const int base = (int)(base64 - base_al64), base_al = 0;  // tile-local: the aligned start is 0, the first entry 0 or 1
@@ -284,10 +269,6 @@ __global__ __launch_bounds__(BLOCK) void spmv_stream_xc(int nb, int xchunk, cons
   // the gathers: ALL of them in flight before the first LDS write, and before the loads below that depend on each other.
   // (Written as `if (k < nu) xs[k] = x[uc[q]]`, every load sat in a branch of its own with its wait and its LDS write:
   // up to eight serial round trips per tile.  Lanes beyond the list read x[0] -- uc is 0 there -- one cached sector.)
-  if (coded) {  // (after the stream loads have been issued: the codes are waited for here)
-#pragma unroll
-    for (int q = 0; q < NU; q++) uc[q] = (__shfl(myblock, uc[q] >> 10, 64) << 10) | (uc[q] & 1023);
-  }
   double xv[NU];
 #pragma unroll
   for (int q = 0; q < NU; q++) xv[q] = x[(MI_ABLATE & 1) ? min(uc[q], 63) : uc[q]];
@@ -369,8 +350,7 @@ __global__ __launch_bounds__(BLOCK) void spmv_stream_xc(int nb, int xchunk, cons
 }
 
 __global__ __launch_bounds__(256) void tile_desc_k(int nb, const int *__restrict__ rb, const long long *__restrict__ ia,
-                                                   const int *__restrict__ uptr, int *__restrict__ desc,
-                                                   const long long *__restrict__ bptr) {
+                                                   const int *__restrict__ uptr, int *__restrict__ desc) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= nb) return;
   const int r0 = rb[b], r1 = rb[b + 1];
@@ -379,47 +359,7 @@ __global__ __launch_bounds__(256) void tile_desc_k(int nb, const int *__restrict
   const long long base = ia[r0], len = ia[r1] - base;
   // a single row longer than any tile (>= 2^31 entries it cannot be: such rows do not exist) keeps its true length
   d[0] = make_int4(r0, r1, (int)(unsigned)(base & 0xffffffffLL), (int)(len > 0x7fffffffLL ? 0x7fffffffLL : len));
-  d[1] = make_int4(u0, u1 - u0, (int)(base >> 32), bptr ? (int)bptr[b] : 0);  // (>= 0: coded tile; < 0: -(offset in the side list) - 1)
-}
-
-// Block-coded column lists (DevCSR::ucode / ubase): one wave per tile walks the tile's sorted unique columns in steps of
-// 64, a column opens a new block when its id >> 10 differs from its predecessor's.  FILL = false counts the blocks,
-// FILL = true writes the block numbers behind bptr[tile] and the 16-bit codes.
-template <bool FILL>
-__global__ __launch_bounds__(256) void ucode_blocks_k(int ntiles, const int *__restrict__ uptr, const int *__restrict__ ucols,
-                                                      int *__restrict__ nblk, const long long *__restrict__ bptr,
-                                                      int *__restrict__ ubase, unsigned short *__restrict__ ucode,
-                                                      int *__restrict__ maxblk, int *__restrict__ wide_list) {
-  const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (tile >= ntiles) return;
-  const int u0 = uptr[tile], u1 = uptr[tile + 1];
-  if (FILL && bptr[tile] < 0) {  // a tile with more than 64 blocks: its 4-byte list moves to the compact side list
-    const long long w0 = -bptr[tile] - 1;
-    for (int k = u0 + lane; k < u1; k += 64) wide_list[w0 + (k - u0)] = ucols[k];
-    return;
-  }
-  int run = 0, prev = -1;
-  for (int k0 = u0; k0 < u1; k0 += 64) {
-    const int k = k0 + lane;
-    const int c = k < u1 ? ucols[k] : -1;
-    const int blk = k < u1 ? (c >> 10) : -2;
-    int left = __shfl_up(blk, 1, 64);
-    if (lane == 0) left = prev;
-    const bool isnew = k < u1 && blk != left;
-    const unsigned long long m = __ballot(isnew);
-    const int sel = run + __popcll(m & ((2ull << lane) - 1ull)) - 1;  // blocks opened up to and including this lane
-    if (FILL) {
-      if (isnew) ubase[bptr[tile] + sel] = blk;
-      if (k < u1) ucode[k] = (unsigned short)(((sel & 63) << 10) | (c & 1023));
-    }
-    run += __popcll(m);
-    prev = __shfl(blk, 63, 64);
-  }
-  if (!FILL && lane == 0) {
-    nblk[tile] = run;
-    atomicMax(maxblk, run);
-  }
+  d[1] = make_int4(u0, u1 - u0, (int)(base >> 32), 0);
 }
 
 // compressed-row off-diagonal block: one lane per stored row (halo rows are few
@@ -489,10 +429,10 @@ __global__ __launch_bounds__(GS_BLOCK) void gs_hybrid_k(int n, int chunk0, int n
 }
 
 // ---------------------------------------------------------------------------
-// Hybrid Gauss-Seidel, cooperative form (the one that runs when chunk == 8).
-// A group of LPC lanes (8/16/32/64, chosen from the level's mean row length)
-// owns one chunk of R = 8 consecutive rows; a wave holds 64/LPC chunks, so for
-// the 7-point fine level the wave's 64 lanes read 64 consecutive rows' entries.
+// Hybrid Gauss-Seidel, cooperative form (chunk == 8, mean row length <= 8).
+// A group of LPC = 8 lanes owns one chunk of R = 8 consecutive rows; a wave
+// holds 64/LPC chunks, so for the 7-point fine level the wave's 64 lanes read
+// 64 consecutive rows' entries.
 //   phase A  every row of the chunk is loaded up front: lane g takes entries
 //            g, g+LPC, ... of each row (adjacent lanes -> adjacent addresses),
 //            and gathers u_old for the columns outside the chunk.  Nothing in
@@ -870,9 +810,7 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void gs_tile_k(int blk0, int n
                                                         int row_begin, int row_end, int zero_from,
                                                         double *__restrict__ tout, int t_from,
                                                         const unsigned char *__restrict__ vidx,
-                                                        const double *__restrict__ vlut,
-                                                        const unsigned short *__restrict__ ucode,
-                                                        const int *__restrict__ ubase) {
+                                                        const double *__restrict__ vlut) {
 #define UOLD(j) (((j) < split ? u_lo : u_hi)[(j)])
   constexpr int TILE = 8 * BLOCK;        // TILE / TILE_WIDE
   __shared__ double buf[TILE];           // x cache, then products / in-chunk coefficients
@@ -900,18 +838,7 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void gs_tile_k(int blk0, int n
   const bool all_zero = zero_from <= 0;
   constexpr int NU = TILE / BLOCK;
   int ucid[NU];
-  int myblock = 0;
-  const bool coded = ucode && d1.w >= 0;  // (uniform per tile, see spmv_stream_xc)
-  if (ucode && !coded) ucols += (-d1.w - 1) - u0;
-  if (!all_zero && coded) {
-    myblock = LIST_LOAD(ubase + d1.w + (tid & 63));
-#pragma unroll
-    for (int q = 0; q < NU; q++) {
-      const int k = tid + q * BLOCK;
-      ucid[q] = 0;
-      if (k < nu) ucid[q] = LIST_LOAD(ucode + u0 + k);
-    }
-  } else if (!all_zero) {
+  if (!all_zero) {
 #pragma unroll
     for (int q = 0; q < NU; q++) {
       const int k = tid + q * BLOCK;
@@ -950,10 +877,6 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void gs_tile_k(int blk0, int n
   // batches -- the first covers tiles of up to 4 * BLOCK unique columns, i.e. nearly all of them.
   constexpr int GB = VAL8 ? NU : NU / 2;
   double xv[GB];
-  if (!all_zero && coded) {
-#pragma unroll
-    for (int q = 0; q < NU; q++) ucid[q] = (__shfl(myblock, ucid[q] >> 10, 64) << 10) | (ucid[q] & 1023);
-  }
   if (!all_zero) {
 #pragma unroll
     for (int q = 0; q < GB; q++) {
@@ -1611,13 +1534,6 @@ inline int vec_grid(int n) {
 // tile Gauss-Seidel kernel needs; *chunk_aligned says whether that held for the whole matrix.
 int choose_tile_entries(int64_t nnz, int nrows) {
   static const double wide_min = getenv("MI_HYPRE_WIDE_TILE_MIN_ROWLEN") ? atof(getenv("MI_HYPRE_WIDE_TILE_MIN_ROWLEN")) : 100.0;
-  // very short rows (the fine level's zero-guess sub-operator: 3.5 entries per row) leave a 256-row tile half empty:
-  // MI_HYPRE_WIDE_TILE_MAX_SHORT = x gives operators with at most x entries per row the 512-row tiles too (experiment)
-  static const double short_max = getenv("MI_HYPRE_WIDE_TILE_MAX_SHORT") ? atof(getenv("MI_HYPRE_WIDE_TILE_MAX_SHORT")) : 0.0;
-  // (only operators that get the x-cache format: the plain stream kernel has 2048-entry tiles only)
-  static const int xc_min = getenv("MI_HYPRE_XCACHE_MIN") ? atoi(getenv("MI_HYPRE_XCACHE_MIN")) : 3;
-  if (nrows > 0 && short_max > 0.0 && (double)nnz / (double)nrows <= short_max && (double)nnz / (double)nrows >= (double)xc_min)
-    return SPMV_TILE_WIDE;
   return (nrows > 0 && wide_min > 0.0 && (double)nnz / (double)nrows >= wide_min) ? SPMV_TILE_WIDE : SPMV_TILE;
 }
 
@@ -1655,22 +1571,6 @@ static bool gs_tile_mode(const DevCSR &A) {
   static const double thr = getenv("MI_HYPRE_GS_TILE_AVG") ? atof(getenv("MI_HYPRE_GS_TILE_AVG")) : 5.0;
   return (double)A.nnz / (double)std::max(1, A.nrows) > thr;
 }
-static bool gs_use_old() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("MI_HYPRE_GS_OLD");
-    v = (e && atoi(e)) ? 1 : 0;
-  }
-  return v == 1;
-}
-static bool gs_force_generic() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("MI_HYPRE_GS_GENERIC");
-    v = (e && atoi(e)) ? 1 : 0;
-  }
-  return v == 1;
-}
 
 // returns the name of the instantiation it launched (as rocprofv3's kernel statistics spell it)
 static const char *launch_stream(int epi, const DevCSR &A, const double *x, double *y, const EpiArgs &e, hipStream_t s,
@@ -1686,7 +1586,7 @@ static const char *launch_stream(int epi, const DevCSR &A, const double *x, doub
 #define XC_LAUNCH_W(EPI_, V8_)                                                                                       \
   name = "spmv_stream_xc<" #EPI_ ", 0, " #V8_ ", 512>";                                                              \
   hipLaunchKernelGGL((spmv_stream_xc<EPI_, 0, V8_, SPMV_BLOCK_WIDE>), grid, wide, 0, s, nb, xchunk, A.tdesc.p, A.ia.p, \
-                     A.ja.p, A.a.p, A.ucols.p, A.lcol.p, x, y, e, A.vidx.p, A.vlut.p, A.ucode.p, A.ubase.p)
+                     A.ja.p, A.a.p, A.ucols.p, A.lcol.p, x, y, e, A.vidx.p, A.vlut.p)
     if (A.val8) {
       if (epi == 0) {
         XC_LAUNCH_W(0, true);
@@ -1705,7 +1605,7 @@ static const char *launch_stream(int epi, const DevCSR &A, const double *x, doub
 #define XC_LAUNCH(EPI_, TAG_, V8_)                                                                                  \
   name = "spmv_stream_xc<" #EPI_ ", " #TAG_ ", " #V8_ ", 256>";                                                       \
   hipLaunchKernelGGL((spmv_stream_xc<EPI_, TAG_, V8_, SPMV_BLOCK>), grid, block, 0, s, nb, xchunk, A.tdesc.p, A.ia.p, A.ja.p, \
-                     A.a.p, A.ucols.p, A.lcol.p, x, y, e, A.vidx.p, A.vlut.p, A.ucode.p, A.ubase.p)
+                     A.a.p, A.ucols.p, A.lcol.p, x, y, e, A.vidx.p, A.vlut.p)
     if (A.val8) {
       if (epi == 0 && level0) {
         XC_LAUNCH(0, 1, true);
@@ -1825,67 +1725,14 @@ void build_value_dictionary(DevCSR &A, hipStream_t s) {
   A.val8 = true;
 }
 
-// block-coded column lists of an x-cache operator (DevCSR::ucode / ubase) from its 4-byte lists (MI_HYPRE_UCODE=0: keep
-// those).  Per tile: at most 64 blocks of 1024 ids -> coded, bptr[tile] = start of its blocks in ubase; more (tiles at the
-// seams of the internal numbering's cells and segments: a few per cent at 512^3) -> the tile keeps a 4-byte list, moved to a
-// compact side list (A.ucols afterwards), bptr[tile] = -(its offset there) - 1.
-static void build_block_coded_lists(DevCSR &A, DVec<long long> &bptr, hipStream_t s) {
-  A.ucode.release();
-  A.ubase.release();
-  A.n_unique = (long long)A.ucols.n;
-  A.ucode_max_blocks = 0;
-  A.ucode_wide_tiles = 0;
-  // OFF by default: measured at 512^3 (profiles/r04_ab_block_coded_lists.txt) the decode -- a wave-wide block table and one
-  // ds_bpermute per column between the list load and the gather -- costs the tile Gauss-Seidel kernel and the residual SpMVs
-  // of levels 1-2 more (+3..12 %) than the 2 bytes per unique column save; only the level-0 dictionary SpMV gains (-5 %)
-  static const bool on = getenv("MI_HYPRE_UCODE") && atoi(getenv("MI_HYPRE_UCODE")) != 0;
-  if (!on || !A.xcache || A.nblocks <= 0 || !A.uptr.p || A.ucols.n == 0) return;
-  const int nt = A.nblocks;
-  DVec<int> nblk((size_t)nt), maxblk(1);
-  MI_HIP(hipMemsetAsync(maxblk.p, 0, sizeof(int), s));
-  const dim3 grid((unsigned)((nt + 3) / 4));
-  hipLaunchKernelGGL(ucode_blocks_k<false>, grid, dim3(256), 0, s, nt, A.uptr.p, A.ucols.p, nblk.p, nullptr, nullptr, nullptr, maxblk.p, nullptr);
-  MI_HIP(hipGetLastError());
-  MI_HIP(hipStreamSynchronize(s));  // (DVec::to_host copies on the null stream, which does not wait for this one)
-  const std::vector<int> hn = nblk.to_host();   // (tiles: at most a few hundred thousand; through the pinned staging buffer)
-  const std::vector<int> hu = A.uptr.to_host();
-  std::vector<long long> hp((size_t)nt + 1, 0);
-  long long nb_tot = 0, wide_tot = 0;
-  for (int t = 0; t < nt; t++) {
-    A.ucode_max_blocks = std::max(A.ucode_max_blocks, hn[(size_t)t]);
-    if (hn[(size_t)t] <= 64) {
-      hp[(size_t)t] = nb_tot;
-      nb_tot += hn[(size_t)t];
-    } else {
-      hp[(size_t)t] = -wide_tot - 1;
-      wide_tot += hu[(size_t)t + 1] - hu[(size_t)t];
-      A.ucode_wide_tiles++;
-    }
-  }
-  if (wide_tot * 2 > (long long)A.ucols.n) return;  // mostly wide tiles: not worth two formats -- the 4-byte lists stay
-  bptr.alloc((size_t)nt + 1);
-  MI_HIP(hipMemcpyAsync(bptr.p, hp.data(), ((size_t)nt + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
-  MI_HIP(hipStreamSynchronize(s));
-  A.ubase.alloc((size_t)nb_tot, 64);  // (a wave loads 64 ints from a tile's first block on: padded)
-  MI_HIP(hipMemsetAsync(A.ubase.p, 0, ((size_t)nb_tot + 64) * sizeof(int), s));
-  A.ucode.alloc(A.ucols.n);
-  DVec<int> wide((size_t)wide_tot);
-  hipLaunchKernelGGL(ucode_blocks_k<true>, grid, dim3(256), 0, s, nt, A.uptr.p, A.ucols.p, nullptr, bptr.p, A.ubase.p, A.ucode.p, nullptr, wide.p);
-  MI_HIP(hipGetLastError());
-  MI_HIP(hipStreamSynchronize(s));
-  A.ucols = std::move(wide);  // what is left of the 4-byte lists: the wide tiles'
-}
-
 void build_tile_desc(DevCSR &A, const long long *ia64, hipStream_t s) {
   A.tdesc.release();
   if (A.nblocks <= 0 || !A.rb.p) return;
-  DVec<long long> bptr;
-  build_block_coded_lists(A, bptr, s);
   A.tdesc.alloc((size_t)A.nblocks * 8);
   hipLaunchKernelGGL(tile_desc_k, dim3((unsigned)((A.nblocks + 255) / 256)), dim3(256), 0, s, A.nblocks, A.rb.p, ia64,
-                     A.xcache ? A.uptr.p : nullptr, A.tdesc.p, A.ucode.p ? bptr.p : nullptr);
+                     A.xcache ? A.uptr.p : nullptr, A.tdesc.p);
   MI_HIP(hipGetLastError());
-  MI_HIP(hipStreamSynchronize(s));  // (bptr goes away)
+  MI_HIP(hipStreamSynchronize(s));
   build_value_dictionary(A, s);
 }
 
@@ -1931,15 +1778,15 @@ void spmv_offd_set(const DevOffd &B, const double *xext, double *out, hipStream_
 }
 
 bool gs_uses_tiles(const DevCSR &A, int chunk) {
-  return chunk == 8 && A.gs_tiles && A.xcache && gs_tile_mode(A) && !gs_force_generic() && !gs_use_old();
+  return chunk == 8 && A.gs_tiles && A.xcache && gs_tile_mode(A);
 }
 
-// whether a sweep of A with zero_from == 0 never reads the pre-sweep vector (the tile kernel and the shuffle kernel
-// skip every gather and take 0 for the rows' own values; the dense-chunk and the generic kernel read real zeros)
+// whether a sweep of A with zero_from == 0 never reads the pre-sweep vector (gs_tile_k and gs_group_k skip every
+// gather and take 0 for the rows' own values; gs_dense_k and gs_hybrid_k, for chunk != 8, read real zeros)
 bool gs_ignores_zero_vector(const DevCSR &A, int chunk) {
   if (A.nrows == 0) return false;
   if (gs_uses_tiles(A, chunk)) return true;
-  if (chunk != 8 || gs_force_generic()) return false;
+  if (chunk != 8) return false;
   return (double)A.nnz / (double)A.nrows <= 8.0;  // gs_group_k (see the dispatch in gs_hybrid)
 }
 
@@ -1967,7 +1814,7 @@ void gs_hybrid(const DevCSR &A, const double *u_lo, const double *u_hi, int spli
   hipLaunchKernelGGL((gs_tile_k<V8_, BLOCK_>), dim3((unsigned)(b1 - b0)), dim3(BLOCK_), 0, s, b0, b1 - b0, A.tdesc.p, \
                      A.ia.p, A.a.p, A.ucols.p, A.lcol.p, cf, points, d, f, offc, u_lo, u_hi, split, out, fwd ? 1 : 0,  \
                      bwd ? 1 : 0, w, first_row, last_row, zero_from, tout, t_from, V8_ ? A.vidx.p : nullptr,          \
-                     V8_ ? A.vlut.p : nullptr, A.ucode.p, A.ubase.p)
+                     V8_ ? A.vlut.p : nullptr)
     const bool wide = A.tile_entries == SPMV_TILE_WIDE;
     if (b1 > b0 && A.val8 && wide) {
       GS_TILE_LAUNCH(true, SPMV_BLOCK_WIDE);
@@ -1979,7 +1826,7 @@ void gs_hybrid(const DevCSR &A, const double *u_lo, const double *u_hi, int spli
       GS_TILE_LAUNCH(false, SPMV_BLOCK);
     }
 #undef GS_TILE_LAUNCH
-  } else if (chunk == 8 && !gs_force_generic()) {
+  } else if (chunk == 8) {
     MI_REQUIRE(!A.big(), "an operator with 2^31 entries or more is swept by the tile Gauss-Seidel kernel only");
     prof_name(prof, "gs_group_k / gs_dense_k (chunk kernels)");
     const double avg = (double)A.nnz / (double)A.nrows;
@@ -1991,8 +1838,6 @@ void gs_hybrid(const DevCSR &A, const double *u_lo, const double *u_hi, int spli
                        (int)c1, A.ia.p, A.ja.p, A.a.p, cf, points, d, f, offc, u_lo, u_hi, split, out,          \
                        fwd ? 1 : 0, bwd ? 1 : 0, w, zero_from);                                                 \
   }
-#define GS_LAUNCH(LPC, E) \
-  if (gs_use_old()) GS_LAUNCH_K(gs_group_k, LPC, E) else GS_LAUNCH_K(gs_dense_k, LPC, E)
     // Measured per level (256^3 / 512^3 Laplacian hierarchies, profiles/compare_gs.*):
     //   mean row length <= 8 (the fine level): the shuffle kernel with 8 lanes per chunk is memory-bound
     //   already (3.9 TB/s) and beats the dense-chunk kernel, whose barriers and LDS block it does not need;
@@ -2001,18 +1846,15 @@ void gs_hybrid(const DevCSR &A, const double *u_lo, const double *u_hi, int spli
     if (avg <= 8.0) {
       if (p95 <= 8) GS_LAUNCH_K(gs_group_k, 8, 1) else GS_LAUNCH_K(gs_group_k, 8, 2)
     } else if (avg <= 16.0) {
-      if (p95 <= 16) GS_LAUNCH(16, 1) else GS_LAUNCH(16, 2)
+      if (p95 <= 16) GS_LAUNCH_K(gs_dense_k, 16, 1) else GS_LAUNCH_K(gs_dense_k, 16, 2)
     } else if (avg <= 32.0) {
-      if (gs_use_old()) {
-        if (p95 <= 32) GS_LAUNCH_K(gs_group_k, 32, 1) else GS_LAUNCH_K(gs_group_k, 64, 1)
-      } else {
-        if (p95 <= 64) GS_LAUNCH_K(gs_dense_k, 32, 1) else GS_LAUNCH_K(gs_dense_k, 32, 2)
-      }
+      if (p95 <= 64) GS_LAUNCH_K(gs_dense_k, 32, 1) else GS_LAUNCH_K(gs_dense_k, 32, 2)
     } else {
-      if (p95 <= 64) GS_LAUNCH(64, 1) else if (p95 <= 128) GS_LAUNCH(64, 2) else GS_LAUNCH(64, 4)
+      if (p95 <= 64) GS_LAUNCH_K(gs_dense_k, 64, 1)
+      else if (p95 <= 128) GS_LAUNCH_K(gs_dense_k, 64, 2)
+      else GS_LAUNCH_K(gs_dense_k, 64, 4)
     }
 #undef GS_LAUNCH_K
-#undef GS_LAUNCH
   } else {
     MI_REQUIRE(!A.big(), "an operator with 2^31 entries or more is swept by the tile Gauss-Seidel kernel only");
     const size_t lds = (size_t)chunk * GS_BLOCK * sizeof(double);

@@ -160,14 +160,13 @@ __global__ __launch_bounds__(BLK) void split_rows_k(int nlist, const int *__rest
 }
 
 // ---------------------------------------------------------------- SpGEMM, one group of G lanes per row
+// Symbolic phase: nout[row] = the row's distinct columns.
 // S = lanes that share one row of B during the hash phase (power of two <= G)
-template <int G, int CAP, bool NUMERIC>
+template <int G, int CAP>
 __global__ __launch_bounds__(BLK) void spgemm_group_k(int nlist, const int *__restrict__ rows, int S,
                                                       const long long *__restrict__ Aia, const int *__restrict__ Aja,
-                                                      const double *__restrict__ Aa, const long long *__restrict__ Bia,
-                                                      const int *__restrict__ Bja, const double *__restrict__ Ba,
-                                                      int *__restrict__ nout, const long long *__restrict__ Cia,
-                                                      int *__restrict__ Cja, double *__restrict__ Ca) {
+                                                      const long long *__restrict__ Bia, const int *__restrict__ Bja,
+                                                      int *__restrict__ nout) {
   constexpr int H = 2 * CAP;
   constexpr int LOGH = (H == 64) ? 6 : (H == 256) ? 8 : 10;
   static_assert(H == 64 || H == 256 || H == 1024, "table size");
@@ -182,10 +181,8 @@ __global__ __launch_bounds__(BLK) void spgemm_group_k(int nlist, const int *__re
   for (int t = lane; t < H; t += G) tab[g][t] = EMPTY;
   if (lane == 0) cnt[g] = 0;
   group_sync<G>();
-  long long a0 = 0, a1 = 0;
   if (active) {
-    a0 = Aia[row];
-    a1 = Aia[row + 1];
+    const long long a0 = Aia[row], a1 = Aia[row + 1];
     const int sub = lane / S, sl = lane % S, nsub = G / S;
     for (long long ka = a0 + sub; ka < a1; ka += nsub) {
       const int kr = Aja[ka];
@@ -198,27 +195,15 @@ __global__ __launch_bounds__(BLK) void spgemm_group_k(int nlist, const int *__re
   }
   group_sync<G>();
   if (!active) return;
-  const int no = cnt[g];
-  if (!NUMERIC) {
-    if (lane == 0) nout[row] = no;
-    return;
-  }
-  const long long c0 = Cia[row];
-  for (int r = lane; r < no; r += G) {
-    const int j = list[g][r];
-    int rank = 0;
-    for (int t = 0; t < no; t++) rank += (list[g][t] < j);
-    Cja[c0 + rank] = j;
-    Ca[c0 + rank] = row_dot(a0, a1, Aja, Aa, Bia, Bja, Ba, j);
-  }
+  if (lane == 0) nout[row] = cnt[g];
 }
 
-// Numeric phase of the same product (round 4).  spgemm_group_k<.,.,true> finds every entry of C by its own walk over
-// A's row with a binary search in each row of B: (entries of C) x (entries of A's row) x log(row of B) dependent loads --
-// 13 x the products of a Galerkin row.  Here the group walks A's row ONCE, in stored order, one entry per step; the G
-// lanes take the entries of that row of B (distinct columns), and each adds its product to the column's slot of an
-// LDS hash table: first product assigned, the rest added, in the order of A's row -- the order of the host loop and of
-// row_dot, so the sums are the same bits.  Steps are separated by wave_lds_sync (a step's slot may be the next step's).
+// Numeric phase of the same product.  Finding every entry of C by its own walk over A's row with a binary search in
+// each row of B costs (entries of C) x (entries of A's row) x log(row of B) dependent loads -- 13 x the products of a
+// Galerkin row.  Here the group walks A's row ONCE, in stored order, one entry per step; the G lanes take the entries
+// of that row of B (distinct columns), and each adds its product to the column's slot of an LDS hash table: first
+// product assigned, the rest added, in the order of A's row -- the order of the host loop and of row_dot, so the sums
+// are the same bits.  Steps are separated by wave_lds_sync (a step's slot may be the next step's).
 template <int G, int CAP>
 __global__ __launch_bounds__(BLK) void spgemm_accum_k(int nlist, const int *__restrict__ rows,
                                                       const long long *__restrict__ Aia, const int *__restrict__ Aja,
@@ -1977,12 +1962,7 @@ void launch_bins(const Bins &bins, const int *rows, const int *T, int S_hint, co
                  hipStream_t s) {
   const int n0 = bins.start[1] - bins.start[0], n1 = bins.start[2] - bins.start[1], n2 = bins.start[3] - bins.start[2],
             n3 = bins.start[4] - bins.start[3];
-  // MI_HYPRE_SPGEMM_ACCUM=0: the numeric phase by per-entry search (spgemm_group_k<.,.,true>), as before round 4
-  static const bool accum = [] {
-    const char *e = getenv("MI_HYPRE_SPGEMM_ACCUM");
-    return !(e && atoi(e) == 0);
-  }();
-  if (NUMERIC && accum) {
+  if (NUMERIC) {
     // the bins bound a row's PRODUCTS; its table only has to hold its distinct columns, which the symbolic pass has counted
     // (a Galerkin row of the 7-point benchmark: 377 products, 30 columns): rows whose count fits the next smaller table
     // take it -- 15 instead of 60 KB of LDS per workgroup, four times the rows in flight
@@ -2040,19 +2020,19 @@ void launch_bins(const Bins &bins, const int *rows, const int *T, int S_hint, co
     MI_HIP(hipStreamSynchronize(s));  // `part` is released on return
   } else {
     if (n0)
-      spgemm_group_k<8, 32, NUMERIC><<<grid_for(((long long)n0 + 31) / 32), BLK, 0, s>>>(
-          n0, rows + bins.start[0], std::min(S_hint, 8), A.ia.p, A.ja.p, A.a.p, B.ia.p, B.ja.p, B.a.p, nout, Cia, Cja, Ca);
+      spgemm_group_k<8, 32><<<grid_for(((long long)n0 + 31) / 32), BLK, 0, s>>>(
+          n0, rows + bins.start[0], std::min(S_hint, 8), A.ia.p, A.ja.p, B.ia.p, B.ja.p, nout);
     if (n1)
-      spgemm_group_k<16, 128, NUMERIC><<<grid_for(((long long)n1 + 15) / 16), BLK, 0, s>>>(
-          n1, rows + bins.start[1], std::min(S_hint, 16), A.ia.p, A.ja.p, A.a.p, B.ia.p, B.ja.p, B.a.p, nout, Cia, Cja, Ca);
+      spgemm_group_k<16, 128><<<grid_for(((long long)n1 + 15) / 16), BLK, 0, s>>>(
+          n1, rows + bins.start[1], std::min(S_hint, 16), A.ia.p, A.ja.p, B.ia.p, B.ja.p, nout);
     if (n2)
-      spgemm_group_k<64, 512, NUMERIC><<<grid_for(((long long)n2 + 3) / 4), BLK, 0, s>>>(
-          n2, rows + bins.start[2], std::min(S_hint, 64), A.ia.p, A.ja.p, A.a.p, B.ia.p, B.ja.p, B.a.p, nout, Cia, Cja, Ca);
+      spgemm_group_k<64, 512><<<grid_for(((long long)n2 + 3) / 4), BLK, 0, s>>>(
+          n2, rows + bins.start[2], std::min(S_hint, 64), A.ia.p, A.ja.p, B.ia.p, B.ja.p, nout);
+    if (n3)
+      spgemm_block_k<false><<<(unsigned)std::min(n3, block_grid), BLK, 0, s>>>(
+          n3, rows + bins.start[3], T, B.ncols, S_hint, gscratch, scratch_per_block, A.ia.p, A.ja.p, A.a.p, B.ia.p,
+          B.ja.p, B.a.p, nout, Cia, Cja, Ca);
   }
-  if (n3 && !(NUMERIC && accum))
-    spgemm_block_k<NUMERIC><<<(unsigned)std::min(n3, block_grid), BLK, 0, s>>>(
-        n3, rows + bins.start[3], T, B.ncols, S_hint, gscratch, scratch_per_block, A.ia.p, A.ja.p, A.a.p, B.ia.p,
-        B.ja.p, B.a.p, nout, Cia, Cja, Ca);
   MI_HIP(hipGetLastError());
 }
 }  // namespace
@@ -2694,31 +2674,24 @@ bool interp(const DCsr &A, const DCsr &S, DVec<int> &cf, int interp_type, double
   }
   if (n1) {
     // bound 33 ... 128: first with 32-entry tables (a quarter of the LDS, four times the rows in flight); the rows that do
-    // not fit come back marked and go through the tables sized by the bound.  MI_HYPRE_INTERP_TRY=0: all of them there.
-    static const bool try_small = !(getenv("MI_HYPRE_INTERP_TRY") && atoi(getenv("MI_HYPRE_INTERP_TRY")) == 0);
-    const int *big = rows.p + bins.start[1];
-    int nbig = n1;
-    DVec<int> part1;
-    if (try_small) {
-      static_assert(16 <= 32, "CAP + G keys must stay below the 2 CAP slots of the table");
-      interp_group_k<16, 32, 256, true><<<grid_for(((long long)n1 + 15) / 16), 256, 0, s>>>(
-          n1, rows.p + bins.start[1], ext, A.ia.p, A.ja.p, A.a.p, S.ia.p, S.ja.p, cf.p, f2c.p, trunc_factor, pmax,
-          slack_ia.p, sj.p, sa.p, len.p);
-      part1.alloc((size_t)2 * (size_t)n1 + 2);
-      int *cnt1 = part1.p + 2 * (size_t)n1;
-      int h1[2] = {0, 0};
-      MI_HIP(hipMemsetAsync(cnt1, 0, 2 * sizeof(int), s));
-      split_rows_k<<<grid_for(((long long)n1 + BLK - 1) / BLK), BLK, 0, s>>>(n1, rows.p + bins.start[1], len.p, -1, part1.p,
-                                                                           part1.p + n1, cnt1);
-      d2h(h1, cnt1, sizeof(h1), s);
-      MI_HIP(hipStreamSynchronize(s));
-      big = part1.p;  // the rows marked -1
-      nbig = h1[0];
-    }
+    // not fit come back marked and go through the tables sized by the bound.
+    static_assert(16 <= 32, "CAP + G keys must stay below the 2 CAP slots of the table");
+    interp_group_k<16, 32, 256, true><<<grid_for(((long long)n1 + 15) / 16), 256, 0, s>>>(
+        n1, rows.p + bins.start[1], ext, A.ia.p, A.ja.p, A.a.p, S.ia.p, S.ja.p, cf.p, f2c.p, trunc_factor, pmax,
+        slack_ia.p, sj.p, sa.p, len.p);
+    DVec<int> part1((size_t)2 * (size_t)n1 + 2);
+    int *cnt1 = part1.p + 2 * (size_t)n1;
+    int h1[2] = {0, 0};
+    MI_HIP(hipMemsetAsync(cnt1, 0, 2 * sizeof(int), s));
+    split_rows_k<<<grid_for(((long long)n1 + BLK - 1) / BLK), BLK, 0, s>>>(n1, rows.p + bins.start[1], len.p, -1, part1.p,
+                                                                         part1.p + n1, cnt1);
+    d2h(h1, cnt1, sizeof(h1), s);
+    MI_HIP(hipStreamSynchronize(s));
+    const int nbig = h1[0];  // the rows marked -1, at the front of part1
     if (nbig)
       interp_group_k<16, 128, 128><<<grid_for(((long long)nbig + 7) / 8), 128, 0, s>>>(
-          nbig, big, ext, A.ia.p, A.ja.p, A.a.p, S.ia.p, S.ja.p, cf.p, f2c.p, trunc_factor, pmax, slack_ia.p, sj.p, sa.p,
-          len.p);
+          nbig, part1.p, ext, A.ia.p, A.ja.p, A.a.p, S.ia.p, S.ja.p, cf.p, f2c.p, trunc_factor, pmax, slack_ia.p, sj.p,
+          sa.p, len.p);
     MI_HIP(hipGetLastError());
     MI_HIP(hipStreamSynchronize(s));  // part1 is released at the end of this block
   }

@@ -1,5 +1,5 @@
 #!/bin/bash
-# kernel-trace of the 256^3 run for a list of env settings:  bash profiles/compare_gs.sh "MI_HYPRE_GS_OLD=1" "MI_HYPRE_GS_OLD=0" ...
+# kernel-trace of the 256^3 run for a list of env settings:  bash profiles/compare_gs.sh "MI_HYPRE_GS_TILE=0" "MI_HYPRE_GS_TILE=1" ...
 cd "${GRAFT_REPO_ROOT:-.}"
 REPO=$(pwd)
 export TMPDIR=/tmp
