@@ -228,6 +228,8 @@ struct BoomerAMG {
   void relax(int level, int type, int points, const double *f, bool u_is_zero = false);
   void relax_pair(int level, int type, int first, const double *f, bool u_is_zero = false);
   void relax_sweeps(int level, int which, const double *f, bool u_is_zero = false);
+  // host-side census of the tile Gauss-Seidel kernel's sweep branches for one pass of relax / relax_pair
+  bool gs_sweep_paths(int level, int points, bool u_is_zero, long long counts[5]);
   void cycle(int level, bool u_is_zero = false);
   // complex smoothers of the levels < p.smooth_num_levels (end of setup_device); fsai_signature: the FSAI and
   // iterative-ILU parameters they were built with -- a change after Setup rebuilds them before the next cycle

@@ -276,6 +276,25 @@ void BoomerAMG::relax_pair(int level, int type, int first, const double *f, bool
   std::swap(Lv.u.p, Lv.snap.p);  // snap now holds every row
 }
 
+// Which branches of the tile kernel's sweep phase the waves of one hybrid-GS pass take (k::gs_tile_path_census), for
+// the launch relax() makes (points 0: every row) or relax_pair() makes for a C-then-F pair (points +1: its C pass,
+// -1: its F pass, which on a zero guess reads zeros from row nc on).  One rank; false: not on the tile kernel.
+bool BoomerAMG::gs_sweep_paths(int level, int points, bool u_is_zero, long long counts[5]) {
+  AmgLevel &Lv = L[(size_t)level];
+  ensure_host(level);
+  const HostCSR &H = Lv.A->diag;
+  const bool has_cf = Lv.has_cf && !Lv.cf.empty();
+  if (!has_cf) points = 0;
+  const int ch = chunk();
+  const bool zs = u_is_zero && zero_skip_mode() > 0;
+  const bool use_Az = zs && Lv.has_Az && Lv.Az_chunk == ch;
+  const int row_begin = (points == -1) ? Lv.nc : 0;
+  const int row_end = (points == 1) ? Lv.nc : Lv.n;
+  const int zero_from = !zs ? k::GS_NO_ZEROS : (points == -1) ? Lv.nc : 0;
+  return k::gs_tile_path_census(use_Az ? Lv.Az : Lv.A->d_diag, ch, H.ia.data(), H.ja.data(),
+                                has_cf ? Lv.cf.host().data() : nullptr, points, row_begin, row_end, zero_from, counts);
+}
+
 // which: 0 down, 1 up, 2 coarsest.  relax_order 1: C then F going down, F then
 // C going up, all points on the coarsest level (hypre_BoomerAMGRelaxIF)
 void BoomerAMG::relax_sweeps(int level, int which, const double *f, bool u_is_zero) {

@@ -1749,6 +1749,42 @@ HYPRE_Int HYPRE_MI_BoomerAMGRelaxLevel(HYPRE_Solver solver, HYPRE_Int level, HYP
   if (n) d2h(u_host, Lv.u.p, (size_t)n * sizeof(double), nullptr);
   API_END
 }
+HYPRE_Int HYPRE_MI_BoomerAMGRelaxPairLevel(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int relax_type, HYPRE_Int first,
+                                           HYPRE_Int zero_guess, const HYPRE_Real *f_host, HYPRE_Real *u_host) {
+  API_BEGIN
+  AmgSolver *a = AMG(solver);
+  if (!a->amg.is_setup) fail(HYPRE_ERROR_GENERIC, "RelaxPairLevel: AMG is not set up");
+  if (level < 0 || level >= (int)a->amg.L.size()) fail(HYPRE_ERROR_ARG, "AMG level out of range");
+  if (first != 1 && first != -1) fail(HYPRE_ERROR_ARG, "RelaxPairLevel: first is +1 (C then F) or -1 (F then C)");
+  AmgLevel &Lv = a->amg.L[(size_t)level];
+  const int n = Lv.n;
+  DVec<double> f((size_t)n);
+  if (n) {
+    f.upload(f_host, (size_t)n);
+    MI_HIP(hipStreamSynchronize(ctx().stream));
+    if (zero_guess)
+      MI_HIP(hipMemset(Lv.u.p, 0, (size_t)n * sizeof(double)));
+    else
+      MI_HIP(hipMemcpy(Lv.u.p, u_host, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+  }
+  a->amg.relax_pair(level, relax_type, first, f.p, zero_guess != 0);
+  MI_HIP(hipStreamSynchronize(ctx().stream));
+  if (n) d2h(u_host, Lv.u.p, (size_t)n * sizeof(double), nullptr);
+  API_END
+}
+HYPRE_Int HYPRE_MI_BoomerAMGGetGSSweepPaths(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int points, HYPRE_Int zero_guess,
+                                            HYPRE_Int *on_tiles, HYPRE_BigInt *counts) {
+  API_BEGIN
+  AmgSolver *a = AMG(solver);
+  if (!a->amg.is_setup) fail(HYPRE_ERROR_GENERIC, "GetGSSweepPaths: AMG is not set up");
+  if (level < 0 || level >= (int)a->amg.L.size()) fail(HYPRE_ERROR_ARG, "AMG level out of range");
+  if (points < -1 || points > 1) fail(HYPRE_ERROR_ARG, "GetGSSweepPaths: points is 0, +1 or -1");
+  long long c[5];
+  const bool tiles = a->amg.gs_sweep_paths(level, points, zero_guess != 0, c);
+  if (on_tiles) *on_tiles = tiles ? 1 : 0;
+  for (int q = 0; q < 5; q++) counts[q] = c[q];
+  API_END
+}
 static FsaiSolver *level_fsai_or_null(HYPRE_Solver solver, int level) {
   AmgSolver *a = AMG(solver);
   if (!a->amg.is_setup) fail(HYPRE_ERROR_GENERIC, "GetLevelFSAI: AMG is not set up");

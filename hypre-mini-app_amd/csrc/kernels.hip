@@ -785,6 +785,107 @@ __global__ __launch_bounds__(256) void gs_dense_k(int n, int chunk0, int nchunks
 
 
 // ---------------------------------------------------------------------------
+// The dense 8x8 in-chunk sweep of gs_tile_k: crow[] = the lane's row of the chunk's block, uc[] = the lane's copy of
+// the chunk's eight values (filled here), myu = the row's value before / after.
+// The phase is VALU throughput (profiles/r04_ablation_tile_kernels.txt: 16 steps x (8 double FMAs + update + cross-lane
+// read) on every wave = a quarter of a pass).  Every lane forms ITS row's sum at every step although only row t's is
+// used at step t; what can be shared without touching the order of the additions (S, then columns 0..7 ascending):
+// * forward, rows above t already hold their new values when row t's turn comes, and they are the FIRST terms of its
+//   sum: `acc` = S + the terms of the columns swept so far is carried along (one FMA per step), step t adds the 8 - t
+//   remaining terms to a copy of it -- 44 instead of 64 FMAs.  (Backward the new values are the LAST terms; the prefix
+//   over the old ones has a different length in every lane, and masking it costs what it saves: all 8 terms there.)
+// * the row's own value at its step is uc[t] (the lane's copy of the chunk's values), so `myu` need not follow the
+//   sweep: it is picked out of uc[] once at the end instead of a select per step.
+// Same operations on the same operands for the row whose turn it is; the other lanes' results were never used.
+// zero_tile (uniform in the workgroup): every value of the chunk is 0 before the sweep.  The values are then not
+// fetched from the other lanes, and in the forward sweep the terms over the columns not yet swept (j >= t) are
+// products with 0: step t needs the carried `acc` alone -- 8 instead of 44 FMAs.  A backward sweep that follows (or
+// comes alone) is the general one.
+// A step reads lane gbase + t * LPR (below 64).  The byte address for ds_bpermute_b32 is formed at the step, one add of
+// a scalar to the lane's 4 * gbase: held in registers through both sweeps, the eight addresses cost 8 VGPRs that the
+// kernel does not have, and the compiler would otherwise hold them (the empty asm keeps the add where it is used).
+__device__ __forceinline__ double gs_lane_read(const double v, const int gbase4, int off4) {
+  asm volatile("" : "+s"(off4));
+  const int lo = __builtin_amdgcn_ds_bpermute(gbase4 + off4, __double2loint(v));
+  const int hi = __builtin_amdgcn_ds_bpermute(gbase4 + off4, __double2hiint(v));
+  return __hiloint2double(hi, lo);
+}
+
+__device__ __forceinline__ void gs_tile_sweep(const double (&crow)[8], double (&uc)[8], double &myu, const double S,
+                                              const double myrhs, const double wd, const int g, const int gbase,
+                                              const int LPR, const int fwd, const int bwd, const bool zero_tile) {
+#if !defined(MI_GS_SHARED_PREFIX) || MI_GS_SHARED_PREFIX
+  const int gbase4 = 4 * gbase;
+  int LPR4 = 4 * LPR;  // one of four constants selected by the tile's row count: as a plain number, t * LPR4 is one scalar op
+  asm volatile("" : "+s"(LPR4));
+  if (zero_tile) {
+#pragma unroll
+    for (int j = 0; j < 8; j++) uc[j] = 0.0;
+    if (fwd) {
+      double acc = S;
+#pragma unroll
+      for (int t = 0; t < 8; t++) {
+        const double nu2 = 0.0 + (myrhs - acc) * wd;  // unselected rows: wd == 0
+        const double b = gs_lane_read(nu2, gbase4, t * LPR4);
+        uc[t] = b;
+        acc += crow[t] * b;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; j++) uc[j] = gs_lane_read(myu, gbase4, j * LPR4);
+    if (fwd) {
+      double acc = S;
+#pragma unroll
+      for (int t = 0; t < 8; t++) {
+        double sacc = acc;
+#pragma unroll
+        for (int j = t; j < 8; j++) sacc += crow[j] * uc[j];
+        const double nu2 = uc[t] + (myrhs - sacc) * wd;  // unselected rows: wd == 0
+        const double b = gs_lane_read(nu2, gbase4, t * LPR4);
+        uc[t] = b;
+        acc += crow[t] * b;
+      }
+    }
+  }
+  if (bwd) {
+#pragma unroll
+    for (int tt = 0; tt < 8; tt++) {
+      const int t = 7 - tt;
+      double sacc = S;
+#pragma unroll
+      for (int j = 0; j < 8; j++) sacc += crow[j] * uc[j];
+      const double nu2 = uc[t] + (myrhs - sacc) * wd;
+      uc[t] = gs_lane_read(nu2, gbase4, t * LPR4);
+    }
+  }
+  if (fwd || bwd) {
+#pragma unroll
+    for (int j = 0; j < 8; j++) myu = (g == j) ? uc[j] : myu;
+  }
+#else
+  // the sweep before the shared prefix (A/B timing): every step forms the full sum; no zero-tile path
+#pragma unroll
+  for (int j = 0; j < 8; j++) uc[j] = __shfl(myu, gbase + j * LPR, 64);
+#pragma unroll
+  for (int dir = 0; dir < 2; dir++) {
+    if (dir == 0 ? !fwd : !bwd) continue;
+#pragma unroll
+    for (int tt = 0; tt < 8; tt++) {
+      const int t = (dir == 0) ? tt : 7 - tt;
+      double sacc = S;
+#pragma unroll
+      for (int j = 0; j < 8; j++) sacc += crow[j] * uc[j];
+      const double nu2 = myu + (myrhs - sacc) * wd;  // unselected rows: wd == 0
+      const double b = __shfl(nu2, gbase + t * LPR, 64);
+      uc[t] = b;
+      if (g == t) myu = b;
+    }
+  }
+#endif
+}
+
+// ---------------------------------------------------------------------------
 // Hybrid Gauss-Seidel on the SpMV tiles (levels with an x cache).
 //
 // The chunk kernels above read the matrix row by row and gather u through L1;
@@ -982,78 +1083,47 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void gs_tile_k(int blk0, int n
   // follows needs from those columns (BoomerAMG::cycle)
   // (f is read again here rather than kept in two registers through the kernel: 66 -> 64 VGPRs = 8 waves per SIMD)
   if (tout && rowsel && sub == 0 && i >= t_from) tout[i] = f[i] - S;
-  double crow[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) {
-    const bool has = (inmask >> j) & 1u;
-    const int pos = kin + __popc(inmask & ((1u << j) - 1u));
-    crow[j] = has ? buf[has ? pos : 0] : 0.0;
-  }
   // the sweep: a chunk = 8 rows = 8 * LPR consecutive lanes (tiles start on a multiple of 8 rows)
   const int lane = tid & 63;
   const int g = (lane / LPR) & 7;
   const int gbase = lane & ~(8 * LPR - 1);
-  double uc[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) uc[j] = __shfl(myu, gbase + j * LPR, 64);
-  // The phase is VALU throughput (profiles/r04_ablation_tile_kernels.txt: 16 steps x (8 double FMAs + update + cross-lane
-  // read) on every wave = a quarter of a pass).  Every lane forms ITS row's sum at every step although only row t's is
-  // used at step t; what can be shared without touching the order of the additions (S, then columns 0..7 ascending):
-  // * forward, rows above t already hold their new values when row t's turn comes, and they are the FIRST terms of its
-  //   sum: `acc` = S + the terms of the columns swept so far is carried along (one FMA per step), step t adds the 8 - t
-  //   remaining terms to a copy of it -- 44 instead of 64 FMAs.  (Backward the new values are the LAST terms; the prefix
-  //   over the old ones has a different length in every lane, and masking it costs what it saves: all 8 terms there.)
-  // * the row's own value at its step is uc[t] (the lane's copy of the chunk's values), so `myu` need not follow the
-  //   sweep: it is picked out of uc[] once at the end instead of a select per step.
-  // Same operations on the same operands for the row whose turn it is; the other lanes' results were never used.
-#if !defined(MI_GS_SHARED_PREFIX) || MI_GS_SHARED_PREFIX
-  if (!(MI_ABLATE & 8)) {
-    if (fwd) {
-      double acc = S;
-#pragma unroll
-      for (int t = 0; t < 8; t++) {
-        double sacc = acc;
-#pragma unroll
-        for (int j = t; j < 8; j++) sacc += crow[j] * uc[j];
-        const double nu2 = uc[t] + (myrhs - sacc) * wd;  // unselected rows: wd == 0
-        const double b = __shfl(nu2, gbase + t * LPR, 64);
-        uc[t] = b;
-        acc += crow[t] * b;
-      }
-    }
-    if (bwd) {
-#pragma unroll
-      for (int tt = 0; tt < 8; tt++) {
-        const int t = 7 - tt;
-        double sacc = S;
-#pragma unroll
-        for (int j = 0; j < 8; j++) sacc += crow[j] * uc[j];
-        const double nu2 = uc[t] + (myrhs - sacc) * wd;
-        uc[t] = __shfl(nu2, gbase + t * LPR, 64);
-      }
-    }
-    if (fwd || bwd) {
-#pragma unroll
-      for (int j = 0; j < 8; j++) myu = (g == j) ? uc[j] : myu;
-    }
-  }
-#else
-#pragma unroll
-  for (int dir = 0; dir < 2; dir++) {
-    if ((MI_ABLATE & 8) || (dir == 0 ? !fwd : !bwd)) continue;
-#pragma unroll
-    for (int tt = 0; tt < 8; tt++) {
-      const int t = (dir == 0) ? tt : 7 - tt;
-      double sacc = S;
-#pragma unroll
-      for (int j = 0; j < 8; j++) sacc += crow[j] * uc[j];
-      const double nu2 = myu + (myrhs - sacc) * wd;  // unselected rows: wd == 0
-      const double b = __shfl(nu2, gbase + t * LPR, 64);
-      uc[t] = b;
-      if (g == t) myu = b;
-    }
-  }
+  // Three cases in which the 16-step sweep below would only multiply structural zeros are taken out of it, each by a
+  // branch that is uniform in the wave (ballots) or in the tile (zero_tile), so no lane diverges inside a sweep.  None
+  // changes the order or the operands of an addition that reaches a result: what is left out are terms c * 0 and
+  // 0 * u (for finite data at most the sign of an exact zero can differ).  -DMI_GS_SWEEP_PATHS=<bits> selects them
+  // (1: zero-guess tiles, 2: diagonal chunks, 4: idle waves; 0 = every wave runs the general sweep) for A/B timing.
+#ifndef MI_GS_SWEEP_PATHS
+#define MI_GS_SWEEP_PATHS 7
 #endif
+  // * no row of the wave is selected (LPR * nr <= 192, the last tile of a pass, a tile of the other colour's rows):
+  //   every lane has wd == 0, the sweep would hand every row its old value back
+  const bool wave_idle = (MI_GS_SWEEP_PATHS & 4) && __ballot(rowsel) == 0;
+  // * no row of the wave has an in-chunk entry besides its diagonal (the C rows of a level on which all connections
+  //   are strong: PMIS C points are an independent set): no row reads another row's new value, so every row's step is
+  //   u += wd * (rhs - (S + a_ii u)) at once, the expression the sweep evaluates for row g at step g
+  const bool wave_diag = (MI_GS_SWEEP_PATHS & 2) && __ballot((inmask & ~(1u << g)) != 0u) == 0;
+  // * every row of the tile starts from 0 (first sweep on a zero guess: the whole C pass, the F pass but for the tile
+  //   that straddles zero_from): the chunk's values need not be fetched, and the forward sum over the columns not yet
+  //   swept is a sum of products with 0
+  const bool zero_tile = (MI_GS_SWEEP_PATHS & 1) && r0 >= zero_from;
+  if (wave_idle || (MI_ABLATE & 8)) {
+    // nothing to sweep: myu is the row's value
+  } else if (wave_diag) {
+    const bool has = (inmask >> g) & 1u;
+    const double cd = has ? buf[has ? kin : 0] : 0.0;
+    if (fwd) myu = myu + (myrhs - (S + cd * myu)) * wd;  // unselected rows: wd == 0
+    if (bwd) myu = myu + (myrhs - (S + cd * myu)) * wd;
+  } else {
+    double crow[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const bool has = (inmask >> j) & 1u;
+      const int pos = kin + __popc(inmask & ((1u << j) - 1u));
+      crow[j] = has ? buf[has ? pos : 0] : 0.0;
+    }
+    double uc[8];
+    gs_tile_sweep(crow, uc, myu, S, myrhs, wd, g, gbase, LPR, fwd, bwd, zero_tile);
+  }
   if (rl < nr && sub == 0) u_new[i] = myu;
 #undef UOLD
 }
@@ -1790,6 +1860,50 @@ bool gs_ignores_zero_vector(const DevCSR &A, int chunk) {
   return (double)A.nnz / (double)A.nrows <= 8.0;  // gs_group_k (see the dispatch in gs_hybrid)
 }
 
+// the tile kernel's launch for the rows [row_begin, row_end): the chunks [c0, c1) that intersect them are rows
+// [first_row, last_row); they lie in the tiles [b0, b1) -- first tile with rb[b+1] > c0*8, last tile with rb[b] < c1*8
+static void gs_tile_range(const DevCSR &A, int row_begin, int row_end, int &first_row, int &last_row, int &b0, int &b1) {
+  const long long c0 = row_begin / 8;
+  const long long c1 = ((long long)row_end + 7) / 8;
+  const std::vector<int> &rbh = A.rb_host;
+  first_row = (int)(c0 * 8);
+  last_row = (int)std::min<long long>(c1 * 8, A.nrows);
+  b0 = (int)(std::upper_bound(rbh.begin(), rbh.end(), first_row) - rbh.begin()) - 1;
+  b1 = (int)(std::lower_bound(rbh.begin(), rbh.end(), last_row) - rbh.begin());
+}
+
+// Host-side census of the branches gs_tile_k's sweep phase takes in one pass (tests, and the per-level shares in
+// DESIGN.md section 5): the same launch geometry and the same three predicates, evaluated on a host copy of the
+// operator's pattern (ia / ja: any operator with A's in-chunk entries, e.g. the level operator for its zero-guess
+// sub-operator; cf: +1 / -1 per row or null).  counts: waves launched, waves without a selected row, waves whose
+// chunks couple to nothing in-chunk but their own diagonal, zero-guess waves on the short forward sweep, waves on the
+// general sweep.  false: the pass does not run on the tile kernel.
+bool gs_tile_path_census(const DevCSR &A, int chunk, const int64_t *ia, const int *ja, const int *cf, int points,
+                         int row_begin, int row_end, int zero_from, long long counts[5]) {
+  for (int q = 0; q < 5; q++) counts[q] = 0;
+  if (A.nrows == 0 || row_end <= row_begin || !gs_uses_tiles(A, chunk)) return false;
+  int first_row, last_row, b0, b1;
+  gs_tile_range(A, row_begin, row_end, first_row, last_row, b0, b1);
+  const int block = A.tile_entries == SPMV_TILE_WIDE ? SPMV_BLOCK_WIDE : SPMV_BLOCK;
+  for (int b = b0; b < b1; b++) {
+    const int r0 = A.rb_host[(size_t)b], nr = A.rb_host[(size_t)b + 1] - r0;
+    const int LPR = nr <= block / 8 ? 8 : nr <= block / 4 ? 4 : nr <= block / 2 ? 2 : 1;
+    for (int wv = 0; wv < block / 64; wv++) {
+      bool any = false, coupled = false;
+      for (int rl = wv * 64 / LPR; rl < std::min((wv + 1) * 64 / LPR, nr); rl++) {
+        const int i = r0 + rl;
+        const int mark = (points != 0 && cf != nullptr) ? cf[i] : points;
+        if (mark != points || i < first_row || i >= last_row) continue;
+        any = true;
+        for (int64_t q = ia[i]; q < ia[i + 1]; q++) coupled |= (ja[q] >> 3) == (i >> 3) && ja[q] != i;
+      }
+      counts[0]++;
+      counts[!any ? 1 : !coupled ? 2 : r0 >= zero_from ? 3 : 4]++;
+    }
+  }
+  return true;
+}
+
 void gs_hybrid(const DevCSR &A, const double *u_lo, const double *u_hi, int split, double *out, const double *f,
                const double *offc, const double *d, const signed char *cf, int points, int chunk, bool fwd, bool bwd,
                double w, int row_begin, int row_end, hipStream_t s, int prof, int zero_from, double *tout,
@@ -1803,11 +1917,8 @@ void gs_hybrid(const DevCSR &A, const double *u_lo, const double *u_hi, int spli
   const long long nch = c1 - c0;
   prof_begin(prof, s);
   if (gs_uses_tiles(A, chunk)) {
-    // tiles that hold the chunks [c0, c1): first tile with rb[b+1] > c0*8, last tile with rb[b] < c1*8
-    const std::vector<int> &rbh = A.rb_host;
-    const int first_row = (int)(c0 * 8), last_row = (int)std::min<long long>(c1 * 8, A.nrows);
-    const int b0 = (int)(std::upper_bound(rbh.begin(), rbh.end(), first_row) - rbh.begin()) - 1;
-    const int b1 = (int)(std::lower_bound(rbh.begin(), rbh.end(), last_row) - rbh.begin());
+    int first_row, last_row, b0, b1;
+    gs_tile_range(A, row_begin, row_end, first_row, last_row, b0, b1);
 #define GS_TILE_LAUNCH(V8_, BLOCK_)                                                                                  \
   prof_name(prof, V8_ ? (BLOCK_ == 512 ? "gs_tile_k<true, 512>" : "gs_tile_k<true, 256>")                             \
                       : (BLOCK_ == 512 ? "gs_tile_k<false, 512>" : "gs_tile_k<false, 256>"));                         \

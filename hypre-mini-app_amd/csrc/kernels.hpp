@@ -159,6 +159,9 @@ void gs_hybrid(const DevCSR &A, const double *u_lo, const double *u_hi, int spli
                double *tout = nullptr, int t_from = 0);
 // tout (tile kernel only -- check gs_uses_tiles): every swept row i >= t_from also stores f[i] minus its
 // out-of-chunk sum there
+// which branches of the tile kernel's sweep phase the waves of such a pass take, counted on the host (kernels.hip)
+bool gs_tile_path_census(const DevCSR &A, int chunk, const int64_t *ia, const int *ja, const int *cf, int points,
+                         int row_begin, int row_end, int zero_from, long long counts[5]);
 
 // BLAS-1
 void dot(const double *x, const double *y, int n, double *out_dev, hipStream_t s);  // local sum, no collective

@@ -381,6 +381,24 @@ class BoomerAMG:
         call("HYPRE_MI_BoomerAMGRelaxLevel", self.h, level, relax_type, points, f, u)
         return u
 
+    def relax_pair_level(self, level, relax_type, first, f, u=None):
+        """A C/F pair of hybrid-GS passes of the level on host arrays (first +1: C then F); u None = zero guess."""
+        f = dbl(f)
+        zero = u is None
+        u = np.zeros_like(f) if zero else np.array(u, dtype=np.float64)
+        call("HYPRE_MI_BoomerAMGRelaxPairLevel", self.h, level, relax_type, first, 1 if zero else 0, f, u)
+        return u
+
+    def gs_sweep_paths(self, level, points, zero_guess=False):
+        """Host-side census of the tile GS kernel's sweep branches for one pass: None when the pass does not run on
+        the tile kernel, else dict(waves, idle, diagonal, zero, general)."""
+        on = c_int()
+        counts = np.zeros(5, dtype=np.int64)
+        call("HYPRE_MI_BoomerAMGGetGSSweepPaths", self.h, level, points, 1 if zero_guess else 0, C.byref(on), counts)
+        if not on.value:
+            return None
+        return dict(zip(("waves", "idle", "diagonal", "zero", "general"), (int(c) for c in counts)))
+
     def set_fsai(self, **kw):
         """Change FSAI smoother parameters (fsai_* keys of the constructor), also after setup."""
         names = {"fsai_algo_type": ("HYPRE_BoomerAMGSetFSAIAlgoType", int),

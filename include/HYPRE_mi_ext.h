@@ -157,6 +157,17 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetLevelOffdColMap(HYPRE_Solver solver, HYPRE_Int le
 /* one relaxation call / one cycle on HOST arrays of the level's local length */
 HYPRE_Int HYPRE_MI_BoomerAMGRelaxLevel(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int relax_type, HYPRE_Int points,
                                        const HYPRE_Real *f_host, HYPRE_Real *u_host);
+/* a C/F pair of hybrid Gauss-Seidel passes on HOST arrays, as a cycle runs them (first +1: C then F, -1: F then C);
+ * zero_guess != 0 takes u = 0 on entry (u_host is then output only) and sweeps as the first sweep of a down leg does */
+HYPRE_Int HYPRE_MI_BoomerAMGRelaxPairLevel(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int relax_type, HYPRE_Int first,
+                                           HYPRE_Int zero_guess, const HYPRE_Real *f_host, HYPRE_Real *u_host);
+/* which branch of the tile Gauss-Seidel kernel's in-chunk sweep the waves of one pass take, counted on the host from
+ * the level's pattern (points 0: an all-point pass; +1 / -1: the C / F pass of a C-then-F pair; zero_guess: the first
+ * sweep on a zero guess).  counts[5]: waves launched, waves without a selected row (no sweep), waves whose chunks
+ * couple to nothing in-chunk but their diagonals (one update per row), zero-guess waves (short forward sweep), waves
+ * on the general sweep.  *on_tiles = 0 (and all counts 0) when the pass does not run on the tile kernel. */
+HYPRE_Int HYPRE_MI_BoomerAMGGetGSSweepPaths(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int points, HYPRE_Int zero_guess,
+                                            HYPRE_Int *on_tiles, HYPRE_BigInt *counts);
 /* FSAI smoother of a level (smooth_type 4, levels < smooth_num_levels): its G as CSR in GetLevelCSR's numbering (the
  * rows and columns of the level's diag block), and omega.  Size: 0 x 0 and nnz 0 when the level has none */
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelFSAISize(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int *nrows, HYPRE_BigInt *nnz);
