@@ -28,6 +28,11 @@ struct AmgParams {
   int gs_chunk = 0;  // 0 => runtime default (ctx().gs_chunk)
   int agg_num_levels = 0, agg_interp_type = 4, agg_pmax_elmts = 0, keep_transpose = 0, rap2 = 0;
   double agg_trunc_factor = 0.0;
+  // agg_interp_type 5 (two-stage extended interpolation): truncation of the two stage operators P1 and P2; 0 = none
+  int agg_p12_max_elmts = 0;
+  double agg_p12_trunc_factor = 0.0;
+  // test hook (HYPRE_MI_BoomerAMGSetKeepAggMarkers): keep both stage markers of such levels for the inspection getter
+  int keep_agg_markers = 0;
   int smooth_num_sweeps = 1;
   // complex smoother on levels < smooth_num_levels (src/HypreSystem.cpp:235-320): 5 = ILU (block-Jacobi ILU(k), the
   // IluSolver behind HYPRE_ILU) and 4 = FSAI (static pattern, the FsaiSolver behind HYPRE_FSAI) are implemented; library
@@ -102,6 +107,10 @@ struct AmgLevel {
   bool halo_rows_ready = false;
   std::vector<InteriorRange> interior_cache;
   LazyInts cf;  // +1 C, -1 F (empty on the coarsest level)
+  // aggressive level with the two-stage interpolation (agg_interp_type 5): the markers after the first coarsening and
+  // after the second one (+1 C, -1 F, -3 special F), natural order of the level; kept only when
+  // AmgParams::keep_agg_markers asks for them (inspection)
+  std::vector<signed char> agg_m1, agg_m2;
   bool has_cf = false;  // the level has a C/F splitting -- a GLOBAL fact (cf itself is empty on a rank without rows)
   DVec<signed char> d_cf;
   // C-first ordering of this level: perm[new] = old local row;

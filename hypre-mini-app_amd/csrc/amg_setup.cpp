@@ -683,9 +683,11 @@ void second_strength(int n, const Strength &S, const std::vector<int> &cf, Stren
 }
 
 // aggressive coarsening of one level (par_amg_setup.c, level < agg_num_levels; src/HypreSystem.cpp:215-219):
-// coarsen with S, coarsen the C points again with the second-generation graph, keep what survives both
-void coarsen_aggressive(int type, int n, const Strength &S, std::vector<int> &cf) {
+// coarsen with S, coarsen the C points again with the second-generation graph, keep what survives both.
+// stage1 (optional): the marker after the first coarsening -- the two-stage interpolation's C1
+void coarsen_aggressive(int type, int n, const Strength &S, std::vector<int> &cf, std::vector<int> *stage1 = nullptr) {
   coarsen_by_type(type, n, S, cf);
+  if (stage1) *stage1 = cf;
   Strength S2;
   int nc = 0;
   second_strength(n, S, cf, S2, nc);
@@ -851,6 +853,194 @@ void build_multipass(const ParCSR &A, const Strength &S, std::vector<int> &cf, d
   });
   for (int i = 0; i < n; i++)
     if (cf[(size_t)i] == SF_PT) cf[(size_t)i] = F_PT;
+}
+
+// Extended interpolation E(A, S, m) of the two-stage interpolation ("Two-stage extended
+// interpolation"), in matrix-matrix form: numerators N = Lo * M by host_spgemm, then w_ij = -n_ij / d_i, then the
+// truncation.  rows (optional): build these rows only (the C1 rows of the second stage); columns: C points of m in
+// fine order.  Every row is one thread's, every sum runs in stored order.
+static void two_stage_ext_operands(const HostCSR &D, const Strength &S, const std::vector<int> &m,
+                                   const std::vector<int> *rows, HostCSR &Lo, HostCSR &M, std::vector<double> &d,
+                                   int &nc_out) {
+  const int n = D.nrows;
+  std::vector<int> f2c((size_t)n, -1);
+  int nc = 0;
+  for (int i = 0; i < n; i++)
+    if (m[(size_t)i] == C_PT) f2c[(size_t)i] = nc++;
+  nc_out = nc;
+  // beta_k = sum of a_kl over the strong C neighbours of k, and the length of M's row k
+  std::vector<double> beta((size_t)n, 0.0);
+  std::vector<int> mlen((size_t)n, 0);
+  parallel_for(n, [&](int64_t b, int64_t e, int) {
+    for (int64_t k = b; k < e; k++) {
+      if (m[(size_t)k] == C_PT) {
+        mlen[(size_t)k] = 1;
+        continue;
+      }
+      double bk = 0.0;
+      int cnt = 0;
+      int64_t ks = S.ia[(size_t)k];
+      const int64_t kse = S.ia[(size_t)k + 1];
+      for (int64_t q = D.ia[(size_t)k]; q < D.ia[(size_t)k + 1] && ks < kse; q++) {
+        const int l = D.ja[(size_t)q];
+        while (ks < kse && S.ja[(size_t)ks] < l) ks++;
+        if (ks < kse && S.ja[(size_t)ks] == l && m[(size_t)l] == C_PT) {
+          bk += D.a[(size_t)q];
+          cnt++;
+        }
+      }
+      beta[(size_t)k] = bk;
+      mlen[(size_t)k] = bk != 0.0 ? cnt : 0;
+    }
+  });
+  M.nrows = n;
+  M.ncols = nc;
+  M.ia.assign((size_t)n + 1, 0);
+  for (int k = 0; k < n; k++) M.ia[(size_t)k + 1] = M.ia[(size_t)k] + mlen[(size_t)k];
+  M.ja.resize((size_t)M.nnz());
+  M.a.resize((size_t)M.nnz());
+  parallel_for(n, [&](int64_t b, int64_t e, int) {
+    for (int64_t k = b; k < e; k++) {
+      int64_t w = M.ia[(size_t)k];
+      if (m[(size_t)k] == C_PT) {
+        M.ja[(size_t)w] = f2c[(size_t)k];
+        M.a[(size_t)w] = 1.0;
+        continue;
+      }
+      if (!mlen[(size_t)k]) continue;
+      int64_t ks = S.ia[(size_t)k];
+      const int64_t kse = S.ia[(size_t)k + 1];
+      for (int64_t q = D.ia[(size_t)k]; q < D.ia[(size_t)k + 1] && ks < kse; q++) {
+        const int l = D.ja[(size_t)q];
+        while (ks < kse && S.ja[(size_t)ks] < l) ks++;
+        if (ks < kse && S.ja[(size_t)ks] == l && m[(size_t)l] == C_PT) {
+          M.ja[(size_t)w] = f2c[(size_t)l];
+          M.a[(size_t)w] = D.a[(size_t)q] / beta[(size_t)k];
+          w++;
+        }
+      }
+    }
+  });
+  // left operand: C row -> (i, 1) (the unit row comes out of the product as 1 * 1), F row -> its strong entries,
+  // special F row -> nothing; d_i of the F rows
+  const int nr = rows ? (int)rows->size() : n;
+  Lo.nrows = nr;
+  Lo.ncols = n;
+  Lo.ia.assign((size_t)nr + 1, 0);
+  for (int r = 0; r < nr; r++) {
+    const int i = rows ? (*rows)[(size_t)r] : r;
+    const int64_t len = m[(size_t)i] == C_PT ? 1 : m[(size_t)i] == F_PT ? S.ia[(size_t)i + 1] - S.ia[(size_t)i] : 0;
+    Lo.ia[(size_t)r + 1] = Lo.ia[(size_t)r] + len;
+  }
+  Lo.ja.resize((size_t)Lo.nnz());
+  Lo.a.resize((size_t)Lo.nnz());
+  d.assign((size_t)nr, 0.0);
+  parallel_for(nr, [&](int64_t b, int64_t e, int) {
+    for (int64_t r = b; r < e; r++) {
+      const int i = rows ? (*rows)[(size_t)r] : (int)r;
+      int64_t w = Lo.ia[(size_t)r];
+      if (m[(size_t)i] == C_PT) {
+        Lo.ja[(size_t)w] = i;
+        Lo.a[(size_t)w] = 1.0;
+        continue;
+      }
+      if (m[(size_t)i] != F_PT) continue;
+      double di = 0.0;
+      int64_t ks = S.ia[(size_t)i];
+      const int64_t kse = S.ia[(size_t)i + 1];
+      for (int64_t q = D.ia[(size_t)i]; q < D.ia[(size_t)i + 1]; q++) {
+        const int j = D.ja[(size_t)q];
+        while (ks < kse && S.ja[(size_t)ks] < j) ks++;
+        const bool strong = ks < kse && S.ja[(size_t)ks] == j;
+        if (strong) {
+          Lo.ja[(size_t)w] = j;
+          Lo.a[(size_t)w] = D.a[(size_t)q];
+          w++;
+          if (m[(size_t)j] != C_PT && beta[(size_t)j] == 0.0) di += D.a[(size_t)q];
+        } else
+          di += D.a[(size_t)q];  // the diagonal and the weak entries
+      }
+      d[(size_t)r] = di;
+    }
+  });
+}
+
+void two_stage_zero_denominator(int level, int row) {
+  fail(4, "BoomerAMGSetup: two-stage extended interpolation (agg_interp_type 5) on level " + std::to_string(level) +
+              ": row " + std::to_string(row) + " has a zero denominator d_i with a non-empty numerator");
+}
+
+// rows of N in place: F rows become w = -n / d, then every row is truncated; compacted into P
+static void two_stage_finish_rows(HostCSR &N, const std::vector<int> *rows, const std::vector<int> *m,
+                                  const std::vector<double> *d, double trunc_factor, int pmax, int level, HostCSR &P) {
+  const int nr = N.nrows;
+  std::vector<int> flen((size_t)nr, 0);
+  std::atomic<int> bad{-1};
+  parallel_for(nr, [&](int64_t b, int64_t e, int) {
+    std::vector<char> keep;
+    for (int64_t r = b; r < e; r++) {
+      const int64_t s0 = N.ia[(size_t)r];
+      int len = (int)(N.ia[(size_t)r + 1] - s0);
+      if (len == 0) continue;
+      if (m) {
+        const int i = rows ? (*rows)[(size_t)r] : (int)r;
+        if ((*m)[(size_t)i] == F_PT) {
+          const double di = (*d)[(size_t)r];
+          if (di == 0.0) {
+            int seen = bad.load();
+            while ((seen < 0 || i < seen) && !bad.compare_exchange_weak(seen, i)) {
+            }
+            continue;
+          }
+          for (int k = 0; k < len; k++) N.a[(size_t)(s0 + k)] = -N.a[(size_t)(s0 + k)] / di;
+        }
+      }
+      if (trunc_factor > 0.0 || pmax > 0)
+        len = truncate_row(len, N.ja.data() + s0, N.a.data() + s0, trunc_factor, pmax, keep);
+      flen[(size_t)r] = len;
+    }
+  });
+  if (bad.load() >= 0) two_stage_zero_denominator(level, bad.load());
+  P.nrows = nr;
+  P.ncols = N.ncols;
+  P.ia.assign((size_t)nr + 1, 0);
+  for (int r = 0; r < nr; r++) P.ia[(size_t)r + 1] = P.ia[(size_t)r] + flen[(size_t)r];
+  P.ja.resize((size_t)P.nnz());
+  P.a.resize((size_t)P.nnz());
+  parallel_for(nr, [&](int64_t b, int64_t e, int) {
+    for (int64_t r = b; r < e; r++) {
+      if (!flen[(size_t)r]) continue;
+      memcpy(P.ja.data() + P.ia[(size_t)r], N.ja.data() + N.ia[(size_t)r], (size_t)flen[(size_t)r] * sizeof(int));
+      memcpy(P.a.data() + P.ia[(size_t)r], N.a.data() + N.ia[(size_t)r], (size_t)flen[(size_t)r] * sizeof(double));
+    }
+  });
+}
+
+// Two-stage extended interpolation of an aggressive level (agg_interp_type 5; Yang 2010, in the matrix-matrix form of
+// Li, Sjogreen, Yang 2021): P = P1 * P2 with P1 = E(A, S, m1) (n x |C1|) and P2 = the C1 rows of E(A, S, m2)
+// (|C1| x |C2|); P1 and P2 truncated by the P12 parameters, P by the aggressive ones.  m2 is handed on as multipass
+// hands it on (special F -> F).
+void build_two_stage_ext(const ParCSR &A, const Strength &S, const std::vector<int> &m1, std::vector<int> &m2,
+                         double p12_trunc_factor, int p12_max, double trunc_factor, int pmax, int level, HostCSR &P,
+                         int &nc_out) {
+  const HostCSR &D = A.diag;
+  const int n = D.nrows;
+  std::vector<int> c1;
+  for (int i = 0; i < n; i++)
+    if (m1[(size_t)i] == C_PT) c1.push_back(i);
+  HostCSR Lo, M, N, P1, P2;
+  std::vector<double> d;
+  int nc1 = 0;
+  two_stage_ext_operands(D, S, m1, nullptr, Lo, M, d, nc1);
+  host_spgemm(Lo, M, N);
+  two_stage_finish_rows(N, nullptr, &m1, &d, p12_trunc_factor, p12_max, level, P1);
+  two_stage_ext_operands(D, S, m2, &c1, Lo, M, d, nc_out);
+  host_spgemm(Lo, M, N);
+  two_stage_finish_rows(N, &c1, &m2, &d, p12_trunc_factor, p12_max, level, P2);
+  host_spgemm(P1, P2, N);
+  two_stage_finish_rows(N, nullptr, nullptr, nullptr, trunc_factor, pmax, level, P);
+  for (int i = 0; i < n; i++)
+    if (m2[(size_t)i] == SF_PT) m2[(size_t)i] = F_PT;
 }
 
 void dense_inverse(int n, std::vector<double> &M, std::vector<double> &inv) {
@@ -1594,9 +1784,9 @@ void BoomerAMG::setup_host(ParCSR &A0) {
   if (!coarsen_type_restated(p.coarsen_type))
     fail(4, "BoomerAMGSetup: coarsen_type " + std::to_string(p.coarsen_type) +
                 " is not implemented (8 PMIS, 10 HMIS, 11, 6 Falgout, 1, 3, 0 CLJP, 7 are); refusing to substitute another one");
-  if (p.agg_num_levels > 0 && p.agg_interp_type != 4)
+  if (p.agg_num_levels > 0 && p.agg_interp_type != 4 && p.agg_interp_type != 5)
     fail(4, "BoomerAMGSetup: agg_interp_type " + std::to_string(p.agg_interp_type) +
-                " is not implemented (4 = multipass is); refusing to substitute another one");
+                " is not implemented (4 = multipass and 5 = two-stage extended are); refusing to substitute another one");
   for (int k = 0; k < 3; k++) {
     const int t = p.relax_type[k];
     const bool known = t == 0 || t == 7 || t == 18 || t == 3 || t == 4 || t == 6 || t == 8 || t == 13 || t == 14 ||
@@ -1778,11 +1968,15 @@ void BoomerAMG::build_natural(ParCSR &A0) {
     // aggressive coarsening (level < agg_num_levels) and the Ruge-Stueben family are host algorithms: on a level
     // the device builds, the strength graph still comes from the device and the Galerkin product stays there
     const bool aggressive = l < p.agg_num_levels;
-    const bool host_coarsen = aggressive || (p.coarsen_type != 8 && p.coarsen_type != 9);
+    // (with the two-stage interpolation, agg_interp_type 5, and PMIS the aggressive level stays on the device: second
+    // graph, second PMIS, marker correction and the interpolation's sparse products)
+    const bool two_stage = aggressive && p.agg_interp_type == 5;
+    const bool pmis_type = p.coarsen_type == 8 || p.coarsen_type == 9;
+    const bool host_coarsen = (aggressive && !(two_stage && pmis_type)) || !pmis_type;
     Strength S;
-    std::vector<int> cf;
+    std::vector<int> cf, cf1;  // cf1: the marker after the first coarsening of an aggressive level (two-stage interpolation)
     sk::DCsr dS;
-    DVec<int> dcf;
+    DVec<int> dcf, dcf1;  // dcf1: the first coarsening's marker on the device (two-stage interpolation)
     const std::string lname = "level " + std::to_string(l) + ": ";
     std::unique_ptr<TraceRange> trace_level(new TraceRange((lname + "strength + coarsening").c_str()));
     double tp0 = wall_time();
@@ -1803,12 +1997,17 @@ void BoomerAMG::build_natural(ParCSR &A0) {
       if (host_coarsen) {
         strength_to_host(s);
         if (aggressive)
-          coarsen_aggressive(p.coarsen_type, n, S, cf);
+          coarsen_aggressive(p.coarsen_type, n, S, cf, two_stage ? &cf1 : nullptr);
         else
           coarsen_by_type(p.coarsen_type, n, S, cf);
         dcf.upload(cf);
       } else {
         sk::pmis(dS, 2747, dcf, s);  // (the marks stay on the device: LazyInts)
+        if (aggressive) {
+          dcf1.alloc((size_t)n);
+          MI_HIP(hipMemcpyAsync(dcf1.p, dcf.p, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, s));
+          sk::aggressive_second_stage(dS, dcf, 2747, s);
+        }
       }
       t_phase[1] += wall_time() - tp0;
     } else {
@@ -1816,7 +2015,7 @@ void BoomerAMG::build_natural(ParCSR &A0) {
       t_phase[0] += wall_time() - tp0;
       tp0 = wall_time();
       if (aggressive)
-        coarsen_aggressive(p.coarsen_type, n, S, cf);
+        coarsen_aggressive(p.coarsen_type, n, S, cf, two_stage ? &cf1 : nullptr);
       else
         coarsen_by_type(p.coarsen_type, n, S, cf);
       t_phase[1] += wall_time() - tp0;
@@ -1846,6 +2045,19 @@ void BoomerAMG::build_natural(ParCSR &A0) {
       hipStream_t s = ctx().stream;
       if (!aggressive && (p.interp_type == 6 || p.interp_type == 0))
         p_on_device = sk::interp(Lv.sA, dS, dcf, p.interp_type, p.trunc_factor, p.pmax_elmts, Lv.sP, nc, s);
+      if (two_stage) {
+        if (!dcf1.p) dcf1.upload(cf1);  // (a coarsening the host ran: the interpolation is the device's all the same)
+        if (p.keep_agg_markers) {  // (inspection: both markers to the host before the interpolation rewrites -3)
+          const std::vector<int> h1 = dcf1.to_host(), h2 = dcf.to_host();
+          Lv.agg_m1.assign(h1.begin(), h1.end());
+          Lv.agg_m2.assign(h2.begin(), h2.end());
+        }
+        const int bad = sk::two_stage_ext(Lv.sA, dS, dcf1, dcf, p.agg_p12_trunc_factor, p.agg_p12_max_elmts,
+                                          p.agg_trunc_factor, p.agg_pmax_elmts, Lv.sP, nc, s);
+        if (bad >= 0) two_stage_zero_denominator(l, bad);
+        dcf1.release();
+        p_on_device = true;
+      }
       if (p_on_device) {
         // stays on the device; the dimensions are all the host needs
         Lv.P = HostCSR();
@@ -1869,7 +2081,14 @@ void BoomerAMG::build_natural(ParCSR &A0) {
       dS.release();
     }
     if (!p_on_device) {
-      if (aggressive)
+      if (two_stage) {
+        if (p.keep_agg_markers) {  // (inspection, HYPRE_MI_BoomerAMGGetLevelAggMarkers: natural order)
+          Lv.agg_m1.assign(cf1.begin(), cf1.end());
+          Lv.agg_m2.assign(cf.begin(), cf.end());
+        }
+        build_two_stage_ext(A, S, cf1, cf, p.agg_p12_trunc_factor, p.agg_p12_max_elmts, p.agg_trunc_factor,
+                            p.agg_pmax_elmts, l, Lv.P, nc);
+      } else if (aggressive)
         build_multipass(A, S, cf, p.agg_trunc_factor, p.agg_pmax_elmts, Lv.P, nc);
       else if (p.interp_type == 4)  // multipass interpolation on an ordinary splitting (its first pass is all there is
         build_multipass(A, S, cf, p.trunc_factor, p.pmax_elmts, Lv.P, nc);  // unless F points lack a strong C point)

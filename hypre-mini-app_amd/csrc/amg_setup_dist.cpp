@@ -1891,6 +1891,9 @@ bool BoomerAMG::can_build_distributed() const {
   // Coarsening types 10 / 11 / 1 / 6 are PER-RANK algorithms by HYPRE's definition (dist_coarsen): only the distributed
   // setup builds them on N > 1, whatever the switch says.  CLJP (0 / 7) is global and distributed like PMIS; type 3
   // (a third Ruge-Stueben pass on the boundary) is the one left to the replicated setup.
+  // The two-stage extended interpolation of aggressive levels (agg_interp_type 5) has no distributed form yet: such
+  // hierarchies are built replicated, whatever the coarsening type.
+  if (p.agg_num_levels > 0 && p.agg_interp_type == 5) return false;
   if (p.coarsen_type == 10 || p.coarsen_type == 11 || p.coarsen_type == 1 || p.coarsen_type == 6) return true;
   return !forced_off && (p.coarsen_type == 8 || p.coarsen_type == 9 || p.coarsen_type == 0 || p.coarsen_type == 7);
 }

@@ -798,6 +798,13 @@ AMG_SET(AggNumLevels, HYPRE_Int, p.agg_num_levels = v)
 AMG_SET(AggInterpType, HYPRE_Int, p.agg_interp_type = v)
 AMG_SET(AggPMaxElmts, HYPRE_Int, p.agg_pmax_elmts = v)
 AMG_SET(AggTruncFactor, HYPRE_Real, p.agg_trunc_factor = v)
+AMG_SET(AggP12MaxElmts, HYPRE_Int, p.agg_p12_max_elmts = v)
+AMG_SET(AggP12TruncFactor, HYPRE_Real, p.agg_p12_trunc_factor = v)
+HYPRE_Int HYPRE_MI_BoomerAMGSetKeepAggMarkers(HYPRE_Solver solver, HYPRE_Int keep) {
+  API_BEGIN
+  AMG(solver)->amg.p.keep_agg_markers = keep ? 1 : 0;
+  API_END
+}
 AMG_SET(KeepTranspose, HYPRE_Int, p.keep_transpose = v)
 AMG_SET(RAP2, HYPRE_Int, p.rap2 = v)
 AMG_SET(Variant, HYPRE_Int, if (v != 0) warn_ignored("variant", v))
@@ -1683,6 +1690,26 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCF(HYPRE_Solver solver, HYPRE_Int level, HYP
   AmgSolver *a = AMG(solver);
   const auto &v = level_ref(a, level).cf;
   for (size_t i = 0; i < v.size(); i++) cf[i] = v[i];
+  API_END
+}
+// markers of the two coarsening stages of an aggressive level built with agg_interp_type 5, in the level's reported
+// (C-first) ordering: the C points of the final marker first, the others after, both groups in natural order
+HYPRE_Int HYPRE_MI_BoomerAMGGetLevelAggMarkers(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int *stage1, HYPRE_Int *stage2) {
+  API_BEGIN
+  AmgSolver *a = AMG(solver);
+  AmgLevel &Lv = level_ref(a, level);
+  const size_t n = Lv.agg_m2.size();
+  MI_REQUIRE(n > 0 && n == (size_t)Lv.A->nrows && Lv.agg_m1.size() == n,
+             "GetLevelAggMarkers: the level was not built by the two-stage interpolation on this rank, or "
+             "HYPRE_MI_BoomerAMGSetKeepAggMarkers was not set before Setup");
+  size_t q = 0;
+  for (int pass = 0; pass < 2; pass++)
+    for (size_t i = 0; i < n; i++)
+      if ((Lv.agg_m2[i] == 1) == (pass == 0)) {
+        if (stage1) stage1[q] = Lv.agg_m1[i];
+        if (stage2) stage2[q] = Lv.agg_m2[i];
+        q++;
+      }
   API_END
 }
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelPerm(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int *perm) {

@@ -15,6 +15,7 @@
 #include "setup_kernels.hpp"
 
 #include <algorithm>
+#include <climits>
 
 #include "kernels.hpp"
 #include "parcsr.hpp"
@@ -3629,6 +3630,429 @@ int fsai_local_solve(const DCsr &B, const DCsr &P, DCsr &G, int &max_row, int &b
 void fsai_random_vector(int n, long long gid0, int seed, double *v, hipStream_t s) {
   if (n) fsai_random_k<<<grid_for(((long long)n + BLK - 1) / BLK), BLK, 0, s>>>(n, gid0, seed, v);
   MI_HIP(hipGetLastError());
+}
+
+
+// ---------------------------------------------------------------- aggressive level on the device: second-generation
+// graph, marker correction, and the two-stage extended interpolation (agg_interp_type 5; amg_setup.cpp
+// coarsen_aggressive / build_two_stage_ext).  Sums that the host forms in stored order are formed
+// in stored order by one lane; the sparse products are sk::spgemm's.
+namespace {
+// SI = S + I with values 1 (columns ascending): FILL = false counts, FILL = true writes
+template <bool FILL>
+__global__ __launch_bounds__(BLK) void agg_s_plus_i_k(int n, const long long *__restrict__ sia, const int *__restrict__ sja,
+                                                      int *__restrict__ cnt, const long long *__restrict__ oia,
+                                                      int *__restrict__ oja, double *__restrict__ oa) {
+  const long long i = bid() * BLK + threadIdx.x;
+  if (i >= n) return;
+  const long long k0 = sia[i], k1 = sia[i + 1];
+  if (!FILL) {
+    cnt[i] = (int)(k1 - k0) + 1;
+    return;
+  }
+  long long w = oia[i];
+  bool placed = false;
+  for (long long k = k0; k < k1; k++) {
+    const int j = sja[k];
+    if (!placed && j > i) {
+      oja[w] = (int)i, oa[w] = 1.0, w++;
+      placed = true;
+    }
+    oja[w] = j, oa[w] = 1.0, w++;
+  }
+  if (!placed) oja[w] = (int)i, oa[w] = 1.0;
+}
+
+// rows of the second-generation graph: row r (C1 point rows[r]) keeps the columns of T's row r that are C1 points other
+// than itself, in C1 numbering (ascending stays ascending)
+template <bool FILL>
+__global__ __launch_bounds__(BLK) void agg_second_graph_k(int nc1, const int *__restrict__ rows, const long long *__restrict__ tia,
+                                                          const int *__restrict__ tja, const int *__restrict__ m1,
+                                                          const long long *__restrict__ crank, int *__restrict__ cnt,
+                                                          const long long *__restrict__ oia, int *__restrict__ oja) {
+  const long long r = bid() * BLK + threadIdx.x;
+  if (r >= nc1) return;
+  const int i = rows[r];
+  long long w = FILL ? oia[r] : 0;
+  int c = 0;
+  for (long long k = tia[r]; k < tia[r + 1]; k++) {
+    const int j = tja[k];
+    if (j == i || m1[j] != C_PT) continue;
+    if (FILL) oja[w++] = (int)crank[j];
+    c++;
+  }
+  if (!FILL) cnt[r] = c;
+}
+
+// hypre_BoomerAMGCorrectCFMarker: a C1 point the second coarsening rejected takes its second mark (F or special F)
+__global__ __launch_bounds__(BLK) void agg_correct_marker_k(int n, int *__restrict__ cf, const long long *__restrict__ crank,
+                                                            const int *__restrict__ cf2) {
+  const long long i = bid() * BLK + threadIdx.x;
+  if (i >= n || cf[i] != C_PT) return;
+  const int c2 = cf2[crank[i]];
+  if (c2 != C_PT) cf[i] = c2;
+}
+
+// beta_k and the length of M's row k.  S_k is a subsequence of A's row k (two-pointer membership)
+__global__ __launch_bounds__(BLK) void agg2s_beta_k(int n, const long long *__restrict__ ia, const int *__restrict__ ja,
+                                                    const double *__restrict__ a, const long long *__restrict__ sia,
+                                                    const int *__restrict__ sja, const int *__restrict__ m,
+                                                    double *__restrict__ beta, int *__restrict__ mlen) {
+  const long long k = bid() * BLK + threadIdx.x;
+  if (k >= n) return;
+  if (m[k] == C_PT) {
+    beta[k] = 0.0;
+    mlen[k] = 1;
+    return;
+  }
+  double bk = 0.0;
+  int c = 0;
+  long long ks = sia[k];
+  const long long kse = sia[k + 1];
+  for (long long q = ia[k]; q < ia[k + 1] && ks < kse; q++) {
+    const int l = ja[q];
+    while (ks < kse && sja[ks] < l) ks++;
+    if (ks < kse && sja[ks] == l && m[l] == C_PT) {
+      bk += a[q];
+      c++;
+    }
+  }
+  beta[k] = bk;
+  mlen[k] = bk != 0.0 ? c : 0;
+}
+
+// right operand M: C row -> e_k; other rows with beta_k != 0 -> a_kl / beta_k over the strong C neighbours
+__global__ __launch_bounds__(BLK) void agg2s_m_fill_k(int n, const long long *__restrict__ ia, const int *__restrict__ ja,
+                                                      const double *__restrict__ a, const long long *__restrict__ sia,
+                                                      const int *__restrict__ sja, const int *__restrict__ m,
+                                                      const long long *__restrict__ crank, const double *__restrict__ beta,
+                                                      const long long *__restrict__ mia, int *__restrict__ mja,
+                                                      double *__restrict__ ma) {
+  const long long k = bid() * BLK + threadIdx.x;
+  if (k >= n) return;
+  long long w = mia[k];
+  if (m[k] == C_PT) {
+    mja[w] = (int)crank[k];
+    ma[w] = 1.0;
+    return;
+  }
+  if (mia[k + 1] == w) return;
+  const double bk = beta[k];
+  long long ks = sia[k];
+  const long long kse = sia[k + 1];
+  for (long long q = ia[k]; q < ia[k + 1] && ks < kse; q++) {
+    const int l = ja[q];
+    while (ks < kse && sja[ks] < l) ks++;
+    if (ks < kse && sja[ks] == l && m[l] == C_PT) {
+      mja[w] = (int)crank[l];
+      ma[w] = a[q] / bk;
+      w++;
+    }
+  }
+}
+
+// left operand: row r (point rows[r], or r) -> (i, 1) for a C point, the strong entries for an F point, nothing for a
+// special F point; d of the F rows in stored order.  FILL = false: the lengths
+template <bool FILL>
+__global__ __launch_bounds__(BLK) void agg2s_left_k(int nr, const int *__restrict__ rows, const long long *__restrict__ ia,
+                                                    const int *__restrict__ ja, const double *__restrict__ a,
+                                                    const long long *__restrict__ sia, const int *__restrict__ sja,
+                                                    const int *__restrict__ m, const double *__restrict__ beta,
+                                                    int *__restrict__ cnt, const long long *__restrict__ lia,
+                                                    int *__restrict__ lja, double *__restrict__ la, double *__restrict__ d) {
+  const long long r = bid() * BLK + threadIdx.x;
+  if (r >= nr) return;
+  const int i = rows ? rows[r] : (int)r;
+  const int mi = m[i];
+  if (!FILL) {
+    cnt[r] = mi == C_PT ? 1 : mi == F_PT ? (int)(sia[i + 1] - sia[i]) : 0;
+    return;
+  }
+  long long w = lia[r];
+  if (mi != F_PT) {
+    if (mi == C_PT) lja[w] = i, la[w] = 1.0;
+    d[r] = 0.0;
+    return;
+  }
+  double di = 0.0;
+  long long ks = sia[i];
+  const long long kse = sia[i + 1];
+  for (long long q = ia[i]; q < ia[i + 1]; q++) {
+    const int j = ja[q];
+    const double v = a[q];
+    while (ks < kse && sja[ks] < j) ks++;
+    if (ks < kse && sja[ks] == j) {
+      lja[w] = j, la[w] = v, w++;
+      if (m[j] != C_PT && beta[j] == 0.0) di += v;
+    } else
+      di += v;  // the diagonal and the weak entries
+  }
+  d[r] = di;
+}
+
+// w_ij = -n_ij / d_i on the F rows, G lanes per row; the smallest F row with d_i = 0 and a non-empty numerator -> bad
+template <int G>
+__global__ __launch_bounds__(BLK) void agg2s_scale_k(int nr, const int *__restrict__ rows, const int *__restrict__ m,
+                                                     const double *__restrict__ d, const long long *__restrict__ nia,
+                                                     double *__restrict__ na, int *__restrict__ bad) {
+  const long long r = (bid() * BLK + threadIdx.x) / G;
+  const int sub = threadIdx.x % G;
+  if (r >= nr) return;
+  const int i = rows ? rows[r] : (int)r;
+  if (m[i] != F_PT) return;
+  const long long k0 = nia[r], k1 = nia[r + 1];
+  if (k0 == k1) return;
+  const double di = d[r];
+  if (di == 0.0) {
+    if (sub == 0) atomicMin(bad, i);
+    return;
+  }
+  for (long long k = k0 + sub; k < k1; k += G) na[k] = -na[k] / di;
+}
+
+// Truncation of the rows of a CSR (hs::truncate_row): entries with |v| >= trunc_factor * max|v|, of those the pmax
+// largest by (|v| descending, position ascending), rescaled to the row sum, stored order kept.  G lanes share a row.
+// The two sums are taken in stored order by every lane of the group alike (the row is read through the cache, the
+// same address by all lanes); which entries stay is decided per entry: it stays iff fewer than pmax passing entries
+// precede it in that order -- the entry of rank pmax - 1 is the cut, found by one rank count per entry.
+// FILL = false: the kept length per row
+template <bool FILL, int G>
+__global__ __launch_bounds__(BLK) void truncate_rows_k(int nr, const long long *__restrict__ ia, const int *__restrict__ ja,
+                                                       const double *__restrict__ a, double trunc_factor, int pmax,
+                                                       int *__restrict__ cnt, const long long *__restrict__ oia,
+                                                       int *__restrict__ oja, double *__restrict__ oa) {
+  const long long r = (bid() * BLK + threadIdx.x) / G;
+  const int sub = threadIdx.x % G, lane = threadIdx.x & 63, gbase = lane - sub;
+  const bool live = r < nr;
+  const long long k0 = live ? ia[r] : 0, k1 = live ? ia[r + 1] : 0;
+  const int len = (int)(k1 - k0);
+  double row_sum = 0.0, maxabs = 0.0;
+  for (long long k = k0; k < k1; k++) {
+    const double v = a[k];
+    row_sum += v;
+    maxabs = fmax(maxabs, fabs(v));
+  }
+  const double thr = trunc_factor * maxabs;
+  const bool use_thr = trunc_factor > 0.0;
+  int npass = len;
+  if (use_thr) {
+    npass = 0;
+    for (long long k = k0; k < k1; k++) npass += fabs(a[k]) >= thr;
+  }
+  const bool cut = pmax > 0 && npass > pmax;
+  if (!FILL) {
+    if (live && sub == 0) cnt[r] = cut ? pmax : npass;
+    return;
+  }
+  // the trip counts of the loops with cross-lane steps: the longest row of the wave
+  int wlen = len;
+  for (int mm = G; mm < 64; mm <<= 1) wlen = max(wlen, __shfl_xor(wlen, mm, 64));
+  // the cut: (|v|, position) of the passing entry of rank pmax - 1
+  double cabs = -1.0;
+  int cpos = len;
+  if (cut) {
+    for (int t = sub; t < len; t += G) {
+      const double av = fabs(a[k0 + t]);
+      if (use_thr && !(av >= thr)) continue;
+      int rank = 0;
+      for (int u = 0; u < len; u++) {
+        const double au = fabs(a[k0 + u]);
+        if (use_thr && !(au >= thr)) continue;
+        rank += (au > av) || (au == av && u < t);
+      }
+      if (rank == pmax - 1) cabs = av, cpos = t;
+    }
+  }
+  for (int mm = 1; mm < G; mm <<= 1) {  // exactly one lane of the group holds it
+    const double oabs = __shfl_xor(cabs, mm, 64);
+    const int opos = __shfl_xor(cpos, mm, 64);
+    if (oabs > cabs) cabs = oabs, cpos = opos;
+  }
+  auto kept = [&](int t, double v) {
+    const double av = fabs(v);
+    if (use_thr && !(av >= thr)) return false;
+    return !cut || av > cabs || (av == cabs && t <= cpos);
+  };
+  // the kept sum in stored order, by every lane
+  double kept_sum = 0.0;
+  for (int t = 0; t < len; t++) {
+    const double v = a[k0 + t];
+    if (kept(t, v)) kept_sum += v;
+  }
+  const double scale = (kept_sum != 0.0) ? row_sum / kept_sum : 1.0;
+  long long w = live ? oia[r] : 0;
+  const long long wend = live ? oia[r + 1] : 0;  // (the count pass and this one agree; NaN values could make them differ)
+  for (int t0 = 0; t0 < wlen; t0 += G) {
+    const int t = t0 + sub;
+    const bool ok = t < len;
+    const double v = ok ? a[k0 + t] : 0.0;
+    const bool keep = ok && kept(t, v);
+    if (G == 1) {
+      if (keep && w < wend) oja[w] = ja[k0 + t], oa[w] = v * scale, w++;
+    } else {
+      const unsigned long long bal = __ballot(keep);
+      const unsigned long long mine = (G == 64) ? bal : ((bal >> gbase) & ((1ull << G) - 1ull));
+      const long long q = w + __popcll(mine & ((1ull << sub) - 1ull));
+      if (keep && q < wend) {
+        oja[q] = ja[k0 + t];
+        oa[q] = v * scale;
+      }
+      w += __popcll(mine);
+    }
+  }
+}
+
+__global__ __launch_bounds__(BLK) void agg_sf_to_f_k(int n, int *__restrict__ cf) {
+  const long long i = bid() * BLK + threadIdx.x;
+  if (i < n && cf[i] == SF_PT) cf[i] = F_PT;
+}
+
+long long scan_total(const int *cnt, long long *ia, long long n, hipStream_t s) {
+  exclusive_scan(cnt, ia, n, s);
+  long long total = 0;
+  d2h(&total, ia + n, sizeof(long long), s);
+  MI_HIP(hipStreamSynchronize(s));
+  return total;
+}
+
+// B = rows of A truncated (A is consumed when nothing is to be done)
+void truncate_rows(DCsr &A, double trunc_factor, int pmax, DCsr &B, hipStream_t s) {
+  if ((trunc_factor <= 0.0 && pmax <= 0) || A.nnz == 0) {
+    B = std::move(A);
+    return;
+  }
+  const int n = A.nrows;
+  B.release();
+  B.nrows = n;
+  B.ncols = A.ncols;
+  B.ia.alloc((size_t)n + 1);
+  DVec<int> cnt((size_t)n);
+  const int rg = row_group(A.nnz, n);
+  const dim3 grid = grid_for(((long long)n * rg + BLK - 1) / BLK);
+  MI_ROW_GROUP_DISPATCH(rg, (truncate_rows_k<false, G><<<grid, BLK, 0, s>>>(n, A.ia.p, A.ja.p, A.a.p, trunc_factor, pmax, cnt.p, nullptr, nullptr, nullptr)))
+  B.nnz = scan_total(cnt.p, B.ia.p, n, s);
+  B.ja.alloc((size_t)B.nnz);
+  B.a.alloc((size_t)B.nnz);
+  if (B.nnz) {
+    MI_ROW_GROUP_DISPATCH(rg, (truncate_rows_k<true, G><<<grid, BLK, 0, s>>>(n, A.ia.p, A.ja.p, A.a.p, trunc_factor, pmax, nullptr, B.ia.p, B.ja.p, B.a.p)))
+  }
+  MI_HIP(hipGetLastError());
+  MI_HIP(hipStreamSynchronize(s));
+  A.release();
+}
+
+// E(A, S, m) for the rows `rows` (null: all), truncated: the stage operator.  bad: device int, atomic minimum of the
+// rows that cannot be interpolated
+void two_stage_stage(const DCsr &A, const DCsr &S, const int *m, const int *rows, int nr, double trunc_factor, int pmax,
+                     DCsr &P, int &nc, int *bad, hipStream_t s) {
+  const int n = A.nrows;
+  const dim3 gn = grid_for(((long long)n + BLK - 1) / BLK), gr = grid_for(((long long)nr + BLK - 1) / BLK);
+  DVec<long long> crank;
+  nc = (int)count_c_points(m, n, crank, s);
+  DVec<double> beta((size_t)n), d((size_t)nr);
+  DVec<int> cnt((size_t)std::max(n, nr));
+  DCsr M, Lo, N;
+  M.nrows = n, M.ncols = nc;
+  M.ia.alloc((size_t)n + 1);
+  agg2s_beta_k<<<gn, BLK, 0, s>>>(n, A.ia.p, A.ja.p, A.a.p, S.ia.p, S.ja.p, m, beta.p, cnt.p);
+  M.nnz = scan_total(cnt.p, M.ia.p, n, s);
+  M.ja.alloc((size_t)M.nnz);
+  M.a.alloc((size_t)M.nnz);
+  agg2s_m_fill_k<<<gn, BLK, 0, s>>>(n, A.ia.p, A.ja.p, A.a.p, S.ia.p, S.ja.p, m, crank.p, beta.p, M.ia.p, M.ja.p, M.a.p);
+  Lo.nrows = nr, Lo.ncols = n;
+  Lo.ia.alloc((size_t)nr + 1);
+  agg2s_left_k<false><<<gr, BLK, 0, s>>>(nr, rows, A.ia.p, A.ja.p, A.a.p, S.ia.p, S.ja.p, m, beta.p, cnt.p, nullptr, nullptr, nullptr, nullptr);
+  Lo.nnz = scan_total(cnt.p, Lo.ia.p, nr, s);
+  Lo.ja.alloc((size_t)Lo.nnz);
+  Lo.a.alloc((size_t)Lo.nnz);
+  agg2s_left_k<true><<<gr, BLK, 0, s>>>(nr, rows, A.ia.p, A.ja.p, A.a.p, S.ia.p, S.ja.p, m, beta.p, nullptr, Lo.ia.p, Lo.ja.p, Lo.a.p, d.p);
+  MI_HIP(hipGetLastError());
+  spgemm(Lo, M, N, s);
+  Lo.release();
+  M.release();
+  if (N.nnz) {
+    const int rg = row_group(N.nnz, nr);
+    MI_ROW_GROUP_DISPATCH(rg, (agg2s_scale_k<G><<<grid_for(((long long)nr * rg + BLK - 1) / BLK), BLK, 0, s>>>(nr, rows, m, d.p, N.ia.p, N.a.p, bad)))
+    MI_HIP(hipGetLastError());
+  }
+  truncate_rows(N, trunc_factor, pmax, P, s);
+  MI_HIP(hipStreamSynchronize(s));  // (the temporaries go away here)
+}
+}  // namespace
+
+void aggressive_second_stage(const DCsr &S, DVec<int> &cf, int seed, hipStream_t s) {
+  const int n = S.nrows;
+  if (n == 0) return;
+  const dim3 gn = grid_for(((long long)n + BLK - 1) / BLK);
+  DVec<long long> crank;
+  const int nc1 = (int)count_c_points(cf.p, n, crank, s);
+  if (nc1 == 0) return;
+  // C1 rows, ascending: the head of the C-first order
+  DVec<int> pos((size_t)n), rows((size_t)n);
+  cfirst_order(cf.p, crank.p, n, nc1, pos.p, rows.p, s);
+  // T = (C1 rows of S + I) * (S + I): the pattern of every strong path of length <= 2 (and of the point itself)
+  DCsr SI, Sc, T, S2;
+  SI.nrows = n, SI.ncols = n;
+  SI.ia.alloc((size_t)n + 1);
+  DVec<int> cnt((size_t)n);
+  agg_s_plus_i_k<false><<<gn, BLK, 0, s>>>(n, S.ia.p, S.ja.p, cnt.p, nullptr, nullptr, nullptr);
+  SI.nnz = scan_total(cnt.p, SI.ia.p, n, s);
+  SI.ja.alloc((size_t)SI.nnz);
+  SI.a.alloc((size_t)SI.nnz);
+  agg_s_plus_i_k<true><<<gn, BLK, 0, s>>>(n, S.ia.p, S.ja.p, nullptr, SI.ia.p, SI.ja.p, SI.a.p);
+  MI_HIP(hipGetLastError());
+  extract_rows(SI, rows.p, nc1, nullptr, Sc, s);
+  spgemm(Sc, SI, T, s);
+  Sc.release();
+  SI.release();
+  const dim3 gc = grid_for(((long long)nc1 + BLK - 1) / BLK);
+  S2.nrows = nc1, S2.ncols = nc1;
+  S2.ia.alloc((size_t)nc1 + 1);
+  agg_second_graph_k<false><<<gc, BLK, 0, s>>>(nc1, rows.p, T.ia.p, T.ja.p, cf.p, crank.p, cnt.p, nullptr, nullptr);
+  S2.nnz = scan_total(cnt.p, S2.ia.p, nc1, s);
+  S2.ja.alloc((size_t)S2.nnz);
+  if (S2.nnz) agg_second_graph_k<true><<<gc, BLK, 0, s>>>(nc1, rows.p, T.ia.p, T.ja.p, cf.p, crank.p, nullptr, S2.ia.p, S2.ja.p);
+  MI_HIP(hipGetLastError());
+  T.release();
+  DVec<int> cf2;
+  pmis(S2, seed, cf2, s);
+  agg_correct_marker_k<<<gn, BLK, 0, s>>>(n, cf.p, crank.p, cf2.p);
+  MI_HIP(hipGetLastError());
+  MI_HIP(hipStreamSynchronize(s));
+}
+
+int two_stage_ext(const DCsr &A, const DCsr &S, const DVec<int> &m1, DVec<int> &m2, double p12_trunc_factor, int p12_max,
+                  double trunc_factor, int pmax, DCsr &P, int &nc, hipStream_t s) {
+  const int n = A.nrows;
+  DVec<int> bad(1);
+  const int none = INT_MAX;
+  MI_HIP(hipMemcpyAsync(bad.p, &none, sizeof(int), hipMemcpyHostToDevice, s));
+  MI_HIP(hipStreamSynchronize(s));
+  DVec<long long> crank;
+  const int nc1 = (int)count_c_points(m1.p, n, crank, s);
+  DVec<int> pos((size_t)n), rows((size_t)n);
+  cfirst_order(m1.p, crank.p, n, nc1, pos.p, rows.p, s);
+  pos.release();
+  crank.release();
+  DCsr P1, P2, N;
+  int nc1b = 0;
+  int first_bad = none;
+  two_stage_stage(A, S, m1.p, nullptr, n, p12_trunc_factor, p12_max, P1, nc1b, bad.p, s);
+  d2h(&first_bad, bad.p, sizeof(int), s);
+  MI_HIP(hipStreamSynchronize(s));
+  if (first_bad != none) return first_bad;  // (stage by stage, as the host routine reports it)
+  two_stage_stage(A, S, m2.p, rows.p, nc1, p12_trunc_factor, p12_max, P2, nc, bad.p, s);
+  d2h(&first_bad, bad.p, sizeof(int), s);
+  MI_HIP(hipStreamSynchronize(s));
+  if (first_bad != none) return first_bad;
+  spgemm(P1, P2, N, s);
+  P1.release();
+  P2.release();
+  truncate_rows(N, trunc_factor, pmax, P, s);
+  if (n) agg_sf_to_f_k<<<grid_for(((long long)n + BLK - 1) / BLK), BLK, 0, s>>>(n, m2.p);
+  MI_HIP(hipGetLastError());
+  MI_HIP(hipStreamSynchronize(s));
+  return -1;
 }
 
 }  // namespace sk

@@ -43,6 +43,18 @@ void pmis(const DCsr &S, int seed, DVec<int> &cf, hipStream_t s);
 bool interp(const DCsr &A, const DCsr &S, DVec<int> &cf, int interp_type, double trunc_factor, int pmax, DCsr &P,
             int &nc, hipStream_t s);
 
+// Aggressive level (amg_setup.cpp coarsen_aggressive): cf holds the marker of the first coarsening on entry.  The
+// second-generation graph on its C points (C point i depends on C point j != i iff j is in S_i or in S_k for some k in
+// S_i; C numbering, ascending) is coarsened by PMIS with `seed` and the marker corrected: a C point the second
+// coarsening rejected takes its second mark (-1 or -3).  Point for point the host's splitting.
+void aggressive_second_stage(const DCsr &S, DVec<int> &cf, int seed, hipStream_t s);
+// Two-stage extended interpolation (agg_interp_type 5): P = trunc(trunc12(E(A, S, m1)) *
+// trunc12(C1 rows of E(A, S, m2))), the numerators by spgemm -- bit for bit hs::build_two_stage_ext.  m2 is updated
+// like the host code does (-3 -> -1); nc = number of C points of m2.  Returns -1, or the first row whose denominator
+// is zero while its numerator is not empty (P is then not built).
+int two_stage_ext(const DCsr &A, const DCsr &S, const DVec<int> &m1, DVec<int> &m2, double p12_trunc_factor, int p12_max,
+                  double trunc_factor, int pmax, DCsr &P, int &nc, hipStream_t s);
+
 // C = A * B.  Rows of B must have ascending columns.  Entry (i, j) is the sum of
 // a_ik * b_kj taken in the stored order of A's row i (first product assigned,
 // the others added one by one) -- exactly host_spgemm (amg_setup.cpp) and the

@@ -381,6 +381,7 @@ void HypreSystem::setup_boomeramg_precond() {
       {"agg_num_levels", HYPRE_BoomerAMGSetAggNumLevels},
       {"agg_interp_type", HYPRE_BoomerAMGSetAggInterpType},
       {"agg_pmax_elmts", HYPRE_BoomerAMGSetAggPMaxElmts},
+      {"agg_p12_max_elmts", HYPRE_BoomerAMGSetAggP12MaxElmts}, /* this library's key: the reference has none */
       {"smooth_type", HYPRE_BoomerAMGSetSmoothType},
       {"smooth_num_sweeps", HYPRE_BoomerAMGSetSmoothNumSweeps},
       {"smooth_num_levels", HYPRE_BoomerAMGSetSmoothNumLevels},
@@ -399,6 +400,8 @@ void HypreSystem::setup_boomeramg_precond() {
   for (const IntKey &k : int_keys)
     if (node[k.key]) k.fn(precond_, node[k.key].as<int>());
   if (node["trunc_factor"]) HYPRE_BoomerAMGSetTruncFactor(precond_, node["trunc_factor"].as<double>());
+  if (node["agg_p12_trunc_factor"])
+    HYPRE_BoomerAMGSetAggP12TruncFactor(precond_, node["agg_p12_trunc_factor"].as<double>());
   if (node["ilu_drop_tol"]) HYPRE_BoomerAMGSetILUDroptol(precond_, node["ilu_drop_tol"].as<double>());
   if (node["iterative_ilu_tolerance"])
     HYPRE_BoomerAMGSetILUIterSetupTolerance(precond_, node["iterative_ilu_tolerance"].as<double>());

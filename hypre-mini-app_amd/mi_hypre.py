@@ -265,6 +265,8 @@ class BoomerAMG:
                               ("agg_pmax_elmts", "HYPRE_BoomerAMGSetAggPMaxElmts", int),
                               ("pmax_elmts", "HYPRE_BoomerAMGSetAggPMaxElmts", int),  # sic, HypreSystem.cpp:210-213
                               ("agg_trunc_factor", "HYPRE_BoomerAMGSetAggTruncFactor", float),
+                              ("agg_p12_max_elmts", "HYPRE_BoomerAMGSetAggP12MaxElmts", int),
+                              ("agg_p12_trunc_factor", "HYPRE_BoomerAMGSetAggP12TruncFactor", float),
                               ("trunc_factor", "HYPRE_BoomerAMGSetTruncFactor", float),
                               ("keep_transpose", "HYPRE_BoomerAMGSetKeepTranspose", int),
                               ("rap2", "HYPRE_BoomerAMGSetRAP2", int),
@@ -293,6 +295,8 @@ class BoomerAMG:
                               ("true_pmax_elmts", "HYPRE_BoomerAMGSetPMaxElmts", int)):
             if key in cfg:
                 call(fn, s, conv(cfg[key]))
+        if cfg.get("keep_agg_markers"):  # test hook: level_agg_markers() after a setup with agg_interp_type 5
+            call("HYPRE_MI_BoomerAMGSetKeepAggMarkers", s, 1)
         # non_galerkin_tol + non_galerkin_level_tols {levels, tolerances}, HypreSystem.cpp:161-176
         if "non_galerkin_tol" in cfg:
             call("HYPRE_BoomerAMGSetNonGalerkinTol", s, float(cfg["non_galerkin_tol"]))
@@ -341,6 +345,15 @@ class BoomerAMG:
         cf = np.zeros(nr.value, dtype=np.int32)
         call("HYPRE_MI_BoomerAMGGetLevelCF", self.h, level, cf)
         return cf
+
+    def level_agg_markers(self, level):
+        """(stage-1 marker, stage-2 marker) of an aggressive level built with agg_interp_type 5, level_csr's rows."""
+        nr, nc, nnz = c_int(), c_int(), c_big()
+        call("HYPRE_MI_BoomerAMGGetLevelCSRSize", self.h, level, 0, C.byref(nr), C.byref(nc), C.byref(nnz))
+        m1 = np.zeros(nr.value, dtype=np.int32)
+        m2 = np.zeros(nr.value, dtype=np.int32)
+        call("HYPRE_MI_BoomerAMGGetLevelAggMarkers", self.h, level, m1, m2)
+        return m1, m2
 
     def level_perm(self, level):
         """perm[new local row] = old local row of the level's C-first ordering."""

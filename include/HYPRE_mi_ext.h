@@ -140,6 +140,12 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCSRSize(HYPRE_Solver solver, HYPRE_Int level
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCSR(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int which, HYPRE_BigInt *ia,
                                         HYPRE_Int *ja, HYPRE_Complex *a);
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCF(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int *cf);
+/* aggressive level built with agg_interp_type 5 (one rank): the markers after the first coarsening (stage1: C1) and
+ * after the second one and the marker correction (stage2: C2, special F points still -3), in GetLevelCSR's row
+ * numbering.  Either array may be NULL.  The markers are kept only when SetKeepAggMarkers(solver, 1) was called before
+ * Setup (two bytes per row of host memory; off by default).  An error on every other level. */
+HYPRE_Int HYPRE_MI_BoomerAMGSetKeepAggMarkers(HYPRE_Solver solver, HYPRE_Int keep);
+HYPRE_Int HYPRE_MI_BoomerAMGGetLevelAggMarkers(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int *stage1, HYPRE_Int *stage2);
 /* the level's C-first ordering: perm[new local row] = old local row (level matrices, P, R and the
  * C/F marker are reported in the NEW ordering; level 0 is a renumbered copy of the caller's matrix) */
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelPerm(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int *perm);
