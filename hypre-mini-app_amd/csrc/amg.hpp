@@ -63,6 +63,14 @@ struct AmgParams {
   // N > 1 ranks: levels >= 1 with at most this many global rows are kept whole on every rank and cycled
   // redundantly, without halo exchanges (HYPRE_BoomerAMGSetSeqThreshold); -1 = MI_HYPRE_REDUNDANT_ROWS or 200000
   long long redundant_rows = -1;
+  // value storage of the operators of levels >= value_first_level (HYPRE_MI_BoomerAMGSetValueStorage; DESIGN.md
+  // section 3): 0 = fp64, 1 = fp32 stream, 2 = fp64 stream holding the fp32-rounded values.  The public setter takes
+  // first_level >= 1; a redundant tail counts its levels from 0 and may hold a smaller number.
+  int value_storage = 0, value_first_level = 1;
+  // set for a redundant tail, whose print_level is 0: the number of its level 0 in the whole hierarchy, and whether
+  // it reports the operators that keep fp64 values
+  int value_level_base = 0;
+  bool value_report = false;
 };
 
 struct SolverBase;
@@ -119,6 +127,8 @@ struct AmgLevel {
   DVec<int> d_perm;
   int nc = 0;
   std::vector<double> diag, l1gs, l1jac;
+  // what apply_value_storage decided for A, P and R of this level: 0 = left as built, else the mode that was applied
+  int value_kind[3] = {0, 0, 0};
   DVec<double> d_diag, d_l1gs, d_l1jac;
   DVec<double> u, f, tmp, snap;
   DVec<double> ts_work;  // second work vector of the two-stage Gauss-Seidel (relax types 11 / 12), on first use
@@ -228,6 +238,9 @@ struct BoomerAMG {
   void finish_host();                 // l1 norms, coarsest-level dense inverse
   // device mirror of the hierarchy (needs a GPU)
   void setup_device();
+  // p.value_storage: round (mode 2) or narrow (mode 1) the operator values of this hierarchy's levels >=
+  // p.value_first_level, host arrays and -- with on_device -- the placed device operators; the last step of a setup
+  void apply_value_storage(bool on_device);
   // HYPRE_BoomerAMGSolve: x is the initial guess; up to max_iter cycles
   void solve(ParCSR &A, ParVector &b, ParVector &x);
 

@@ -2610,6 +2610,9 @@ void BoomerAMG::build_replicated(ParCSR &A0) {
     tail->p.max_levels = std::max(1, p.max_levels - (int)(nlev - 1));
     tail->p.smooth_num_levels = std::max(0, p.smooth_num_levels - (int)(nlev - 1));
     tail->p.agg_num_levels = std::max(0, p.agg_num_levels - (int)(nlev - 1));
+    tail->p.value_first_level = p.value_first_level - (int)(nlev - 1);
+    tail->p.value_level_base = p.value_level_base + (int)(nlev - 1);
+    tail->p.value_report = p.print_level > 0 && comm.rank == 0;
     {  // the tail counts its levels from 0: level-specific non-Galerkin tolerances move with it
       std::vector<double> shifted;
       for (size_t q = nlev - 1; q < p.non_galerkin_level_tol.size(); q++) shifted.push_back(p.non_galerkin_level_tol[q]);
@@ -2684,6 +2687,77 @@ std::vector<double> BoomerAMG::current_fsai_signature() const {
   if (p.smooth_type != 4 || p.smooth_num_levels <= 0) return {};
   return {(double)p.smooth_num_levels, (double)p.fsai_algo_type, (double)p.fsai_num_levels, p.fsai_threshold,
           (double)p.fsai_eig_max_iters};
+}
+
+// Value storage: the hierarchy is built as in mode 0; here, as the last step, the values of A, P
+// and R of every level >= value_first_level are replaced by (double)(float)v -- in the host arrays that exist, in the
+// halo blocks on the device (which keep 8-byte storage), and in the diag blocks on the device, which in mode 1 then
+// hold floats only.  An operator with a finite non-zero value outside the normal floats' range, in either block on any
+// rank, stays as it is: the ranks agree on the choice with one all-reduce, so it is that of a one-rank run.  The
+// zero-guess sub-operators hold entries of A and follow A.
+void BoomerAMG::apply_value_storage(bool on_device) {
+  for (AmgLevel &Lv : L) Lv.value_kind[0] = Lv.value_kind[1] = Lv.value_kind[2] = 0;
+  const int mode = p.value_storage;
+  if (mode == 0) return;
+  MI_REQUIRE(mode == 1 || mode == 2, "BoomerAMG: value storage mode must be 0, 1 or 2");
+  Comm &comm = my_comm();
+  hipStream_t s = on_device ? ctx().stream : nullptr;
+  auto host_fits = [](const HostCSR &h) {
+    for (double v : h.a)
+      if (!k::fits_float(v)) return false;
+    return true;
+  };
+  auto host_round = [](HostCSR &h) {
+    for (double &v : h.a) v = (double)(float)v;
+  };
+  const size_t first = (size_t)std::max(0, p.value_first_level);
+  auto operators = [](AmgLevel &Lv, ParCSR *ops[3]) { ops[0] = Lv.A, ops[1] = Lv.Pm.get(), ops[2] = Lv.Rm.get(); };
+  // 1 where this rank's part of the operator fits; an operator that a rank does not hold counts as fitting there
+  std::vector<int> fits(3 * L.size(), 1);
+  for (size_t li = first; li < L.size(); li++) {
+    ParCSR *ops[3];
+    operators(L[li], ops);
+    for (int op = 0; op < 3; op++) {
+      ParCSR *M = ops[op];
+      if (!M) continue;
+      const bool placed = on_device && M->d_diag.ia.p != nullptr;
+      MI_REQUIRE(!M->host_diag_stale || placed, "value storage: an operator has neither host nor device values");
+      bool ok = host_fits(M->offd);
+      if (!M->host_diag_stale)
+        ok = ok && host_fits(M->diag);
+      else
+        ok = ok && k::values_fit_float(M->d_diag.a.p, M->d_diag.nnz, s);
+      fits[3 * li + (size_t)op] = ok ? 1 : 0;
+    }
+  }
+  if (comm.size > 1 && first < L.size()) comm.allreduce_host(fits.data() + 3 * first, 3 * (L.size() - first), CommDType::I32, CommOp::MIN);
+  for (size_t li = first; li < L.size(); li++) {
+    AmgLevel &Lv = L[li];
+    ParCSR *ops[3];
+    operators(Lv, ops);
+    for (int op = 0; op < 3; op++) {
+      ParCSR *M = ops[op];
+      if (!M) continue;
+      if (!fits[3 * li + (size_t)op]) {
+        if ((p.print_level > 0 && comm.rank == 0) || p.value_report)
+          printf("mi_hypre BoomerAMG: level %zu %s keeps fp64 values (a value outside the range of normal floats)\n",
+                 li + (size_t)p.value_level_base, op == 0 ? "A" : op == 1 ? "P" : "R");
+        continue;
+      }
+      const bool placed = on_device && M->d_diag.ia.p != nullptr;
+      if (!M->host_diag_stale) host_round(M->diag);
+      host_round(M->offd);
+      if (placed) {
+        k::narrow_values(M->d_diag, mode, s);
+        if (M->d_diag.rowmap.p) ctx().n_value_row_mapped++;
+        if (M->d_offd.a.p) k::round_values(M->d_offd.a.p, M->d_offd.nnz, s);
+        if (op == 0 && Lv.has_Az) k::narrow_values(Lv.Az, mode, s);
+        if (op == 0 && Lv.has_Ar) k::narrow_values(Lv.Ar, mode, s);
+      }
+      Lv.value_kind[op] = mode;
+    }
+  }
+  if (on_device) MI_HIP(hipStreamSynchronize(s));
 }
 
 void BoomerAMG::setup_device() {
@@ -2809,6 +2883,7 @@ void BoomerAMG::setup_device() {
     }
   }
   build_smoothers();
+  apply_value_storage(true);  // after everything Setup derives from the operators as built
   AmgLevel &Lc = L.back();
   if (Lc.dense) {
     const size_t width = (size_t)comm.size * (size_t)Lc.slot;

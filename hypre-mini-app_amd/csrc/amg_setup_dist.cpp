@@ -2840,6 +2840,9 @@ void BoomerAMG::build_distributed(ParCSR &A0) {
     tail->p.max_levels = std::max(1, p.max_levels - (int)(nlev - 1));
     tail->p.smooth_num_levels = std::max(0, p.smooth_num_levels - (int)(nlev - 1));
     tail->p.agg_num_levels = std::max(0, p.agg_num_levels - (int)(nlev - 1));
+    tail->p.value_first_level = p.value_first_level - (int)(nlev - 1);
+    tail->p.value_level_base = p.value_level_base + (int)(nlev - 1);
+    tail->p.value_report = p.print_level > 0 && comm.rank == 0;
     {  // the tail counts its levels from 0: level-specific non-Galerkin tolerances move with it
       std::vector<double> shifted;
       for (size_t q = nlev - 1; q < p.non_galerkin_level_tol.size(); q++) shifted.push_back(p.non_galerkin_level_tol[q]);

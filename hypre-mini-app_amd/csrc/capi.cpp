@@ -434,6 +434,8 @@ HYPRE_Int HYPRE_MI_BoomerAMGSetupHostOnly(HYPRE_Solver solver, HYPRE_ParCSRMatri
   if (!A) fail(HYPRE_ERROR_ARG, "BoomerAMGSetupHostOnly: NULL matrix");
   AMG(solver)->amg.device_min_rows = -1;  // host threads only
   AMG(solver)->amg.setup_host(*PM(A));
+  AMG(solver)->amg.apply_value_storage(false);
+  if (AMG(solver)->amg.tail) AMG(solver)->amg.tail->apply_value_storage(false);
   API_END
 }
 // setup-phase sparse kernels on caller (host) CSR arrays; results are malloc'ed (HYPRE_MI_Free)
@@ -717,10 +719,27 @@ HYPRE_Int HYPRE_ParVectorCopy(HYPRE_ParVector x, HYPRE_ParVector y) {
 }
 
 // ------------------------------------------------------------------ BoomerAMG
+static void set_value_storage(AmgParams &p, int mode, int first_level) {
+  if (mode < 0 || mode > 2)
+    fail(HYPRE_ERROR_ARG, "value storage mode " + std::to_string(mode) + " is not implemented: 0 (fp64), 1 (fp32) or 2 (fp64 holding fp32-rounded values)");
+  if (first_level < 1)
+    fail(HYPRE_ERROR_ARG, "value storage first_level " + std::to_string(first_level) +
+                              " < 1: level 0 is the operator the Krylov solver multiplies by and is never narrowed");
+  p.value_storage = mode;
+  p.value_first_level = first_level;
+}
+HYPRE_Int HYPRE_MI_BoomerAMGSetValueStorage(HYPRE_Solver solver, HYPRE_Int mode, HYPRE_Int first_level) {
+  API_BEGIN
+  set_value_storage(AMG(solver)->amg.p, mode, first_level);
+  API_END
+}
 HYPRE_Int HYPRE_BoomerAMGCreate(HYPRE_Solver *solver) {
   API_BEGIN
   if (!solver) fail(HYPRE_ERROR_ARG, "BoomerAMGCreate: NULL output");
-  *solver = reinterpret_cast<HYPRE_Solver>(static_cast<SolverBase *>(new AmgSolver()));
+  std::unique_ptr<AmgSolver> a(new AmgSolver());
+  const char *vs = getenv("MI_HYPRE_VALUE_STORAGE"), *vl = getenv("MI_HYPRE_VALUE_STORAGE_FIRST_LEVEL");
+  set_value_storage(a->amg.p, vs ? atoi(vs) : 0, vl ? atoi(vl) : 1);
+  *solver = reinterpret_cast<HYPRE_Solver>(static_cast<SolverBase *>(a.release()));
   API_END
 }
 HYPRE_Int HYPRE_BoomerAMGDestroy(HYPRE_Solver solver) {
@@ -1410,6 +1429,8 @@ HYPRE_Int HYPRE_MI_GetCounter(const char *name, long long *value) {
     *value = ctx().n_halo_exchange;
   else if (n == "allgather")
     *value = ctx().n_allgather;
+  else if (n == "value_storage_row_mapped")
+    *value = ctx().n_value_row_mapped;
   else if (dist_setup_counter(n.c_str()) >= 0)
     *value = dist_setup_counter(n.c_str());
   else
@@ -1683,6 +1704,37 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCSR(HYPRE_Solver solver, HYPRE_Int level, HY
   for (int i = 0; i <= c.nrows; i++) ia[i] = c.ia[(size_t)i];
   if (!c.ja.empty()) memcpy(ja, c.ja.data(), c.ja.size() * sizeof(int));
   if (!c.a.empty()) memcpy(a, c.a.data(), c.a.size() * sizeof(double));
+  API_END
+}
+HYPRE_Int HYPRE_MI_BoomerAMGGetLevelValueStorage(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int which, HYPRE_Int *kind,
+                                                 HYPRE_BigInt *value_bytes) {
+  API_BEGIN
+  AmgLevel &L = level_ref(AMG(solver), level);
+  int kd = 0;
+  long long bytes = 0;
+  auto of_dev = [&](const DevCSR &D) {
+    kd = D.val8 ? 8 : D.value_kind;
+    bytes = k::value_stream_bytes(D);
+  };
+  if (which == 6 || which == 8) {
+    if (which == 6 ? L.has_Az : L.has_Ar) of_dev(which == 6 ? L.Az : L.Ar);
+  } else if (which >= 0 && which <= 5) {
+    const int op = which <= 1 ? 0 : (which == 2 || which == 4) ? 1 : 2;
+    const ParCSR *M = op == 0 ? L.A : op == 1 ? L.Pm.get() : L.Rm.get();
+    if (M && (which == 0 || which == 2 || which == 3)) {
+      if (M->d_diag.ia.p)
+        of_dev(M->d_diag);
+      else
+        kd = L.value_kind[op];
+    } else if (M) {
+      kd = L.value_kind[op] ? 2 : 0;
+      if (M->d_offd.a.p) bytes = (long long)(M->d_offd.a.n + 2) * 8;
+    }
+  } else {
+    fail(HYPRE_ERROR_ARG, "which must be 0..5, 6 or 8");
+  }
+  if (kind) *kind = kd;
+  if (value_bytes) *value_bytes = bytes;
   API_END
 }
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCF(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int *cf) {

@@ -32,6 +32,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 // vector from L2.  (Not in the GS kernel: its per-row segments share lines between load instructions, and
 // non-temporal lines are not kept in L1 -- measured 35 % slower.)
 typedef double d2_t __attribute__((ext_vector_type(2)));
+typedef float f2_t __attribute__((ext_vector_type(2)));
 typedef int i2_t __attribute__((ext_vector_type(2)));
 typedef unsigned short us2_t __attribute__((ext_vector_type(2)));
 typedef unsigned char uc2_t __attribute__((ext_vector_type(2)));
@@ -113,10 +114,12 @@ __device__ __forceinline__ void epilogue(int r, double s, const double *__restri
 
 // TAG only names the instantiation: TAG 1 = the level-0 operator, so that the
 // rocprofv3 kernel statistics carry a row for exactly the launches bench.py times
-template <int EPI, int TAG>
+// VT: the type of the stored values (double, or float for an operator with fp32 value storage -- DevCSR::a32; the
+// value is widened where the product is formed, everything after it is the same arithmetic)
+template <int EPI, int TAG, class VT = double>
 __global__ __launch_bounds__(SPMV_BLOCK) void spmv_stream(int nb, int xchunk, const int *__restrict__ rb,
                                                           const int *__restrict__ ia, const int *__restrict__ ja,
-                                                          const double *__restrict__ av, const double *__restrict__ x,
+                                                          const VT *__restrict__ av, const double *__restrict__ x,
                                                           double *__restrict__ y, EpiArgs e) {
   __shared__ double prod[SPMV_TILE];
   const int blk = xcd_remap(blockIdx.x, xchunk);
@@ -127,7 +130,7 @@ __global__ __launch_bounds__(SPMV_BLOCK) void spmv_stream(int nb, int xchunk, co
   if (end - base >= SPMV_TILE) {
     // one long row: every lane strides over it, two-level reduction
     double s = 0.0;
-    for (int k = base + tid; k < end; k += SPMV_BLOCK) s += av[k] * x[ja[k]];
+    for (int k = base + tid; k < end; k += SPMV_BLOCK) s += (double)av[k] * x[ja[k]];
     s = wave_sum(s);
     if ((tid & 63) == 0) prod[tid >> 6] = s;
     __syncthreads();
@@ -138,14 +141,15 @@ __global__ __launch_bounds__(SPMV_BLOCK) void spmv_stream(int nb, int xchunk, co
   const int base_al = base & ~1;
   const int cnt = end - base_al;  // <= SPMV_TILE
   for (int k = 2 * tid; k < cnt; k += 2 * SPMV_BLOCK) {
-    const d2_t v = nt_load(reinterpret_cast<const d2_t *>(av + base_al + k));
+    typedef VT v2_t __attribute__((ext_vector_type(2)));
+    const v2_t v = nt_load(reinterpret_cast<const v2_t *>(av + base_al + k));
     const i2_t c = nt_load(reinterpret_cast<const i2_t *>(ja + base_al + k));
     const bool ok0 = (base_al + k >= base);
     const bool ok1 = (base_al + k + 1 < end);
     const double x0 = ok0 ? x[c.x] : 0.0;
     const double x1 = ok1 ? x[c.y] : 0.0;
-    prod[k] = v.x * x0;
-    if (k + 1 < SPMV_TILE) prod[k + 1] = v.y * x1;
+    prod[k] = (double)v.x * x0;
+    if (k + 1 < SPMV_TILE) prod[k + 1] = (double)v.y * x1;
   }
   __syncthreads();
   // phase 2
@@ -182,7 +186,11 @@ __global__ __launch_bounds__(SPMV_BLOCK) void spmv_stream(int nb, int xchunk, co
 // kernel is not bound by this chain alone -- VALU, LDS and the L1 gather path are each 25-30 % busy.)
 // VAL8: the operator has a value dictionary (DevCSR::vidx / vlut): the stream is one byte per value, looked up in
 // a 2 KB LDS copy of the table
-template <int EPI, int TAG, bool VAL8, int BLOCK>
+// VAL4: the operator stores fp32 values (DevCSR::a32, handed in through `av`): the stream is 4 bytes per value, loaded
+// in pairs and widened to double where the product is formed; products, the product buffer and the row sums are the
+// fp64 ones of the plain stream.  (A trailing parameter, so that the instantiations that existed before it keep the
+// leading part of their names in the profiler's statistics.)
+template <int EPI, int TAG, bool VAL8, int BLOCK, bool VAL4 = false>
 __global__ __launch_bounds__(BLOCK) void spmv_stream_xc(int nb, int xchunk, const int *__restrict__ tdesc,
                                                              const int *__restrict__ ia, const int *__restrict__ ja,
                                                              const double *__restrict__ av,
@@ -191,6 +199,7 @@ __global__ __launch_bounds__(BLOCK) void spmv_stream_xc(int nb, int xchunk, cons
                                                              const double *__restrict__ x, double *__restrict__ y,
                                                              EpiArgs e, const unsigned char *__restrict__ vidx,
                                                              const double *__restrict__ vlut) {
+  static_assert(!(VAL8 && VAL4), "one value format per instantiation");
   constexpr int TILE = 8 * BLOCK;  // TILE / TILE_WIDE
   __shared__ double prod[TILE];
   __shared__ double slut[VAL8 ? 256 : 1];
@@ -217,7 +226,12 @@ __global__ __launch_bounds__(BLOCK) void spmv_stream_xc(int nb, int xchunk, cons
   const long long base64 = ((long long)d1.z << 32) | (long long)(unsigned)d0.z;
   if (len >= TILE) {
     double s = 0.0;
-    for (long long k = base64 + tid; k < base64 + len; k += BLOCK) s += av[k] * x[ja[k]];
+    if (VAL4) {
+      const float *av4 = reinterpret_cast<const float *>(av);
+      for (long long k = base64 + tid; k < base64 + len; k += BLOCK) s += (double)av4[k] * x[ja[k]];
+    } else {
+      for (long long k = base64 + tid; k < base64 + len; k += BLOCK) s += av[k] * x[ja[k]];
+    }
     s = wave_sum(s);
     if ((tid & 63) == 0) prod[tid >> 6] = s;
     __syncthreads();
@@ -244,11 +258,13 @@ __global__ __launch_bounds__(BLOCK) void spmv_stream_xc(int nb, int xchunk, cons
   const int end = base + len;
   const int cnt = end;
   const unsigned ia_off = (unsigned)base_al64;  // low word: (unsigned)ia[row] - ia_off = the row's tile-local offset
+  const float *av4 = reinterpret_cast<const float *>(av) + base_al64;  // VAL4: the same argument, 4-byte entries
   av += base_al64;
   lcol += base_al64;
   if (VAL8) vidx += base_al64;
   constexpr int NIT = TILE / (2 * BLOCK);
   d2_t vv[NIT];
+  f2_t vf[NIT];  // VAL4: two values, as loaded (widened after the first barrier)
   unsigned cw[NIT];  // two 16-bit column words, as loaded
   unsigned vw[NIT];  // two value indices, as loaded, one register each (nothing is unpacked or packed inside the
                      // branches: that makes the compiler wait for each load where it stands)
@@ -257,10 +273,12 @@ __global__ __launch_bounds__(BLOCK) void spmv_stream_xc(int nb, int xchunk, cons
     const int k = 2 * tid + it * 2 * BLOCK;
     cw[it] = 0;
     vw[it] = 0;
-    if (MI_ABLATE & 4) vv[it] = d2_t{1.0, 1.0};
+    if (MI_ABLATE & 4) vv[it] = d2_t{1.0, 1.0}, vf[it] = f2_t{1.0f, 1.0f};
     if (!(MI_ABLATE & 4) && k < cnt) {
       if (VAL8)
         vw[it] = STREAM_LOAD(reinterpret_cast<const unsigned short *>(vidx + base_al + k));
+      else if (VAL4)
+        vf[it] = STREAM_LOAD(reinterpret_cast<const f2_t *>(av4 + base_al + k));
       else
         vv[it] = STREAM_LOAD(reinterpret_cast<const d2_t *>(av + base_al + k));
       cw[it] = STREAM_LOAD(reinterpret_cast<const unsigned *>(lcol + base_al + k));
@@ -307,6 +325,10 @@ __global__ __launch_bounds__(BLOCK) void spmv_stream_xc(int nb, int xchunk, cons
       if (VAL8) {
         vv[it].x = slut[vw[it] & 0xffu];
         vv[it].y = slut[vw[it] >> 8];
+      }
+      if (VAL4) {
+        vv[it].x = (double)vf[it].x;
+        vv[it].y = (double)vf[it].y;
       }
       vv[it].x = ok0 ? vv[it].x * xs[cw[it] & XC_ID_MASK] : 0.0;
       vv[it].y = ok1 ? vv[it].y * xs[(cw[it] >> 16) & XC_ID_MASK] : 0.0;
@@ -388,8 +410,9 @@ __global__ __launch_bounds__(256) void spmv_offd_k(int nrc, const int *__restric
 // threads/ranks (par_relax.c) and is bitwise independent of
 // scheduling because u_old is never written.
 // ---------------------------------------------------------------------------
+template <class VT>
 __global__ __launch_bounds__(GS_BLOCK) void gs_hybrid_k(int n, int chunk0, int nchunks, int chunk, const int *__restrict__ ia,
-                                                        const int *__restrict__ ja, const double *__restrict__ av,
+                                                        const int *__restrict__ ja, const VT *__restrict__ av,
                                                         const signed char *__restrict__ cf, int points,
                                                         const double *__restrict__ dd, const double *__restrict__ f,
                                                         const double *__restrict__ offc,
@@ -419,7 +442,7 @@ __global__ __launch_bounds__(GS_BLOCK) void gs_hybrid_k(int n, int chunk0, int n
         const int j = ja[k];
         const unsigned o = (unsigned)(j - cs);
         const double v = (o < (unsigned)len) ? ucur[o * GS_BLOCK + tid] : UOLD(j);
-        res -= av[k] * v;
+        res -= (double)av[k] * v;
       }
       ucur[tt * GS_BLOCK + tid] += w * res / d;
     }
@@ -466,9 +489,9 @@ __device__ __forceinline__ double group_sum(double v) {
   return v;
 }
 
-template <int LPC, int E>
+template <int LPC, int E, class VT = double>
 __global__ __launch_bounds__(256) void gs_group_k(int n, int chunk0, int nchunks, const int *__restrict__ ia,
-                                                  const int *__restrict__ ja, const double *__restrict__ av,
+                                                  const int *__restrict__ ja, const VT *__restrict__ av,
                                                   const signed char *__restrict__ cf, int points,
                                                   const double *__restrict__ dd, const double *__restrict__ f,
                                                   const double *__restrict__ offc,
@@ -527,7 +550,7 @@ __global__ __launch_bounds__(256) void gs_group_k(int n, int chunk0, int nchunks
     for (int e = 0; e < E; e++) {
       const int k = k0s[t] + g + e * LPC;
       const bool ok = k < k1s[t];
-      wv[t][e] = ok ? av[k] : 0.0;
+      wv[t][e] = ok ? (double)av[k] : 0.0;
       cols[t][e] = ok ? ja[k] : cs;
     }
   }
@@ -568,7 +591,7 @@ __global__ __launch_bounds__(256) void gs_group_k(int n, int chunk0, int nchunks
           double v = 0.0, x = 0.0;
           int o = -1;
           if (k < k1) {
-            v = av[k];
+            v = (double)av[k];
             const int j = ja[k];
             const unsigned oo = (unsigned)(j - cs);
             if (oo < (unsigned)len)
@@ -645,9 +668,9 @@ __device__ __forceinline__ void rs_step(double *p, int g) {
   }
 }
 
-template <int LPC, int E>
+template <int LPC, int E, class VT = double>
 __global__ __launch_bounds__(256) void gs_dense_k(int n, int chunk0, int nchunks, const int *__restrict__ ia,
-                                                  const int *__restrict__ ja, const double *__restrict__ av,
+                                                  const int *__restrict__ ja, const VT *__restrict__ av,
                                                   const signed char *__restrict__ cf, int points,
                                                   const double *__restrict__ dd, const double *__restrict__ f,
                                                   const double *__restrict__ offc,
@@ -705,7 +728,7 @@ __global__ __launch_bounds__(256) void gs_dense_k(int n, int chunk0, int nchunks
     for (int e = 0; e < E; e++) {
       const int k = k0s[t] + g + e * LPC;
       const bool ok = k < k1s[t];
-      wv[t][e] = ok ? av[k] : 0.0;
+      wv[t][e] = ok ? (double)av[k] : 0.0;
       cols[t][e] = ok ? ja[k] : -1;
     }
   }
@@ -727,7 +750,7 @@ __global__ __launch_bounds__(256) void gs_dense_k(int n, int chunk0, int nchunks
     }
     if (k1s[t] - k0s[t] > LPC * E) {  // the rest of a long row (uniform inside the group)
       for (int k = k0s[t] + LPC * E + g; k < k1s[t]; k += LPC) {
-        const double a = av[k];
+        const double a = (double)av[k];
         const int j = ja[k];
         const unsigned oo = (unsigned)(j - cs);
         if (oo < (unsigned)len)
@@ -897,7 +920,8 @@ __device__ __forceinline__ void gs_tile_sweep(const double (&crow)[8], double (&
 // products out of LDS, picks its in-chunk coefficients by the code bits of the
 // 16-bit column entries, and runs the dense 8x8 sweep of gs_dense_k.
 // ---------------------------------------------------------------------------
-template <bool VAL8, int BLOCK>
+// VAL4: fp32 value storage, see spmv_stream_xc.
+template <bool VAL8, int BLOCK, bool VAL4 = false>
 __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void gs_tile_k(int blk0, int nblk, const int *__restrict__ tdesc,
                                                         const int *__restrict__ ia, const double *__restrict__ av,
                                                         const int *__restrict__ ucols,
@@ -952,21 +976,25 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void gs_tile_k(int blk0, int n
   const int end = base + len;
   const int cnt = end;
   const unsigned ia_off = (unsigned)base_al64;
+  const float *av4 = reinterpret_cast<const float *>(av) + base_al64;  // VAL4: the same argument, 4-byte entries
   av += base_al64;
   lcol += base_al64;
   if (VAL8) vidx += base_al64;
   constexpr int NIT = TILE / (2 * BLOCK);
   d2_t vv[NIT];
+  f2_t vf[NIT];  // VAL4: two values, as loaded (widened after the first barrier)
   unsigned cw[NIT], vw[NIT];  // two 16-bit column words / two value indices, as loaded (see spmv_stream_xc)
 #pragma unroll
   for (int it = 0; it < NIT; it++) {
     const int k = 2 * tid + it * 2 * BLOCK;
     cw[it] = 0;
     vw[it] = 0;
-    if (MI_ABLATE & 4) vv[it] = d2_t{1.0, 1.0};
+    if (MI_ABLATE & 4) vv[it] = d2_t{1.0, 1.0}, vf[it] = f2_t{1.0f, 1.0f};
     if (!(MI_ABLATE & 4) && k < cnt) {
       if (VAL8)
         vw[it] = STREAM_LOAD(reinterpret_cast<const unsigned short *>(vidx + base_al + k));
+      else if (VAL4)
+        vf[it] = STREAM_LOAD(reinterpret_cast<const f2_t *>(av4 + base_al + k));
       else
         vv[it] = STREAM_LOAD(reinterpret_cast<const d2_t *>(av + base_al + k));
       cw[it] = STREAM_LOAD(reinterpret_cast<const unsigned *>(lcol + base_al + k));
@@ -975,8 +1003,9 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void gs_tile_k(int blk0, int n
   // the gathers in flight together, before the first LDS write and before the per-row chain (see spmv_stream_xc); lanes
   // beyond the list and columns from zero_from on read entry 0 and are overwritten / not stored.  With 8-byte values in
   // registers all NU at once would cost 74 VGPRs (6 instead of 8 waves per SIMD): that variant takes them in two
-  // batches -- the first covers tiles of up to 4 * BLOCK unique columns, i.e. nearly all of them.
-  constexpr int GB = VAL8 ? NU : NU / 2;
+  // batches -- the first covers tiles of up to 4 * BLOCK unique columns, i.e. nearly all of them.  With 4-byte values
+  // (VAL4) the stream holds half the registers and all NU gathers go out at once, as with the dictionary.
+  constexpr int GB = (VAL8 || VAL4) ? NU : NU / 2;
   double xv[GB];
   if (!all_zero) {
 #pragma unroll
@@ -1038,6 +1067,10 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void gs_tile_k(int blk0, int n
       if (VAL8) {
         vv[it].x = slut[vw[it] & 0xffu];
         vv[it].y = slut[vw[it] >> 8];
+      }
+      if (VAL4) {
+        vv[it].x = (double)vf[it].x;
+        vv[it].y = (double)vf[it].y;
       }
       // out-of-chunk: product with the snapshot value; in-chunk: the coefficient itself
       const double x0 = all_zero ? 0.0 : buf[c0 & XC_ID_MASK], x1 = all_zero ? 0.0 : buf[c1 & XC_ID_MASK];
@@ -1427,8 +1460,9 @@ __global__ __launch_bounds__(256) void two_stage_first_k(int n, const double *__
   z[i] = zi;
   u[i] += zi;
 }
+template <class VT>
 __global__ __launch_bounds__(256) void two_stage_lower_k(int n, const int *__restrict__ ia, const int *__restrict__ ja,
-                                                         const double *__restrict__ a, const double *__restrict__ d,
+                                                         const VT *__restrict__ a, const double *__restrict__ d,
                                                          const double *__restrict__ zin, double sign,
                                                          double *__restrict__ zout, double *__restrict__ u) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -1436,7 +1470,7 @@ __global__ __launch_bounds__(256) void two_stage_lower_k(int n, const int *__res
   double s = 0.0;
   for (int k = ia[i]; k < ia[i + 1]; k++) {
     const int j = ja[k];
-    if (j < i) s += a[k] * zin[j];
+    if (j < i) s += (double)a[k] * zin[j];
   }
   const double zi = (d[i] != 0.0) ? s / d[i] : 0.0;
   zout[i] = zi;
@@ -1648,6 +1682,8 @@ static const char *launch_stream(int epi, const DevCSR &A, const double *x, doub
   if (A.nrows == 0) return "";
   MI_REQUIRE(A.xcache || !A.big(), "an operator with 2^31 entries or more must be in the x-cache tile format");
   const char *name = "";
+  const bool f32 = A.a32.p != nullptr;  // fp32 value storage (k::narrow_values): `a` is gone, the kernels stream a32
+  MI_REQUIRE(f32 || A.a.p || A.nnz == 0, "SpMV: the operator holds no value array");
   const int nb = A.nblocks;
   const int xchunk = (nb + 7) / 8;
   const dim3 grid(xchunk * 8), block(SPMV_BLOCK);
@@ -1657,7 +1693,18 @@ static const char *launch_stream(int epi, const DevCSR &A, const double *x, doub
   name = "spmv_stream_xc<" #EPI_ ", 0, " #V8_ ", 512>";                                                              \
   hipLaunchKernelGGL((spmv_stream_xc<EPI_, 0, V8_, SPMV_BLOCK_WIDE>), grid, wide, 0, s, nb, xchunk, A.tdesc.p, A.ia.p, \
                      A.ja.p, A.a.p, A.ucols.p, A.lcol.p, x, y, e, A.vidx.p, A.vlut.p)
-    if (A.val8) {
+#define XC_LAUNCH_W4(EPI_)                                                                                           \
+  name = "spmv_stream_xc<" #EPI_ ", 0, false, 512, true>";                                                           \
+  hipLaunchKernelGGL((spmv_stream_xc<EPI_, 0, false, SPMV_BLOCK_WIDE, true>), grid, wide, 0, s, nb, xchunk, A.tdesc.p, \
+                     A.ia.p, A.ja.p, reinterpret_cast<const double *>(A.a32.p), A.ucols.p, A.lcol.p, x, y, e, nullptr, \
+                     nullptr)
+    if (f32) {
+      if (epi == 0) {
+        XC_LAUNCH_W4(0);
+      } else {
+        XC_LAUNCH_W4(1);
+      }
+    } else if (A.val8) {
       if (epi == 0) {
         XC_LAUNCH_W(0, true);
       } else {
@@ -1671,12 +1718,26 @@ static const char *launch_stream(int epi, const DevCSR &A, const double *x, doub
       }
     }
 #undef XC_LAUNCH_W
+#undef XC_LAUNCH_W4
   } else if (A.xcache) {
 #define XC_LAUNCH(EPI_, TAG_, V8_)                                                                                  \
   name = "spmv_stream_xc<" #EPI_ ", " #TAG_ ", " #V8_ ", 256>";                                                       \
   hipLaunchKernelGGL((spmv_stream_xc<EPI_, TAG_, V8_, SPMV_BLOCK>), grid, block, 0, s, nb, xchunk, A.tdesc.p, A.ia.p, A.ja.p, \
                      A.a.p, A.ucols.p, A.lcol.p, x, y, e, A.vidx.p, A.vlut.p)
-    if (A.val8) {
+#define XC_LAUNCH4(EPI_, TAG_)                                                                                      \
+  name = "spmv_stream_xc<" #EPI_ ", " #TAG_ ", false, 256, true>";                                                    \
+  hipLaunchKernelGGL((spmv_stream_xc<EPI_, TAG_, false, SPMV_BLOCK, true>), grid, block, 0, s, nb, xchunk, A.tdesc.p, \
+                     A.ia.p, A.ja.p, reinterpret_cast<const double *>(A.a32.p), A.ucols.p, A.lcol.p, x, y, e, nullptr, \
+                     nullptr)
+    if (f32) {
+      if (epi == 0 && level0) {
+        XC_LAUNCH4(0, 1);
+      } else if (epi == 0) {
+        XC_LAUNCH4(0, 0);
+      } else {
+        XC_LAUNCH4(1, 0);
+      }
+    } else if (A.val8) {
       if (epi == 0 && level0) {
         XC_LAUNCH(0, 1, true);
       } else if (epi == 0) {
@@ -1694,6 +1755,18 @@ static const char *launch_stream(int epi, const DevCSR &A, const double *x, doub
       }
     }
 #undef XC_LAUNCH
+#undef XC_LAUNCH4
+  } else if (f32) {
+    if (epi == 0 && level0) {
+      name = "spmv_stream<0, 1, float>";
+      hipLaunchKernelGGL((spmv_stream<0, 1, float>), grid, block, 0, s, nb, xchunk, A.rb.p, A.ia.p, A.ja.p, A.a32.p, x, y, e);
+    } else if (epi == 0) {
+      name = "spmv_stream<0, 0, float>";
+      hipLaunchKernelGGL((spmv_stream<0, 0, float>), grid, block, 0, s, nb, xchunk, A.rb.p, A.ia.p, A.ja.p, A.a32.p, x, y, e);
+    } else {
+      name = "spmv_stream<1, 0, float>";
+      hipLaunchKernelGGL((spmv_stream<1, 0, float>), grid, block, 0, s, nb, xchunk, A.rb.p, A.ia.p, A.ja.p, A.a32.p, x, y, e);
+    }
   } else if (epi == 0 && level0) {
     name = "spmv_stream<0, 1>";
     hipLaunchKernelGGL((spmv_stream<0, 1>), grid, block, 0, s, nb, xchunk, A.rb.p, A.ia.p, A.ja.p, A.a.p, x, y, e);
@@ -1915,6 +1988,7 @@ void gs_hybrid(const DevCSR &A, const double *u_lo, const double *u_hi, int spli
   const long long c0 = row_begin / chunk;
   const long long c1 = ((long long)row_end + chunk - 1) / chunk;
   const long long nch = c1 - c0;
+  const bool f32 = A.a32.p != nullptr;  // fp32 value storage
   prof_begin(prof, s);
   if (gs_uses_tiles(A, chunk)) {
     int first_row, last_row, b0, b1;
@@ -1926,8 +2000,18 @@ void gs_hybrid(const DevCSR &A, const double *u_lo, const double *u_hi, int spli
                      A.ia.p, A.a.p, A.ucols.p, A.lcol.p, cf, points, d, f, offc, u_lo, u_hi, split, out, fwd ? 1 : 0,  \
                      bwd ? 1 : 0, w, first_row, last_row, zero_from, tout, t_from, V8_ ? A.vidx.p : nullptr,          \
                      V8_ ? A.vlut.p : nullptr)
+#define GS_TILE_LAUNCH4(BLOCK_)                                                                                      \
+  prof_name(prof, BLOCK_ == 512 ? "gs_tile_k<false, 512, true>" : "gs_tile_k<false, 256, true>");                     \
+  hipLaunchKernelGGL((gs_tile_k<false, BLOCK_, true>), dim3((unsigned)(b1 - b0)), dim3(BLOCK_), 0, s, b0, b1 - b0,    \
+                     A.tdesc.p, A.ia.p, reinterpret_cast<const double *>(A.a32.p), A.ucols.p, A.lcol.p, cf, points, d, \
+                     f, offc, u_lo, u_hi, split, out, fwd ? 1 : 0, bwd ? 1 : 0, w, first_row, last_row, zero_from,    \
+                     tout, t_from, nullptr, nullptr)
     const bool wide = A.tile_entries == SPMV_TILE_WIDE;
-    if (b1 > b0 && A.val8 && wide) {
+    if (b1 > b0 && f32 && wide) {
+      GS_TILE_LAUNCH4(SPMV_BLOCK_WIDE);
+    } else if (b1 > b0 && f32) {
+      GS_TILE_LAUNCH4(SPMV_BLOCK);
+    } else if (b1 > b0 && A.val8 && wide) {
       GS_TILE_LAUNCH(true, SPMV_BLOCK_WIDE);
     } else if (b1 > b0 && A.val8) {
       GS_TILE_LAUNCH(true, SPMV_BLOCK);
@@ -1937,6 +2021,7 @@ void gs_hybrid(const DevCSR &A, const double *u_lo, const double *u_hi, int spli
       GS_TILE_LAUNCH(false, SPMV_BLOCK);
     }
 #undef GS_TILE_LAUNCH
+#undef GS_TILE_LAUNCH4
   } else if (chunk == 8) {
     MI_REQUIRE(!A.big(), "an operator with 2^31 entries or more is swept by the tile Gauss-Seidel kernel only");
     prof_name(prof, "gs_group_k / gs_dense_k (chunk kernels)");
@@ -1945,9 +2030,15 @@ void gs_hybrid(const DevCSR &A, const double *u_lo, const double *u_hi, int spli
 #define GS_LAUNCH_K(KERNEL, LPC, E)                                                                             \
   {                                                                                                             \
     const long long waves = (nch + (64 / LPC) - 1) / (64 / LPC);                                                \
-    hipLaunchKernelGGL((KERNEL<LPC, E>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, A.nrows, (int)c0,   \
-                       (int)c1, A.ia.p, A.ja.p, A.a.p, cf, points, d, f, offc, u_lo, u_hi, split, out,          \
-                       fwd ? 1 : 0, bwd ? 1 : 0, w, zero_from);                                                 \
+    if (f32) prof_name(prof, #KERNEL "<" #LPC ", " #E ", float>");                                              \
+    if (f32)                                                                                                    \
+      hipLaunchKernelGGL((KERNEL<LPC, E, float>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, A.nrows,  \
+                         (int)c0, (int)c1, A.ia.p, A.ja.p, A.a32.p, cf, points, d, f, offc, u_lo, u_hi, split,  \
+                         out, fwd ? 1 : 0, bwd ? 1 : 0, w, zero_from);                                          \
+    else                                                                                                        \
+      hipLaunchKernelGGL((KERNEL<LPC, E>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, A.nrows, (int)c0, \
+                         (int)c1, A.ia.p, A.ja.p, A.a.p, cf, points, d, f, offc, u_lo, u_hi, split, out,        \
+                         fwd ? 1 : 0, bwd ? 1 : 0, w, zero_from);                                               \
   }
     // Measured per level (256^3 / 512^3 Laplacian hierarchies, profiles/compare_gs.*):
     //   mean row length <= 8 (the fine level): the shuffle kernel with 8 lanes per chunk is memory-bound
@@ -1969,10 +2060,15 @@ void gs_hybrid(const DevCSR &A, const double *u_lo, const double *u_hi, int spli
   } else {
     MI_REQUIRE(!A.big(), "an operator with 2^31 entries or more is swept by the tile Gauss-Seidel kernel only");
     const size_t lds = (size_t)chunk * GS_BLOCK * sizeof(double);
-    prof_name(prof, "gs_hybrid_k");
-    hipLaunchKernelGGL(gs_hybrid_k, dim3((unsigned)((nch + GS_BLOCK - 1) / GS_BLOCK)), dim3(GS_BLOCK), lds, s,
-                       A.nrows, (int)c0, (int)c1, chunk, A.ia.p, A.ja.p, A.a.p, cf, points, d, f, offc, u_lo, u_hi,
-                       split, out, fwd ? 1 : 0, bwd ? 1 : 0, w);
+    prof_name(prof, f32 ? "gs_hybrid_k<float>" : "gs_hybrid_k");
+    if (f32)
+      hipLaunchKernelGGL(gs_hybrid_k<float>, dim3((unsigned)((nch + GS_BLOCK - 1) / GS_BLOCK)), dim3(GS_BLOCK), lds, s,
+                         A.nrows, (int)c0, (int)c1, chunk, A.ia.p, A.ja.p, A.a32.p, cf, points, d, f, offc, u_lo, u_hi,
+                         split, out, fwd ? 1 : 0, bwd ? 1 : 0, w);
+    else
+      hipLaunchKernelGGL(gs_hybrid_k<double>, dim3((unsigned)((nch + GS_BLOCK - 1) / GS_BLOCK)), dim3(GS_BLOCK), lds, s,
+                         A.nrows, (int)c0, (int)c1, chunk, A.ia.p, A.ja.p, A.a.p, cf, points, d, f, offc, u_lo, u_hi,
+                         split, out, fwd ? 1 : 0, bwd ? 1 : 0, w);
   }
   MI_HIP(hipGetLastError());
   prof_end(prof, s);
@@ -2215,8 +2311,87 @@ void two_stage_lower(const DevCSR &A, const double *d, const double *zin, double
                      hipStream_t s) {
   if (A.nrows <= 0) return;
   MI_REQUIRE(!A.big(), "two-stage Gauss-Seidel: operators with 2^31 entries or more are not supported");
-  hipLaunchKernelGGL(two_stage_lower_k, dim3((A.nrows + 255) / 256), dim3(256), 0, s, A.nrows, A.ia.p, A.ja.p, A.a.p, d,
-                     zin, sign, zout, u);
+  if (A.a32.p)
+    hipLaunchKernelGGL(two_stage_lower_k<float>, dim3((A.nrows + 255) / 256), dim3(256), 0, s, A.nrows, A.ia.p, A.ja.p,
+                       A.a32.p, d, zin, sign, zout, u);
+  else
+    hipLaunchKernelGGL(two_stage_lower_k<double>, dim3((A.nrows + 255) / 256), dim3(256), 0, s, A.nrows, A.ia.p, A.ja.p,
+                       A.a.p, d, zin, sign, zout, u);
+}
+
+// ---------------------------------------------------------------- fp32 value storage
+namespace {
+// *flag = 1 when a finite non-zero value lies outside the range of normal floats
+__global__ __launch_bounds__(256) void float_range_k(long long n, const double *__restrict__ a, int *__restrict__ flag) {
+  const long long stride = (long long)gridDim.x * 256;
+  int bad = 0;
+  for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < n; k += stride) bad |= !fits_float(a[k]);
+  if (bad) *flag = 1;  // every writer stores the same value
+}
+__global__ __launch_bounds__(256) void round_to_float_k(long long n, double *__restrict__ a) {
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < n; k += stride) a[k] = (double)(float)a[k];
+}
+__global__ __launch_bounds__(256) void narrow_k(long long n, const double *__restrict__ a, float *__restrict__ out) {
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < n; k += stride) out[k] = (float)a[k];
+}
+__global__ __launch_bounds__(256) void widen_k(long long n, const float *__restrict__ a, double *__restrict__ out) {
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < n; k += stride) out[k] = (double)a[k];
+}
+unsigned value_grid(long long n) { return (unsigned)std::max<long long>(1, std::min<long long>(4096, (n + 255) / 256)); }
+}  // namespace
+
+bool values_fit_float(const double *a, long long n, hipStream_t s) {
+  if (n <= 0) return true;
+  DVec<int> flag(1);
+  MI_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), s));
+  hipLaunchKernelGGL(float_range_k, dim3(value_grid(n)), dim3(256), 0, s, n, a, flag.p);
+  MI_HIP(hipGetLastError());
+  int bad = 0;
+  d2h(&bad, flag.p, sizeof(int), s);
+  MI_HIP(hipStreamSynchronize(s));
+  return bad == 0;
+}
+
+void round_values(double *a, long long n, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(round_to_float_k, dim3(value_grid(n)), dim3(256), 0, s, n, a);
+  MI_HIP(hipGetLastError());
+}
+
+void narrow_values(DevCSR &A, int mode, hipStream_t s) {
+  MI_REQUIRE(mode == 1 || mode == 2, "value storage: mode 1 or 2");
+  MI_REQUIRE(!A.a32.p, "value storage: the operator is narrowed already");
+  A.value_kind = A.val8 ? 8 : mode;
+  if (A.val8) round_values(A.vlut.p, 256, s);  // the table and the fp64 array kept beside it: the same values
+  if (A.val8 || mode == 2) {
+    round_values(A.a.p, A.nnz, s);
+  } else {
+    A.a32.alloc((size_t)A.nnz);
+    hipLaunchKernelGGL(narrow_k, dim3(value_grid(A.nnz)), dim3(256), 0, s, (long long)A.nnz, A.a.p, A.a32.p);
+    MI_HIP(hipGetLastError());
+    MI_HIP(hipStreamSynchronize(s));
+    A.a.release();
+  }
+}
+
+const double *fp64_values(const DevCSR &A, DVec<double> &tmp, hipStream_t s) {
+  if (!A.a32.p) return A.a.p;
+  tmp.alloc((size_t)A.nnz);
+  if (A.nnz) hipLaunchKernelGGL(widen_k, dim3(value_grid(A.nnz)), dim3(256), 0, s, (long long)A.nnz, A.a32.p, tmp.p);
+  MI_HIP(hipGetLastError());
+  return tmp.p;
+}
+
+long long value_stream_bytes(const DevCSR &A) {
+  long long b = 0;
+  if (A.a.p) b += (long long)(A.a.n + 2) * 8;
+  if (A.a32.p) b += (long long)(A.a32.n + 2) * 4;
+  if (A.vidx.p) b += (long long)(A.vidx.n + 2);
+  if (A.vlut.p) b += (long long)(A.vlut.n + 2) * 8;
+  return b;
 }
 
 void ipc_exchange(const IpcBatch &b, unsigned long long spin_limit, int *error_flag, hipStream_t s) {

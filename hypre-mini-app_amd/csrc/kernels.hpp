@@ -127,6 +127,24 @@ void build_value_dictionary(DevCSR &A, hipStream_t s);
 // MI_HYPRE_VALUE_DICT / HYPRE_MI_SetValueDictionary: applies to operators put into the solve format afterwards
 bool value_dictionary_enabled();
 void set_value_dictionary(bool on);
+// ---- fp32 value storage (HYPRE_MI_BoomerAMGSetValueStorage; the rule is DESIGN.md section 3)
+// whether the value may be stored as a float: zero, Inf and NaN pass (they convert exactly); a finite non-zero value
+// needs FLT_MIN <= |v| <= FLT_MAX, so that (double)(float)v is neither a subnormal, zero nor infinity
+__host__ __device__ inline bool fits_float(double v) {
+  const double m = v < 0.0 ? -v : v;
+  if (!(m <= 1.79769313486231570814527423731704357e+308)) return true;  // Inf, NaN
+  return m == 0.0 || (m >= 1.17549435082228750796873653722224568e-38 && m <= 3.40282346638528859811704183484516925e+38);
+}
+// device arrays: whether all n values fit (synchronises s); a[k] = (double)(float)a[k]
+bool values_fit_float(const double *a, long long n, hipStream_t s);
+void round_values(double *a, long long n, hipStream_t s);
+// an operator in the solve format whose values fit: mode 1 moves them into A.a32 (A.a is released), mode 2 rounds A.a
+// in place; an operator with a value dictionary keeps it in either mode, with the table and A.a rounded.  Sets A.value_kind.
+void narrow_values(DevCSR &A, int mode, hipStream_t s);
+// the operator's values as doubles: A.a, or A.a32 widened into tmp (setup paths that read a placed operator again)
+const double *fp64_values(const DevCSR &A, DVec<double> &tmp, hipStream_t s);
+// device bytes of the operator's value arrays (values, dictionary indices and table), padding included
+long long value_stream_bytes(const DevCSR &A);
 // y = alpha*A*x + beta*b   (b may alias y)
 // b_lo (optional): rows < b_split take their b entry from b_lo instead of b
 void spmv(const DevCSR &A, const double *x, double alpha, double beta, const double *b, double *y, hipStream_t s,

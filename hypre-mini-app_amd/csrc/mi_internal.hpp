@@ -207,6 +207,10 @@ struct DevCSR {
   bool big() const { return nnz >= (int64_t)2147483647; }
   DVec<int> ja;
   DVec<double> a;
+  // fp32 value storage (k::narrow_values, HYPRE_MI_BoomerAMGSetValueStorage mode 1): the values as floats; `a` is then
+  // released and every solve kernel runs its float instantiation, widening each value where the product is formed
+  DVec<float> a32;
+  int value_kind = 0;  // 0 fp64, 1 fp32 (a32), 2 fp64 holding fp32-rounded values, 8 value dictionary (rounded or not)
   // row-block schedule of the LDS-staged SpMV (kernels.hip: spmv_stream)
   DVec<int> rb;
   int nblocks = 0;
@@ -341,6 +345,7 @@ struct Ctx {
   // collectives the solve phase issued on N > 1 ranks: scalar / block all-reduces (inner products), neighbour
   // exchange groups (one per halo update), all-gathers (coarsest / redundant levels)
   long long n_allreduce = 0, n_halo_exchange = 0, n_allgather = 0;
+  long long n_value_row_mapped = 0;  // row-mapped restriction operators that took fp32-rounded values (tests)
 };
 Ctx &ctx();
 void ensure_init();

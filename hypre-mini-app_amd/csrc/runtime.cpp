@@ -773,6 +773,8 @@ void DevCSR::upload(const HostCSR &h) {
   nnz = h.nnz();
   require_int32_block(nrows, nnz, "solve format (host builder: small operators; large ones go through sk::to_solve_format)");
   ia64.release();
+  a32.release();  // a placement starts from fp64 values (k::narrow_values narrows them again where asked)
+  value_kind = 0;
   std::vector<int> ia32((size_t)nrows + 1);
   for (int i = 0; i <= nrows; i++) ia32[(size_t)i] = (int)h.ia[(size_t)i];
   ia.upload(ia32);

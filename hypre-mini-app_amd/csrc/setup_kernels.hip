@@ -2126,6 +2126,8 @@ void to_solve_format(DCsr &src, DevCSR &dst, hipStream_t s) {
   dst.nnz = src.nnz;
   dst.ia.alloc((size_t)n + 1);
   dst.ia64.release();
+  dst.a32.release();  // a placement starts from fp64 values (k::narrow_values narrows them again where asked)
+  dst.value_kind = 0;
   ia_to_32_k<<<(unsigned)((n + 1 + BLK - 1) / BLK), BLK, 0, s>>>((long long)n + 1, src.ia.p, dst.ia.p);  // low words
   // row-length percentile (GS kernel variant choice) from a device histogram
   dst.rowlen_p95 = 0;
@@ -2220,12 +2222,14 @@ void zero_guess_operator(const DevCSR &A, int nc, int chunk, DCsr &Z, hipStream_
   DVec<int> cnt((size_t)n);
   DVec<long long> ia_tmp;
   const long long *Aia = n ? wide_row_pointers(A, ia_tmp, s) : nullptr;
+  DVec<double> a_tmp;  // (an operator with fp32 value storage: its values widened -- the sub-operator is fp64 again)
+  const double *Aa = k::fp64_values(A, a_tmp, s);
   const int rg = row_group(A.nnz, n);
   const dim3 grid = grid_for(((long long)n * rg + BLK - 1) / BLK);
   if (n && mode == 0) {
-    MI_ROW_GROUP_DISPATCH(rg, (zero_guess_rows_k<false, 0, G><<<grid, BLK, 0, s>>>(n, nc, chunk, Aia, A.ja.p, A.a.p, cnt.p, nullptr, nullptr, nullptr)))
+    MI_ROW_GROUP_DISPATCH(rg, (zero_guess_rows_k<false, 0, G><<<grid, BLK, 0, s>>>(n, nc, chunk, Aia, A.ja.p, Aa, cnt.p, nullptr, nullptr, nullptr)))
   } else if (n) {
-    MI_ROW_GROUP_DISPATCH(rg, (zero_guess_rows_k<false, 1, G><<<grid, BLK, 0, s>>>(n, nc, chunk, Aia, A.ja.p, A.a.p, cnt.p, nullptr, nullptr, nullptr)))
+    MI_ROW_GROUP_DISPATCH(rg, (zero_guess_rows_k<false, 1, G><<<grid, BLK, 0, s>>>(n, nc, chunk, Aia, A.ja.p, Aa, cnt.p, nullptr, nullptr, nullptr)))
   }
   exclusive_scan(cnt.p, Z.ia.p, n, s);
   long long total = 0;
@@ -2235,9 +2239,9 @@ void zero_guess_operator(const DevCSR &A, int nc, int chunk, DCsr &Z, hipStream_
   Z.ja.alloc((size_t)total);
   Z.a.alloc((size_t)total);
   if (n && total && mode == 0) {
-    MI_ROW_GROUP_DISPATCH(rg, (zero_guess_rows_k<true, 0, G><<<grid, BLK, 0, s>>>(n, nc, chunk, Aia, A.ja.p, A.a.p, nullptr, Z.ia.p, Z.ja.p, Z.a.p)))
+    MI_ROW_GROUP_DISPATCH(rg, (zero_guess_rows_k<true, 0, G><<<grid, BLK, 0, s>>>(n, nc, chunk, Aia, A.ja.p, Aa, nullptr, Z.ia.p, Z.ja.p, Z.a.p)))
   } else if (n && total) {
-    MI_ROW_GROUP_DISPATCH(rg, (zero_guess_rows_k<true, 1, G><<<grid, BLK, 0, s>>>(n, nc, chunk, Aia, A.ja.p, A.a.p, nullptr, Z.ia.p, Z.ja.p, Z.a.p)))
+    MI_ROW_GROUP_DISPATCH(rg, (zero_guess_rows_k<true, 1, G><<<grid, BLK, 0, s>>>(n, nc, chunk, Aia, A.ja.p, Aa, nullptr, Z.ia.p, Z.ja.p, Z.a.p)))
   }
   MI_HIP(hipGetLastError());
   MI_HIP(hipStreamSynchronize(s));
@@ -2256,7 +2260,8 @@ void solve_format_to_host(const DevCSR &src, HostCSR &h, hipStream_t s) {
     d2h(h.ia.data(), ia64, ((size_t)n + 1) * sizeof(long long), s);
     if (src.nnz) {
       d2h(h.ja.data(), src.ja.p, (size_t)src.nnz * sizeof(int), s);
-      d2h(h.a.data(), src.a.p, (size_t)src.nnz * sizeof(double), s);
+      DVec<double> a_tmp;
+      d2h(h.a.data(), k::fp64_values(src, a_tmp, s), (size_t)src.nnz * sizeof(double), s);
     }
     MI_HIP(hipStreamSynchronize(s));
   }
@@ -2332,7 +2337,9 @@ void from_solve_format(const DevCSR &src, DCsr &dst, hipStream_t s) {
     ia_to_64_k<<<(unsigned)((n + 1 + BLK - 1) / BLK), BLK, 0, s>>>((long long)n + 1, src.ia.p, dst.ia.p);
   if (src.nnz) {
     MI_HIP(hipMemcpyAsync(dst.ja.p, src.ja.p, (size_t)src.nnz * sizeof(int), hipMemcpyDeviceToDevice, s));
-    MI_HIP(hipMemcpyAsync(dst.a.p, src.a.p, (size_t)src.nnz * sizeof(double), hipMemcpyDeviceToDevice, s));
+    DVec<double> a_tmp;
+    MI_HIP(hipMemcpyAsync(dst.a.p, k::fp64_values(src, a_tmp, s), (size_t)src.nnz * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (a_tmp.p) MI_HIP(hipStreamSynchronize(s));  // the temporary is released on return
   }
   MI_HIP(hipGetLastError());
 }

@@ -399,6 +399,20 @@ void HypreSystem::setup_boomeramg_precond() {
   };
   for (const IntKey &k : int_keys)
     if (node[k.key]) k.fn(precond_, node[k.key].as<int>());
+  /* this library's keys: value storage of the AMG levels >= mi_value_storage_first_level (0 fp64, 1 fp32, 2 fp64
+   * holding the fp32-rounded values); a key that is absent leaves the solver's default (MI_HYPRE_VALUE_STORAGE*) */
+  if (node["mi_value_storage"] || node["mi_value_storage_first_level"]) {
+    const char *vs = getenv("MI_HYPRE_VALUE_STORAGE"), *vl = getenv("MI_HYPRE_VALUE_STORAGE_FIRST_LEVEL");
+    const int mode = get_optional(node, "mi_value_storage", vs ? atoi(vs) : 0);
+    const int first = get_optional(node, "mi_value_storage_first_level", vl ? atoi(vl) : 1);
+#ifdef MI_HOST_WITH_LIBHYPRE
+    (void)mode, (void)first;
+    throw std::runtime_error("Hypre Config:: mi_value_storage is a key of libmi_hypre; libHYPRE has no such setting");
+#else
+    if (HYPRE_MI_BoomerAMGSetValueStorage(precond_, mode, first))
+      throw std::runtime_error(std::string("Hypre Config:: mi_value_storage: ") + HYPRE_MI_LastErrorMessage());
+#endif
+  }
   if (node["trunc_factor"]) HYPRE_BoomerAMGSetTruncFactor(precond_, node["trunc_factor"].as<double>());
   if (node["agg_p12_trunc_factor"])
     HYPRE_BoomerAMGSetAggP12TruncFactor(precond_, node["agg_p12_trunc_factor"].as<double>());

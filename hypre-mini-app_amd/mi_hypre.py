@@ -295,6 +295,13 @@ class BoomerAMG:
                               ("true_pmax_elmts", "HYPRE_BoomerAMGSetPMaxElmts", int)):
             if key in cfg:
                 call(fn, s, conv(cfg[key]))
+        # this library's keys: value storage of the levels >= mi_value_storage_first_level (0 fp64, 1 fp32, 2 fp64
+        # holding fp32-rounded values); absent keys leave the solver's defaults (MI_HYPRE_VALUE_STORAGE*)
+        if "mi_value_storage" in cfg or "mi_value_storage_first_level" in cfg:
+            env = os.environ.get
+            call("HYPRE_MI_BoomerAMGSetValueStorage", s,
+                 int(cfg.get("mi_value_storage", env("MI_HYPRE_VALUE_STORAGE", 0))),
+                 int(cfg.get("mi_value_storage_first_level", env("MI_HYPRE_VALUE_STORAGE_FIRST_LEVEL", 1))))
         if cfg.get("keep_agg_markers"):  # test hook: level_agg_markers() after a setup with agg_interp_type 5
             call("HYPRE_MI_BoomerAMGSetKeepAggMarkers", s, 1)
         # non_galerkin_tol + non_galerkin_level_tols {levels, tolerances}, HypreSystem.cpp:161-176
@@ -338,6 +345,13 @@ class BoomerAMG:
         a = np.zeros(max(nnz.value, 1), dtype=np.float64)
         call("HYPRE_MI_BoomerAMGGetLevelCSR", self.h, level, which, ia, ja, a)
         return ia, ja[: nnz.value], a[: nnz.value], (nr.value, nc.value)
+
+    def level_value_storage(self, level, which):
+        """(kind, value_bytes) of an operator after setup; which as in level_csr, or 6 / 8 for the zero-guess
+        sub-operators.  kind: 0 fp64, 1 fp32, 2 fp64 holding fp32-rounded values, 8 value dictionary."""
+        kind, nbytes = c_int(), c_big()
+        call("HYPRE_MI_BoomerAMGGetLevelValueStorage", self.h, level, which, C.byref(kind), C.byref(nbytes))
+        return kind.value, nbytes.value
 
     def level_cf(self, level):
         nr, nc, nnz = c_int(), c_int(), c_big()

@@ -140,6 +140,21 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCSRSize(HYPRE_Solver solver, HYPRE_Int level
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCSR(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int which, HYPRE_BigInt *ia,
                                         HYPRE_Int *ja, HYPRE_Complex *a);
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCF(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int *cf);
+/* Value storage of the operators (A, P, R, the zero-guess sub-operators) of the AMG levels >= first_level; call before
+ * Setup.  mode 0: fp64 (the default), 1: the values are stored and streamed as fp32 and widened to fp64 where a
+ * product is formed, 2: fp64 storage holding the fp32-rounded values (the reference semantics of mode 1: every
+ * solve-phase result of the two is the same bit for bit).  Vectors, sums, diagonals, l1 norms, the coarsest dense
+ * inverse and the Krylov solver stay fp64; the hierarchy is mode 0's with each stored value v replaced by
+ * (double)(float)v.  first_level >= 1: level 0 is the system the Krylov solver multiplies by.  An operator with a
+ * finite non-zero value outside the range of normal floats keeps its fp64 values.  Any other mode, or first_level < 1,
+ * is HYPRE_ERROR_ARG.  Defaults of a new solver: MI_HYPRE_VALUE_STORAGE (0), MI_HYPRE_VALUE_STORAGE_FIRST_LEVEL (1). */
+HYPRE_Int HYPRE_MI_BoomerAMGSetValueStorage(HYPRE_Solver solver, HYPRE_Int mode, HYPRE_Int first_level);
+/* What an operator holds after Setup.  which: as in GetLevelCSRSize, 0-5, 6 and 8.  kind: 0 fp64 as built, 1 fp32,
+ * 2 fp64 holding fp32-rounded values (halo blocks of a narrowed operator are always of this kind), 8 value dictionary.
+ * value_bytes: device bytes of the operator's value arrays, padding included (0 for a hierarchy that is not on the
+ * device, where kind is what Setup decided for the operator).  Either output may be NULL. */
+HYPRE_Int HYPRE_MI_BoomerAMGGetLevelValueStorage(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int which, HYPRE_Int *kind,
+                                                 HYPRE_BigInt *value_bytes);
 /* aggressive level built with agg_interp_type 5 (one rank): the markers after the first coarsening (stage1: C1) and
  * after the second one and the marker correction (stage2: C2, special F points still -3), in GetLevelCSR's row
  * numbering.  Either array may be NULL.  The markers are kept only when SetKeepAggMarkers(solver, 1) was called before
