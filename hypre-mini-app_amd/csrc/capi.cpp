@@ -10,6 +10,7 @@
 
 #include "HYPRE_mi_ext.h"
 #include "_hypre_parcsr_ls.h"
+#include "ij_assembly.hpp"
 #include "kernels.hpp"
 #include "profile.hpp"
 #include "solvers.hpp"
@@ -46,6 +47,11 @@ int record_error(int code, const std::string &msg) {
 struct IJMatrixObj {
   gidx ilower, iupper, jlower, jupper;
   std::vector<IJEntryBatch> batches;
+  // batches whose arrays all arrived in device memory stay there (ij_assembly.hpp) until a host batch joins them:
+  // then they are fetched and the matrix takes the host path.  At most one of the two lists is in use.
+  std::vector<ij::DevBatch> dev_batches;
+  bool device_path = true;  // no host batch so far
+  bool device_failed = false;  // a device assembly failed: its batches may be gone, the matrix is not usable
   ParCSR par;
   bool assembled = false;
 };
@@ -82,27 +88,59 @@ KrylovSolver *KR(HYPRE_Solver s) {
 }
 
 // copy n elements from a host-or-device pointer into a host vector
+// counted: entries of an IJ matrix batch or IJ vector indices (HYPRE_MI_GetCounter "ij_entries_fetched_to_host")
 template <class T>
-void fetch(const T *src, size_t n, std::vector<T> &dst) {
+void fetch(const T *src, size_t n, std::vector<T> &dst, bool counted = false) {
   dst.resize(n);
   if (!n) return;
-  if (is_device_pointer(src))
+  if (is_device_pointer(src)) {
     d2h(dst.data(), src, n * sizeof(T), nullptr);
-  else
+    if (counted) ij::counters().entries_fetched += (long long)n;
+  } else {
     memcpy(dst.data(), src, n * sizeof(T));
+  }
+}
+
+// a host batch joins device batches: they come to the host, in call order, and the matrix takes the host path
+void ij_demote(IJMatrixObj *m) {
+  for (auto &d : m->dev_batches) {
+    IJEntryBatch b;
+    b.add = d.add;
+    fetch(d.rows.p, (size_t)d.n, b.rows);
+    fetch(d.cols.p, (size_t)d.n, b.cols);
+    fetch(d.vals.p, (size_t)d.n, b.vals, true);
+    m->batches.push_back(std::move(b));
+  }
+  m->dev_batches.clear();
+  m->device_path = false;
 }
 
 void ij_stage(IJMatrixObj *m, int nrows, const int *ncols, const gidx *rows, const int *row_indexes, const gidx *cols,
               const double *vals, bool add) {
   if (m->assembled) fail(HYPRE_ERROR_GENERIC, "IJMatrix: values set after Assemble (re-assembly is not supported)");
   if (nrows <= 0) return;
+  if (m->device_path && ij::device_assembly_enabled()) {
+    const bool all_dev = is_device_pointer(rows) && is_device_pointer(cols) && is_device_pointer(vals) &&
+                         (!ncols || is_device_pointer(ncols)) && (!row_indexes || is_device_pointer(row_indexes));
+    if (all_dev) {
+      ij::DevBatch d;
+      if (!ncols)
+        ij::stage_coo(rows, cols, vals, nrows, add, d);
+      else
+        ij::stage_ncols(nrows, ncols, rows, row_indexes, cols, vals, add, d);
+      m->dev_batches.push_back(std::move(d));
+      return;
+    }
+    if (!m->dev_batches.empty()) ij_demote(m);
+  }
+  m->device_path = false;
   IJEntryBatch b;
   b.add = add;
   if (!ncols) {
     // one entry per "row" (src/HypreSystem.cpp:942: ncols == NULL, row_indexes == NULL)
     fetch(rows, (size_t)nrows, b.rows);
     fetch(cols, (size_t)nrows, b.cols);
-    fetch(vals, (size_t)nrows, b.vals);
+    fetch(vals, (size_t)nrows, b.vals, true);
   } else {
     std::vector<int> nc, ri;
     std::vector<gidx> r;
@@ -118,7 +156,7 @@ void ij_stage(IJMatrixObj *m, int nrows, const int *ncols, const gidx *rows, con
     std::vector<gidx> c;
     std::vector<double> v;
     fetch(cols, span, c);
-    fetch(vals, span, v);
+    fetch(vals, span, v, true);
     b.rows.reserve(total);
     b.cols.reserve(total);
     b.vals.reserve(total);
@@ -142,9 +180,15 @@ void vec_set(IJVectorObj *v, int n, const gidx *indices, const double *values, b
   ensure_init();
   hipStream_t s = ctx().stream;
   std::vector<gidx> idx;
-  std::vector<int> loc((size_t)n);
-  if (indices) {
-    fetch(indices, (size_t)n, idx);
+  DVec<int> dloc;
+  const bool dev_idx = indices && ij::device_assembly_enabled() && is_device_pointer(indices);
+  std::vector<int> loc(dev_idx ? (size_t)0 : (size_t)n);
+  if (dev_idx) {
+    // device indices: range check and conversion to local ids on the device
+    dloc.alloc((size_t)n);
+    ij::vec_local_ids(indices, n, v->jlower, v->jupper, dloc.p);
+  } else if (indices) {
+    fetch(indices, (size_t)n, idx, true);
     for (int i = 0; i < n; i++) {
       const gidx g = idx[(size_t)i];
       if (g < v->jlower || g > v->jupper) fail(HYPRE_ERROR_ARG, "IJVector: index outside the local range");
@@ -154,8 +198,7 @@ void vec_set(IJVectorObj *v, int n, const gidx *indices, const double *values, b
     if (n > v->par.n) fail(HYPRE_ERROR_ARG, "IJVector: more values than local entries");
     for (int i = 0; i < n; i++) loc[(size_t)i] = i;
   }
-  DVec<int> dloc;
-  dloc.upload(loc);
+  if (!dev_idx) dloc.upload(loc);
   DVec<double> dval;
   const double *src = values;
   if (!is_device_pointer(values)) {
@@ -377,6 +420,7 @@ HYPRE_Int HYPRE_IJMatrixSetConstantValues(HYPRE_IJMatrix matrix, HYPRE_Complex v
   if (!m) fail(HYPRE_ERROR_ARG, "IJMatrixSetConstantValues: NULL handle");
   if (m->assembled) fail(HYPRE_ERROR_GENERIC, "IJMatrixSetConstantValues after Assemble is not supported");
   for (auto &b : m->batches) std::fill(b.vals.begin(), b.vals.end(), value);
+  for (auto &d : m->dev_batches) ij::fill_values(d, value);
   API_END
 }
 HYPRE_Int HYPRE_IJMatrixSetValues2(HYPRE_IJMatrix matrix, HYPRE_Int nrows, HYPRE_Int *ncols, const HYPRE_BigInt *rows,
@@ -405,6 +449,29 @@ HYPRE_Int HYPRE_IJMatrixAssemble(HYPRE_IJMatrix matrix) {
   API_BEGIN
   IJMatrixObj *m = M(matrix);
   if (!m) fail(HYPRE_ERROR_ARG, "IJMatrixAssemble: NULL handle");
+  if (m->device_failed)
+    fail(HYPRE_ERROR_GENERIC, "IJMatrixAssemble: an earlier assembly of this matrix failed and its entries are gone; "
+                              "create the matrix and set its values again");
+  if (!m->assembled && !m->dev_batches.empty()) {
+    // every batch arrived in device memory: sorted, folded and split there (ij_assembly.hip); the diag block is
+    // already on the device when its solve format is built.  The matrix counts as assembled only when all of it
+    // succeeded; a failure (a refusal, out of memory) leaves it unusable instead of half built -- a second Assemble
+    // must not find consumed batches and build an empty matrix.
+    Comm &comm = current_comm();
+    try {
+      sk::DCsr diag;
+      ij::assemble_parcsr_device(comm, m->ilower, m->iupper, m->jlower, m->jupper, m->dev_batches, m->par, diag);
+      m->par.build_halo_plan(comm);
+      dev_arena_hint((size_t)13 * 12 * (size_t)(diag.nnz + m->par.offd.nnz()));
+      ij::finish_device(m->par, diag);
+    } catch (...) {
+      m->device_failed = true;
+      m->dev_batches.clear();
+      throw;
+    }
+    m->assembled = true;
+    return 0;
+  }
   if (!m->assembled) {
     Comm &comm = current_comm();
     assemble_parcsr(comm, m->ilower, m->iupper, m->jlower, m->jupper, m->batches, m->par);
@@ -422,11 +489,63 @@ HYPRE_Int HYPRE_MI_IJMatrixAssembleHostOnly(HYPRE_IJMatrix matrix) {
   IJMatrixObj *m = M(matrix);
   if (!m) fail(HYPRE_ERROR_ARG, "IJMatrixAssembleHostOnly: NULL handle");
   if (!m->assembled) {
+    if (!m->dev_batches.empty()) ij_demote(m);
     Comm &comm = current_comm();
     assemble_parcsr(comm, m->ilower, m->iupper, m->jlower, m->jupper, m->batches, m->par);
     m->par.build_halo_plan(comm);
     m->assembled = true;
   }
+  API_END
+}
+// inspection of an assembled matrix: which 0 host diag block, 1 host offd block (compressed columns: GetColMapOffd),
+// 2 the diag block as the device solve format holds it
+static void parcsr_block(ParCSR &A, int which, HostCSR &tmp, const HostCSR *&blk) {
+  if (which == 0)
+    blk = &A.diag;
+  else if (which == 1)
+    blk = &A.offd;
+  else if (which == 2) {
+    if (!A.on_device) fail(HYPRE_ERROR_GENERIC, "ParCSRGetCSR: the matrix has no device mirror");
+    sk::solve_format_to_host(A.d_diag, tmp, ctx().stream);
+    blk = &tmp;
+  } else
+    fail(HYPRE_ERROR_ARG, "ParCSRGetCSR: which must be 0, 1 or 2");
+}
+HYPRE_Int HYPRE_MI_ParCSRGetCSRSize(HYPRE_ParCSRMatrix A, HYPRE_Int which, HYPRE_Int *nrows, HYPRE_Int *ncols,
+                                    HYPRE_BigInt *nnz) {
+  API_BEGIN
+  if (!A) fail(HYPRE_ERROR_ARG, "ParCSRGetCSRSize: NULL matrix");
+  ParCSR &P = *PM(A);
+  if (which == 2) {
+    if (!P.on_device) fail(HYPRE_ERROR_GENERIC, "ParCSRGetCSRSize: the matrix has no device mirror");
+    *nrows = P.d_diag.nrows, *ncols = P.d_diag.ncols, *nnz = P.d_diag.nnz;
+    return 0;
+  }
+  if (which != 0 && which != 1) fail(HYPRE_ERROR_ARG, "ParCSRGetCSRSize: which must be 0, 1 or 2");
+  const HostCSR &h = which == 0 ? P.diag : P.offd;
+  *nrows = h.nrows, *ncols = h.ncols, *nnz = h.nnz();
+  API_END
+}
+HYPRE_Int HYPRE_MI_ParCSRGetCSR(HYPRE_ParCSRMatrix A, HYPRE_Int which, HYPRE_BigInt *ia, HYPRE_Int *ja, HYPRE_Complex *a) {
+  API_BEGIN
+  if (!A) fail(HYPRE_ERROR_ARG, "ParCSRGetCSR: NULL matrix");
+  HostCSR tmp;
+  const HostCSR *h = nullptr;
+  parcsr_block(*PM(A), which, tmp, h);
+  if (ia) {
+    if (h->ia.empty())
+      std::fill(ia, ia + h->nrows + 1, (HYPRE_BigInt)0);
+    else
+      std::copy(h->ia.begin(), h->ia.end(), ia);
+  }
+  if (ja) std::copy(h->ja.begin(), h->ja.begin() + h->nnz(), ja);
+  if (a) std::copy(h->a.begin(), h->a.begin() + h->nnz(), a);
+  API_END
+}
+HYPRE_Int HYPRE_MI_ParCSRGetColMapOffd(HYPRE_ParCSRMatrix A, HYPRE_BigInt *col_map_offd) {
+  API_BEGIN
+  if (!A || !col_map_offd) fail(HYPRE_ERROR_ARG, "ParCSRGetColMapOffd: NULL argument");
+  std::copy(PM(A)->col_map_offd.begin(), PM(A)->col_map_offd.end(), col_map_offd);
   API_END
 }
 HYPRE_Int HYPRE_MI_BoomerAMGSetupHostOnly(HYPRE_Solver solver, HYPRE_ParCSRMatrix A) {
@@ -1417,7 +1536,18 @@ HYPRE_Int HYPRE_MI_GetCounter(const char *name, long long *value) {
     else fail(HYPRE_ERROR_ARG, "GetCounter: unknown counter " + n);
     return 0;
   }
-  if (n == "matvec_overlapped")
+  if (n == "ij_device_assemblies")
+    *value = ij::counters().device_assemblies;
+  else if (n == "ij_entries_fetched_to_host")
+    *value = ij::counters().entries_fetched;
+  else if (n == "ij_host_mirror_bytes")
+    *value = ij::counters().host_mirror_bytes;
+  else if (n == "ij_device_sort_lds_capacity")
+    *value = ij::SORT_LDS_CAP;
+  else if (n == "ij_last_kernels_us" || n == "ij_last_mirror_us" || n == "ij_last_format_us")
+    *value = (long long)(1e6 * (n == "ij_last_kernels_us" ? ij::counters().t_kernels
+                                : n == "ij_last_mirror_us" ? ij::counters().t_mirror : ij::counters().t_format));
+  else if (n == "matvec_overlapped")
     *value = ctx().n_matvec_overlapped;
   else if (n == "gs_overlapped")
     *value = ctx().n_gs_overlapped;
@@ -2010,5 +2140,21 @@ HYPRE_Int HYPRE_MI_Laplace3D(HYPRE_Int nx, HYPRE_Int ny, HYPRE_Int nz, HYPRE_Int
   API_END
 }
 void HYPRE_MI_Free(void *p) { free(p); }
+
+HYPRE_Int HYPRE_MI_Laplace3DDevice(HYPRE_Int nx, HYPRE_Int ny, HYPRE_Int nz, HYPRE_Int stencil, HYPRE_BigInt ilower,
+                                   HYPRE_BigInt iupper, HYPRE_BigInt *nnz_out, HYPRE_BigInt **rows_out,
+                                   HYPRE_BigInt **cols_out, HYPRE_Complex **vals_out, HYPRE_Complex **rhs_out) {
+  API_BEGIN
+  if (stencil != 7 && stencil != 27) fail(HYPRE_ERROR_ARG, "Laplace3DDevice: stencil must be 7 or 27");
+  const gidx N = (gidx)nx * ny * nz;
+  if (ilower < 0 || iupper >= N || iupper < ilower - 1) fail(HYPRE_ERROR_ARG, "Laplace3DDevice: bad row range");
+  int64_t nnz = 0;
+  ij::laplace3d_device(nx, ny, nz, stencil, ilower, iupper, &nnz, rows_out, cols_out, vals_out, rhs_out);
+  *nnz_out = nnz;
+  API_END
+}
+void HYPRE_MI_FreeDevice(void *p) {
+  if (p) (void)hipFree(p);
+}
 
 }  // extern "C"

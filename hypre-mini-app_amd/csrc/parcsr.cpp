@@ -243,6 +243,13 @@ void assemble_parcsr(Comm &comm, gidx ilower, gidx iupper, gidx jlower, gidx jup
   std::vector<gidx>().swap(cj);
   std::vector<double>().swap(cv);
   std::vector<char>().swap(cadd);
+  assemble_halo_columns_and_partition(comm, ilower, iupper, ogid, out);
+}
+
+// the end of an assembly, host or device: out.offd holds the halo block's rows and values, ogid its global column
+// ids entry by entry -> column map, compressed ids, row partition, stamp
+void assemble_halo_columns_and_partition(Comm &comm, gidx ilower, gidx iupper, const std::vector<gidx> &ogid, ParCSR &out) {
+  HostCSR &O = out.offd;
   out.col_map_offd = ogid;
   std::sort(out.col_map_offd.begin(), out.col_map_offd.end());
   out.col_map_offd.erase(std::unique(out.col_map_offd.begin(), out.col_map_offd.end()), out.col_map_offd.end());
@@ -252,7 +259,7 @@ void assemble_parcsr(Comm &comm, gidx ilower, gidx iupper, gidx jlower, gidx jup
   O.ncols = (int)out.col_map_offd.size();
   out.row_start = ilower;
   out.row_end = iupper + 1;
-  out.nrows = nrows;
+  out.nrows = (int)(iupper - ilower + 1);
   // global partition
   std::vector<gidx> starts((size_t)comm.size);
   gidx mine = ilower;
@@ -263,6 +270,11 @@ void assemble_parcsr(Comm &comm, gidx ilower, gidx iupper, gidx jlower, gidx jup
   out.row_starts.push_back(gend);
   static unsigned long long stamp = 0;
   out.assembly_stamp = ++stamp;
+}
+
+long long device_format_min_nnz() {
+  static const long long dev_min = getenv("MI_HYPRE_DEVICE_FORMAT_MIN_NNZ") ? atoll(getenv("MI_HYPRE_DEVICE_FORMAT_MIN_NNZ")) : 4000000;
+  return dev_min;
 }
 
 // ------------------------------------------------------------------ halo plan + device mirror
@@ -315,8 +327,7 @@ void ParCSR::to_device() {
   MI_REQUIRE(!host_diag_stale, "to_device: the host copy of the diag block was not built");
   // large blocks: raw upload, then row-block schedule inputs, x cache and Gauss-Seidel code bits on the device
   // (sk::to_solve_format); small ones through the host builder (DevCSR::upload) -- same result
-  static const long long dev_min = getenv("MI_HYPRE_DEVICE_FORMAT_MIN_NNZ") ? atoll(getenv("MI_HYPRE_DEVICE_FORMAT_MIN_NNZ")) : 4000000;
-  if (diag.nnz() >= dev_min) {
+  if (diag.nnz() >= device_format_min_nnz()) {
     sk::DCsr raw;
     raw.upload(diag, ctx().stream);
     sk::to_solve_format(raw, d_diag, ctx().stream);

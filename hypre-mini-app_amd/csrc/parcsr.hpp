@@ -110,6 +110,13 @@ struct IJEntryBatch {
 void assemble_parcsr(Comm &comm, gidx ilower, gidx iupper, gidx jlower, gidx jupper,
                      std::vector<IJEntryBatch> &batches, ParCSR &out);
 
+// the end of an assembly, shared by the host path above and the device path (ij_assembly.hip): from the halo block's
+// global column ids (entry by entry; out.offd holds its rows and values) the column map and the compressed ids, then the
+// row partition (collective) and a fresh assembly stamp
+void assemble_halo_columns_and_partition(Comm &comm, gidx ilower, gidx iupper, const std::vector<gidx> &ogid, ParCSR &out);
+// MI_HYPRE_DEVICE_FORMAT_MIN_NNZ: diag blocks of at least this many entries get their solve format built on the device
+long long device_format_min_nnz();
+
 bool is_device_pointer(const void *p);
 
 // The solve format keeps 32-bit local row ids per rank; a rank's DIAGONAL block may hold any number of entries (64-bit

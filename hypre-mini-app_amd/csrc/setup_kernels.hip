@@ -1916,6 +1916,8 @@ inline int row_group(long long nnz, long long n) {
 }  // namespace
 
 // ---------------------------------------------------------------- host-facing entry points
+void exclusive_scan_counts(const int *in, long long *out, long long n, hipStream_t s) { exclusive_scan(in, out, n, s); }
+
 void DCsr::upload(const HostCSR &h, hipStream_t s) {
   ensure_init();
   nrows = h.nrows;

@@ -70,6 +70,9 @@ void sparsify_non_galerkin(DCsr &A, double tol, hipStream_t s, int row0 = 0, con
 // m[row0 + i] = max_{j != row0 + i} |a_ij| for the rows of A
 void non_galerkin_row_maxima(const DCsr &A, int row0, double *m, hipStream_t s);
 
+// out[0..n] = exclusive scan of the counts in[0..n) with 64-bit sums (out[n] = the total); complete on return
+void exclusive_scan_counts(const int *in, long long *out, long long n, hipStream_t s);
+
 // T = A^T with ascending columns in every row (entries of one output row keep
 // the order of A's rows)
 void transpose(const DCsr &A, DCsr &T, hipStream_t s);

@@ -601,6 +601,14 @@ void HypreSystem::assemble_system() {
   if (iproc_ == 0) printf("Assembling HYPRE data structures\n");
   HYPRE_IJMatrixAssemble(mat_);
   HYPRE_IJMatrixGetObject(mat_, (void **)&parMat_);
+#ifndef MI_HOST_WITH_LIBHYPRE
+  if (device_assembly()) {
+    long long on_device = 0, fetched = 0;
+    HYPRE_MI_GetCounter("ij_device_assemblies", &on_device);
+    HYPRE_MI_GetCounter("ij_entries_fetched_to_host", &fetched);
+    if (iproc_ == 0) printf("\tmi_device_assembly: %lld matrix assembled on the device, %lld entries fetched to the host\n", on_device, fetched);
+  }
+#endif
   for (int i = 0; i < numSolves_; ++i) {
     HYPRE_IJVectorAssemble(rhs_[(size_t)i]);
     HYPRE_IJVectorAssemble(sln_[(size_t)i]);
@@ -800,11 +808,39 @@ void HypreSystem::summarize_timers() {
     std::cout << "    " << std::setw(25) << std::left << t.first << t.second << " seconds" << std::endl;
 }
 
+// linear_system: mi_device_assembly: 1 -- the entries and the vector indices are handed over in device memory, as the
+// reference's GPU build does (/root/reference/src/HypreSystem.cpp:907-945, :989-1005); the library then assembles on
+// the device.  Off by default.
+bool HypreSystem::device_assembly() {
+  YAML::Node linsys = inpfile_["linear_system"];
+  return get_optional(linsys, "mi_device_assembly", 0) != 0;
+}
+
+namespace {
+template <class T>
+T *to_device(const T *h, size_t n) {
+  T *d = hypre_TAlloc(T, n ? n : 1, HYPRE_MEMORY_DEVICE);
+  if (!d) throw std::runtime_error("mi_device_assembly: out of device memory");
+  if (n) hypre_TMemcpy(d, h, T, n, HYPRE_MEMORY_DEVICE, HYPRE_MEMORY_HOST);
+  return d;
+}
+}  // namespace
+
 // /root/reference/src/HypreSystem.cpp:897-955: one entry per "row", ncols == NULL.
 // Host pointers go in; the library stages them itself.
 void HypreSystem::hypre_matrix_set_values() {
   if (iproc_ == 0) printf("%s : loading matrix into HYPRE_IJMatrix\n", __FUNCTION__);
   const size_t step = (size_t)1 << 30;  // HYPRE_Int nrows
+  if (device_assembly()) {
+    HYPRE_BigInt *dr = to_device(rows_.data(), rows_.size()), *dc = to_device(cols_.data(), cols_.size());
+    HYPRE_Complex *dv = to_device(vals_.data(), vals_.size());
+    for (size_t s = 0; s < vals_.size(); s += step) {
+      const size_t e = std::min(vals_.size(), s + step);
+      HYPRE_IJMatrixSetValues2(mat_, (HYPRE_Int)(e - s), NULL, dr + s, NULL, dc + s, dv + s);
+    }
+    hypre_TFree(dr, HYPRE_MEMORY_DEVICE), hypre_TFree(dc, HYPRE_MEMORY_DEVICE), hypre_TFree(dv, HYPRE_MEMORY_DEVICE);
+    return;
+  }
   for (size_t s = 0; s < vals_.size(); s += step) {
     const size_t e = std::min(vals_.size(), s + step);
     HYPRE_IJMatrixSetValues2(mat_, (HYPRE_Int)(e - s), NULL, rows_.data() + s, NULL, cols_.data() + s,
@@ -822,7 +858,12 @@ void HypreSystem::hypre_vector_set_values(std::vector<HYPRE_IJVector> &vec, int 
     v = vec[(size_t)component];
     HYPRE_IJVectorSetComponent(v, 0);
   }
-  if (!vector_values_.empty())
+  if (!vector_values_.empty() && device_assembly()) {
+    HYPRE_BigInt *di = to_device(vector_indices_.data(), vector_values_.size());
+    HYPRE_Complex *dv = to_device(vector_values_.data(), vector_values_.size());
+    HYPRE_IJVectorSetValues(v, (HYPRE_Int)vector_values_.size(), di, dv);
+    hypre_TFree(di, HYPRE_MEMORY_DEVICE), hypre_TFree(dv, HYPRE_MEMORY_DEVICE);
+  } else if (!vector_values_.empty())
     HYPRE_IJVectorSetValues(v, (HYPRE_Int)vector_values_.size(), vector_indices_.data(), vector_values_.data());
 }
 
@@ -1138,7 +1179,9 @@ void HypreSystem::build_stencil(int default_stencil, bool per_rank_dims) {
     M_ = N_ = (int)totalRows_;
     init_row_decomposition();
     init_system();
-    if (HYPRE_MI_Laplace3D(nx_, ny_, nz_, stencil, iLower_, iUpper_, &nnz, &rows, &cols, &vals, &rhs))
+    const bool on_device = device_assembly();
+    if ((on_device ? HYPRE_MI_Laplace3DDevice : HYPRE_MI_Laplace3D)(nx_, ny_, nz_, stencil, iLower_, iUpper_, &nnz, &rows, &cols,
+                                                                    &vals, &rhs))
       throw std::runtime_error("synthetic generator failed");
     const size_t step = (size_t)1 << 30;
     for (size_t s = 0; s < (size_t)nnz; s += step) {
@@ -1148,8 +1191,15 @@ void HypreSystem::build_stencil(int default_stencil, bool per_rank_dims) {
     vector_indices_.resize((size_t)numRows_);
     for (HYPRE_BigInt i = 0; i < numRows_; i++) vector_indices_[(size_t)i] = iLower_ + i;
     HYPRE_IJVectorSetComponent(rhs_[0], 0);
-    HYPRE_IJVectorSetValues(rhs_[0], (HYPRE_Int)numRows_, vector_indices_.data(), rhs);
-    HYPRE_MI_Free(rows), HYPRE_MI_Free(cols), HYPRE_MI_Free(vals), HYPRE_MI_Free(rhs);
+    if (on_device) {
+      HYPRE_BigInt *di = to_device(vector_indices_.data(), vector_indices_.size());
+      HYPRE_IJVectorSetValues(rhs_[0], (HYPRE_Int)numRows_, di, rhs);
+      hypre_TFree(di, HYPRE_MEMORY_DEVICE);
+      HYPRE_MI_FreeDevice(rows), HYPRE_MI_FreeDevice(cols), HYPRE_MI_FreeDevice(vals), HYPRE_MI_FreeDevice(rhs);
+    } else {
+      HYPRE_IJVectorSetValues(rhs_[0], (HYPRE_Int)numRows_, vector_indices_.data(), rhs);
+      HYPRE_MI_Free(rows), HYPRE_MI_Free(cols), HYPRE_MI_Free(vals), HYPRE_MI_Free(rhs);
+    }
   } else {
     int npx, npy, npz;
     process_grid(nproc_, npx, npy, npz);

@@ -60,6 +60,7 @@ class HypreSystem {
   void load_matrix_market();
   void load_hypre_format();
   void build_stencil(int default_stencil, bool per_rank_dims);
+  bool device_assembly();  // linear_system: mi_device_assembly
   void determine_ij_system_sizes(const std::string &, int);
   void determine_mm_system_sizes(const std::string &);
   void init_row_decomposition();

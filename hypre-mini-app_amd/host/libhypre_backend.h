@@ -46,4 +46,35 @@ inline int HYPRE_MI_Laplace3D(int nx, int ny, int nz, int stencil, HYPRE_BigInt 
   return 0;
 }
 inline void HYPRE_MI_Free(void *p) { free(p); }
+// the same arrays in libHYPRE's device memory space (linear_system: mi_device_assembly; host memory in a CPU build)
+inline int HYPRE_MI_Laplace3DDevice(int nx, int ny, int nz, int stencil, HYPRE_BigInt ilower, HYPRE_BigInt iupper,
+                                    HYPRE_BigInt *nnz, HYPRE_BigInt **rows, HYPRE_BigInt **cols, HYPRE_Complex **vals,
+                                    HYPRE_Complex **rhs) {
+  // (never compiled where this was written -- no libHYPRE there; whoever builds app-libhypre first: check it)
+  HYPRE_BigInt *r = nullptr, *c = nullptr;
+  HYPRE_Complex *v = nullptr, *b = nullptr;
+  const int rc = HYPRE_MI_Laplace3D(nx, ny, nz, stencil, ilower, iupper, nnz, &r, &c, &v, &b);
+  if (rc || !r || !c || !v || !b) {
+    free(r), free(c), free(v), free(b);
+    return rc ? rc : 1;
+  }
+  const size_t ne = (size_t)*nnz + 1, nr = (size_t)(iupper - ilower + 1) + 1;
+  *rows = hypre_TAlloc(HYPRE_BigInt, ne, HYPRE_MEMORY_DEVICE);
+  *cols = hypre_TAlloc(HYPRE_BigInt, ne, HYPRE_MEMORY_DEVICE);
+  *vals = hypre_TAlloc(HYPRE_Complex, ne, HYPRE_MEMORY_DEVICE);
+  *rhs = hypre_TAlloc(HYPRE_Complex, nr, HYPRE_MEMORY_DEVICE);
+  if (!*rows || !*cols || !*vals || !*rhs) {
+    hypre_Free(*rows, HYPRE_MEMORY_DEVICE), hypre_Free(*cols, HYPRE_MEMORY_DEVICE);
+    hypre_Free(*vals, HYPRE_MEMORY_DEVICE), hypre_Free(*rhs, HYPRE_MEMORY_DEVICE);
+    free(r), free(c), free(v), free(b);
+    return 2;
+  }
+  hypre_TMemcpy(*rows, r, HYPRE_BigInt, ne - 1, HYPRE_MEMORY_DEVICE, HYPRE_MEMORY_HOST);
+  hypre_TMemcpy(*cols, c, HYPRE_BigInt, ne - 1, HYPRE_MEMORY_DEVICE, HYPRE_MEMORY_HOST);
+  hypre_TMemcpy(*vals, v, HYPRE_Complex, ne - 1, HYPRE_MEMORY_DEVICE, HYPRE_MEMORY_HOST);
+  hypre_TMemcpy(*rhs, b, HYPRE_Complex, nr - 1, HYPRE_MEMORY_DEVICE, HYPRE_MEMORY_HOST);
+  free(r), free(c), free(v), free(b);
+  return 0;
+}
+inline void HYPRE_MI_FreeDevice(void *p) { hypre_Free(p, HYPRE_MEMORY_DEVICE); }
 #endif

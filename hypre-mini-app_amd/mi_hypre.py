@@ -141,6 +141,13 @@ class IJMatrix:
             e = min(n, s + step)
             call(fn, self.h, e - s, None, vp(rows_ptr + 8 * s), None, vp(cols_ptr + 8 * s), vp(vals_ptr + 8 * s))
 
+    def set_values_rows_ptr(self, nrows, ncols_ptr, rows_ptr, row_indexes_ptr, cols_ptr, vals_ptr, add=False):
+        """The ncols / row_indexes form: row rows[i] gets ncols[i] entries that start at row_indexes[i] of cols / vals
+        (row_indexes_ptr None or 0: packed one row after the other).  Pointers are host or device addresses."""
+        fn = "HYPRE_IJMatrixAddToValues2" if add else "HYPRE_IJMatrixSetValues2"
+        call(fn, self.h, nrows, vp(ncols_ptr), vp(rows_ptr), vp(row_indexes_ptr) if row_indexes_ptr else None,
+             vp(cols_ptr), vp(vals_ptr))
+
     def assemble(self):
         call("HYPRE_IJMatrixAssemble", self.h)
         call("HYPRE_IJMatrixGetObject", self.h, C.byref(self.par))
@@ -684,6 +691,54 @@ def laplace3d_free(g):
         if g.get(k):
             lib().HYPRE_MI_Free(vp(g[k]))
             g[k] = None
+
+
+def laplace3d_device(nx, ny, nz, stencil, ilower, iupper):
+    """laplace3d with the arrays generated into device memory (addresses of device arrays; laplace3d_device_free)."""
+    nnz = c_big()
+    rows, cols, vals, rhs = vp(), vp(), vp(), vp()
+    call("HYPRE_MI_Laplace3DDevice", nx, ny, nz, stencil, c_big(ilower), c_big(iupper), C.byref(nnz), C.byref(rows),
+         C.byref(cols), C.byref(vals), C.byref(rhs))
+    return dict(nnz=nnz.value, rows=rows.value, cols=cols.value, vals=vals.value, rhs=rhs.value,
+                nloc=iupper - ilower + 1)
+
+
+def laplace3d_device_free(g):
+    lib().HYPRE_MI_FreeDevice.argtypes = [vp]
+    lib().HYPRE_MI_FreeDevice.restype = None
+    for k in ("rows", "cols", "vals", "rhs"):
+        if g.get(k):
+            lib().HYPRE_MI_FreeDevice(vp(g[k]))
+            g[k] = None
+
+
+def counter(name):
+    v = C.c_longlong()
+    call("HYPRE_MI_GetCounter", name.encode(), C.byref(v))
+    return v.value
+
+
+def parcsr_csr(A, which):
+    """A block of an assembled matrix: which 0 host diag, 1 host offd (compressed columns), 2 the diag block as the
+    device solve format holds it -> (ia int64, ja int32, a f64, shape)."""
+    par = A.par if hasattr(A, "par") else A
+    nr, nc, nnz = c_int(), c_int(), c_big()
+    call("HYPRE_MI_ParCSRGetCSRSize", par, which, C.byref(nr), C.byref(nc), C.byref(nnz))
+    ia = np.zeros(nr.value + 1, dtype=np.int64)
+    ja = np.zeros(max(nnz.value, 1), dtype=np.int32)
+    a = np.zeros(max(nnz.value, 1), dtype=np.float64)
+    call("HYPRE_MI_ParCSRGetCSR", par, which, ia, ja, a)
+    return ia, ja[: nnz.value], a[: nnz.value], (nr.value, nc.value)
+
+
+def parcsr_colmap(A):
+    """sorted global column ids of the offd block's compressed columns"""
+    par = A.par if hasattr(A, "par") else A
+    nr, nc, nnz = c_int(), c_int(), c_big()
+    call("HYPRE_MI_ParCSRGetCSRSize", par, 1, C.byref(nr), C.byref(nc), C.byref(nnz))
+    cm = np.zeros(max(nc.value, 1), dtype=np.int64)
+    call("HYPRE_MI_ParCSRGetColMapOffd", par, cm)
+    return cm[: nc.value]
 
 
 def build_laplace_system(nx, ny, nz, stencil=7, rank=0, size=1):

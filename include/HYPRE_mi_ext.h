@@ -63,6 +63,14 @@ HYPRE_Int HYPRE_MI_ParCSRGetHaloPlan(HYPRE_ParCSRMatrix A, HYPRE_Int *nsend_peer
                                      HYPRE_Int *send_starts, HYPRE_Int *send_map, HYPRE_Int *nrecv_peers,
                                      HYPRE_Int *recv_peers, HYPRE_Int *recv_starts);
 
+/* ---- an assembled matrix as the library holds it (tests of the IJ assembly).  which: 0 the host copy of the diag
+ * block (local columns), 1 the host copy of the offd block (compressed columns; their global ids: GetColMapOffd, ncols
+ * entries), 2 the diag block read back from the device solve format.  0 and 1 need no device.  Arrays may be NULL. */
+HYPRE_Int HYPRE_MI_ParCSRGetCSRSize(HYPRE_ParCSRMatrix A, HYPRE_Int which, HYPRE_Int *nrows, HYPRE_Int *ncols,
+                                    HYPRE_BigInt *nnz);
+HYPRE_Int HYPRE_MI_ParCSRGetCSR(HYPRE_ParCSRMatrix A, HYPRE_Int which, HYPRE_BigInt *ia, HYPRE_Int *ja, HYPRE_Complex *a);
+HYPRE_Int HYPRE_MI_ParCSRGetColMapOffd(HYPRE_ParCSRMatrix A, HYPRE_BigInt *col_map_offd);
+
 /* ---- device / stream */
 HYPRE_Int HYPRE_MI_GetStream(void **hip_stream);
 HYPRE_Int HYPRE_MI_StreamSynchronize(void);
@@ -101,7 +109,12 @@ HYPRE_Int HYPRE_MI_SetValueDictionary(HYPRE_Int on);
  * "halo_exchange" (neighbour send/recv groups), "allgather" (coarsest / redundant levels); the distributed setup:
  * "setup_distributed" (count), "setup_ext_rows_max" (largest per-rank extended sub-problem, rows),
  * "setup_global_rows_gathered" (rows gathered on every rank: the redundant tail only), "setup_device_levels" (levels
- * of the distributed setup whose per-rank pieces were built on the device). */
+ * of the distributed setup whose per-rank pieces were built on the device).
+ * IJ assembly: "ij_device_assemblies" (matrices whose batches all arrived in device memory and
+ * were assembled there; MI_HYPRE_DEVICE_ASSEMBLY=0 turns the path off), "ij_entries_fetched_to_host" (entries of matrix
+ * batches and vector indices copied device -> host: zero for a device assembly), "ij_host_mirror_bytes" (host mirrors
+ * downloaded by device assemblies), "ij_device_sort_lds_capacity" (rows with more entries are sorted by the any-length
+ * path), "ij_last_kernels_us" / "ij_last_mirror_us" / "ij_last_format_us" (phases of the last device assembly). */
 HYPRE_Int HYPRE_MI_GetCounter(const char *name, long long *value);
 /* One rank's block keeps 32-bit local row ids in the solve format; the entry offsets of its diagonal block are 64-bit
  * (the reference's 27-point operator at 512^3 -- 3.6e9 entries, /root/reference/src/laplace_3d_weak_scaling.hpp:558,600
@@ -228,6 +241,12 @@ HYPRE_Int HYPRE_MI_Laplace3D(HYPRE_Int nx, HYPRE_Int ny, HYPRE_Int nz, HYPRE_Int
                              HYPRE_BigInt iupper, HYPRE_BigInt *nnz, HYPRE_BigInt **rows, HYPRE_BigInt **cols,
                              HYPRE_Complex **vals, HYPRE_Complex **rhs);
 void HYPRE_MI_Free(void *p);
+/* the same arrays generated by a kernel into DEVICE memory (row offsets from a scan of the per-row counts); released
+ * with HYPRE_MI_FreeDevice */
+HYPRE_Int HYPRE_MI_Laplace3DDevice(HYPRE_Int nx, HYPRE_Int ny, HYPRE_Int nz, HYPRE_Int stencil, HYPRE_BigInt ilower,
+                                   HYPRE_BigInt iupper, HYPRE_BigInt *nnz, HYPRE_BigInt **rows, HYPRE_BigInt **cols,
+                                   HYPRE_Complex **vals, HYPRE_Complex **rhs);
+void HYPRE_MI_FreeDevice(void *p);
 
 #ifdef __cplusplus
 }
