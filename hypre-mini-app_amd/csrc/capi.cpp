@@ -1874,6 +1874,28 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCF(HYPRE_Solver solver, HYPRE_Int level, HYP
   for (size_t i = 0; i < v.size(); i++) cf[i] = v[i];
   API_END
 }
+// diagonal and signed l1 norms of a level as the smoothers divide by them: from the host vectors of a level set up on
+// the host, from the device vectors of a level set up on the device
+HYPRE_Int HYPRE_MI_BoomerAMGGetLevelNorms(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Real *diag, HYPRE_Real *l1gs,
+                                          HYPRE_Real *l1jac) {
+  API_BEGIN
+  AmgSolver *a = AMG(solver);
+  AmgLevel &Lv = level_ref(a, level);
+  const size_t n = (size_t)Lv.A->nrows;
+  auto get = [&](HYPRE_Real *out, const std::vector<double> &h, const DVec<double> &d) {
+    if (!out || n == 0) return;
+    if (h.size() == n)
+      std::copy(h.begin(), h.end(), out);
+    else if (d.p)
+      MI_HIP(hipMemcpy(out, d.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    else
+      fail(HYPRE_ERROR_GENERIC, "GetLevelNorms: the level has no norms (Setup did not finish)");
+  };
+  get(diag, Lv.diag, Lv.d_diag);
+  get(l1gs, Lv.l1gs, Lv.d_l1gs);
+  get(l1jac, Lv.l1jac, Lv.d_l1jac);
+  API_END
+}
 // markers of the two coarsening stages of an aggressive level built with agg_interp_type 5, in the level's reported
 // (C-first) ordering: the C points of the final marker first, the others after, both groups in natural order
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelAggMarkers(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int *stage1, HYPRE_Int *stage2) {

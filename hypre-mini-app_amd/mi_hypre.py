@@ -264,6 +264,7 @@ class BoomerAMG:
         call("HYPRE_BoomerAMGSetMaxLevels", s, cfg["max_levels"])
         call("HYPRE_BoomerAMGSetStrongThreshold", s, float(cfg["strong_threshold"]))
         for key, fn, conv in (("interp_type", "HYPRE_BoomerAMGSetInterpType", int),
+                              ("max_row_sum", "HYPRE_BoomerAMGSetMaxRowSum", float),
                               ("min_coarse_size", "HYPRE_BoomerAMGSetMinCoarseSize", int),
                               ("max_coarse_size", "HYPRE_BoomerAMGSetMaxCoarseSize", int),
                               ("seq_threshold", "HYPRE_BoomerAMGSetSeqThreshold", int),
@@ -366,6 +367,14 @@ class BoomerAMG:
         cf = np.zeros(nr.value, dtype=np.int32)
         call("HYPRE_MI_BoomerAMGGetLevelCF", self.h, level, cf)
         return cf
+
+    def level_norms(self, level):
+        """(diagonal, signed l1 norm of the hybrid-GS chunks, signed full l1 norm) of a level, level_csr's rows."""
+        nr, nc, nnz = c_int(), c_int(), c_big()
+        call("HYPRE_MI_BoomerAMGGetLevelCSRSize", self.h, level, 0, C.byref(nr), C.byref(nc), C.byref(nnz))
+        out = [np.zeros(nr.value, dtype=np.float64) for _ in range(3)]
+        call("HYPRE_MI_BoomerAMGGetLevelNorms", self.h, level, *out)
+        return tuple(out)
 
     def level_agg_markers(self, level):
         """(stage-1 marker, stage-2 marker) of an aggressive level built with agg_interp_type 5, level_csr's rows."""

@@ -153,6 +153,11 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCSRSize(HYPRE_Solver solver, HYPRE_Int level
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCSR(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int which, HYPRE_BigInt *ia,
                                         HYPRE_Int *ja, HYPRE_Complex *a);
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCF(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int *cf);
+/* What the smoothers of a level divide by, in GetLevelCSR's row numbering: the diagonal, the l1 norm of the hybrid
+ * Gauss-Seidel chunks (C/F aware, replaced by |a_ii| where it is at most 4/3 of it) and the full l1 norm of the row;
+ * both norms carry the sign of the diagonal.  Any array may be NULL. */
+HYPRE_Int HYPRE_MI_BoomerAMGGetLevelNorms(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Real *diag, HYPRE_Real *l1gs,
+                                          HYPRE_Real *l1jac);
 /* Value storage of the operators (A, P, R, the zero-guess sub-operators) of the AMG levels >= first_level; call before
  * Setup.  mode 0: fp64 (the default), 1: the values are stored and streamed as fp32 and widened to fp64 where a
  * product is formed, 2: fp64 storage holding the fp32-rounded values (the reference semantics of mode 1: every

@@ -75,7 +75,15 @@ def main():
                     help="callbacks (gloo through host staging) | ipc (halo exchanges by peer stores into IPC-mapped "
                          "mailboxes, HYPRE_MI_CommEnablePeerStoreExchange; reductions stay on the callbacks) | tcp (the "
                          "library's own TCP mesh, MI_HYPRE_TRANSPORT=tcp)")
+    ap.add_argument("--signs", type=int, default=0,
+                    help="with --random: 1 = 30 %% of the couplings positive (0.4 of their size); 2 = also the whole "
+                         "operator and right-hand side negated; 3 = 1 plus 30 %% of the rows multiplied by -1 (negative "
+                         "diagonals among positive ones; host mode only: its solves are not known to converge)")
     args = ap.parse_args()
+    if args.signs and not args.random:
+        ap.error("--signs needs --random")
+    if args.signs not in (0, 1, 2, 3) or (args.signs == 3 and args.mode != "host"):
+        ap.error("--signs is 0, 1, 2, or (host mode only) 3")
     import torch
     import torch.distributed as dist
 
@@ -115,6 +123,22 @@ def main():
         R.eliminate_zeros()
         Mr = (-abs(R) + sp.diags(np.asarray(abs(R).sum(axis=1)).ravel() * float(rng.choice([1.0, 1.02, 1.2])) + 1e-3)).tocsr()
         Mr.sort_indices()
+        if args.signs:
+            # not an M-matrix any more (a stream of its own: the operators of --signs 0 stay what they were)
+            rs = np.random.default_rng(9900 + args.grid)
+            dg = Mr.diagonal()
+            off = (Mr - sp.diags(dg)).tocsr()
+            off.eliminate_zeros()
+            off.sort_indices()
+            pos = rs.random(off.nnz) < 0.3
+            off.data[pos] = 0.4 * np.abs(off.data[pos])
+            scale = np.ones(N)
+            if args.signs == 2:
+                scale[:] = -1.0
+            if args.signs == 3:
+                scale[rs.random(N) < 0.3] = -1.0
+            Mr = (sp.diags(scale) @ (off + sp.diags(dg))).tocsr()
+            Mr.sort_indices()
         Ao, bo = oc.Csr.from_scipy(Mr), np.asarray(Mr @ np.ones(N))
     else:
         Ao, bo = oc.Csr.laplace(n, n, n, st)

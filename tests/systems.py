@@ -46,3 +46,33 @@ def three_component_rhs(A, seed=99):
     t = np.linspace(0.0, 1.0, N)
     xs = np.stack([1.0 + 0.0 * t, np.sin(6.0 * t) + 0.1 * rng.standard_normal(N), rng.standard_normal(N)])
     return np.stack([A @ x for x in xs]), xs
+
+
+def mixed_sign_system(n, seed, flip_rows, pos_frac, per, symmetric_pattern=True):
+    """An operator that is NOT an M-matrix (sorted CSR): a seeded random pattern of about `per` draws per row
+    (symmetrised unless symmetric_pattern=False, so roughly twice as many entries), couplings -|v| - 0.1 of which the
+    fraction pos_frac is turned into small positive ones (0.4 |v|), a diagonal that dominates the row by up to 20 %,
+    and the fraction flip_rows of the rows multiplied by -1: negative diagonals with positive couplings, the mirrored
+    branch of the strength rule, of the interpolation formulas and of the l1 norms."""
+    rng = np.random.default_rng(seed)
+    B = sp.random(n, n, density=per / n, random_state=rng, format="csr")
+    if symmetric_pattern:
+        B = (B + B.T).tocsr()
+    B = (B - sp.diags(B.diagonal())).tocsr()
+    B.eliminate_zeros()
+    B.sort_indices()
+    B.data = -np.abs(B.data) - 0.1
+    pos = rng.random(B.nnz) < pos_frac
+    B.data[pos] = 0.4 * np.abs(B.data[pos])
+    d = np.asarray(abs(B).sum(axis=1)).ravel() * (1.0 + 0.2 * rng.random(n)) + 1e-3
+    flip = rng.random(n) < flip_rows
+    M = (sp.diags(np.where(flip, -1.0, 1.0)) @ (B + sp.diags(d))).tocsr()
+    M.sort_indices()
+    return M
+
+
+# the operators of the mixed-sign tests: (n, seed, flip_rows, pos_frac, per); 4 to 89 entries per row on average, so
+# that the setup kernels pick 4, 8, 16, 32 and 64 lanes per row; the last two are the pure cases (every diagonal
+# negative with M-matrix magnitudes; every diagonal positive with 35 % positive couplings)
+MIXED_SIGN_CASES = [(2000, 43, .3, .25, 1.5), (2000, 49, .3, .25, 4.5), (2000, 58, .5, .3, 9), (1500, 76, .3, .25, 18),
+                    (1200, 130, .3, .25, 45), (2000, 49, 1.0, 0, 4.5), (2000, 49, 0, .35, 4.5)]

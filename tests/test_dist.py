@@ -18,7 +18,8 @@ WORKER = os.path.join(ROOT, "tests", "dist_worker.py")
 
 
 def _run(nproc, mode, n, stencil, port, staging="host", seq=-1, devmin=None, golden="", replicated=False, locality=0,
-         smooth=0, relax=0, combo=-1, transport="", ng=0.0, agg=0, interp=-1, aggtrunc=0.0, aggpmax=0, coarsen=-1, random=0):
+         smooth=0, relax=0, combo=-1, transport="", ng=0.0, agg=0, interp=-1, aggtrunc=0.0, aggpmax=0, coarsen=-1, random=0,
+         signs=0):
     env = dict(os.environ)
     env["MI_HYPRE_REPLICATED_SETUP"] = "1" if replicated else "0"
     if devmin is not None:  # levels with at least this many rows are built (and sliced) on the device
@@ -52,6 +53,8 @@ def _run(nproc, mode, n, stencil, port, staging="host", seq=-1, devmin=None, gol
         cmd += ["--coarsen", str(coarsen)]
     if random:
         cmd += ["--random", str(random)]
+    if signs:
+        cmd += ["--signs", str(signs)]
     if nproc >= 5:
         # without the torch.distributed.run launcher: on a GPU box it holds the device open too, and launcher + pytest + 5
         # ranks are 7 processes on a card that admits 6
@@ -182,6 +185,18 @@ def test_host_setup_random_operators_distributed_gloo(nproc, rows, seed, seq, co
     assert "dist host setup ok" in out
 
 
+@pytest.mark.parametrize("nproc,rows,seed,seq,coarsen,agg,interp,ng,signs",
+                         [(3, 1200, 3, 0, -1, 0, -1, 0.0, 1), (4, 1500, 4, 0, -1, 0, 0, 0.0, 2), (2, 1300, 5, 0, -1, 0, -1, 0.0, 3),
+                          (4, 1600, 7, 0, -1, 0, 0, 0.0, 3), (3, 1400, 11, 100, 10, 0, -1, 0.05, 3), (4, 1500, 12, 0, 6, 1, -1, 0.0, 3)])
+def test_host_setup_mixed_sign_operators_distributed_gloo(nproc, rows, seed, seq, coarsen, agg, interp, ng, signs):
+    """The same on operators that are not M-matrices (tests/dist_worker.py --signs): 30 % positive couplings (1), the
+    whole system negated as well (2), 30 % of the rows multiplied by -1 (3) -- the mirrored strength rule of the
+    distributed setup and the sign handling of its interpolation routines, level by level against the oracle."""
+    out = _run(nproc, "host", seed, 7, 31211 + 10 * signs + nproc + seed, seq=seq, coarsen=coarsen, agg=agg, interp=interp, ng=ng,
+               random=rows, signs=signs)
+    assert "dist host setup ok" in out
+
+
 @pytest.mark.parametrize("nproc,n,stencil,seq,coarsen,agg", [(2, 12, 7, 0, -1, 0), (4, 12, 27, 100, 6, 0), (8, 10, 7, 0, -1, 1)])
 def test_host_setup_tcp_transport_gloo_free(nproc, n, stencil, seq, coarsen, agg):
     """The library's own host transport (csrc/comm.cpp TcpMesh, MI_HYPRE_TRANSPORT=tcp, bound by
@@ -291,6 +306,15 @@ def test_device_solve_random_operators_shared_gpu(nproc, rows, seed, seq, devmin
     third-rank owners) through the distributed setup -- device-resident levels with the threshold at 0, the host loop
     otherwise -- and the device solve: hierarchy, halo plans, iterations, residual history, solution vs the oracle."""
     out = _run(nproc, "solve", seed, 7, 30751 + nproc + seed, seq=seq, devmin=devmin, coarsen=coarsen, agg=agg, random=rows)
+    assert "dist solve ok" in out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nproc,rows,seed,seq,signs", [(3, 3000, 31, 0, 1), (4, 4000, 32, 0, 2), (2, 3500, 33, 0, 2)])
+def test_device_solve_mixed_sign_operators_shared_gpu(nproc, rows, seed, seq, signs):
+    """Operators with 30 % positive couplings (signs 1) and their negatives (2: every diagonal negative, the mirrored
+    branches) through the distributed setup with every level on the device, and the device solve, against the oracle."""
+    out = _run(nproc, "solve", seed, 7, 31311 + 10 * signs + nproc + seed, seq=seq, devmin=0, random=rows, signs=signs)
     assert "dist solve ok" in out
 
 

@@ -13,6 +13,8 @@ import pytest
 import scipy.sparse as sp
 import scipy.sparse.linalg as spl
 
+from tests.interp_ref import classical_modified_reference, extended_i_reference, strength_pattern
+
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
@@ -336,19 +338,9 @@ def test_iluk_pattern_factor_and_limit(oc, fill):
 # 512^3 (profiles/r02_agg_sideline_512.txt) come from the method or from a deviation.
 # ---------------------------------------------------------------------------------------------------------------
 def _strength_pattern(A, theta=0.57):
-    """a_ij strong iff a_ij < theta * min_k a_ik (a_ii > 0): CSR 0/1 pattern, diagonal excluded."""
-    A = A.tocsr()
-    rows, cols = [], []
-    for i in range(A.shape[0]):
-        c, v = A.indices[A.indptr[i]:A.indptr[i + 1]], A.data[A.indptr[i]:A.indptr[i + 1]]
-        off = c != i
-        if not off.any():
-            continue
-        mn = v[off].min()
-        sel = off & (v < theta * mn)
-        rows += [i] * int(sel.sum())
-        cols += list(c[sel])
-    return sp.csr_matrix((np.ones(len(rows)), (rows, cols)), shape=A.shape)
+    """0/1 CSR pattern of the strength graph, diagonal excluded (tests/interp_ref.py: the mirrored rule for negative
+    diagonals and the oracle's default max_row_sum included)."""
+    return strength_pattern(A, theta)
 
 
 def _multipass_reference(A, S, cf, special):
@@ -465,52 +457,7 @@ def test_aggressive_coarsening_and_multipass_against_an_independent_restatement(
 # ("distance-two interpolation for parallel algebraic multigrid", the extended+i formula).  Written for the test,
 # sharing no code with oracle.c / amg_setup.cpp.
 # ---------------------------------------------------------------------------------------------------------------
-def _extended_i_reference(A, S, cf):
-    """P (no truncation) by the extended+i formula: for an F point i with strong C neighbours C_i, strong F neighbours
-    F_i and Chat_i = C_i U (U_{k in F_i} C_k):
-        w_ij = -(1 / att_i) (a_ij + sum_{k in F_i} a_ik abar_kj / d_ik),  j in Chat_i,
-        att_i = a_ii + sum_{n weak neighbour of i, n not in Chat_i} a_in + sum_{k in F_i} a_ik abar_ki / d_ik,
-        d_ik = sum_{l in Chat_i U {i}} abar_kl,   abar_kl = a_kl if its sign differs from a_kk's, else 0."""
-    A, S = A.tocsr(), S.tocsr()
-    n = A.shape[0]
-    rows = [dict(zip(A.indices[A.indptr[i]:A.indptr[i + 1]], A.data[A.indptr[i]:A.indptr[i + 1]])) for i in range(n)]
-    strong = [set(S.indices[S.indptr[i]:S.indptr[i + 1]]) for i in range(n)]
-    cidx = -np.ones(n, dtype=int)
-    cidx[cf == 1] = np.arange(int((cf == 1).sum()))
-    P = sp.lil_matrix((n, int((cf == 1).sum())))
-
-    def abar(k, l):
-        v = rows[k].get(l, 0.0)
-        return v if v * rows[k][k] < 0 else 0.0
-
-    for i in range(n):
-        if cf[i] == 1:
-            P[i, cidx[i]] = 1.0
-            continue
-        Ci = [j for j in strong[i] if cf[j] == 1]
-        Fi = [k for k in strong[i] if cf[k] != 1]
-        chat = set(Ci)
-        for k in Fi:
-            chat |= {j for j in strong[k] if cf[j] == 1}
-        if not chat:
-            continue
-        att = rows[i][i]
-        for nb, v in rows[i].items():
-            if nb != i and nb not in strong[i] and nb not in chat:
-                att += v
-        w = {j: rows[i].get(j, 0.0) for j in chat}
-        for k in Fi:
-            d = sum(abar(k, l) for l in chat | {i})
-            if d == 0.0:
-                att += rows[i][k]
-                continue
-            f = rows[i][k] / d
-            for j in chat:
-                w[j] += f * abar(k, j)
-            att += f * abar(k, i)
-        for j, v in w.items():
-            P[i, cidx[j]] = -v / att
-    return P.tocsr()
+_extended_i_reference = extended_i_reference   # (tests/interp_ref.py)
 
 
 @pytest.mark.parametrize("n,stencil", [(10, 7), (7, 27)])
@@ -567,35 +514,7 @@ def test_extended_i_with_weak_connections_and_classical_modified(oc):
     Al.sort_indices()
     cf = np.asarray(amg0.level_cf(0))
     S = _strength_pattern(Al)
-    N = Al.shape[0]
-    rows = [dict(zip(Al.indices[Al.indptr[i]:Al.indptr[i + 1]], Al.data[Al.indptr[i]:Al.indptr[i + 1]])) for i in range(N)]
-    strong = [set(S.indices[S.indptr[i]:S.indptr[i + 1]]) for i in range(N)]
-    cidx = -np.ones(N, dtype=int)
-    cidx[cf == 1] = np.arange(int((cf == 1).sum()))
-    P = sp.lil_matrix((N, int((cf == 1).sum())))
-    for i in range(N):
-        if cf[i] == 1:
-            P[i, cidx[i]] = 1.0
-            continue
-        Ci = [j for j in strong[i] if cf[j] == 1]
-        if not Ci:
-            continue
-        diag = rows[i][i] + sum(v for nb, v in rows[i].items() if nb != i and nb not in strong[i])
-        w = {j: rows[i][j] for j in Ci}
-        for k in strong[i]:
-            if cf[k] == 1:
-                continue
-            d = sum(rows[k].get(m, 0.0) for m in Ci if rows[k].get(m, 0.0) * rows[k][k] < 0)
-            if d == 0.0:
-                diag += rows[i][k]
-                continue
-            for j in Ci:
-                v = rows[k].get(j, 0.0)
-                if v * rows[k][k] < 0:
-                    w[j] += rows[i][k] * v / d
-        for j, v in w.items():
-            P[i, cidx[j]] = -v / diag
-    Pref0 = P.tocsr().tocsc()[:, np.asarray(amg0.level_perm(1))].tocsr()
+    Pref0 = classical_modified_reference(Al, S, cf).tocsc()[:, np.asarray(amg0.level_perm(1))].tocsr()
     assert abs(amg0.level_P(0).to_scipy() - Pref0).max() < 1e-13
 
 
