@@ -592,6 +592,12 @@ void BoomerAMG::apply_global(const double *f, double *e, bool zero_guess) {
 
 void BoomerAMG::solve(ParCSR &A, ParVector &b, ParVector &x) {
   if (!is_setup) setup(A);
+  // A hierarchy whose level 0 IS the caller's matrix (no C-first copy, e.g. one level) reads that matrix's values in
+  // every sweep: after an update round they are new, while the diagonals, l1 norms and coarse operators were built
+  // from the old ones.  (A hierarchy that owns a renumbered copy stays a consistent preconditioner of the old operator.)
+  if (!L.empty() && source_matrix && L[0].A == source_matrix && L[0].A->assembly_stamp != source_stamp)
+    fail(1, "BoomerAMGSolve: the values of the matrix changed (IJMatrix update round) after this solver was set up on it "
+            "and its first level is that matrix itself; call HYPRE_BoomerAMGSetup again");
   MI_REQUIRE(x.ncomp == b.ncomp, "BoomerAMGSolve: b and x differ in their number of components");
   MI_REQUIRE(x.n == L[0].n && b.n == L[0].n, "BoomerAMGSolve: vector size does not match the matrix");
   Comm &comm = my_comm();

@@ -54,6 +54,18 @@ struct IJMatrixObj {
   bool device_failed = false;  // a device assembly failed: its batches may be gone, the matrix is not usable
   ParCSR par;
   bool assembled = false;
+  // An update round of an assembled matrix (the pattern is frozen): the set / add calls are staged in `batches` or
+  // `dev_batches` as before the first Assemble, SetConstantValues is recorded at its place among them, and the
+  // next Assemble applies all of it in call order to the stored values.
+  bool round_open = false;
+  bool round_refused = false;  // a set call of this round was refused (N > 1 ranks: the collective Assemble reports it)
+  std::vector<IJUpdateConst> consts;
+  void drop_round() {
+    batches.clear();
+    dev_batches.clear();
+    consts.clear();
+    round_open = round_refused = false;
+  }
 };
 
 struct IJVectorObj {
@@ -115,10 +127,32 @@ void ij_demote(IJMatrixObj *m) {
   m->device_path = false;
 }
 
+// the first call after an Assemble that touches the values opens an update round
+void ij_open_round(IJMatrixObj *m) {
+  if (m->round_open) return;
+  if (m->device_failed) fail(HYPRE_ERROR_GENERIC, "IJMatrix: an earlier assembly of this matrix failed; create it again");
+  m->round_open = true;
+  m->round_refused = false;
+  m->device_path = true;  // every round chooses its path anew
+}
+
+// a host batch of an update round is checked against the pattern by the call that brings it; a refusal discards
+// the round (on N > 1 ranks it stays open, so that the collective Assemble fails on every rank)
+void ij_check_round_batch(IJMatrixObj *m) {
+  try {
+    check_update_batch(m->par, m->jlower, m->jupper, m->batches.back());
+  } catch (...) {
+    const bool collective = current_comm().size > 1;
+    m->drop_round();
+    m->round_open = m->round_refused = collective;
+    throw;
+  }
+}
+
 void ij_stage(IJMatrixObj *m, int nrows, const int *ncols, const gidx *rows, const int *row_indexes, const gidx *cols,
               const double *vals, bool add) {
-  if (m->assembled) fail(HYPRE_ERROR_GENERIC, "IJMatrix: values set after Assemble (re-assembly is not supported)");
-  if (nrows <= 0) return;
+  if (m->assembled) ij_open_round(m);
+  if (nrows <= 0 || m->round_refused) return;
   if (m->device_path && ij::device_assembly_enabled()) {
     const bool all_dev = is_device_pointer(rows) && is_device_pointer(cols) && is_device_pointer(vals) &&
                          (!ncols || is_device_pointer(ncols)) && (!row_indexes || is_device_pointer(row_indexes));
@@ -172,6 +206,58 @@ void ij_stage(IJMatrixObj *m, int nrows, const int *ncols, const gidx *rows, con
     }
   }
   m->batches.push_back(std::move(b));
+  if (m->round_open) ij_check_round_batch(m);
+}
+
+// Assemble of an update round.  Locate / validate first, agree on the outcome (one host all-reduce on N > 1 ranks),
+// then write: a refused round changes nothing on any rank.  host_only: the host arrays alone (CPU tests).
+void ij_apply_round(IJMatrixObj *m, bool host_only) {
+  Comm &comm = current_comm();
+  int refused = m->round_refused ? 1 : 0;
+  std::string why = "IJMatrixAssemble: a set call of this update round was refused; the round was discarded";
+  const bool on_device = !host_only && !refused && !m->dev_batches.empty() && m->par.on_device;
+  ij::UpdatePlan plan;
+  if (!refused) {
+    try {
+      if (!on_device && !m->dev_batches.empty()) ij_demote(m);
+      if (on_device && !ij::update_locate(m->ilower, m->iupper, m->jlower, m->jupper, m->dev_batches, m->par, plan)) {
+        // a row outside this rank's range: the host check words the refusal (first entry in submission order)
+        ij_demote(m);
+        for (auto &b : m->batches) check_update_batch(m->par, m->jlower, m->jupper, b);
+        fail(HYPRE_ERROR_GENERIC, "IJMatrix: a row of the update round is not owned by this rank");
+      }
+      if (!on_device)  // host batches were checked when they arrived; demoted device batches are checked here
+        for (auto &b : m->batches) check_update_batch(m->par, m->jlower, m->jupper, b);
+    } catch (const mi::Error &e) {
+      refused = 1;
+      why = e.what();
+    }
+  }
+  if (comm.size > 1) {
+    int any = refused;
+    comm.allreduce_host(&any, 1, CommDType::I32, CommOp::MAX);
+    if (any && !refused) why = "IJMatrixAssemble: another rank refused an entry of this update round; no rank's values changed";
+    refused = any;
+  }
+  if (refused) {
+    m->drop_round();
+    fail(HYPRE_ERROR_GENERIC, why);
+  }
+  if (on_device) {
+    std::vector<ij::UpdateConst> cs;
+    for (auto &c : m->consts) {
+      long long before = 0;
+      for (size_t b = 0; b < std::min(c.before_batch, plan.batch_sizes.size()); b++) before += plan.batch_sizes[b];
+      cs.push_back({before, c.value});
+    }
+    ij::update_apply(plan, cs, m->par);
+    ij::counters().device_value_updates++;
+  } else {
+    update_parcsr_values(m->par, m->jlower, m->jupper, m->batches, m->consts);
+    if (!host_only) refresh_device_values(m->par);
+  }
+  ij::counters().value_updates++;
+  m->drop_round();
 }
 
 void vec_set(IJVectorObj *v, int n, const gidx *indices, const double *values, bool add) {
@@ -405,7 +491,11 @@ HYPRE_Int HYPRE_IJMatrixSetObjectType(HYPRE_IJMatrix, HYPRE_Int type) {
 HYPRE_Int HYPRE_IJMatrixInitialize(HYPRE_IJMatrix matrix) {
   API_BEGIN
   if (!matrix) fail(HYPRE_ERROR_ARG, "IJMatrixInitialize: NULL handle");
-  ensure_init();
+  // on an assembled matrix: an update round opens and the stored values stay (as in HYPRE)
+  if (M(matrix)->assembled)
+    ij_open_round(M(matrix));
+  else
+    ensure_init();
   API_END
 }
 HYPRE_Int HYPRE_IJMatrixGetObject(HYPRE_IJMatrix matrix, void **object) {
@@ -418,7 +508,11 @@ HYPRE_Int HYPRE_IJMatrixSetConstantValues(HYPRE_IJMatrix matrix, HYPRE_Complex v
   API_BEGIN
   IJMatrixObj *m = M(matrix);
   if (!m) fail(HYPRE_ERROR_ARG, "IJMatrixSetConstantValues: NULL handle");
-  if (m->assembled) fail(HYPRE_ERROR_GENERIC, "IJMatrixSetConstantValues after Assemble is not supported");
+  if (m->assembled) {
+    ij_open_round(m);
+    if (!m->round_refused) m->consts.push_back({m->batches.size() + m->dev_batches.size(), value});
+    return 0;
+  }
   for (auto &b : m->batches) std::fill(b.vals.begin(), b.vals.end(), value);
   for (auto &d : m->dev_batches) ij::fill_values(d, value);
   API_END
@@ -452,6 +546,10 @@ HYPRE_Int HYPRE_IJMatrixAssemble(HYPRE_IJMatrix matrix) {
   if (m->device_failed)
     fail(HYPRE_ERROR_GENERIC, "IJMatrixAssemble: an earlier assembly of this matrix failed and its entries are gone; "
                               "create the matrix and set its values again");
+  if (m->assembled && m->round_open) {
+    ij_apply_round(m, false);
+    return 0;
+  }
   if (!m->assembled && !m->dev_batches.empty()) {
     // every batch arrived in device memory: sorted, folded and split there (ij_assembly.hip); the diag block is
     // already on the device when its solve format is built.  The matrix counts as assembled only when all of it
@@ -488,6 +586,10 @@ HYPRE_Int HYPRE_MI_IJMatrixAssembleHostOnly(HYPRE_IJMatrix matrix) {
   API_BEGIN
   IJMatrixObj *m = M(matrix);
   if (!m) fail(HYPRE_ERROR_ARG, "IJMatrixAssembleHostOnly: NULL handle");
+  if (m->assembled && m->round_open) {
+    ij_apply_round(m, true);
+    return 0;
+  }
   if (!m->assembled) {
     if (!m->dev_batches.empty()) ij_demote(m);
     Comm &comm = current_comm();
@@ -510,6 +612,19 @@ static void parcsr_block(ParCSR &A, int which, HostCSR &tmp, const HostCSR *&blk
     blk = &tmp;
   } else
     fail(HYPRE_ERROR_ARG, "ParCSRGetCSR: which must be 0, 1 or 2");
+}
+HYPRE_Int HYPRE_MI_ParCSRGetAssemblyStamp(HYPRE_ParCSRMatrix A, unsigned long long *stamp) {
+  API_BEGIN
+  if (!A || !stamp) fail(HYPRE_ERROR_ARG, "ParCSRGetAssemblyStamp: NULL argument");
+  *stamp = PM(A)->assembly_stamp;
+  API_END
+}
+HYPRE_Int HYPRE_MI_ParCSRGetValueKind(HYPRE_ParCSRMatrix A, HYPRE_Int *kind) {
+  API_BEGIN
+  if (!A || !kind) fail(HYPRE_ERROR_ARG, "ParCSRGetValueKind: NULL argument");
+  if (!PM(A)->on_device) fail(HYPRE_ERROR_GENERIC, "ParCSRGetValueKind: the matrix has no device mirror");
+  *kind = PM(A)->d_diag.val8 ? 8 : PM(A)->d_diag.value_kind;
+  API_END
 }
 HYPRE_Int HYPRE_MI_ParCSRGetCSRSize(HYPRE_ParCSRMatrix A, HYPRE_Int which, HYPRE_Int *nrows, HYPRE_Int *ncols,
                                     HYPRE_BigInt *nnz) {
@@ -1538,6 +1653,13 @@ HYPRE_Int HYPRE_MI_GetCounter(const char *name, long long *value) {
   }
   if (n == "ij_device_assemblies")
     *value = ij::counters().device_assemblies;
+  else if (n == "ij_value_updates")
+    *value = ij::counters().value_updates;
+  else if (n == "ij_device_value_updates")
+    *value = ij::counters().device_value_updates;
+  else if (n == "ij_update_kernels_us" || n == "ij_update_dictionary_us" || n == "ij_update_mirror_us")
+    *value = (long long)(1e6 * (n == "ij_update_kernels_us" ? ij::counters().t_update_kernels
+                                : n == "ij_update_dictionary_us" ? ij::counters().t_update_dict : ij::counters().t_update_mirror));
   else if (n == "ij_entries_fetched_to_host")
     *value = ij::counters().entries_fetched;
   else if (n == "ij_host_mirror_bytes")

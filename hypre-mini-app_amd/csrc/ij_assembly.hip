@@ -5,6 +5,7 @@
 // undone by the per-row sort on (column, submission index), a total order.  Every value is folded by ONE thread in
 // submission order with a plain +, as assemble_parcsr does.
 #include "ij_assembly.hpp"
+#include "kernels.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -166,12 +167,14 @@ __device__ __forceinline__ bool add_of(long long sub, int nb, const long long *_
 
 // One row per workgroup of T lanes, the row in LDS: rank of every entry under (column, submission index) by
 // comparison with all others, placement, then one lane per run of equal columns folds it in submission order.
-template <int T, int CAP>
+// UPD (an update round): nothing is folded -- the row goes back sorted, with the tags (submission index * 2 + Add
+// bit, which order like the submission indices) in `tag` moved along; they are read in place of `sub`.
+template <int T, int CAP, bool UPD>
 __global__ __launch_bounds__(T) void sort_fold_lds_k(int nlist, const int *__restrict__ list, const long long *__restrict__ ia,
                                                      gidx *__restrict__ cj, double *__restrict__ cv,
                                                      const long long *__restrict__ sub, int nb,
                                                      const long long *__restrict__ boff, const unsigned char *__restrict__ badd,
-                                                     bool uniform, int *__restrict__ rowlen) {
+                                                     bool uniform, int *__restrict__ rowlen, long long *__restrict__ tag) {
   __shared__ gidx ucol[CAP], scol[CAP];
   __shared__ long long usub[CAP];
   __shared__ double uval[CAP], sval[CAP];
@@ -185,7 +188,7 @@ __global__ __launch_bounds__(T) void sort_fold_lds_k(int nlist, const int *__res
   if (len > CAP) return;  // (the lists are built by length: never taken)
   for (int e = threadIdx.x; e < len; e += T) {
     ucol[e] = cj[s + e];
-    usub[e] = sub ? sub[s + e] : s + e;
+    usub[e] = UPD ? tag[s + e] : sub ? sub[s + e] : s + e;
     uval[e] = cv[s + e];
   }
   __syncthreads();
@@ -194,10 +197,17 @@ __global__ __launch_bounds__(T) void sort_fold_lds_k(int nlist, const int *__res
     const long long q = usub[e];
     int rank = 0;
     for (int j = 0; j < len; j++) rank += (ucol[j] < c || (ucol[j] == c && usub[j] < q)) ? 1 : 0;
-    scol[rank] = c;
-    sval[rank] = uval[e];
-    sadd[rank] = add_of(q, nb, boff, badd, uniform) ? 1 : 0;
+    if (UPD) {  // every lane has its entry in LDS: the row may be overwritten
+      cj[s + rank] = c;
+      cv[s + rank] = uval[e];
+      tag[s + rank] = q;
+    } else {
+      scol[rank] = c;
+      sval[rank] = uval[e];
+      sadd[rank] = add_of(q, nb, boff, badd, uniform) ? 1 : 0;
+    }
   }
+  if (UPD) return;
   __syncthreads();
   // output position of every sorted entry = runs of equal columns begun before it: chunks of T flags, scanned
   int m = 0;
@@ -221,30 +231,42 @@ __global__ __launch_bounds__(T) void sort_fold_lds_k(int nlist, const int *__res
 }
 
 // The same for a row of any length: the sorted copy lives in global scratch (toff[li]: the row's offset there)
+template <bool UPD>
 __global__ __launch_bounds__(BLK) void sort_fold_long_k(int nlist, const int *__restrict__ list, const long long *__restrict__ toff,
                                                         const long long *__restrict__ ia, gidx *__restrict__ cj,
                                                         double *__restrict__ cv, const long long *__restrict__ sub, int nb,
                                                         const long long *__restrict__ boff, const unsigned char *__restrict__ badd,
                                                         bool uniform, gidx *__restrict__ tcol, double *__restrict__ tval,
                                                         unsigned char *__restrict__ tadd, long long *__restrict__ tpos,
-                                                        int *__restrict__ rowlen) {
+                                                        int *__restrict__ rowlen, long long *__restrict__ tag) {
   if ((int)blockIdx.x >= nlist) return;
   const int row = list[blockIdx.x];
   const long long s = ia[row], len = ia[row + 1] - s, t0 = toff[blockIdx.x];
   for (long long e = threadIdx.x; e < len; e += BLK) {
     const gidx c = cj[s + e];
-    const long long q = sub ? sub[s + e] : s + e;
+    const long long q = UPD ? tag[s + e] : sub ? sub[s + e] : s + e;
     long long rank = 0;
     for (long long j = 0; j < len; j++) {
       const gidx cc = cj[s + j];
-      const long long qq = sub ? sub[s + j] : s + j;
+      const long long qq = UPD ? tag[s + j] : sub ? sub[s + j] : s + j;
       rank += (cc < c || (cc == c && qq < q)) ? 1 : 0;
     }
     tcol[t0 + rank] = c;
     tval[t0 + rank] = cv[s + e];
-    tadd[t0 + rank] = add_of(q, nb, boff, badd, uniform) ? 1 : 0;
+    if (UPD)
+      tpos[t0 + rank] = q;
+    else
+      tadd[t0 + rank] = add_of(q, nb, boff, badd, uniform) ? 1 : 0;
   }
   __syncthreads();
+  if (UPD) {  // the sorted row goes back as it is, tags (held in tpos) moved along
+    for (long long e = threadIdx.x; e < len; e += BLK) {
+      cj[s + e] = tcol[t0 + e];
+      cv[s + e] = tval[t0 + e];
+      tag[s + e] = tpos[t0 + e];
+    }
+    return;
+  }
   __shared__ int scan[BLK];
   long long m = 0;
   for (long long base = 0; base < len; base += BLK) {
@@ -304,6 +326,120 @@ __global__ __launch_bounds__(BLK) void write_split_k(int nrows, const long long 
         po++;
       }
     }
+  }
+}
+
+// ---------------------------------------------------------------- update round of an assembled matrix
+__global__ __launch_bounds__(BLK) void tag_entries_k(long long E, const long long *__restrict__ sub, int nb,
+                                                     const long long *__restrict__ boff, const unsigned char *__restrict__ badd,
+                                                     bool uniform, long long *__restrict__ tag) {
+  IJ_GRID_STRIDE(p, E) {
+    const long long q = sub ? sub[p] : p;
+    tag[p] = (q << 1) | (add_of(q, nb, boff, badd, uniform) ? 1 : 0);
+  }
+}
+__global__ __launch_bounds__(BLK) void local_rows_k(long long E, const gidx *__restrict__ R, const long long *__restrict__ sub,
+                                                    gidx ilower, int *__restrict__ prow) {
+  IJ_GRID_STRIDE(p, E) prow[p] = (int)(R[sub ? sub[p] : p] - ilower);
+}
+
+template <class T>
+__device__ __forceinline__ long long find_sorted(const T *__restrict__ a, long long lo, long long hi, T key) {
+  const long long end = hi;
+  while (lo < hi) {
+    const long long mid = (lo + hi) >> 1;
+    if (a[mid] < key)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return (lo < end && a[lo] == key) ? lo : -1;
+}
+
+// The stored operator as the locate kernel sees it.  Diag block: solve format, row pointers 32-bit (dia) or, for a
+// block of 2^31 entries or more, 64-bit (dia64).  Halo block: only the rows that own halo entries are stored (orows:
+// their local ids, ascending); its columns are positions in the column map.
+struct StoredPattern {
+  const int *dia;
+  const long long *dia64;
+  const int *dja;
+  const int *orows, *oia, *oja;
+  const gidx *colmap;
+  int nrows_c, next;
+  gidx jlower, jupper;
+};
+
+// One lane per sorted entry; the first entry of a run of equal (row, column) finds the pair in the stored diag row or
+// the stored halo row.  A pair that is not stored leaves the smallest submission index of its run in st[ST_BAD] (the
+// head of a run is its first entry in submission order).  Nothing of the matrix is written.
+__global__ __launch_bounds__(BLK) void locate_k(long long E, const long long *__restrict__ ia, const int *__restrict__ prow,
+                                                const gidx *__restrict__ cj, const long long *__restrict__ tag,
+                                                StoredPattern P, long long *__restrict__ loc, ull *__restrict__ st) {
+  IJ_GRID_STRIDE(p, E) {
+    const int i = prow[p];
+    const gidx c = cj[p];
+    if (p > ia[i] && cj[p - 1] == c) continue;
+    long long at = -1;
+    bool halo = false;
+    if (c >= P.jlower && c <= P.jupper) {
+      const long long lo = P.dia64 ? P.dia64[i] : (long long)P.dia[i], hi = P.dia64 ? P.dia64[i + 1] : (long long)P.dia[i + 1];
+      at = find_sorted<int>(P.dja, lo, hi, (int)(c - P.jlower));
+    } else {
+      halo = true;
+      const long long cid = find_sorted<gidx>(P.colmap, 0, P.next, c);
+      const long long cr = cid < 0 ? -1 : find_sorted<int>(P.orows, 0, P.nrows_c, i);
+      if (cr >= 0) at = find_sorted<int>(P.oja, P.oia[cr], P.oia[cr + 1], (int)cid);
+    }
+    if (at < 0) atomicMin(&st[ST_BAD], (ull)(tag[p] >> 1));
+    loc[p] = halo ? ~at : at;
+  }
+}
+// the refused entry, for the message: its global row and column
+__global__ __launch_bounds__(BLK) void find_entry_k(long long E, const int *__restrict__ prow, const gidx *__restrict__ cj,
+                                                    const long long *__restrict__ tag, long long q, gidx ilower,
+                                                    gidx *__restrict__ out) {
+  IJ_GRID_STRIDE(p, E)
+    if ((tag[p] >> 1) == q) {
+      out[0] = ilower + prow[p];
+      out[1] = cj[p];
+    }
+}
+// One lane per run: from the stored value, the run's entries in submission order -- Set replaces, Add is one plain +;
+// a SetConstantValues call (cbefore[k] entries were submitted before it) takes effect between them.  The result
+// goes to the head's slot of cv; the matrix is written by store_runs_k, after the constant fill.
+__global__ __launch_bounds__(BLK) void walk_runs_k(long long E, const long long *__restrict__ ia, const int *__restrict__ prow,
+                                                   const gidx *__restrict__ cj, double *__restrict__ cv,
+                                                   const long long *__restrict__ tag, const long long *__restrict__ loc,
+                                                   const double *__restrict__ da, const double *__restrict__ oa, int nc,
+                                                   const long long *__restrict__ cbefore, const double *__restrict__ cval) {
+  IJ_GRID_STRIDE(p, E) {
+    const int i = prow[p];
+    const gidx c = cj[p];
+    if (p > ia[i] && cj[p - 1] == c) continue;
+    const long long at = loc[p], end = ia[i + 1];
+    double v = at >= 0 ? da[at] : oa[~at];
+    int kc = 0;
+    for (long long j = p; j < end && cj[j] == c; j++) {
+      const long long t = tag[j];
+      for (; kc < nc && cbefore[kc] <= (t >> 1); kc++) v = cval[kc];
+      v = (t & 1) ? v + cv[j] : cv[j];
+    }
+    if (kc < nc) v = cval[nc - 1];
+    cv[p] = v;
+  }
+}
+__global__ __launch_bounds__(BLK) void store_runs_k(long long E, const long long *__restrict__ ia, const int *__restrict__ prow,
+                                                    const gidx *__restrict__ cj, const double *__restrict__ cv,
+                                                    const long long *__restrict__ loc, double *__restrict__ da,
+                                                    double *__restrict__ oa) {
+  IJ_GRID_STRIDE(p, E) {
+    const int i = prow[p];
+    if (p > ia[i] && cj[p - 1] == cj[p]) continue;
+    const long long at = loc[p];
+    if (at >= 0)
+      da[at] = cv[p];
+    else
+      oa[~at] = cv[p];
   }
 }
 
@@ -426,70 +562,88 @@ void fill_values(DevBatch &b, double v) {
   MI_HIP(hipStreamSynchronize(s));
 }
 
-void assemble_parcsr_device(Comm &comm, gidx ilower, gidx iupper, gidx jlower, gidx jupper, std::vector<DevBatch> &batches,
-                            ParCSR &out, sk::DCsr &diag) {
-  ensure_init();
-  hipStream_t s = ctx().stream;
-  const double t_begin = wall_time();
-  require_int32_block(iupper - ilower + 1, 0, "IJMatrixAssemble");
-  const int nrows = (int)(iupper - ilower + 1);
-  const int ncols_loc = (int)(jupper - jlower + 1);
+namespace {
+// The front of an assembly and of an update round: the staged batches checked, concatenated, bucketed by row and
+// every row sorted by (column, submission index).
+struct Staged {
   int64_t E = 0;
-  for (auto &b : batches) E += b.n;
-
-  // the entries in submission order: one batch as it is, several concatenated (each released once copied)
+  int nrows = 0;
   DVec<gidx> R, cj;
   DVec<double> cv;
+  DVec<long long> ia;
+  DVec<long long> sub;  // submission index of every entry (counting sort only; empty: the position itself)
+  DVec<int> rowlen;
+  bool uniform_add = false, mixed = false;
   std::vector<long long> boff_h;
   std::vector<unsigned char> badd_h;
-  bool uniform_add = batches.empty() ? false : batches.front().add, mixed = false;
-  for (auto &b : batches) mixed = mixed || (b.add != uniform_add);
-  if (mixed) {
-    long long o = 0;
-    for (auto &b : batches) {
-      if (!b.n) continue;
-      boff_h.push_back(o);
-      badd_h.push_back(b.add ? 1 : 0);
-      o += b.n;
-    }
-    boff_h.push_back(o);
-  }
-  // the first pass only reads the batches: a refusal leaves them as they were
-  DVec<ull> st(ST_WORDS);
-  {
-    ull init[ST_WORDS] = {~0ull, 0, 0, 0, 0, 0, 0, 0};
-    MI_HIP(hipMemcpyAsync(st.p, init, sizeof(init), hipMemcpyHostToDevice, s));
-    MI_HIP(hipStreamSynchronize(s));
-  }
-  ull h[ST_WORDS];
-  {
-    // per batch: ownership and order inside it; across batches: the first row of one against the last of the one before
-    DVec<ull> stb(ST_WORDS);
-    const gidx *prev_last = nullptr;
-    bool unordered = false;
-    for (auto &b : batches) {
-      if (!b.n) continue;
-      ull init[ST_WORDS] = {~0ull, 0, 0, 0, 0, 0, 0, 0};
-      MI_HIP(hipMemcpyAsync(stb.p, init, sizeof(init), hipMemcpyHostToDevice, s));
-      MI_HIP(hipStreamSynchronize(s));
-      if (prev_last) batch_edge_k<<<1, 64, 0, s>>>(prev_last, b.rows.p, stb.p);
-      prev_last = b.rows.p + (b.n - 1);
-      validate_k<<<grid_for(b.n), BLK, 0, s>>>(b.n, b.rows.p, ilower, iupper, stb.p);
-      MI_HIP(hipGetLastError());
-      read_status(stb, h, s);
-      if (h[ST_BAD] != ~0ull) {
-        // the one row id that travels to the host: the message names it, as the host path's does
-        gidx bad = 0;
-        d2h(&bad, b.rows.p + h[ST_BAD], sizeof(gidx), s);
-        MI_HIP(hipStreamSynchronize(s));
-        fail(4, "IJMatrix: row " + std::to_string(bad) + " is not owned by this rank");
-      }
-      unordered = unordered || h[ST_UNORDERED] != 0;
-    }
-    h[ST_UNORDERED] = unordered ? 1 : 0;
-  }
-  const bool in_row_order = E > 0 && h[ST_UNORDERED] == 0;
+  DVec<long long> boff;
+  DVec<unsigned char> badd;
+  int nb = 0;
+};
 
+// Set / Add per batch (only when the batches differ), on the host and on the device
+void batch_kinds(const std::vector<DevBatch> &batches, Staged &g, hipStream_t s) {
+  g.uniform_add = batches.empty() ? false : batches.front().add;
+  for (auto &b : batches) g.mixed = g.mixed || (b.add != g.uniform_add);
+  if (!g.mixed) return;
+  long long o = 0;
+  for (auto &b : batches) {
+    if (!b.n) continue;
+    g.boff_h.push_back(o);
+    g.badd_h.push_back(b.add ? 1 : 0);
+    o += b.n;
+  }
+  g.boff_h.push_back(o);
+  g.nb = (int)g.badd_h.size();
+  g.boff.alloc(g.boff_h.size());
+  g.badd.alloc(g.badd_h.size());
+  MI_HIP(hipMemcpyAsync(g.boff.p, g.boff_h.data(), g.boff_h.size() * sizeof(long long), hipMemcpyHostToDevice, s));
+  MI_HIP(hipMemcpyAsync(g.badd.p, g.badd_h.data(), g.badd_h.size(), hipMemcpyHostToDevice, s));
+  MI_HIP(hipStreamSynchronize(s));  // the host vectors may be pageable
+}
+
+// The first pass only reads the batches.  Per batch: ownership and order inside it; across batches: the first row of
+// one against the last of the one before.  false: a row is not owned (*bad_row: the first one of its batch).
+bool check_rows(const std::vector<DevBatch> &batches, gidx ilower, gidx iupper, bool *in_row_order, gidx *bad_row,
+                hipStream_t s) {
+  ull h[ST_WORDS];
+  DVec<ull> stb(ST_WORDS);
+  const gidx *prev_last = nullptr;
+  bool unordered = false;
+  int64_t E = 0;
+  for (auto &b : batches) {
+    if (!b.n) continue;
+    E += b.n;
+    ull init[ST_WORDS] = {~0ull, 0, 0, 0, 0, 0, 0, 0};
+    MI_HIP(hipMemcpyAsync(stb.p, init, sizeof(init), hipMemcpyHostToDevice, s));
+    MI_HIP(hipStreamSynchronize(s));
+    if (prev_last) batch_edge_k<<<1, 64, 0, s>>>(prev_last, b.rows.p, stb.p);
+    prev_last = b.rows.p + (b.n - 1);
+    validate_k<<<grid_for(b.n), BLK, 0, s>>>(b.n, b.rows.p, ilower, iupper, stb.p);
+    MI_HIP(hipGetLastError());
+    read_status(stb, h, s);
+    if (h[ST_BAD] != ~0ull) {
+      // the one row id that travels to the host: the message names it, as the host path's does
+      d2h(bad_row, b.rows.p + h[ST_BAD], sizeof(gidx), s);
+      MI_HIP(hipStreamSynchronize(s));
+      return false;
+    }
+    unordered = unordered || h[ST_UNORDERED] != 0;
+  }
+  *in_row_order = E > 0 && !unordered;
+  return true;
+}
+
+// The entries in submission order (one batch as it is, several concatenated, each released once copied), then the
+// row pointers: found at the row boundaries when the entries arrive in row order, by a counting sort otherwise.
+// prow (update rounds): the local row of every bucketed entry.
+void bucket_rows(std::vector<DevBatch> &batches, bool in_row_order, gidx ilower, int nrows, Staged &g, DVec<int> *prow,
+                 hipStream_t s) {
+  const int64_t E = g.E;
+  DVec<gidx> &R = g.R, &cj = g.cj;
+  DVec<double> &cv = g.cv;
+  DVec<long long> &ia = g.ia, &sub = g.sub;
+  g.nrows = nrows;
   if (batches.size() == 1) {
     R = std::move(batches[0].rows);
     cj = std::move(batches[0].cols);
@@ -516,12 +670,13 @@ void assemble_parcsr_device(Comm &comm, gidx ilower, gidx iupper, gidx jlower, g
   }
   batches.clear();
 
-  DVec<long long> ia((size_t)nrows + 1);
-  DVec<long long> sub;  // submission index of every entry (counting sort only; empty: the position itself)
+  ia.alloc((size_t)nrows + 1);
   if (E == 0) {
     MI_HIP(hipMemsetAsync(ia.p, 0, ((size_t)nrows + 1) * sizeof(long long), s));
   } else if (in_row_order) {
     boundaries_k<<<grid_for(E), BLK, 0, s>>>(E, R.p, ilower, nrows, ia.p);
+    MI_HIP(hipGetLastError());
+    if (prow) local_rows_k<<<grid_for(E), BLK, 0, s>>>(E, R.p, nullptr, ilower, prow->p);
     MI_HIP(hipGetLastError());
     MI_HIP(hipStreamSynchronize(s));
     R.release();
@@ -544,14 +699,29 @@ void assemble_parcsr_device(Comm &comm, gidx ilower, gidx iupper, gidx jlower, g
     DVec<double> ov((size_t)E);
     gather_entries_k<<<grid_for(E), BLK, 0, s>>>(E, sub.p, cj.p, cv.p, oj.p, ov.p);
     MI_HIP(hipGetLastError());
+    if (prow) local_rows_k<<<grid_for(E), BLK, 0, s>>>(E, R.p, sub.p, ilower, prow->p);
+    MI_HIP(hipGetLastError());
     MI_HIP(hipStreamSynchronize(s));
     R.release();
     cj = std::move(oj);
     cv = std::move(ov);
   }
+}
 
-  // step 2
-  DVec<int> rowlen((size_t)nrows);
+// step 2: every row whose columns are not strictly ascending is sorted by (column, submission index); an assembly
+// (tag null) folds the runs of equal columns and leaves the folded lengths in rowlen, an update round keeps every
+// entry and moves its tag along
+void sort_rows(Staged &g, long long *tag, DVec<ull> &st, hipStream_t s) {
+  const int nrows = g.nrows;
+  DVec<long long> &ia = g.ia, &sub = g.sub, &boff = g.boff;
+  DVec<gidx> &cj = g.cj;
+  DVec<double> &cv = g.cv;
+  DVec<int> &rowlen = g.rowlen;
+  DVec<unsigned char> &badd = g.badd;
+  const int nb = g.nb;
+  const bool uniform_add = g.uniform_add;
+  ull h[ST_WORDS];
+  rowlen.alloc((size_t)nrows);
   if (nrows) {
     DVec<unsigned char> cls((size_t)nrows);
     classify_k<<<grid_for(nrows), BLK, 0, s>>>(nrows, ia.p, cj.p, cls.p, rowlen.p, st.p);
@@ -564,24 +734,19 @@ void assemble_parcsr_device(Comm &comm, gidx ilower, gidx iupper, gidx jlower, g
       DVec<unsigned> cur(4);
       MI_HIP(hipMemsetAsync(cur.p, 0, 4 * sizeof(unsigned), s));
       list_rows_k<<<grid_for(nrows), BLK, 0, s>>>(nrows, cls.p, l1.p, l2.p, l3.p, cur.p);
-      DVec<long long> boff;
-      DVec<unsigned char> badd;
-      int nb = 0;
-      if (mixed) {
-        nb = (int)badd_h.size();
-        boff.alloc(boff_h.size());
-        badd.alloc(badd_h.size());
-        MI_HIP(hipMemcpyAsync(boff.p, boff_h.data(), boff_h.size() * sizeof(long long), hipMemcpyHostToDevice, s));
-        MI_HIP(hipMemcpyAsync(badd.p, badd_h.data(), badd_h.size(), hipMemcpyHostToDevice, s));
-        MI_HIP(hipStreamSynchronize(s));  // the host vectors may be pageable
-      }
       // a launch takes at most 2^31 - 1 workgroups in x: far more than the rows of a rank (32-bit local row ids)
-      if (n1)
-        sort_fold_lds_k<64, SORT_WAVE_CAP><<<(unsigned)n1, 64, 0, s>>>((int)n1, l1.p, ia.p, cj.p, cv.p, sub.p, nb, boff.p, badd.p,
-                                                                     uniform_add, rowlen.p);
-      if (n2)
-        sort_fold_lds_k<BLK, SORT_LDS_CAP><<<(unsigned)n2, BLK, 0, s>>>((int)n2, l2.p, ia.p, cj.p, cv.p, sub.p, nb, boff.p, badd.p,
-                                                                       uniform_add, rowlen.p);
+      if (n1 && tag)
+        sort_fold_lds_k<64, SORT_WAVE_CAP, true><<<(unsigned)n1, 64, 0, s>>>((int)n1, l1.p, ia.p, cj.p, cv.p, sub.p, nb, boff.p,
+                                                                           badd.p, uniform_add, rowlen.p, tag);
+      else if (n1)
+        sort_fold_lds_k<64, SORT_WAVE_CAP, false><<<(unsigned)n1, 64, 0, s>>>((int)n1, l1.p, ia.p, cj.p, cv.p, sub.p, nb, boff.p,
+                                                                            badd.p, uniform_add, rowlen.p, nullptr);
+      if (n2 && tag)
+        sort_fold_lds_k<BLK, SORT_LDS_CAP, true><<<(unsigned)n2, BLK, 0, s>>>((int)n2, l2.p, ia.p, cj.p, cv.p, sub.p, nb, boff.p,
+                                                                             badd.p, uniform_add, rowlen.p, tag);
+      else if (n2)
+        sort_fold_lds_k<BLK, SORT_LDS_CAP, false><<<(unsigned)n2, BLK, 0, s>>>((int)n2, l2.p, ia.p, cj.p, cv.p, sub.p, nb, boff.p,
+                                                                              badd.p, uniform_add, rowlen.p, nullptr);
       MI_HIP(hipGetLastError());
       if (n3) {
         // scratch of the long rows: their lengths (still the unsorted ones in rowlen) gathered and scanned on the device
@@ -595,16 +760,55 @@ void assemble_parcsr_device(Comm &comm, gidx ilower, gidx iupper, gidx jlower, g
         const size_t tt = (size_t)tt_ll;
         DVec<gidx> tcol(tt);
         DVec<double> tval(tt);
-        DVec<unsigned char> tadd(tt);
+        DVec<unsigned char> tadd(tag ? (size_t)0 : tt);
         DVec<long long> tpos(tt);
-        sort_fold_long_k<<<(unsigned)n3, BLK, 0, s>>>((int)n3, l3.p, toff.p, ia.p, cj.p, cv.p, sub.p, nb, boff.p, badd.p,
-                                                      uniform_add, tcol.p, tval.p, tadd.p, tpos.p, rowlen.p);
+        if (tag)
+          sort_fold_long_k<true><<<(unsigned)n3, BLK, 0, s>>>((int)n3, l3.p, toff.p, ia.p, cj.p, cv.p, sub.p, nb, boff.p, badd.p,
+                                                            uniform_add, tcol.p, tval.p, tadd.p, tpos.p, rowlen.p, tag);
+        else
+          sort_fold_long_k<false><<<(unsigned)n3, BLK, 0, s>>>((int)n3, l3.p, toff.p, ia.p, cj.p, cv.p, sub.p, nb, boff.p, badd.p,
+                                                             uniform_add, tcol.p, tval.p, tadd.p, tpos.p, rowlen.p, nullptr);
         MI_HIP(hipGetLastError());
         MI_HIP(hipStreamSynchronize(s));
       }
       MI_HIP(hipStreamSynchronize(s));
     }
   }
+}
+
+void new_status(DVec<ull> &st, hipStream_t s) {
+  st.alloc(ST_WORDS);
+  ull init[ST_WORDS] = {~0ull, 0, 0, 0, 0, 0, 0, 0};
+  MI_HIP(hipMemcpyAsync(st.p, init, sizeof(init), hipMemcpyHostToDevice, s));
+  MI_HIP(hipStreamSynchronize(s));
+}
+
+}  // namespace
+
+void assemble_parcsr_device(Comm &comm, gidx ilower, gidx iupper, gidx jlower, gidx jupper, std::vector<DevBatch> &batches,
+                            ParCSR &out, sk::DCsr &diag) {
+  ensure_init();
+  hipStream_t s = ctx().stream;
+  const double t_begin = wall_time();
+  require_int32_block(iupper - ilower + 1, 0, "IJMatrixAssemble");
+  const int nrows = (int)(iupper - ilower + 1);
+  const int ncols_loc = (int)(jupper - jlower + 1);
+  Staged g;
+  for (auto &b : batches) g.E += b.n;
+  // a refusal leaves the batches as they were
+  bool in_row_order = false;
+  gidx bad = 0;
+  if (!check_rows(batches, ilower, iupper, &in_row_order, &bad, s))
+    fail(4, "IJMatrix: row " + std::to_string(bad) + " is not owned by this rank");
+  batch_kinds(batches, g, s);
+  DVec<ull> st;
+  new_status(st, s);
+  bucket_rows(batches, in_row_order, ilower, nrows, g, nullptr, s);
+  sort_rows(g, nullptr, st, s);
+  DVec<long long> &ia = g.ia, &sub = g.sub;
+  DVec<gidx> &cj = g.cj;
+  DVec<double> &cv = g.cv;
+  DVec<int> &rowlen = g.rowlen;
   sub.release();
 
   // step 3
@@ -679,6 +883,125 @@ void finish_device(ParCSR &par, sk::DCsr &diag) {
     par.to_device();
   }
   counters().t_format = wall_time() - t1;
+}
+
+bool update_locate(gidx ilower, gidx iupper, gidx jlower, gidx jupper, std::vector<DevBatch> &batches, const ParCSR &par,
+                   UpdatePlan &plan) {
+  ensure_init();
+  hipStream_t s = ctx().stream;
+  const double t_begin = wall_time();
+  MI_REQUIRE(par.on_device, "IJMatrix update: the matrix has no device mirror");
+  MI_REQUIRE(par.d_diag.a.p || par.d_diag.nnz == 0, "IJMatrix update: the device diag block holds no fp64 values");
+  const int nrows = (int)(iupper - ilower + 1);
+  Staged g;
+  plan.batch_sizes.clear();
+  for (auto &b : batches) {
+    g.E += b.n;
+    plan.batch_sizes.push_back(b.n);
+  }
+  bool in_row_order = false;
+  gidx bad_row = 0;
+  if (!check_rows(batches, ilower, iupper, &in_row_order, &bad_row, s)) return false;
+  batch_kinds(batches, g, s);
+  DVec<ull> st;
+  new_status(st, s);
+  const int64_t E = g.E;
+  plan.E = E;
+  plan.nrows = nrows;
+  plan.prow.alloc((size_t)E);
+  bucket_rows(batches, in_row_order, ilower, nrows, g, &plan.prow, s);
+  plan.tag.alloc((size_t)E);
+  if (E) tag_entries_k<<<grid_for(E), BLK, 0, s>>>(E, g.sub.p, g.nb, g.boff.p, g.badd.p, g.uniform_add, plan.tag.p);
+  MI_HIP(hipGetLastError());
+  sort_rows(g, plan.tag.p, st, s);
+  g.sub.release();
+  g.rowlen.release();
+  plan.ia = std::move(g.ia);
+  plan.cj = std::move(g.cj);
+  plan.cv = std::move(g.cv);
+  plan.loc.alloc((size_t)E);
+  if (E) {
+    // DevOffd stores only the rows that own halo entries, and its columns are positions in the column map: the
+    // map gets a device copy for the round
+    DVec<gidx> colmap;
+    colmap.upload(par.col_map_offd);
+    StoredPattern P;
+    P.dia = par.d_diag.ia.p;
+    P.dia64 = par.d_diag.ia64.p;
+    P.dja = par.d_diag.ja.p;
+    P.orows = par.d_offd.rows.p;
+    P.oia = par.d_offd.ia.p;
+    P.oja = par.d_offd.ja.p;
+    P.colmap = colmap.p;
+    P.nrows_c = par.d_offd.nrows_c;
+    P.next = (int)par.col_map_offd.size();
+    P.jlower = jlower;
+    P.jupper = jupper;
+    locate_k<<<grid_for(E), BLK, 0, s>>>(E, plan.ia.p, plan.prow.p, plan.cj.p, plan.tag.p, P, plan.loc.p, st.p);
+    MI_HIP(hipGetLastError());
+    // the whole round is located and the flag read before any value is written: a refused round changes nothing
+    ull h[ST_WORDS];
+    read_status(st, h, s);
+    if (h[ST_BAD] != ~0ull) {
+      DVec<gidx> who(2);
+      find_entry_k<<<grid_for(E), BLK, 0, s>>>(E, plan.prow.p, plan.cj.p, plan.tag.p, (long long)h[ST_BAD], ilower, who.p);
+      MI_HIP(hipGetLastError());
+      gidx rc[2] = {0, 0};
+      d2h(rc, who.p, sizeof(rc), s);
+      MI_HIP(hipStreamSynchronize(s));
+      fail(1, "IJMatrix: entry (row " + std::to_string(rc[0]) + ", column " + std::to_string(rc[1]) +
+                  ") is not in the pattern of the assembled matrix; the pattern is frozen by the first Assemble and "
+                  "the update round was discarded");
+    }
+  }
+  counters().t_update_kernels = wall_time() - t_begin;
+  return true;
+}
+
+void update_apply(UpdatePlan &plan, const std::vector<UpdateConst> &consts, ParCSR &par) {
+  hipStream_t s = ctx().stream;
+  const double t_begin = wall_time();
+  const int64_t E = plan.E;
+  const int nc = (int)consts.size();
+  DevCSR &D = par.d_diag;
+  DevOffd &O = par.d_offd;
+  DVec<long long> cbefore;
+  DVec<double> cval;
+  if (nc) {
+    std::vector<long long> cb;
+    std::vector<double> cvl;
+    for (auto &c : consts) {
+      cb.push_back(c.before);
+      cvl.push_back(c.value);
+    }
+    cbefore.upload(cb);
+    cval.upload(cvl);
+  }
+  // every run's final value from the stored one, into the round's own arrays; then the constant (the last one is what
+  // entries that no run mentions end with); then the runs' values into d_diag.a / d_offd.a, in place
+  if (E)
+    walk_runs_k<<<grid_for(E), BLK, 0, s>>>(E, plan.ia.p, plan.prow.p, plan.cj.p, plan.cv.p, plan.tag.p, plan.loc.p, D.a.p, O.a.p,
+                                            nc, cbefore.p, cval.p);
+  if (nc && D.nnz) fill_k<<<grid_for(D.nnz), BLK, 0, s>>>(D.a.p, (long long)D.nnz, consts.back().value);
+  if (nc && O.nnz) fill_k<<<grid_for(O.nnz), BLK, 0, s>>>(O.a.p, (long long)O.nnz, consts.back().value);
+  if (E) store_runs_k<<<grid_for(E), BLK, 0, s>>>(E, plan.ia.p, plan.prow.p, plan.cj.p, plan.cv.p, plan.loc.p, D.a.p, O.a.p);
+  MI_HIP(hipGetLastError());
+  MI_HIP(hipStreamSynchronize(s));
+  plan = UpdatePlan();
+  const double t_kernels = wall_time();
+  counters().t_update_kernels += t_kernels - t_begin;
+  // what depends on the values and nothing else.  The tile schedule (rb), the tile descriptors (tdesc), the x-cache
+  // column lists (ucols, lcol) and the halo plan depend on the pattern alone: they are not touched.
+  k::build_value_dictionary(D, s);
+  const double t_dict = wall_time();
+  counters().t_update_dict = t_dict - t_kernels;
+  // the host mirrors (ILU, FSAI, the locality numbering and the dumps read them): the value arrays only
+  if (D.nnz) d2h(par.diag.a.data(), D.a.p, (size_t)D.nnz * sizeof(double), s);
+  if (O.nnz) d2h(par.offd.a.data(), O.a.p, (size_t)O.nnz * sizeof(double), s);
+  MI_HIP(hipStreamSynchronize(s));
+  counters().host_mirror_bytes += (long long)((size_t)(D.nnz + O.nnz) * sizeof(double));
+  counters().t_update_mirror = wall_time() - t_dict;
+  par.assembly_stamp = next_assembly_stamp();
 }
 
 void vec_local_ids(const gidx *indices, int n, gidx jlower, gidx jupper, int *loc) {

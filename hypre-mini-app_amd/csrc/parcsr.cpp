@@ -268,8 +268,128 @@ void assemble_halo_columns_and_partition(Comm &comm, gidx ilower, gidx iupper, c
   comm.allreduce_host(&gend, 1, CommDType::I64, CommOp::MAX);
   out.row_starts = starts;
   out.row_starts.push_back(gend);
+  out.assembly_stamp = next_assembly_stamp();
+}
+
+unsigned long long next_assembly_stamp() {
   static unsigned long long stamp = 0;
-  out.assembly_stamp = ++stamp;
+  return ++stamp;
+}
+
+// ------------------------------------------------------------------ value updates of an assembled matrix
+namespace {
+constexpr int64_t NOT_IN_PATTERN = INT64_MIN;
+// position of (r, c) in the stored values: p >= 0 in diag.a, ~p < 0 in offd.a
+int64_t locate_entry(const ParCSR &A, gidx jlower, gidx jupper, gidx r, gidx c) {
+  if (r < A.row_start || r >= A.row_end) return NOT_IN_PATTERN;
+  const size_t i = (size_t)(r - A.row_start);
+  if (c >= jlower && c <= jupper) {
+    const int lc = (int)(c - jlower);
+    const int *b = A.diag.ja.data() + A.diag.ia[i], *e = A.diag.ja.data() + A.diag.ia[i + 1];
+    const int *q = std::lower_bound(b, e, lc);
+    return (q != e && *q == lc) ? (int64_t)(q - A.diag.ja.data()) : NOT_IN_PATTERN;
+  }
+  auto g = std::lower_bound(A.col_map_offd.begin(), A.col_map_offd.end(), c);
+  if (g == A.col_map_offd.end() || *g != c) return NOT_IN_PATTERN;
+  const int cid = (int)(g - A.col_map_offd.begin());
+  const int *b = A.offd.ja.data() + A.offd.ia[i], *e = A.offd.ja.data() + A.offd.ia[i + 1];
+  const int *q = std::lower_bound(b, e, cid);
+  return (q != e && *q == cid) ? ~(int64_t)(q - A.offd.ja.data()) : NOT_IN_PATTERN;
+}
+[[noreturn]] void refuse_entry(const ParCSR &A, gidx r, gidx c) {
+  const bool owned = r >= A.row_start && r < A.row_end;
+  fail(1, "IJMatrix: entry (row " + std::to_string(r) + ", column " + std::to_string(c) + ") " +
+              (owned ? "is not in the pattern of the assembled matrix" : "lies in a row that this rank does not own") +
+              "; the pattern is frozen by the first Assemble and the update round was discarded");
+}
+// positions of b's entries (pos, if given) and the index of the first one that has none (-1: all found)
+int64_t locate_batch(const ParCSR &A, gidx jlower, gidx jupper, const IJEntryBatch &b, int64_t *pos) {
+  const int64_t m = (int64_t)b.rows.size();
+  std::vector<int64_t> bad((size_t)host_threads() + 1, -1);
+  parallel_for(m, [&](int64_t k0, int64_t k1, int t) {
+    for (int64_t k = k0; k < k1; k++) {
+      const int64_t p = locate_entry(A, jlower, jupper, b.rows[(size_t)k], b.cols[(size_t)k]);
+      if (pos) pos[k] = p;
+      if (p == NOT_IN_PATTERN && bad[(size_t)t] < 0) bad[(size_t)t] = k;
+    }
+  });
+  int64_t first = -1;
+  for (int64_t k : bad)
+    if (k >= 0 && (first < 0 || k < first)) first = k;
+  return first;
+}
+}  // namespace
+
+void check_update_batch(const ParCSR &A, gidx jlower, gidx jupper, const IJEntryBatch &b) {
+  const int64_t k = locate_batch(A, jlower, jupper, b, nullptr);
+  if (k >= 0) refuse_entry(A, b.rows[(size_t)k], b.cols[(size_t)k]);
+}
+
+void update_parcsr_values(ParCSR &A, gidx jlower, gidx jupper, const std::vector<IJEntryBatch> &batches,
+                          const std::vector<IJUpdateConst> &consts) {
+  MI_REQUIRE(!A.host_diag_stale, "IJMatrix update: the host copy of the diag block was not built");
+  const int nrows = A.nrows;
+  int64_t E = 0;
+  std::vector<int64_t> boff;
+  for (auto &b : batches) {
+    boff.push_back(E);
+    E += (int64_t)b.rows.size();
+  }
+  boff.push_back(E);
+  // validate everything first: a refusal leaves the values as they were
+  std::vector<int64_t> pos((size_t)E);
+  for (size_t bi = 0; bi < batches.size(); bi++) {
+    const int64_t k = locate_batch(A, jlower, jupper, batches[bi], pos.data() + boff[bi]);
+    if (k >= 0) refuse_entry(A, batches[bi].rows[(size_t)k], batches[bi].cols[(size_t)k]);
+  }
+  // a constant takes effect before the entries with submission index >= cbefore
+  std::vector<int64_t> cbefore;
+  for (auto &c : consts) cbefore.push_back(boff[std::min(c.before_batch, batches.size())]);
+  // the entries bucketed by row, submission order kept inside a row
+  std::vector<int64_t> ra((size_t)nrows + 1, 0);
+  for (auto &b : batches)
+    for (gidx r : b.rows) ra[(size_t)(r - A.row_start) + 1]++;
+  for (int i = 0; i < nrows; i++) ra[(size_t)i + 1] += ra[(size_t)i];
+  std::vector<int64_t> bsub((size_t)E);
+  {
+    std::vector<int64_t> cur(ra.begin(), ra.end() - 1);
+    for (size_t bi = 0; bi < batches.size(); bi++)
+      for (size_t k = 0; k < batches[bi].rows.size(); k++)
+        bsub[(size_t)cur[(size_t)(batches[bi].rows[k] - A.row_start)]++] = boff[bi] + (int64_t)k;
+  }
+  HostCSR &D = A.diag, &O = A.offd;
+  parallel_for(nrows, [&](int64_t r0, int64_t r1, int) {
+    for (int64_t i = r0; i < r1; i++) {
+      auto fill_row = [&](double c) {
+        std::fill(D.a.begin() + D.ia[(size_t)i], D.a.begin() + D.ia[(size_t)i + 1], c);
+        std::fill(O.a.begin() + O.ia[(size_t)i], O.a.begin() + O.ia[(size_t)i + 1], c);
+      };
+      size_t kc = 0, bi = 0;
+      for (int64_t q = ra[(size_t)i]; q < ra[(size_t)i + 1]; q++) {
+        const int64_t sub = bsub[(size_t)q];
+        for (; kc < cbefore.size() && cbefore[kc] <= sub; kc++) fill_row(consts[kc].value);
+        while (boff[bi + 1] <= sub) bi++;
+        const double v = batches[bi].vals[(size_t)(sub - boff[bi])];
+        const int64_t p = pos[(size_t)sub];
+        double &dst = p >= 0 ? D.a[(size_t)p] : O.a[(size_t)~p];
+        dst = batches[bi].add ? dst + v : v;
+      }
+      if (kc < cbefore.size()) fill_row(consts.back().value);
+    }
+  });
+  A.assembly_stamp = next_assembly_stamp();
+}
+
+void refresh_device_values(ParCSR &A) {
+  if (!A.on_device) return;
+  hipStream_t s = ctx().stream;
+  MI_REQUIRE(A.d_diag.a.p || A.d_diag.nnz == 0, "IJMatrix update: the device diag block holds no fp64 values");
+  if (A.d_diag.nnz) MI_HIP(hipMemcpyAsync(A.d_diag.a.p, A.diag.a.data(), (size_t)A.d_diag.nnz * sizeof(double), hipMemcpyHostToDevice, s));
+  if (A.d_offd.nnz) MI_HIP(hipMemcpyAsync(A.d_offd.a.p, A.offd.a.data(), (size_t)A.d_offd.nnz * sizeof(double), hipMemcpyHostToDevice, s));
+  MI_HIP(hipStreamSynchronize(s));
+  // what depends on the values and nothing else: the tile schedule (rb), the tile descriptors (tdesc), the x-cache
+  // column lists (ucols, lcol) and the halo plan depend on the pattern alone and are not touched
+  k::build_value_dictionary(A.d_diag, s);
 }
 
 long long device_format_min_nnz() {

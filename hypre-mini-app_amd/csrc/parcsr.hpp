@@ -110,6 +110,25 @@ struct IJEntryBatch {
 void assemble_parcsr(Comm &comm, gidx ilower, gidx iupper, gidx jlower, gidx jupper,
                      std::vector<IJEntryBatch> &batches, ParCSR &out);
 
+// ---- value updates of an assembled matrix (HYPRE_IJMatrixSetValues / AddToValues / SetConstantValues after Assemble):
+// the pattern is frozen, a round of calls is applied in call order to the stored values
+// HYPRE_IJMatrixSetConstantValues at its place in a round: after `before_batch` batches
+struct IJUpdateConst {
+  size_t before_batch = 0;
+  double value = 0.0;
+};
+// fails (HYPRE_ERROR_GENERIC, naming global row and column) at the first entry of b, in submission order, whose row
+// is not owned or whose (row, column) is not in A's pattern
+void check_update_batch(const ParCSR &A, gidx jlower, gidx jupper, const IJEntryBatch &b);
+// The specification of an update round.  Everything is validated first (fails like check_update_batch: nothing is
+// written then); then, threads over rows, every row's operations are applied in submission order: Set replaces,
+// Add is one plain fp64 + per entry, a constant sets every stored entry of the row in both blocks.  Host arrays only.
+void update_parcsr_values(ParCSR &A, gidx jlower, gidx jupper, const std::vector<IJEntryBatch> &batches,
+                          const std::vector<IJUpdateConst> &consts);
+// after a host update: the device value arrays and the value dictionary follow diag.a / offd.a (no-op off the device)
+void refresh_device_values(ParCSR &A);
+unsigned long long next_assembly_stamp();
+
 // the end of an assembly, shared by the host path above and the device path (ij_assembly.hip): from the halo block's
 // global column ids (entry by entry; out.offd holds its rows and values) the column map and the compressed ids, then the
 // row partition (collective) and a fresh assembly stamp

@@ -703,6 +703,10 @@ void HypreSystem::solve() {
              relres_[(size_t)i]);
     fflush(stdout);
   }
+  updateSteps_ = get_optional(inpfile_["linear_system"], "mi_update_steps", 0);
+  if (updateSteps_ > 0 && !updatable_)
+    throw std::runtime_error("linear_system: mi_update_steps needs the synthetic laplace_3d system");
+  for (int step = 1; step <= updateSteps_; ++step) update_step(step, setup, solve_t);
   push_timer("Preconditioner setup", setup);
   if (writeAmgMatrices_) push_timer("Write AMG Matrices", write_operators);
   push_timer("Solve", solve_t);
@@ -865,6 +869,63 @@ void HypreSystem::hypre_vector_set_values(std::vector<HYPRE_IJVector> &vec, int 
     hypre_TFree(di, HYPRE_MEMORY_DEVICE), hypre_TFree(dv, HYPRE_MEMORY_DEVICE);
   } else if (!vector_values_.empty())
     HYPRE_IJVectorSetValues(v, (HYPRE_Int)vector_values_.size(), vector_indices_.data(), vector_values_.data());
+}
+
+// One time step of a caller that keeps its IJ matrix: new values on the frozen pattern, then Setup and Solve again.
+void HypreSystem::update_step(int step, double &setup, double &solve_t) {
+  const double scale = 1.0 + 0.5 * step;
+  const bool on_device = device_assembly();
+  HYPRE_BigInt nnz = 0;
+  HYPRE_BigInt *rows = nullptr, *cols = nullptr;
+  HYPRE_Complex *vals = nullptr, *rhs = nullptr;
+  if (HYPRE_MI_Laplace3D(nx_, ny_, nz_, stencil_, iLower_, iUpper_, &nnz, &rows, &cols, &vals, &rhs))
+    throw std::runtime_error("synthetic generator failed");
+  for (HYPRE_BigInt k = 0; k < nnz; k++) vals[k] *= scale;
+  for (HYPRE_BigInt i = 0; i < numRows_; i++) rhs[i] *= scale;  // b = A * 1 still
+  MPI_Barrier(comm_);
+  Stopwatch s0;
+  HYPRE_IJMatrixInitialize(mat_);
+  HYPRE_IJMatrixSetConstantValues(mat_, 0.0);
+  HYPRE_BigInt *dr = rows, *dc = cols, *di = vector_indices_.data();
+  HYPRE_Complex *dv = vals, *db = rhs;
+  if (on_device) {
+    dr = to_device(rows, (size_t)nnz), dc = to_device(cols, (size_t)nnz), dv = to_device(vals, (size_t)nnz);
+    di = to_device(vector_indices_.data(), vector_indices_.size()), db = to_device(rhs, (size_t)numRows_);
+  }
+  const size_t chunk = (size_t)1 << 30;
+  for (size_t s = 0; s < (size_t)nnz; s += chunk) {
+    const size_t e = std::min<size_t>((size_t)nnz, s + chunk);
+    HYPRE_IJMatrixAddToValues2(mat_, (HYPRE_Int)(e - s), NULL, dr + s, NULL, dc + s, dv + s);
+  }
+  if (HYPRE_IJMatrixAssemble(mat_)) throw std::runtime_error("mi_update_steps: the update round was refused");
+  HYPRE_IJMatrixGetObject(mat_, (void **)&parMat_);
+  HYPRE_IJVectorSetComponent(rhs_[0], 0);
+  HYPRE_IJVectorSetValues(rhs_[0], (HYPRE_Int)numRows_, di, db);
+  HYPRE_ParVectorSetConstantValues(parSln_[0], 0.0);
+  if (on_device) {
+    hypre_TFree(dr, HYPRE_MEMORY_DEVICE), hypre_TFree(dc, HYPRE_MEMORY_DEVICE), hypre_TFree(dv, HYPRE_MEMORY_DEVICE);
+    hypre_TFree(di, HYPRE_MEMORY_DEVICE), hypre_TFree(db, HYPRE_MEMORY_DEVICE);
+  }
+  HYPRE_MI_Free(rows), HYPRE_MI_Free(cols), HYPRE_MI_Free(vals), HYPRE_MI_Free(rhs);
+  MPI_Barrier(comm_);
+  if (iproc_ == 0) printf("Update step %d : values scaled by %g in place, %.3f s\n", step, scale, s0.seconds());
+
+  Stopwatch s1;
+  if (solverSetupPtr_(solver_, parMat_, parRhs_[0], parSln_[0])) throw std::runtime_error("setup after an update step failed");
+  MPI_Barrier(comm_);
+  setup += s1.seconds();
+  Stopwatch s3;
+  solverSolvePtr_(solver_, parMat_, parRhs_[0], parSln_[0]);
+  MPI_Barrier(comm_);
+  solve_t += s3.seconds();
+  HYPRE_Int iters = 0;
+  double relres = 0.0;
+  if (solverItersPtr_) solverItersPtr_(solver_, &iters);
+  if (solverResPtr_) solverResPtr_(solver_, &relres);
+  if (iproc_ == 0) printf("Solve %d : %d iterations, final relative residual %.6e\n", step, (int)iters, relres);
+  solveComplete_ = true;
+  check_solution();
+  fflush(stdout);
 }
 
 void HypreSystem::read_vector_files(const YAML::Node &linsys, std::vector<std::string> &rhs,
@@ -1179,6 +1240,8 @@ void HypreSystem::build_stencil(int default_stencil, bool per_rank_dims) {
     M_ = N_ = (int)totalRows_;
     init_row_decomposition();
     init_system();
+    stencil_ = stencil;
+    updatable_ = true;
     const bool on_device = device_assembly();
     if ((on_device ? HYPRE_MI_Laplace3DDevice : HYPRE_MI_Laplace3D)(nx_, ny_, nz_, stencil, iLower_, iUpper_, &nnz, &rows, &cols,
                                                                     &vals, &rhs))

@@ -61,6 +61,11 @@ class HypreSystem {
   void load_hypre_format();
   void build_stencil(int default_stencil, bool per_rank_dims);
   bool device_assembly();  // linear_system: mi_device_assembly
+  // linear_system: mi_update_steps: K (default 0).  After the first solve, K times: the matrix gets new values in place
+  // (Initialize, SetConstantValues(0), the same entries scaled by 1 + 0.5 * step added, Assemble -- the pattern stays),
+  // the right-hand side is scaled alike, preconditioner and solver are set up again and the system is solved.
+  // The reference has no such key; synthetic laplace_3d systems only.
+  void update_step(int step, double &setup, double &solve_t);
   void determine_ij_system_sizes(const std::string &, int);
   void determine_mm_system_sizes(const std::string &);
   void init_row_decomposition();
@@ -121,6 +126,8 @@ class HypreSystem {
   int M_{0}, N_{0};
   long long nnz_{0};
   int nx_{0}, ny_{0}, nz_{0};
+  int stencil_{0}, updateSteps_{0};
+  bool updatable_{false};  // built by the laplace_3d generator: update_step can make the entries again
   int iproc_{0}, nproc_{0};
 
   bool segregatedSolve_{true}, solveComplete_{false}, checkSolution_{false}, outputSystem_{false},

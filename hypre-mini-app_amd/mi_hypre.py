@@ -148,7 +148,16 @@ class IJMatrix:
         call(fn, self.h, nrows, vp(ncols_ptr), vp(rows_ptr), vp(row_indexes_ptr) if row_indexes_ptr else None,
              vp(cols_ptr), vp(vals_ptr))
 
+    def initialize(self):
+        """On an assembled matrix: opens an update round; the stored values stay."""
+        call("HYPRE_IJMatrixInitialize", self.h)
+
+    def set_constant_values(self, v):
+        call("HYPRE_IJMatrixSetConstantValues", self.h, c_dbl(v))
+
     def assemble(self):
+        """The first call builds the matrix; a later one closes an update round (set / add calls after the first
+        assemble change values of the frozen pattern) and is a no-op when no round is open."""
         call("HYPRE_IJMatrixAssemble", self.h)
         call("HYPRE_IJMatrixGetObject", self.h, C.byref(self.par))
 
@@ -724,6 +733,22 @@ def laplace3d_device_free(g):
 def counter(name):
     v = C.c_longlong()
     call("HYPRE_MI_GetCounter", name.encode(), C.byref(v))
+    return v.value
+
+
+def assembly_stamp(A):
+    """unique per assembly and per closed update round of an IJ matrix"""
+    par = A.par if hasattr(A, "par") else A
+    v = C.c_ulonglong()
+    call("HYPRE_MI_ParCSRGetAssemblyStamp", par, C.byref(v))
+    return v.value
+
+
+def parcsr_value_kind(A):
+    """0: the device diag block streams plain fp64 values, 8: through a value dictionary"""
+    par = A.par if hasattr(A, "par") else A
+    v = c_int()
+    call("HYPRE_MI_ParCSRGetValueKind", par, C.byref(v))
     return v.value
 
 

@@ -21,6 +21,11 @@ HYPRE_Int HYPRE_IJMatrixCreate(MPI_Comm comm, HYPRE_BigInt ilower, HYPRE_BigInt 
                                HYPRE_BigInt jupper, HYPRE_IJMatrix *matrix);
 HYPRE_Int HYPRE_IJMatrixDestroy(HYPRE_IJMatrix matrix);                            /* :501 */
 HYPRE_Int HYPRE_IJMatrixSetObjectType(HYPRE_IJMatrix matrix, HYPRE_Int type);      /* :553 */
+/* After the first HYPRE_IJMatrixAssemble the sparsity pattern is frozen.  Initialize (which keeps the stored values),
+ * SetValues(2), AddToValues(2) and SetConstantValues then open an update round that the next Assemble closes: its calls
+ * are applied in call order to the stored values.  An entry outside the pattern is refused (HYPRE_ERROR_GENERIC, the
+ * message names its global row and column) and the whole round is discarded; the matrix keeps its values.  On N > 1
+ * ranks the Assemble of a round is collective.  Assemble with no round open does nothing. */
 HYPRE_Int HYPRE_IJMatrixInitialize(HYPRE_IJMatrix matrix);                         /* :554 */
 /* :555, :606 -- borrowed HYPRE_ParCSRMatrix, valid before and after Assemble */
 HYPRE_Int HYPRE_IJMatrixGetObject(HYPRE_IJMatrix matrix, void **object);

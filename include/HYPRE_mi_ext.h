@@ -70,6 +70,11 @@ HYPRE_Int HYPRE_MI_ParCSRGetCSRSize(HYPRE_ParCSRMatrix A, HYPRE_Int which, HYPRE
                                     HYPRE_BigInt *nnz);
 HYPRE_Int HYPRE_MI_ParCSRGetCSR(HYPRE_ParCSRMatrix A, HYPRE_Int which, HYPRE_BigInt *ia, HYPRE_Int *ja, HYPRE_Complex *a);
 HYPRE_Int HYPRE_MI_ParCSRGetColMapOffd(HYPRE_ParCSRMatrix A, HYPRE_BigInt *col_map_offd);
+/* the assembly stamp: unique per assembly and per closed update round of an IJ matrix (0 = never assembled); a
+ * preconditioner set up on another stamp was built from other values */
+HYPRE_Int HYPRE_MI_ParCSRGetAssemblyStamp(HYPRE_ParCSRMatrix A, unsigned long long *stamp);
+/* how the device diag block streams its values: 0 plain fp64, 8 through a value dictionary (at most 256 distinct values) */
+HYPRE_Int HYPRE_MI_ParCSRGetValueKind(HYPRE_ParCSRMatrix A, HYPRE_Int *kind);
 
 /* ---- device / stream */
 HYPRE_Int HYPRE_MI_GetStream(void **hip_stream);
