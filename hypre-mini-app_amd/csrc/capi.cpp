@@ -1741,6 +1741,67 @@ HYPRE_Int HYPRE_MI_TileScheduleCheck(HYPRE_Int n, const HYPRE_BigInt *row_ptr, H
   API_END
 }
 
+// test hook (tests/test_gpu_krylov_paths.py): exactly one launch sequence of one of the Krylov loops' vector kernels, on
+// this rank's part of the given ParVectors (all components of a multivector; no collective).  Device coefficients go
+// into the context's scalar slots the way GmresSolver::solve leaves them there; scalar results come back in out.
+//   op 0  k::mass_dot            out[j] = <vecs[j], w>, j < m                                   (1 <= m <= 120)
+//   op 1  k::mass_axpy           w += sum_j (scale * coef[j]) vecs[j], coef in device slots     (1 <= m <= 120)
+//   op 2  k::lin_comb            w = (init) / w += sum_j coef[j] vecs[j], coef passed by value  (1 <= m <= 250)
+//   op 3  k::axpy_dot            w += (scale * coef[0]) vecs[0]; out[0] = <xd, w> (xd NULL: <w, w>)
+//   op 4  k::scale_inv_sqrt_post w *= 1 / sqrt(coef[0]) when coef[0] > 0; the m slots coef[0 .. m) are posted into
+//         pinned host memory, then the sequence number: out[0 .. m) = the posted doubles, out[m] = the flag word after
+//         the kernel, out[m + 1] = the sequence number the kernel was given                    (1 <= m <= 255)
+HYPRE_Int HYPRE_MI_VectorKernelOp(HYPRE_Int op, HYPRE_Int m, HYPRE_ParVector *vecs, const HYPRE_Real *coef,
+                                  HYPRE_Real scale, HYPRE_ParVector w, HYPRE_ParVector xd, HYPRE_Int init,
+                                  HYPRE_Real *out) {
+  API_BEGIN
+  ensure_init();
+  Ctx &c = ctx();
+  hipStream_t s = c.stream;
+  MI_REQUIRE(w, "VectorKernelOp: NULL vector w");
+  MI_REQUIRE(op >= 0 && op <= 4, "VectorKernelOp: op must be 0 .. 4");
+  const int mmax = (op <= 1) ? 120 : (op == 2 ? 250 : (op == 3 ? 1 : 255));
+  MI_REQUIRE(m >= 1 && m <= mmax, "VectorKernelOp: m out of range for this op");
+  MI_REQUIRE(op == 0 || coef, "VectorKernelOp: NULL coefficients");
+  MI_REQUIRE(op == 1 || op == 2 || out, "VectorKernelOp: NULL output");
+  const int n = PV(w)->len();
+  std::vector<const double *> vp;
+  if (op != 4) {
+    MI_REQUIRE(vecs, "VectorKernelOp: NULL vector list");
+    for (int j = 0; j < m; j++) {
+      MI_REQUIRE(vecs[j] && PV(vecs[j])->len() == n, "VectorKernelOp: vecs[j] is NULL or differs from w in length");
+      MI_REQUIRE(vecs[j] != w, "VectorKernelOp: w among vecs");
+      vp.push_back(PV(vecs[j])->all());
+    }
+  }
+  MI_REQUIRE(!xd || (op == 3 && PV(xd)->len() == n && xd != w), "VectorKernelOp: xd goes with op 3 and has w's length");
+  double *slots = c.red_out.p;
+  if (op == 1 || op == 3 || op == 4)
+    MI_HIP(hipMemcpyAsync(slots, coef, (size_t)(op == 3 ? 1 : m) * sizeof(double), hipMemcpyHostToDevice, s));
+  switch (op) {
+    case 0:
+      k::mass_dot(vp.data(), m, PV(w)->all(), n, slots, s);
+      d2h(out, slots, (size_t)m * sizeof(double), s);
+      break;
+    case 1: k::mass_axpy(vp.data(), m, slots, scale, PV(w)->all(), n, s); break;
+    case 2: k::lin_comb(vp.data(), coef, m, init != 0, PV(w)->all(), n, s); break;
+    case 3:
+      k::axpy_dot(slots, scale, vp[0], PV(w)->all(), xd ? PV(xd)->all() : nullptr, n, slots + 1, s);
+      d2h(out, slots + 1, sizeof(double), s);
+      break;
+    default: {
+      const unsigned long long seq = ++c.post_seq;
+      k::scale_inv_sqrt_post(slots, PV(w)->all(), n, slots, m, c.h_pinned + 256, c.h_post_flag, seq, s);
+      MI_HIP(hipStreamSynchronize(s));
+      for (int j = 0; j < m; j++) out[j] = c.h_pinned[256 + j];
+      out[m] = (double)__atomic_load_n(c.h_post_flag, __ATOMIC_ACQUIRE);
+      out[m + 1] = (double)seq;
+    }
+  }
+  MI_HIP(hipStreamSynchronize(s));
+  API_END
+}
+
 HYPRE_Int HYPRE_MI_ArenaSelfTest(HYPRE_Int seed, HYPRE_Int rounds, HYPRE_BigInt max_block_bytes, HYPRE_BigInt *verified,
                                  HYPRE_BigInt *peak_bytes) {
   API_BEGIN

@@ -452,6 +452,13 @@ int PcgSolver::solve(ParCSR &A_in, ParVector &b_in, ParVector &x_in) {
   norms.clear();
   converged = false;
   num_iterations = 0;
+  if (bi_prod != bi_prod) {  // NaN in b or in the preconditioner (pcg.c's IEEE check comes before its zero-rhs exit):
+    leave_level_order(amg, x_in);  // x as it came in
+    MI_HIP(hipStreamSynchronize(s));
+    rel_residual_norm = bi_prod;
+    solve_seconds = wall_time() - t_start;
+    return 1;
+  }
   if (!(bi_prod > 0.0)) {  // zero right-hand side: x = 0 (pcg.c)
     k::fill(x.all(), n, 0.0, s);
     leave_level_order(amg, x_in);

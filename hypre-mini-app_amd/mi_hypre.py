@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("MI_HYPRE_LIB") or os.path.join(_HERE, "libmi_hypre.so
 HYPRE_PARCSR = 5555
 HYPRE_MEMORY_DEVICE = 1
 HYPRE_EXEC_DEVICE = 1
+HYPRE_ERROR_GENERIC = 1
 HYPRE_ERROR_CONV = 256
 
 c_big = C.c_longlong
@@ -613,8 +614,10 @@ class FSAI:
 class _Krylov:
     prefix = None
 
-    def __init__(self, tolerance=1e-5, max_iterations=1000, kspace=10, print_level=4):
-        """setup_gmres / setup_bicg, /root/reference/src/HypreSystem.cpp:390-404, :423-438 (same defaults)."""
+    def __init__(self, tolerance=1e-5, max_iterations=1000, kspace=10, print_level=4, absolute_tol=None,
+                 min_iterations=None):
+        """setup_gmres / setup_bicg, /root/reference/src/HypreSystem.cpp:390-404, :423-438 (same defaults);
+        absolute_tol / min_iterations: SetAbsoluteTol / SetMinIter when given (the driver never calls them)."""
         self.h = vp()
         call(f"{self.prefix}Create", 0, C.byref(self.h))
         call(f"{self.prefix}SetTol", self.h, float(tolerance))
@@ -622,6 +625,10 @@ class _Krylov:
         if self.prefix.endswith("GMRES"):
             call(f"{self.prefix}SetKDim", self.h, int(kspace))
         call(f"{self.prefix}SetPrintLevel", self.h, int(print_level))
+        if absolute_tol is not None:
+            call(f"{self.prefix}SetAbsoluteTol", self.h, float(absolute_tol))
+        if min_iterations is not None:
+            call(f"{self.prefix}SetMinIter", self.h, int(min_iterations))
         self.precond = None
 
     def set_precond(self, amg):
@@ -635,8 +642,14 @@ class _Krylov:
     def setup(self, A, b, x):
         call(f"{self.prefix}Setup", self.h, A.par, b.par, x.par)
 
-    def solve(self, A, b, x):
-        return call(f"{self.prefix}Solve", self.h, A.par, b.par, x.par, allow=(HYPRE_ERROR_CONV,))
+    def solve(self, A, b, x, allow_generic=False):
+        """0, or HYPRE_ERROR_CONV (256) when max_iterations ended the solve.  allow_generic: also hand out 1
+        (HYPRE_ERROR_GENERIC: a NaN ended the solve) instead of raising, with the error flag cleared."""
+        allow = (HYPRE_ERROR_CONV, HYPRE_ERROR_GENERIC) if allow_generic else (HYPRE_ERROR_CONV,)
+        rc = call(f"{self.prefix}Solve", self.h, A.par, b.par, x.par, allow=allow)
+        if rc == HYPRE_ERROR_GENERIC:
+            call("HYPRE_ClearAllErrors")
+        return rc
 
     @property
     def num_iterations(self):
@@ -689,9 +702,21 @@ class FlexGMRES(_Krylov):
 class PCG(_Krylov):
     prefix = "HYPRE_ParCSRPCG"
 
+    def __init__(self, *args, two_norm=None, **kw):
+        """two_norm 1: the convergence measure is <r, r> / <b, b> instead of <C r, r> / <C b, b>"""
+        super().__init__(*args, **kw)
+        if two_norm is not None:
+            call("HYPRE_ParCSRPCGSetTwoNorm", self.h, int(two_norm))
+
 
 class COGMRES(_Krylov):
     prefix = "HYPRE_ParCSRCOGMRES"
+
+    def __init__(self, *args, cgs=None, **kw):
+        """cgs <= 1: one classical Gram-Schmidt pass per Arnoldi step (the default), cgs >= 2: two"""
+        super().__init__(*args, **kw)
+        if cgs is not None:
+            call("HYPRE_ParCSRCOGMRESSetCGS", self.h, int(cgs))
 
 
 def laplace3d(nx, ny, nz, stencil, ilower, iupper):
@@ -948,3 +973,25 @@ def csr_device_op(op, A, B=None, perm=None, colpos=None):
     for ptr in (cia, cja, ca):
         lib().HYPRE_MI_Free(ptr)
     return ia, ja, a, (nr.value, nc.value)
+
+
+VEC_MASS_DOT, VEC_MASS_AXPY, VEC_LIN_COMB, VEC_AXPY_DOT, VEC_SCALE_POST = range(5)
+
+
+def vector_kernel_op(op, vecs, coef, w, scale=1.0, xd=None, init=False):
+    """One of the Krylov loops' vector kernels on IJVectors (HYPRE_MI_VectorKernelOp, test hook): returns the scalar
+    results -- m inner products (VEC_MASS_DOT), one (VEC_AXPY_DOT), (posted doubles, flag word, sequence number) for
+    VEC_SCALE_POST, None for the updates.  w (and nothing else) is changed in place on the device."""
+    m = len(coef) if op == VEC_SCALE_POST else len(vecs)
+    arr = (vp * max(len(vecs), 1))(*[v.par for v in vecs])
+    cf = None if coef is None else dbl(coef)
+    out = np.zeros(m + 2)
+    call("HYPRE_MI_VectorKernelOp", op, m, arr, cf, c_dbl(scale), w.par, xd.par if xd is not None else None,
+         1 if init else 0, out)
+    if op == VEC_MASS_DOT:
+        return out[:m].copy()
+    if op == VEC_AXPY_DOT:
+        return float(out[0])
+    if op == VEC_SCALE_POST:
+        return out[:m].copy(), int(out[m]), int(out[m + 1])
+    return None

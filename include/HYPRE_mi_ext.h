@@ -96,6 +96,17 @@ HYPRE_Int HYPRE_MI_BoomerAMGPoisonWorkVectors(HYPRE_Solver solver);
  * host's tile count.  row_cap: 256 (operators a Gauss-Seidel kernel sweeps) ... 1024 (SpMV only); tile_entries: 2048 / 4096 */
 HYPRE_Int HYPRE_MI_TileScheduleCheck(HYPRE_Int n, const HYPRE_BigInt *row_ptr, HYPRE_Int row_cap, HYPRE_Int tile_entries,
                                      HYPRE_Int *ntiles, HYPRE_Int *mismatch);
+/* test hook: exactly one of the Krylov loops' vector kernels on this rank's part of ParVectors (every component of a
+ * multivector, no collective); device coefficients are uploaded into the scalar slots the solvers use, the call
+ * synchronises and copies scalar results into out.  op 0 block inner products out[j] = <vecs[j], w> (m <= 120); 1 block
+ * update w += sum_j (scale * coef[j]) vecs[j] (m <= 120); 2 linear combination w = (init != 0) or w += sum_j coef[j]
+ * vecs[j] (m <= 250); 3 fused update and inner product w += (scale * coef[0]) vecs[0], out[0] = <xd, w> (xd NULL:
+ * <w, w>), m = 1; 4 the scaling kernel that posts an Arnoldi step's Hessenberg column to the host: w *= 1 / sqrt(coef[0])
+ * when coef[0] > 0, out[0 .. m) = the m posted doubles (coef as the slots held them), out[m] = the flag word after the
+ * kernel, out[m + 1] = the sequence number it was given (m <= 255).  The block kernels work in passes of 8 vectors. */
+HYPRE_Int HYPRE_MI_VectorKernelOp(HYPRE_Int op, HYPRE_Int m, HYPRE_ParVector *vecs, const HYPRE_Real *coef,
+                                  HYPRE_Real scale, HYPRE_ParVector w, HYPRE_ParVector xd, HYPRE_Int init,
+                                  HYPRE_Real *out);
 /* test hook: a seeded storm of device allocations / releases of every size through the library's allocator (arena, block
  * cache or plain, whatever MI_HYPRE_POOL says), every block pattern-filled and checked before its release */
 HYPRE_Int HYPRE_MI_ArenaSelfTest(HYPRE_Int seed, HYPRE_Int rounds, HYPRE_BigInt max_block_bytes, HYPRE_BigInt *verified,

@@ -79,6 +79,9 @@ def main():
                     help="with --random: 1 = 30 %% of the couplings positive (0.4 of their size); 2 = also the whole "
                          "operator and right-hand side negated; 3 = 1 plus 30 %% of the rows multiplied by -1 (negative "
                          "diagonals among positive ones; host mode only: its solves are not known to converge)")
+    ap.add_argument("--x0", type=int, default=0,
+                    help="solve mode: seed of a random initial guess for the library's Krylov solves and the oracle's "
+                         "GMRES (0 = the zero guess): x0 gathered into the level ordering, the first residual b - A x0")
     args = ap.parse_args()
     if args.signs and not args.random:
         ap.error("--signs needs --random")
@@ -355,9 +358,21 @@ def main():
                 out[name] = v.value
             return out
 
+        # --x0: the same global random vector on every rank (caller's numbering); the oracle gets it in the numbering of
+        # its operator
+        x0g = np.random.default_rng(args.x0).standard_normal(N) if args.x0 else np.zeros(N)
+        x0_used = x0g if Ao_used is Ao else x0g[order_g]
+
+        def reset_x():
+            if args.x0:
+                x.set(x0g[starts[rank]:starts[rank + 1]])
+            else:
+                x.fill(0.0)
+
         gm = mi.GMRES(tolerance=1e-8, max_iterations=60, kspace=20, print_level=0)
         gm.set_precond(amg)
         gm.setup(A, b, x)
+        reset_x()
         c0 = counters()
         rc = gm.solve(A, b, x)
         c1 = counters()
@@ -377,7 +392,7 @@ def main():
                 assert per_cycle <= 7 * n_dist + 2, (per_cycle, n_dist)
                 assert (c1["allgather"] - c0["allgather"]) <= cycles  # coarsest gather or redundant tail: one per cycle
             # COGMRES (method: cogmres, src/HypreSystem.cpp:372-388): one block all-reduce + the norm per step
-            x.fill(0.0)
+            reset_x()
             cg = mi.COGMRES(tolerance=1e-8, max_iterations=60, kspace=20, print_level=0)
             cg.set_precond(amg)
             cg.setup(A, b, x)
@@ -391,9 +406,9 @@ def main():
                 print(f"collectives per solve: GMRES {c1['allreduce'] - c0['allreduce']} all-reduces ({m} iterations), "
                       f"COGMRES {c3['allreduce'] - c2['allreduce']} ({mc} iterations), {per_cycle:.1f} halo exchanges per cycle "
                       f"on {n_dist} distributed levels")
-            x.fill(0.0)
+            reset_x()
             assert gm.solve(A, b, x) == 0  # back to the GMRES solution for the checks below
-        xo, info = oc.gmres(Ao_used, bo_used, kdim=20, tol=1e-8, maxit=60, amg=oamg)
+        xo, info = oc.gmres(Ao_used, bo_used, x0=x0_used, kdim=20, tol=1e-8, maxit=60, amg=oamg)
         assert gm.num_iterations == info["iters"], (gm.num_iterations, info["iters"])
         hist = gm.residual_history()
         assert np.allclose(hist, info["norms"], rtol=1e-7), (hist, info["norms"])

@@ -19,7 +19,7 @@ WORKER = os.path.join(ROOT, "tests", "dist_worker.py")
 
 def _run(nproc, mode, n, stencil, port, staging="host", seq=-1, devmin=None, golden="", replicated=False, locality=0,
          smooth=0, relax=0, combo=-1, transport="", ng=0.0, agg=0, interp=-1, aggtrunc=0.0, aggpmax=0, coarsen=-1, random=0,
-         signs=0):
+         signs=0, x0=0):
     env = dict(os.environ)
     env["MI_HYPRE_REPLICATED_SETUP"] = "1" if replicated else "0"
     if devmin is not None:  # levels with at least this many rows are built (and sliced) on the device
@@ -55,6 +55,8 @@ def _run(nproc, mode, n, stencil, port, staging="host", seq=-1, devmin=None, gol
         cmd += ["--random", str(random)]
     if signs:
         cmd += ["--signs", str(signs)]
+    if x0:
+        cmd += ["--x0", str(x0)]
     if nproc >= 5:
         # without the torch.distributed.run launcher: on a GPU box it holds the device open too, and launcher + pytest + 5
         # ranks are 7 processes on a card that admits 6
@@ -405,6 +407,16 @@ def test_device_solve_cuda_staged_transport():
     """bench.py's fallback transport (torch.distributed collectives on device tensors behind the callback
     interface), exercised here over gloo because two nccl ranks cannot share the one GPU of the test box."""
     out = _run(2, "solve", 12, 7, 29699, staging="cuda")
+    assert "dist solve ok" in out
+
+
+@pytest.mark.gpu
+def test_device_solve_nonzero_initial_guess_shared_gpu():
+    """Two ranks on the library's TCP transport with a random initial guess (tests/dist_worker.py --x0) for the
+    library's GMRES / COGMRES and the oracle's GMRES: x0 gathered through each rank's level-0 permutation, the first
+    residual b - A x0 across the halo, x scattered back; every assertion of the zero-guess solve stays.  (Seed 7: the
+    oracle's last two estimates are 2.2 and 0.20 times the threshold.)"""
+    out = _run(2, "solve", 12, 7, 29717, transport="tcp", x0=7)
     assert "dist solve ok" in out
 
 

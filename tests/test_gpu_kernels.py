@@ -72,8 +72,9 @@ def test_spmv_laplace_bitwise(mi, oc):
     assert np.array_equal(yi.get(), Ao.matvec(xv))
 
 
-@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 511, 100003])
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 511, 100003, 768 * 512 + 1, 2 * 768 * 512 + 3])
 def test_blas1(mi, n):
+    """(the last two lengths exceed 768 workgroups * 512 elements: the grid-stride loops take a second and a third trip)"""
     rng = np.random.default_rng(n)
     xv, yv = rng.standard_normal(n), rng.standard_normal(n)
     x = mi.IJVector(0, n - 1, xv)
