@@ -119,6 +119,10 @@ struct AmgLevel {
   // after the second one (+1 C, -1 F, -3 special F), natural order of the level; kept only when
   // AmgParams::keep_agg_markers asks for them (inspection)
   std::vector<signed char> agg_m1, agg_m2;
+  // what sk::interp ran for this level's P (HYPRE_MI_BoomerAMGGetInterpCensus); interp_by_host: P came from a host
+  // routine or another device routine and the census is all zeros (a level that fell back has census.fell_back)
+  sk::InterpCensus interp_census;
+  bool interp_by_host = true;
   bool has_cf = false;  // the level has a C/F splitting -- a GLOBAL fact (cf itself is empty on a rank without rows)
   DVec<signed char> d_cf;
   // C-first ordering of this level: perm[new] = old local row;

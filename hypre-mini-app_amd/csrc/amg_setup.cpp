@@ -2043,8 +2043,10 @@ void BoomerAMG::build_natural(ParCSR &A0) {
     bool p_on_device = false;
     if (on_device) {
       hipStream_t s = ctx().stream;
-      if (!aggressive && (p.interp_type == 6 || p.interp_type == 0))
-        p_on_device = sk::interp(Lv.sA, dS, dcf, p.interp_type, p.trunc_factor, p.pmax_elmts, Lv.sP, nc, s);
+      if (!aggressive && (p.interp_type == 6 || p.interp_type == 0)) {
+        p_on_device = sk::interp(Lv.sA, dS, dcf, p.interp_type, p.trunc_factor, p.pmax_elmts, Lv.sP, nc, s, &Lv.interp_census);
+        Lv.interp_by_host = false;
+      }
       if (two_stage) {
         if (!dcf1.p) dcf1.upload(cf1);  // (a coarsening the host ran: the interpolation is the device's all the same)
         if (p.keep_agg_markers) {  // (inspection: both markers to the host before the interpolation rewrites -3)

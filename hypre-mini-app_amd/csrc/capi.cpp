@@ -2099,6 +2099,15 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetLevelAggMarkers(HYPRE_Solver solver, HYPRE_Int le
       }
   API_END
 }
+HYPRE_Int HYPRE_MI_BoomerAMGGetInterpCensus(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int out[8]) {
+  API_BEGIN
+  const AmgLevel &Lv = level_ref(AMG(solver), level);
+  const sk::InterpCensus &c = Lv.interp_census;
+  const HYPRE_Int v[8] = {c.cap16, c.cap32, c.try32_kept, c.try32_retried, c.cap512, c.cap1024, c.max_bound,
+                          (c.fell_back ? 1 : 0) | (Lv.interp_by_host ? 2 : 0)};
+  for (int i = 0; i < 8; i++) out[i] = v[i];
+  API_END
+}
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelPerm(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int *perm) {
   API_BEGIN
   AmgSolver *a = AMG(solver);

@@ -2623,8 +2623,9 @@ void pmis(const DCsr &S, int seed, DVec<int> &cf, hipStream_t s) {
 }
 
 bool interp(const DCsr &A, const DCsr &S, DVec<int> &cf, int interp_type, double trunc_factor, int pmax, DCsr &P,
-            int &nc, hipStream_t s) {
+            int &nc, hipStream_t s, InterpCensus *census) {
   MI_REQUIRE(interp_type == 6 || interp_type == 0, "device interpolation: type 6 (ext+i) or 0 (classical modified)");
+  if (census) *census = InterpCensus();
   const int n = A.nrows;
   const int ext = interp_type == 6;
   P.release();
@@ -2636,7 +2637,11 @@ bool interp(const DCsr &A, const DCsr &S, DVec<int> &cf, int interp_type, double
   int hmeta[16];
   d2h(hmeta, meta.p, sizeof(hmeta), s);
   MI_HIP(hipStreamSynchronize(s));
-  if (hmeta[3] > 0 && hmeta[4] > 1024) return false;  // a row may exceed the largest LDS table
+  if (census) census->max_bound = hmeta[4];
+  if (hmeta[3] > 0 && hmeta[4] > 1024) {  // a row may exceed the largest LDS table
+    if (census) census->fell_back = true;
+    return false;
+  }
   Bins bins;
   for (int b = 0; b < 4; b++) bins.start[b + 1] = bins.start[b] + hmeta[b];
   for (int b = 0; b < 4; b++) hmeta[8 + b] = bins.start[b], hmeta[12 + b] = 0;
@@ -2655,6 +2660,7 @@ bool interp(const DCsr &A, const DCsr &S, DVec<int> &cf, int interp_type, double
   DVec<double> sa((size_t)tot[1]);
   const int n0 = bins.start[1] - bins.start[0], n1 = bins.start[2] - bins.start[1], n2 = bins.start[3] - bins.start[2],
             n3 = bins.start[4] - bins.start[3];
+  if (census) census->cap512 = n2, census->cap1024 = n3;
   if (n3)  // up to 1024 candidates: one workgroup per row
     interp_group_k<256, 1024, 256><<<grid_for(n3), 256, 0, s>>>(
         n3, rows.p + bins.start[3], ext, A.ia.p, A.ja.p, A.a.p, S.ia.p, S.ja.p, cf.p, f2c.p, trunc_factor, pmax,
@@ -2671,6 +2677,7 @@ bool interp(const DCsr &A, const DCsr &S, DVec<int> &cf, int interp_type, double
                                                                          part0.p + n0, cnt0);
     d2h(h0, cnt0, sizeof(h0), s);
     MI_HIP(hipStreamSynchronize(s));
+    if (census) census->cap16 = h0[0], census->cap32 = h0[1];
     if (h0[0])
       interp_group_k<8, 16, 256><<<grid_for(((long long)h0[0] + 31) / 32), 256, 0, s>>>(
           h0[0], part0.p, ext, A.ia.p, A.ja.p, A.a.p, S.ia.p, S.ja.p, cf.p, f2c.p, trunc_factor, pmax, slack_ia.p, sj.p,
@@ -2698,6 +2705,7 @@ bool interp(const DCsr &A, const DCsr &S, DVec<int> &cf, int interp_type, double
     d2h(h1, cnt1, sizeof(h1), s);
     MI_HIP(hipStreamSynchronize(s));
     const int nbig = h1[0];  // the rows marked -1, at the front of part1
+    if (census) census->try32_kept = n1 - nbig, census->try32_retried = nbig;
     if (nbig)
       interp_group_k<16, 128, 128><<<grid_for(((long long)nbig + 7) / 8), 128, 0, s>>>(
           nbig, part1.p, ext, A.ia.p, A.ja.p, A.a.p, S.ia.p, S.ja.p, cf.p, f2c.p, trunc_factor, pmax, slack_ia.p, sj.p,

@@ -40,8 +40,17 @@ void pmis(const DCsr &S, int seed, DVec<int> &cf, hipStream_t s);
 // trunc_factor, rows of A and S in ascending column order.  cf is updated like the host code does (-3 -> -1).
 // Returns false -- and builds nothing -- when a row's interpolatory set may exceed the kernels' LDS capacity
 // (the caller then runs the host routine for this level).  nc = number of C points.
+// census (optional): which instantiation of the kernel took how many of the rows (C points and rows without an
+// interpolatory set count with the smallest tables) -- numbers the routine has on the host anyway.
+struct InterpCensus {
+  int cap16 = 0, cap32 = 0;              // bound <= 16, <= 32
+  int try32_kept = 0, try32_retried = 0; // bound 33 ... 128: finished in the 32-entry tables / rerun in the 128-entry ones
+  int cap512 = 0, cap1024 = 0;           // bound 129 ... 512, 513 ... 1024
+  int max_bound = 0;                     // the largest bound of the level
+  bool fell_back = false;                // a row's bound exceeds 1024: nothing ran, the return value is false
+};
 bool interp(const DCsr &A, const DCsr &S, DVec<int> &cf, int interp_type, double trunc_factor, int pmax, DCsr &P,
-            int &nc, hipStream_t s);
+            int &nc, hipStream_t s, InterpCensus *census = nullptr);
 
 // Aggressive level (amg_setup.cpp coarsen_aggressive): cf holds the marker of the first coarsening on entry.  The
 // second-generation graph on its C points (C point i depends on C point j != i iff j is in S_i or in S_k for some k in

@@ -395,6 +395,16 @@ class BoomerAMG:
         call("HYPRE_MI_BoomerAMGGetLevelAggMarkers", self.h, level, m1, m2)
         return m1, m2
 
+    def interp_census(self, level):
+        """What the device interpolation kernel ran for the level's P: rows per instantiation, the largest bound and
+        the flags fell_back (a bound above 1024: host routine) / host (the kernel was not asked)."""
+        out = np.zeros(8, dtype=np.int32)
+        call("HYPRE_MI_BoomerAMGGetInterpCensus", self.h, level, out)
+        names = ("cap16", "cap32", "try32_kept", "try32_retried", "cap512", "cap1024", "max_bound")
+        d = {k: int(v) for k, v in zip(names, out)}
+        d["fell_back"], d["host"] = bool(out[7] & 1), bool(out[7] & 2)
+        return d
+
     def level_perm(self, level):
         """perm[new local row] = old local row of the level's C-first ordering."""
         nr, nc, nnz = c_int(), c_int(), c_big()

@@ -195,6 +195,14 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetLevelValueStorage(HYPRE_Solver solver, HYPRE_Int 
  * Setup (two bytes per row of host memory; off by default).  An error on every other level. */
 HYPRE_Int HYPRE_MI_BoomerAMGSetKeepAggMarkers(HYPRE_Solver solver, HYPRE_Int keep);
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelAggMarkers(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int *stage1, HYPRE_Int *stage2);
+/* What the device interpolation kernel ran to build the level's P (one rank): rows are binned by a
+ * bound T on their interpolatory set and every bin has its own instantiation.  out[0..5]: rows taken by the 16-entry
+ * tables (T <= 16, C points and empty rows included), the 32-entry tables (T <= 32), the 32-entry tables tried for
+ * 33 <= T <= 128 and kept, the same rows given up and rerun in 128-entry tables, the 512-entry tables (T <= 512), the
+ * 1024-entry tables (T <= 1024); out[6]: the largest T of the level; out[7]: flags -- 1: a row had T > 1024 and the
+ * level's P was handed to the host routine (out[0..5] are zero), 2: the kernel was not asked at all (level set up on
+ * the host, another interpolation type, the coarsest level; everything else is zero). */
+HYPRE_Int HYPRE_MI_BoomerAMGGetInterpCensus(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int out[8]);
 /* the level's C-first ordering: perm[new local row] = old local row (level matrices, P, R and the
  * C/F marker are reported in the NEW ordering; level 0 is a renumbered copy of the caller's matrix) */
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelPerm(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int *perm);

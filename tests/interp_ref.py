@@ -37,13 +37,14 @@ def special_f_points(S, cf):
     return (np.asarray(cf) != 1) & (np.diff(S.indptr) == 0)
 
 
-def extended_i_reference(A, S, cf, census=None):
+def extended_i_reference(A, S, cf, census=None, only_rows=None):
     """P (no truncation) by the extended+i formula: for an F point i with strong C neighbours C_i, strong F neighbours
     F_i (special F points excepted) and Chat_i = C_i U (U_{k in F_i} C_k):
         w_ij = -(1 / att_i) (a_ij + sum_{k in F_i} a_ik abar_kj / d_ik),  j in Chat_i,
         att_i = a_ii + sum_{n weak or special-F neighbour of i, n not in Chat_i} a_in + sum_{k in F_i} a_ik abar_ki / d_ik,
         d_ik = sum_{l in Chat_i U {i}} abar_kl,   abar_kl = a_kl if its sign differs from a_kk's, else 0;
-    a k in F_i with d_ik = 0 adds a_ik to att_i instead.  census (a dict) counts the special-F and zero-sum events."""
+    a k in F_i with d_ik = 0 adds a_ik to att_i instead.  census (a dict) counts the special-F and zero-sum events.
+    only_rows: the F rows to compute (the others stay empty, and out of the census); default all."""
     rows, strong = _rows_and_strong(A, S)
     n = len(rows)
     cf = np.asarray(cf)
@@ -60,6 +61,8 @@ def extended_i_reference(A, S, cf, census=None):
     for i in range(n):
         if cf[i] == 1:
             P[i, cidx[i]] = 1.0
+            continue
+        if only_rows is not None and i not in only_rows:
             continue
         Ci = [j for j in strong[i] if cf[j] == 1]
         Fi = [k for k in strong[i] if cf[k] != 1 and not special[k]]
@@ -92,10 +95,11 @@ def extended_i_reference(A, S, cf, census=None):
     return P.tocsr()
 
 
-def classical_modified_reference(A, S, cf, census=None):
+def classical_modified_reference(A, S, cf, census=None, only_rows=None):
     """P (no truncation) by classical modified interpolation: for an F point i with strong C neighbours C_i,
         w_ij = -(a_ij + sum_{k in F_i} a_ik abar_kj / sum_{m in C_i} abar_km) / (a_ii + sum_{weak or special-F n} a_in),
-    abar as above; a strong F neighbour without a common C point (zero distribution sum) is lumped into the diagonal."""
+    abar as above; a strong F neighbour without a common C point (zero distribution sum) is lumped into the diagonal.
+    census, only_rows: as in extended_i_reference."""
     rows, strong = _rows_and_strong(A, S)
     n = len(rows)
     cf = np.asarray(cf)
@@ -107,6 +111,8 @@ def classical_modified_reference(A, S, cf, census=None):
     for i in range(n):
         if cf[i] == 1:
             P[i, cidx[i]] = 1.0
+            continue
+        if only_rows is not None and i not in only_rows:
             continue
         Ci = [j for j in strong[i] if cf[j] == 1]
         if not Ci:

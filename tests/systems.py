@@ -76,3 +76,70 @@ def mixed_sign_system(n, seed, flip_rows, pos_frac, per, symmetric_pattern=True)
 # negative with M-matrix magnitudes; every diagonal positive with 35 % positive couplings)
 MIXED_SIGN_CASES = [(2000, 43, .3, .25, 1.5), (2000, 49, .3, .25, 4.5), (2000, 58, .5, .3, 9), (1500, 76, .3, .25, 18),
                     (1200, 130, .3, .25, 45), (2000, 49, 1.0, 0, 4.5), (2000, 49, 0, .35, 4.5)]
+
+
+# ---- operators of the interpolation-table tests (tests/test_interp_tables_spec.py, tests/test_gpu_interp_tables.py)
+HUB_BASE = (3000, 49, .3, .25, 4.5)
+HUB_LENGTHS = (16, 17, 32, 33, 128, 129, 512, 513, 1024)   # a table's capacity and one more, for every table
+
+
+def hub_system(lengths, seed, base=HUB_BASE):
+    """mixed_sign_system(*base) with planted ONE-WAY hub rows; returns (operator, hub rows, their lengths).
+    Hub number q (row hubs[q], a seeded choice) gets lengths[q] strong couplings to seeded non-hub columns and every entry
+    of column hubs[q] is removed from the other rows: nobody depends on a hub, so its PMIS measure stays below 1 and it
+    becomes an F point, and no other row's interpolatory set grows.  The style of a hub goes round with q:
+      q % 4 == 0   couplings -1, diagonal 1.01 L
+      q % 4 == 1   the same row negated (negative diagonal, positive couplings)
+      q % 4 == 2   couplings drawn from {-1, -0.5} (both strong at theta <= 0.25: exact ties in |weight|), plus 5 weak
+                   couplings +0.25 of the diagonal's sign (terms that go to the diagonal); diagonal 1.01 L + 1.25
+      q % 4 == 3   style 2 negated
+    so a tuple of lengths repeated four times plants every length in every style."""
+    M = mixed_sign_system(*base).tolil()
+    n = M.shape[0]
+    rng = np.random.default_rng(seed)
+    hubs = np.sort(rng.choice(n, size=len(lengths), replace=False))
+    others = np.setdiff1d(np.arange(n), hubs)
+    M[:, hubs] = 0.0
+    M[hubs, :] = 0.0
+    for q, (h, L) in enumerate(zip(hubs, lengths)):
+        style = q % 4
+        cols = rng.choice(others, size=L + (5 if style >= 2 else 0), replace=False)
+        vals = -np.ones(L) if style < 2 else -rng.choice([1.0, 0.5], size=L)
+        if style >= 2:
+            vals = np.concatenate([vals, np.full(5, 0.25)])
+        sign = -1.0 if style % 2 else 1.0
+        M[h, cols] = sign * vals
+        M[h, h] = sign * (1.01 * L + (1.25 if style >= 2 else 0.0))
+    M = M.tocsr()
+    M.eliminate_zeros()
+    M.sort_indices()
+    return M, hubs, np.asarray(lengths)
+
+
+# hubs_ext: under ext+i the bound of a hub is about 1.9 times its length (its own C points plus those of its strong F
+# neighbours, with multiplicity).  Lengths and seed were chosen on the CPU so that the bounds hit 128, 129, 512 and 513
+# and stay below 1024 on every row (asserted in tests/test_interp_tables_spec.py)
+HUB_EXT_LENGTHS = (8, 9, 10, 16, 17, 18, 19, 20) + tuple(range(60, 76)) + tuple(range(256, 288, 2)) + (505, 515, 525, 535)
+
+# name -> (builder arguments of hub_system, or the mixed_sign_system case), strong_threshold, interpolation the
+# operator was made for (6 ext+i, 0 classical modified)
+INTERP_TABLE_OPERATORS = {
+    # dense random operators: hundreds of candidates per row, counted with multiplicity by the bound the kernel bins on
+    "dense1200": ((1200, 9, .3, .25, 60), 0.25, 6),
+    "dense1600": ((1600, 11, .3, .25, 70), 0.1, 6),
+    "hubs": ((HUB_LENGTHS * 4, 7), 0.25, 0),
+    "hubs_ext": ((HUB_EXT_LENGTHS, 39), 0.25, 6),
+    # one row over the largest table: a hub of 1025 couplings (classical), a hub whose ext+i bound is 1040 (seed chosen so
+    # that no row of level 1 exceeds the tables: the coarse levels of the hub operators are dense, and under ext+i most
+    # seeds give a level 1 that falls back as well)
+    "overflow": ((HUB_LENGTHS * 4 + (1025,), 7), 0.25, 0),
+    "overflow_ext": ((HUB_EXT_LENGTHS + (560,), 14), 0.25, 6),
+}
+
+
+def interp_table_operator(name):
+    """(operator, hub rows, hub lengths) of a name in INTERP_TABLE_OPERATORS (no hubs: two empty arrays)"""
+    args = INTERP_TABLE_OPERATORS[name][0]
+    if name.startswith("dense"):
+        return mixed_sign_system(*args), np.zeros(0, dtype=int), np.zeros(0, dtype=int)
+    return hub_system(*args)
