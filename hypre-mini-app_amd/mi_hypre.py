@@ -779,6 +779,11 @@ def assembly_stamp(A):
     return v.value
 
 
+def set_value_dictionary(on):
+    """value dictionary on / off for the operators placed from now on (process-wide; on by default)"""
+    call("HYPRE_MI_SetValueDictionary", 1 if on else 0)
+
+
 def parcsr_value_kind(A):
     """0: the device diag block streams plain fp64 values, 8: through a value dictionary"""
     par = A.par if hasattr(A, "par") else A
