@@ -2935,8 +2935,9 @@ void BoomerAMG::setup_device() {
     printf("   value dictionaries (1-byte value stream):");
     for (size_t li = 0; li < L.size(); li++) {
       const AmgLevel &Lv = L[li];
-      printf(" L%zu[%s%s%s%s%s]", li, Lv.A->d_diag.val8 ? "A" : "", Lv.has_Az && Lv.Az.val8 ? " Az" : "",
-             Lv.has_Ar && Lv.Ar.val8 ? " Ar" : "", Lv.Pm && Lv.Pm->d_diag.val8 ? " P" : "", Lv.Rm && Lv.Rm->d_diag.val8 ? " R" : "");
+      auto dict = [](const DevCSR &D) { return D.value_format() == ValueFormat::DICT; };
+      printf(" L%zu[%s%s%s%s%s]", li, dict(Lv.A->d_diag) ? "A" : "", Lv.has_Az && dict(Lv.Az) ? " Az" : "",
+             Lv.has_Ar && dict(Lv.Ar) ? " Ar" : "", Lv.Pm && dict(Lv.Pm->d_diag) ? " P" : "", Lv.Rm && dict(Lv.Rm->d_diag) ? " R" : "");
     }
     printf("\n");
   }

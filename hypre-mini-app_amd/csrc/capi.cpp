@@ -623,7 +623,7 @@ HYPRE_Int HYPRE_MI_ParCSRGetValueKind(HYPRE_ParCSRMatrix A, HYPRE_Int *kind) {
   API_BEGIN
   if (!A || !kind) fail(HYPRE_ERROR_ARG, "ParCSRGetValueKind: NULL argument");
   if (!PM(A)->on_device) fail(HYPRE_ERROR_GENERIC, "ParCSRGetValueKind: the matrix has no device mirror");
-  *kind = PM(A)->d_diag.val8 ? 8 : PM(A)->d_diag.value_kind;
+  *kind = PM(A)->d_diag.reported_value_kind();
   API_END
 }
 HYPRE_Int HYPRE_MI_ParCSRGetCSRSize(HYPRE_ParCSRMatrix A, HYPRE_Int which, HYPRE_Int *nrows, HYPRE_Int *ncols,
@@ -2026,7 +2026,7 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetLevelValueStorage(HYPRE_Solver solver, HYPRE_Int 
   int kd = 0;
   long long bytes = 0;
   auto of_dev = [&](const DevCSR &D) {
-    kd = D.val8 ? 8 : D.value_kind;
+    kd = D.reported_value_kind();
     bytes = k::value_stream_bytes(D);
   };
   if (which == 6 || which == 8) {
@@ -2277,6 +2277,31 @@ HYPRE_Int HYPRE_MI_ProfileKernelName(HYPRE_Int id, char *name, HYPRE_Int max_len
   if (!name || max_len < 1) fail(HYPRE_ERROR_ARG, "ProfileKernelName: no buffer");
   const char *n = (ctx().timer && id >= 0 && id < k::PROF_COUNT && ctx().timer->kernel_name[id]) ? ctx().timer->kernel_name[id] : "";
   snprintf(name, (size_t)max_len, "%s", n);
+  API_END
+}
+HYPRE_Int HYPRE_MI_SolveKernelChoice(HYPRE_Int family, HYPRE_Int xcache, HYPRE_Int tile_entries, HYPRE_Int has_fp32,
+                                     HYPRE_Int has_dictionary, HYPRE_Int epilogue, HYPRE_Int level0, HYPRE_Int chunk,
+                                     HYPRE_Int tiles, HYPRE_BigInt nnz, HYPRE_Int nrows, HYPRE_Int rowlen_p95, char *name,
+                                     HYPRE_Int max_len) {
+  API_BEGIN
+  if (!name || max_len < 1) fail(HYPRE_ERROR_ARG, "SolveKernelChoice: no buffer");
+  if (family != 0 && family != 1) fail(HYPRE_ERROR_ARG, "SolveKernelChoice: family must be 0 (SpMV / Jacobi) or 1 (hybrid GS)");
+  if (tile_entries != k::SPMV_TILE && tile_entries != k::SPMV_TILE_WIDE) fail(HYPRE_ERROR_ARG, "SolveKernelChoice: tile_entries must be 2048 or 4096");
+  if (epilogue != 0 && epilogue != 1) fail(HYPRE_ERROR_ARG, "SolveKernelChoice: epilogue must be 0 or 1");
+  if (chunk < 1 || chunk > k::GS_MAX_CHUNK) fail(HYPRE_ERROR_ARG, "SolveKernelChoice: chunk out of range");
+  if (nnz < 0 || nrows < 1 || rowlen_p95 < 0) fail(HYPRE_ERROR_ARG, "SolveKernelChoice: an operator has nnz >= 0, nrows >= 1, rowlen_p95 >= 0");
+  k::SolveKernelDesc d;
+  d.xcache = xcache != 0;
+  d.tile_entries = tile_entries;
+  d.format = value_format_of(has_fp32 != 0, has_dictionary != 0);
+  d.epi = epilogue;
+  d.level0 = level0 != 0;
+  d.chunk = chunk;
+  d.tiles = tiles != 0;
+  d.nnz = nnz;
+  d.nrows = nrows;
+  d.rowlen_p95 = rowlen_p95;
+  snprintf(name, (size_t)max_len, "%s", (family == 0 ? k::choose_stream_kernel(d) : k::choose_gs_kernel(d)).name);
   API_END
 }
 HYPRE_Int HYPRE_MI_ProfileReset(void) {

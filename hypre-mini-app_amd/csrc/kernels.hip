@@ -10,6 +10,7 @@
 #include "kernels.hpp"
 
 #include <cstring>
+#include <limits>
 #include "profile.hpp"
 
 namespace mi {
@@ -1676,109 +1677,100 @@ static bool gs_tile_mode(const DevCSR &A) {
   return (double)A.nnz / (double)std::max(1, A.nrows) > thr;
 }
 
-// returns the name of the instantiation it launched (as rocprofv3's kernel statistics spell it)
+// ---- the instantiations of the solve kernels, and which of them runs.  An entry's pointer and its name (as rocprofv3's
+// kernel statistics spell it) come from the same template arguments.  A table's type is its family's signature, so an
+// instantiation of another family does not compile INTO A TABLE; a KernelChoice carries the pointer untyped, and the
+// launchers cast it back by its family tag -- that pairing is theirs to get right.
+// The compiler emits the kernels in the order the tables name them.  The tables, and ValueFormat's values that index
+// them, keep the order in which the kernels have always been emitted -- fp32, dictionary, fp64; wide tiles first; TAG 1
+// first; float before double -- so that the code object is laid out as it was when the kernels were tuned.
+template <class Fn>
+struct KernelEntry {
+  Fn kernel;
+  const char *name;
+};
+#define MI_KERNEL(...) {&__VA_ARGS__, #__VA_ARGS__}
+using XcKernel = decltype(&spmv_stream_xc<0, 0, false, SPMV_BLOCK>);
+using GsTileKernel = decltype(&gs_tile_k<false, SPMV_BLOCK>);
+template <class VT>
+using StreamKernel = decltype(&spmv_stream<0, 0, VT>);
+template <class VT>
+using GsChunkKernel = decltype(&gs_group_k<8, 1, VT>);  // gs_dense_k has the same signature
+template <class VT>
+using GsHybridKernel = decltype(&gs_hybrid_k<VT>);
+static_assert(SPMV_BLOCK == 256 && SPMV_BLOCK_WIDE == 512, "the tables below spell the block sizes out");
+
+static int tile_block(int tile_entries) { return tile_entries == SPMV_TILE_WIDE ? SPMV_BLOCK_WIDE : SPMV_BLOCK; }
+
+template <class Fn>
+static KernelChoice chosen(const KernelEntry<Fn> &e, KernelFamily family, int block, int lpc = 0) {
+  return KernelChoice{(const void *)e.kernel, e.name, family, block, lpc};
+}
+
+// EPI: 0 mat-vec, 1 masked Jacobi.  TAG 1 names the mat-vec of the level-0 class; the wide tiles have no such instantiation.
+KernelChoice choose_stream_kernel(const SolveKernelDesc &d) {
+  // [ValueFormat][EPI]
+  static const KernelEntry<XcKernel> xc_wide[3][2] = {
+      {MI_KERNEL(spmv_stream_xc<0, 0, false, 512, true>), MI_KERNEL(spmv_stream_xc<1, 0, false, 512, true>)},
+      {MI_KERNEL(spmv_stream_xc<0, 0, true, 512>), MI_KERNEL(spmv_stream_xc<1, 0, true, 512>)},
+      {MI_KERNEL(spmv_stream_xc<0, 0, false, 512>), MI_KERNEL(spmv_stream_xc<1, 0, false, 512>)}};
+  // [ValueFormat][EPI, TAG = 0, 1 / 0, 0 / 1, 0]
+  static const KernelEntry<XcKernel> xc[3][3] = {
+      {MI_KERNEL(spmv_stream_xc<0, 1, false, 256, true>), MI_KERNEL(spmv_stream_xc<0, 0, false, 256, true>),
+       MI_KERNEL(spmv_stream_xc<1, 0, false, 256, true>)},
+      {MI_KERNEL(spmv_stream_xc<0, 1, true, 256>), MI_KERNEL(spmv_stream_xc<0, 0, true, 256>),
+       MI_KERNEL(spmv_stream_xc<1, 0, true, 256>)},
+      {MI_KERNEL(spmv_stream_xc<0, 1, false, 256>), MI_KERNEL(spmv_stream_xc<0, 0, false, 256>),
+       MI_KERNEL(spmv_stream_xc<1, 0, false, 256>)}};
+  // the plain stream has no dictionary form: [EPI, TAG]
+  static const KernelEntry<StreamKernel<float>> plain32[3] = {
+      MI_KERNEL(spmv_stream<0, 1, float>), MI_KERNEL(spmv_stream<0, 0, float>), MI_KERNEL(spmv_stream<1, 0, float>)};
+  static const KernelEntry<StreamKernel<double>> plain[3] = {MI_KERNEL(spmv_stream<0, 1>), MI_KERNEL(spmv_stream<0, 0>),
+                                                             MI_KERNEL(spmv_stream<1, 0>)};
+  const int fmt = (int)d.format;
+  const int epi_tag = d.epi == 1 ? 2 : d.level0 ? 0 : 1;
+  if (d.xcache)
+    return chosen(d.tile_entries == SPMV_TILE_WIDE ? xc_wide[fmt][d.epi] : xc[fmt][epi_tag], KernelFamily::STREAM_XC,
+                  tile_block(d.tile_entries));
+  if (d.format == ValueFormat::FP32) return chosen(plain32[epi_tag], KernelFamily::STREAM, SPMV_BLOCK);
+  return chosen(plain[epi_tag], KernelFamily::STREAM, SPMV_BLOCK);
+}
+
+// the value stream as the tile kernels (spmv_stream_xc, gs_tile_k) take it: their VAL4 instantiations read the floats
+// through the `av` of the other instantiations.  (vidx / vlut go to every instantiation; only the VAL8 ones look at them.)
+static const double *tile_values(const DevCSR &A) {
+  return A.value_format() == ValueFormat::FP32 ? reinterpret_cast<const double *>(A.a32.p) : A.a.p;
+}
+// launch(kernel, values) with the float or the double signature of a family whose kernels take the values as VT
+template <template <class> class Fn, class Launch>
+static void launch_on_values(const DevCSR &A, const KernelChoice &c, Launch launch) {
+  if (A.value_format() == ValueFormat::FP32)
+    launch((Fn<float>)c.kernel, A.a32.p);
+  else
+    launch((Fn<double>)c.kernel, A.a.p);
+}
+
+// returns the name of the instantiation it launched
 static const char *launch_stream(int epi, const DevCSR &A, const double *x, double *y, const EpiArgs &e, hipStream_t s,
                                  bool level0 = false) {
   if (A.nrows == 0) return "";
   MI_REQUIRE(A.xcache || !A.big(), "an operator with 2^31 entries or more must be in the x-cache tile format");
-  const char *name = "";
-  const bool f32 = A.a32.p != nullptr;  // fp32 value storage (k::narrow_values): `a` is gone, the kernels stream a32
-  MI_REQUIRE(f32 || A.a.p || A.nnz == 0, "SpMV: the operator holds no value array");
+  // (fp32 value storage, k::narrow_values: `a` is gone, the kernels stream a32)
+  MI_REQUIRE(A.value_format() == ValueFormat::FP32 || A.a.p || A.nnz == 0, "SpMV: the operator holds no value array");
+  const KernelChoice c = choose_stream_kernel({A.xcache, A.tile_entries, A.value_format(), epi, level0});
   const int nb = A.nblocks;
   const int xchunk = (nb + 7) / 8;
-  const dim3 grid(xchunk * 8), block(SPMV_BLOCK);
-  if (A.xcache && A.tile_entries == SPMV_TILE_WIDE) {
-    const dim3 wide(SPMV_BLOCK_WIDE);
-#define XC_LAUNCH_W(EPI_, V8_)                                                                                       \
-  name = "spmv_stream_xc<" #EPI_ ", 0, " #V8_ ", 512>";                                                              \
-  hipLaunchKernelGGL((spmv_stream_xc<EPI_, 0, V8_, SPMV_BLOCK_WIDE>), grid, wide, 0, s, nb, xchunk, A.tdesc.p, A.ia.p, \
-                     A.ja.p, A.a.p, A.ucols.p, A.lcol.p, x, y, e, A.vidx.p, A.vlut.p)
-#define XC_LAUNCH_W4(EPI_)                                                                                           \
-  name = "spmv_stream_xc<" #EPI_ ", 0, false, 512, true>";                                                           \
-  hipLaunchKernelGGL((spmv_stream_xc<EPI_, 0, false, SPMV_BLOCK_WIDE, true>), grid, wide, 0, s, nb, xchunk, A.tdesc.p, \
-                     A.ia.p, A.ja.p, reinterpret_cast<const double *>(A.a32.p), A.ucols.p, A.lcol.p, x, y, e, nullptr, \
-                     nullptr)
-    if (f32) {
-      if (epi == 0) {
-        XC_LAUNCH_W4(0);
-      } else {
-        XC_LAUNCH_W4(1);
-      }
-    } else if (A.val8) {
-      if (epi == 0) {
-        XC_LAUNCH_W(0, true);
-      } else {
-        XC_LAUNCH_W(1, true);
-      }
-    } else {
-      if (epi == 0) {
-        XC_LAUNCH_W(0, false);
-      } else {
-        XC_LAUNCH_W(1, false);
-      }
-    }
-#undef XC_LAUNCH_W
-#undef XC_LAUNCH_W4
-  } else if (A.xcache) {
-#define XC_LAUNCH(EPI_, TAG_, V8_)                                                                                  \
-  name = "spmv_stream_xc<" #EPI_ ", " #TAG_ ", " #V8_ ", 256>";                                                       \
-  hipLaunchKernelGGL((spmv_stream_xc<EPI_, TAG_, V8_, SPMV_BLOCK>), grid, block, 0, s, nb, xchunk, A.tdesc.p, A.ia.p, A.ja.p, \
-                     A.a.p, A.ucols.p, A.lcol.p, x, y, e, A.vidx.p, A.vlut.p)
-#define XC_LAUNCH4(EPI_, TAG_)                                                                                      \
-  name = "spmv_stream_xc<" #EPI_ ", " #TAG_ ", false, 256, true>";                                                    \
-  hipLaunchKernelGGL((spmv_stream_xc<EPI_, TAG_, false, SPMV_BLOCK, true>), grid, block, 0, s, nb, xchunk, A.tdesc.p, \
-                     A.ia.p, A.ja.p, reinterpret_cast<const double *>(A.a32.p), A.ucols.p, A.lcol.p, x, y, e, nullptr, \
-                     nullptr)
-    if (f32) {
-      if (epi == 0 && level0) {
-        XC_LAUNCH4(0, 1);
-      } else if (epi == 0) {
-        XC_LAUNCH4(0, 0);
-      } else {
-        XC_LAUNCH4(1, 0);
-      }
-    } else if (A.val8) {
-      if (epi == 0 && level0) {
-        XC_LAUNCH(0, 1, true);
-      } else if (epi == 0) {
-        XC_LAUNCH(0, 0, true);
-      } else {
-        XC_LAUNCH(1, 0, true);
-      }
-    } else {
-      if (epi == 0 && level0) {
-        XC_LAUNCH(0, 1, false);
-      } else if (epi == 0) {
-        XC_LAUNCH(0, 0, false);
-      } else {
-        XC_LAUNCH(1, 0, false);
-      }
-    }
-#undef XC_LAUNCH
-#undef XC_LAUNCH4
-  } else if (f32) {
-    if (epi == 0 && level0) {
-      name = "spmv_stream<0, 1, float>";
-      hipLaunchKernelGGL((spmv_stream<0, 1, float>), grid, block, 0, s, nb, xchunk, A.rb.p, A.ia.p, A.ja.p, A.a32.p, x, y, e);
-    } else if (epi == 0) {
-      name = "spmv_stream<0, 0, float>";
-      hipLaunchKernelGGL((spmv_stream<0, 0, float>), grid, block, 0, s, nb, xchunk, A.rb.p, A.ia.p, A.ja.p, A.a32.p, x, y, e);
-    } else {
-      name = "spmv_stream<1, 0, float>";
-      hipLaunchKernelGGL((spmv_stream<1, 0, float>), grid, block, 0, s, nb, xchunk, A.rb.p, A.ia.p, A.ja.p, A.a32.p, x, y, e);
-    }
-  } else if (epi == 0 && level0) {
-    name = "spmv_stream<0, 1>";
-    hipLaunchKernelGGL((spmv_stream<0, 1>), grid, block, 0, s, nb, xchunk, A.rb.p, A.ia.p, A.ja.p, A.a.p, x, y, e);
-  } else if (epi == 0) {
-    name = "spmv_stream<0, 0>";
-    hipLaunchKernelGGL((spmv_stream<0, 0>), grid, block, 0, s, nb, xchunk, A.rb.p, A.ia.p, A.ja.p, A.a.p, x, y, e);
+  const dim3 grid(xchunk * 8), block(c.block);
+  if (c.family == KernelFamily::STREAM_XC) {
+    hipLaunchKernelGGL((XcKernel)c.kernel, grid, block, 0, s, nb, xchunk, A.tdesc.p, A.ia.p, A.ja.p, tile_values(A),
+                       A.ucols.p, A.lcol.p, x, y, e, A.vidx.p, A.vlut.p);
   } else {
-    name = "spmv_stream<1, 0>";
-    hipLaunchKernelGGL((spmv_stream<1, 0>), grid, block, 0, s, nb, xchunk, A.rb.p, A.ia.p, A.ja.p, A.a.p, x, y, e);
+    launch_on_values<StreamKernel>(A, c, [&](auto kernel, auto *values) {
+      hipLaunchKernelGGL(kernel, grid, block, 0, s, nb, xchunk, A.rb.p, A.ia.p, A.ja.p, values, x, y, e);
+    });
   }
   MI_HIP(hipGetLastError());
-  return name;
+  return c.name;
 }
 
 namespace {
@@ -1825,7 +1817,6 @@ void set_value_dictionary(bool on) { g_value_dict = on ? 1 : 0; }
 // one pass then encodes every entry or finds one that is not in the table (the operator keeps the plain stream).
 // MI_HYPRE_VALUE_DICT=0 switches it off.
 void build_value_dictionary(DevCSR &A, hipStream_t s) {
-  A.val8 = false;
   A.vidx.release();
   A.vlut.release();
   if (!value_dictionary_enabled() || !A.xcache || A.nnz < (1 << 16) || !A.a.p) return;
@@ -1864,8 +1855,7 @@ void build_value_dictionary(DevCSR &A, hipStream_t s) {
   }
   std::vector<double> lut(256, 0.0);
   std::memcpy(lut.data(), bits.data(), (size_t)nt * sizeof(double));
-  A.vlut.upload(lut);
-  A.val8 = true;
+  A.vlut.upload(lut);  // (its presence is what makes the operator a dictionary one: DevCSR::value_format)
 }
 
 void build_tile_desc(DevCSR &A, const long long *ia64, hipStream_t s) {
@@ -1920,17 +1910,70 @@ void spmv_offd_set(const DevOffd &B, const double *xext, double *out, hipStream_
   MI_HIP(hipGetLastError());
 }
 
-bool gs_uses_tiles(const DevCSR &A, int chunk) {
-  return chunk == 8 && A.gs_tiles && A.xcache && gs_tile_mode(A);
+// Measured per level (256^3 / 512^3 Laplacian hierarchies, profiles/compare_gs.*):
+//   mean row length <= 8 (the fine level): the shuffle kernel with 8 lanes per chunk is memory-bound
+//   already (3.9 TB/s) and beats the dense-chunk kernel, whose barriers and LDS block it does not need;
+//   longer rows: the dense-chunk kernel wins 10-18 %; for means up to 32 two chunks per wave (32 lanes
+//   each, rows beyond 32 entries finished in the pre-sweep loop) beat one chunk per wave.
+KernelChoice choose_gs_kernel(const SolveKernelDesc &d) {
+  if (d.chunk == 8 && d.tiles && d.xcache) {
+    // [ValueFormat][2048-entry tiles]
+    static const KernelEntry<GsTileKernel> tile[3][2] = {
+        {MI_KERNEL(gs_tile_k<false, 512, true>), MI_KERNEL(gs_tile_k<false, 256, true>)},
+        {MI_KERNEL(gs_tile_k<true, 512>), MI_KERNEL(gs_tile_k<true, 256>)},
+        {MI_KERNEL(gs_tile_k<false, 512>), MI_KERNEL(gs_tile_k<false, 256>)}};
+    return chosen(tile[(int)d.format][d.tile_entries != SPMV_TILE_WIDE], KernelFamily::GS_TILE, tile_block(d.tile_entries));
+  }
+  const bool f32 = d.format == ValueFormat::FP32;
+  if (d.chunk == 8) {
+    // the first rule that holds: mean row length <= avg_max and 95th percentile of the row lengths <= p95_max
+    struct Rule {
+      double avg_max;
+      int p95_max;
+      KernelFamily family;
+      int lpc;
+      KernelEntry<GsChunkKernel<float>> fp32;
+      KernelEntry<GsChunkKernel<double>> fp64;
+    };
+#define MI_CHUNK_KERNEL(KERNEL, FAMILY, LPC, E) \
+  KernelFamily::FAMILY, LPC, MI_KERNEL(KERNEL<LPC, E, float>), MI_KERNEL(KERNEL<LPC, E>)
+    constexpr int any = std::numeric_limits<int>::max();
+    constexpr double longer = std::numeric_limits<double>::infinity();
+    static const Rule rules[] = {{8.0, 8, MI_CHUNK_KERNEL(gs_group_k, GS_GROUP, 8, 1)},
+                                 {8.0, any, MI_CHUNK_KERNEL(gs_group_k, GS_GROUP, 8, 2)},
+                                 {16.0, 16, MI_CHUNK_KERNEL(gs_dense_k, GS_DENSE, 16, 1)},
+                                 {16.0, any, MI_CHUNK_KERNEL(gs_dense_k, GS_DENSE, 16, 2)},
+                                 {32.0, 64, MI_CHUNK_KERNEL(gs_dense_k, GS_DENSE, 32, 1)},
+                                 {32.0, any, MI_CHUNK_KERNEL(gs_dense_k, GS_DENSE, 32, 2)},
+                                 {longer, 64, MI_CHUNK_KERNEL(gs_dense_k, GS_DENSE, 64, 1)},
+                                 {longer, 128, MI_CHUNK_KERNEL(gs_dense_k, GS_DENSE, 64, 2)},
+                                 {longer, any, MI_CHUNK_KERNEL(gs_dense_k, GS_DENSE, 64, 4)}};
+#undef MI_CHUNK_KERNEL
+    const double avg = (double)d.nnz / (double)std::max(1, d.nrows);
+    const Rule *r = rules;
+    while (avg > r->avg_max || d.rowlen_p95 > r->p95_max) r++;  // (the last rule holds for every operator)
+    return f32 ? chosen(r->fp32, r->family, 256, r->lpc) : chosen(r->fp64, r->family, 256, r->lpc);
+  }
+  static const KernelEntry<GsHybridKernel<float>> hybrid32 = MI_KERNEL(gs_hybrid_k<float>);
+  // (the fp64 instantiation has gone by the template's bare name since before there was a float one)
+  static const KernelEntry<GsHybridKernel<double>> hybrid = {&gs_hybrid_k<double>, "gs_hybrid_k"};
+  return f32 ? chosen(hybrid32, KernelFamily::GS_HYBRID, GS_BLOCK) : chosen(hybrid, KernelFamily::GS_HYBRID, GS_BLOCK);
 }
+#undef MI_KERNEL
+
+static KernelChoice gs_choice(const DevCSR &A, int chunk) {
+  return choose_gs_kernel({A.xcache, A.tile_entries, A.value_format(), 0, false, chunk, A.gs_tiles && gs_tile_mode(A), A.nnz,
+                           A.nrows, A.rowlen_p95});
+}
+
+bool gs_uses_tiles(const DevCSR &A, int chunk) { return gs_choice(A, chunk).family == KernelFamily::GS_TILE; }
 
 // whether a sweep of A with zero_from == 0 never reads the pre-sweep vector (gs_tile_k and gs_group_k skip every
 // gather and take 0 for the rows' own values; gs_dense_k and gs_hybrid_k, for chunk != 8, read real zeros)
 bool gs_ignores_zero_vector(const DevCSR &A, int chunk) {
   if (A.nrows == 0) return false;
-  if (gs_uses_tiles(A, chunk)) return true;
-  if (chunk != 8) return false;
-  return (double)A.nnz / (double)A.nrows <= 8.0;  // gs_group_k (see the dispatch in gs_hybrid)
+  const KernelFamily family = gs_choice(A, chunk).family;
+  return family == KernelFamily::GS_TILE || family == KernelFamily::GS_GROUP;
 }
 
 // the tile kernel's launch for the rows [row_begin, row_end): the chunks [c0, c1) that intersect them are rows
@@ -1954,10 +1997,11 @@ static void gs_tile_range(const DevCSR &A, int row_begin, int row_end, int &firs
 bool gs_tile_path_census(const DevCSR &A, int chunk, const int64_t *ia, const int *ja, const int *cf, int points,
                          int row_begin, int row_end, int zero_from, long long counts[5]) {
   for (int q = 0; q < 5; q++) counts[q] = 0;
-  if (A.nrows == 0 || row_end <= row_begin || !gs_uses_tiles(A, chunk)) return false;
+  const KernelChoice c = gs_choice(A, chunk);
+  if (A.nrows == 0 || row_end <= row_begin || c.family != KernelFamily::GS_TILE) return false;
   int first_row, last_row, b0, b1;
   gs_tile_range(A, row_begin, row_end, first_row, last_row, b0, b1);
-  const int block = A.tile_entries == SPMV_TILE_WIDE ? SPMV_BLOCK_WIDE : SPMV_BLOCK;
+  const int block = c.block;
   for (int b = b0; b < b1; b++) {
     const int r0 = A.rb_host[(size_t)b], nr = A.rb_host[(size_t)b + 1] - r0;
     const int LPR = nr <= block / 8 ? 8 : nr <= block / 4 ? 4 : nr <= block / 2 ? 2 : 1;
@@ -1988,87 +2032,36 @@ void gs_hybrid(const DevCSR &A, const double *u_lo, const double *u_hi, int spli
   const long long c0 = row_begin / chunk;
   const long long c1 = ((long long)row_end + chunk - 1) / chunk;
   const long long nch = c1 - c0;
-  const bool f32 = A.a32.p != nullptr;  // fp32 value storage
+  const KernelChoice c = gs_choice(A, chunk);
+  const dim3 block(c.block);
   prof_begin(prof, s);
-  if (gs_uses_tiles(A, chunk)) {
+  if (c.family == KernelFamily::GS_TILE) {
     int first_row, last_row, b0, b1;
     gs_tile_range(A, row_begin, row_end, first_row, last_row, b0, b1);
-#define GS_TILE_LAUNCH(V8_, BLOCK_)                                                                                  \
-  prof_name(prof, V8_ ? (BLOCK_ == 512 ? "gs_tile_k<true, 512>" : "gs_tile_k<true, 256>")                             \
-                      : (BLOCK_ == 512 ? "gs_tile_k<false, 512>" : "gs_tile_k<false, 256>"));                         \
-  hipLaunchKernelGGL((gs_tile_k<V8_, BLOCK_>), dim3((unsigned)(b1 - b0)), dim3(BLOCK_), 0, s, b0, b1 - b0, A.tdesc.p, \
-                     A.ia.p, A.a.p, A.ucols.p, A.lcol.p, cf, points, d, f, offc, u_lo, u_hi, split, out, fwd ? 1 : 0,  \
-                     bwd ? 1 : 0, w, first_row, last_row, zero_from, tout, t_from, V8_ ? A.vidx.p : nullptr,          \
-                     V8_ ? A.vlut.p : nullptr)
-#define GS_TILE_LAUNCH4(BLOCK_)                                                                                      \
-  prof_name(prof, BLOCK_ == 512 ? "gs_tile_k<false, 512, true>" : "gs_tile_k<false, 256, true>");                     \
-  hipLaunchKernelGGL((gs_tile_k<false, BLOCK_, true>), dim3((unsigned)(b1 - b0)), dim3(BLOCK_), 0, s, b0, b1 - b0,    \
-                     A.tdesc.p, A.ia.p, reinterpret_cast<const double *>(A.a32.p), A.ucols.p, A.lcol.p, cf, points, d, \
-                     f, offc, u_lo, u_hi, split, out, fwd ? 1 : 0, bwd ? 1 : 0, w, first_row, last_row, zero_from,    \
-                     tout, t_from, nullptr, nullptr)
-    const bool wide = A.tile_entries == SPMV_TILE_WIDE;
-    if (b1 > b0 && f32 && wide) {
-      GS_TILE_LAUNCH4(SPMV_BLOCK_WIDE);
-    } else if (b1 > b0 && f32) {
-      GS_TILE_LAUNCH4(SPMV_BLOCK);
-    } else if (b1 > b0 && A.val8 && wide) {
-      GS_TILE_LAUNCH(true, SPMV_BLOCK_WIDE);
-    } else if (b1 > b0 && A.val8) {
-      GS_TILE_LAUNCH(true, SPMV_BLOCK);
-    } else if (b1 > b0 && wide) {
-      GS_TILE_LAUNCH(false, SPMV_BLOCK_WIDE);
-    } else if (b1 > b0) {
-      GS_TILE_LAUNCH(false, SPMV_BLOCK);
+    if (b1 > b0) {
+      prof_name(prof, c.name);
+      hipLaunchKernelGGL((GsTileKernel)c.kernel, dim3((unsigned)(b1 - b0)), block, 0, s, b0, b1 - b0, A.tdesc.p, A.ia.p,
+                         tile_values(A), A.ucols.p, A.lcol.p, cf, points, d, f, offc, u_lo, u_hi, split, out, fwd ? 1 : 0,
+                         bwd ? 1 : 0, w, first_row, last_row, zero_from, tout, t_from, A.vidx.p, A.vlut.p);
     }
-#undef GS_TILE_LAUNCH
-#undef GS_TILE_LAUNCH4
-  } else if (chunk == 8) {
-    MI_REQUIRE(!A.big(), "an operator with 2^31 entries or more is swept by the tile Gauss-Seidel kernel only");
-    prof_name(prof, "gs_group_k / gs_dense_k (chunk kernels)");
-    const double avg = (double)A.nnz / (double)A.nrows;
-    const int p95 = A.rowlen_p95;
-#define GS_LAUNCH_K(KERNEL, LPC, E)                                                                             \
-  {                                                                                                             \
-    const long long waves = (nch + (64 / LPC) - 1) / (64 / LPC);                                                \
-    if (f32) prof_name(prof, #KERNEL "<" #LPC ", " #E ", float>");                                              \
-    if (f32)                                                                                                    \
-      hipLaunchKernelGGL((KERNEL<LPC, E, float>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, A.nrows,  \
-                         (int)c0, (int)c1, A.ia.p, A.ja.p, A.a32.p, cf, points, d, f, offc, u_lo, u_hi, split,  \
-                         out, fwd ? 1 : 0, bwd ? 1 : 0, w, zero_from);                                          \
-    else                                                                                                        \
-      hipLaunchKernelGGL((KERNEL<LPC, E>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, A.nrows, (int)c0, \
-                         (int)c1, A.ia.p, A.ja.p, A.a.p, cf, points, d, f, offc, u_lo, u_hi, split, out,        \
-                         fwd ? 1 : 0, bwd ? 1 : 0, w, zero_from);                                               \
-  }
-    // Measured per level (256^3 / 512^3 Laplacian hierarchies, profiles/compare_gs.*):
-    //   mean row length <= 8 (the fine level): the shuffle kernel with 8 lanes per chunk is memory-bound
-    //   already (3.9 TB/s) and beats the dense-chunk kernel, whose barriers and LDS block it does not need;
-    //   longer rows: the dense-chunk kernel wins 10-18 %; for means up to 32 two chunks per wave (32 lanes
-    //   each, rows beyond 32 entries finished in the pre-sweep loop) beat one chunk per wave.
-    if (avg <= 8.0) {
-      if (p95 <= 8) GS_LAUNCH_K(gs_group_k, 8, 1) else GS_LAUNCH_K(gs_group_k, 8, 2)
-    } else if (avg <= 16.0) {
-      if (p95 <= 16) GS_LAUNCH_K(gs_dense_k, 16, 1) else GS_LAUNCH_K(gs_dense_k, 16, 2)
-    } else if (avg <= 32.0) {
-      if (p95 <= 64) GS_LAUNCH_K(gs_dense_k, 32, 1) else GS_LAUNCH_K(gs_dense_k, 32, 2)
-    } else {
-      if (p95 <= 64) GS_LAUNCH_K(gs_dense_k, 64, 1)
-      else if (p95 <= 128) GS_LAUNCH_K(gs_dense_k, 64, 2)
-      else GS_LAUNCH_K(gs_dense_k, 64, 4)
-    }
-#undef GS_LAUNCH_K
   } else {
     MI_REQUIRE(!A.big(), "an operator with 2^31 entries or more is swept by the tile Gauss-Seidel kernel only");
-    const size_t lds = (size_t)chunk * GS_BLOCK * sizeof(double);
-    prof_name(prof, f32 ? "gs_hybrid_k<float>" : "gs_hybrid_k");
-    if (f32)
-      hipLaunchKernelGGL(gs_hybrid_k<float>, dim3((unsigned)((nch + GS_BLOCK - 1) / GS_BLOCK)), dim3(GS_BLOCK), lds, s,
-                         A.nrows, (int)c0, (int)c1, chunk, A.ia.p, A.ja.p, A.a32.p, cf, points, d, f, offc, u_lo, u_hi,
-                         split, out, fwd ? 1 : 0, bwd ? 1 : 0, w);
-    else
-      hipLaunchKernelGGL(gs_hybrid_k<double>, dim3((unsigned)((nch + GS_BLOCK - 1) / GS_BLOCK)), dim3(GS_BLOCK), lds, s,
-                         A.nrows, (int)c0, (int)c1, chunk, A.ia.p, A.ja.p, A.a.p, cf, points, d, f, offc, u_lo, u_hi,
-                         split, out, fwd ? 1 : 0, bwd ? 1 : 0, w);
+    prof_name(prof, c.name);
+    if (c.family == KernelFamily::GS_HYBRID) {
+      const size_t lds = (size_t)chunk * GS_BLOCK * sizeof(double);
+      launch_on_values<GsHybridKernel>(A, c, [&](auto kernel, auto *values) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((nch + GS_BLOCK - 1) / GS_BLOCK)), block, lds, s, A.nrows, (int)c0,
+                           (int)c1, chunk, A.ia.p, A.ja.p, values, cf, points, d, f, offc, u_lo, u_hi, split, out,
+                           fwd ? 1 : 0, bwd ? 1 : 0, w);
+      });
+    } else {
+      const long long waves = (nch + (64 / c.lpc) - 1) / (64 / c.lpc);
+      launch_on_values<GsChunkKernel>(A, c, [&](auto kernel, auto *values) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((waves + 3) / 4)), block, 0, s, A.nrows, (int)c0, (int)c1, A.ia.p,
+                           A.ja.p, values, cf, points, d, f, offc, u_lo, u_hi, split, out, fwd ? 1 : 0, bwd ? 1 : 0, w,
+                           zero_from);
+      });
+    }
   }
   MI_HIP(hipGetLastError());
   prof_end(prof, s);
@@ -2364,9 +2357,10 @@ void round_values(double *a, long long n, hipStream_t s) {
 void narrow_values(DevCSR &A, int mode, hipStream_t s) {
   MI_REQUIRE(mode == 1 || mode == 2, "value storage: mode 1 or 2");
   MI_REQUIRE(!A.a32.p, "value storage: the operator is narrowed already");
-  A.value_kind = A.val8 ? 8 : mode;
-  if (A.val8) round_values(A.vlut.p, 256, s);  // the table and the fp64 array kept beside it: the same values
-  if (A.val8 || mode == 2) {
+  A.value_kind = mode;
+  const bool dict = A.value_format() == ValueFormat::DICT;
+  if (dict) round_values(A.vlut.p, 256, s);  // the table and the fp64 array kept beside it: the same values
+  if (dict || mode == 2) {
     round_values(A.a.p, A.nnz, s);
   } else {
     A.a32.alloc((size_t)A.nnz);

@@ -145,6 +145,32 @@ void narrow_values(DevCSR &A, int mode, hipStream_t s);
 const double *fp64_values(const DevCSR &A, DVec<double> &tmp, hipStream_t s);
 // device bytes of the operator's value arrays (values, dictionary indices and table), padding included
 long long value_stream_bytes(const DevCSR &A);
+// ---- which instantiation of the solve kernels runs: decided here and nowhere else.  Pure host code that reads no
+// device memory (HYPRE_MI_SolveKernelChoice hands it plain integers; tests/test_kernel_choice_spec.py holds the table).
+struct SolveKernelDesc {
+  bool xcache = false;
+  int tile_entries = SPMV_TILE;
+  ValueFormat format = ValueFormat::FP64;
+  int epi = 0;          // SpMV family: 0 mat-vec, 1 masked Jacobi
+  bool level0 = false;  // SpMV family: launched under the profiler's level-0 class
+  // hybrid Gauss-Seidel family
+  int chunk = 8;
+  bool tiles = false;  // the tiles are whole 8-row chunks (DevCSR::gs_tiles) and MI_HYPRE_GS_TILE lets the operator use them
+  int64_t nnz = 0;
+  int nrows = 0;
+  int rowlen_p95 = 0;
+};
+enum class KernelFamily { STREAM, STREAM_XC, GS_TILE, GS_GROUP, GS_DENSE, GS_HYBRID };
+struct KernelChoice {
+  const void *kernel;  // instantiations of one family share a signature (apart from the value pointer of the float ones)
+  const char *name;    // the instantiation as rocprofv3's kernel statistics spell it
+  KernelFamily family;
+  int block;  // threads per workgroup
+  int lpc;    // GS_GROUP / GS_DENSE: lanes per chunk
+};
+KernelChoice choose_stream_kernel(const SolveKernelDesc &d);
+KernelChoice choose_gs_kernel(const SolveKernelDesc &d);
+
 // y = alpha*A*x + beta*b   (b may alias y)
 // b_lo (optional): rows < b_split take their b entry from b_lo instead of b
 void spmv(const DevCSR &A, const double *x, double alpha, double beta, const double *b, double *y, hipStream_t s,

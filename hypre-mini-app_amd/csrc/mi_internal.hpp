@@ -192,6 +192,14 @@ struct HostCSR {
 };
 
 // ---------------------------------------------------------------- device CSR
+// What the solve kernels stream for the values of an operator (DevCSR): doubles (`a`), floats (`a32`) or one byte per
+// entry that indexes a table of doubles (`vidx` / `vlut`, kept beside `a`).  An operator that holds floats runs the
+// float instantiations whatever else it holds.
+enum class ValueFormat { FP32 = 0, DICT = 1, FP64 = 2 };  // (the row order of the kernel tables in kernels.hip)
+inline ValueFormat value_format_of(bool has_fp32, bool has_dictionary) {
+  return has_fp32 ? ValueFormat::FP32 : has_dictionary ? ValueFormat::DICT : ValueFormat::FP64;
+}
+
 // Row pointers: `ia` holds the LOW 32 bits of every entry offset (4 bytes per row in the solve kernels' streams).
 // The tile kernels (spmv_stream_xc, gs_tile_k) take a tile's full 64-bit base from its descriptor and form
 // tile-local offsets as (unsigned)ia[row] - (unsigned)base, which is exact because a tile holds < 2^16 entries -- so
@@ -210,7 +218,9 @@ struct DevCSR {
   // fp32 value storage (k::narrow_values, HYPRE_MI_BoomerAMGSetValueStorage mode 1): the values as floats; `a` is then
   // released and every solve kernel runs its float instantiation, widening each value where the product is formed
   DVec<float> a32;
-  int value_kind = 0;  // 0 fp64, 1 fp32 (a32), 2 fp64 holding fp32-rounded values, 8 value dictionary (rounded or not)
+  // the mode k::narrow_values ran with (0: it did not): 1 fp32 values in a32, 2 fp64 holding fp32-rounded values -- as
+  // does an operator with a value dictionary in either mode
+  int value_kind = 0;
   // row-block schedule of the LDS-staged SpMV (kernels.hip: spmv_stream)
   DVec<int> rb;
   int nblocks = 0;
@@ -234,8 +244,10 @@ struct DevCSR {
   // x-cache SpMV and the tile Gauss-Seidel kernel then stream 3 instead of 10 bytes per entry and look the value up
   // in a 2 KB LDS table -- the same doubles, so results do not change by a bit
   DVec<unsigned char> vidx;
-  DVec<double> vlut;  // 256 entries (unused ones zero)
-  bool val8 = false;
+  DVec<double> vlut;  // 256 entries (unused ones zero); present only with a complete vidx
+  ValueFormat value_format() const { return value_format_of(a32.p != nullptr, vlut.p != nullptr); }
+  // as the library reports it: 0 fp64, 1 fp32, 2 fp64 holding fp32-rounded values, 8 value dictionary (rounded or not)
+  int reported_value_kind() const { return value_format() == ValueFormat::DICT ? 8 : value_kind; }
   // Rows stored in another order than the vectors they produce (SpMV only): stored row r is entry rowmap[r] of y
   // (and of b).  The restriction operators use it: their rows are kept in the order of the FINE level's C points --
   // consecutive rows then gather neighbouring fine entries -- while the coarse level's vectors are in its own

@@ -846,6 +846,16 @@ def profile_kernel_name(pid):
     return buf.value.decode()
 
 
+def solve_kernel_choice(family, xcache=False, tile_entries=2048, fp32=False, dictionary=False, epilogue=0, level0=False,
+                        chunk=8, tiles=False, nnz=0, nrows=1, rowlen_p95=0):
+    """instantiation the library launches for an operator with these properties (no device needed).  family 0: SpMV /
+    Jacobi (epilogue 1), family 1: hybrid Gauss-Seidel."""
+    buf = C.create_string_buffer(128)
+    call("HYPRE_MI_SolveKernelChoice", family, int(xcache), tile_entries, int(fp32), int(dictionary), epilogue, int(level0),
+         chunk, int(tiles), c_big(nnz), nrows, rowlen_p95, buf, 128)
+    return buf.value.decode()
+
+
 def profile_get(pid):
     n, tot, mn = C.c_longlong(), c_dbl(), c_dbl()
     call("HYPRE_MI_ProfileGet", pid, C.byref(n), C.byref(tot), C.byref(mn))

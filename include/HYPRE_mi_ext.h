@@ -260,6 +260,16 @@ HYPRE_Int HYPRE_MI_ProfileReset(void);
  * under the class; empty when none was */
 HYPRE_Int HYPRE_MI_ProfileKernelName(HYPRE_Int id, char *name, HYPRE_Int max_len);
 HYPRE_Int HYPRE_MI_ProfileGet(HYPRE_Int id, long long *launches, double *total_ms, double *min_ms);
+/* test hook, needs no device: the instantiation the library launches for an operator described by plain integers.
+ * family 0: SpMV (epilogue 0; level0: under class 0) / masked Jacobi (epilogue 1); family 1: hybrid Gauss-Seidel with
+ * `chunk` rows per chunk, where tiles != 0 says that the operator's tiles are whole 8-row chunks and the tile mode
+ * (MI_HYPRE_GS_TILE) lets it use them.  xcache: the operator has the LDS x cache (mean row length >= 3); tile_entries
+ * 2048 or 4096; has_fp32 / has_dictionary: the value arrays it holds (fp32 wins); nnz, nrows, rowlen_p95 (the entry
+ * floor(0.95 (nrows - 1)) of the sorted row lengths): of its diagonal block */
+HYPRE_Int HYPRE_MI_SolveKernelChoice(HYPRE_Int family, HYPRE_Int xcache, HYPRE_Int tile_entries, HYPRE_Int has_fp32,
+                                     HYPRE_Int has_dictionary, HYPRE_Int epilogue, HYPRE_Int level0, HYPRE_Int chunk,
+                                     HYPRE_Int tiles, HYPRE_BigInt nnz, HYPRE_Int nrows, HYPRE_Int rowlen_p95, char *name,
+                                     HYPRE_Int max_len);
 
 /* ---- synthetic problem: n^3-type Laplacian, true lexicographic global numbering
  * (7-point: diag 6 / off -1; 27-point: diag 26 / off -1 as
