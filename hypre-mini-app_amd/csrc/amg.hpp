@@ -45,6 +45,10 @@ struct AmgParams {
   // smooth_type 4 = FSAI with the static pattern (algo type 3, the only one built), one step per sweep
   int fsai_algo_type = 3, fsai_num_levels = 1, fsai_eig_max_iters = 5;
   double fsai_threshold = 0.01;
+  // relax type 16 = Chebyshev: steps per sweep (1 ... 4), where the smoothed interval starts between
+  // the eigenvalue bounds of D^-1 A, CG-Lanczos steps of the estimate (0 = Gershgorin); only variant 0 with scale 1 is built
+  int cheby_order = 2, cheby_eig_est = 10, cheby_variant = 0, cheby_scale = 1;
+  double cheby_fraction = 0.3;
   // non-Galerkin coarse operators (src/HypreSystem.cpp:161-176): drop tolerance for the coarse operator built FROM
   // level l (HYPRE's index): level_tol[l] when set (>= 0), else the global one; 0 = Galerkin
   double non_galerkin_tol = 0.0;
@@ -135,6 +139,17 @@ struct AmgLevel {
   int value_kind[3] = {0, 0, 0};
   DVec<double> d_diag, d_l1gs, d_l1jac;
   DVec<double> u, f, tmp, snap;
+  // relax type 16 (Chebyshev), on every level when some relax_type slot is 16 at Setup (BoomerAMG::build_cheby):
+  // eigenvalue bounds of D^-1 A, the interval [lower, upper] the polynomial is built for, its centre and half width,
+  // and the coefficients (a_k, b_k) of the steps of one sweep
+  struct Cheby {
+    bool ready = false;
+    int eig_est = -1;  // the setting eig_min / eig_max were estimated with
+    double eig_min = 0.0, eig_max = 0.0, lower = 0.0, upper = 0.0, theta = 0.0, delta = 0.0;
+    int order = 0;
+    double a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
+  } cheby;
+  DVec<double> cheby_d;  // the direction vector d of the sweep (step 0 writes it before any step reads it)
   DVec<double> ts_work;  // second work vector of the two-stage Gauss-Seidel (relax types 11 / 12), on first use
   // coarsest level dense solve (relax type 9)
   std::vector<double> Cinv_host;
@@ -149,6 +164,7 @@ struct BoomerAMG {
   AmgParams p;
   std::vector<AmgLevel> L;
   bool is_setup = false, host_ready = false;
+  bool host_only = false;  // set up by HYPRE_MI_BoomerAMGSetupHostOnly: nothing that needs the device exists
   // levels with at least this many rows run their sparse products / transposes / renumbering on the
   // device; -1 = everything on host threads (HYPRE_MI_BoomerAMGSetupHostOnly)
   long long device_min_rows = -1;
@@ -224,6 +240,7 @@ struct BoomerAMG {
   static long long default_device_min_rows();
 
   void setup(ParCSR &A) {
+    host_only = false;
     device_min_rows = default_device_min_rows();
     setup_host(A);
     setup_device();
@@ -262,6 +279,14 @@ struct BoomerAMG {
   void build_smoothers();
   std::vector<double> fsai_signature;
   std::vector<double> current_fsai_signature() const;
+  // Chebyshev data of every level (relax type 16 in some slot; end of build_smoothers): the eigenvalue estimate is
+  // collective and runs on the device.  cheby_signature: the parameters the data was built with -- a change after Setup
+  // rebuilds it before the next cycle or sweep (the bounds are estimated again only when cheby_eig_est changed)
+  void build_cheby();
+  bool wants_cheby() const { return p.relax_type[0] == 16 || p.relax_type[1] == 16 || p.relax_type[2] == 16; }
+  std::vector<double> cheby_signature;
+  std::vector<double> current_cheby_signature() const;
+  void refresh_cheby();
   // cycle(level, true) never reads Lv.u before it has overwritten every row (one rank, Gauss-Seidel down sweep on
   // the zero-skipping kernels, or the dense coarsest solve): the caller need not zero-fill u first -- at 512^3 the
   // fills of a cycle are 1.6 GB of writes, 0.8 % of the solve, and one launch per level

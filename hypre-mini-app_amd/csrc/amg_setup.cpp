@@ -1790,15 +1790,35 @@ void BoomerAMG::setup_host(ParCSR &A0) {
   for (int k = 0; k < 3; k++) {
     const int t = p.relax_type[k];
     const bool known = t == 0 || t == 7 || t == 18 || t == 3 || t == 4 || t == 6 || t == 8 || t == 13 || t == 14 ||
-                       t == 11 || t == 12 || t == 9;
+                       t == 11 || t == 12 || t == 9 || t == 16;
     if (!known)
       fail(4, "BoomerAMGSetup: relax_type " + std::to_string(t) +
-                  " is not implemented (0, 3, 4, 6, 7, 8, 9, 11, 12, 13, 14, 18 are); refusing to smooth with something else");
+                  " is not implemented (0, 3, 4, 6, 7, 8, 9, 11, 12, 13, 14, 16, 18 are); refusing to smooth with something else");
+    if (t == 16 && host_only)
+      fail(4, "BoomerAMGSetup: relax_type 16 (Chebyshev) is not implemented by the host-only setup, which has no eigenvalue "
+              "estimate (that is device code); refusing to smooth with something else");
     // 9 = direct solve: the coarsest level only (BoomerAMG::relax would otherwise have to smooth the other
     // levels with something else, or fail inside the Krylov loop)
     if (t == 9 && k < 2)
       fail(4, std::string("BoomerAMGSetup: relax_type 9 (Gaussian elimination) is implemented for the coarsest level only, not as the ") +
                   (k == 0 ? "down" : "up") + " smoother; refusing to smooth with something else");
+  }
+  if (wants_cheby()) {
+    if (p.cheby_order < 1 || p.cheby_order > 4)
+      fail(4, "BoomerAMGSetup: Chebyshev order " + std::to_string(p.cheby_order) +
+                  " is not implemented (1, 2, 3 and 4 are); refusing to smooth with another polynomial");
+    if (!(p.cheby_fraction > 0.0 && p.cheby_fraction < 1.0))
+      fail(4, "BoomerAMGSetup: Chebyshev eigenvalue fraction " + std::to_string(p.cheby_fraction) +
+                  " is not implemented (a value strictly between 0 and 1 is); refusing to smooth on another interval");
+    if (p.cheby_eig_est < 0)
+      fail(4, "BoomerAMGSetup: Chebyshev eig_est " + std::to_string(p.cheby_eig_est) +
+                  " is not implemented (0 = Gershgorin and k > 0 CG steps are); refusing to estimate another way");
+    if (p.cheby_variant != 0)
+      fail(4, "BoomerAMGSetup: Chebyshev variant " + std::to_string(p.cheby_variant) +
+                  " is not implemented (0 is); refusing to smooth with another variant");
+    if (p.cheby_scale != 1)
+      fail(4, "BoomerAMGSetup: Chebyshev scale " + std::to_string(p.cheby_scale) +
+                  " is not implemented (1 = the diagonally scaled operator is); refusing to smooth the unscaled one");
   }
   if (p.interp_type != 0 && p.interp_type != 3 && p.interp_type != 4 && p.interp_type != 6)
     fail(4, "BoomerAMGSetup: interp_type " + std::to_string(p.interp_type) +
@@ -2621,6 +2641,7 @@ void BoomerAMG::build_replicated(ParCSR &A0) {
       tail->p.non_galerkin_level_tol = shifted;
     }
     tail->device_min_rows = device_min_rows;
+    tail->host_only = host_only;
     tail->use_private_self_comm();
     tail->setup_host(*tail_A);
     tail_start = starts[nlev - 1][(size_t)rank];
@@ -2680,6 +2701,163 @@ void BoomerAMG::build_smoothers() {
     Lv.smoother = std::move(ilu);
   }
   fsai_signature = current_fsai_signature();
+  for (AmgLevel &Lv : L) Lv.cheby = AmgLevel::Cheby();
+  build_cheby();
+}
+
+namespace {
+// number of eigenvalues below x of the symmetric tridiagonal matrix (d, e): sign changes of the Sturm sequence
+int sturm_count(const std::vector<double> &d, const std::vector<double> &e, double x) {
+  int count = 0;
+  double q = 1.0;
+  for (size_t i = 0; i < d.size(); i++) {
+    const double off2 = i ? e[i - 1] * e[i - 1] : 0.0;
+    if (q == 0.0) q = 1e-300;
+    q = d[i] - x - off2 / q;
+    if (q < 0.0) count++;
+  }
+  return count;
+}
+// smallest and largest eigenvalue of that matrix by bisection inside its Gershgorin interval
+void tridiagonal_extremes(const std::vector<double> &d, const std::vector<double> &e, double &lmin, double &lmax) {
+  const int m = (int)d.size();
+  double gl = d[0], gu = d[0];
+  for (int i = 0; i < m; i++) {
+    const double r = (i ? std::fabs(e[(size_t)i - 1]) : 0.0) + (i + 1 < m ? std::fabs(e[(size_t)i]) : 0.0);
+    gl = std::min(gl, d[(size_t)i] - r);
+    gu = std::max(gu, d[(size_t)i] + r);
+  }
+  auto kth = [&](int k) {  // the k-th smallest (1-based): the supremum of { x : count(x) < k }
+    double lo = gl, hi = gu;
+    for (int it = 0; it < 2000; it++) {
+      const double mid = lo + 0.5 * (hi - lo);
+      if (!(mid > lo && mid < hi)) break;
+      if (sturm_count(d, e, mid) >= k)
+        hi = mid;
+      else
+        lo = mid;
+    }
+    return lo + 0.5 * (hi - lo);
+  };
+  lmin = kth(1);
+  lmax = kth(m);
+}
+}  // namespace
+
+std::vector<double> BoomerAMG::current_cheby_signature() const {
+  if (!wants_cheby()) return {};
+  return {(double)p.cheby_order, p.cheby_fraction, (double)p.cheby_eig_est, (double)p.cheby_variant, (double)p.cheby_scale};
+}
+
+void BoomerAMG::refresh_cheby() {
+  if (cheby_signature != current_cheby_signature()) build_cheby();
+}
+
+// Chebyshev relaxation (relax type 16): per level the eigenvalue bounds of D^-1 A -- Gershgorin, or
+// cheby_eig_est steps of conjugate gradients on D^-1/2 A D^-1/2 from the Park-Miller vector, whose coefficients give
+// the Lanczos tridiagonal matrix -- then the interval, its centre and half width and the coefficients of the steps.
+// Collective: every rank runs the same steps on every level (the stub in front of a redundant tail is never smoothed).
+void BoomerAMG::build_cheby() {
+  cheby_signature = current_cheby_signature();
+  if (!wants_cheby()) return;
+  if (p.cheby_order < 1 || p.cheby_order > 4 || !(p.cheby_fraction > 0.0 && p.cheby_fraction < 1.0) || p.cheby_eig_est < 0 ||
+      p.cheby_variant != 0 || p.cheby_scale != 1) {
+    for (AmgLevel &Lv : L) Lv.cheby.ready = false;
+    fail(4, "BoomerAMG: Chebyshev order " + std::to_string(p.cheby_order) + ", fraction " + std::to_string(p.cheby_fraction) +
+                ", eig_est " + std::to_string(p.cheby_eig_est) + ", variant " + std::to_string(p.cheby_variant) + ", scale " +
+                std::to_string(p.cheby_scale) +
+                " is not implemented (order 1 ... 4, fraction in (0, 1), eig_est >= 0, variant 0, scale 1 are); refusing to smooth "
+                "with other settings");
+  }
+  Comm &comm = my_comm();
+  hipStream_t s = ctx().stream;
+  const size_t nlev = tail ? L.size() - 1 : L.size();
+  for (size_t li = 0; li < nlev; li++) {
+    AmgLevel &Lv = L[li];
+    AmgLevel::Cheby &c = Lv.cheby;
+    ParCSR &A = *Lv.A;
+    const int n = Lv.n;
+    const std::string where = "BoomerAMGSetup: level " + std::to_string(li) + ": Chebyshev relaxation (relax_type 16): ";
+    if (!c.ready || c.eig_est != p.cheby_eig_est) {
+      c.ready = false;
+      DVec<double> w((size_t)n);
+      double gmax = 0.0;
+      long long bad = 0;
+      k::gershgorin(A.d_diag, A.d_offd, Lv.d_diag.p, w.p, &gmax, &bad, s);
+      double red[2] = {gmax, (double)bad};
+      if (std::isnan(gmax)) red[0] = HUGE_VAL;  // (a maximum over the ranks that keeps a NaN visible)
+      if (comm.size > 1) {
+        comm.allreduce_host(&red[0], 1, CommDType::F64, CommOp::MAX);
+        comm.allreduce_host(&red[1], 1, CommDType::F64, CommOp::SUM);
+      }
+      if (red[1] > 0.0)
+        fail(4, where + std::to_string((long long)red[1]) +
+                    " row(s) with a diagonal entry that is not positive: the smoother for such an operator is not "
+                    "implemented (a positive diagonal is); refusing to smooth with something else");
+      double emin = 0.0, emax = red[0];
+      if (p.cheby_eig_est > 0) {
+        DVec<double> dis((size_t)n), r((size_t)n), pv((size_t)n), t((size_t)n);
+        k::inv_sqrt(Lv.d_diag.p, dis.p, n, s);
+        sk::fsai_random_vector(n, (long long)A.row_start, 2747, r.p, s);
+        k::copy(r.p, pv.p, n, s);
+        double rr = par_dot_host(comm, r.p, r.p, n, s);
+        std::vector<double> alpha, beta;
+        for (int j = 0; j < p.cheby_eig_est; j++) {
+          if (!(rr > 0.0)) break;  // the residual is zero
+          k::vec_mul(pv.p, dis.p, t.p, n, s);
+          A.matvec(comm, 1.0, t.p, 0.0, nullptr, w.p, s);
+          k::vec_mul(w.p, dis.p, w.p, n, s);
+          const double pBp = par_dot_host(comm, pv.p, w.p, n, s);
+          if (!(pBp > 0.0)) break;
+          const double al = rr / pBp;
+          k::axpy(-al, w.p, r.p, n, s);
+          const double rr_new = par_dot_host(comm, r.p, r.p, n, s);
+          const double be = rr_new / rr;
+          alpha.push_back(al);
+          beta.push_back(be);
+          rr = rr_new;
+          k::scale(be, pv.p, n, s);
+          k::axpy(1.0, r.p, pv.p, n, s);
+        }
+        MI_HIP(hipStreamSynchronize(s));  // the work vectors are released on leaving this block
+        const size_t m = alpha.size();
+        if (m == 0)
+          fail(1, where + "the conjugate-gradient eigenvalue estimate made no step (zero start vector or p^T B p <= 0: the "
+                          "operator is not positive definite)");
+        std::vector<double> td(m), te(m > 1 ? m - 1 : 0);
+        for (size_t j = 0; j < m; j++) {
+          td[j] = 1.0 / alpha[j] + (j ? beta[j - 1] / alpha[j - 1] : 0.0);
+          if (j + 1 < m) te[j] = std::sqrt(beta[j]) / alpha[j];
+        }
+        tridiagonal_extremes(td, te, emin, emax);
+      }
+      c.eig_min = emin;
+      c.eig_max = emax;
+      c.eig_est = p.cheby_eig_est;
+    }
+    c.upper = p.cheby_eig_est > 0 ? 1.1 * c.eig_max : c.eig_max;
+    c.lower = c.eig_min + p.cheby_fraction * (c.upper - c.eig_min);
+    c.theta = (c.upper + c.lower) / 2.0;
+    c.delta = (c.upper - c.lower) / 2.0;
+    if (!std::isfinite(c.eig_min) || !std::isfinite(c.upper) || !std::isfinite(c.lower) || !(c.upper > 0.0) || !(c.lower < c.upper)) {
+      c.ready = false;
+      fail(1, where + "eigenvalue bounds [" + std::to_string(c.lower) + ", " + std::to_string(c.upper) +
+                  "] of D^-1 A are not a finite interval with a positive upper end");
+    }
+    c.order = p.cheby_order;
+    const double sigma = c.theta / c.delta;
+    double rho = 1.0 / sigma;
+    c.a[0] = 0.0;
+    c.b[0] = 1.0 / c.theta;
+    for (int k = 1; k < c.order; k++) {
+      const double rho_new = 1.0 / (2.0 * sigma - rho);
+      c.a[k] = rho_new * rho;
+      c.b[k] = 2.0 * rho_new / c.delta;
+      rho = rho_new;
+    }
+    if (Lv.cheby_d.n != (size_t)n) Lv.cheby_d.alloc((size_t)n);
+    c.ready = true;
+  }
 }
 
 std::vector<double> BoomerAMG::current_fsai_signature() const {

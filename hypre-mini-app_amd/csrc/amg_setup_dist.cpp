@@ -2849,6 +2849,7 @@ void BoomerAMG::build_distributed(ParCSR &A0) {
       tail->p.non_galerkin_level_tol = shifted;
     }
     tail->device_min_rows = device_min_rows;
+    tail->host_only = host_only;
     tail->use_private_self_comm();
     tail->setup_host(*tail_A);
     tail_start = Ls.starts[(size_t)rank];

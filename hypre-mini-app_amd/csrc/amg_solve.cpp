@@ -45,11 +45,13 @@ int relax_prof_id(int level, bool zero_guess) {
 struct GsKind {
   bool jacobi, l1, fwd, bwd;
   int two_stage;  // relax types 11 / 12: inner iterations of the two-stage Gauss-Seidel
+  bool cheby;     // relax type 16
 };
 GsKind classify(int type) {
   GsKind g{};
   g.two_stage = (type == 11) ? 1 : (type == 12) ? 2 : 0;
-  if (g.two_stage) return g;
+  g.cheby = type == 16;
+  if (g.two_stage || g.cheby) return g;
   g.jacobi = (type == 0 || type == 7 || type == 18);
   g.l1 = (type == 8 || type == 13 || type == 14 || type == 18);
   g.fwd = (type == 3 || type == 6 || type == 8 || type == 13);
@@ -203,6 +205,25 @@ void BoomerAMG::relax(int level, int type, int points, const double *f, bool u_i
     }
     return;
   }
+  if (g.cheby) {
+    // cheby.order steps, each one pass over A with the update in the SpMV's epilogue; the new
+    // iterate lands in the other buffer.  The C/F marker, the weights and relax_order play no part.
+    refresh_cheby();
+    const AmgLevel::Cheby &c = Lv.cheby;
+    if (!c.ready)
+      fail(4, "BoomerAMG: relax type 16 (Chebyshev) on level " + std::to_string(level) +
+                  ", but the level has no Chebyshev data (Setup saw no relax_type 16, or the Chebyshev settings were refused)");
+    for (int st = 0; st < c.order; st++) {
+      if (st == 0 && u_is_zero) {  // no matrix pass, no halo: d = b0 f / diag, u = d
+        k::cheby_first(f, Lv.d_diag.p, c.b[0], Lv.cheby_d.p, Lv.u.p, Lv.n, s);
+        continue;
+      }
+      const double *offc = A.offd_contrib(comm, Lv.u.p, s);
+      k::cheby_step(A.d_diag, Lv.u.p, Lv.snap.p, Lv.cheby_d.p, f, offc, Lv.d_diag.p, c.a[st], c.b[st], s, prof);
+      std::swap(Lv.u.p, Lv.snap.p);  // every row was written
+    }
+    return;
+  }
   if (g.jacobi) {
     // a zero vector has a zero halo: no exchange, no halo contribution
     const double *offc = u_is_zero ? nullptr : A.offd_contrib(comm, u, s);
@@ -235,6 +256,10 @@ void BoomerAMG::relax(int level, int type, int points, const double *f, bool u_i
 void BoomerAMG::relax_pair(int level, int type, int first, const double *f, bool u_is_zero) {
   AmgLevel &Lv = L[(size_t)level];
   const GsKind g = classify(type);
+  if (g.cheby) {  // a Chebyshev sweep is not split into a C and an F half
+    relax(level, type, 0, f, u_is_zero);
+    return;
+  }
   if (g.jacobi || g.two_stage || Lv.cf.empty() || Lv.nc == 0 || Lv.nc == Lv.n) {
     relax(level, type, first, f, u_is_zero);
     relax(level, type, -first, f, false);
@@ -361,6 +386,7 @@ bool BoomerAMG::zero_cycle_ignores_u(int level) {
   if (Lv.smoother || p.num_sweeps[0] < 1 || zero_skip_mode() < 1) return false;
   const int type = p.relax_type[0];
   if (type == 9 || type == 11 || type == 12) return false;
+  if (type == 16) return Lv.cheby.ready;  // step 0 on a zero guess: u = d = b0 f / diag overwrites every row
   const GsKind g = classify(type);
   if (g.jacobi || !(g.fwd || g.bwd)) return false;
   const int ch = chunk();
@@ -387,6 +413,16 @@ void BoomerAMG::cycle(int level, bool u_is_zero) {
       tail->p.ilu_iter_max_iter = p.ilu_iter_max_iter;
       tail->p.ilu_iter_tol = p.ilu_iter_tol;
     }
+  }
+  if (level == 0) {
+    if (tail) {  // the redundant tail rebuilds its own at its next cycle
+      tail->p.cheby_order = p.cheby_order;
+      tail->p.cheby_fraction = p.cheby_fraction;
+      tail->p.cheby_eig_est = p.cheby_eig_est;
+      tail->p.cheby_variant = p.cheby_variant;
+      tail->p.cheby_scale = p.cheby_scale;
+    }
+    refresh_cheby();  // a Chebyshev parameter changed after Setup
   }
   if (level == 0 && collapsed_level >= 0 && collapsed_signature != cycle_signature())
     build_collapsed_tail();  // a cycle parameter changed after Setup: the tabulated map is of another cycle
@@ -527,6 +563,7 @@ std::vector<double> BoomerAMG::cycle_signature() const {
   v.push_back(p.smooth_num_sweeps);
   v.push_back(p.ilu_max_iter);
   for (double x : current_fsai_signature()) v.push_back(x);
+  for (double x : current_cheby_signature()) v.push_back(x);
   return v;
 }
 

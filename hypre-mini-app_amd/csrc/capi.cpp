@@ -667,6 +667,7 @@ HYPRE_Int HYPRE_MI_BoomerAMGSetupHostOnly(HYPRE_Solver solver, HYPRE_ParCSRMatri
   API_BEGIN
   if (!A) fail(HYPRE_ERROR_ARG, "BoomerAMGSetupHostOnly: NULL matrix");
   AMG(solver)->amg.device_min_rows = -1;  // host threads only
+  AMG(solver)->amg.host_only = true;
   AMG(solver)->amg.setup_host(*PM(A));
   AMG(solver)->amg.apply_value_storage(false);
   if (AMG(solver)->amg.tail) AMG(solver)->amg.tail->apply_value_storage(false);
@@ -1083,6 +1084,13 @@ AMG_SET(FSAINumLevels, HYPRE_Int, p.fsai_num_levels = v)
 AMG_SET(FSAIThreshold, HYPRE_Real, if (v < 0.0) fail(HYPRE_ERROR_ARG, "fsai_threshold < 0"); p.fsai_threshold = v)
 AMG_SET(FSAIEigMaxIters, HYPRE_Int, if (v < 0) fail(HYPRE_ERROR_ARG, "fsai_eig_max_iters < 0"); p.fsai_eig_max_iters = v)
 AMG_SET(FSAIMaxSteps, HYPRE_Int, warn_ignored("fsai_max_steps", v))
+/* relax type 16: stored here, checked at Setup like every other choice (order 1 ... 4, fraction in (0, 1), eig_est >= 0,
+ * variant 0 and scale 1 are built) */
+AMG_SET(ChebyOrder, HYPRE_Int, p.cheby_order = v)
+AMG_SET(ChebyFraction, HYPRE_Real, p.cheby_fraction = v)
+AMG_SET(ChebyEigEst, HYPRE_Int, p.cheby_eig_est = v)
+AMG_SET(ChebyVariant, HYPRE_Int, p.cheby_variant = v)
+AMG_SET(ChebyScale, HYPRE_Int, p.cheby_scale = v)
 AMG_SET(FSAIMaxStepSize, HYPRE_Int, warn_ignored("fsai_max_step_size", v))
 AMG_SET(FSAIMaxNnzRow, HYPRE_Int, warn_ignored("fsai_max_nnz_row", v))
 AMG_SET(FSAIKapTolerance, HYPRE_Real, warn_ignored("fsai_kap_tolerance", v))
@@ -2233,6 +2241,20 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetLevelFSAI(HYPRE_Solver solver, HYPRE_Int level, H
   if (omega) *omega = fs->omega;
   API_END
 }
+HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCheby(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Real *out) {
+  API_BEGIN
+  AmgSolver *a = AMG(solver);
+  if (!a->amg.is_setup) fail(HYPRE_ERROR_GENERIC, "GetLevelCheby: AMG is not set up");
+  if (!out) fail(HYPRE_ERROR_ARG, "GetLevelCheby: no buffer");
+  BoomerAMG *o = nullptr;
+  int loc = 0;
+  AmgLevel &Lv = level_ref(a, level, &o, &loc);
+  o->refresh_cheby();
+  const AmgLevel::Cheby &c = Lv.cheby;
+  if (!c.ready) fail(HYPRE_ERROR_ARG, "GetLevelCheby: the level has no Chebyshev data (Setup saw no relax_type 16)");
+  out[0] = c.eig_min, out[1] = c.eig_max, out[2] = c.lower, out[3] = c.upper, out[4] = c.theta, out[5] = c.delta;
+  API_END
+}
 HYPRE_Int HYPRE_MI_BoomerAMGSmoothLevel(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int zero_guess,
                                         const HYPRE_Real *f_host, HYPRE_Real *u_host) {
   API_BEGIN
@@ -2302,6 +2324,19 @@ HYPRE_Int HYPRE_MI_SolveKernelChoice(HYPRE_Int family, HYPRE_Int xcache, HYPRE_I
   d.nrows = nrows;
   d.rowlen_p95 = rowlen_p95;
   snprintf(name, (size_t)max_len, "%s", (family == 0 ? k::choose_stream_kernel(d) : k::choose_gs_kernel(d)).name);
+  API_END
+}
+HYPRE_Int HYPRE_MI_ChebyKernelChoice(HYPRE_Int xcache, HYPRE_Int tile_entries, HYPRE_Int has_fp32, HYPRE_Int has_dictionary,
+                                     char *name, HYPRE_Int max_len) {
+  API_BEGIN
+  if (!name || max_len < 1) fail(HYPRE_ERROR_ARG, "ChebyKernelChoice: no buffer");
+  if (tile_entries != k::SPMV_TILE && tile_entries != k::SPMV_TILE_WIDE) fail(HYPRE_ERROR_ARG, "ChebyKernelChoice: tile_entries must be 2048 or 4096");
+  k::SolveKernelDesc d;
+  d.xcache = xcache != 0;
+  d.tile_entries = tile_entries;
+  d.format = value_format_of(has_fp32 != 0, has_dictionary != 0);
+  d.epi = 2;
+  snprintf(name, (size_t)max_len, "%s", k::choose_stream_kernel(d).name);
   API_END
 }
 HYPRE_Int HYPRE_MI_ProfileReset(void) {

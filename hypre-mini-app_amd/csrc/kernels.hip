@@ -78,6 +78,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int chunk) { return (bid & 7) 
 // whole-workgroup path instead.
 // EPI 0: y = alpha*s + beta*b          (matvec / residual / restrict / prolong)
 // EPI 1: masked Jacobi  y = x_i + w*(f - offc - s)/d on selected rows, else x_i
+// EPI 2: Chebyshev step dc_i = ca*dc_i + cb*((f - s - offc)/d), y = x_i + dc_i  (relax type 16)
 // ---------------------------------------------------------------------------
 struct EpiArgs {
   double alpha, beta;      // EPI 0
@@ -89,6 +90,8 @@ struct EpiArgs {
   const int *rowmap;       // EPI 0 (nullable): stored row r is row rowmap[r] of y and b (DevCSR::rowmap)
   const double *b_lo;      // EPI 0 (nullable): rows < b_split take their b entry from here (a composite right-hand
   int b_split;             //   side: BoomerAMG's residual after a zero-guess sweep, f for the C rows, f - A_FC u_C after)
+  double *dc;              // EPI 2: the Chebyshev direction vector, updated in place (b = f, offc, d as for EPI 1)
+  double ca, cb;           // EPI 2: the step's coefficients (ca == 0: step 0, dc is not read)
 };
 __device__ __forceinline__ double epi_b(const EpiArgs &e, int ro) { return ((e.b_lo && ro < e.b_split) ? e.b_lo : e.b)[ro]; }
 
@@ -99,6 +102,16 @@ __device__ __forceinline__ void epilogue(int r, double s, const double *__restri
     // y is written once and next read by another kernel: keep it out of L2's way
     const int ro = e.rowmap ? e.rowmap[r] : r;
     __builtin_nontemporal_store((e.beta == 0.0) ? e.alpha * s : e.alpha * s + e.beta * epi_b(e, ro), y + ro);
+  } else if (EPI == 2) {
+    // the specification's order of operations, without contraction: the restatement in the tests rounds the same way
+#pragma clang fp contract(off)
+    const double xi = x[r];
+    double res = e.b[r] - s;
+    if (e.offc) res -= e.offc[r];
+    double dn = e.cb * (res / e.d[r]);
+    if (e.ca != 0.0) dn = e.ca * e.dc[r] + dn;  // only row r's finishing lane touches dc[r]
+    e.dc[r] = dn;
+    y[r] = xi + dn;
   } else {
     const double xi = x[r];
     double out = xi;
@@ -1707,28 +1720,33 @@ static KernelChoice chosen(const KernelEntry<Fn> &e, KernelFamily family, int bl
   return KernelChoice{(const void *)e.kernel, e.name, family, block, lpc};
 }
 
-// EPI: 0 mat-vec, 1 masked Jacobi.  TAG 1 names the mat-vec of the level-0 class; the wide tiles have no such instantiation.
+// EPI: 0 mat-vec, 1 masked Jacobi, 2 Chebyshev step.  TAG 1 names the mat-vec of the level-0 class; the wide tiles have no such instantiation.
 KernelChoice choose_stream_kernel(const SolveKernelDesc &d) {
   // [ValueFormat][EPI]
-  static const KernelEntry<XcKernel> xc_wide[3][2] = {
-      {MI_KERNEL(spmv_stream_xc<0, 0, false, 512, true>), MI_KERNEL(spmv_stream_xc<1, 0, false, 512, true>)},
-      {MI_KERNEL(spmv_stream_xc<0, 0, true, 512>), MI_KERNEL(spmv_stream_xc<1, 0, true, 512>)},
-      {MI_KERNEL(spmv_stream_xc<0, 0, false, 512>), MI_KERNEL(spmv_stream_xc<1, 0, false, 512>)}};
-  // [ValueFormat][EPI, TAG = 0, 1 / 0, 0 / 1, 0]
-  static const KernelEntry<XcKernel> xc[3][3] = {
+  static const KernelEntry<XcKernel> xc_wide[3][3] = {
+      {MI_KERNEL(spmv_stream_xc<0, 0, false, 512, true>), MI_KERNEL(spmv_stream_xc<1, 0, false, 512, true>),
+       MI_KERNEL(spmv_stream_xc<2, 0, false, 512, true>)},
+      {MI_KERNEL(spmv_stream_xc<0, 0, true, 512>), MI_KERNEL(spmv_stream_xc<1, 0, true, 512>),
+       MI_KERNEL(spmv_stream_xc<2, 0, true, 512>)},
+      {MI_KERNEL(spmv_stream_xc<0, 0, false, 512>), MI_KERNEL(spmv_stream_xc<1, 0, false, 512>),
+       MI_KERNEL(spmv_stream_xc<2, 0, false, 512>)}};
+  // [ValueFormat][EPI, TAG = 0, 1 / 0, 0 / 1, 0 / 2, 0]
+  static const KernelEntry<XcKernel> xc[3][4] = {
       {MI_KERNEL(spmv_stream_xc<0, 1, false, 256, true>), MI_KERNEL(spmv_stream_xc<0, 0, false, 256, true>),
-       MI_KERNEL(spmv_stream_xc<1, 0, false, 256, true>)},
+       MI_KERNEL(spmv_stream_xc<1, 0, false, 256, true>), MI_KERNEL(spmv_stream_xc<2, 0, false, 256, true>)},
       {MI_KERNEL(spmv_stream_xc<0, 1, true, 256>), MI_KERNEL(spmv_stream_xc<0, 0, true, 256>),
-       MI_KERNEL(spmv_stream_xc<1, 0, true, 256>)},
+       MI_KERNEL(spmv_stream_xc<1, 0, true, 256>), MI_KERNEL(spmv_stream_xc<2, 0, true, 256>)},
       {MI_KERNEL(spmv_stream_xc<0, 1, false, 256>), MI_KERNEL(spmv_stream_xc<0, 0, false, 256>),
-       MI_KERNEL(spmv_stream_xc<1, 0, false, 256>)}};
+       MI_KERNEL(spmv_stream_xc<1, 0, false, 256>), MI_KERNEL(spmv_stream_xc<2, 0, false, 256>)}};
   // the plain stream has no dictionary form: [EPI, TAG]
-  static const KernelEntry<StreamKernel<float>> plain32[3] = {
-      MI_KERNEL(spmv_stream<0, 1, float>), MI_KERNEL(spmv_stream<0, 0, float>), MI_KERNEL(spmv_stream<1, 0, float>)};
-  static const KernelEntry<StreamKernel<double>> plain[3] = {MI_KERNEL(spmv_stream<0, 1>), MI_KERNEL(spmv_stream<0, 0>),
-                                                             MI_KERNEL(spmv_stream<1, 0>)};
+  static const KernelEntry<StreamKernel<float>> plain32[4] = {
+      MI_KERNEL(spmv_stream<0, 1, float>), MI_KERNEL(spmv_stream<0, 0, float>), MI_KERNEL(spmv_stream<1, 0, float>),
+      MI_KERNEL(spmv_stream<2, 0, float>)};
+  static const KernelEntry<StreamKernel<double>> plain[4] = {MI_KERNEL(spmv_stream<0, 1>), MI_KERNEL(spmv_stream<0, 0>),
+                                                             MI_KERNEL(spmv_stream<1, 0>), MI_KERNEL(spmv_stream<2, 0>)};
+  MI_REQUIRE(d.epi >= 0 && d.epi <= 2, "choose_stream_kernel: the epilogue is 0, 1 or 2");
   const int fmt = (int)d.format;
-  const int epi_tag = d.epi == 1 ? 2 : d.level0 ? 0 : 1;
+  const int epi_tag = d.epi == 2 ? 3 : d.epi == 1 ? 2 : d.level0 ? 0 : 1;
   if (d.xcache)
     return chosen(d.tile_entries == SPMV_TILE_WIDE ? xc_wide[fmt][d.epi] : xc[fmt][epi_tag], KernelFamily::STREAM_XC,
                   tile_block(d.tile_entries));
@@ -1895,6 +1913,135 @@ void jacobi(const DevCSR &A, const double *u_old, double *u_new, const double *f
   prof_begin(prof, s);
   prof_name(prof, launch_stream(1, A, u_old, u_new, e, s));
   prof_end(prof, s);
+}
+
+void cheby_step(const DevCSR &A, const double *u_old, double *u_new, double *dc, const double *f, const double *offc,
+                const double *diag, double a, double b, hipStream_t s, int prof) {
+  EpiArgs e{};
+  e.b = f;
+  e.offc = offc;
+  e.d = diag;
+  e.dc = dc;
+  e.ca = a;
+  e.cb = b;
+  prof_begin(prof, s);
+  prof_name(prof, launch_stream(2, A, u_old, u_new, e, s));
+  prof_end(prof, s);
+}
+
+namespace {
+// step 0 of a Chebyshev sweep on a zero guess: what the EPI 2 epilogue computes from a zero vector (row sum +0, no halo
+// part), bit for bit
+__global__ __launch_bounds__(256) void cheby_first_k(int n, const double *__restrict__ f, const double *__restrict__ diag,
+                                                     double b0, double *__restrict__ dc, double *__restrict__ u) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double dn = b0 * ((f[i] - 0.0) / diag[i]);
+  dc[i] = dn;
+  u[i] = 0.0 + dn;
+}
+__global__ __launch_bounds__(256) void inv_sqrt_k(int n, const double *__restrict__ x, double *__restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = 1.0 / sqrt(x[i]);
+}
+__global__ __launch_bounds__(256) void vec_mul_k(int n, const double *__restrict__ x, const double *__restrict__ y,
+                                                 double *__restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = x[i] * y[i];
+}
+// sum[i] = sum_j |a_ij| of the rows of a diag block (IA: the 32-bit row pointers, or the 64-bit ones of a big operator)
+template <class IA, class VT>
+__global__ __launch_bounds__(256) void row_abs_sum_k(int n, const IA *__restrict__ ia, const VT *__restrict__ a,
+                                                     double *__restrict__ sum) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double t = 0.0;
+  for (long long k = (long long)ia[i]; k < (long long)ia[i + 1]; k++) t += fabs((double)a[k]);
+  sum[i] = t;
+}
+// ... plus the halo block's entries (compressed rows: each stored row belongs to one lane)
+__global__ __launch_bounds__(256) void offd_abs_add_k(int nrows_c, const int *__restrict__ rows, const int *__restrict__ ia,
+                                                      const double *__restrict__ a, double *__restrict__ sum) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= nrows_c) return;
+  double t = 0.0;
+  for (int k = ia[q]; k < ia[q + 1]; k++) t += fabs(a[k]);
+  sum[rows[q]] += t;
+}
+// out[0] = max_i sum[i] / diag[i] as the bit pattern of a non-negative double (patterns order like the values; a NaN
+// sorts above every number and so survives), out[1] = number of rows whose diagonal is not positive.  out starts as 0, 0.
+__global__ __launch_bounds__(256) void gershgorin_k(int n, const double *__restrict__ sum, const double *__restrict__ diag,
+                                                    unsigned long long *__restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  unsigned long long bits = 0ULL, bad = 0ULL;
+  if (i < n) {
+    const double d = diag[i];
+    if (d > 0.0)
+      bits = (unsigned long long)__double_as_longlong(fabs(sum[i] / d));
+    else
+      bad = 1ULL;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long o = __shfl_down(bits, off, 64);
+    bits = o > bits ? o : bits;
+    bad += __shfl_down(bad, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (bits) atomicMax(out, bits);
+    if (bad) atomicAdd(out + 1, bad);
+  }
+}
+}  // namespace
+
+void cheby_first(const double *f, const double *diag, double b0, double *dc, double *u, int n, hipStream_t s) {
+  if (n == 0) return;
+  hipLaunchKernelGGL(cheby_first_k, dim3((n + 255) / 256), dim3(256), 0, s, n, f, diag, b0, dc, u);
+  MI_HIP(hipGetLastError());
+}
+void inv_sqrt(const double *x, double *out, int n, hipStream_t s) {
+  if (n == 0) return;
+  hipLaunchKernelGGL(inv_sqrt_k, dim3((n + 255) / 256), dim3(256), 0, s, n, x, out);
+  MI_HIP(hipGetLastError());
+}
+void vec_mul(const double *x, const double *y, double *out, int n, hipStream_t s) {
+  if (n == 0) return;
+  hipLaunchKernelGGL(vec_mul_k, dim3((n + 255) / 256), dim3(256), 0, s, n, x, y, out);
+  MI_HIP(hipGetLastError());
+}
+void gershgorin(const DevCSR &A, const DevOffd &B, const double *diag, double *work, double *lambda_max,
+                long long *bad_diagonals, hipStream_t s) {
+  const int n = A.nrows;
+  *lambda_max = 0.0;
+  *bad_diagonals = 0;
+  if (n == 0) return;
+  const dim3 grid((n + 255) / 256), block(256);
+  MI_REQUIRE(A.a.p || A.a32.p || A.nnz == 0, "gershgorin: the operator holds no value array");
+  if (A.big()) {
+    MI_REQUIRE(A.ia64.p != nullptr, "gershgorin: a big operator without 64-bit row pointers");
+    if (A.a.p)
+      hipLaunchKernelGGL((row_abs_sum_k<long long, double>), grid, block, 0, s, n, A.ia64.p, A.a.p, work);
+    else
+      hipLaunchKernelGGL((row_abs_sum_k<long long, float>), grid, block, 0, s, n, A.ia64.p, A.a32.p, work);
+  } else if (A.a.p) {
+    hipLaunchKernelGGL((row_abs_sum_k<int, double>), grid, block, 0, s, n, A.ia.p, A.a.p, work);
+  } else {
+    hipLaunchKernelGGL((row_abs_sum_k<int, float>), grid, block, 0, s, n, A.ia.p, A.a32.p, work);
+  }
+  MI_HIP(hipGetLastError());
+  if (B.nrows_c > 0) {
+    hipLaunchKernelGGL(offd_abs_add_k, dim3((B.nrows_c + 255) / 256), block, 0, s, B.nrows_c, B.rows.p, B.ia.p, B.a.p, work);
+    MI_HIP(hipGetLastError());
+  }
+  DVec<unsigned long long> out(2);
+  MI_HIP(hipMemsetAsync(out.p, 0, 2 * sizeof(unsigned long long), s));
+  hipLaunchKernelGGL(gershgorin_k, grid, block, 0, s, n, work, diag, out.p);
+  MI_HIP(hipGetLastError());
+  unsigned long long h[2] = {0, 0};
+  d2h(h, out.p, sizeof(h), s);
+  MI_HIP(hipStreamSynchronize(s));
+  std::memcpy(lambda_max, &h[0], sizeof(double));
+  *bad_diagonals = (long long)h[1];
 }
 
 void spmv_offd_add(const DevOffd &B, const double *xext, double alpha, double *y, hipStream_t s) {

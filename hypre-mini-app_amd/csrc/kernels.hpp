@@ -151,7 +151,7 @@ struct SolveKernelDesc {
   bool xcache = false;
   int tile_entries = SPMV_TILE;
   ValueFormat format = ValueFormat::FP64;
-  int epi = 0;          // SpMV family: 0 mat-vec, 1 masked Jacobi
+  int epi = 0;          // SpMV family: 0 mat-vec, 1 masked Jacobi, 2 Chebyshev step
   bool level0 = false;  // SpMV family: launched under the profiler's level-0 class
   // hybrid Gauss-Seidel family
   int chunk = 8;
@@ -183,6 +183,20 @@ void spmv_offd_set(const DevOffd &B, const double *xext, double *out, hipStream_
 // masked Jacobi family: u_new = u_old + w*(f - offc - A*u_old)/d on selected rows, copy elsewhere
 void jacobi(const DevCSR &A, const double *u_old, double *u_new, const double *f, const double *offc, const double *d,
             const signed char *cf, int points, double w, hipStream_t s, int prof = PROF_NONE);
+// Chebyshev step (relax type 16) in the stream SpMV's epilogue, one pass over A:
+//   dc_i = a*dc_i + b*((f_i - (A u_old)_i - offc_i) / diag_i)   (a == 0: step 0, dc is not read),   u_new_i = u_old_i + dc_i
+// dc is updated in place (row i's finishing lane alone touches dc_i); u_new must not alias u_old
+void cheby_step(const DevCSR &A, const double *u_old, double *u_new, double *dc, const double *f, const double *offc,
+                const double *diag, double a, double b, hipStream_t s, int prof = PROF_NONE);
+// step 0 on a zero guess, no matrix pass: dc_i = b0*(f_i / diag_i), u_i = dc_i -- the bits cheby_step gives from u_old = 0
+void cheby_first(const double *f, const double *diag, double b0, double *dc, double *u, int n, hipStream_t s);
+// out = 1 / sqrt(x);  out = x .* y (out may alias either)
+void inv_sqrt(const double *x, double *out, int n, hipStream_t s);
+void vec_mul(const double *x, const double *y, double *out, int n, hipStream_t s);
+// this rank's Gershgorin bound of D^-1 A: max_i sum_j |a_ij| / diag_i over the diag block A and the halo block B, and
+// the number of rows whose diag_i is not positive (they take no part in the maximum); work: n doubles; synchronises s
+void gershgorin(const DevCSR &A, const DevOffd &B, const double *diag, double *work, double *lambda_max,
+                long long *bad_diagonals, hipStream_t s);
 // hybrid Gauss-Seidel family: chunks of `chunk` consecutive rows are swept
 // sequentially (forward and/or backward), chunks see each other's pre-sweep
 // values.  Only the chunks that intersect [row_begin, row_end) are swept (a C or

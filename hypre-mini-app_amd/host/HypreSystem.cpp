@@ -413,6 +413,17 @@ void HypreSystem::setup_boomeramg_precond() {
       throw std::runtime_error(std::string("Hypre Config:: mi_value_storage: ") + HYPRE_MI_LastErrorMessage());
 #endif
   }
+  /* this library's keys for relax_type 16 (Chebyshev): steps per sweep, smoothed fraction of the spectrum, CG steps of
+   * the eigenvalue estimate (0 = Gershgorin); an absent key leaves the solver's default (2, 0.3, 10) */
+  if (node["mi_cheby_order"] || node["mi_cheby_fraction"] || node["mi_cheby_eig_est"]) {
+#ifdef MI_HOST_WITH_LIBHYPRE
+    throw std::runtime_error("Hypre Config:: mi_cheby_* are keys of libmi_hypre; libHYPRE has no such setting");
+#else
+    if (node["mi_cheby_order"]) HYPRE_BoomerAMGSetChebyOrder(precond_, node["mi_cheby_order"].as<int>());
+    if (node["mi_cheby_fraction"]) HYPRE_BoomerAMGSetChebyFraction(precond_, node["mi_cheby_fraction"].as<double>());
+    if (node["mi_cheby_eig_est"]) HYPRE_BoomerAMGSetChebyEigEst(precond_, node["mi_cheby_eig_est"].as<int>());
+#endif
+  }
   if (node["trunc_factor"]) HYPRE_BoomerAMGSetTruncFactor(precond_, node["trunc_factor"].as<double>());
   if (node["agg_p12_trunc_factor"])
     HYPRE_BoomerAMGSetAggP12TruncFactor(precond_, node["agg_p12_trunc_factor"].as<double>());

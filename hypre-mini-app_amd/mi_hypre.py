@@ -310,6 +310,11 @@ class BoomerAMG:
                               ("fsai_max_step_size", "HYPRE_BoomerAMGSetFSAIMaxStepSize", int),
                               ("fsai_max_nnz_row", "HYPRE_BoomerAMGSetFSAIMaxNnzRow", int),
                               ("fsai_kap_tolerance", "HYPRE_BoomerAMGSetFSAIKapTolerance", float),
+                              ("cheby_order", "HYPRE_BoomerAMGSetChebyOrder", int),  # relax type 16
+                              ("cheby_fraction", "HYPRE_BoomerAMGSetChebyFraction", float),
+                              ("cheby_eig_est", "HYPRE_BoomerAMGSetChebyEigEst", int),
+                              ("cheby_variant", "HYPRE_BoomerAMGSetChebyVariant", int),
+                              ("cheby_scale", "HYPRE_BoomerAMGSetChebyScale", int),
                               ("true_pmax_elmts", "HYPRE_BoomerAMGSetPMaxElmts", int)):
             if key in cfg:
                 call(fn, s, conv(cfg[key]))
@@ -472,6 +477,25 @@ class BoomerAMG:
             fn, conv = names[k]
             call(fn, self.h, conv(v))
             self.cfg[k] = v
+
+    def set_cheby(self, **kw):
+        """Change Chebyshev parameters (cheby_* keys of the constructor), also after setup."""
+        names = {"cheby_order": ("HYPRE_BoomerAMGSetChebyOrder", int),
+                 "cheby_fraction": ("HYPRE_BoomerAMGSetChebyFraction", float),
+                 "cheby_eig_est": ("HYPRE_BoomerAMGSetChebyEigEst", int),
+                 "cheby_variant": ("HYPRE_BoomerAMGSetChebyVariant", int),
+                 "cheby_scale": ("HYPRE_BoomerAMGSetChebyScale", int)}
+        for k, v in kw.items():
+            fn, conv = names[k]
+            call(fn, self.h, conv(v))
+            self.cfg[k] = v
+
+    def level_cheby(self, level):
+        """Chebyshev data of a level set up with relax type 16 in some slot: dict(eig_min, eig_max, lower, upper,
+        theta, delta) of D^-1 A; raises when the level has none."""
+        out = np.zeros(6, dtype=np.float64)
+        call("HYPRE_MI_BoomerAMGGetLevelCheby", self.h, level, out)
+        return dict(zip(("eig_min", "eig_max", "lower", "upper", "theta", "delta"), (float(v) for v in out)))
 
     def level_fsai(self, level):
         """(ia int64, ja int32, a f64, omega) of the level's FSAI factor G (GetLevelCSR numbering); None without one."""
@@ -853,6 +877,13 @@ def solve_kernel_choice(family, xcache=False, tile_entries=2048, fp32=False, dic
     buf = C.create_string_buffer(128)
     call("HYPRE_MI_SolveKernelChoice", family, int(xcache), tile_entries, int(fp32), int(dictionary), epilogue, int(level0),
          chunk, int(tiles), c_big(nnz), nrows, rowlen_p95, buf, 128)
+    return buf.value.decode()
+
+
+def cheby_kernel_choice(xcache=False, tile_entries=2048, fp32=False, dictionary=False):
+    """instantiation the library launches for a Chebyshev step (relax type 16) on such an operator (no device needed)."""
+    buf = C.create_string_buffer(128)
+    call("HYPRE_MI_ChebyKernelChoice", int(xcache), tile_entries, int(fp32), int(dictionary), buf, 128)
     return buf.value.decode()
 
 

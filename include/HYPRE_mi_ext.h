@@ -236,6 +236,10 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetGSSweepPaths(HYPRE_Solver solver, HYPRE_Int level
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelFSAISize(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int *nrows, HYPRE_BigInt *nnz);
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelFSAI(HYPRE_Solver solver, HYPRE_Int level, HYPRE_BigInt *ia, HYPRE_Int *ja,
                                          HYPRE_Complex *a, HYPRE_Real *omega);
+/* Chebyshev data of a level (relax type 16 in some slot at Setup): out[0 .. 5] = the estimated
+ * smallest and largest eigenvalue of D^-1 A, the interval [lower, upper] the polynomial is built for, its centre theta
+ * and half width delta.  An error when the level has none. */
+HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCheby(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Real *out);
 /* HYPRE_ILU with the iterative setup (types 1-4): sweeps run by the last Setup on this rank and
  * the last correction / residual norm (-1 when the option bits did not ask for it); the kept histories (option bit
  * 16; null arrays: the lengths only); the factors L (unit, strictly lower) and U as one CSR of the rank's diagonal
@@ -270,6 +274,9 @@ HYPRE_Int HYPRE_MI_SolveKernelChoice(HYPRE_Int family, HYPRE_Int xcache, HYPRE_I
                                      HYPRE_Int has_dictionary, HYPRE_Int epilogue, HYPRE_Int level0, HYPRE_Int chunk,
                                      HYPRE_Int tiles, HYPRE_BigInt nnz, HYPRE_Int nrows, HYPRE_Int rowlen_p95, char *name,
                                      HYPRE_Int max_len);
+/* the same for the Chebyshev step (relax type 16), the third epilogue of the SpMV family */
+HYPRE_Int HYPRE_MI_ChebyKernelChoice(HYPRE_Int xcache, HYPRE_Int tile_entries, HYPRE_Int has_fp32, HYPRE_Int has_dictionary,
+                                     char *name, HYPRE_Int max_len);
 
 /* ---- synthetic problem: n^3-type Laplacian, true lexicographic global numbering
  * (7-point: diag 6 / off -1; 27-point: diag 26 / off -1 as
