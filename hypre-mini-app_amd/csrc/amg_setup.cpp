@@ -25,146 +25,38 @@ namespace hs {  // host setup algorithms, shared with amg_setup_dist.cpp (amg_se
 
 constexpr int MAX_DENSE = 4096;
 
-// hypre_SeedRand / hypre_Rand (Park-Miller minimal standard)
-struct ParkMiller {
-  int seed;
-  explicit ParkMiller(int s) : seed(s ? s : 13579) {}
-  double next() {
-    const int a = 16807, m = 2147483647, q = 127773, r = 2836;
-    const int lo = seed % q, hi = seed / q;
-    const int t = a * lo - r * hi;
-    seed = (t > 0) ? t : t + m;
-    return (double)seed / m;
-  }
-};
-
 // strong iff a_ij < theta*min_k a_ik (a_ii > 0; mirrored for a_ii < 0); the row
 // scale and row sum run over diag AND offd entries; only diag-block entries are
 // kept because halo connections do not take part in rank-local coarsening
 void strength(const ParCSR &A, double theta, double max_row_sum, Strength &S) {
   const HostCSR &D = A.diag, &O = A.offd;
   const int n = D.nrows;
-  std::vector<int> cnt((size_t)n, 0);
-  std::vector<double> thr((size_t)n, 0.0);
-  std::vector<signed char> mode((size_t)n, 0);  // 0 none, 1 diag>=0, -1 diag<0
+  std::vector<StrengthRule> rule((size_t)n);
+  std::vector<int64_t> dpos((size_t)n, -1);  // the diagonal's entry
+  S.ia.assign((size_t)n + 1, 0);
   parallel_for(n, [&](int64_t b, int64_t e, int) {
     for (int64_t i = b; i < e; i++) {
-      double diag = 0.0, row_sum = 0.0;
-      for (int64_t k = D.ia[(size_t)i]; k < D.ia[(size_t)i + 1]; k++) {
-        row_sum += D.a[(size_t)k];
-        if (D.ja[(size_t)k] == i) diag = D.a[(size_t)k];
-      }
-      for (int64_t k = O.ia[(size_t)i]; k < O.ia[(size_t)i + 1]; k++) row_sum += O.a[(size_t)k];
-      double scale = 0.0;
-      auto upd = [&](double v) {
-        if (diag < 0) {
-          if (v > scale) scale = v;
-        } else {
-          if (v < scale) scale = v;
-        }
-      };
-      for (int64_t k = D.ia[(size_t)i]; k < D.ia[(size_t)i + 1]; k++)
-        if (D.ja[(size_t)k] != i) upd(D.a[(size_t)k]);
-      for (int64_t k = O.ia[(size_t)i]; k < O.ia[(size_t)i + 1]; k++) upd(O.a[(size_t)k]);
-      const bool all_weak = (std::fabs(row_sum) > std::fabs(diag) * max_row_sum) && (max_row_sum < 1.0);
-      if (all_weak) continue;
-      mode[(size_t)i] = (diag < 0) ? -1 : 1;
-      thr[(size_t)i] = theta * scale;
-      int c = 0;
-      for (int64_t k = D.ia[(size_t)i]; k < D.ia[(size_t)i + 1]; k++) {
-        if (D.ja[(size_t)k] == i) continue;
-        const double v = D.a[(size_t)k];
-        if ((diag < 0) ? (v > thr[(size_t)i]) : (v < thr[(size_t)i])) c++;
-      }
-      cnt[(size_t)i] = c;
+      const int64_t r0 = D.ia[(size_t)i], r1 = D.ia[(size_t)i + 1], o0 = O.ia[(size_t)i];
+      for (int64_t k = r0; k < r1; k++)
+        if (D.ja[(size_t)k] == i) dpos[(size_t)i] = k;
+      const int64_t dp = dpos[(size_t)i];
+      const StrengthRule r = strength_rule(D.a.data() + r0, r1 - r0, dp < 0 ? -1 : dp - r0, theta, max_row_sum,
+                                           O.a.data() + o0, O.ia[(size_t)i + 1] - o0);
+      int64_t c = 0;
+      for (int64_t k = r0; k < r1; k++) c += (k != dp && r(D.a[(size_t)k]));
+      rule[(size_t)i] = r;
+      S.ia[(size_t)i + 1] = c;
     }
   });
-  S.ia.assign((size_t)n + 1, 0);
-  for (int i = 0; i < n; i++) S.ia[(size_t)i + 1] = S.ia[(size_t)i] + cnt[(size_t)i];
+  for (int i = 0; i < n; i++) S.ia[(size_t)i + 1] += S.ia[(size_t)i];
   S.ja.resize((size_t)S.ia[(size_t)n]);
   parallel_for(n, [&](int64_t b, int64_t e, int) {
     for (int64_t i = b; i < e; i++) {
-      if (!mode[(size_t)i]) continue;
       int64_t q = S.ia[(size_t)i];
-      for (int64_t k = D.ia[(size_t)i]; k < D.ia[(size_t)i + 1]; k++) {
-        if (D.ja[(size_t)k] == i) continue;
-        const double v = D.a[(size_t)k];
-        if ((mode[(size_t)i] < 0) ? (v > thr[(size_t)i]) : (v < thr[(size_t)i])) S.ja[(size_t)q++] = D.ja[(size_t)k];
-      }
+      for (int64_t k = D.ia[(size_t)i]; k < D.ia[(size_t)i + 1]; k++)
+        if (k != dpos[(size_t)i] && rule[(size_t)i](D.a[(size_t)k])) S.ja[(size_t)q++] = D.ja[(size_t)k];
     }
   });
-}
-
-// PMIS, rank-local graph; measure = |S^T row| + Park-Miller(2747 + rank)
-void pmis(int n, const Strength &S, int rank, std::vector<int> &cf) {
-  std::vector<double> measure((size_t)n, 0.0);
-  for (int64_t k = 0; k < (int64_t)S.ja.size(); k++) measure[(size_t)S.ja[(size_t)k]] += 1.0;
-  ParkMiller rng(2747 + rank);
-  for (int i = 0; i < n; i++) measure[(size_t)i] += rng.next();
-  cf.assign((size_t)n, 0);
-  std::vector<int> graph;
-  graph.reserve((size_t)n);
-  for (int i = 0; i < n; i++) {
-    if (S.ia[(size_t)i + 1] == S.ia[(size_t)i]) {
-      cf[(size_t)i] = SF_PT;
-      measure[(size_t)i] = 0.0;
-    } else if (measure[(size_t)i] < 1.0) {
-      cf[(size_t)i] = F_PT;
-      measure[(size_t)i] = 0.0;
-    } else
-      graph.push_back(i);
-  }
-  std::vector<signed char> tmp((size_t)n, 0);
-  while (!graph.empty()) {
-    const int64_t ng = (int64_t)graph.size();
-    parallel_for(ng, [&](int64_t b, int64_t e, int) {
-      for (int64_t g = b; g < e; g++) tmp[(size_t)graph[(size_t)g]] = 1;
-    });
-    parallel_for(ng, [&](int64_t b, int64_t e, int) {
-      for (int64_t g = b; g < e; g++) {
-        const int i = graph[(size_t)g];
-        for (int64_t k = S.ia[(size_t)i]; k < S.ia[(size_t)i + 1]; k++) {
-          const int j = S.ja[(size_t)k];
-          if (cf[(size_t)j] != 0) continue;
-          if (measure[(size_t)i] > measure[(size_t)j])
-            __atomic_store_n(&tmp[(size_t)j], (signed char)0, __ATOMIC_RELAXED);
-          else if (measure[(size_t)j] > measure[(size_t)i])
-            __atomic_store_n(&tmp[(size_t)i], (signed char)0, __ATOMIC_RELAXED);
-        }
-      }
-    });
-    parallel_for(ng, [&](int64_t b, int64_t e, int) {
-      for (int64_t g = b; g < e; g++) {
-        const int i = graph[(size_t)g];
-        if (tmp[(size_t)i] == 1) cf[(size_t)i] = C_PT;
-      }
-    });
-    // new F points: undecided rows that depend on a C point (C points of this
-    // round included, exactly as the serial loop sees them)
-    std::vector<signed char> becomes_f((size_t)ng, 0);
-    parallel_for(ng, [&](int64_t b, int64_t e, int) {
-      for (int64_t g = b; g < e; g++) {
-        const int i = graph[(size_t)g];
-        if (cf[(size_t)i] != 0) continue;
-        for (int64_t k = S.ia[(size_t)i]; k < S.ia[(size_t)i + 1]; k++)
-          if (cf[(size_t)S.ja[(size_t)k]] == C_PT) {
-            becomes_f[(size_t)g] = 1;
-            break;
-          }
-      }
-    });
-    std::vector<int> next;
-    next.reserve(graph.size());
-    for (int64_t g = 0; g < ng; g++) {
-      const int i = graph[(size_t)g];
-      if (becomes_f[(size_t)g]) cf[(size_t)i] = F_PT;
-      if (cf[(size_t)i] == 0)
-        next.push_back(i);
-      else
-        measure[(size_t)i] = 0.0;
-    }
-    graph.swap(next);
-  }
 }
 
 // keep entries >= trunc_factor*max|p|, then the pmax largest by (|p| desc,
@@ -525,108 +417,53 @@ bool coarsen_type_restated(int type) {
   return type == 8 || type == 9 || type == 10 || type == 11 || type == 6 || type == 1 || type == 3 || type == 0 || type == 7;
 }
 
-// CLJP (par_coarsen.c hypre_BoomerAMGCoarsen; oracle/oracle.c cljp for the statement of the algorithm):
-// w = |S^T row| + the global Park-Miller stream; rounds of { independent set of the undecided points -> C;
-// H1: edges out of a new C point leave, w-- at their undecided ends; H2: an undecided row loses its edges to C
-// points, and the edges to undecided points that share one of its C points, w-- there; w < 1 -> F }.
-// Within a round every step reads what the previous step left (counts and flags commute): host threads.
-void cljp(int n, const Strength &S, std::vector<int> &cf) {
-  const int64_t nnz = (int64_t)S.ja.size();
-  std::vector<char> gone((size_t)nnz, 0);
-  std::vector<int> dec((size_t)n, 0);  // pending decrements of a round (integers: order does not matter)
-  std::vector<double> measure((size_t)n, 0.0);
-  for (int64_t k = 0; k < nnz; k++) measure[(size_t)S.ja[(size_t)k]] += 1.0;
-  ParkMiller rng(2747);
-  for (int i = 0; i < n; i++) measure[(size_t)i] += rng.next();
-  cf.assign((size_t)n, 0);
-  std::vector<int> graph;
-  graph.reserve((size_t)n);
-  for (int i = 0; i < n; i++) {
-    if (measure[(size_t)i] < 1.0)
-      cf[(size_t)i] = (S.ia[(size_t)i + 1] == S.ia[(size_t)i]) ? SF_PT : F_PT;
-    else
-      graph.push_back(i);
+// The graph view of the coarsening core (amg_setup_internal.hpp) for a Strength pattern on one rank: every neighbour
+// is an own row, every exchange is empty.
+struct LocalGraph {
+  static constexpr bool has_halo = false;
+  const int nrows;
+  const Strength &S;
+  int n() const { return nrows; }
+  int nh() const { return 0; }
+  int64_t nnz() const { return (int64_t)S.ja.size(); }
+  gidx first_id() const { return 0; }
+  template <class F>
+  bool each(int i, F f) const {
+    for (int64_t k = S.ia[(size_t)i]; k < S.ia[(size_t)i + 1]; k++)
+      if (f(k, S.ja[(size_t)k], -1)) return true;
+    return false;
   }
-  std::vector<signed char> tmp((size_t)n, 0);
-  const int nt = host_threads();
-  std::vector<std::vector<int>> common((size_t)nt);  // per thread: common[c] == i + 1: C point c is in the row of i
-  while (!graph.empty()) {
-    const int64_t ng = (int64_t)graph.size();
-    parallel_for(ng, [&](int64_t b, int64_t e, int) {
-      for (int64_t g = b; g < e; g++) tmp[(size_t)graph[(size_t)g]] = 1;
-    });
-    parallel_for(ng, [&](int64_t b, int64_t e, int) {
-      for (int64_t g = b; g < e; g++) {
-        const int i = graph[(size_t)g];
-        for (int64_t k = S.ia[(size_t)i]; k < S.ia[(size_t)i + 1]; k++) {
-          const int j = S.ja[(size_t)k];
-          if (cf[(size_t)j] != 0) continue;
-          if (measure[(size_t)i] > measure[(size_t)j])
-            __atomic_store_n(&tmp[(size_t)j], (signed char)0, __ATOMIC_RELAXED);
-          else if (measure[(size_t)j] > measure[(size_t)i])
-            __atomic_store_n(&tmp[(size_t)i], (signed char)0, __ATOMIC_RELAXED);
-        }
-      }
-    });
-    parallel_for(ng, [&](int64_t b, int64_t e, int) {
-      for (int64_t g = b; g < e; g++)
-        if (tmp[(size_t)graph[(size_t)g]] == 1) cf[(size_t)graph[(size_t)g]] = C_PT;
-    });
-    // H1 (rows of the new C points) and H2 (undecided rows): disjoint rows, decrements collected in `dec`
-    parallel_for(ng, [&](int64_t b, int64_t e, int t) {
-      std::vector<int> &cm = common[(size_t)t];
-      if (cm.size() != (size_t)n) cm.assign((size_t)n, 0);
-      for (int64_t g = b; g < e; g++) {
-        const int i = graph[(size_t)g];
-        if (cf[(size_t)i] == C_PT) {
-          for (int64_t k = S.ia[(size_t)i]; k < S.ia[(size_t)i + 1]; k++) {
-            if (gone[(size_t)k]) continue;
-            gone[(size_t)k] = 1;
-            if (cf[(size_t)S.ja[(size_t)k]] == 0) __atomic_fetch_add(&dec[(size_t)S.ja[(size_t)k]], 1, __ATOMIC_RELAXED);
-          }
-          continue;
-        }
-        for (int64_t k = S.ia[(size_t)i]; k < S.ia[(size_t)i + 1]; k++)
-          if (cf[(size_t)S.ja[(size_t)k]] == C_PT) {
-            gone[(size_t)k] = 1;
-            cm[(size_t)S.ja[(size_t)k]] = i + 1;
-          }
-        for (int64_t k = S.ia[(size_t)i]; k < S.ia[(size_t)i + 1]; k++) {
-          const int j = S.ja[(size_t)k];
-          if (gone[(size_t)k] || cf[(size_t)j] != 0) continue;
-          for (int64_t kk = S.ia[(size_t)j]; kk < S.ia[(size_t)j + 1]; kk++)
-            if (cm[(size_t)S.ja[(size_t)kk]] == i + 1) {
-              gone[(size_t)k] = 1;
-              __atomic_fetch_add(&dec[(size_t)j], 1, __ATOMIC_RELAXED);
-              break;
-            }
-        }
-      }
-    });
-    std::vector<int> next;
-    next.reserve(graph.size());
-    for (int64_t g = 0; g < ng; g++) {
-      const int i = graph[(size_t)g];
-      if (cf[(size_t)i] == C_PT) continue;
-      for (; dec[(size_t)i] > 0; dec[(size_t)i]--) measure[(size_t)i] -= 1.0;  // one at a time, as the oracle does
-      if (measure[(size_t)i] < 1.0)
-        cf[(size_t)i] = F_PT;
-      else
-        next.push_back(i);
-    }
-    graph.swap(next);
+  template <class T>
+  void forward(const std::vector<T> &, std::vector<T> &) const {}
+  template <class T, class F>
+  void reverse(const std::vector<T> &, std::vector<T> &, F) const {}
+  long long global_sum(long long v) const { return v; }
+  // CLJP H2, "do rows i and j share a C point": marker form.  marks[c] == i + 1: C point c is in the row of i -- one
+  // array of n per thread, no search.  (DistGraph in amg_setup_dist.cpp keeps the sorted-list form: there a C point
+  // may be a halo point or a point two rings away, which has no index to mark.)
+  using Marks = std::vector<int>;
+  void fetch_strong_halo_rows() {}
+  std::vector<Marks> make_marks() const { return std::vector<Marks>((size_t)host_threads()); }
+  void begin_row(Marks &mk, int) const {
+    if (mk.size() != (size_t)nrows) mk.assign((size_t)nrows, 0);
   }
-}
+  void mark(Marks &mk, int i, int64_t, int j) const { mk[(size_t)j] = i + 1; }
+  bool shares(const Marks &mk, int i, int j, int) const {
+    return each(j, [&](int64_t, int c, int) { return mk[(size_t)c] == i + 1; });
+  }
+};
 
 // HYPRE_BoomerAMGSetCoarsenType (src/HypreSystem.cpp:125-126): 8 PMIS; 10 HMIS / 11 = one-pass Ruge-Stueben;
 // 6 Falgout / 1 / 3 = two-pass Ruge-Stueben.  HMIS and Falgout finish with PMIS / CLJP on what the Ruge-Stueben
 // pass leaves undecided; coarsening sees the whole graph here, where nothing is left --
 // as on a single HYPRE rank.
 void coarsen_by_type(int type, int n, const Strength &S, std::vector<int> &cf) {
+  LocalGraph g{n, S};
+  std::vector<int> no_halo;
   if (type == 8 || type == 9)  // 9 = PMIS with one global random stream: what 8 is here anyway
-    pmis(n, S, 0, cf);
+    pmis(g, cf, no_halo);
   else if (type == 0 || type == 7)  // 7 = CLJP with one global random stream: the only kind this library draws
-    cljp(n, S, cf);
+    cljp(g, cf, no_halo);
   else if (type == 10 || type == 11)
     ruge_stueben(n, S, false, cf);
   else if (type == 6 || type == 1 || type == 3)
@@ -1495,53 +1332,8 @@ namespace hs {
 void sparsify_non_galerkin(HostCSR &A, double tol) {
   const int n = A.nrows;
   if (n == 0 || !(tol > 0.0)) return;
-  std::vector<double> m((size_t)n, 0.0);
-  parallel_for(n, [&](int64_t b, int64_t e, int) {
-    for (int64_t i = b; i < e; i++) {
-      double mx = 0.0;
-      for (int64_t k = A.ia[(size_t)i]; k < A.ia[(size_t)i + 1]; k++)
-        if (A.ja[(size_t)k] != i && std::fabs(A.a[(size_t)k]) > mx) mx = std::fabs(A.a[(size_t)k]);
-      m[(size_t)i] = mx;
-    }
-  });
-  HostCSR B;
-  B.nrows = n;
-  B.ncols = A.ncols;
-  B.ia.assign((size_t)n + 1, 0);
-  auto keeps = [&](int64_t i, int64_t k) {
-    const int j = A.ja[(size_t)k];
-    const double lim = tol * std::min(m[(size_t)i], m[(size_t)j]);
-    return j == i || !(std::fabs(A.a[(size_t)k]) < lim);
-  };
-  parallel_for(n, [&](int64_t b, int64_t e, int) {
-    for (int64_t i = b; i < e; i++) {
-      int64_t c = 0;
-      for (int64_t k = A.ia[(size_t)i]; k < A.ia[(size_t)i + 1]; k++) c += keeps(i, k) ? 1 : 0;
-      B.ia[(size_t)i + 1] = c;
-    }
-  });
-  for (int i = 0; i < n; i++) B.ia[(size_t)i + 1] += B.ia[(size_t)i];
-  B.ja.resize((size_t)B.nnz());
-  B.a.resize((size_t)B.nnz());
-  parallel_for(n, [&](int64_t b, int64_t e, int) {
-    for (int64_t i = b; i < e; i++) {
-      int64_t w = B.ia[(size_t)i], dpos = -1;
-      double lump = 0.0;
-      bool first = true;
-      for (int64_t k = A.ia[(size_t)i]; k < A.ia[(size_t)i + 1]; k++) {
-        if (keeps(i, k)) {
-          if (A.ja[(size_t)k] == i) dpos = w;
-          B.ja[(size_t)w] = A.ja[(size_t)k];
-          B.a[(size_t)w++] = A.a[(size_t)k];
-        } else {
-          lump = first ? A.a[(size_t)k] : lump + A.a[(size_t)k];
-          first = false;
-        }
-      }
-      if (!first && dpos >= 0) B.a[(size_t)dpos] = B.a[(size_t)dpos] + lump;
-    }
-  });
-  A = std::move(B);
+  const std::vector<double> m = offdiag_row_maxima(n, A.ia, A.ja, A.a, 0);
+  drop_and_lump(n, A.ia, A.ja, A.a, 0, m, [&](int j) { return m[(size_t)j]; }, tol);
 }
 }  // namespace hs
 

@@ -29,8 +29,17 @@
 // Below the redundancy threshold (HYPRE_BoomerAMGSetSeqThreshold) the level is gathered and every rank builds
 // the small remaining hierarchy for itself, as before.  Aggressive levels (second-generation PMIS on the C points,
 // multipass interpolation pass by pass with the halo rows of the previous pass) are distributed too (host loop).
-// HMIS / per-rank Ruge-Stueben / Falgout (dist_coarsen) and CLJP (dist_cljp) are host passes of this file too; only
+// HMIS / per-rank Ruge-Stueben / Falgout and CLJP (dist_coarsen) are host passes of this file too; only
 // coarsening type 3 (a third Ruge-Stueben pass on the boundary) keeps the replicated path on N > 1.
+//
+// Shared with the single-rank host setup (amg_setup_internal.hpp), stated once: the strength rule of a row
+// (hs::strength_rule), PMIS and CLJP (hs::pmis / hs::cljp over a graph view: DistGraph here, LocalGraph there; only
+// CLJP's common-C-point test has a form per view), the Park-Miller stream, and the non-Galerkin drop-and-lump
+// (hs::drop_and_lump).  Within this file every halo exchange goes through the two Ring primitives (to_halo /
+// to_owners), per-halo-row records through Ring::each_record, and the host loop and the device levels share
+// transpose_exchange.  Deliberately still separate pairs: build_multipass / dist_multipass and second_strength /
+// dist_second_stage (the distributed forms work pass by pass on fetched halo rows), and hs::build_interp, which runs
+// unchanged on the extended sub-problem.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -91,6 +100,11 @@ struct Reader {
   }
   bool done() const { return p >= e; }
 };
+template <class T>
+struct Ragged {  // list q = items[off[q] .. off[q + 1])
+  std::vector<int64_t> off{0};
+  std::vector<T> items;
+};
 
 // Neighbour plan for a sorted set of remote ids of a vector partitioned by `starts`: who owns them (receive side)
 // and which of my entries the others asked for (send side).  hypre_ParCSRCommPkg for an arbitrary id set.
@@ -134,45 +148,68 @@ struct Ring {
   int slot_of(gidx g) const {  // position of a remote id in `ids`
     return (int)(std::lower_bound(ids.begin(), ids.end(), g) - ids.begin());
   }
+  // The transport under every halo exchange of this file: send[i] goes to to[i], the answers come back indexed by
+  // position in `back`.  Every peer of a plan owes at least one entry, so a peer of `back` that stays silent is an error.
+  static std::vector<std::vector<char>> transport(Comm &comm, const std::vector<int> &to, const std::vector<std::vector<char>> &send,
+                                                  const std::vector<int> &back) {
+    std::vector<int> from;
+    std::vector<std::vector<char>> got;
+    comm.exchange_host(to, send, from, got);
+    std::vector<std::vector<char>> out(back.size());
+    std::vector<char> heard(back.size(), 0);
+    for (size_t i = 0; i < from.size(); i++) {
+      const size_t pi = (size_t)(std::find(back.begin(), back.end(), from[i]) - back.begin());
+      MI_REQUIRE(pi < back.size(), "distributed setup: unexpected sender");
+      out[pi].swap(got[i]);
+      heard[pi] = 1;
+    }
+    MI_REQUIRE(std::find(heard.begin(), heard.end(), 0) == heard.end(), "distributed setup: a halo peer sent nothing");
+    return out;
+  }
+  // the two primitives: byte strings for send_peers -> byte strings by position in recv_peers, and the way back
+  std::vector<std::vector<char>> to_halo(Comm &comm, const std::vector<std::vector<char>> &send) const {
+    return transport(comm, send_peers, send, recv_peers);
+  }
+  std::vector<std::vector<char>> to_owners(Comm &comm, const std::vector<std::vector<char>> &send) const {
+    return transport(comm, recv_peers, send, send_peers);
+  }
+  // fixed-size payloads: v is cut at `cuts` into one message per peer / the messages are laid out at `cuts`
+  template <class T>
+  static std::vector<std::vector<char>> split(const std::vector<T> &v, const std::vector<int> &cuts) {
+    std::vector<std::vector<char>> msg(cuts.size() - 1);
+    for (size_t i = 0; i + 1 < cuts.size(); i++) put(msg[i], v.data() + cuts[i], (size_t)(cuts[i + 1] - cuts[i]));
+    return msg;
+  }
+  template <class T>
+  static std::vector<T> join(const std::vector<std::vector<char>> &msg, const std::vector<int> &cuts) {
+    std::vector<T> v((size_t)cuts.back());
+    for (size_t i = 0; i < msg.size(); i++) {
+      MI_REQUIRE(msg[i].size() == (size_t)(cuts[i + 1] - cuts[i]) * sizeof(T), "distributed setup: halo message of the wrong size");
+      memcpy(v.data() + cuts[i], msg[i].data(), msg[i].size());
+    }
+    return v;
+  }
+  // values in send_map order -> the halo copies (ids order); one value per halo id -> the owners, in send_map order
+  template <class T>
+  std::vector<T> forward_packed(Comm &comm, const std::vector<T> &at_send) const {
+    return join<T>(to_halo(comm, split(at_send, send_starts)), recv_starts);
+  }
+  template <class T>
+  std::vector<T> reverse_packed(Comm &comm, const std::vector<T> &ext) const {
+    return join<T>(to_owners(comm, split(ext, recv_starts)), send_starts);
+  }
   // values of my entries -> their halo copies
   template <class T>
   std::vector<T> forward(Comm &comm, const std::vector<T> &local) const {
-    std::vector<T> ext(ids.size());
-    std::vector<std::vector<char>> send(send_peers.size());
-    for (size_t i = 0; i < send_peers.size(); i++) {
-      send[i].resize((size_t)(send_starts[i + 1] - send_starts[i]) * sizeof(T));
-      T *o = reinterpret_cast<T *>(send[i].data());
-      for (int k = send_starts[i]; k < send_starts[i + 1]; k++) o[k - send_starts[i]] = local[(size_t)send_map[(size_t)k]];
-    }
-    std::vector<int> from;
-    std::vector<std::vector<char>> got;
-    comm.exchange_host(send_peers, send, from, got);
-    for (size_t i = 0; i < from.size(); i++) {
-      const size_t pi = (size_t)(std::find(recv_peers.begin(), recv_peers.end(), from[i]) - recv_peers.begin());
-      MI_REQUIRE(pi < recv_peers.size(), "distributed setup: unexpected sender");
-      const size_t cnt = (size_t)(recv_starts[pi + 1] - recv_starts[pi]);
-      MI_REQUIRE(got[i].size() == cnt * sizeof(T), "distributed setup: halo message of the wrong size");
-      memcpy(ext.data() + recv_starts[pi], got[i].data(), got[i].size());
-    }
-    return ext;
+    std::vector<T> at_send(send_map.size());
+    for (size_t k = 0; k < send_map.size(); k++) at_send[k] = local[(size_t)send_map[k]];
+    return forward_packed(comm, at_send);
   }
   // one value per halo id -> the owners, folded into their entries
   template <class T, class F>
   void reverse(Comm &comm, const std::vector<T> &ext, std::vector<T> &local, F fold) const {
-    std::vector<std::vector<char>> send(recv_peers.size());
-    for (size_t i = 0; i < recv_peers.size(); i++)
-      put(send[i], ext.data() + recv_starts[i], (size_t)(recv_starts[i + 1] - recv_starts[i]));
-    std::vector<int> from;
-    std::vector<std::vector<char>> got;
-    comm.exchange_host(recv_peers, send, from, got);
-    for (size_t i = 0; i < from.size(); i++) {
-      const size_t pi = (size_t)(std::find(send_peers.begin(), send_peers.end(), from[i]) - send_peers.begin());
-      MI_REQUIRE(pi < send_peers.size(), "distributed setup: unexpected sender");
-      const size_t cnt = (size_t)(send_starts[pi + 1] - send_starts[pi]);
-      MI_REQUIRE(got[i].size() == cnt * sizeof(T), "distributed setup: reverse halo message of the wrong size");
-      const T *v = reinterpret_cast<const T *>(got[i].data());
-      for (size_t k = 0; k < cnt; k++) fold(local[(size_t)send_map[(size_t)send_starts[pi] + k]], v[k]);
-    }
+    const std::vector<T> at_send = reverse_packed(comm, ext);
+    for (size_t k = 0; k < send_map.size(); k++) fold(local[(size_t)send_map[k]], at_send[k]);
   }
   // a variable-size record of every row the peers asked for -> per receive peer one byte string holding the
   // records of its ids in ascending id order
@@ -181,31 +218,30 @@ struct Ring {
     std::vector<std::vector<char>> send(send_peers.size());
     for (size_t i = 0; i < send_peers.size(); i++)
       for (int k = send_starts[i]; k < send_starts[i + 1]; k++) pack(send_map[(size_t)k], send[i]);
-    std::vector<int> from;
-    std::vector<std::vector<char>> got;
-    comm.exchange_host(send_peers, send, from, got);
-    std::vector<std::vector<char>> out(recv_peers.size());
-    for (size_t i = 0; i < from.size(); i++) {
-      const size_t pi = (size_t)(std::find(recv_peers.begin(), recv_peers.end(), from[i]) - recv_peers.begin());
-      MI_REQUIRE(pi < recv_peers.size(), "distributed setup: unexpected sender");
-      out[pi].swap(got[i]);
+    return to_halo(comm, send);
+  }
+  // ... and their reader: read(q, rd) takes the record of halo slot q off the Reader; every string must be used up
+  template <class Read>
+  void each_record(const std::vector<std::vector<char>> &rec, Read read) const {
+    for (size_t pi = 0; pi < rec.size(); pi++) {
+      Reader rd(rec[pi]);
+      for (int q = recv_starts[pi]; q < recv_starts[pi + 1]; q++) read(q, rd);
+      MI_REQUIRE(rd.done(), "distributed setup: halo records longer than their plan");
     }
-    return out;
+  }
+  // records that are "count, then that many T": the lists of all halo slots, back to back
+  template <class T>
+  Ragged<T> read_lists(const std::vector<std::vector<char>> &rec) const {
+    Ragged<T> r;
+    each_record(rec, [&](int, Reader &rd) {
+      const size_t len = (size_t)rd.get<int>(), o = r.items.size();
+      r.items.resize(o + len);
+      rd.get(r.items.data() + o, len);
+      r.off.push_back((int64_t)r.items.size());
+    });
+    return r;
   }
 };
-
-// element `index` (0-based) of the Park-Miller stream seeded with `seed`: seed * 16807^(index+1) mod (2^31 - 1)
-int park_miller_at(int seed, long long index) {
-  const unsigned long long m = 2147483647ULL;
-  unsigned long long base = 16807ULL, acc = (unsigned long long)(seed ? seed : 13579) % m;
-  unsigned long long e = (unsigned long long)index + 1ULL;
-  while (e) {
-    if (e & 1ULL) acc = (acc * base) % m;
-    base = (base * base) % m;
-    e >>= 1;
-  }
-  return (int)acc;
-}
 
 // one level of the hierarchy while it is being built (natural ordering, global ids)
 struct DLevel {
@@ -360,15 +396,7 @@ void spgemm_auto(const HostCSR &A, const HostCSR &B, HostCSR &C, long long devic
 void sparsify_non_galerkin_dist(Comm &comm, GlobCSR &A, const std::vector<gidx> &starts, double tol) {
   const int n = A.nrows;
   const gidx s = starts[(size_t)comm.rank], e = starts[(size_t)comm.rank + 1];
-  std::vector<double> m((size_t)n, 0.0);
-  parallel_for(n, [&](int64_t b, int64_t en, int) {
-    for (int64_t i = b; i < en; i++) {
-      double mx = 0.0;
-      for (int64_t k = A.ia[(size_t)i]; k < A.ia[(size_t)i + 1]; k++)
-        if (A.gj[(size_t)k] != s + i && std::fabs(A.a[(size_t)k]) > mx) mx = std::fabs(A.a[(size_t)k]);
-      m[(size_t)i] = mx;
-    }
-  });
+  const std::vector<double> m = offdiag_row_maxima(n, A.ia, A.gj, A.a, s);
   Ring ring;
   {
     std::vector<gidx> need;
@@ -377,44 +405,8 @@ void sparsify_non_galerkin_dist(Comm &comm, GlobCSR &A, const std::vector<gidx> 
     ring.build(comm, starts, std::move(need));
   }
   const std::vector<double> m_h = ring.forward(comm, m);
-  auto keeps = [&](int64_t i, int64_t k) {
-    const gidx j = A.gj[(size_t)k];
-    const double mj = (j >= s && j < e) ? m[(size_t)(j - s)] : m_h[(size_t)ring.slot_of(j)];
-    const double lim = tol * std::min(m[(size_t)i], mj);
-    return j == s + i || !(std::fabs(A.a[(size_t)k]) < lim);
-  };
-  GlobCSR B;
-  B.nrows = n;
-  B.ia.assign((size_t)n + 1, 0);
-  parallel_for(n, [&](int64_t b, int64_t en, int) {
-    for (int64_t i = b; i < en; i++) {
-      int64_t c = 0;
-      for (int64_t k = A.ia[(size_t)i]; k < A.ia[(size_t)i + 1]; k++) c += keeps(i, k) ? 1 : 0;
-      B.ia[(size_t)i + 1] = c;
-    }
-  });
-  for (int i = 0; i < n; i++) B.ia[(size_t)i + 1] += B.ia[(size_t)i];
-  B.gj.resize((size_t)B.nnz());
-  B.a.resize((size_t)B.nnz());
-  parallel_for(n, [&](int64_t b, int64_t en, int) {
-    for (int64_t i = b; i < en; i++) {
-      int64_t w = B.ia[(size_t)i], dpos = -1;
-      double lump = 0.0;
-      bool first = true;
-      for (int64_t k = A.ia[(size_t)i]; k < A.ia[(size_t)i + 1]; k++) {
-        if (keeps(i, k)) {
-          if (A.gj[(size_t)k] == s + i) dpos = w;
-          B.gj[(size_t)w] = A.gj[(size_t)k];
-          B.a[(size_t)w++] = A.a[(size_t)k];
-        } else {
-          lump = first ? A.a[(size_t)k] : lump + A.a[(size_t)k];
-          first = false;
-        }
-      }
-      if (!first && dpos >= 0) B.a[(size_t)dpos] = B.a[(size_t)dpos] + lump;
-    }
-  });
-  A = std::move(B);
+  auto m_of = [&](gidx j) { return (j >= s && j < e) ? m[(size_t)(j - s)] : m_h[(size_t)ring.slot_of(j)]; };
+  drop_and_lump(n, A.ia, A.gj, A.a, s, m, m_of, tol);
 }
 
 // ============================================================================================================
@@ -507,20 +499,11 @@ RowSet fetch_rows(Comm &comm, const Ring &ring, const sk::DCsr &M, int row_shift
     put(send[i], g.data(), g.size());
     put(send[i], h.a.data() + e0, (size_t)(e1 - e0));
   }
-  std::vector<int> from;
-  std::vector<std::vector<char>> got;
-  comm.exchange_host(ring.send_peers, send, from, got);
-  std::vector<const std::vector<char> *> by(ring.recv_peers.size(), nullptr);
-  for (size_t i = 0; i < from.size(); i++) {
-    const size_t pi = (size_t)(std::find(ring.recv_peers.begin(), ring.recv_peers.end(), from[i]) - ring.recv_peers.begin());
-    MI_REQUIRE(pi < ring.recv_peers.size(), "distributed setup: unexpected sender");
-    by[pi] = &got[i];
-  }
+  const std::vector<std::vector<char>> got = ring.to_halo(comm, send);
   RowSet out;
-  for (size_t pi = 0; pi < ring.recv_peers.size(); pi++) {
+  for (size_t pi = 0; pi < got.size(); pi++) {
     const size_t cnt = (size_t)(ring.recv_starts[pi + 1] - ring.recv_starts[pi]);
-    MI_REQUIRE(by[pi] != nullptr, "distributed setup: a halo owner sent no rows");
-    Reader rd(*by[pi]);
+    Reader rd(got[pi]);
     std::vector<int> len(cnt);
     rd.get(len.data(), cnt);
     size_t total = 0;
@@ -590,20 +573,7 @@ struct DevHalo {
       d2h(sv.data(), tmp.p, (size_t)ns * sizeof(T), s);
       MI_HIP(hipStreamSynchronize(s));
     }
-    std::vector<std::vector<char>> send(ring.send_peers.size());
-    for (size_t i = 0; i < ring.send_peers.size(); i++)
-      put(send[i], sv.data() + ring.send_starts[i], (size_t)(ring.send_starts[i + 1] - ring.send_starts[i]));
-    std::vector<int> from;
-    std::vector<std::vector<char>> got;
-    comm.exchange_host(ring.send_peers, send, from, got);
-    std::vector<T> ext(ring.ids.size());
-    for (size_t i = 0; i < from.size(); i++) {
-      const size_t pi = (size_t)(std::find(ring.recv_peers.begin(), ring.recv_peers.end(), from[i]) - ring.recv_peers.begin());
-      MI_REQUIRE(pi < ring.recv_peers.size(), "distributed setup: unexpected sender");
-      const size_t cnt = (size_t)(ring.recv_starts[pi + 1] - ring.recv_starts[pi]);
-      MI_REQUIRE(got[i].size() == cnt * sizeof(T), "distributed setup: halo message of the wrong size");
-      memcpy(ext.data() + ring.recv_starts[pi], got[i].data(), got[i].size());
-    }
+    const std::vector<T> ext = ring.forward_packed(comm, sv);
     if (nb) MI_HIP(hipMemcpyAsync(vec, ext.data(), (size_t)nb * sizeof(T), hipMemcpyHostToDevice, s));
     if (ne - n - nb) MI_HIP(hipMemcpyAsync(vec + nb + n, ext.data() + nb, (size_t)(ne - n - nb) * sizeof(T), hipMemcpyHostToDevice, s));
     MI_HIP(hipStreamSynchronize(s));
@@ -615,23 +585,69 @@ struct DevHalo {
     if (nb) d2h(ext.data(), vec, (size_t)nb * sizeof(T), s);
     if (ne - n - nb) d2h(ext.data() + nb, vec + nb + n, (size_t)(ne - n - nb) * sizeof(T), s);
     MI_HIP(hipStreamSynchronize(s));
-    std::vector<std::vector<char>> send(ring.recv_peers.size());
-    for (size_t i = 0; i < ring.recv_peers.size(); i++)
-      put(send[i], ext.data() + ring.recv_starts[i], (size_t)(ring.recv_starts[i + 1] - ring.recv_starts[i]));
-    std::vector<int> from;
-    std::vector<std::vector<char>> got;
-    comm.exchange_host(ring.recv_peers, send, from, got);
-    std::vector<T> sv(ring.send_map.size());
-    for (size_t i = 0; i < from.size(); i++) {
-      const size_t pi = (size_t)(std::find(ring.send_peers.begin(), ring.send_peers.end(), from[i]) - ring.send_peers.begin());
-      MI_REQUIRE(pi < ring.send_peers.size(), "distributed setup: unexpected sender");
-      const size_t cnt = (size_t)(ring.send_starts[pi + 1] - ring.send_starts[pi]);
-      MI_REQUIRE(got[i].size() == cnt * sizeof(T), "distributed setup: reverse halo message of the wrong size");
-      memcpy(sv.data() + ring.send_starts[pi], got[i].data(), got[i].size());
-    }
-    at_send.upload(sv);
+    at_send.upload(ring.reverse_packed(comm, ext));
   }
 };
+
+// Transpose exchange of the Galerkin product: the P entries whose coarse column lives on another rank travel to its
+// owner together with the (A P) row of their fine row, so that the owner of a coarse row evaluates R (A P) itself.
+struct Incoming {
+  gidx fine;
+  std::vector<gidx> pc;  // coarse ids (the receiver's)
+  std::vector<double> pv;
+  std::vector<gidx> ac;  // the fine row's (A P) row
+  std::vector<double> av;
+};
+// rows(emit) calls emit(fine global id, P row: global coarse ids (ascending) / values / length, (A P) row: global ids /
+// values / length) for the rows of this rank that may reach other ranks, fine ids ascending; next_starts = the coarse
+// partition.  Returns what the other ranks sent here, sorted by fine id.
+template <class Rows>
+std::vector<Incoming> transpose_exchange(Comm &comm, const std::vector<gidx> &next_starts, Rows rows) {
+  std::vector<std::vector<char>> out((size_t)comm.size);
+  rows([&](gidx fine, const gidx *pc, const double *pv, int64_t np, const gidx *ac, const double *av, int64_t na) {
+    for (int64_t k = 0; k < np;) {
+      const int o = rank_of_id(next_starts, pc[k]);
+      const int64_t k0 = k;
+      while (k < np && pc[k] < next_starts[(size_t)o + 1]) k++;  // columns ascend: one owner's run
+      if (o == comm.rank) continue;
+      std::vector<char> &buf = out[(size_t)o];
+      put1<gidx>(buf, fine);
+      put1<int>(buf, (int)(k - k0));
+      put(buf, pc + k0, (size_t)(k - k0));
+      put(buf, pv + k0, (size_t)(k - k0));
+      put1<int>(buf, (int)na);
+      put(buf, ac, (size_t)na);
+      put(buf, av, (size_t)na);
+    }
+  });
+  std::vector<int> peers, from;
+  std::vector<std::vector<char>> send, got;
+  for (int r = 0; r < comm.size; r++)
+    if (!out[(size_t)r].empty()) {
+      peers.push_back(r);
+      send.emplace_back(std::move(out[(size_t)r]));
+    }
+  comm.exchange_host(peers, send, from, got);
+  std::vector<Incoming> inc;
+  for (auto &buf : got) {
+    Reader rd(buf);
+    while (!rd.done()) {
+      inc.emplace_back();
+      Incoming &in = inc.back();
+      in.fine = rd.get<gidx>();
+      const int np = rd.get<int>();
+      in.pc.resize((size_t)np), in.pv.resize((size_t)np);
+      rd.get(in.pc.data(), (size_t)np);
+      rd.get(in.pv.data(), (size_t)np);
+      const int na = rd.get<int>();
+      in.ac.resize((size_t)na), in.av.resize((size_t)na);
+      rd.get(in.ac.data(), (size_t)na);
+      rd.get(in.av.data(), (size_t)na);
+    }
+  }
+  std::sort(inc.begin(), inc.end(), [](const Incoming &x, const Incoming &y) { return x.fine < y.fine; });
+  return inc;
+}
 
 // sorted unique ids of v outside [lo, hi) appended to `out` (kept sorted unique)
 void merge_outside(const std::vector<gidx> &v, gidx lo, gidx hi, std::vector<gidx> &out) {
@@ -884,13 +900,6 @@ bool dev_level(BoomerAMG &amg, Comm &comm, int level, DevLevel &Lv, std::vector<
   lap("device: A*P");
 
   // ---- transpose exchange: P entries whose coarse column lives elsewhere travel to its owner with the (A P) row
-  struct Incoming {
-    gidx fine;
-    std::vector<gidx> pc;
-    std::vector<double> pv;
-    std::vector<gidx> ac;
-    std::vector<double> av;
-  };
   std::vector<Incoming> inc;
   {
     std::vector<int> brows;
@@ -906,63 +915,16 @@ bool dev_level(BoomerAMG &amg, Comm &comm, int level, DevLevel &Lv, std::vector<
       sp.download(hp, s);
       sa.download(ha, s);
     }
-    std::vector<std::vector<char>> out((size_t)size);
-    std::vector<gidx> pc, acol;
-    std::vector<double> pv;
-    for (int q = 0; q < nbr; q++) {
-      const int i = brows[(size_t)q];
-      const int64_t ab = ha.ia[(size_t)q], alen = ha.ia[(size_t)q + 1] - ab;
-      acol.resize((size_t)alen);
-      for (int64_t k = 0; k < alen; k++) acol[(size_t)k] = CE.global(ha.ja[(size_t)(ab + k)]);
-      int64_t k = hp.ia[(size_t)q];
-      const int64_t ke = hp.ia[(size_t)q + 1];
-      while (k < ke) {
-        const gidx g0 = CE.global(hp.ja[(size_t)k]);
-        const int o = rank_of_id(next_starts, g0);
-        pc.clear(), pv.clear();
-        while (k < ke && CE.global(hp.ja[(size_t)k]) < next_starts[(size_t)o + 1]) {  // columns ascend: one owner's run
-          pc.push_back(CE.global(hp.ja[(size_t)k]));
-          pv.push_back(hp.a[(size_t)k]);
-          k++;
-        }
-        if (o == rank) continue;
-        std::vector<char> &buf = out[(size_t)o];
-        put1<gidx>(buf, gs + i);
-        put1<int>(buf, (int)pc.size());
-        put(buf, pc.data(), pc.size());
-        put(buf, pv.data(), pv.size());
-        put1<int>(buf, (int)alen);
-        put(buf, acol.data(), (size_t)alen);
-        put(buf, ha.a.data() + ab, (size_t)alen);
+    std::vector<gidx> pg(hp.ja.size()), ag(ha.ja.size());  // the downloaded blocks' columns as global coarse ids
+    for (size_t k = 0; k < pg.size(); k++) pg[k] = CE.global(hp.ja[k]);
+    for (size_t k = 0; k < ag.size(); k++) ag[k] = CE.global(ha.ja[k]);
+    inc = transpose_exchange(comm, next_starts, [&](auto emit) {
+      for (int q = 0; q < nbr; q++) {
+        const int64_t pb = hp.ia[(size_t)q], ab = ha.ia[(size_t)q];
+        emit(gs + brows[(size_t)q], pg.data() + pb, hp.a.data() + pb, hp.ia[(size_t)q + 1] - pb, ag.data() + ab, ha.a.data() + ab,
+             ha.ia[(size_t)q + 1] - ab);
       }
-    }
-    std::vector<int> peers;
-    std::vector<std::vector<char>> send;
-    for (int r = 0; r < size; r++)
-      if (!out[(size_t)r].empty()) {
-        peers.push_back(r);
-        send.emplace_back(std::move(out[(size_t)r]));
-      }
-    std::vector<int> from;
-    std::vector<std::vector<char>> got;
-    comm.exchange_host(peers, send, from, got);
-    for (auto &buf : got) {
-      Reader rd(buf);
-      while (!rd.done()) {
-        inc.emplace_back();
-        Incoming &in = inc.back();
-        in.fine = rd.get<gidx>();
-        const int np = rd.get<int>();
-        in.pc.resize((size_t)np), in.pv.resize((size_t)np);
-        rd.get(in.pc.data(), (size_t)np);
-        rd.get(in.pv.data(), (size_t)np);
-        const int na = rd.get<int>();
-        in.ac.resize((size_t)na), in.av.resize((size_t)na);
-        rd.get(in.ac.data(), (size_t)na);
-        rd.get(in.av.data(), (size_t)na);
-      }
-    }
-    std::sort(inc.begin(), inc.end(), [](const Incoming &x, const Incoming &y) { return x.fine < y.fine; });
+    });
   }
   lap("device: transpose exchange");
 
@@ -1127,389 +1089,74 @@ std::unique_ptr<ParCSR> assemble_dev(const sk::DCsr &M, const ExtIndex &cols, co
 }
 
 
-// PMIS on a distributed graph (par_coarsen.c hypre_BoomerAMGCoarsenPMIS; oracle/oracle.c pmis): this rank's rows
-// [starts[rank], starts[rank+1]) with GLOBAL column ids, `strong` = per-entry flag (null: every entry counts), `ring` =
-// the plan over the remote columns, `hslot` = halo slot per entry (-1: own column).  One global random stream indexed
-// by the global row id, so the splitting does not depend on the partition.  Used on the strength graph of a level
-// and on the second-generation graph of an aggressive level.  Leaves cf (0 never; C_PT / F_PT / SF_PT) and the
-// halo copy cf_h.
-void dist_pmis(Comm &comm, const std::vector<gidx> &starts, int n, const std::vector<int64_t> &ia, const std::vector<gidx> &gj,
-               const char *strong, const Ring &ring, const std::vector<int> &hslot, std::vector<int> &cf, std::vector<int> &cf_h,
-               const std::vector<int> *init = nullptr) {
-  const gidx s = starts[(size_t)comm.rank];
-  const int nh = (int)ring.ids.size();
-  cf.assign((size_t)n, 0);
-  // (integer counts and flags below are updated from several host threads with relaxed atomics: sums and
-  // "set to 0" stores commute, so the outcome does not depend on the schedule)
-  std::vector<int> cnt((size_t)n, 0), cnt_h((size_t)nh, 0);
-  parallel_for(n, [&](int64_t b, int64_t en, int) {
-    for (int64_t i = b; i < en; i++)
-      for (int64_t k = ia[(size_t)i]; k < ia[(size_t)i + 1]; k++) {
-        if (strong && !strong[(size_t)k]) continue;
-        int *slot = hslot[(size_t)k] < 0 ? &cnt[(size_t)(gj[(size_t)k] - s)] : &cnt_h[(size_t)hslot[(size_t)k]];
-        __atomic_fetch_add(slot, 1, __ATOMIC_RELAXED);
-      }
-  });
-  ring.reverse(comm, cnt_h, cnt, [](int &mine, int v) { mine += v; });
-  std::vector<double> measure((size_t)n, 0.0);
-  parallel_for(n, [&](int64_t b, int64_t en, int) {
-    if (b >= en) return;
-    int seed = park_miller_at(2747, s + b);  // element s + b of the stream; the following ones by the recurrence
-    for (int64_t i = b; i < en; i++) {
-      if (i > b) {
-        const int a = 16807, m = 2147483647, q = 127773, r = 2836;
-        const int lo = seed % q, hi = seed / q;
-        const int t = a * lo - r * hi;
-        seed = (t > 0) ? t : t + m;
-      }
-      measure[(size_t)i] = (double)cnt[(size_t)i] + (double)seed / 2147483647;
+// The graph view of the coarsening core (hs::pmis / hs::cljp, amg_setup_internal.hpp) for a distributed graph: this
+// rank's rows [starts[rank], starts[rank+1]) with GLOBAL column ids, `strong` = per-entry flag (null: every entry
+// counts), `ring` = the plan over the remote columns, `hslot` = halo slot per entry (-1: own column).  Used on the
+// strength graph of a level and on the second-generation graph of an aggressive level.
+struct DistGraph {
+  static constexpr bool has_halo = true;
+  Comm &comm;
+  const gidx s;
+  const int nrows;
+  const std::vector<int64_t> &ia;
+  const std::vector<gidx> &gj;
+  const char *strong;
+  const Ring &ring;
+  const std::vector<int> &hslot;
+  Ragged<gidx> hrow;  // strong rows of the halo points, global column ids (CLJP)
+  int n() const { return nrows; }
+  int nh() const { return (int)ring.ids.size(); }
+  int64_t nnz() const { return ia.empty() ? 0 : ia[(size_t)nrows]; }
+  gidx first_id() const { return s; }
+  template <class F>
+  bool each(int i, F f) const {
+    for (int64_t k = ia[(size_t)i]; k < ia[(size_t)i + 1]; k++) {
+      if (strong && !strong[(size_t)k]) continue;
+      const int h = hslot[(size_t)k];
+      if (f(k, h < 0 ? (int)(gj[(size_t)k] - s) : -1, h)) return true;
     }
-  });
-  std::vector<int> graph;
-  parallel_for(n, [&](int64_t b, int64_t en, int) {
-    for (int64_t i = b; i < en; i++) {
-      bool any = false, boundary = false;
-      for (int64_t k = ia[(size_t)i]; k < ia[(size_t)i + 1] && !(any && (boundary || !init)); k++) {
-        if (strong && !strong[(size_t)k]) continue;
-        any = true;
-        boundary = boundary || hslot[(size_t)k] >= 0;
-      }
-      if (!any) {
-        cf[(size_t)i] = SF_PT;
-        measure[(size_t)i] = 0.0;
-      } else if (init && (*init)[(size_t)i] == C_PT && !boundary) {
-        // HMIS (CF_init = 1): an interior C point of the per-rank Ruge-Stueben pass is kept; boundary points -- rows
-        // with a strong connection to another rank -- and every F point are decided again by the rounds below
-        cf[(size_t)i] = C_PT;
-        measure[(size_t)i] = 0.0;
-      } else if (measure[(size_t)i] < 1.0) {
-        cf[(size_t)i] = F_PT;
-        measure[(size_t)i] = 0.0;
-      }
-    }
-  });
-  for (int i = 0; i < n; i++)
-    if (cf[(size_t)i] == 0) graph.push_back(i);
-  const std::vector<double> m_h = ring.forward(comm, measure);
-  cf_h = ring.forward(comm, cf);
-  std::vector<signed char> tmp((size_t)n, 0);
-  if (init) {
-    // the kept C points are the first independent set: undecided points that strongly depend on one become F
-    const int64_t ng = (int64_t)graph.size();
-    parallel_for(ng, [&](int64_t b, int64_t en, int) {
-      for (int64_t q = b; q < en; q++) {
-        const int g = graph[(size_t)q];
-        bool dep_c = false;
-        for (int64_t k = ia[(size_t)g]; k < ia[(size_t)g + 1] && !dep_c; k++) {
-          if (strong && !strong[(size_t)k]) continue;
-          const int h = hslot[(size_t)k];
-          dep_c = h < 0 ? cf[(size_t)(gj[(size_t)k] - s)] == C_PT : cf_h[(size_t)h] == C_PT;
-        }
-        tmp[(size_t)g] = dep_c ? 2 : 3;
-      }
-    });
-    std::vector<int> next;
-    for (int g : graph) {
-      if (tmp[(size_t)g] == 2) {
-        cf[(size_t)g] = F_PT;
-        measure[(size_t)g] = 0.0;
-      } else
-        next.push_back(g);
-    }
-    graph.swap(next);
-    cf_h = ring.forward(comm, cf);
+    return false;
   }
-  for (;;) {
-    long long left = (long long)graph.size();
-    comm.allreduce_host(&left, 1, CommDType::I64, CommOp::SUM);
-    if (left == 0) break;
-    std::vector<int> lose_h((size_t)nh, 1);  // 0: the halo point lost a comparison against one of my rows
-    const int64_t ng = (int64_t)graph.size();
-    parallel_for(ng, [&](int64_t b, int64_t en, int) {
-      for (int64_t q = b; q < en; q++) tmp[(size_t)graph[(size_t)q]] = 1;
-    });
-    parallel_for(ng, [&](int64_t b, int64_t en, int) {
-      for (int64_t q = b; q < en; q++) {
-        const int g = graph[(size_t)q];
-        const double mi_ = measure[(size_t)g];
-        bool lost = false;
-        for (int64_t k = ia[(size_t)g]; k < ia[(size_t)g + 1]; k++) {
-          if (strong && !strong[(size_t)k]) continue;
-          const int h = hslot[(size_t)k];
-          if (h < 0) {
-            const int j = (int)(gj[(size_t)k] - s);
-            if (cf[(size_t)j] != 0) continue;
-            if (mi_ > measure[(size_t)j])
-              __atomic_store_n(&tmp[(size_t)j], (signed char)0, __ATOMIC_RELAXED);
-            else if (measure[(size_t)j] > mi_)
-              lost = true;
-          } else {
-            if (cf_h[(size_t)h] != 0) continue;
-            if (mi_ > m_h[(size_t)h])
-              __atomic_store_n(&lose_h[(size_t)h], 0, __ATOMIC_RELAXED);
-            else if (m_h[(size_t)h] > mi_)
-              lost = true;
-          }
-        }
-        if (lost) __atomic_store_n(&tmp[(size_t)g], (signed char)0, __ATOMIC_RELAXED);
-      }
-    });
-    {
-      std::vector<int> keep((size_t)n, 1);
-      ring.reverse(comm, lose_h, keep, [](int &mine, int v) { mine = std::min(mine, v); });
-      parallel_for(ng, [&](int64_t b, int64_t en, int) {
-        for (int64_t q = b; q < en; q++) {
-          const int g = graph[(size_t)q];
-          if (!keep[(size_t)g]) tmp[(size_t)g] = 0;
-          if (tmp[(size_t)g] == 1) cf[(size_t)g] = C_PT;
-        }
-      });
-    }
-    cf_h = ring.forward(comm, cf);
-    parallel_for(ng, [&](int64_t b, int64_t en, int) {
-      for (int64_t q = b; q < en; q++) {
-        const int g = graph[(size_t)q];
-        if (cf[(size_t)g] != 0) continue;
-        bool dep_c = false;
-        for (int64_t k = ia[(size_t)g]; k < ia[(size_t)g + 1] && !dep_c; k++) {
-          if (strong && !strong[(size_t)k]) continue;
-          const int h = hslot[(size_t)k];
-          dep_c = h < 0 ? cf[(size_t)(gj[(size_t)k] - s)] == C_PT : cf_h[(size_t)h] == C_PT;
-        }
-        tmp[(size_t)g] = dep_c ? 2 : 3;  // 2: becomes F once the scan is over (the scan sees this round's C points only)
-      }
-    });
-    std::vector<int> next;
-    for (int g : graph) {
-      if (cf[(size_t)g] != 0) continue;
-      if (tmp[(size_t)g] == 2)
-        cf[(size_t)g] = F_PT;
-      else
-        next.push_back(g);
-    }
-    graph.swap(next);
-    cf_h = ring.forward(comm, cf);
+  template <class T>
+  void forward(const std::vector<T> &local, std::vector<T> &ext) const {
+    ext = ring.forward(comm, local);
   }
-}
-
-
-// CLJP on a distributed graph (par_coarsen.c hypre_BoomerAMGCoarsen; oracle/oracle.c cljp, cljp_from; host form:
-// hs::cljp): w = |S^T_i| + the global random stream; rounds of { independent set of the undecided points -> C;
-// H1: edges out of a new C point leave, w-- at their undecided ends; H2: an undecided row loses its edges to C points,
-// and the edges to undecided points that share one of its C points, w-- there; w < 1 -> F }.  Within a round every
-// step reads what the previous one left and the decrements are integers, so the round is the sequential one whatever
-// the partition: decrements of halo points travel back to their owners, the weights and states of the halo points
-// forward.  The strong rows of the halo points (needed by H2) are fetched once.
-// init (Falgout, coarsen_type 6): INTERIOR rows keep the verdict of the per-rank Ruge-Stueben passes and stop voting
-// (their edges leave before the first selection), BOUNDARY rows -- a strong connection to another rank -- are decided
-// here, H2 runs once with the kept C points (oracle cljp_from).
-void dist_cljp(Comm &comm, const std::vector<gidx> &starts, int n, const std::vector<int64_t> &ia, const std::vector<gidx> &gj,
-               const char *strong, const Ring &ring, const std::vector<int> &hslot, std::vector<int> &cf, std::vector<int> &cf_h,
-               const std::vector<int> *init = nullptr) {
-  const gidx s = starts[(size_t)comm.rank];
-  const int nh = (int)ring.ids.size();
-  auto is_strong = [&](int64_t k) { return !strong || strong[(size_t)k] != 0; };
-  // strong rows of the halo points, global column ids
-  std::vector<int64_t> hoff((size_t)nh + 1, 0);
-  std::vector<gidx> hcol;
-  {
-    const std::vector<std::vector<char>> rec = ring.forward_records(comm, [&](int row, std::vector<char> &buf) {
+  template <class T, class F>
+  void reverse(const std::vector<T> &ext, std::vector<T> &local, F fold) const {
+    ring.reverse(comm, ext, local, fold);
+  }
+  long long global_sum(long long v) const {
+    comm.allreduce_host(&v, 1, CommDType::I64, CommOp::SUM);
+    return v;
+  }
+  // CLJP H2, "do rows i and j share a C point": sorted-list form.  The C points of row i are collected as global ids
+  // (ascending, like the row) and looked up by binary search in the strong row of j -- an own row, or the row of a
+  // halo point fetched once.  (LocalGraph in amg_setup.cpp keeps the marker-array form: on one rank every C point has
+  // a local index to mark, which is cheaper; here it may lie two rings away and has none.)
+  using Marks = std::vector<gidx>;
+  void fetch_strong_halo_rows() {
+    hrow = ring.read_lists<gidx>(ring.forward_records(comm, [&](int row, std::vector<char> &buf) {
       int cnt = 0;
-      for (int64_t k = ia[(size_t)row]; k < ia[(size_t)row + 1]; k++) cnt += is_strong(k);
+      for (int64_t k = ia[(size_t)row]; k < ia[(size_t)row + 1]; k++) cnt += (!strong || strong[(size_t)k]);
       put1<int>(buf, cnt);
       for (int64_t k = ia[(size_t)row]; k < ia[(size_t)row + 1]; k++)
-        if (is_strong(k)) put1<gidx>(buf, gj[(size_t)k]);
-    });
-    for (size_t pi = 0; pi < rec.size(); pi++) {
-      Reader rd(rec[pi]);
-      for (int q = ring.recv_starts[pi]; q < ring.recv_starts[pi + 1]; q++) {
-        const int len = rd.get<int>();
-        hoff[(size_t)q + 1] = len;
-        const size_t o = hcol.size();
-        hcol.resize(o + (size_t)len);
-        rd.get(hcol.data() + o, (size_t)len);
-      }
-    }
-    for (int q = 0; q < nh; q++) hoff[(size_t)q + 1] += hoff[(size_t)q];
+        if (!strong || strong[(size_t)k]) put1<gidx>(buf, gj[(size_t)k]);
+    }));
   }
-  // weights
-  std::vector<int> cnt((size_t)n, 0), cnt_h((size_t)nh, 0);
-  parallel_for(n, [&](int64_t b, int64_t en, int) {
-    for (int64_t i = b; i < en; i++)
-      for (int64_t k = ia[(size_t)i]; k < ia[(size_t)i + 1]; k++) {
-        if (!is_strong(k)) continue;
-        int *slot = hslot[(size_t)k] < 0 ? &cnt[(size_t)(gj[(size_t)k] - s)] : &cnt_h[(size_t)hslot[(size_t)k]];
-        __atomic_fetch_add(slot, 1, __ATOMIC_RELAXED);
-      }
-  });
-  ring.reverse(comm, cnt_h, cnt, [](int &mine, int v) { mine += v; });
-  std::vector<double> measure((size_t)n, 0.0);
-  parallel_for(n, [&](int64_t b, int64_t en, int) {
-    if (b >= en) return;
-    int seed = park_miller_at(2747, s + b);
-    for (int64_t i = b; i < en; i++) {
-      if (i > b) {
-        const int a = 16807, m = 2147483647, q = 127773, r = 2836;
-        const int lo = seed % q, hi = seed / q;
-        const int t = a * lo - r * hi;
-        seed = (t > 0) ? t : t + m;
-      }
-      measure[(size_t)i] = (double)cnt[(size_t)i] + (double)seed / 2147483647;
-    }
-  });
-  const int64_t nnz = ia.empty() ? 0 : ia[(size_t)n];
-  std::vector<char> gone((size_t)nnz, 0), interior((size_t)n, 0);
-  std::vector<int> dec((size_t)n, 0), dec_h((size_t)nh, 0);
-  cf.assign((size_t)n, 0);
-  std::vector<int> graph;
-  for (int i = 0; i < n; i++) {
-    bool any = false, boundary = false;
-    for (int64_t k = ia[(size_t)i]; k < ia[(size_t)i + 1]; k++) {
-      if (!is_strong(k)) continue;
-      any = true;
-      boundary = boundary || hslot[(size_t)k] >= 0;
-    }
-    if (init && !boundary) {
-      interior[(size_t)i] = 1;
-      cf[(size_t)i] = (*init)[(size_t)i];
-    } else if (measure[(size_t)i] < 1.0)
-      cf[(size_t)i] = any ? F_PT : SF_PT;
-    else
-      graph.push_back(i);
-  }
-  cf_h = ring.forward(comm, cf);
-  std::vector<double> m_h = ring.forward(comm, measure);
-  auto dec_end = [&](int64_t k) {  // one decrement at the undecided end of entry k
-    const int h = hslot[(size_t)k];
+  std::vector<Marks> make_marks() const { return std::vector<Marks>((size_t)host_threads()); }
+  void begin_row(Marks &mk, int) const { mk.clear(); }
+  void mark(Marks &mk, int, int64_t k, int) const { mk.push_back(gj[(size_t)k]); }
+  bool shares(const Marks &mk, int, int j, int h) const {
     if (h < 0) {
-      const int j = (int)(gj[(size_t)k] - s);
-      if (cf[(size_t)j] == 0) __atomic_fetch_add(&dec[(size_t)j], 1, __ATOMIC_RELAXED);
-    } else if (cf_h[(size_t)h] == 0)
-      __atomic_fetch_add(&dec_h[(size_t)h], 1, __ATOMIC_RELAXED);
-  };
-  if (init)  // decided points no longer vote (an interior row has no halo ends)
-    parallel_for(n, [&](int64_t b, int64_t en, int) {
-      for (int64_t i = b; i < en; i++) {
-        if (!interior[(size_t)i]) continue;
-        for (int64_t k = ia[(size_t)i]; k < ia[(size_t)i + 1]; k++) {
-          if (!is_strong(k)) continue;
-          gone[(size_t)k] = 1;
-          dec_end(k);
-        }
-      }
-    });
-  std::vector<signed char> tmp((size_t)n, 0);
-  for (int round = init ? 0 : 1;; round++) {
-    if (round > 0) {
-      long long left = (long long)graph.size();
-      comm.allreduce_host(&left, 1, CommDType::I64, CommOp::SUM);
-      if (left == 0) break;
+      for (int64_t kk = ia[(size_t)j]; kk < ia[(size_t)j + 1]; kk++)
+        if ((!strong || strong[(size_t)kk]) && std::binary_search(mk.begin(), mk.end(), gj[(size_t)kk])) return true;
+      return false;
     }
-    const int64_t ng = (int64_t)graph.size();
-    if (round > 0) {
-      std::vector<int> lose_h((size_t)nh, 1);
-      parallel_for(ng, [&](int64_t b, int64_t en, int) {
-        for (int64_t q = b; q < en; q++) tmp[(size_t)graph[(size_t)q]] = 1;
-      });
-      parallel_for(ng, [&](int64_t b, int64_t en, int) {
-        for (int64_t q = b; q < en; q++) {
-          const int g = graph[(size_t)q];
-          const double mi_ = measure[(size_t)g];
-          bool lost = false;
-          for (int64_t k = ia[(size_t)g]; k < ia[(size_t)g + 1]; k++) {
-            if (!is_strong(k)) continue;
-            const int h = hslot[(size_t)k];
-            if (h < 0) {
-              const int j = (int)(gj[(size_t)k] - s);
-              if (cf[(size_t)j] != 0) continue;
-              if (mi_ > measure[(size_t)j])
-                __atomic_store_n(&tmp[(size_t)j], (signed char)0, __ATOMIC_RELAXED);
-              else if (measure[(size_t)j] > mi_)
-                lost = true;
-            } else {
-              if (cf_h[(size_t)h] != 0) continue;
-              if (mi_ > m_h[(size_t)h])
-                __atomic_store_n(&lose_h[(size_t)h], 0, __ATOMIC_RELAXED);
-              else if (m_h[(size_t)h] > mi_)
-                lost = true;
-            }
-          }
-          if (lost) __atomic_store_n(&tmp[(size_t)g], (signed char)0, __ATOMIC_RELAXED);
-        }
-      });
-      std::vector<int> keep((size_t)n, 1);
-      ring.reverse(comm, lose_h, keep, [](int &mine, int v) { mine = std::min(mine, v); });
-      parallel_for(ng, [&](int64_t b, int64_t en, int) {
-        for (int64_t q = b; q < en; q++) {
-          const int g = graph[(size_t)q];
-          if (!keep[(size_t)g]) tmp[(size_t)g] = 0;
-          if (tmp[(size_t)g] == 1) cf[(size_t)g] = C_PT;
-        }
-      });
-      cf_h = ring.forward(comm, cf);
-    }
-    // H1 (rows of this round's C points) and H2 (undecided rows): disjoint rows, decrements collected in dec / dec_h
-    parallel_for(ng, [&](int64_t b, int64_t en, int) {
-      std::vector<gidx> crow;  // C points in the row of i (ascending, like the row)
-      for (int64_t q = b; q < en; q++) {
-        const int i = graph[(size_t)q];
-        if (cf[(size_t)i] == C_PT) {
-          for (int64_t k = ia[(size_t)i]; k < ia[(size_t)i + 1]; k++) {
-            if (!is_strong(k) || gone[(size_t)k]) continue;
-            gone[(size_t)k] = 1;
-            dec_end(k);
-          }
-          continue;
-        }
-        crow.clear();
-        for (int64_t k = ia[(size_t)i]; k < ia[(size_t)i + 1]; k++) {
-          if (!is_strong(k)) continue;
-          const int h = hslot[(size_t)k];
-          if ((h < 0 ? cf[(size_t)(gj[(size_t)k] - s)] : cf_h[(size_t)h]) == C_PT) {
-            gone[(size_t)k] = 1;
-            crow.push_back(gj[(size_t)k]);
-          }
-        }
-        if (crow.empty()) continue;
-        for (int64_t k = ia[(size_t)i]; k < ia[(size_t)i + 1]; k++) {
-          if (!is_strong(k) || gone[(size_t)k]) continue;
-          const int h = hslot[(size_t)k];
-          bool shares = false;
-          if (h < 0) {
-            const int j = (int)(gj[(size_t)k] - s);
-            if (cf[(size_t)j] != 0) continue;
-            for (int64_t kk = ia[(size_t)j]; kk < ia[(size_t)j + 1] && !shares; kk++)
-              shares = is_strong(kk) && std::binary_search(crow.begin(), crow.end(), gj[(size_t)kk]);
-          } else {
-            if (cf_h[(size_t)h] != 0) continue;
-            for (int64_t t = hoff[(size_t)h]; t < hoff[(size_t)h + 1] && !shares; t++)
-              shares = std::binary_search(crow.begin(), crow.end(), hcol[(size_t)t]);
-          }
-          if (shares) {
-            gone[(size_t)k] = 1;
-            dec_end(k);
-          }
-        }
-      }
-    });
-    ring.reverse(comm, dec_h, dec, [](int &mine, int v) { mine += v; });
-    std::fill(dec_h.begin(), dec_h.end(), 0);
-    std::vector<int> next;
-    next.reserve(graph.size());
-    for (int64_t q = 0; q < ng; q++) {
-      const int i = graph[(size_t)q];
-      if (cf[(size_t)i] == C_PT) continue;
-      for (; dec[(size_t)i] > 0; dec[(size_t)i]--) measure[(size_t)i] -= 1.0;  // one at a time, as the oracle does
-      if (measure[(size_t)i] < 1.0)
-        cf[(size_t)i] = F_PT;
-      else
-        next.push_back(i);
-    }
-    graph.swap(next);
-    cf_h = ring.forward(comm, cf);
-    m_h = ring.forward(comm, measure);
+    for (int64_t t = hrow.off[(size_t)h]; t < hrow.off[(size_t)h + 1]; t++)
+      if (std::binary_search(mk.begin(), mk.end(), hrow.items[(size_t)t])) return true;
+    return false;
   }
-}
+};
 
 // Coarsening of a distributed graph by type.  8 / 9: PMIS.  The types HYPRE defines PER PROCESSOR (par_coarsen.c
 // hypre_BoomerAMGCoarsenRuge / ...HMIS; oracle/oracle.c coarsen_by_type_parts): 11 = first Ruge-Stueben pass and 1 = both
@@ -1519,16 +1166,17 @@ void dist_cljp(Comm &comm, const std::vector<gidx> &starts, int n, const std::ve
 void dist_coarsen(Comm &comm, int type, const std::vector<gidx> &starts, int n, const std::vector<int64_t> &ia,
                   const std::vector<gidx> &gj, const char *strong, const Ring &ring, const std::vector<int> &hslot,
                   std::vector<int> &cf, std::vector<int> &cf_h) {
+  const gidx s = starts[(size_t)comm.rank];
+  DistGraph g{comm, s, n, ia, gj, strong, ring, hslot, {}};
   if (type == 8 || type == 9) {
-    dist_pmis(comm, starts, n, ia, gj, strong, ring, hslot, cf, cf_h);
+    pmis(g, cf, cf_h);
     return;
   }
   if (type == 0 || type == 7) {  // CLJP: a global algorithm whose rounds commute -- the same splitting on any partition
-    dist_cljp(comm, starts, n, ia, gj, strong, ring, hslot, cf, cf_h);
+    cljp(g, cf, cf_h);
     return;
   }
   MI_REQUIRE(type == 10 || type == 11 || type == 1 || type == 6, "distributed setup: coarsening type without a distributed form");
-  const gidx s = starts[(size_t)comm.rank];
   Strength Sl;
   Sl.ia.assign((size_t)n + 1, 0);
   for (int i = 0; i < n; i++) {
@@ -1547,9 +1195,9 @@ void dist_coarsen(Comm &comm, int type, const std::vector<gidx> &starts, int n, 
   std::vector<int> cf0;
   if (n > 0) ruge_stueben(n, Sl, type == 1 || type == 6, cf0);
   if (type == 10) {
-    dist_pmis(comm, starts, n, ia, gj, strong, ring, hslot, cf, cf_h, &cf0);
+    pmis(g, cf, cf_h, &cf0);
   } else if (type == 6) {  // Falgout: CLJP on the boundary from the interior verdicts
-    dist_cljp(comm, starts, n, ia, gj, strong, ring, hslot, cf, cf_h, &cf0);
+    cljp(g, cf, cf_h, &cf0);
   } else {
     cf.swap(cf0);
     cf_h = ring.forward(comm, cf);
@@ -1568,7 +1216,6 @@ void dist_second_stage(Comm &comm, int type, const std::vector<gidx> &starts, co
   const int rank = comm.rank, size = comm.size;
   const int n = A.nrows;
   const gidx s = starts[(size_t)rank];
-  const int nh = (int)ring.ids.size();
   long long nc1 = 0;
   for (int i = 0; i < n; i++) nc1 += (cf[(size_t)i] == C_PT);
   std::vector<gidx> st1((size_t)size + 1, 0);
@@ -1594,28 +1241,13 @@ void dist_second_stage(Comm &comm, int type, const std::vector<gidx> &starts, co
     return h < 0 ? cg1[(size_t)(A.gj[(size_t)k] - s)] : cg1_h[(size_t)h];
   };
   // the strong C neighbours of every halo point, as first-stage coarse ids
-  std::vector<int64_t> hoff((size_t)nh + 1, 0);
-  std::vector<gidx> hl;
-  {
-    const std::vector<std::vector<char>> rec = ring.forward_records(comm, [&](int row, std::vector<char> &buf) {
-      int cnt = 0;
-      for (int64_t k = A.ia[(size_t)row]; k < A.ia[(size_t)row + 1]; k++) cnt += (strong[(size_t)k] && cg_of(k) >= 0);
-      put1<int>(buf, cnt);
-      for (int64_t k = A.ia[(size_t)row]; k < A.ia[(size_t)row + 1]; k++)
-        if (strong[(size_t)k] && cg_of(k) >= 0) put1<gidx>(buf, cg_of(k));
-    });
-    for (size_t pi = 0; pi < rec.size(); pi++) {
-      Reader rd(rec[pi]);
-      for (int q = ring.recv_starts[pi]; q < ring.recv_starts[pi + 1]; q++) {
-        const int len = rd.get<int>();
-        hoff[(size_t)q + 1] = len;
-        const size_t o = hl.size();
-        hl.resize(o + (size_t)len);
-        rd.get(hl.data() + o, (size_t)len);
-      }
-    }
-    for (int q = 0; q < nh; q++) hoff[(size_t)q + 1] += hoff[(size_t)q];
-  }
+  const Ragged<gidx> hl = ring.read_lists<gidx>(ring.forward_records(comm, [&](int row, std::vector<char> &buf) {
+    int cnt = 0;
+    for (int64_t k = A.ia[(size_t)row]; k < A.ia[(size_t)row + 1]; k++) cnt += (strong[(size_t)k] && cg_of(k) >= 0);
+    put1<int>(buf, cnt);
+    for (int64_t k = A.ia[(size_t)row]; k < A.ia[(size_t)row + 1]; k++)
+      if (strong[(size_t)k] && cg_of(k) >= 0) put1<gidx>(buf, cg_of(k));
+  }));
   // rows of the second-generation graph: sorted global coarse ids, the point itself left out
   GlobCSR G;
   G.nrows = (int)nc1;
@@ -1639,8 +1271,8 @@ void dist_second_stage(Comm &comm, int type, const std::vector<gidx> &starts, co
             if (g2 >= 0 && g2 != me) row.push_back(g2);
           }
         } else {
-          for (int64_t t = hoff[(size_t)h]; t < hoff[(size_t)h + 1]; t++)
-            if (hl[(size_t)t] != me) row.push_back(hl[(size_t)t]);
+          for (int64_t t = hl.off[(size_t)h]; t < hl.off[(size_t)h + 1]; t++)
+            if (hl.items[(size_t)t] != me) row.push_back(hl.items[(size_t)t]);
         }
       }
       std::sort(row.begin(), row.end());
@@ -1811,19 +1443,16 @@ void dist_multipass(Comm &comm, const std::vector<gidx> &starts, const GlobCSR &
       put(buf, pool_v.data() + rstart[(size_t)row], (size_t)len);
     });
     hpool_c.clear(), hpool_v.clear();
-    for (size_t pi = 0; pi < rec.size(); pi++) {
-      Reader rd(rec[pi]);
-      for (int q = ring.recv_starts[pi]; q < ring.recv_starts[pi + 1]; q++) {
-        const int len = rd.get<int>();
-        const size_t o = hpool_c.size();
-        hstart[(size_t)q] = (int64_t)o;
-        hlen[(size_t)q] = len;
-        hpool_c.resize(o + (size_t)len);
-        hpool_v.resize(o + (size_t)len);
-        rd.get(hpool_c.data() + o, (size_t)len);
-        rd.get(hpool_v.data() + o, (size_t)len);
-      }
-    }
+    ring.each_record(rec, [&](int q, Reader &rd) {
+      const int len = rd.get<int>();
+      const size_t o = hpool_c.size();
+      hstart[(size_t)q] = (int64_t)o;
+      hlen[(size_t)q] = len;
+      hpool_c.resize(o + (size_t)len);
+      hpool_v.resize(o + (size_t)len);
+      rd.get(hpool_c.data() + o, (size_t)len);
+      rd.get(hpool_v.data() + o, (size_t)len);
+    });
   }
   // truncation and sort row by row (in place in the pool), then compaction into P
   std::vector<int> flen((size_t)n, 0);
@@ -2070,29 +1699,12 @@ void BoomerAMG::build_distributed(ParCSR &A0) {
     Lv.strong.assign((size_t)A.nnz(), 0);
     parallel_for(n, [&](int64_t b, int64_t en, int) {
       for (int64_t i = b; i < en; i++) {
-        const gidx gi = s + i;
-        double diag = 0.0, row_sum = 0.0, scale = 0.0;
-        for (int64_t k = A.ia[(size_t)i]; k < A.ia[(size_t)i + 1]; k++) {
-          row_sum += A.a[(size_t)k];
-          if (A.gj[(size_t)k] == gi) diag = A.a[(size_t)k];
-        }
-        for (int64_t k = A.ia[(size_t)i]; k < A.ia[(size_t)i + 1]; k++) {
-          if (A.gj[(size_t)k] == gi) continue;
-          const double v = A.a[(size_t)k];
-          if (diag < 0) {
-            if (v > scale) scale = v;
-          } else {
-            if (v < scale) scale = v;
-          }
-        }
-        const bool all_weak = (std::fabs(row_sum) > std::fabs(diag) * p.max_row_sum) && (p.max_row_sum < 1.0);
-        if (all_weak) continue;
-        const double thr = p.strong_threshold * scale;
-        for (int64_t k = A.ia[(size_t)i]; k < A.ia[(size_t)i + 1]; k++) {
-          if (A.gj[(size_t)k] == gi) continue;
-          const double v = A.a[(size_t)k];
-          if ((diag < 0) ? (v > thr) : (v < thr)) Lv.strong[(size_t)k] = 1;
-        }
+        const int64_t r0 = A.ia[(size_t)i], r1 = A.ia[(size_t)i + 1];
+        int64_t dpos = -1;
+        for (int64_t k = r0; k < r1; k++)
+          if (A.gj[(size_t)k] == s + i) dpos = k;
+        const StrengthRule rule = strength_rule(A.a.data() + r0, r1 - r0, dpos < 0 ? -1 : dpos - r0, p.strong_threshold, p.max_row_sum);
+        for (int64_t k = r0; k < r1; k++) Lv.strong[(size_t)k] = (k != dpos && rule(A.a[(size_t)k]));
       }
     });
     // halo of A
@@ -2186,23 +1798,20 @@ void BoomerAMG::build_distributed(ParCSR &A0) {
       ExtIndex X;
       X.s = s, X.e = e;
       X.remote = ring.ids;
-      for (size_t pi = 0; pi < hrows.size(); pi++) {
-        Reader rd(hrows[pi]);
-        for (int q = ring.recv_starts[pi]; q < ring.recv_starts[pi + 1]; q++) {
-          HRow &hr = H[(size_t)q];
-          const int len = rd.get<int>();
-          hr.col.resize((size_t)len), hr.val.resize((size_t)len), hr.strong.resize((size_t)len);
-          hr.cfc.resize((size_t)len), hr.cg.resize((size_t)len);
-          rd.get(hr.col.data(), (size_t)len);
-          rd.get(hr.val.data(), (size_t)len);
-          rd.get(hr.strong.data(), (size_t)len);
-          for (int k = 0; k < len; k++) {
-            hr.cfc[(size_t)k] = rd.get<int>();
-            hr.cg[(size_t)k] = rd.get<gidx>();
-            if (hr.col[(size_t)k] < s || hr.col[(size_t)k] >= e) X.remote.push_back(hr.col[(size_t)k]);
-          }
+      ring.each_record(hrows, [&](int q, Reader &rd) {
+        HRow &hr = H[(size_t)q];
+        const int len = rd.get<int>();
+        hr.col.resize((size_t)len), hr.val.resize((size_t)len), hr.strong.resize((size_t)len);
+        hr.cfc.resize((size_t)len), hr.cg.resize((size_t)len);
+        rd.get(hr.col.data(), (size_t)len);
+        rd.get(hr.val.data(), (size_t)len);
+        rd.get(hr.strong.data(), (size_t)len);
+        for (int k = 0; k < len; k++) {
+          hr.cfc[(size_t)k] = rd.get<int>();
+          hr.cg[(size_t)k] = rd.get<gidx>();
+          if (hr.col[(size_t)k] < s || hr.col[(size_t)k] >= e) X.remote.push_back(hr.col[(size_t)k]);
         }
-      }
+      });
       std::vector<std::vector<char>>().swap(hrows);
       lap("interp: unpack halo rows");
       sort_unique(X.remote);
@@ -2367,15 +1976,12 @@ void BoomerAMG::build_distributed(ParCSR &A0) {
       Pe.ia.assign((size_t)n1 + 1, 0);
       std::vector<std::vector<gidx>> hc((size_t)nh);
       std::vector<std::vector<double>> hv((size_t)nh);
-      for (size_t pi = 0; pi < prow.size(); pi++) {
-        Reader rd(prow[pi]);
-        for (int q = ring.recv_starts[pi]; q < ring.recv_starts[pi + 1]; q++) {
-          const int len = rd.get<int>();
-          hc[(size_t)q].resize((size_t)len), hv[(size_t)q].resize((size_t)len);
-          rd.get(hc[(size_t)q].data(), (size_t)len);
-          rd.get(hv[(size_t)q].data(), (size_t)len);
-        }
-      }
+      ring.each_record(prow, [&](int q, Reader &rd) {
+        const int len = rd.get<int>();
+        hc[(size_t)q].resize((size_t)len), hv[(size_t)q].resize((size_t)len);
+        rd.get(hc[(size_t)q].data(), (size_t)len);
+        rd.get(hv[(size_t)q].data(), (size_t)len);
+      });
       lap("galerkin: unpack P rows");
       // coarse columns of the extended P: my whole coarse range plus the remote ids that occur (ascending global
       // order, as in the single-rank product)
@@ -2443,69 +2049,13 @@ void BoomerAMG::build_distributed(ParCSR &A0) {
     lap("galerkin: A*P to global ids");
     // transpose exchange: P entries whose coarse column lives elsewhere travel to its owner together with the
     // (A P) row of their fine row
-    struct Incoming {
-      gidx fine;
-      std::vector<gidx> pc;  // coarse ids (mine)
-      std::vector<double> pv;
-      std::vector<gidx> ac;  // the fine row's (A P) row
-      std::vector<double> av;
-    };
-    std::vector<Incoming> inc;
-    {
-      std::vector<std::vector<char>> out((size_t)size);
-      std::vector<gidx> pc;
-      std::vector<double> pv;
+    const std::vector<Incoming> inc = transpose_exchange(comm, Ln.starts, [&](auto emit) {
       for (int i = 0; i < n; i++) {
-        int64_t k = P.ia[(size_t)i];
-        const int64_t ke = P.ia[(size_t)i + 1];
-        while (k < ke) {
-          const int o = rank_of_id(Ln.starts, P.gj[(size_t)k]);
-          pc.clear(), pv.clear();
-          while (k < ke && P.gj[(size_t)k] < Ln.starts[(size_t)o + 1]) {  // columns ascend: one owner's run
-            pc.push_back(P.gj[(size_t)k]);
-            pv.push_back(P.a[(size_t)k]);
-            k++;
-          }
-          if (o == rank) continue;
-          std::vector<char> &buf = out[(size_t)o];
-          put1<gidx>(buf, s + i);
-          put1<int>(buf, (int)pc.size());
-          put(buf, pc.data(), pc.size());
-          put(buf, pv.data(), pv.size());
-          const int64_t ab = AP.ia[(size_t)i], alen = AP.ia[(size_t)i + 1] - ab;
-          put1<int>(buf, (int)alen);
-          put(buf, AP.gj.data() + ab, (size_t)alen);
-          put(buf, AP.a.data() + ab, (size_t)alen);
-        }
+        const int64_t pb = P.ia[(size_t)i], ab = AP.ia[(size_t)i];
+        emit(s + i, P.gj.data() + pb, P.a.data() + pb, P.ia[(size_t)i + 1] - pb, AP.gj.data() + ab, AP.a.data() + ab,
+             AP.ia[(size_t)i + 1] - ab);
       }
-      std::vector<int> peers;
-      std::vector<std::vector<char>> send;
-      for (int r = 0; r < size; r++)
-        if (!out[(size_t)r].empty()) {
-          peers.push_back(r);
-          send.emplace_back(std::move(out[(size_t)r]));
-        }
-      std::vector<int> from;
-      std::vector<std::vector<char>> got;
-      comm.exchange_host(peers, send, from, got);
-      for (auto &buf : got) {
-        Reader rd(buf);
-        while (!rd.done()) {
-          inc.emplace_back();
-          Incoming &in = inc.back();
-          in.fine = rd.get<gidx>();
-          const int np = rd.get<int>();
-          in.pc.resize((size_t)np), in.pv.resize((size_t)np);
-          rd.get(in.pc.data(), (size_t)np);
-          rd.get(in.pv.data(), (size_t)np);
-          const int na = rd.get<int>();
-          in.ac.resize((size_t)na), in.av.resize((size_t)na);
-          rd.get(in.ac.data(), (size_t)na);
-          rd.get(in.av.data(), (size_t)na);
-        }
-      }
-      std::sort(inc.begin(), inc.end(), [](const Incoming &x, const Incoming &y) { return x.fine < y.fine; });
-    }
+    });
     lap("galerkin: transpose exchange");
     {
       const int ncl = (int)nc_loc;
