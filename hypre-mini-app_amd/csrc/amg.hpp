@@ -239,14 +239,33 @@ struct BoomerAMG {
   }
   static long long default_device_min_rows();
 
-  void setup(ParCSR &A) {
-    host_only = false;
-    device_min_rows = default_device_min_rows();
-    setup_host(A);
-    setup_device();
-    source_matrix = &A;
-    source_stamp = A.assembly_stamp;
-  }
+  // ---- setup reuse (HYPRE_MI_BoomerAMGSetSetupReuse; DESIGN.md section 3, "Setup reuse"): with mode 1 a Setup on a
+  // handle that holds a finished hierarchy of the same matrix object and pattern, built by the same entry point with
+  // the same structural settings, keeps the splittings, orderings, P, R and every pattern and recomputes the values
+  int setup_reuse = 0;
+  // the verdict of the last Setup: kind 0 never set up, 1 built from scratch, 2 refreshed; reason (kind 1): 0 reuse off,
+  // 1 first Setup or the previous one failed, 2 another matrix object or pattern, 3 a structural setting changed, 4 a
+  // setting the refresh does not cover, 5 more than one rank, 6 the other entry point built the hierarchy
+  int setup_kind = 0, setup_reason = 0;
+  bool built_ok = false, built_host_only = false;  // a finished hierarchy, and the entry point that built it
+  const ParCSR *built_matrix = nullptr;
+  unsigned long long built_pattern = 0;
+  // everything the structure depends on, at the last build
+  std::vector<double> structure_signature;
+  std::vector<double> current_structure_signature(const ParCSR &A) const;
+  int refresh_verdict(const ParCSR &A, bool entry_host_only) const;  // -1: refresh; else the reason of the rebuild
+  // both entry points: refresh or rebuild, verdict, counters, print
+  void setup_entry(ParCSR &A, bool entry_host_only);
+  void validate_settings() const;  // the settings a Setup refuses, checked before a build and before a refresh
+  void build_from_scratch(ParCSR &A, bool entry_host_only);
+  void refresh(ParCSR &A);
+  void refresh_level0(ParCSR &A);
+  void refresh_coarse_operator(int level, double *seconds);  // A_{level+1} from A, P, R of `level`
+  void refresh_norms_and_sub_operators(int level);
+  void build_coarsest_inverse();  // relax type 9: dense inverse of the coarsest level (host)
+  void upload_coarsest_inverse();
+
+  void setup(ParCSR &A) { setup_entry(A, false); }
   // hierarchy construction: host only (threads + host collectives)
   void setup_host(ParCSR &A);
   void build_natural(ParCSR &A);      // strength / PMIS / interpolation / Galerkin loop, natural ordering
@@ -313,6 +332,10 @@ bool &zero_guess_hint();
 // gathered on every rank (the redundant tail only), number of distributed setups; -1 = unknown name
 long long dist_setup_counter(const char *name);
 void dist_setup_counters_reset();
+// Setups of this process that built from scratch / refreshed ("amg_setups_full", "amg_setups_refreshed"); -1 = unknown name
+long long setup_reuse_counter(const char *name);
+// the reason of a rebuild in words (HYPRE_MI_BoomerAMGGetSetupKind's reasons 0 ... 6; HYPRE_MI_SetupReuseReasonText)
+const char *setup_reuse_reason_text(int reason);
 
 // host algorithms (amg_setup.cpp), exposed for tests
 void host_transpose(const HostCSR &A, HostCSR &T);

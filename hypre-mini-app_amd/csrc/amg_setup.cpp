@@ -1565,14 +1565,8 @@ bool BoomerAMG::use_locality_order(const ParCSR &A) const {
   return rows >= min_rows;
 }
 
-void BoomerAMG::setup_host(ParCSR &A0) {
-  TraceRange trace_setup("mi_hypre BoomerAMGSetup (hierarchy)");
-  Comm &comm = my_comm();
-  t_setup_start = wall_time();
-  for (double &t : t_phase) t = 0.0;
-  is_setup = false;
-  host_ready = false;
-  MI_REQUIRE(!A0.row_starts.empty(), "BoomerAMGSetup: matrix is not assembled");
+// What a Setup refuses before it builds or refreshes anything: settings that are not implemented (never a substitute)
+void BoomerAMG::validate_settings() const {
   if (!coarsen_type_restated(p.coarsen_type))
     fail(4, "BoomerAMGSetup: coarsen_type " + std::to_string(p.coarsen_type) +
                 " is not implemented (8 PMIS, 10 HMIS, 11, 6 Falgout, 1, 3, 0 CLJP, 7 are); refusing to substitute another one");
@@ -1632,6 +1626,17 @@ void BoomerAMG::setup_host(ParCSR &A0) {
                 std::to_string(p.ilu_level) + ", option " + std::to_string(p.ilu_iter_option) + ", max iterations " +
                 std::to_string(p.ilu_iter_max_iter) +
                 " is not implemented (types 0 ... 4 with ILU(0), option bits 1 ... 32, max iterations >= 1 are)");
+}
+
+void BoomerAMG::setup_host(ParCSR &A0) {
+  TraceRange trace_setup("mi_hypre BoomerAMGSetup (hierarchy)");
+  Comm &comm = my_comm();
+  t_setup_start = wall_time();
+  for (double &t : t_phase) t = 0.0;
+  is_setup = false;
+  host_ready = false;
+  MI_REQUIRE(!A0.row_starts.empty(), "BoomerAMGSetup: matrix is not assembled");
+  validate_settings();
   if (device_min_rows >= 0) dev_arena_hint((size_t)13 * 12 * (size_t)(A0.diag_nnz() + A0.offd.nnz()));
   if (comm.size > 1) input_order.clear();
   if (comm.size > 1 && can_build_distributed()) {
@@ -2006,9 +2011,13 @@ void BoomerAMG::finish_host() {
     if (Lv.has_cf) cf_ext = A.halo_exchange_host_int(comm, Lv.cf.host());  // collective: gated by the global flag
     level_norms(A, Lv.cf.host(), cf_ext, ch, Lv.diag, Lv.l1gs, Lv.l1jac);
   }
-  ensure_host((int)L.size() - 1);
+  build_coarsest_inverse();
+}
 
-  // coarsest level: dense inverse (relax type 9), every rank holds its own rows
+// coarsest level: dense inverse (relax type 9), every rank holds its own rows
+void BoomerAMG::build_coarsest_inverse() {
+  Comm &comm = my_comm();
+  ensure_host((int)L.size() - 1);
   AmgLevel &Lc = L.back();
   const gidx ng = Lc.A->global_rows();
   if (!tail && p.relax_type[2] == 9 && ng <= MAX_DENSE && ng > 0) {
@@ -2856,15 +2865,7 @@ void BoomerAMG::setup_device() {
   }
   build_smoothers();
   apply_value_storage(true);  // after everything Setup derives from the operators as built
-  AmgLevel &Lc = L.back();
-  if (Lc.dense) {
-    const size_t width = (size_t)comm.size * (size_t)Lc.slot;
-    Lc.Cinv.upload(Lc.Cinv_host);
-    Lc.fgather.alloc(width);
-    Lc.fslot.alloc((size_t)Lc.slot);
-    zero_on_stream(Lc.fslot.p, ((size_t)Lc.slot + 2) * sizeof(double));
-    zero_on_stream(Lc.fgather.p, (width + 2) * sizeof(double));
-  }
+  upload_coarsest_inverse();
   if (tail) {
     tail->setup_device();
     const size_t ng = (size_t)tail_A->nrows;
@@ -2924,6 +2925,275 @@ void BoomerAMG::setup_device() {
              (long long)Lv.A->global_rows(), (long long)(Lv.A->diag_nnz() + Lv.A->offd.nnz()),
              &o != this ? "  (whole level on every rank)" : "");
     }
+  }
+}
+
+void BoomerAMG::upload_coarsest_inverse() {
+  AmgLevel &Lc = L.back();
+  if (!Lc.dense) return;
+  const size_t width = (size_t)my_comm().size * (size_t)Lc.slot;
+  if (Lc.Cinv.p && Lc.Cinv.n == Lc.Cinv_host.size() && Lc.fgather.n == width && Lc.fslot.n == (size_t)Lc.slot) {
+    // a refresh: the buffers of the build take the new inverse (the gather buffers hold nothing between cycles)
+    if (!Lc.Cinv_host.empty()) Lc.Cinv.upload(Lc.Cinv_host.data(), Lc.Cinv_host.size());
+    return;
+  }
+  Lc.Cinv.upload(Lc.Cinv_host);
+  Lc.fgather.alloc(width);
+  Lc.fslot.alloc((size_t)Lc.slot);
+  zero_on_stream(Lc.fslot.p, ((size_t)Lc.slot + 2) * sizeof(double));
+  zero_on_stream(Lc.fgather.p, (width + 2) * sizeof(double));
+}
+
+// ------------------------------------------------------------------ setup reuse ("Setup reuse")
+namespace {
+long long g_setups_full = 0, g_setups_refreshed = 0;
+const char *const REBUILD_REASON[7] = {"reuse is off",
+                                       "first Setup of this handle, or the previous one failed",
+                                       "another matrix object or another pattern",
+                                       "a setting the structure depends on changed since the last Setup",
+                                       "a setting the refresh does not cover is on (non-Galerkin tolerances or value storage)",
+                                       "more than one rank",
+                                       "the other setup entry point built the hierarchy"};
+}  // namespace
+
+const char *setup_reuse_reason_text(int reason) { return reason >= 0 && reason < 7 ? REBUILD_REASON[reason] : "unknown reason"; }
+
+long long setup_reuse_counter(const char *name) {
+  const std::string n(name ? name : "");
+  return n == "amg_setups_full" ? g_setups_full : n == "amg_setups_refreshed" ? g_setups_refreshed : -1;
+}
+
+// Everything the kept part of a hierarchy depends on: the splittings and P (coarsening, interpolation, truncation, level
+// limits, aggressive settings), the orderings (locality numbering), the sub-operators' patterns (GS chunk, zero-guess
+// mode, whether the down smoother is of the Gauss-Seidel family), what exists besides (coarsest dense inverse, value
+// dictionaries, value storage, non-Galerkin sparsification) and which levels the device built.
+std::vector<double> BoomerAMG::current_structure_signature(const ParCSR &A) const {
+  std::vector<double> v = {(double)p.coarsen_type, (double)p.interp_type, p.strong_threshold, p.max_row_sum, p.trunc_factor,
+                           (double)p.pmax_elmts, (double)p.max_levels, (double)p.max_coarse_size, (double)p.min_coarse_size,
+                           (double)p.agg_num_levels, (double)p.agg_interp_type, (double)p.agg_pmax_elmts, p.agg_trunc_factor,
+                           (double)p.agg_p12_max_elmts, p.agg_p12_trunc_factor, (double)p.keep_agg_markers,
+                           use_locality_order(A) ? 1.0 : 0.0, (double)chunk(), (double)zero_skip_mode(),
+                           k::value_dictionary_enabled() ? 1.0 : 0.0, (double)p.value_storage, (double)p.value_first_level,
+                           p.non_galerkin_tol};
+  for (double t : p.non_galerkin_level_tol) v.push_back(t);
+  const int t0 = p.relax_type[0];
+  v.push_back((t0 == 3 || t0 == 4 || t0 == 6 || t0 == 8 || t0 == 13 || t0 == 14) ? 1.0 : 0.0);
+  v.push_back(p.relax_type[2] == 9 ? 1.0 : 0.0);
+  v.push_back((double)default_device_min_rows());
+  return v;
+}
+
+int BoomerAMG::refresh_verdict(const ParCSR &A, bool entry_host_only) const {
+  if (setup_reuse == 0) return 0;
+  if (!built_ok || L.empty()) return 1;
+  if (my_comm().size > 1) return 5;
+  if (built_host_only != entry_host_only) return 6;
+  if (built_matrix != &A || built_pattern != A.pattern_stamp) return 2;
+  if (p.non_galerkin() || p.value_storage != 0) return 4;
+  if (structure_signature != current_structure_signature(A)) return 3;
+  return -1;
+}
+
+void BoomerAMG::build_from_scratch(ParCSR &A, bool entry_host_only) {
+  host_only = entry_host_only;
+  if (entry_host_only) {
+    device_min_rows = -1;  // host threads only
+    setup_host(A);
+    apply_value_storage(false);
+    if (tail) tail->apply_value_storage(false);
+  } else {
+    device_min_rows = default_device_min_rows();
+    setup_host(A);
+    setup_device();
+  }
+}
+
+void BoomerAMG::setup_entry(ParCSR &A, bool entry_host_only) {
+  const int verdict = refresh_verdict(A, entry_host_only);
+  built_ok = false;  // a Setup that fails leaves the handle not set up: the next one rebuilds (reason 1)
+  if (verdict < 0) {
+    is_setup = false;
+    host_ready = false;
+    host_only = entry_host_only;
+    validate_settings();  // cycle settings may have changed since the build: what a full Setup refuses is refused here too
+    refresh(A);
+    setup_kind = 2, setup_reason = 0;
+    g_setups_refreshed++;
+  } else {
+    build_from_scratch(A, entry_host_only);
+    setup_kind = 1, setup_reason = verdict;
+    g_setups_full++;
+    built_host_only = entry_host_only;
+    built_matrix = &A;
+    built_pattern = A.pattern_stamp;
+    structure_signature = current_structure_signature(A);
+  }
+  built_ok = true;
+  if (!entry_host_only) {
+    source_matrix = &A;
+    source_stamp = A.assembly_stamp;
+  }
+  if (p.print_level > 0 && my_comm().rank == 0 && setup_reuse != 0) {
+    if (setup_kind == 2)
+      printf("mi_hypre BoomerAMG setup: refreshed (values on the kept structure), %.3f s\n", setup_seconds);
+    else
+      printf("mi_hypre BoomerAMG setup: rebuilt from scratch: %s\n", REBUILD_REASON[setup_reason]);
+  }
+}
+
+namespace {
+// stored entry (r, c) of D takes the caller's entry (perm[r], perm[c]); false (and the row) when the caller has none
+bool host_value_lookup(HostCSR &D, const std::vector<int> &perm, const HostCSR &S, int &bad_row) {
+  std::vector<double> a((size_t)D.nnz());
+  std::atomic<int> bad{INT_MAX};
+  parallel_for(D.nrows, [&](int64_t b, int64_t e, int) {
+    for (int64_t r = b; r < e; r++) {
+      const int sr = perm[(size_t)r];
+      const int *s0 = S.ja.data() + S.ia[(size_t)sr], *s1 = S.ja.data() + S.ia[(size_t)sr + 1];
+      for (int64_t k = D.ia[(size_t)r]; k < D.ia[(size_t)r + 1]; k++) {
+        const int sc = perm[(size_t)D.ja[(size_t)k]];
+        const int *q = std::lower_bound(s0, s1, sc);
+        if (q == s1 || *q != sc) {
+          int cur = bad.load();
+          while ((int)r < cur && !bad.compare_exchange_weak(cur, (int)r)) {
+          }
+          continue;
+        }
+        a[(size_t)k] = S.a[(size_t)(q - S.ja.data())];
+      }
+    }
+  });
+  bad_row = bad.load();
+  if (bad_row != INT_MAX) return false;
+  D.a.swap(a);
+  return true;
+}
+
+void values_to_host(const DevCSR &D, HostCSR &H, hipStream_t s) {
+  MI_REQUIRE((int64_t)H.a.size() == D.nnz, "setup reuse: host and device copies of an operator differ in size");
+  if (D.nnz) d2h(H.a.data(), D.a.p, (size_t)D.nnz * sizeof(double), s);
+}
+}  // namespace
+
+// step 1: the hierarchy's own copy of the caller's matrix (internal numbering, then C-first) takes the new values
+void BoomerAMG::refresh_level0(ParCSR &A0) {
+  AmgLevel &L0 = L[0];
+  if (L0.A == &A0) return;  // no copy: level 0 is the caller's matrix itself
+  ParCSR &A = *L0.A;
+  MI_REQUIRE(L0.perm.size() == (size_t)A0.nrows && A.nrows == A0.nrows, "setup reuse: level 0 has no permutation of the caller's rows");
+  const std::string where = "BoomerAMGSetup (refresh): level 0: internal error: the caller's matrix has no entry for a stored one (row ";
+  if (!host_only && A0.on_device && A0.d_diag.a.p) {
+    hipStream_t s = ctx().stream;
+    const int bad = sk::value_lookup(A.d_diag, L0.d_perm.p, L0.d_perm.p, A0.d_diag, s);
+    if (bad >= 0) fail(1, where + std::to_string(bad) + ")");
+    if (!A.host_diag_stale) values_to_host(A.d_diag, A.diag, s);
+  } else {
+    if (!host_only) ensure_host(0);
+    int bad = 0;
+    if (!host_value_lookup(A.diag, L0.perm.host(), A0.diag, bad)) fail(1, where + std::to_string(bad) + ")");
+    if (!host_only && A.d_diag.nnz)
+      MI_HIP(hipMemcpy(A.d_diag.a.p, A.diag.a.data(), (size_t)A.d_diag.nnz * sizeof(double), hipMemcpyHostToDevice));
+  }
+  if (!host_only) k::build_value_dictionary(A.d_diag, ctx().stream);  // the value format is decided again
+}
+
+// step 2: A_{level+1} = P^T (A P) into its stored pattern, in the order contract of host_spgemm on the stored operators
+void BoomerAMG::refresh_coarse_operator(int level, double *seconds) {
+  AmgLevel &Lf = L[(size_t)level], &Lc = L[(size_t)level + 1];
+  const std::string where = "BoomerAMGSetup (refresh): level " + std::to_string(level + 1) + ": internal error: ";
+  if (!Lf.Pm || !Lf.Rm) fail(1, where + "the level above has no transfer operators");
+  ParCSR &C = *Lc.A;
+  if (!host_only) {
+    hipStream_t s = ctx().stream;
+    const int bad = sk::galerkin_values(Lf.A->d_diag, Lf.Pm->d_diag, Lf.Rm->d_diag, C.d_diag, s, seconds);
+    if (bad >= 0) fail(1, where + "the Galerkin product's pattern is not the stored one (row " + std::to_string(bad) + ")");
+    k::build_value_dictionary(C.d_diag, s);
+    if (!C.host_diag_stale) values_to_host(C.d_diag, C.diag, s);
+    return;
+  }
+  const double t0 = wall_time();
+  HostCSR T, G;
+  host_spgemm(Lf.A->diag, Lf.Pm->diag, T);
+  const double t1 = wall_time();
+  host_spgemm(Lf.Rm->diag, T, G);
+  if (G.nrows != C.diag.nrows || G.ia != C.diag.ia || G.ja != C.diag.ja)
+    fail(1, where + "the Galerkin product's pattern is not the stored one");
+  C.diag.a.swap(G.a);
+  if (seconds) seconds[0] = t1 - t0, seconds[1] = wall_time() - t1;
+}
+
+// step 3: diagonal and l1 norms, and the values of the zero-guess sub-operators (entry subsets of A on kept patterns)
+void BoomerAMG::refresh_norms_and_sub_operators(int level) {
+  AmgLevel &Lv = L[(size_t)level];
+  ParCSR &A = *Lv.A;
+  const int ch = chunk();
+  Lv.t_valid = false;
+  if (host_only) {
+    level_norms(A, Lv.cf.host(), {}, ch, Lv.diag, Lv.l1gs, Lv.l1jac);
+    return;
+  }
+  hipStream_t s = ctx().stream;
+  if (Lv.n) {
+    sk::level_norms(A.d_diag, Lv.cf.empty() ? nullptr : Lv.cf.dev(), ch, Lv.d_diag.p, Lv.d_l1gs.p, Lv.d_l1jac.p, s);
+    if (!Lv.diag.empty()) {  // a level the host built keeps its host copies
+      d2h(Lv.diag.data(), Lv.d_diag.p, (size_t)Lv.n * sizeof(double), s);
+      d2h(Lv.l1gs.data(), Lv.d_l1gs.p, (size_t)Lv.n * sizeof(double), s);
+      d2h(Lv.l1jac.data(), Lv.d_l1jac.p, (size_t)Lv.n * sizeof(double), s);
+    }
+  }
+  const std::string where = "BoomerAMGSetup (refresh): level " + std::to_string(level) + ": internal error: ";
+  if (Lv.has_Az) {
+    const int bad = sk::value_lookup(Lv.Az, nullptr, nullptr, A.d_diag, s);
+    if (bad >= 0) fail(1, where + "the zero-guess sub-operator has an entry the operator lacks (row " + std::to_string(bad) + ")");
+    k::build_value_dictionary(Lv.Az, s);
+  }
+  if (Lv.has_Ar) {
+    const int bad = sk::value_lookup(Lv.Ar, nullptr, nullptr, A.d_diag, s);
+    if (bad >= 0) fail(1, where + "the residual sub-operator has an entry the operator lacks (row " + std::to_string(bad) + ")");
+    k::build_value_dictionary(Lv.Ar, s);
+  }
+}
+
+// A Setup that keeps the structure (cf, both permutations, nc, P, R, every pattern, tile schedule and column list, the
+// work vectors) and recomputes what depends on the values, level by level.  One rank.
+void BoomerAMG::refresh(ParCSR &A0) {
+  TraceRange trace_setup("mi_hypre BoomerAMGSetup (refresh)");
+  const bool timing = getenv("MI_HYPRE_SETUP_TIMING") != nullptr;
+  t_setup_start = wall_time();
+  for (double &t : t_phase) t = 0.0;
+  double t0 = wall_time();
+  refresh_level0(A0);
+  if (timing) printf("   refresh: level-0 values %.3f s\n", wall_time() - t0);
+  for (int l = 0; l + 1 < (int)L.size(); l++) {
+    double sec[2] = {0.0, 0.0};
+    t0 = wall_time();
+    refresh_coarse_operator(l, sec);
+    t_phase[3] += wall_time() - t0;
+    if (timing && l < 4) printf("   refresh: level %d Galerkin values %.3f s (A P %.3f, P^T T into the pattern %.3f)\n", l + 1, wall_time() - t0, sec[0], sec[1]);
+  }
+  if (timing) printf("   refresh: Galerkin values, all levels %.3f s\n", t_phase[3]);
+  t0 = wall_time();
+  for (int l = 0; l < (int)L.size(); l++) refresh_norms_and_sub_operators(l);
+  build_coarsest_inverse();
+  host_ready = true;
+  if (timing) printf("   refresh: norms, sub-operators, coarsest inverse %.3f s\n", wall_time() - t0);
+  if (!host_only) {
+    t0 = wall_time();
+    upload_coarsest_inverse();
+    build_smoothers();
+    MI_HIP(hipDeviceSynchronize());
+    if (timing) printf("   refresh: smoothers %.3f s\n", wall_time() - t0);
+    t0 = wall_time();
+    build_collapsed_tail();
+    if (timing) printf("   refresh: collapsed tail %.3f s\n", wall_time() - t0);
+    is_setup = true;
+  }
+  t_phase[5] = wall_time() - t_setup_start;
+  setup_seconds = t_phase[5];
+  if (timing && !host_only) {
+    long long mp = 0, iu = 0, pm = 0, pu = 0;
+    dev_arena_stats(&mp, &iu, &pm, &pu);
+    printf("   refresh: total %.3f s; device arena %.1f GiB in use (peak %.1f)\n", setup_seconds, iu / 1073741824.0, pu / 1073741824.0);
   }
 }
 

@@ -484,7 +484,7 @@ void BoomerAMG::tabulate_cycle(int lt, DVec<double> &Bt) {
   AmgLevel &Lv = L[(size_t)lt];
   const int n = Lv.n;
   hipStream_t s = ctx().stream;
-  Bt.alloc((size_t)n * (size_t)n);
+  if (!Bt.p || Bt.n != (size_t)n * (size_t)n) Bt.alloc((size_t)n * (size_t)n);  // (a refresh tabulates into the map it has)
   double *own_f = Lv.f.p;
   DVec<double> e((size_t)n);
   DVec<int> col(1);
@@ -571,7 +571,7 @@ void BoomerAMG::build_collapsed_tail() {
   collapsed_signature = cycle_signature();
   collapsed_level = -1;
   collapsed_n = 0;
-  collapsed_Bt.release();
+  DVec<double> Bt = std::move(collapsed_Bt);  // kept when the level has the size of the last map (setup reuse)
   static const long long max_rows = getenv("MI_HYPRE_DENSE_TAIL_ROWS") ? atoll(getenv("MI_HYPRE_DENSE_TAIL_ROWS")) : 1024;
   if (max_rows <= 0 || my_comm().size != 1 || tail) return;
   const int nlev = (int)L.size();
@@ -582,7 +582,6 @@ void BoomerAMG::build_collapsed_tail() {
       break;
     }
   if (lt < 0) return;
-  DVec<double> Bt;
   tabulate_cycle(lt, Bt);
   collapsed_Bt = std::move(Bt);
   collapsed_n = L[(size_t)lt].n;

@@ -666,11 +666,88 @@ HYPRE_Int HYPRE_MI_ParCSRGetColMapOffd(HYPRE_ParCSRMatrix A, HYPRE_BigInt *col_m
 HYPRE_Int HYPRE_MI_BoomerAMGSetupHostOnly(HYPRE_Solver solver, HYPRE_ParCSRMatrix A) {
   API_BEGIN
   if (!A) fail(HYPRE_ERROR_ARG, "BoomerAMGSetupHostOnly: NULL matrix");
-  AMG(solver)->amg.device_min_rows = -1;  // host threads only
-  AMG(solver)->amg.host_only = true;
-  AMG(solver)->amg.setup_host(*PM(A));
-  AMG(solver)->amg.apply_value_storage(false);
-  if (AMG(solver)->amg.tail) AMG(solver)->amg.tail->apply_value_storage(false);
+  AMG(solver)->amg.setup_entry(*PM(A), true);  // host threads only
+  API_END
+}
+HYPRE_Int HYPRE_MI_BoomerAMGSetSetupReuse(HYPRE_Solver solver, HYPRE_Int mode) {
+  API_BEGIN
+  if (mode != 0 && mode != 1)
+    fail(HYPRE_ERROR_ARG, "BoomerAMGSetSetupReuse: mode " + std::to_string(mode) + " is not implemented (0 = every Setup builds from "
+                          "scratch and 1 = refresh the values on the kept structure are)");
+  AMG(solver)->amg.setup_reuse = mode;
+  API_END
+}
+const char *HYPRE_MI_SetupReuseReasonText(HYPRE_Int reason) { return setup_reuse_reason_text((int)reason); }
+HYPRE_Int HYPRE_MI_BoomerAMGGetSetupKind(HYPRE_Solver solver, HYPRE_Int *kind, HYPRE_Int *reason) {
+  API_BEGIN
+  if (!kind || !reason) fail(HYPRE_ERROR_ARG, "BoomerAMGGetSetupKind: NULL output");
+  *kind = AMG(solver)->amg.setup_kind;
+  *reason = AMG(solver)->amg.setup_reason;
+  API_END
+}
+// The setup-reuse kernels on caller (host) CSR arrays (64-bit row pointers, columns ascending).
+// op 0: c_a[stored entry (i, j) of C] = (P^T (A P))_ij in the order contract of the refresh; B = P, R = P^T is formed
+//       here (sk::transpose); `lanes` (0, 1, 2, ... 64) = lanes per coarse row, 0 = the library's choice.
+// op 1: c_a[stored entry (r, c) of C] = A[rowmap[r], colmap[c]] (null maps: identity).
+// *bad_row = -1, or the first row of C that does not fit (then c_a is untouched and the call returns an error).
+HYPRE_Int HYPRE_MI_CSRReuseOp(HYPRE_Int op, HYPRE_Int a_nrows, HYPRE_Int a_ncols, const HYPRE_BigInt *a_ia, const HYPRE_Int *a_ja,
+                              const HYPRE_Complex *a_a, HYPRE_Int b_nrows, HYPRE_Int b_ncols, const HYPRE_BigInt *b_ia,
+                              const HYPRE_Int *b_ja, const HYPRE_Complex *b_a, const HYPRE_Int *rowmap, const HYPRE_Int *colmap,
+                              HYPRE_Int lanes, HYPRE_Int c_nrows, HYPRE_Int c_ncols, const HYPRE_BigInt *c_ia,
+                              const HYPRE_Int *c_ja, HYPRE_Complex *c_a, HYPRE_Int *bad_row) {
+  API_BEGIN
+  if (!a_ia || !c_ia || !c_a || !bad_row) fail(HYPRE_ERROR_ARG, "CSRReuseOp: NULL argument");
+  if (lanes < 0 || lanes > 64 || (lanes & (lanes - 1))) fail(HYPRE_ERROR_ARG, "CSRReuseOp: lanes must be 0 or a power of two up to 64");
+  ensure_init();
+  hipStream_t s = ctx().stream;
+  auto to_host = [](const char *what, HYPRE_Int nr, HYPRE_Int nc, const HYPRE_BigInt *ia, const HYPRE_Int *ja, const HYPRE_Complex *a) {
+    HostCSR h;
+    if (nr < 0 || nc < 0 || ia[0] != 0) fail(HYPRE_ERROR_ARG, std::string("CSRReuseOp: bad dimensions of ") + what);
+    h.nrows = nr;
+    h.ncols = nc;
+    h.ia.assign(ia, ia + nr + 1);
+    for (HYPRE_Int i = 0; i < nr; i++)
+      if (ia[i + 1] < ia[i]) fail(HYPRE_ERROR_ARG, std::string("CSRReuseOp: row pointers of ") + what + " decrease");
+    h.ja.assign(ja, ja + ia[nr]);
+    for (HYPRE_Int i = 0; i < nr; i++)
+      for (HYPRE_BigInt k = ia[i]; k < ia[i + 1]; k++)
+        if (ja[k] < 0 || ja[k] >= nc || (k > ia[i] && ja[k] <= ja[k - 1]))
+          fail(HYPRE_ERROR_ARG, std::string("CSRReuseOp: columns of ") + what + " out of range or not ascending");
+    if (a)
+      h.a.assign(a, a + ia[nr]);
+    else
+      h.a.assign((size_t)ia[nr], 0.0);
+    return h;
+  };
+  sk::DCsr dA, dC;
+  dA.upload(to_host("A", a_nrows, a_ncols, a_ia, a_ja, a_a), s);
+  dC.upload(to_host("C", c_nrows, c_ncols, c_ia, c_ja, nullptr), s);
+  int bad = -1;
+  if (op == 0) {
+    if (!b_ia) fail(HYPRE_ERROR_ARG, "CSRReuseOp: the product needs P");
+    if (a_ncols != b_nrows || a_nrows != b_nrows || c_nrows != b_ncols || c_ncols != b_ncols)
+      fail(HYPRE_ERROR_ARG, "CSRReuseOp: the dimensions of A, P and C do not fit");
+    sk::DCsr dP, dR;
+    dP.upload(to_host("P", b_nrows, b_ncols, b_ia, b_ja, b_a), s);
+    sk::transpose(dP, dR, s);
+    bad = sk::galerkin_values(sk::ref_of(dA), sk::ref_of(dP), sk::ref_of(dR), nullptr, sk::ref_of(dC), dC.a.p, lanes, s);
+  } else if (op == 1) {
+    if (c_nrows > 0 && rowmap)
+      for (HYPRE_Int r = 0; r < c_nrows; r++)
+        if (rowmap[r] < 0 || rowmap[r] >= a_nrows) fail(HYPRE_ERROR_ARG, "CSRReuseOp: rowmap out of range");
+    if (!rowmap && c_nrows > a_nrows) fail(HYPRE_ERROR_ARG, "CSRReuseOp: C has more rows than A");
+    DVec<int> drow, dcol;
+    if (rowmap) drow.upload(std::vector<int>(rowmap, rowmap + c_nrows));
+    if (colmap) dcol.upload(std::vector<int>(colmap, colmap + c_ncols));
+    bad = sk::value_lookup(sk::ref_of(dC), dC.a.p, rowmap ? drow.p : nullptr, colmap ? dcol.p : nullptr, sk::ref_of(dA), s);
+  } else {
+    fail(HYPRE_ERROR_ARG, "CSRReuseOp: op must be 0 (Galerkin values) or 1 (value lookup)");
+  }
+  *bad_row = bad;
+  if (bad >= 0)
+    fail(HYPRE_ERROR_GENERIC, "CSRReuseOp: internal error: row " + std::to_string(bad) + " of the pattern does not fit the source");
+  if (dC.nnz) d2h(c_a, dC.a.p, (size_t)dC.nnz * sizeof(double), s);
+  MI_HIP(hipStreamSynchronize(s));
   API_END
 }
 // setup-phase sparse kernels on caller (host) CSR arrays; results are malloc'ed (HYPRE_MI_Free)
@@ -1691,6 +1768,8 @@ HYPRE_Int HYPRE_MI_GetCounter(const char *name, long long *value) {
     *value = ctx().n_allgather;
   else if (n == "value_storage_row_mapped")
     *value = ctx().n_value_row_mapped;
+  else if (setup_reuse_counter(n.c_str()) >= 0)
+    *value = setup_reuse_counter(n.c_str());
   else if (dist_setup_counter(n.c_str()) >= 0)
     *value = dist_setup_counter(n.c_str());
   else
@@ -2017,6 +2096,19 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCSRSize(HYPRE_Solver solver, HYPRE_Int level
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCSR(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int which, HYPRE_BigInt *ia,
                                         HYPRE_Int *ja, HYPRE_Complex *a) {
   API_BEGIN
+  if (which == 6 || which == 8) {  // the zero-guess sub-operators live on the device only
+    AmgLevel &L = level_ref(AMG(solver), level);
+    if (!(which == 6 ? L.has_Az : L.has_Ar)) {
+      ia[0] = 0;
+      return 0;
+    }
+    HostCSR h;
+    sk::solve_format_to_host(which == 6 ? L.Az : L.Ar, h, ctx().stream);
+    for (int i = 0; i <= h.nrows; i++) ia[i] = h.ia[(size_t)i];
+    if (!h.ja.empty()) memcpy(ja, h.ja.data(), h.ja.size() * sizeof(int));
+    if (!h.a.empty()) memcpy(a, h.a.data(), h.a.size() * sizeof(double));
+    return 0;
+  }
   const HostCSR &c = level_csr(AMG(solver), level, which);
   if (c.ia.empty()) {
     for (int i = 0; i <= c.nrows; i++) ia[i] = 0;

@@ -269,6 +269,7 @@ void assemble_halo_columns_and_partition(Comm &comm, gidx ilower, gidx iupper, c
   out.row_starts = starts;
   out.row_starts.push_back(gend);
   out.assembly_stamp = next_assembly_stamp();
+  out.pattern_stamp = out.assembly_stamp;  // update rounds move assembly_stamp and keep this one
 }
 
 unsigned long long next_assembly_stamp() {

@@ -48,6 +48,9 @@ struct ParCSR {
   // unique per assembly (0 = never assembled): tells a re-assembled or re-allocated matrix from the one a
   // preconditioner was set up on
   unsigned long long assembly_stamp = 0;
+  // the assembly stamp of the assembly that fixed the pattern: update rounds write values on it and keep it, so the
+  // same object with the same pattern stamp has the pattern a hierarchy was built on (BoomerAMG setup reuse)
+  unsigned long long pattern_stamp = 0;
   // A level built by the device setup keeps its diag block on the device only: the host arrays of `diag`
   // are filled on demand (BoomerAMG::ensure_host); nrows / ncols of `diag` are always valid.
   bool host_diag_stale = false;

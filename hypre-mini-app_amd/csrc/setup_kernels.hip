@@ -1916,6 +1916,7 @@ inline int row_group(long long nnz, long long n) {
 }  // namespace
 
 // ---------------------------------------------------------------- host-facing entry points
+CsrRef ref_of(const DCsr &A) { return CsrRef{A.nrows, A.ncols, A.nnz, A.ia.p, A.ja.p, A.a.p}; }
 void exclusive_scan_counts(const int *in, long long *out, long long n, hipStream_t s) { exclusive_scan(in, out, n, s); }
 
 void DCsr::upload(const HostCSR &h, hipStream_t s) {
@@ -1960,7 +1961,7 @@ struct Bins {
 };
 
 template <bool NUMERIC>
-void launch_bins(const Bins &bins, const int *rows, const int *T, int S_hint, const DCsr &A, const DCsr &B, int *nout,
+void launch_bins(const Bins &bins, const int *rows, const int *T, int S_hint, const CsrRef &A, const CsrRef &B, int *nout,
                  const long long *Cia, int *Cja, double *Ca, int *gscratch, long long scratch_per_block, int block_grid,
                  hipStream_t s) {
   const int n0 = bins.start[1] - bins.start[0], n1 = bins.start[2] - bins.start[1], n2 = bins.start[3] - bins.start[2],
@@ -1996,45 +1997,45 @@ void launch_bins(const Bins &bins, const int *rows, const int *T, int S_hint, co
     }
     if (n0)
       spgemm_accum_k<8, 32><<<grid_for(((long long)n0 + 31) / 32), BLK, 0, s>>>(
-          n0, rows + bins.start[0], A.ia.p, A.ja.p, A.a.p, B.ia.p, B.ja.p, B.a.p, Cia, Cja, Ca);
+          n0, rows + bins.start[0], A.ia, A.ja, A.a, B.ia, B.ja, B.a, Cia, Cja, Ca);
     if (hc[0])
       spgemm_accum_k<16, 32><<<grid_for(((long long)hc[0] + 15) / 16), BLK, 0, s>>>(
-          hc[0], s1, A.ia.p, A.ja.p, A.a.p, B.ia.p, B.ja.p, B.a.p, Cia, Cja, Ca);
+          hc[0], s1, A.ia, A.ja, A.a, B.ia, B.ja, B.a, Cia, Cja, Ca);
     if (hc[1])
       spgemm_accum_k<16, 128><<<grid_for(((long long)hc[1] + 15) / 16), BLK, 0, s>>>(
-          hc[1], b1, A.ia.p, A.ja.p, A.a.p, B.ia.p, B.ja.p, B.a.p, Cia, Cja, Ca);
+          hc[1], b1, A.ia, A.ja, A.a, B.ia, B.ja, B.a, Cia, Cja, Ca);
     if (hc[2])
       spgemm_accum_k<64, 128><<<grid_for(((long long)hc[2] + 3) / 4), BLK, 0, s>>>(
-          hc[2], s2, A.ia.p, A.ja.p, A.a.p, B.ia.p, B.ja.p, B.a.p, Cia, Cja, Ca);
+          hc[2], s2, A.ia, A.ja, A.a, B.ia, B.ja, B.a, Cia, Cja, Ca);
     if (hc[3])
       spgemm_accum_k<64, 512><<<grid_for(((long long)hc[3] + 3) / 4), BLK, 0, s>>>(
-          hc[3], b2, A.ia.p, A.ja.p, A.a.p, B.ia.p, B.ja.p, B.a.p, Cia, Cja, Ca);
+          hc[3], b2, A.ia, A.ja, A.a, B.ia, B.ja, B.a, Cia, Cja, Ca);
     if (hc[4])
       spgemm_accum_k<64, 128><<<grid_for(((long long)hc[4] + 3) / 4), BLK, 0, s>>>(
-          hc[4], s3, A.ia.p, A.ja.p, A.a.p, B.ia.p, B.ja.p, B.a.p, Cia, Cja, Ca);
+          hc[4], s3, A.ia, A.ja, A.a, B.ia, B.ja, B.a, Cia, Cja, Ca);
     if (hc[6])
       spgemm_accum_k<64, 512><<<grid_for(((long long)hc[6] + 3) / 4), BLK, 0, s>>>(
-          hc[6], m3, A.ia.p, A.ja.p, A.a.p, B.ia.p, B.ja.p, B.a.p, Cia, Cja, Ca);
+          hc[6], m3, A.ia, A.ja, A.a, B.ia, B.ja, B.a, Cia, Cja, Ca);
     if (hc[7])
       spgemm_block_k<true><<<(unsigned)std::min(hc[7], block_grid), BLK, 0, s>>>(
-          hc[7], g3, T, B.ncols, S_hint, gscratch, scratch_per_block, A.ia.p, A.ja.p, A.a.p, B.ia.p, B.ja.p, B.a.p, nout,
+          hc[7], g3, T, B.ncols, S_hint, gscratch, scratch_per_block, A.ia, A.ja, A.a, B.ia, B.ja, B.a, nout,
           Cia, Cja, Ca);
     MI_HIP(hipGetLastError());
     MI_HIP(hipStreamSynchronize(s));  // `part` is released on return
   } else {
     if (n0)
       spgemm_group_k<8, 32><<<grid_for(((long long)n0 + 31) / 32), BLK, 0, s>>>(
-          n0, rows + bins.start[0], std::min(S_hint, 8), A.ia.p, A.ja.p, B.ia.p, B.ja.p, nout);
+          n0, rows + bins.start[0], std::min(S_hint, 8), A.ia, A.ja, B.ia, B.ja, nout);
     if (n1)
       spgemm_group_k<16, 128><<<grid_for(((long long)n1 + 15) / 16), BLK, 0, s>>>(
-          n1, rows + bins.start[1], std::min(S_hint, 16), A.ia.p, A.ja.p, B.ia.p, B.ja.p, nout);
+          n1, rows + bins.start[1], std::min(S_hint, 16), A.ia, A.ja, B.ia, B.ja, nout);
     if (n2)
       spgemm_group_k<64, 512><<<grid_for(((long long)n2 + 3) / 4), BLK, 0, s>>>(
-          n2, rows + bins.start[2], std::min(S_hint, 64), A.ia.p, A.ja.p, B.ia.p, B.ja.p, nout);
+          n2, rows + bins.start[2], std::min(S_hint, 64), A.ia, A.ja, B.ia, B.ja, nout);
     if (n3)
       spgemm_block_k<false><<<(unsigned)std::min(n3, block_grid), BLK, 0, s>>>(
-          n3, rows + bins.start[3], T, B.ncols, S_hint, gscratch, scratch_per_block, A.ia.p, A.ja.p, A.a.p, B.ia.p,
-          B.ja.p, B.a.p, nout, Cia, Cja, Ca);
+          n3, rows + bins.start[3], T, B.ncols, S_hint, gscratch, scratch_per_block, A.ia, A.ja, A.a, B.ia,
+          B.ja, B.a, nout, Cia, Cja, Ca);
   }
   MI_HIP(hipGetLastError());
 }
@@ -2555,7 +2556,7 @@ void invert_permutation(const int *order, int n, int *pos, hipStream_t s) {
   MI_HIP(hipGetLastError());
 }
 
-void level_norms(const DCsr &A, const int *cf, int chunk, double *diag, double *l1gs, double *l1jac, hipStream_t s,
+void level_norms(const CsrRef &A, const int *cf, int chunk, double *diag, double *l1gs, double *l1jac, hipStream_t s,
                  const DCsr *halo, const int *cf_ext) {
   const int n = A.nrows;
   if (n == 0) return;
@@ -2564,8 +2565,13 @@ void level_norms(const DCsr &A, const int *cf, int chunk, double *diag, double *
   const long long *oia = (halo && halo->nnz > 0) ? halo->ia.p : nullptr;
   const int *oja = oia ? halo->ja.p : nullptr;
   const double *oa = oia ? halo->a.p : nullptr;
-  MI_ROW_GROUP_DISPATCH(rg, (level_norms_k<G><<<grid, BLK, 0, s>>>(n, A.ia.p, A.ja.p, A.a.p, cf, chunk, diag, l1gs, l1jac, oia, oja, oa, cf_ext)))
+  MI_ROW_GROUP_DISPATCH(rg, (level_norms_k<G><<<grid, BLK, 0, s>>>(n, A.ia, A.ja, A.a, cf, chunk, diag, l1gs, l1jac, oia, oja, oa, cf_ext)))
   MI_HIP(hipGetLastError());
+}
+
+void level_norms(const DCsr &A, const int *cf, int chunk, double *diag, double *l1gs, double *l1jac, hipStream_t s,
+                 const DCsr *halo, const int *cf_ext) {
+  level_norms(ref_of(A), cf, chunk, diag, l1gs, l1jac, s, halo, cf_ext);
 }
 
 void strength(const DCsr &A, double theta, double max_row_sum, DCsr &S, hipStream_t s) {
@@ -2735,7 +2741,7 @@ bool interp(const DCsr &A, const DCsr &S, DVec<int> &cf, int interp_type, double
   return true;
 }
 
-void spgemm(const DCsr &A, const DCsr &B, DCsr &C, hipStream_t s) {
+void spgemm(const CsrRef &A, const CsrRef &B, DCsr &C, hipStream_t s) {
   MI_REQUIRE(A.ncols == B.nrows, "spgemm: inner dimensions differ");
   const int n = A.nrows;
   C.release();
@@ -2753,7 +2759,7 @@ void spgemm(const DCsr &A, const DCsr &B, DCsr &C, hipStream_t s) {
   DVec<int> T((size_t)n), rows((size_t)n), nout((size_t)n), meta(16);
   MI_HIP(hipMemsetAsync(meta.p, 0, 16 * sizeof(int), s));
   // meta: [0..3] bin counts, [4] max T, [8..11] bin starts, [12..15] fill cursors
-  row_products_k<<<grid_rows, BLK, 0, s>>>(n, A.ia.p, A.ja.p, B.ia.p, T.p, meta.p, meta.p + 4);
+  row_products_k<<<grid_rows, BLK, 0, s>>>(n, A.ia, A.ja, B.ia, T.p, meta.p, meta.p + 4);
   int hmeta[16];
   d2h(hmeta, meta.p, sizeof(hmeta), s);
   MI_HIP(hipStreamSynchronize(s));
@@ -2795,6 +2801,8 @@ void spgemm(const DCsr &A, const DCsr &B, DCsr &C, hipStream_t s) {
                     s);
   MI_HIP(hipStreamSynchronize(s));
 }
+
+void spgemm(const DCsr &A, const DCsr &B, DCsr &C, hipStream_t s) { spgemm(ref_of(A), ref_of(B), C, s); }
 
 void transpose(const DCsr &A, DCsr &T, hipStream_t s) {
   T.release();
@@ -4070,6 +4078,172 @@ int two_stage_ext(const DCsr &A, const DCsr &S, const DVec<int> &m1, DVec<int> &
   MI_HIP(hipGetLastError());
   MI_HIP(hipStreamSynchronize(s));
   return -1;
+}
+
+// ---------------------------------------------------------------- setup reuse: values on known patterns
+// ("Setup reuse"; section 8).  Nothing here counts, scans, sorts or allocates an output: the
+// patterns are the stored ones, every output entry has ONE owner lane that sums in the stated order, and the only
+// atomic is an integer minimum on the status word (the first row that does not fit its pattern).
+namespace {
+
+// position of column j in the ascending row [k0, k1), or -1
+__device__ __forceinline__ long long find_col(const int *__restrict__ ja, long long k0, long long k1, int j) {
+  long long lo = k0, hi = k1;
+  while (lo < hi) {
+    const long long mid = (lo + hi) >> 1;
+    if (ja[mid] < j)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return (lo < k1 && ja[lo] == j) ? lo : -1;
+}
+
+// C[out row, j] = sum_k r_k T_kj over the stored entries k of R's row (k ascending; first product assigned, the others
+// added one by one), for the STORED entries (out row, j) of C.  G lanes per row of R; stored row r of R is row
+// rowmap[r] of C (null: r).  A row fits iff every stored entry of C met at least one T_kj and every T_kj of the rows k
+// met a stored entry (hits == sum of the lengths of the rows T_k): otherwise status = min(status, out row).
+template <int G>
+__global__ __launch_bounds__(BLK) void galerkin_values_k(int nr, const long long *__restrict__ ria, const int *__restrict__ rja,
+                                                         const double *__restrict__ ra, const int *__restrict__ rowmap,
+                                                         const long long *__restrict__ tia, const int *__restrict__ tja,
+                                                         const double *__restrict__ ta, const long long *__restrict__ cia,
+                                                         const int *__restrict__ cja, double *__restrict__ out,
+                                                         int *__restrict__ status) {
+  const long long r = (bid() * BLK + threadIdx.x) / G;
+  const int sub = threadIdx.x % G;
+  const bool live = r < nr;
+  const int i = live ? (rowmap ? rowmap[r] : (int)r) : 0;
+  const long long r0 = live ? ria[r] : 0, r1 = live ? ria[r + 1] : 0;
+  const long long c0 = live ? cia[i] : 0, c1 = live ? cia[i + 1] : 0;
+  long long balance = 0;  // hits of my entries minus my share of the lengths of the rows T_k
+  bool bad = false;
+  for (long long q = r0 + sub; q < r1; q += G) {
+    const int k = rja[q];
+    balance -= tia[k + 1] - tia[k];
+  }
+  for (long long pos = c0 + sub; pos < c1; pos += G) {
+    const int j = cja[pos];
+    double acc = 0.0;
+    bool first = true;
+    for (long long q = r0; q < r1; q++) {
+      const int k = rja[q];
+      const long long t = find_col(tja, tia[k], tia[k + 1], j);
+      if (t < 0) continue;
+      const double v = ra[q] * ta[t];
+      acc = first ? v : acc + v;
+      first = false;
+      balance++;
+    }
+    if (first) bad = true;
+    out[pos] = acc;
+  }
+  for (int m = 1; m < G; m <<= 1) balance += __shfl_xor(balance, m, 64);
+  if (live && (bad || (sub == 0 && balance != 0))) atomicMin(status, i);
+}
+
+// dst[r, c] = src[rowmap[r], colmap[c]] for every stored entry of dst (null maps: identity); rows of src ascending.
+// WRITE false: only looks (status = the first dst row with an entry src does not store)
+template <bool WRITE, int G>
+__global__ __launch_bounds__(BLK) void value_lookup_k(int n, const long long *__restrict__ dia, const int *__restrict__ dja,
+                                                      double *__restrict__ da, const int *__restrict__ rowmap,
+                                                      const int *__restrict__ colmap, const long long *__restrict__ sia,
+                                                      const int *__restrict__ sja, const double *__restrict__ sa,
+                                                      int *__restrict__ status) {
+  const long long r = (bid() * BLK + threadIdx.x) / G;
+  const int sub = threadIdx.x % G;
+  if (r >= n) return;
+  const int sr = rowmap ? rowmap[r] : (int)r;
+  const long long s0 = sia[sr], s1 = sia[sr + 1];
+  bool bad = false;
+  for (long long pos = dia[r] + sub; pos < dia[r + 1]; pos += G) {
+    const int c = dja[pos];
+    const long long t = find_col(sja, s0, s1, colmap ? colmap[c] : c);
+    if (t < 0)
+      bad = true;
+    else if (WRITE)
+      da[pos] = sa[t];
+  }
+  if (bad) atomicMin(status, (int)r);
+}
+
+struct StatusWord {
+  DVec<int> d;
+  explicit StatusWord(hipStream_t s) : d(1) {
+    const int none = INT_MAX;
+    MI_HIP(hipMemcpyAsync(d.p, &none, sizeof(int), hipMemcpyHostToDevice, s));
+    MI_HIP(hipStreamSynchronize(s));
+  }
+  int read(hipStream_t s) {  // -1: every row fitted
+    int v = 0;
+    d2h(&v, d.p, sizeof(int), s);
+    return v == INT_MAX ? -1 : v;
+  }
+};
+
+CsrRef ref_of(const DevCSR &A, DVec<long long> &ia_tmp, hipStream_t s) {
+  MI_REQUIRE(A.a.p || A.nnz == 0, "setup reuse: an operator holds no fp64 values");
+  return CsrRef{A.nrows, A.ncols, A.nnz, A.nrows ? wide_row_pointers(A, ia_tmp, s) : nullptr, A.ja.p, A.a.p};
+}
+}  // namespace
+
+
+int value_lookup(const CsrRef &dst, double *dst_a, const int *rowmap, const int *colmap, const CsrRef &src, hipStream_t s) {
+  const int n = dst.nrows;
+  if (n == 0 || dst.nnz == 0) return -1;
+  StatusWord st(s);
+  const int rg = row_group(dst.nnz, n);
+  const dim3 grid = grid_for(((long long)n * rg + BLK - 1) / BLK);
+  MI_ROW_GROUP_DISPATCH(rg, (value_lookup_k<false, G><<<grid, BLK, 0, s>>>(n, dst.ia, dst.ja, nullptr, rowmap, colmap, src.ia, src.ja, src.a, st.d.p)))
+  MI_HIP(hipGetLastError());
+  const int bad = st.read(s);
+  if (bad >= 0) return bad;
+  MI_ROW_GROUP_DISPATCH(rg, (value_lookup_k<true, G><<<grid, BLK, 0, s>>>(n, dst.ia, dst.ja, dst_a, rowmap, colmap, src.ia, src.ja, src.a, st.d.p)))
+  MI_HIP(hipGetLastError());
+  MI_HIP(hipStreamSynchronize(s));
+  return -1;
+}
+
+int value_lookup(DevCSR &dst, const int *rowmap, const int *colmap, const DevCSR &src, hipStream_t s) {
+  DVec<long long> di, si;
+  const CsrRef d = ref_of(dst, di, s), sr = ref_of(src, si, s);
+  return value_lookup(d, dst.a.p, rowmap, colmap, sr, s);
+}
+
+int galerkin_values(const CsrRef &A, const CsrRef &P, const CsrRef &R, const int *r_rowmap, const CsrRef &C, double *c_a,
+                    int lanes, hipStream_t s, double *seconds) {
+  MI_REQUIRE(A.ncols == P.nrows && R.ncols == A.nrows && R.nrows == C.nrows && P.ncols == C.ncols,
+             "setup reuse: the dimensions of A, P, R and the coarse pattern do not fit");
+  if (C.nrows == 0) return -1;
+  const double t0 = wall_time();
+  DCsr T;
+  spgemm(A, P, T, s);  // T_kj = sum_m a_km p_mj, m ascending: the first product's order contract
+  const double t1 = wall_time();
+  DVec<double> out((size_t)C.nnz);  // the operator takes the values only when every row fitted
+  StatusWord st(s);
+  const int rg = lanes > 0 ? lanes : row_group(C.nnz, C.nrows);
+  const dim3 grid = grid_for(((long long)R.nrows * rg + BLK - 1) / BLK);
+  MI_ROW_GROUP_DISPATCH(rg, (galerkin_values_k<G><<<grid, BLK, 0, s>>>(R.nrows, R.ia, R.ja, R.a, r_rowmap, T.ia.p, T.ja.p, T.a.p, C.ia, C.ja, out.p, st.d.p)))
+  MI_HIP(hipGetLastError());
+  const int bad = st.read(s);
+  if (bad < 0) {
+    MI_HIP(hipMemcpyAsync(c_a, out.p, (size_t)C.nnz * sizeof(double), hipMemcpyDeviceToDevice, s));
+    MI_HIP(hipStreamSynchronize(s));
+  }
+  if (seconds) seconds[0] = t1 - t0, seconds[1] = wall_time() - t1;
+  return bad;
+}
+
+int galerkin_values(const DevCSR &A, const DevCSR &P, const DevCSR &R, DevCSR &C, hipStream_t s, double *seconds) {
+  DVec<long long> ai, pi, ri, ci;
+  const CsrRef a = ref_of(A, ai, s), p = ref_of(P, pi, s), r = ref_of(R, ri, s), c = ref_of(C, ci, s);
+  return galerkin_values(a, p, r, R.rowmap.p, c, C.a.p, 0, s, seconds);
+}
+
+void level_norms(const DevCSR &A, const int *cf, int chunk, double *diag, double *l1gs, double *l1jac, hipStream_t s) {
+  DVec<long long> ai;
+  level_norms(ref_of(A, ai, s), cf, chunk, diag, l1gs, l1jac, s, nullptr, nullptr);
+  MI_HIP(hipStreamSynchronize(s));  // (the widened row pointers are released on return)
 }
 
 }  // namespace sk

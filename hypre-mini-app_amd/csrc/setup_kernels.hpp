@@ -140,6 +140,35 @@ void solve_format_to_host(const DevCSR &src, HostCSR &h, hipStream_t s);
 void level_norms(const DCsr &A, const int *cf, int chunk, double *diag, double *l1gs, double *l1jac, hipStream_t s,
                  const DCsr *halo = nullptr, const int *cf_ext = nullptr);
 
+// ---- setup reuse ("Setup reuse"): new values on the stored patterns of a finished hierarchy
+// a CSR somebody else owns: 64-bit row pointers, columns ascending in every row
+struct CsrRef {
+  int nrows, ncols;
+  int64_t nnz;
+  const long long *ia;
+  const int *ja;
+  const double *a;
+};
+CsrRef ref_of(const DCsr &A);
+// spgemm and level_norms on such views (the solve format's own arrays; the DCsr forms call these)
+void spgemm(const CsrRef &A, const CsrRef &B, DCsr &C, hipStream_t s);
+void level_norms(const CsrRef &A, const int *cf, int chunk, double *diag, double *l1gs, double *l1jac, hipStream_t s,
+                 const DCsr *halo, const int *cf_ext);
+// Numeric-only Galerkin product: the stored entries (i, j) of C take sum_k r_ik T_kj, k ascending along R's row, with
+// T = spgemm(A, P) -- the bits of host_spgemm(R, host_spgemm(A, P)).  Stored row r of R is row r_rowmap[r] of C (null:
+// r).  Two stages: spgemm for T, then one owner lane per stored entry of C that finds its column in the rows T_k by
+// binary search (`lanes` per row: 0 = by the mean row length; rows of any length).  Returns -1 and writes c_a, or the
+// first row of C whose stored pattern is not the product's -- then c_a is untouched.  seconds (optional): the stages.
+int galerkin_values(const CsrRef &A, const CsrRef &P, const CsrRef &R, const int *r_rowmap, const CsrRef &C, double *c_a,
+                    int lanes, hipStream_t s, double *seconds = nullptr);
+int galerkin_values(const DevCSR &A, const DevCSR &P, const DevCSR &R, DevCSR &C, hipStream_t s, double *seconds = nullptr);
+// dst_a[entry (r, c) of dst] = src[rowmap[r], colmap[c]] by binary search in src's row (null maps: identity).  Returns
+// -1, or the first row of dst with an entry src does not store -- found by a pass that only looks, so nothing is written
+int value_lookup(const CsrRef &dst, double *dst_a, const int *rowmap, const int *colmap, const CsrRef &src, hipStream_t s);
+int value_lookup(DevCSR &dst, const int *rowmap, const int *colmap, const DevCSR &src, hipStream_t s);
+// level_norms of an operator in the solve format (one rank)
+void level_norms(const DevCSR &A, const int *cf, int chunk, double *diag, double *l1gs, double *l1jac, hipStream_t s);
+
 // ---- ILU(0) of a single-rank block (HYPRE_ILU type 0, fill 0), level-scheduled
 // position of the diagonal entry of every row (-1: none)
 void ilu_diag_positions(const DCsr &A, long long *dpos, hipStream_t s);

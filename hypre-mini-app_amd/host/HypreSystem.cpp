@@ -413,6 +413,16 @@ void HypreSystem::setup_boomeramg_precond() {
       throw std::runtime_error(std::string("Hypre Config:: mi_value_storage: ") + HYPRE_MI_LastErrorMessage());
 #endif
   }
+  /* this library's key: mi_setup_reuse 1 = a Setup after an update round (linear_system: mi_update_steps) keeps the
+   * hierarchy's structure and refreshes its values; 0 (default) = every Setup builds from scratch */
+  if (node["mi_setup_reuse"]) {
+#ifdef MI_HOST_WITH_LIBHYPRE
+    throw std::runtime_error("Hypre Config:: mi_setup_reuse is a key of libmi_hypre; libHYPRE has no such setting");
+#else
+    if (HYPRE_MI_BoomerAMGSetSetupReuse(precond_, node["mi_setup_reuse"].as<int>()))
+      throw std::runtime_error(std::string("Hypre Config:: mi_setup_reuse: ") + HYPRE_MI_LastErrorMessage());
+#endif
+  }
   /* this library's keys for relax_type 16 (Chebyshev): steps per sweep, smoothed fraction of the spectrum, CG steps of
    * the eigenvalue estimate (0 = Gershgorin); an absent key leaves the solver's default (2, 0.3, 10) */
   if (node["mi_cheby_order"] || node["mi_cheby_fraction"] || node["mi_cheby_eig_est"]) {
@@ -924,16 +934,32 @@ void HypreSystem::update_step(int step, double &setup, double &solve_t) {
   Stopwatch s1;
   if (solverSetupPtr_(solver_, parMat_, parRhs_[0], parSln_[0])) throw std::runtime_error("setup after an update step failed");
   MPI_Barrier(comm_);
-  setup += s1.seconds();
+  const double s1_seconds = s1.seconds();
+  setup += s1_seconds;
+#ifndef MI_HOST_WITH_LIBHYPRE
+  if (precond_ && precondSetupPtr_ == &HYPRE_BoomerAMGSetup) {  // what the preconditioner's Setup did (mi_setup_reuse)
+    HYPRE_Int kind = 0, reason = 0;
+    HYPRE_Real amg_seconds = 0.0;
+    HYPRE_MI_BoomerAMGGetSetupKind(precond_, &kind, &reason);
+    HYPRE_MI_BoomerAMGGetSetupSeconds(precond_, &amg_seconds);
+    if (iproc_ == 0 && kind == 2)
+      printf("Setup %d : AMG hierarchy refreshed, %.3f s (solver setup %.3f s)\n", step, amg_seconds, s1.seconds());
+    else if (iproc_ == 0)
+      printf("Setup %d : AMG hierarchy rebuilt (%s), %.3f s (solver setup %.3f s)\n", step,
+             HYPRE_MI_SetupReuseReasonText(reason), amg_seconds, s1.seconds());
+  }
+#endif
   Stopwatch s3;
   solverSolvePtr_(solver_, parMat_, parRhs_[0], parSln_[0]);
   MPI_Barrier(comm_);
-  solve_t += s3.seconds();
+  const double s3_seconds = s3.seconds();
+  solve_t += s3_seconds;
   HYPRE_Int iters = 0;
   double relres = 0.0;
   if (solverItersPtr_) solverItersPtr_(solver_, &iters);
   if (solverResPtr_) solverResPtr_(solver_, &relres);
   if (iproc_ == 0) printf("Solve %d : %d iterations, final relative residual %.6e\n", step, (int)iters, relres);
+  if (iproc_ == 0) printf("Step %d : solver setup %.3f s, solve %.3f s\n", step, s1_seconds, s3_seconds);
   solveComplete_ = true;
   check_solution();
   fflush(stdout);

@@ -325,6 +325,11 @@ class BoomerAMG:
             call("HYPRE_MI_BoomerAMGSetValueStorage", s,
                  int(cfg.get("mi_value_storage", env("MI_HYPRE_VALUE_STORAGE", 0))),
                  int(cfg.get("mi_value_storage_first_level", env("MI_HYPRE_VALUE_STORAGE_FIRST_LEVEL", 1))))
+        # setup reuse (0 = every Setup builds from scratch, 1 = refresh the values on the kept structure); the driver's
+        # key mi_setup_reuse means the same
+        reuse = cfg.get("setup_reuse", cfg.get("mi_setup_reuse"))
+        if reuse is not None:
+            self.set_setup_reuse(int(reuse))
         if cfg.get("keep_agg_markers"):  # test hook: level_agg_markers() after a setup with agg_interp_type 5
             call("HYPRE_MI_BoomerAMGSetKeepAggMarkers", s, 1)
         # non_galerkin_tol + non_galerkin_level_tols {levels, tolerances}, HypreSystem.cpp:161-176
@@ -340,6 +345,19 @@ class BoomerAMG:
 
     def solve(self, A, b, x):
         call("HYPRE_BoomerAMGSolve", self.h, A.par, b.par, x.par)
+
+    def set_setup_reuse(self, mode):
+        """0: every Setup builds from scratch; 1: a Setup on a finished hierarchy of the same matrix and pattern
+        refreshes the values and keeps the structure (setup_kind() tells which happened)."""
+        call("HYPRE_MI_BoomerAMGSetSetupReuse", self.h, int(mode))
+
+    def setup_kind(self):
+        """(kind, reason) of the last Setup: kind 0 never set up, 1 built from scratch, 2 refreshed; reason (kind 1):
+        0 reuse off, 1 first Setup or the previous one failed, 2 another matrix or pattern, 3 a structural setting
+        changed, 4 a setting the refresh does not cover, 5 more than one rank, 6 the other entry point built it."""
+        kind, reason = c_int(), c_int()
+        call("HYPRE_MI_BoomerAMGGetSetupKind", self.h, C.byref(kind), C.byref(reason))
+        return kind.value, reason.value
 
     @property
     def num_levels(self):
@@ -1029,6 +1047,35 @@ def csr_device_op(op, A, B=None, perm=None, colpos=None):
     for ptr in (cia, cja, ca):
         lib().HYPRE_MI_Free(ptr)
     return ia, ja, a, (nr.value, nc.value)
+
+
+def csr_reuse_op(op, A, pattern, P=None, rowmap=None, colmap=None, lanes=0):
+    """The setup-reuse kernels on scipy CSR matrices (ascending columns).  op 0: the values of P^T (A P) on the stored
+    entries of `pattern`, in the refresh's order contract; op 1: pattern[r, c] = A[rowmap[r], colmap[c]].  Returns the
+    value array of `pattern`; raises HypreError (and leaves the array untouched: the exception's `values`) when a row
+    does not fit."""
+    def parts(M):
+        return (np.ascontiguousarray(M.indptr, dtype=np.int64), np.ascontiguousarray(M.indices, dtype=np.int32),
+                np.ascontiguousarray(M.data, dtype=np.float64))
+    aia, aja, aa = parts(A)
+    cia, cja, _ = parts(pattern)
+    if P is not None:
+        bia, bja, ba = parts(P)
+        bn, bm = P.shape
+    else:
+        bia = bja = ba = None
+        bn = bm = 0
+    rm = None if rowmap is None else np.ascontiguousarray(rowmap, dtype=np.int32)
+    cm = None if colmap is None else np.ascontiguousarray(colmap, dtype=np.int32)
+    out = np.full(max(int(cia[-1]), 1), np.nan)
+    bad = c_int(-2)
+    try:
+        call("HYPRE_MI_CSRReuseOp", op, A.shape[0], A.shape[1], aia, aja, aa, bn, bm, bia, bja, ba, rm, cm, int(lanes),
+             pattern.shape[0], pattern.shape[1], cia, cja, out, C.byref(bad))
+    except HypreError as e:
+        e.values, e.bad_row = out[: int(cia[-1])], bad.value
+        raise
+    return out[: int(cia[-1])]
 
 
 VEC_MASS_DOT, VEC_MASS_AXPY, VEC_LIN_COMB, VEC_AXPY_DOT, VEC_SCALE_POST = range(5)

@@ -153,6 +153,30 @@ HYPRE_Int HYPRE_MI_CSRDeviceOp(HYPRE_Int op, HYPRE_Int a_nrows, HYPRE_Int a_ncol
                                const HYPRE_Int *perm, const HYPRE_Int *colpos, HYPRE_Int *c_nrows, HYPRE_Int *c_ncols,
                                HYPRE_BigInt **c_ia, HYPRE_Int **c_ja, HYPRE_Complex **c_a);
 
+/* ---- the setup-reuse kernels ("Setup reuse") on caller (host) CSR arrays with ascending columns.
+ * op 0: c_a[stored entry (i, j) of C] = (P^T (A P))_ij, A = (a_*), P = (b_*), summed in the refresh's order contract;
+ *       lanes = lanes per coarse row of the kernel (a power of two up to 64; 0 = the library's choice).
+ * op 1: c_a[stored entry (r, c) of C] = A[rowmap[r], colmap[c]] (NULL maps: identity).
+ * *bad_row = -1, or the first row of C whose pattern does not fit: the call then fails and c_a is untouched. */
+HYPRE_Int HYPRE_MI_CSRReuseOp(HYPRE_Int op, HYPRE_Int a_nrows, HYPRE_Int a_ncols, const HYPRE_BigInt *a_ia, const HYPRE_Int *a_ja,
+                              const HYPRE_Complex *a_a, HYPRE_Int b_nrows, HYPRE_Int b_ncols, const HYPRE_BigInt *b_ia,
+                              const HYPRE_Int *b_ja, const HYPRE_Complex *b_a, const HYPRE_Int *rowmap, const HYPRE_Int *colmap,
+                              HYPRE_Int lanes, HYPRE_Int c_nrows, HYPRE_Int c_ncols, const HYPRE_BigInt *c_ia,
+                              const HYPRE_Int *c_ja, HYPRE_Complex *c_a, HYPRE_Int *bad_row);
+
+/* ---- setup reuse: mode 0 (default) = every Setup builds from scratch; 1 = a Setup on a handle that holds a finished
+ * hierarchy of the same matrix object and pattern, built by the same entry point with the same structural settings on
+ * one rank, keeps the splittings, orderings, P, R and all patterns and recomputes the values.  A Setup that cannot
+ * refresh rebuilds, and says so.  Any other mode is HYPRE_ERROR_ARG.
+ * GetSetupKind: kind 0 never set up, 1 built from scratch, 2 refreshed; reason (kind 1): 0 reuse is off, 1 first Setup
+ * of this handle or the previous one failed, 2 another matrix object or pattern, 3 a setting the structure depends on
+ * changed, 4 a setting the refresh does not cover is on (non-Galerkin tolerances, value storage), 5 more than one rank,
+ * 6 the other setup entry point built the hierarchy.  Counters: "amg_setups_full", "amg_setups_refreshed". */
+HYPRE_Int HYPRE_MI_BoomerAMGSetSetupReuse(HYPRE_Solver solver, HYPRE_Int mode);
+HYPRE_Int HYPRE_MI_BoomerAMGGetSetupKind(HYPRE_Solver solver, HYPRE_Int *kind, HYPRE_Int *reason);
+/* the reason of a rebuild in words (a static string; the library's print and the driver's use the same) */
+const char *HYPRE_MI_SetupReuseReasonText(HYPRE_Int reason);
+
 /* ---- hierarchy inspection (parity tests; mirrors hypre_ParAMGDataAArray) */
 HYPRE_Int HYPRE_MI_BoomerAMGGetNumLevels(HYPRE_Solver solver, HYPRE_Int *num_levels);
 HYPRE_Int HYPRE_MI_BoomerAMGGetOperatorComplexity(HYPRE_Solver solver, HYPRE_Real *cx);
@@ -163,7 +187,8 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetSetupSeconds(HYPRE_Solver solver, HYPRE_Real *sec
  * first sweep on a zero guess can meet with a non-zero; 0 x 0 when the level has none), and which = 7: the x cache
  * of the level's diag block (nrows = number of tiles, nnz = unique columns summed over the tiles); which = 8: the
  * operator of the residual after a zero-guess sweep (0 x 0 when the level has none); which = 9: the C rows of the diag
- * block (nrows = number of C points, nnz = their entries: what a C pass of the relaxation streams). */
+ * block (nrows = number of C points, nnz = their entries: what a C pass of the relaxation streams).
+ * GetLevelCSR takes which = 0-5, and 6 and 8 (the sub-operators' arrays, fetched from the device). */
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCSRSize(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int which, HYPRE_Int *nrows,
                                             HYPRE_Int *ncols, HYPRE_BigInt *nnz);
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCSR(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int which, HYPRE_BigInt *ia,
