@@ -807,9 +807,10 @@ void two_stage_zero_denominator(int level, int row) {
               ": row " + std::to_string(row) + " has a zero denominator d_i with a non-empty numerator");
 }
 
-// rows of N in place: F rows become w = -n / d, then every row is truncated; compacted into P
-static void two_stage_finish_rows(HostCSR &N, const std::vector<int> *rows, const std::vector<int> *m,
-                                  const std::vector<double> *d, double trunc_factor, int pmax, int level, HostCSR &P) {
+// rows of N in place: F rows become w = -n / d, then every row is truncated; compacted into P.  Returns -1, or the
+// smallest F row with d_i = 0 and a non-empty numerator (P is then not built)
+static int two_stage_finish_rows(HostCSR &N, const std::vector<int> *rows, const std::vector<int> *m,
+                                 const std::vector<double> *d, double trunc_factor, int pmax, HostCSR &P) {
   const int nr = N.nrows;
   std::vector<int> flen((size_t)nr, 0);
   std::atomic<int> bad{-1};
@@ -837,7 +838,7 @@ static void two_stage_finish_rows(HostCSR &N, const std::vector<int> *rows, cons
       flen[(size_t)r] = len;
     }
   });
-  if (bad.load() >= 0) two_stage_zero_denominator(level, bad.load());
+  if (bad.load() >= 0) return bad.load();
   P.nrows = nr;
   P.ncols = N.ncols;
   P.ia.assign((size_t)nr + 1, 0);
@@ -851,6 +852,7 @@ static void two_stage_finish_rows(HostCSR &N, const std::vector<int> *rows, cons
       memcpy(P.a.data() + P.ia[(size_t)r], N.a.data() + N.ia[(size_t)r], (size_t)flen[(size_t)r] * sizeof(double));
     }
   });
+  return -1;
 }
 
 // Two-stage extended interpolation of an aggressive level (agg_interp_type 5; Yang 2010, in the matrix-matrix form of
@@ -870,14 +872,180 @@ void build_two_stage_ext(const ParCSR &A, const Strength &S, const std::vector<i
   int nc1 = 0;
   two_stage_ext_operands(D, S, m1, nullptr, Lo, M, d, nc1);
   host_spgemm(Lo, M, N);
-  two_stage_finish_rows(N, nullptr, &m1, &d, p12_trunc_factor, p12_max, level, P1);
+  int bad = two_stage_finish_rows(N, nullptr, &m1, &d, p12_trunc_factor, p12_max, P1);
+  if (bad >= 0) two_stage_zero_denominator(level, bad);
   two_stage_ext_operands(D, S, m2, &c1, Lo, M, d, nc_out);
   host_spgemm(Lo, M, N);
-  two_stage_finish_rows(N, &c1, &m2, &d, p12_trunc_factor, p12_max, level, P2);
+  bad = two_stage_finish_rows(N, &c1, &m2, &d, p12_trunc_factor, p12_max, P2);
+  if (bad >= 0) two_stage_zero_denominator(level, bad);
   host_spgemm(P1, P2, N);
-  two_stage_finish_rows(N, nullptr, nullptr, nullptr, trunc_factor, pmax, level, P);
+  two_stage_finish_rows(N, nullptr, nullptr, nullptr, trunc_factor, pmax, P);
   for (int i = 0; i < n; i++)
     if (m2[(size_t)i] == SF_PT) m2[(size_t)i] = F_PT;
+}
+
+// Operands of the extended+i interpolation in matrix-matrix form (interp_type 17; DESIGN.md section 3, "Matrix-matrix
+// extended interpolation"): left operand B (n x n) with d, right operand Ah (n x |C|).  F row i is walked once in stored
+// order: the diagonal and the weak entries go to d_i, a strong C neighbour k gives b_ik = a_ik, a strong neighbour k
+// that is not a C point gives b_ik = a_ik / (beta_k + a_ki) and adds b_ik * a_ki to d_i -- or adds a_ik to d_i when
+// beta_k or beta_k + a_ki is zero.  Ah_k = e_k for a C point, the unscaled strong C entries of row k otherwise (none
+// when beta_k = 0).  Every row is one thread's, every sum runs in stored order.
+static void mm_extpi_operands(const HostCSR &D, const Strength &S, const std::vector<int> &m, HostCSR &B, HostCSR &Ah,
+                              std::vector<double> &d, int &nc_out) {
+  const int n = D.nrows;
+  std::vector<int> f2c((size_t)n, -1);
+  int nc = 0;
+  for (int i = 0; i < n; i++)
+    if (m[(size_t)i] == C_PT) f2c[(size_t)i] = nc++;
+  nc_out = nc;
+  std::vector<double> beta((size_t)n, 0.0);
+  std::vector<int> len((size_t)n, 0);
+  parallel_for(n, [&](int64_t b, int64_t e, int) {
+    for (int64_t k = b; k < e; k++) {
+      if (m[(size_t)k] == C_PT) {
+        len[(size_t)k] = 1;
+        continue;
+      }
+      double bk = 0.0;
+      int cnt = 0;
+      int64_t ks = S.ia[(size_t)k];
+      const int64_t kse = S.ia[(size_t)k + 1];
+      for (int64_t q = D.ia[(size_t)k]; q < D.ia[(size_t)k + 1] && ks < kse; q++) {
+        const int l = D.ja[(size_t)q];
+        while (ks < kse && S.ja[(size_t)ks] < l) ks++;
+        if (ks < kse && S.ja[(size_t)ks] == l && m[(size_t)l] == C_PT) {
+          bk += D.a[(size_t)q];
+          cnt++;
+        }
+      }
+      beta[(size_t)k] = bk;
+      len[(size_t)k] = bk != 0.0 ? cnt : 0;
+    }
+  });
+  Ah.nrows = n;
+  Ah.ncols = nc;
+  Ah.ia.assign((size_t)n + 1, 0);
+  for (int k = 0; k < n; k++) Ah.ia[(size_t)k + 1] = Ah.ia[(size_t)k] + len[(size_t)k];
+  Ah.ja.resize((size_t)Ah.nnz());
+  Ah.a.resize((size_t)Ah.nnz());
+  parallel_for(n, [&](int64_t b, int64_t e, int) {
+    for (int64_t k = b; k < e; k++) {
+      int64_t w = Ah.ia[(size_t)k];
+      if (m[(size_t)k] == C_PT) {
+        Ah.ja[(size_t)w] = f2c[(size_t)k];
+        Ah.a[(size_t)w] = 1.0;
+        continue;
+      }
+      if (!len[(size_t)k]) continue;
+      int64_t ks = S.ia[(size_t)k];
+      const int64_t kse = S.ia[(size_t)k + 1];
+      for (int64_t q = D.ia[(size_t)k]; q < D.ia[(size_t)k + 1] && ks < kse; q++) {
+        const int l = D.ja[(size_t)q];
+        while (ks < kse && S.ja[(size_t)ks] < l) ks++;
+        if (ks < kse && S.ja[(size_t)ks] == l && m[(size_t)l] == C_PT) {
+          Ah.ja[(size_t)w] = f2c[(size_t)l];
+          Ah.a[(size_t)w] = D.a[(size_t)q];
+          w++;
+        }
+      }
+    }
+  });
+  // a_ki: the stored entry (k, i), or 0
+  auto entry = [&](int k, int i) {
+    const int *r0 = D.ja.data() + D.ia[(size_t)k], *r1 = D.ja.data() + D.ia[(size_t)k + 1];
+    const int *it = std::lower_bound(r0, r1, i);
+    return (it != r1 && *it == i) ? D.a[(size_t)(it - D.ja.data())] : 0.0;
+  };
+  // one walk of F row i: what(j, kind, b, term) -- kind 0: term goes to d_i; 1: (j, b) goes to B; 2: both
+  auto walk = [&](int i, auto &&what) {
+    int64_t ks = S.ia[(size_t)i];
+    const int64_t kse = S.ia[(size_t)i + 1];
+    for (int64_t q = D.ia[(size_t)i]; q < D.ia[(size_t)i + 1]; q++) {
+      const int j = D.ja[(size_t)q];
+      const double v = D.a[(size_t)q];
+      while (ks < kse && S.ja[(size_t)ks] < j) ks++;
+      if (!(ks < kse && S.ja[(size_t)ks] == j)) {
+        what(j, 0, 0.0, v);  // the diagonal and the weak entries
+      } else if (m[(size_t)j] == C_PT) {
+        what(j, 1, v, 0.0);
+      } else if (beta[(size_t)j] == 0.0) {
+        what(j, 0, 0.0, v);
+      } else {
+        const double aki = entry(j, i);
+        const double delta = beta[(size_t)j] + aki;
+        if (delta == 0.0) {
+          what(j, 0, 0.0, v);
+        } else {
+          const double bik = v / delta;
+          const double prod = bik * aki;  // (one product, rounded on its own)
+          what(j, 2, bik, prod);
+        }
+      }
+    }
+  };
+  B.nrows = n;
+  B.ncols = n;
+  B.ia.assign((size_t)n + 1, 0);
+  parallel_for(n, [&](int64_t b, int64_t e, int) {
+    for (int64_t i = b; i < e; i++) {
+      int c = 0;
+      if (m[(size_t)i] == C_PT)
+        c = 1;
+      else if (m[(size_t)i] == F_PT)
+        walk((int)i, [&](int, int kind, double, double) { c += kind != 0; });
+      B.ia[(size_t)i + 1] = c;
+    }
+  });
+  for (int i = 0; i < n; i++) B.ia[(size_t)i + 1] += B.ia[(size_t)i];
+  B.ja.resize((size_t)B.nnz());
+  B.a.resize((size_t)B.nnz());
+  d.assign((size_t)n, 0.0);
+  parallel_for(n, [&](int64_t b, int64_t e, int) {
+    for (int64_t i = b; i < e; i++) {
+      int64_t w = B.ia[(size_t)i];
+      if (m[(size_t)i] == C_PT) {
+        B.ja[(size_t)w] = (int)i;
+        B.a[(size_t)w] = 1.0;
+        continue;
+      }
+      if (m[(size_t)i] != F_PT) continue;
+      double di = 0.0;
+      walk((int)i, [&](int j, int kind, double bik, double term) {
+        if (kind != 0) {
+          B.ja[(size_t)w] = j;
+          B.a[(size_t)w] = bik;
+          w++;
+        }
+        if (kind != 1) di += term;
+      });
+      d[(size_t)i] = di;
+    }
+  });
+}
+
+void mm_interp_zero_denominator(int interp_type, int level, int row) {
+  fail(4, "BoomerAMGSetup: matrix-matrix extended interpolation (interp_type " + std::to_string(interp_type) + ") on level " +
+              std::to_string(level) + ": row " + std::to_string(row) +
+              " has a zero denominator d_i with a non-empty numerator");
+}
+
+// Extended (16) and extended+i (17) interpolation in matrix-matrix form (Li, Sjogreen, Yang 2021):
+// numerators N = B * Ah by host_spgemm, w_ij = -n_ij / d_i, truncation.  Type 16 is E(A, S, cf) of the two-stage
+// interpolation on the level's own marker.  cf is handed on with special F -> F.
+void build_mm_interp(const ParCSR &A, const Strength &S, std::vector<int> &cf, int interp_type, double trunc_factor,
+                     int pmax, int level, HostCSR &P, int &nc_out) {
+  const HostCSR &D = A.diag;
+  HostCSR B, Ah, N;
+  std::vector<double> d;
+  if (interp_type == 16)
+    two_stage_ext_operands(D, S, cf, nullptr, B, Ah, d, nc_out);
+  else
+    mm_extpi_operands(D, S, cf, B, Ah, d, nc_out);
+  host_spgemm(B, Ah, N);
+  const int bad = two_stage_finish_rows(N, nullptr, &cf, &d, trunc_factor, pmax, P);
+  if (bad >= 0) mm_interp_zero_denominator(interp_type, level, bad);
+  for (size_t i = 0; i < cf.size(); i++)
+    if (cf[i] == SF_PT) cf[i] = F_PT;
 }
 
 void dense_inverse(int n, std::vector<double> &M, std::vector<double> &inv) {
@@ -1606,9 +1774,11 @@ void BoomerAMG::validate_settings() const {
       fail(4, "BoomerAMGSetup: Chebyshev scale " + std::to_string(p.cheby_scale) +
                   " is not implemented (1 = the diagonally scaled operator is); refusing to smooth the unscaled one");
   }
-  if (p.interp_type != 0 && p.interp_type != 3 && p.interp_type != 4 && p.interp_type != 6)
+  if (p.interp_type != 0 && p.interp_type != 3 && p.interp_type != 4 && p.interp_type != 6 && p.interp_type != 16 &&
+      p.interp_type != 17)
     fail(4, "BoomerAMGSetup: interp_type " + std::to_string(p.interp_type) +
-                " is not implemented (0 classical modified, 3 direct, 4 multipass, 6 extended+i are); refusing to substitute another one");
+                " is not implemented (0 classical modified, 3 direct, 4 multipass, 6 extended+i, 16 extended and 17 extended+i in "
+                "matrix-matrix form are); refusing to substitute another one");
   if (p.smooth_num_levels > 0 && p.smooth_type != 5 && p.smooth_type != 4)
     fail(4, "BoomerAMGSetup: smooth_type " + std::to_string(p.smooth_type) + " on " + std::to_string(p.smooth_num_levels) +
                 " level(s) is not implemented (4 = FSAI and 5 = ILU are); refusing to smooth with something else");
@@ -1788,6 +1958,8 @@ void BoomerAMG::build_natural(ParCSR &A0) {
     // (with the two-stage interpolation, agg_interp_type 5, and PMIS the aggressive level stays on the device: second
     // graph, second PMIS, marker correction and the interpolation's sparse products)
     const bool two_stage = aggressive && p.agg_interp_type == 5;
+    // (interp_type 16 / 17: the matrix-matrix extended interpolation of the levels that are not aggressive)
+    const bool mm_interp = !aggressive && (p.interp_type == 16 || p.interp_type == 17);
     const bool pmis_type = p.coarsen_type == 8 || p.coarsen_type == 9;
     const bool host_coarsen = (aggressive && !(two_stage && pmis_type)) || !pmis_type;
     Strength S;
@@ -1877,6 +2049,11 @@ void BoomerAMG::build_natural(ParCSR &A0) {
         dcf1.release();
         p_on_device = true;
       }
+      if (mm_interp) {  // two operand builders and sk::spgemm: rows of any length stay on the device
+        const int bad = sk::mm_interp(Lv.sA, dS, dcf, p.interp_type, p.trunc_factor, p.pmax_elmts, Lv.sP, nc, s);
+        if (bad >= 0) mm_interp_zero_denominator(p.interp_type, l, bad);
+        p_on_device = true;
+      }
       if (p_on_device) {
         // stays on the device; the dimensions are all the host needs
         Lv.P = HostCSR();
@@ -1909,6 +2086,8 @@ void BoomerAMG::build_natural(ParCSR &A0) {
                             p.agg_pmax_elmts, l, Lv.P, nc);
       } else if (aggressive)
         build_multipass(A, S, cf, p.agg_trunc_factor, p.agg_pmax_elmts, Lv.P, nc);
+      else if (mm_interp)
+        build_mm_interp(A, S, cf, p.interp_type, p.trunc_factor, p.pmax_elmts, l, Lv.P, nc);
       else if (p.interp_type == 4)  // multipass interpolation on an ordinary splitting (its first pass is all there is
         build_multipass(A, S, cf, p.trunc_factor, p.pmax_elmts, Lv.P, nc);  // unless F points lack a strong C point)
       else

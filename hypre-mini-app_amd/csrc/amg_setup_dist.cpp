@@ -1523,6 +1523,8 @@ bool BoomerAMG::can_build_distributed() const {
   // The two-stage extended interpolation of aggressive levels (agg_interp_type 5) has no distributed form yet: such
   // hierarchies are built replicated, whatever the coarsening type.
   if (p.agg_num_levels > 0 && p.agg_interp_type == 5) return false;
+  // nor has the matrix-matrix extended interpolation (interp_type 16 / 17)
+  if (p.interp_type == 16 || p.interp_type == 17) return false;
   if (p.coarsen_type == 10 || p.coarsen_type == 11 || p.coarsen_type == 1 || p.coarsen_type == 6) return true;
   return !forced_off && (p.coarsen_type == 8 || p.coarsen_type == 9 || p.coarsen_type == 0 || p.coarsen_type == 7);
 }

@@ -750,6 +750,68 @@ HYPRE_Int HYPRE_MI_CSRReuseOp(HYPRE_Int op, HYPRE_Int a_nrows, HYPRE_Int a_ncols
   MI_HIP(hipStreamSynchronize(s));
   API_END
 }
+// The device routine of interp_type 16 / 17 (sk::mm_interp) on caller (host) arrays: A as CSR with ascending columns,
+// the pattern of S (rows ascending), the marker (+1 C, -1 F, -3 special F).  P is malloc'ed (HYPRE_MI_Free).
+// *bad_row = -1, or the first row with a zero denominator and a non-empty numerator: the call then fails, P is not made.
+HYPRE_Int HYPRE_MI_MMInterpOp(HYPRE_Int type, HYPRE_Int n, const HYPRE_BigInt *a_ia, const HYPRE_Int *a_ja,
+                              const HYPRE_Complex *a_a, const HYPRE_BigInt *s_ia, const HYPRE_Int *s_ja, const HYPRE_Int *cf,
+                              HYPRE_Real trunc_factor, HYPRE_Int pmax, HYPRE_Int lanes, HYPRE_Int *p_ncols,
+                              HYPRE_BigInt **p_ia, HYPRE_Int **p_ja, HYPRE_Complex **p_a, HYPRE_Int *bad_row) {
+  API_BEGIN
+  if (!a_ia || !s_ia || !p_ncols || !p_ia || !p_ja || !p_a || !bad_row) fail(HYPRE_ERROR_ARG, "MMInterpOp: NULL argument");
+  if (type != 16 && type != 17) fail(HYPRE_ERROR_ARG, "MMInterpOp: type must be 16 (extended) or 17 (extended+i)");
+  if (lanes < 0 || lanes > 64 || (lanes & (lanes - 1))) fail(HYPRE_ERROR_ARG, "MMInterpOp: lanes must be 0 or a power of two up to 64");
+  if (n < 0 || a_ia[0] != 0 || s_ia[0] != 0) fail(HYPRE_ERROR_ARG, "MMInterpOp: bad dimensions");
+  if (n > 0 && !cf) fail(HYPRE_ERROR_ARG, "MMInterpOp: NULL marker");
+  auto to_host = [n](const char *what, const HYPRE_BigInt *ia, const HYPRE_Int *ja, const HYPRE_Complex *a) {
+    HostCSR h;
+    h.nrows = h.ncols = n;
+    h.ia.assign(ia, ia + n + 1);
+    for (HYPRE_Int i = 0; i < n; i++)
+      if (ia[i + 1] < ia[i]) fail(HYPRE_ERROR_ARG, std::string("MMInterpOp: row pointers of ") + what + " decrease");
+    if (ia[n] > 0 && !ja) fail(HYPRE_ERROR_ARG, std::string("MMInterpOp: NULL columns of ") + what);
+    h.ja.assign(ja, ja + ia[n]);
+    for (HYPRE_Int i = 0; i < n; i++)
+      for (HYPRE_BigInt k = ia[i]; k < ia[i + 1]; k++)
+        if (ja[k] < 0 || ja[k] >= n || (k > ia[i] && ja[k] <= ja[k - 1]))
+          fail(HYPRE_ERROR_ARG, std::string("MMInterpOp: columns of ") + what + " out of range or not ascending");
+    if (a)
+      h.a.assign(a, a + ia[n]);
+    else
+      h.a.assign((size_t)ia[n], 0.0);
+    return h;
+  };
+  if (a_ia[n] > 0 && !a_a) fail(HYPRE_ERROR_ARG, "MMInterpOp: NULL values of A");
+  for (HYPRE_Int i = 0; i < n; i++)
+    if (cf[i] != 1 && cf[i] != -1 && cf[i] != -3) fail(HYPRE_ERROR_ARG, "MMInterpOp: the marker holds a value other than 1, -1, -3");
+  const HostCSR hA = to_host("A", a_ia, a_ja, a_a), hS = to_host("S", s_ia, s_ja, nullptr);
+  ensure_init();
+  hipStream_t s = ctx().stream;
+  sk::DCsr dA, dS, dP;
+  dA.upload(hA, s);
+  dS.upload(hS, s);
+  DVec<int> dcf;
+  dcf.upload(std::vector<int>(cf, cf + n));
+  int nc = 0;
+  const int bad = sk::mm_interp(dA, dS, dcf, type, trunc_factor, pmax, dP, nc, s, lanes);
+  *bad_row = bad;
+  if (bad >= 0)
+    fail(HYPRE_ERROR_ARG, "MMInterpOp: interp_type " + std::to_string(type) + ": row " + std::to_string(bad) +
+                              " has a zero denominator d_i with a non-empty numerator");
+  HostCSR hp;
+  if (n > 0) dP.download(hp, s);
+  *p_ncols = nc;
+  *p_ia = (HYPRE_BigInt *)malloc(sizeof(HYPRE_BigInt) * ((size_t)n + 1));
+  *p_ja = (HYPRE_Int *)malloc(sizeof(HYPRE_Int) * std::max<size_t>(1, hp.ja.size()));
+  *p_a = (HYPRE_Complex *)malloc(sizeof(HYPRE_Complex) * std::max<size_t>(1, hp.a.size()));
+  (*p_ia)[0] = 0;
+  for (int i = 1; i <= n; i++) (*p_ia)[i] = hp.ia[(size_t)i];
+  if (!hp.ja.empty()) {
+    memcpy(*p_ja, hp.ja.data(), hp.ja.size() * sizeof(int));
+    memcpy(*p_a, hp.a.data(), hp.a.size() * sizeof(double));
+  }
+  API_END
+}
 // setup-phase sparse kernels on caller (host) CSR arrays; results are malloc'ed (HYPRE_MI_Free)
 HYPRE_Int HYPRE_MI_CSRDeviceOp(HYPRE_Int op, HYPRE_Int a_nrows, HYPRE_Int a_ncols, const HYPRE_BigInt *a_ia,
                                const HYPRE_Int *a_ja, const HYPRE_Complex *a_a, HYPRE_Int b_nrows, HYPRE_Int b_ncols,

@@ -3747,6 +3747,8 @@ __global__ __launch_bounds__(BLK) void agg2s_beta_k(int n, const long long *__re
 }
 
 // right operand M: C row -> e_k; other rows with beta_k != 0 -> a_kl / beta_k over the strong C neighbours
+// (SCALED = false: a_kl itself, the right operand of interp_type 17)
+template <bool SCALED>
 __global__ __launch_bounds__(BLK) void agg2s_m_fill_k(int n, const long long *__restrict__ ia, const int *__restrict__ ja,
                                                       const double *__restrict__ a, const long long *__restrict__ sia,
                                                       const int *__restrict__ sja, const int *__restrict__ m,
@@ -3770,7 +3772,7 @@ __global__ __launch_bounds__(BLK) void agg2s_m_fill_k(int n, const long long *__
     while (ks < kse && sja[ks] < l) ks++;
     if (ks < kse && sja[ks] == l && m[l] == C_PT) {
       mja[w] = (int)crank[l];
-      ma[w] = a[q] / bk;
+      ma[w] = SCALED ? a[q] / bk : a[q];
       w++;
     }
   }
@@ -3983,7 +3985,7 @@ void two_stage_stage(const DCsr &A, const DCsr &S, const int *m, const int *rows
   M.nnz = scan_total(cnt.p, M.ia.p, n, s);
   M.ja.alloc((size_t)M.nnz);
   M.a.alloc((size_t)M.nnz);
-  agg2s_m_fill_k<<<gn, BLK, 0, s>>>(n, A.ia.p, A.ja.p, A.a.p, S.ia.p, S.ja.p, m, crank.p, beta.p, M.ia.p, M.ja.p, M.a.p);
+  agg2s_m_fill_k<true><<<gn, BLK, 0, s>>>(n, A.ia.p, A.ja.p, A.a.p, S.ia.p, S.ja.p, m, crank.p, beta.p, M.ia.p, M.ja.p, M.a.p);
   Lo.nrows = nr, Lo.ncols = n;
   Lo.ia.alloc((size_t)nr + 1);
   agg2s_left_k<false><<<gr, BLK, 0, s>>>(nr, rows, A.ia.p, A.ja.p, A.a.p, S.ia.p, S.ja.p, m, beta.p, cnt.p, nullptr, nullptr, nullptr, nullptr);
@@ -4244,6 +4246,163 @@ void level_norms(const DevCSR &A, const int *cf, int chunk, double *diag, double
   DVec<long long> ai;
   level_norms(ref_of(A, ai, s), cf, chunk, diag, l1gs, l1jac, s, nullptr, nullptr);
   MI_HIP(hipStreamSynchronize(s));  // (the widened row pointers are released on return)
+}
+
+// ---------------------------------------------------------------- matrix-matrix extended interpolation (interp_type
+// 16 / 17; amg_setup.cpp build_mm_interp).  Type 16 is the stage operator E(A, S, cf) above; type
+// 17 has operands of its own: the left one needs the stored entry a_ki for every strong neighbour k of row i that is
+// not a C point, found by bisection in row k.
+namespace {
+// Left operand B and d of interp_type 17, G lanes per row.  A lane takes entry t0 + sub of row i: membership in S_i by
+// bisection, then kind 0 (its term goes to d_i: the diagonal, a weak entry, a strong neighbour with beta_k = 0 or
+// beta_k + a_ki = 0), 1 (a strong C neighbour: b_ik = a_ik) or 2 (b_ik = a_ik / (beta_k + a_ki), term b_ik * a_ki).
+// B's entries are placed by a ballot; the terms of a chunk are passed round the group by shuffles and every lane adds
+// them in stored order, so d_i is hs::mm_extpi_operands' sum whatever G is.  C row -> (i, 1); special F row -> nothing.
+// FILL = false: the lengths
+template <bool FILL, int G>
+__global__ __launch_bounds__(BLK) void mm_left_k(int n, const long long *__restrict__ ia, const int *__restrict__ ja,
+                                                 const double *__restrict__ a, const long long *__restrict__ sia,
+                                                 const int *__restrict__ sja, const int *__restrict__ m,
+                                                 const double *__restrict__ beta, int *__restrict__ cnt,
+                                                 const long long *__restrict__ bia, int *__restrict__ bja,
+                                                 double *__restrict__ ba, double *__restrict__ d) {
+  const long long r = (bid() * BLK + threadIdx.x) / G;
+  const int sub = threadIdx.x % G, lane = threadIdx.x & 63, gbase = lane - sub;
+  const bool live = r < n;
+  const int i = live ? (int)r : 0;
+  const int mi = live ? m[i] : SF_PT;
+  const bool frow = mi == F_PT;
+  const long long q0 = frow ? ia[i] : 0, q1 = frow ? ia[i + 1] : 0;
+  const long long s0 = frow ? sia[i] : 0, s1 = frow ? sia[i + 1] : 0;
+  const int len = (int)(q1 - q0);
+  // the trip count of the loop with cross-lane steps: the longest row of the wave
+  int wlen = len;
+  for (int mm = G; mm < 64; mm <<= 1) wlen = max(wlen, __shfl_xor(wlen, mm, 64));
+  const unsigned long long gmask = (G == 64) ? ~0ull : ((1ull << G) - 1ull);
+  long long w = (FILL && live) ? bia[i] : 0;
+  const long long wend = (FILL && live) ? bia[i + 1] : 0;
+  int c = 0;
+  double di = 0.0;
+  for (int t0 = 0; t0 < wlen; t0 += G) {
+    const int t = t0 + sub;
+    int kind = -1, j = 0;
+    double bv = 0.0, term = 0.0;
+    if (t < len) {
+      const long long q = q0 + t;
+      j = ja[q];
+      const double v = a[q];
+      kind = 0, term = v;
+      if (find_col(sja, s0, s1, j) >= 0) {
+        if (m[j] == C_PT) {
+          kind = 1, bv = v;
+        } else {
+          const double bj = beta[j];
+          if (bj != 0.0) {
+            const long long pos = find_col(ja, ia[j], ia[j + 1], i);
+            const double aki = pos >= 0 ? a[pos] : 0.0;
+            const double delta = bj + aki;
+            if (delta != 0.0) {
+              kind = 2, bv = v / delta;
+              term = bv * aki;
+            }
+          }
+        }
+      }
+    }
+    const bool entry = kind > 0, has_term = kind == 0 || kind == 2;
+    const unsigned long long mine = (__ballot(entry) >> gbase) & gmask;
+    if (FILL) {
+      const long long q = w + __popcll(mine & ((1ull << sub) - 1ull));
+      if (entry && q < wend) bja[q] = j, ba[q] = bv;
+      w += __popcll(mine);
+      if (G == 1) {
+        if (has_term) di += term;
+      } else {
+        const unsigned long long tmine = (__ballot(has_term) >> gbase) & gmask;
+        for (int u = 0; u < G; u++) {
+          const double tu = __shfl(term, gbase + u, 64);
+          if ((tmine >> u) & 1ull) di += tu;
+        }
+      }
+    } else {
+      c += __popcll(mine);
+    }
+  }
+  if (!live || sub != 0) return;
+  if (!FILL) {
+    cnt[i] = mi == C_PT ? 1 : c;
+    return;
+  }
+  if (mi == C_PT) bja[w] = i, ba[w] = 1.0;
+  d[i] = di;
+}
+
+// the extended+i interpolation in matrix-matrix form, truncated.  bad: device int, atomic minimum of the rows that
+// cannot be interpolated; lanes: lanes per row of the left-operand kernel (0: by the mean row length)
+void mm_extpi(const DCsr &A, const DCsr &S, const int *m, double trunc_factor, int pmax, DCsr &P, int &nc, int *bad,
+              int lanes, hipStream_t s) {
+  const int n = A.nrows;
+  const dim3 gn = grid_for(((long long)n + BLK - 1) / BLK);
+  DVec<long long> crank;
+  nc = (int)count_c_points(m, n, crank, s);
+  DVec<double> beta((size_t)n), d((size_t)n);
+  DVec<int> cnt((size_t)n);
+  DCsr Ah, B, N;
+  Ah.nrows = n, Ah.ncols = nc;
+  Ah.ia.alloc((size_t)n + 1);
+  agg2s_beta_k<<<gn, BLK, 0, s>>>(n, A.ia.p, A.ja.p, A.a.p, S.ia.p, S.ja.p, m, beta.p, cnt.p);
+  Ah.nnz = scan_total(cnt.p, Ah.ia.p, n, s);
+  Ah.ja.alloc((size_t)Ah.nnz);
+  Ah.a.alloc((size_t)Ah.nnz);
+  agg2s_m_fill_k<false><<<gn, BLK, 0, s>>>(n, A.ia.p, A.ja.p, A.a.p, S.ia.p, S.ja.p, m, crank.p, beta.p, Ah.ia.p, Ah.ja.p, Ah.a.p);
+  B.nrows = n, B.ncols = n;
+  B.ia.alloc((size_t)n + 1);
+  const int rg = lanes > 0 ? lanes : row_group(A.nnz, n);
+  const dim3 gl = grid_for(((long long)n * rg + BLK - 1) / BLK);
+  MI_ROW_GROUP_DISPATCH(rg, (mm_left_k<false, G><<<gl, BLK, 0, s>>>(n, A.ia.p, A.ja.p, A.a.p, S.ia.p, S.ja.p, m, beta.p, cnt.p, nullptr, nullptr, nullptr, nullptr)))
+  B.nnz = scan_total(cnt.p, B.ia.p, n, s);
+  B.ja.alloc((size_t)B.nnz);
+  B.a.alloc((size_t)B.nnz);
+  MI_ROW_GROUP_DISPATCH(rg, (mm_left_k<true, G><<<gl, BLK, 0, s>>>(n, A.ia.p, A.ja.p, A.a.p, S.ia.p, S.ja.p, m, beta.p, nullptr, B.ia.p, B.ja.p, B.a.p, d.p)))
+  MI_HIP(hipGetLastError());
+  spgemm(B, Ah, N, s);
+  B.release();
+  Ah.release();
+  if (N.nnz) {
+    const int sg = row_group(N.nnz, n);
+    MI_ROW_GROUP_DISPATCH(sg, (agg2s_scale_k<G><<<grid_for(((long long)n * sg + BLK - 1) / BLK), BLK, 0, s>>>(n, nullptr, m, d.p, N.ia.p, N.a.p, bad)))
+    MI_HIP(hipGetLastError());
+  }
+  truncate_rows(N, trunc_factor, pmax, P, s);
+  MI_HIP(hipStreamSynchronize(s));  // (the temporaries go away here)
+}
+}  // namespace
+
+int mm_interp(const DCsr &A, const DCsr &S, DVec<int> &cf, int interp_type, double trunc_factor, int pmax, DCsr &P,
+              int &nc, hipStream_t s, int lanes) {
+  MI_REQUIRE(interp_type == 16 || interp_type == 17, "device matrix-matrix interpolation: type 16 (extended) or 17 (extended+i)");
+  MI_REQUIRE(lanes >= 0 && lanes <= 64 && (lanes & (lanes - 1)) == 0, "device matrix-matrix interpolation: lanes must be 0 or a power of two up to 64");
+  const int n = A.nrows;
+  nc = 0;
+  if (n == 0) {
+    P.release();
+    P.ia.alloc(1);
+    MI_HIP(hipMemsetAsync(P.ia.p, 0, sizeof(long long), s));
+    MI_HIP(hipStreamSynchronize(s));
+    return -1;
+  }
+  StatusWord bad(s);
+  if (interp_type == 16)
+    two_stage_stage(A, S, cf.p, nullptr, n, trunc_factor, pmax, P, nc, bad.d.p, s);
+  else
+    mm_extpi(A, S, cf.p, trunc_factor, pmax, P, nc, bad.d.p, lanes, s);
+  const int first_bad = bad.read(s);
+  MI_HIP(hipStreamSynchronize(s));
+  if (first_bad >= 0) return first_bad;
+  agg_sf_to_f_k<<<grid_for(((long long)n + BLK - 1) / BLK), BLK, 0, s>>>(n, cf.p);
+  MI_HIP(hipGetLastError());
+  MI_HIP(hipStreamSynchronize(s));
+  return -1;
 }
 
 }  // namespace sk

@@ -64,6 +64,15 @@ void aggressive_second_stage(const DCsr &S, DVec<int> &cf, int seed, hipStream_t
 int two_stage_ext(const DCsr &A, const DCsr &S, const DVec<int> &m1, DVec<int> &m2, double p12_trunc_factor, int p12_max,
                   double trunc_factor, int pmax, DCsr &P, int &nc, hipStream_t s);
 
+// Extended (interp_type 16) and extended+i (17) interpolation in matrix-matrix form: two operand
+// builders, spgemm for the numerators, w = -n / d, truncation -- bit for bit hs::build_mm_interp; rows of any length.
+// Type 16 is the stage operator E(A, S, cf) of the two-stage interpolation.  Type 17's left operand is built with
+// `lanes` lanes per row (a power of two up to 64; 0 = by the mean row length): the result does not depend on it.
+// cf is updated like the host code does (-3 -> -1); nc = number of C points.  Returns -1, or the first row whose
+// denominator is zero while its numerator is not empty (cf then keeps its -3).
+int mm_interp(const DCsr &A, const DCsr &S, DVec<int> &cf, int interp_type, double trunc_factor, int pmax, DCsr &P,
+              int &nc, hipStream_t s, int lanes = 0);
+
 // C = A * B.  Rows of B must have ascending columns.  Entry (i, j) is the sum of
 // a_ik * b_kj taken in the stored order of A's row i (first product assigned,
 // the others added one by one) -- exactly host_spgemm (amg_setup.cpp) and the

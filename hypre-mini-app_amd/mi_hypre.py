@@ -1078,6 +1078,36 @@ def csr_reuse_op(op, A, pattern, P=None, rowmap=None, colmap=None, lanes=0):
     return out[: int(cia[-1])]
 
 
+def mm_interp_op(interp_type, A, S, cf, trunc_factor=0.0, pmax=0, lanes=0):
+    """The device routine of interp_type 16 / 17 (HYPRE_MI_MMInterpOp) on a scipy CSR operator A (ascending columns), the
+    pattern of the scipy CSR strength graph S and the marker cf (+1 C, -1 F, -3 special F).  Returns P as
+    (ia int64, ja int32, a f64, shape) exactly as the library stores it (a scipy constructor could drop nothing here,
+    but the arrays are what the bit comparisons want).  Raises HypreError with `bad_row` set when a row has a zero
+    denominator and a non-empty numerator."""
+    n = A.shape[0]
+    aia = np.ascontiguousarray(A.indptr, dtype=np.int64)
+    aja = np.ascontiguousarray(A.indices, dtype=np.int32)
+    aa = np.ascontiguousarray(A.data, dtype=np.float64)
+    sia = np.ascontiguousarray(S.indptr, dtype=np.int64)
+    sja = np.ascontiguousarray(S.indices, dtype=np.int32)
+    m = np.ascontiguousarray(cf, dtype=np.int32)
+    nc, bad = c_int(), c_int(-2)
+    pia, pja, pa = vp(), vp(), vp()
+    try:
+        call("HYPRE_MI_MMInterpOp", int(interp_type), n, aia, aja, aa, sia, sja, m, float(trunc_factor), int(pmax),
+             int(lanes), C.byref(nc), C.byref(pia), C.byref(pja), C.byref(pa), C.byref(bad))
+    except HypreError as e:
+        e.bad_row = bad.value
+        raise
+    ia = np.ctypeslib.as_array(C.cast(pia, C.POINTER(c_big)), shape=(n + 1,)).copy()
+    nnz = int(ia[-1])
+    ja = np.ctypeslib.as_array(C.cast(pja, C.POINTER(c_int)), shape=(max(nnz, 1),)).copy()[:nnz]
+    a = np.ctypeslib.as_array(C.cast(pa, C.POINTER(c_dbl)), shape=(max(nnz, 1),)).copy()[:nnz]
+    for ptr in (pia, pja, pa):
+        lib().HYPRE_MI_Free(ptr)
+    return ia, ja, a, (n, nc.value)
+
+
 VEC_MASS_DOT, VEC_MASS_AXPY, VEC_LIN_COMB, VEC_AXPY_DOT, VEC_SCALE_POST = range(5)
 
 

@@ -164,6 +164,18 @@ HYPRE_Int HYPRE_MI_CSRReuseOp(HYPRE_Int op, HYPRE_Int a_nrows, HYPRE_Int a_ncols
                               HYPRE_Int lanes, HYPRE_Int c_nrows, HYPRE_Int c_ncols, const HYPRE_BigInt *c_ia,
                               const HYPRE_Int *c_ja, HYPRE_Complex *c_a, HYPRE_Int *bad_row);
 
+/* ---- the device routine of the matrix-matrix extended interpolation (interp_type 16 extended / 17 extended+i; DESIGN.md
+ * section 3) on caller (host) arrays: the n x n operator A as CSR with ascending columns, the pattern of the strength
+ * graph S (rows ascending), the marker cf (+1 C, -1 F, -3 special F).  trunc_factor / pmax truncate as Setup does;
+ * lanes = lanes per row of the left-operand kernel of type 17 (a power of two up to 64; 0 = the library's choice): the
+ * result does not depend on it.  P (n x *p_ncols, columns = the C points in order) is malloc'ed: release with
+ * HYPRE_MI_Free.  *bad_row = -1, or the first row whose denominator is zero while its numerator is not empty: the call
+ * then fails with HYPRE_ERROR_ARG and P is not made. */
+HYPRE_Int HYPRE_MI_MMInterpOp(HYPRE_Int type, HYPRE_Int n, const HYPRE_BigInt *a_ia, const HYPRE_Int *a_ja,
+                              const HYPRE_Complex *a_a, const HYPRE_BigInt *s_ia, const HYPRE_Int *s_ja, const HYPRE_Int *cf,
+                              HYPRE_Real trunc_factor, HYPRE_Int pmax, HYPRE_Int lanes, HYPRE_Int *p_ncols,
+                              HYPRE_BigInt **p_ia, HYPRE_Int **p_ja, HYPRE_Complex **p_a, HYPRE_Int *bad_row);
+
 /* ---- setup reuse: mode 0 (default) = every Setup builds from scratch; 1 = a Setup on a handle that holds a finished
  * hierarchy of the same matrix object and pattern, built by the same entry point with the same structural settings on
  * one rank, keeps the splittings, orderings, P, R and all patterns and recomputes the values.  A Setup that cannot
