@@ -139,8 +139,29 @@ void IluSolver::setup(ParCSR &A, Comm &comm) {
   dpos.alloc((size_t)n);
   sk::ilu_diag_positions(LU, dpos.p, s);
   if (iter_type == 0) {
-    for (int l = 0; l < nl; l++)
-      sk::ilu_factor_level(LU, dpos.p, order_l.p + lptr[(size_t)l], lptr[(size_t)l + 1] - lptr[(size_t)l], s);
+    // A row without a stored diagonal or with u_jj == 0 has no ILU factorisation (HYPRE's host ILU(k) puts 1e-6 in
+    // place of a tiny pivot; here the setup ends).  The first is known from the pattern, before any kernel that reads
+    // a[dpos[i]] runs; the second after the last level.  One all-reduce: every rank learns of a failure anywhere.
+    long long bad_row = -1;
+    bool stored = true;
+    for (int i = 0; i < n && bad_row < 0; i++) {
+      const int *b = D.ja.data() + D.ia[(size_t)i], *e = D.ja.data() + D.ia[(size_t)i + 1];
+      if (!std::binary_search(b, e, i)) bad_row = i, stored = false;  // columns ascend
+    }
+    if (bad_row < 0) {
+      for (int l = 0; l < nl; l++)
+        sk::ilu_factor_level(LU, dpos.p, order_l.p + lptr[(size_t)l], lptr[(size_t)l + 1] - lptr[(size_t)l], s);
+      MI_HIP(hipGetLastError());
+      bad_row = sk::ilu_zero_pivot(LU, dpos.p, s);
+    }
+    double err = bad_row >= 0 ? 1.0 : 0.0;
+    comm.allreduce_host(&err, 1, CommDType::F64, CommOp::MAX);
+    if (bad_row >= 0)
+      fail(1, "HYPRE_ILUSetup: ILU(" + std::to_string(level_of_fill) + ") setup: zero pivot u_jj in row " +
+                  std::to_string(bad_row) + " of this rank's block (global row " +
+                  std::to_string((long long)A.row_start + bad_row) + ")" +
+                  (stored ? "" : ": the row stores no diagonal entry"));
+    if (err > 0.0) fail(1, "HYPRE_ILUSetup: ILU(" + std::to_string(level_of_fill) + ") setup failed on another rank");
   } else {
     iterative_factor(comm, (long long)A.row_start);
   }

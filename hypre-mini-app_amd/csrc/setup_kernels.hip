@@ -1528,6 +1528,8 @@ __global__ __launch_bounds__(BLK) void ilu_dpos_k(int n, const long long *__rest
   dpos[i] = d;
 }
 
+// Every kernel below but ilu_dpos_k relies on a stored diagonal in every row (dpos[i] >= 0): IluSolver::setup refuses a
+// pattern without one before it launches any of them.
 // one thread per row of the level: the oracle's IKJ loop, same operation order
 __global__ __launch_bounds__(BLK) void ilu_factor_k(int nrows, const int *__restrict__ rows,
                                                     const long long *__restrict__ ia, const int *__restrict__ ja,
@@ -1540,7 +1542,6 @@ __global__ __launch_bounds__(BLK) void ilu_factor_k(int nrows, const int *__rest
     const int k = ja[kk];
     if (k >= i) break;
     const long long dk = dpos[k];
-    if (dk < 0) continue;
     const double l = a[kk] / a[dk];
     a[kk] = l;
     long long pk = dk + 1;
@@ -1575,7 +1576,7 @@ __global__ __launch_bounds__(BLK) void ilu_upper_k(int nrows, const int *__restr
   double s = y[i];
   const long long d = dpos[i];
   for (long long k = d + 1; k < ia[i + 1]; k++) s -= a[k] * x[ja[k]];
-  x[i] = (d >= 0) ? s / a[d] : s;
+  x[i] = s / a[d];
 }
 
 // Jacobi sweeps: every row reads the previous iterate
@@ -1602,7 +1603,16 @@ __global__ __launch_bounds__(BLK) void ilu_upper_jac_k(int n, const long long *_
   const long long d = dpos[i];
   if (in)
     for (long long k = d + 1; k < ia[i + 1]; k++) s -= a[k] * in[ja[k]];
-  out[i] = (d >= 0) ? s / a[d] : s;
+  out[i] = s / a[d];
+}
+
+// the smallest row whose pivot is exactly zero after the factorisation (bad_row starts at all ones)
+__global__ __launch_bounds__(BLK) void ilu_zero_pivot_k(int n, const double *__restrict__ a,
+                                                        const long long *__restrict__ dpos,
+                                                        unsigned long long *__restrict__ bad_row) {
+  const long long i = bid() * BLK + threadIdx.x;
+  if (i >= n) return;
+  if (a[dpos[i]] == 0.0) atomicMin(bad_row, (unsigned long long)i);
 }
 
 // ---------------------------------------------------------------- iterative ILU(0) setup (fixed-point sweeps)
@@ -2900,6 +2910,18 @@ void ilu_upper_jacobi(const DCsr &LU, const long long *dpos, const double *b, co
                       hipStream_t s) {
   const int n = LU.nrows;
   if (n) ilu_upper_jac_k<<<(unsigned)((n + BLK - 1) / BLK), BLK, 0, s>>>(n, LU.ia.p, LU.ja.p, LU.a.p, dpos, b, in, out);
+}
+
+long long ilu_zero_pivot(const DCsr &LU, const long long *dpos, hipStream_t s) {
+  const int n = LU.nrows;
+  if (n == 0) return -1;
+  DVec<unsigned long long> bad(1);
+  MI_HIP(hipMemsetAsync(bad.p, 0xff, sizeof(unsigned long long), s));
+  ilu_zero_pivot_k<<<(unsigned)((n + BLK - 1) / BLK), BLK, 0, s>>>(n, LU.a.p, dpos, bad.p);
+  MI_HIP(hipGetLastError());
+  unsigned long long b = 0;
+  d2h(&b, bad.p, sizeof(b), s);
+  return b == ~0ull ? -1 : (long long)b;
 }
 
 int itilu_plan(const DCsr &LU, const long long *dpos, bool split, ItiluPlan &P, hipStream_t s) {

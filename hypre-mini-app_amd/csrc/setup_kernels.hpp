@@ -181,6 +181,9 @@ void level_norms(const DevCSR &A, const int *cf, int chunk, double *diag, double
 // ---- ILU(0) of a single-rank block (HYPRE_ILU type 0, fill 0), level-scheduled
 // position of the diagonal entry of every row (-1: none)
 void ilu_diag_positions(const DCsr &A, long long *dpos, hipStream_t s);
+// Everything below needs a stored diagonal in every row (dpos[i] >= 0): the caller refuses a pattern without one.
+// The smallest row whose pivot u_ii is exactly zero, or -1 (one small download)
+long long ilu_zero_pivot(const DCsr &LU, const long long *dpos, hipStream_t s);
 // in-place IKJ factorisation of the rows rows[0..nrows) -- one level set: every row they depend on is final
 void ilu_factor_level(DCsr &LU, const long long *dpos, const int *rows, int nrows, hipStream_t s);
 // forward / backward substitution for one level set: y[i] = b[i] - sum_{k<i} l_ik y_k ;

@@ -105,7 +105,8 @@ struct IluSolver : SolverBase {
   int num_iterations = 0;
   double final_rel_res = 0.0;
   IluSolver() : SolverBase(K_ILU) {}
-  // every rank of comm calls it (the iterative setup agrees on failures and reports over comm)
+  // every rank of comm calls it (both setups agree on failures over comm; the iterative one also reports over it).
+  // A row without a stored diagonal or an exactly zero pivot u_jj ends it with an error that names the row.
   void setup(ParCSR &A, Comm &comm);
   void iterative_factor(Comm &comm, long long row0);
   void apply(const double *rhs, double *out);           // out = U^-1 L^-1 rhs

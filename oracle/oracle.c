@@ -1615,9 +1615,14 @@ static void finish_levels(oamg *h) {
     L->old = (double *)xcalloc((size_t)n, sizeof(double));
     if (L->P) L->R = ocsr_transpose(L->P);
     /* par_amg_setup.c: HYPRE_ILUCreate/Setup per level j < smooth_num_levels (not the coarsest) */
-    if (h->p.smooth_type == 5 && l < h->p.smooth_num_levels && l < h->nlev - 1)
+    if (h->p.smooth_type == 5 && l < h->p.smooth_num_levels && l < h->nlev - 1) {
       L->smoother = oilu_setup_k(L->A, h->p.nparts, L->part_starts, h->p.ilu_tri_solve, h->p.ilu_lower_it, h->p.ilu_upper_it,
                                  h->p.ilu_level);
+      if (!L->smoother) { /* never a quiet change of smoother */
+        fprintf(stderr, "oracle: level %d has no ILU factorisation (a missing or zero pivot)\n", l);
+        abort();
+      }
+    }
   }
   olevel *Lc = &h->L[h->nlev - 1];
   if (h->p.relax_type[2] == 9 && Lc->A->nrows <= ORACLE_MAX_DENSE) {
@@ -2258,12 +2263,18 @@ oilu *oilu_setup_k(const ocsr *A, int nparts, const obig *part_starts, int tri_s
         if (LU->ja[k] == i) h->dpos[i] = k;
     }
   }
+  h->LU = LU;
+  /* a row without a stored diagonal has no factorisation: refused, like an exactly zero pivot below */
+  for (int i = 0; i < n; i++)
+    if (h->dpos[i] < 0) {
+      oilu_free(h);
+      return NULL;
+    }
   /* IKJ: for k < i in row i (ascending): l_ik = a_ik / u_kk ; a_ij -= l_ik u_kj for j > k in both patterns */
   for (int i = 0; i < n; i++) {
     for (obig kk = LU->ia[i]; kk < LU->ia[i + 1]; kk++) {
       const int k = LU->ja[kk];
       if (k >= i) break;
-      if (h->dpos[k] < 0) continue;
       const double l = LU->a[kk] / LU->a[h->dpos[k]];
       LU->a[kk] = l;
       obig pk = h->dpos[k] + 1; /* entries of row k right of its diagonal */
@@ -2275,7 +2286,11 @@ oilu *oilu_setup_k(const ocsr *A, int nparts, const obig *part_starts, int tri_s
       }
     }
   }
-  h->LU = LU;
+  for (int i = 0; i < n; i++)
+    if (LU->a[h->dpos[i]] == 0.0) {
+      oilu_free(h);
+      return NULL;
+    }
   return h;
 }
 
@@ -2302,7 +2317,7 @@ void oilu_apply(const oilu *h, const double *r, double *z) {
       double s = y[i];
       const obig d = h->dpos[i];
       for (obig k = d + 1; k < LU->ia[i + 1]; k++) s -= LU->a[k] * z[LU->ja[k]];
-      z[i] = (d >= 0) ? s / LU->a[d] : s;
+      z[i] = s / LU->a[d];
     }
   } else {
     /* Jacobi iterations on the triangular systems: y <- r - L_strict y ;  z <- D^-1 (y - U_strict z) */
@@ -2316,13 +2331,13 @@ void oilu_apply(const oilu *h, const double *r, double *z) {
       }
       memcpy(y, t, sizeof(double) * (size_t)n);
     }
-    for (int i = 0; i < n; i++) z[i] = (h->dpos[i] >= 0) ? y[i] / LU->a[h->dpos[i]] : y[i];
+    for (int i = 0; i < n; i++) z[i] = y[i] / LU->a[h->dpos[i]];
     for (int it = 0; it < h->upper_it; it++) {
       for (int i = 0; i < n; i++) {
         double s = y[i];
         const obig d = h->dpos[i];
         for (obig k = d + 1; k < LU->ia[i + 1]; k++) s -= LU->a[k] * z[LU->ja[k]];
-        t[i] = (d >= 0) ? s / LU->a[d] : s;
+        t[i] = s / LU->a[d];
       }
       memcpy(z, t, sizeof(double) * (size_t)n);
     }

@@ -141,7 +141,8 @@ void omulti_precond(void *ctx, const double *r, double *z);
 typedef struct oilu oilu;
 oilu *oilu_setup(const ocsr *A, int nparts, const obig *part_starts, int tri_solve, int lower_it, int upper_it);
 /* the same with level of fill k (HYPRE_ILUSetLevelOfFill, src/HypreSystem.cpp:345-349; ILU(k), Saad: an entry of the
- * factors is kept when its level  lev(i,j) = min over k of lev(i,k) + lev(k,j) + 1  (0 on A's pattern) is <= k) */
+ * factors is kept when its level  lev(i,j) = min over k of lev(i,k) + lev(k,j) + 1  (0 on A's pattern) is <= k).
+ * Both return NULL when a row of the (filled) block pattern stores no diagonal or a pivot u_jj is exactly zero. */
 oilu *oilu_setup_k(const ocsr *A, int nparts, const obig *part_starts, int tri_solve, int lower_it, int upper_it, int level_of_fill);
 void oilu_free(oilu *h);
 const ocsr *oilu_factor(const oilu *h);                 /* L (unit, strictly lower part) and U in A's pattern */

@@ -315,6 +315,8 @@ class Ilu:
         ps = None if part_starts is None else np.ascontiguousarray(part_starts, dtype=np.int64)
         self._ps = ps
         self.h = lib().oilu_setup_k(A.h, 0 if ps is None else len(ps) - 1, _ptr(ps), tri_solve, lower_it, upper_it, level_of_fill)
+        if not self.h:
+            raise ValueError("ILU: a row stores no diagonal entry, or a pivot u_jj is exactly zero")
         self.is_ilu = True
 
     def factor(self):

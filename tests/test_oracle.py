@@ -330,6 +330,23 @@ def test_iluk_pattern_factor_and_limit(oc, fill):
     assert itk < it0, (itk, it0)
 
 
+@pytest.mark.parametrize("kind", ["missing", "stored_zero", "eliminated"])
+def test_ilu_refuses_a_missing_or_zero_pivot(oc, kind):
+    """A row without a stored diagonal has no pivot, and an exactly zero pivot (stored, or reached by elimination)
+    cannot be divided by: the setup reports it instead of returning factors, at every fill and for both solves."""
+    from tests.ilu_cases import refused
+
+    M, _ = refused(kind)
+    A = oc.Csr.from_scipy(M)
+    for fill in (0, 1):
+        for tri in (0, 1):
+            with pytest.raises(ValueError):
+                oc.Ilu(A, level_of_fill=fill, tri_solve=tri)
+    good = refused("good")[0]
+    ilu = oc.Ilu(oc.Csr.from_scipy(good))
+    assert np.allclose(ilu.apply(good @ np.ones(6)), 1.0, rtol=1e-14)
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # Aggressive coarsening + multipass interpolation against an independent restatement (VERDICT r2 item 8): the
 # product and the oracle share one author, so `second_strength` / `build_multipass` are checked here against a
