@@ -12,6 +12,10 @@ struct AmgParams {
   int interp_type = 6;            // extended+i
   double strong_threshold = 0.25; // the app sets 0.57 (HypreSystem.cpp:159)
   double max_row_sum = 0.9;
+  // restriction: 0 = P^T, 1 = distance-1 approximate ideal restriction with its own strength
+  // threshold theta_R and the filter phi of its rows (HYPRE_BoomerAMGSetRestriction / StrongThresholdR / FilterThresholdR)
+  int restriction = 0;
+  double strong_threshold_r = 0.25, filter_threshold_r = 0.0;
   double trunc_factor = 0.0;
   int pmax_elmts = 4;
   int max_levels = 25;
@@ -127,6 +131,10 @@ struct AmgLevel {
   // routine or another device routine and the census is all zeros (a level that fell back has census.fell_back)
   sk::InterpCensus interp_census;
   bool interp_by_host = true;
+  // how this level's R was made (HYPRE_MI_BoomerAMGGetRestrictionInfo): 0 = the transpose of P, 1 = approximate ideal
+  // restriction built by the device, 2 = by the host routine; air_info: what that routine counted
+  int restriction_kind = 0;
+  sk::AirInfo air_info;
   bool has_cf = false;  // the level has a C/F splitting -- a GLOBAL fact (cf itself is empty on a rank without rows)
   DVec<signed char> d_cf;
   // C-first ordering of this level: perm[new] = old local row;

@@ -1048,6 +1048,197 @@ void build_mm_interp(const ParCSR &A, const Strength &S, std::vector<int> &cf, i
     if (cf[i] == SF_PT) cf[i] = F_PT;
 }
 
+void air_singular_system(int level, int row) {
+  fail(4, "BoomerAMGSetup: approximate ideal restriction (restriction 1) on level " + std::to_string(level) + ": row " +
+              std::to_string(row) + " has a singular local system A[N_i, N_i]; refusing to substitute another restriction");
+}
+
+// Distance-1 approximate ideal restriction (restriction 1; Manteuffel, Ruge, Southworth 2018; DESIGN.md section 3,
+// "Approximate ideal restriction"), bit for bit sk::air_restriction but for neighbourhoods of any size.  For a C point i,
+// N_i = the F columns j != i with |a_ij| >= theta_r * max_{k != i} |a_ik| (ascending); M[t][c] = a(N_c, N_t) and the
+// right-hand side -a(i, N_t) are eliminated with partial pivoting -- the pivot of step k is the unused row with the
+// largest |value| in column k, the lowest row on a tie; rows are not moved -- and substituted back by columns,
+// descending.  Row c(i) of R = (N_t, y_t), less the entries with |y_t| < phi * max_s |y_s| (phi > 0), and (i, 1.0).
+// Returns -1, or the smallest C row whose local system is singular (R is then not built).
+int build_air_restriction(const HostCSR &D, const std::vector<int> &cf, double theta_r, double phi, HostCSR &R,
+                          sk::AirInfo &info) {
+  const int n = D.nrows;
+  info = sk::AirInfo();
+  std::vector<int> c2f;
+  for (int i = 0; i < n; i++)
+    if (cf[(size_t)i] == C_PT) c2f.push_back(i);
+  const int nc = (int)c2f.size();
+  auto neighbourhood = [&](int i, auto &&emit) {
+    double mx = 0.0;
+    for (int64_t k = D.ia[(size_t)i]; k < D.ia[(size_t)i + 1]; k++)
+      if (D.ja[(size_t)k] != i) mx = std::fmax(mx, std::fabs(D.a[(size_t)k]));
+    if (!(mx > 0.0)) return;
+    const double thr = theta_r * mx;
+    for (int64_t k = D.ia[(size_t)i]; k < D.ia[(size_t)i + 1]; k++) {
+      const int j = D.ja[(size_t)k];
+      if (j == i || cf[(size_t)j] == C_PT || !(std::fabs(D.a[(size_t)k]) >= thr)) continue;
+      emit(j, D.a[(size_t)k]);
+    }
+  };
+  // a_rc: the stored entry (r, c), or 0
+  auto entry = [&](int r, int c) {
+    const int *r0 = D.ja.data() + D.ia[(size_t)r], *r1 = D.ja.data() + D.ia[(size_t)r + 1];
+    const int *it = std::lower_bound(r0, r1, c);
+    return (it != r1 && *it == c) ? D.a[(size_t)(it - D.ja.data())] : 0.0;
+  };
+  // rows with slack (1 + |N_i| entries), compacted afterwards
+  std::vector<int64_t> sia((size_t)nc + 1, 0);
+  parallel_for(nc, [&](int64_t b, int64_t e, int) {
+    for (int64_t c = b; c < e; c++) {
+      int m = 0;
+      neighbourhood(c2f[(size_t)c], [&](int, double) { m++; });
+      sia[(size_t)c + 1] = m + 1;
+    }
+  });
+  int max_m = 0, zero_rows = 0;
+  for (int c = 0; c < nc; c++) {
+    const int m = (int)sia[(size_t)c + 1] - 1;
+    max_m = std::max(max_m, m);
+    zero_rows += m == 0;
+    sia[(size_t)c + 1] += sia[(size_t)c];
+  }
+  std::vector<int> sja((size_t)sia[(size_t)nc]);
+  std::vector<double> sa((size_t)sia[(size_t)nc]);
+  std::vector<int> len((size_t)nc, 0);
+  std::atomic<int> bad{-1};
+  parallel_for(nc, [&](int64_t b, int64_t e, int) {
+    std::vector<int> N, piv, step;
+    std::vector<double> M, y;
+    std::vector<char> used;
+    for (int64_t c = b; c < e; c++) {
+      const int i = c2f[(size_t)c];
+      N.clear();
+      y.clear();
+      neighbourhood(i, [&](int j, double v) {
+        N.push_back(j);
+        y.push_back(v);  // g_t, for now
+      });
+      const int m = (int)N.size(), ld = m + 1;
+      M.assign((size_t)m * (size_t)ld, 0.0);
+      for (int t = 0; t < m; t++) {
+        for (int q = 0; q < m; q++) M[(size_t)t * ld + q] = entry(N[(size_t)q], N[(size_t)t]);
+        M[(size_t)t * ld + m] = -y[(size_t)t];
+      }
+      used.assign((size_t)m, 0);
+      step.assign((size_t)m, m);
+      piv.assign((size_t)m, 0);
+      bool singular = false;
+      for (int k = 0; k < m && !singular; k++) {
+        int idx = -1;
+        double v = -1.0;
+        for (int t = 0; t < m; t++)
+          if (!used[(size_t)t] && std::fabs(M[(size_t)t * ld + k]) > v) v = std::fabs(M[(size_t)t * ld + k]), idx = t;
+        if (!(v > 0.0)) {
+          singular = true;
+          break;
+        }
+        piv[(size_t)k] = idx;
+        used[(size_t)idx] = 1;
+        step[(size_t)idx] = k;
+        const double *Mp = &M[(size_t)idx * ld];
+        for (int t = 0; t < m; t++) {
+          if (used[(size_t)t]) continue;
+          double *Mt = &M[(size_t)t * ld];
+          const double l = Mt[k] / Mp[k];
+          for (int q = k + 1; q < m; q++) Mt[q] = Mt[q] - l * Mp[q];
+          Mt[m] = Mt[m] - l * Mp[m];
+        }
+      }
+      if (singular) {
+        int cur = bad.load();
+        while ((cur < 0 || i < cur) && !bad.compare_exchange_weak(cur, i)) {
+        }
+        continue;
+      }
+      for (int q = m - 1; q >= 0; q--) {
+        const double *Mp = &M[(size_t)piv[(size_t)q] * ld];
+        y[(size_t)q] = Mp[m] / Mp[q];
+        for (int t = 0; t < m; t++)
+          if (step[(size_t)t] < q) M[(size_t)t * ld + m] = M[(size_t)t * ld + m] - M[(size_t)t * ld + q] * y[(size_t)q];
+      }
+      double mx = 0.0;
+      if (phi > 0.0)
+        for (int t = 0; t < m; t++) mx = std::fmax(mx, std::fabs(y[(size_t)t]));
+      const double thr = phi * mx;
+      int64_t w = sia[(size_t)c];
+      bool unit_done = false;
+      for (int t = 0; t < m; t++) {
+        if (phi > 0.0 && std::fabs(y[(size_t)t]) < thr) continue;
+        if (!unit_done && N[(size_t)t] > i) sja[(size_t)w] = i, sa[(size_t)w] = 1.0, w++, unit_done = true;
+        sja[(size_t)w] = N[(size_t)t], sa[(size_t)w] = y[(size_t)t], w++;
+      }
+      if (!unit_done) sja[(size_t)w] = i, sa[(size_t)w] = 1.0, w++;
+      len[(size_t)c] = (int)(w - sia[(size_t)c]);
+    }
+  });
+  info.max_m = max_m;
+  info.zero_rows = zero_rows;
+  if (bad.load() >= 0) {
+    info.bad_row = bad.load();
+    return bad.load();
+  }
+  R.nrows = nc;
+  R.ncols = n;
+  R.ia.assign((size_t)nc + 1, 0);
+  for (int c = 0; c < nc; c++) R.ia[(size_t)c + 1] = R.ia[(size_t)c] + len[(size_t)c];
+  R.ja.resize((size_t)R.nnz());
+  R.a.resize((size_t)R.nnz());
+  parallel_for(nc, [&](int64_t b, int64_t e, int) {
+    for (int64_t c = b; c < e; c++) {
+      memcpy(R.ja.data() + R.ia[(size_t)c], sja.data() + sia[(size_t)c], (size_t)len[(size_t)c] * sizeof(int));
+      memcpy(R.a.data() + R.ia[(size_t)c], sa.data() + sia[(size_t)c], (size_t)len[(size_t)c] * sizeof(double));
+    }
+  });
+  info.dropped = sia[(size_t)nc] - R.nnz();
+  return -1;
+}
+
+// One-point interpolation (interp_type 100), bit for bit sk::one_point_interp: a C point i gets
+// (c(i), 1.0); an F point i the C point j of its row of S with the largest |a_ij|, the lowest column on a tie, as
+// (c(j), 1.0) -- or an empty row.  Truncation does not apply.  cf is handed on with special F -> F.
+void build_one_point_interp(const HostCSR &D, const Strength &S, std::vector<int> &cf, HostCSR &P, int &nc_out) {
+  const int n = D.nrows;
+  std::vector<int> f2c((size_t)n, -1), sel((size_t)n, -1);
+  int nc = 0;
+  for (int i = 0; i < n; i++)
+    if (cf[(size_t)i] == C_PT) f2c[(size_t)i] = nc++;
+  nc_out = nc;
+  parallel_for(n, [&](int64_t b, int64_t e, int) {
+    for (int64_t i = b; i < e; i++) {
+      if (cf[(size_t)i] == C_PT) {
+        sel[(size_t)i] = f2c[(size_t)i];
+        continue;
+      }
+      double best = -1.0;
+      int64_t ks = S.ia[(size_t)i];
+      const int64_t kse = S.ia[(size_t)i + 1];
+      for (int64_t k = D.ia[(size_t)i]; k < D.ia[(size_t)i + 1] && ks < kse; k++) {
+        const int j = D.ja[(size_t)k];
+        while (ks < kse && S.ja[(size_t)ks] < j) ks++;
+        if (ks < kse && S.ja[(size_t)ks] == j && cf[(size_t)j] == C_PT && std::fabs(D.a[(size_t)k]) > best)
+          best = std::fabs(D.a[(size_t)k]), sel[(size_t)i] = f2c[(size_t)j];
+      }
+    }
+  });
+  P.nrows = n;
+  P.ncols = nc;
+  P.ia.assign((size_t)n + 1, 0);
+  for (int i = 0; i < n; i++) P.ia[(size_t)i + 1] = P.ia[(size_t)i] + (sel[(size_t)i] >= 0);
+  P.ja.resize((size_t)P.nnz());
+  P.a.assign((size_t)P.nnz(), 1.0);
+  parallel_for(n, [&](int64_t b, int64_t e, int) {
+    for (int64_t i = b; i < e; i++)
+      if (sel[(size_t)i] >= 0) P.ja[(size_t)P.ia[(size_t)i]] = sel[(size_t)i];
+  });
+  for (size_t i = 0; i < cf.size(); i++)
+    if (cf[i] == SF_PT) cf[i] = F_PT;
+}
+
 void dense_inverse(int n, std::vector<double> &M, std::vector<double> &inv) {
   inv.assign((size_t)n * n, 0.0);
   for (int i = 0; i < n; i++) inv[(size_t)i * n + i] = 1.0;
@@ -1467,11 +1658,19 @@ void BoomerAMG::apply_cf_ordering() {
     }
     if (Lv.P.nrows > 0 && (has_pos[l] || (l + 1 < nlev && has_pos[l + 1]))) {
       const bool map_cols = l + 1 < nlev && has_pos[l + 1];
+      // an approximate ideal restriction is not the transpose of P: its natural-order copy is renumbered -- rows by the
+      // coarse level's order, columns by this level's positions
+      const bool own_R = Lv.restriction_kind != 0;
       if (Lv.sP.nnz > 0 && Lv.sP.nrows == Lv.P.nrows) {
         hipStream_t s = ctx().stream;
         sk::permute(Lv.sP, Lv.perm.empty() ? nullptr : Lv.perm.dev(), map_cols ? dpos(l + 1) : nullptr, Lv.oP, s);
         Lv.sP.release();
-        sk::transpose(Lv.oP, Lv.oR, s);
+        if (own_R) {
+          sk::permute(Lv.sR, map_cols ? L[l + 1].perm.dev() : nullptr, has_pos[l] ? dpos(l) : nullptr, Lv.oR, s);
+          Lv.sR.release();
+        } else {
+          sk::transpose(Lv.oP, Lv.oR, s);
+        }
         const int pr = Lv.P.nrows, pc = Lv.P.ncols;
         Lv.P = HostCSR();
         Lv.R = HostCSR();
@@ -1481,7 +1680,14 @@ void BoomerAMG::apply_cf_ordering() {
         HostCSR P2;
         permute(Lv.P, Lv.perm.host(), map_cols ? hpos(l + 1).data() : nullptr, P2);
         Lv.P = std::move(P2);
-        host_transpose(Lv.P, Lv.R);
+        if (own_R) {
+          static const std::vector<int> identity;
+          HostCSR R2;
+          permute(Lv.R, map_cols ? L[l + 1].perm.host() : identity, has_pos[l] ? hpos(l).data() : nullptr, R2);
+          Lv.R = std::move(R2);
+        } else {
+          host_transpose(Lv.P, Lv.R);
+        }
       }
     } else if (Lv.P.nrows > 0 && !Lv.P.ia.empty() && Lv.R.nrows == 0) {
       host_transpose(Lv.P, Lv.R);  // no renumbering on either side: R was not built yet on the device path
@@ -1775,10 +1981,31 @@ void BoomerAMG::validate_settings() const {
                   " is not implemented (1 = the diagonally scaled operator is); refusing to smooth the unscaled one");
   }
   if (p.interp_type != 0 && p.interp_type != 3 && p.interp_type != 4 && p.interp_type != 6 && p.interp_type != 16 &&
-      p.interp_type != 17)
+      p.interp_type != 17 && p.interp_type != 100)
     fail(4, "BoomerAMGSetup: interp_type " + std::to_string(p.interp_type) +
                 " is not implemented (0 classical modified, 3 direct, 4 multipass, 6 extended+i, 16 extended and 17 extended+i in "
-                "matrix-matrix form are); refusing to substitute another one");
+                "matrix-matrix form, 100 one-point are); refusing to substitute another one");
+  if (p.restriction != 0 && p.restriction != 1)
+    fail(4, "BoomerAMGSetup: restriction " + std::to_string(p.restriction) +
+                " is not implemented (0 = the transpose of P and 1 = distance-1 approximate ideal restriction are); refusing "
+                "to substitute another one");
+  // (the two thresholds are refused whatever the restriction: a handle that holds one would build another R once
+  // restriction 1 is set)
+  if (!(p.strong_threshold_r >= 0.0))
+    fail(4, "BoomerAMGSetup: strong_threshold_r " + std::to_string(p.strong_threshold_r) +
+                " is not implemented (a value >= 0 is); refusing to build the restriction on another graph");
+  if (!(p.filter_threshold_r >= 0.0))
+    fail(4, "BoomerAMGSetup: filter_threshold_r " + std::to_string(p.filter_threshold_r) +
+                " is not implemented (a value >= 0 is); refusing to filter the restriction another way");
+  if (p.restriction == 1) {
+    if (p.agg_num_levels > 0)
+      fail(4, "BoomerAMGSetup: restriction 1 (approximate ideal restriction) with agg_num_levels " +
+                  std::to_string(p.agg_num_levels) + " is not implemented (it is on levels that are not aggressive); refusing "
+                  "to restrict an aggressive level with the transpose of P");
+    if (my_comm().size > 1)
+      fail(4, "BoomerAMGSetup: restriction 1 (approximate ideal restriction) is not implemented on more than one rank (" +
+                  std::to_string(my_comm().size) + " ranks); refusing to restrict with the transpose of P");
+  }
   if (p.smooth_num_levels > 0 && p.smooth_type != 5 && p.smooth_type != 4)
     fail(4, "BoomerAMGSetup: smooth_type " + std::to_string(p.smooth_type) + " on " + std::to_string(p.smooth_num_levels) +
                 " level(s) is not implemented (4 = FSAI and 5 = ILU are); refusing to smooth with something else");
@@ -1960,6 +2187,9 @@ void BoomerAMG::build_natural(ParCSR &A0) {
     const bool two_stage = aggressive && p.agg_interp_type == 5;
     // (interp_type 16 / 17: the matrix-matrix extended interpolation of the levels that are not aggressive)
     const bool mm_interp = !aggressive && (p.interp_type == 16 || p.interp_type == 17);
+    // (interp_type 100: one-point interpolation; restriction 1: R is the approximate ideal restriction, not P^T)
+    const bool one_point = !aggressive && p.interp_type == 100;
+    const bool air = p.restriction == 1;
     const bool pmis_type = p.coarsen_type == 8 || p.coarsen_type == 9;
     const bool host_coarsen = (aggressive && !(two_stage && pmis_type)) || !pmis_type;
     Strength S;
@@ -2054,6 +2284,10 @@ void BoomerAMG::build_natural(ParCSR &A0) {
         if (bad >= 0) mm_interp_zero_denominator(p.interp_type, l, bad);
         p_on_device = true;
       }
+      if (one_point) {  // one row per lane: rows of any length stay on the device
+        sk::one_point_interp(Lv.sA, dS, dcf, Lv.sP, nc, s);
+        p_on_device = true;
+      }
       if (p_on_device) {
         // stays on the device; the dimensions are all the host needs
         Lv.P = HostCSR();
@@ -2088,6 +2322,8 @@ void BoomerAMG::build_natural(ParCSR &A0) {
         build_multipass(A, S, cf, p.agg_trunc_factor, p.agg_pmax_elmts, Lv.P, nc);
       else if (mm_interp)
         build_mm_interp(A, S, cf, p.interp_type, p.trunc_factor, p.pmax_elmts, l, Lv.P, nc);
+      else if (one_point)
+        build_one_point_interp(A.diag, S, cf, Lv.P, nc);
       else if (p.interp_type == 4)  // multipass interpolation on an ordinary splitting (its first pass is all there is
         build_multipass(A, S, cf, p.trunc_factor, p.pmax_elmts, Lv.P, nc);  // unless F points lack a strong C point)
       else
@@ -2098,7 +2334,15 @@ void BoomerAMG::build_natural(ParCSR &A0) {
     else
       Lv.cf = cf;
     Lv.has_cf = true;
-    if (!on_device) host_transpose(Lv.P, Lv.R);
+    Lv.restriction_kind = 0;
+    Lv.air_info = sk::AirInfo();
+    if (!on_device && air) {
+      if (build_air_restriction(A.diag, cf, p.strong_threshold_r, p.filter_threshold_r, Lv.R, Lv.air_info) >= 0)
+        air_singular_system(l, Lv.air_info.bad_row);
+      Lv.restriction_kind = 2;
+    } else if (!on_device) {
+      host_transpose(Lv.P, Lv.R);
+    }
     t_phase[2] += wall_time() - tp0;
     tp0 = wall_time();
     trace_level.reset(), trace_level.reset(new TraceRange((lname + "Galerkin product").c_str()));
@@ -2111,8 +2355,26 @@ void BoomerAMG::build_natural(ParCSR &A0) {
       hipStream_t s = ctx().stream;
       if (!p_on_device) Lv.sP.upload(Lv.P, s);
       sk::DCsr dR_local, dAP;
-      sk::DCsr &dR = keep_natural_R ? Lv.sR : dR_local;  // the replicated setup slices R on the device later
-      sk::transpose(Lv.sP, dR, s);
+      // the replicated setup slices R on the device later; an approximate ideal restriction is renumbered, not rebuilt
+      sk::DCsr &dR = (keep_natural_R || air) ? Lv.sR : dR_local;
+      if (air) {
+        const int rc = sk::air_restriction(Lv.sA, Lv.cf.dev(), p.strong_threshold_r, p.filter_threshold_r, dR, Lv.air_info, s);
+        Lv.restriction_kind = 1;
+        if (rc == 1) {  // a neighbourhood outgrows the 64-lane solve: the host routine builds this level's R
+          if (A.host_diag_stale) {
+            Lv.sA.download(A.diag, s);
+            A.host_diag_stale = false;
+            A.ensure_offd_rows();
+          }
+          HostCSR Rh;
+          if (build_air_restriction(A.diag, Lv.cf.host(), p.strong_threshold_r, p.filter_threshold_r, Rh, Lv.air_info) < 0)
+            dR.upload(Rh, s);
+          Lv.restriction_kind = 2;
+        }
+        if (Lv.air_info.bad_row >= 0) air_singular_system(l, Lv.air_info.bad_row);
+      } else {
+        sk::transpose(Lv.sP, dR, s);
+      }
       sk::spgemm(Lv.sA, Lv.sP, dAP, s);
       L.emplace_back();  // the coarse operator is born on the device (L was reserved: references stay valid)
       sk::DCsr &dAc = L[(size_t)l + 1].sA;
@@ -3130,7 +3392,8 @@ const char *const REBUILD_REASON[7] = {"reuse is off",
                                        "first Setup of this handle, or the previous one failed",
                                        "another matrix object or another pattern",
                                        "a setting the structure depends on changed since the last Setup",
-                                       "a setting the refresh does not cover is on (non-Galerkin tolerances or value storage)",
+                                       "a setting the refresh does not cover is on (non-Galerkin tolerances, value storage, restriction 1 or "
+                                       "one-point interpolation)",
                                        "more than one rank",
                                        "the other setup entry point built the hierarchy"};
 }  // namespace
@@ -3153,7 +3416,7 @@ std::vector<double> BoomerAMG::current_structure_signature(const ParCSR &A) cons
                            (double)p.agg_p12_max_elmts, p.agg_p12_trunc_factor, (double)p.keep_agg_markers,
                            use_locality_order(A) ? 1.0 : 0.0, (double)chunk(), (double)zero_skip_mode(),
                            k::value_dictionary_enabled() ? 1.0 : 0.0, (double)p.value_storage, (double)p.value_first_level,
-                           p.non_galerkin_tol};
+                           p.non_galerkin_tol, (double)p.restriction, p.strong_threshold_r, p.filter_threshold_r};
   for (double t : p.non_galerkin_level_tol) v.push_back(t);
   const int t0 = p.relax_type[0];
   v.push_back((t0 == 3 || t0 == 4 || t0 == 6 || t0 == 8 || t0 == 13 || t0 == 14) ? 1.0 : 0.0);
@@ -3169,6 +3432,9 @@ int BoomerAMG::refresh_verdict(const ParCSR &A, bool entry_host_only) const {
   if (built_host_only != entry_host_only) return 6;
   if (built_matrix != &A || built_pattern != A.pattern_stamp) return 2;
   if (p.non_galerkin() || p.value_storage != 0) return 4;
+  // (the neighbourhoods and the filter of an approximate ideal restriction and the choice of one-point interpolation
+  // depend on the values: their patterns are not kept)
+  if (p.restriction != 0 || p.interp_type == 100) return 4;
   if (structure_signature != current_structure_signature(A)) return 3;
   return -1;
 }

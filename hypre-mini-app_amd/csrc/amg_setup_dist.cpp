@@ -1525,6 +1525,8 @@ bool BoomerAMG::can_build_distributed() const {
   if (p.agg_num_levels > 0 && p.agg_interp_type == 5) return false;
   // nor has the matrix-matrix extended interpolation (interp_type 16 / 17)
   if (p.interp_type == 16 || p.interp_type == 17) return false;
+  // nor has one-point interpolation (interp_type 100)
+  if (p.interp_type == 100) return false;
   if (p.coarsen_type == 10 || p.coarsen_type == 11 || p.coarsen_type == 1 || p.coarsen_type == 6) return true;
   return !forced_off && (p.coarsen_type == 8 || p.coarsen_type == 9 || p.coarsen_type == 0 || p.coarsen_type == 7);
 }

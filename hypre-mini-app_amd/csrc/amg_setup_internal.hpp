@@ -56,6 +56,13 @@ inline StrengthRule strength_rule(const double *a, int64_t len, int64_t dpos, do
 void build_interp(const ParCSR &A, const Strength &S, std::vector<int> &cf, int interp_type, double trunc_factor,
                   int pmax, HostCSR &P, int &nc_out, const std::vector<char> *want_rows = nullptr);
 
+// distance-1 approximate ideal restriction (restriction 1) of a square block D with the final marker cf: -1, or the
+// smallest C row with a singular local system (R is then not built); neighbourhoods of any size
+int build_air_restriction(const HostCSR &D, const std::vector<int> &cf, double theta_r, double phi, HostCSR &R,
+                          sk::AirInfo &info);
+// one-point interpolation (interp_type 100); cf is handed on with special F -> F
+void build_one_point_interp(const HostCSR &D, const Strength &S, std::vector<int> &cf, HostCSR &P, int &nc_out);
+
 // classical Ruge-Stueben coarsening of a graph (first pass; second_pass: strong F-F pairs must share a C point)
 void ruge_stueben(int n, const Strength &S, bool second_pass, std::vector<int> &cf);
 // truncation of one interpolation row in place (trunc_factor, pmax; rescaled to the row sum, stored order kept): new length

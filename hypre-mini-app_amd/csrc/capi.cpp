@@ -14,6 +14,7 @@
 #include "kernels.hpp"
 #include "profile.hpp"
 #include "solvers.hpp"
+#include "amg_setup_internal.hpp"
 
 using namespace mi;
 
@@ -812,6 +813,126 @@ HYPRE_Int HYPRE_MI_MMInterpOp(HYPRE_Int type, HYPRE_Int n, const HYPRE_BigInt *a
   }
   API_END
 }
+extern "C++" {
+namespace {
+// caller arrays of an n x n CSR with ascending columns, checked (a == null: a pattern, values 0)
+HostCSR square_csr_of(const std::string &who, const char *what, HYPRE_Int n, const HYPRE_BigInt *ia, const HYPRE_Int *ja,
+                      const HYPRE_Complex *a) {
+  HostCSR h;
+  h.nrows = h.ncols = n;
+  h.ia.assign(ia, ia + n + 1);
+  for (HYPRE_Int i = 0; i < n; i++)
+    if (ia[i + 1] < ia[i]) fail(HYPRE_ERROR_ARG, who + ": row pointers of " + what + " decrease");
+  if (ia[n] > 0 && !ja) fail(HYPRE_ERROR_ARG, who + ": NULL columns of " + what);
+  h.ja.assign(ja, ja + ia[n]);
+  for (HYPRE_Int i = 0; i < n; i++)
+    for (HYPRE_BigInt k = ia[i]; k < ia[i + 1]; k++)
+      if (ja[k] < 0 || ja[k] >= n || (k > ia[i] && ja[k] <= ja[k - 1]))
+        fail(HYPRE_ERROR_ARG, who + ": columns of " + what + " out of range or not ascending");
+  if (a)
+    h.a.assign(a, a + ia[n]);
+  else
+    h.a.assign((size_t)ia[n], 0.0);
+  return h;
+}
+// a HostCSR as malloc'ed caller arrays (HYPRE_MI_Free)
+void csr_to_caller(const HostCSR &h, int nrows, HYPRE_BigInt **ia, HYPRE_Int **ja, HYPRE_Complex **a) {
+  *ia = (HYPRE_BigInt *)malloc(sizeof(HYPRE_BigInt) * ((size_t)nrows + 1));
+  *ja = (HYPRE_Int *)malloc(sizeof(HYPRE_Int) * std::max<size_t>(1, h.ja.size()));
+  *a = (HYPRE_Complex *)malloc(sizeof(HYPRE_Complex) * std::max<size_t>(1, h.a.size()));
+  (*ia)[0] = 0;
+  for (int i = 1; i <= nrows; i++) (*ia)[i] = h.ia[(size_t)i];
+  if (!h.ja.empty()) {
+    memcpy(*ja, h.ja.data(), h.ja.size() * sizeof(int));
+    memcpy(*a, h.a.data(), h.a.size() * sizeof(double));
+  }
+}
+}  // namespace
+}  // extern "C++"
+// The approximate ideal restriction (restriction 1) on caller (host) arrays: the device routine sk::air_restriction
+// (on_host = 0) or the host routine hs::build_air_restriction (on_host = 1, no device needed).  info[8]: status (0 built,
+// 1 not built -- a neighbourhood above 64 entries, the device routine only --, 2 singular local system), the largest
+// |N_i|, the C rows with an empty N_i, the entries the filter dropped, the rows of the 16- / 32- / 64-lane
+// instantiation, the first singular row (-1).  Status 2 fails the call; status 1 does not, and R stays NULL.
+HYPRE_Int HYPRE_MI_AIRRestrictionOp(HYPRE_Int on_host, HYPRE_Int n, const HYPRE_BigInt *a_ia, const HYPRE_Int *a_ja,
+                                    const HYPRE_Complex *a_a, const HYPRE_Int *cf, HYPRE_Real strong_threshold_r,
+                                    HYPRE_Real filter_threshold_r, HYPRE_Int *r_nrows, HYPRE_BigInt **r_ia, HYPRE_Int **r_ja,
+                                    HYPRE_Complex **r_a, HYPRE_Int info[8]) {
+  API_BEGIN
+  const std::string who = "AIRRestrictionOp";
+  if (!a_ia || !cf || !r_nrows || !r_ia || !r_ja || !r_a || !info) fail(HYPRE_ERROR_ARG, who + ": NULL argument");
+  if (n < 1 || a_ia[0] != 0) fail(HYPRE_ERROR_ARG, who + ": bad dimensions");
+  if (a_ia[n] > 0 && !a_a) fail(HYPRE_ERROR_ARG, who + ": NULL values of A");
+  if (!(strong_threshold_r >= 0.0) || !(filter_threshold_r >= 0.0)) fail(HYPRE_ERROR_ARG, who + ": thresholds must be >= 0");
+  int nc = 0;
+  for (HYPRE_Int i = 0; i < n; i++) {
+    if (cf[i] != 1 && cf[i] != -1) fail(HYPRE_ERROR_ARG, who + ": the marker holds a value other than 1, -1");
+    nc += cf[i] == 1;
+  }
+  if (nc == 0) fail(HYPRE_ERROR_ARG, who + ": the marker has no C point");
+  const HostCSR hA = square_csr_of(who, "A", n, a_ia, a_ja, a_a);
+  *r_nrows = nc;
+  *r_ia = nullptr, *r_ja = nullptr, *r_a = nullptr;
+  sk::AirInfo ai;
+  HostCSR hr;
+  int status = 0;
+  if (on_host) {
+    status = hs::build_air_restriction(hA, std::vector<int>(cf, cf + n), strong_threshold_r, filter_threshold_r, hr, ai) >= 0 ? 2 : 0;
+  } else {
+    ensure_init();
+    hipStream_t s = ctx().stream;
+    sk::DCsr dA, dR;
+    dA.upload(hA, s);
+    DVec<int> dcf;
+    dcf.upload(std::vector<int>(cf, cf + n));
+    status = sk::air_restriction(dA, dcf.p, strong_threshold_r, filter_threshold_r, dR, ai, s);
+    if (status == 0) dR.download(hr, s);
+  }
+  const HYPRE_Int v[8] = {status, ai.max_m, ai.zero_rows, (HYPRE_Int)ai.dropped, ai.group_rows[0], ai.group_rows[1],
+                          ai.group_rows[2], ai.bad_row};
+  for (int i = 0; i < 8; i++) info[i] = v[i];
+  if (status == 2)
+    fail(HYPRE_ERROR_ARG, who + ": row " + std::to_string(ai.bad_row) + " has a singular local system A[N_i, N_i]");
+  if (status == 0) csr_to_caller(hr, nc, r_ia, r_ja, r_a);
+  API_END
+}
+// One-point interpolation (interp_type 100) on caller (host) arrays: the device routine sk::one_point_interp (on_host = 0)
+// or the host routine hs::build_one_point_interp (on_host = 1, no device needed).  The marker: +1 C, -1 F, -3 special F.
+HYPRE_Int HYPRE_MI_OnePointInterpOp(HYPRE_Int on_host, HYPRE_Int n, const HYPRE_BigInt *a_ia, const HYPRE_Int *a_ja,
+                                    const HYPRE_Complex *a_a, const HYPRE_BigInt *s_ia, const HYPRE_Int *s_ja,
+                                    const HYPRE_Int *cf, HYPRE_Int *p_ncols, HYPRE_BigInt **p_ia, HYPRE_Int **p_ja,
+                                    HYPRE_Complex **p_a) {
+  API_BEGIN
+  const std::string who = "OnePointInterpOp";
+  if (!a_ia || !s_ia || !cf || !p_ncols || !p_ia || !p_ja || !p_a) fail(HYPRE_ERROR_ARG, who + ": NULL argument");
+  if (n < 1 || a_ia[0] != 0 || s_ia[0] != 0) fail(HYPRE_ERROR_ARG, who + ": bad dimensions");
+  if (a_ia[n] > 0 && !a_a) fail(HYPRE_ERROR_ARG, who + ": NULL values of A");
+  for (HYPRE_Int i = 0; i < n; i++)
+    if (cf[i] != 1 && cf[i] != -1 && cf[i] != -3) fail(HYPRE_ERROR_ARG, who + ": the marker holds a value other than 1, -1, -3");
+  const HostCSR hA = square_csr_of(who, "A", n, a_ia, a_ja, a_a), hS = square_csr_of(who, "S", n, s_ia, s_ja, nullptr);
+  HostCSR hp;
+  int nc = 0;
+  if (on_host) {
+    hs::Strength S;
+    S.ia = hS.ia;
+    S.ja = hS.ja;
+    std::vector<int> m(cf, cf + n);
+    hs::build_one_point_interp(hA, S, m, hp, nc);
+  } else {
+    ensure_init();
+    hipStream_t s = ctx().stream;
+    sk::DCsr dA, dS, dP;
+    dA.upload(hA, s);
+    dS.upload(hS, s);
+    DVec<int> dcf;
+    dcf.upload(std::vector<int>(cf, cf + n));
+    sk::one_point_interp(dA, dS, dcf, dP, nc, s);
+    dP.download(hp, s);
+  }
+  *p_ncols = nc;
+  csr_to_caller(hp, n, p_ia, p_ja, p_a);
+  API_END
+}
 // setup-phase sparse kernels on caller (host) CSR arrays; results are malloc'ed (HYPRE_MI_Free)
 HYPRE_Int HYPRE_MI_CSRDeviceOp(HYPRE_Int op, HYPRE_Int a_nrows, HYPRE_Int a_ncols, const HYPRE_BigInt *a_ia,
                                const HYPRE_Int *a_ja, const HYPRE_Complex *a_a, HYPRE_Int b_nrows, HYPRE_Int b_ncols,
@@ -1180,6 +1301,10 @@ AMG_SET(MaxLevels, HYPRE_Int, if (v < 1) fail(HYPRE_ERROR_ARG, "max_levels < 1")
 AMG_SET(StrongThreshold, HYPRE_Real, p.strong_threshold = v)
 AMG_SET(MaxRowSum, HYPRE_Real, p.max_row_sum = v)
 AMG_SET(InterpType, HYPRE_Int, p.interp_type = v)  /* unknown types are refused at Setup, like every other choice */
+/* restriction: values the library does not build (2 and above, negative thresholds) are refused at Setup, by name */
+AMG_SET(Restriction, HYPRE_Int, p.restriction = v)
+AMG_SET(StrongThresholdR, HYPRE_Real, p.strong_threshold_r = v)
+AMG_SET(FilterThresholdR, HYPRE_Real, p.filter_threshold_r = v)
 AMG_SET(TruncFactor, HYPRE_Real, p.trunc_factor = v)
 AMG_SET(PMaxElmts, HYPRE_Int, p.pmax_elmts = v)
 AMG_SET(MinCoarseSize, HYPRE_Int, p.min_coarse_size = v)
@@ -2268,6 +2393,18 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetInterpCensus(HYPRE_Solver solver, HYPRE_Int level
   const HYPRE_Int v[8] = {c.cap16, c.cap32, c.try32_kept, c.try32_retried, c.cap512, c.cap1024, c.max_bound,
                           (c.fell_back ? 1 : 0) | (Lv.interp_by_host ? 2 : 0)};
   for (int i = 0; i < 8; i++) out[i] = v[i];
+  API_END
+}
+// how R of `level` was made: out[0] = 0 the transpose of P / 1 approximate ideal restriction built by the device / 2 by
+// the host routine; out[1] = the largest |N_i|, out[2] = the C rows with an empty N_i, out[3] = the entries the filter dropped
+HYPRE_Int HYPRE_MI_BoomerAMGGetRestrictionInfo(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int out[4]) {
+  API_BEGIN
+  if (!out) fail(HYPRE_ERROR_ARG, "BoomerAMGGetRestrictionInfo: NULL argument");
+  const AmgLevel &Lv = level_ref(AMG(solver), level);
+  out[0] = Lv.restriction_kind;
+  out[1] = Lv.air_info.max_m;
+  out[2] = Lv.air_info.zero_rows;
+  out[3] = (HYPRE_Int)Lv.air_info.dropped;
   API_END
 }
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelPerm(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int *perm) {

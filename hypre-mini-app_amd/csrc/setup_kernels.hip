@@ -4427,5 +4427,288 @@ int mm_interp(const DCsr &A, const DCsr &S, DVec<int> &cf, int interp_type, doub
   return -1;
 }
 
+
+// ---------------------------------------------------------------- approximate ideal restriction (restriction 1) and
+// one-point interpolation (interp_type 100); amg_setup.cpp build_air_restriction / build_one_point_interp, DESIGN.md
+// section 3.  One lane computes every value in a fixed order: bit for bit the host routines.
+namespace {
+// F-neighbourhood N_i of the C rows, one row per lane: the F columns j != i with |a_ij| >= theta_r * max_{k != i} |a_ik|,
+// ascending.  FILL = false: cnt[c(i)] = |N_i| and c2f[c(i)] = i; FILL = true: the columns and g = a(i, N_t) at nia[c(i)].
+template <bool FILL>
+__global__ __launch_bounds__(BLK) void air_neighbourhood_k(int n, const long long *__restrict__ ia, const int *__restrict__ ja,
+                                                           const double *__restrict__ a, const int *__restrict__ cf,
+                                                           const long long *__restrict__ crank, double theta_r,
+                                                           int *__restrict__ cnt, int *__restrict__ c2f,
+                                                           const long long *__restrict__ nia, int *__restrict__ nja,
+                                                           double *__restrict__ ng) {
+  const long long i = bid() * BLK + threadIdx.x;
+  if (i >= n || cf[i] != C_PT) return;
+  const long long c = crank[i];
+  double mx = 0.0;
+  for (long long k = ia[i]; k < ia[i + 1]; k++)
+    if (ja[k] != (int)i) mx = fmax(mx, fabs(a[k]));
+  int m = 0;
+  if (mx > 0.0) {
+    const double thr = theta_r * mx;
+    const long long o = FILL ? nia[c] : 0;
+    for (long long k = ia[i]; k < ia[i + 1]; k++) {
+      const int j = ja[k];
+      if (j == (int)i || cf[j] == C_PT || !(fabs(a[k]) >= thr)) continue;
+      if (FILL) nja[o + m] = j, ng[o + m] = a[k];
+      m++;
+    }
+  }
+  if (!FILL) cnt[c] = m, c2f[c] = (int)i;
+}
+
+// One row of R per group of GS lanes, the layout and the elimination of fsai_local_solve_k: with N = N_i (m entries,
+// ascending), lane t holds row t of M = A[N, N]^T in LDS (entry c = a(N_c, N_t), found by a binary search in A's sorted
+// row N_c) and the right-hand side -a(i, N_t) in column GS.  Gaussian elimination with partial pivoting: the pivot of
+// step k is the unused row with the largest |value| in column k, the lowest row on a tie; rows are not moved.  Back
+// substitution by columns, descending.  y goes to Y on N's pattern; status[c(i)] = 1 for a singular M.  No atomics.
+template <int GS>
+__global__ __launch_bounds__(64) void air_local_solve_k(const int *__restrict__ rows, int nlist,
+                                                        const long long *__restrict__ Aia, const int *__restrict__ Aja,
+                                                        const double *__restrict__ Aa, const long long *__restrict__ Nia,
+                                                        const int *__restrict__ Nja, const double *__restrict__ Ng,
+                                                        double *__restrict__ Y, unsigned char *__restrict__ status) {
+  constexpr int RPB = 64 / GS, LD = GS + 1;
+  __shared__ double M[RPB][GS][LD];
+  __shared__ double y[RPB][GS];
+  __shared__ int piv[RPB][GS];
+  const int g = threadIdx.x / GS, t = threadIdx.x % GS;
+  const long long q = bid() * RPB + g;
+  int r = 0, m = 0;
+  long long p0 = 0;
+  if (q < nlist) {
+    r = rows[q];
+    p0 = Nia[r];
+    m = (int)(Nia[r + 1] - p0);
+  }
+  double *Mt = &M[g][t][0];
+  if (t < m) {
+    const int col = Nja[p0 + t];
+    for (int c = 0; c < m; c++) {
+      const int row = Nja[p0 + c];
+      long long lo = Aia[row];
+      const long long end = Aia[row + 1];
+      long long hi = end;
+      while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (Aja[mid] < col)
+          lo = mid + 1;
+        else
+          hi = mid;
+      }
+      Mt[c] = (lo < end && Aja[lo] == col) ? Aa[lo] : 0.0;
+    }
+    Mt[GS] = -Ng[p0 + t];
+  }
+  // trip counts: the largest m of the workgroup (one wave), so that every group reaches every barrier
+  int mb = m;
+  for (int off = 32; off > 0; off >>= 1) mb = max(mb, __shfl_xor(mb, off, 64));
+  __syncthreads();
+  bool used = false, singular = false;
+  int step = GS;  // the elimination step this lane's row was the pivot of
+  for (int k = 0; k < mb; k++) {
+    double v = (t < m && !used && k < m) ? fabs(Mt[k]) : -1.0;
+    int idx = t;
+    for (int off = GS / 2; off > 0; off >>= 1) {
+      const double ov = __shfl_xor(v, off, GS);
+      const int oi = __shfl_xor(idx, off, GS);
+      if (ov > v || (ov == v && oi < idx)) v = ov, idx = oi;
+    }
+    if (k < m && !singular) {
+      if (!(v > 0.0)) singular = true;
+      if (t == 0) piv[g][k] = idx;
+      if (t == idx) used = true, step = k;
+      if (!singular && t < m && !used) {
+        const double *Mp = &M[g][idx][0];
+        const double l = Mt[k] / Mp[k];
+        for (int c = k + 1; c < m; c++) Mt[c] = Mt[c] - l * Mp[c];
+        Mt[GS] = Mt[GS] - l * Mp[GS];
+      }
+    }
+    __syncthreads();
+  }
+  for (int c = mb - 1; c >= 0; c--) {
+    if (c < m && !singular && t == piv[g][c]) y[g][c] = Mt[GS] / Mt[c];
+    __syncthreads();
+    if (c < m && !singular && t < m && step < c) Mt[GS] = Mt[GS] - Mt[c] * y[g][c];
+  }
+  __syncthreads();
+  if (q >= nlist) return;
+  if (t < m) Y[p0 + t] = singular ? 0.0 : y[g][t];
+  if (t == 0) status[r] = singular ? 1 : 0;
+}
+
+// Row c of R, one row per lane: the entries (N_t, y_t) that pass the filter (phi > 0 drops |y_t| < phi * max_s |y_s|)
+// and (i, 1.0), columns ascending.  FILL = false: cnt[c] and the number of rows with m = 0 (one atomic per wave);
+// FILL = true: the entries at ria[c].
+template <bool FILL>
+__global__ __launch_bounds__(BLK) void air_finish_k(int nc, const long long *__restrict__ nia, const int *__restrict__ nja,
+                                                    const double *__restrict__ y, const int *__restrict__ c2f, double phi,
+                                                    int *__restrict__ cnt, int *__restrict__ zero_rows,
+                                                    const long long *__restrict__ ria, int *__restrict__ rja,
+                                                    double *__restrict__ ra) {
+  const long long c = bid() * BLK + threadIdx.x;
+  const bool live = c < nc;
+  const long long p0 = live ? nia[c] : 0, p1 = live ? nia[c + 1] : 0;
+  if (!FILL) {
+    const unsigned long long empty = __ballot(live && p1 == p0);
+    if ((threadIdx.x & 63) == 0 && empty) atomicAdd(zero_rows, __popcll(empty));
+  }
+  if (!live) return;
+  double mx = 0.0;
+  if (phi > 0.0)
+    for (long long k = p0; k < p1; k++) mx = fmax(mx, fabs(y[k]));
+  const double thr = phi * mx;
+  const int i = c2f[c];
+  long long w = FILL ? ria[c] : 0;
+  int kept = 1;
+  bool unit_done = false;
+  for (long long k = p0; k < p1; k++) {
+    if (phi > 0.0 && fabs(y[k]) < thr) continue;
+    if (FILL) {
+      if (!unit_done && nja[k] > i) rja[w] = i, ra[w] = 1.0, w++, unit_done = true;
+      rja[w] = nja[k], ra[w] = y[k], w++;
+    }
+    kept++;
+  }
+  if (FILL && !unit_done) rja[w] = i, ra[w] = 1.0;
+  if (!FILL) cnt[c] = kept;
+}
+
+// One-point interpolation, one row per lane: sel[i] = the coarse column of row i, or -1 (an F row without a strong C
+// point) -- a C point its own, an F point the C point j of S_i with the largest |a_ij|, the lowest column on a tie
+__global__ __launch_bounds__(BLK) void one_point_select_k(int n, const long long *__restrict__ ia, const int *__restrict__ ja,
+                                                          const double *__restrict__ a, const long long *__restrict__ sia,
+                                                          const int *__restrict__ sja, const int *__restrict__ cf,
+                                                          const long long *__restrict__ crank, int *__restrict__ sel,
+                                                          int *__restrict__ cnt) {
+  const long long i = bid() * BLK + threadIdx.x;
+  if (i >= n) return;
+  int pick = -1;
+  if (cf[i] == C_PT) {
+    pick = (int)crank[i];
+  } else {
+    double best = -1.0;
+    long long ks = sia[i];
+    const long long kse = sia[i + 1];
+    for (long long k = ia[i]; k < ia[i + 1] && ks < kse; k++) {
+      const int j = ja[k];
+      while (ks < kse && sja[ks] < j) ks++;
+      if (ks < kse && sja[ks] == j && cf[j] == C_PT && fabs(a[k]) > best) best = fabs(a[k]), pick = (int)crank[j];
+    }
+  }
+  sel[i] = pick;
+  cnt[i] = pick >= 0;
+}
+
+__global__ __launch_bounds__(BLK) void one_point_fill_k(int n, const int *__restrict__ sel, const long long *__restrict__ pia,
+                                                        int *__restrict__ pja, double *__restrict__ pa) {
+  const long long i = bid() * BLK + threadIdx.x;
+  if (i >= n || sel[i] < 0) return;
+  pja[pia[i]] = sel[i];
+  pa[pia[i]] = 1.0;
+}
+}  // namespace
+
+int air_restriction(const DCsr &A, const int *cf, double theta_r, double phi, DCsr &R, AirInfo &info, hipStream_t s) {
+  const int n = A.nrows;
+  info = AirInfo();
+  MI_REQUIRE(n > 0 && A.ncols == n, "device approximate ideal restriction: a square operator with rows");
+  const dim3 gr = grid_for(((long long)n + BLK - 1) / BLK);
+  DVec<long long> crank;
+  const int nc = (int)count_c_points(cf, n, crank, s);
+  MI_REQUIRE(nc > 0, "device approximate ideal restriction: the marker has no C point");
+  const dim3 grc = grid_for(((long long)nc + BLK - 1) / BLK);
+  // the neighbourhoods as a CSR with nc rows: columns N_t, values a(i, N_t)
+  DCsr N;
+  N.nrows = nc;
+  N.ncols = n;
+  N.ia.alloc((size_t)nc + 1);
+  DVec<int> cnt((size_t)nc), c2f((size_t)nc);
+  air_neighbourhood_k<false><<<gr, BLK, 0, s>>>(n, A.ia.p, A.ja.p, A.a.p, cf, crank.p, theta_r, cnt.p, c2f.p, nullptr, nullptr, nullptr);
+  MI_HIP(hipGetLastError());
+  exclusive_scan(cnt.p, N.ia.p, nc, s);
+  long long nnz = 0;
+  d2h(&nnz, N.ia.p + nc, sizeof(long long), s);
+  N.nnz = nnz;
+  N.ja.alloc((size_t)nnz);
+  N.a.alloc((size_t)nnz);
+  air_neighbourhood_k<true><<<gr, BLK, 0, s>>>(n, A.ia.p, A.ja.p, A.a.p, cf, crank.p, theta_r, nullptr, nullptr, N.ia.p, N.ja.p, N.a.p);
+  MI_HIP(hipGetLastError());
+  // rows by group size (the FSAI classifier: <= 16, <= 32, <= 64 entries) and the largest m
+  DVec<int> lists((size_t)3 * nc), counters(4);
+  MI_HIP(hipMemsetAsync(counters.p, 0, 4 * sizeof(int), s));
+  fsai_classify_k<<<grc, BLK, 0, s>>>(nc, N.ia.p, lists.p, counters.p);
+  MI_HIP(hipGetLastError());
+  int hc[4];
+  d2h(hc, counters.p, sizeof(hc), s);
+  info.max_m = hc[3];
+  if (info.max_m > 64) return 1;
+  for (int q = 0; q < 3; q++) info.group_rows[q] = hc[q];
+  DVec<double> Y((size_t)nnz);
+  DVec<unsigned char> status((size_t)nc);
+  if (hc[0]) air_local_solve_k<16><<<grid_for((hc[0] + 3) / 4), 64, 0, s>>>(lists.p, hc[0], A.ia.p, A.ja.p, A.a.p, N.ia.p, N.ja.p, N.a.p, Y.p, status.p);
+  if (hc[1]) air_local_solve_k<32><<<grid_for((hc[1] + 1) / 2), 64, 0, s>>>(lists.p + nc, hc[1], A.ia.p, A.ja.p, A.a.p, N.ia.p, N.ja.p, N.a.p, Y.p, status.p);
+  if (hc[2]) air_local_solve_k<64><<<grid_for(hc[2]), 64, 0, s>>>(lists.p + 2LL * nc, hc[2], A.ia.p, A.ja.p, A.a.p, N.ia.p, N.ja.p, N.a.p, Y.p, status.p);
+  MI_HIP(hipGetLastError());
+  MI_HIP(hipMemsetAsync(counters.p, 0x7f, sizeof(int), s));  // 0x7f7f7f7f: above every row
+  fsai_first_bad_k<<<grc, BLK, 0, s>>>(nc, status.p, counters.p);
+  int first = nc;
+  d2h(&first, counters.p, sizeof(int), s);
+  if (first < nc) {
+    d2h(&info.bad_row, c2f.p + first, sizeof(int), s);
+    return 2;
+  }
+  // filter, the unit entry, compaction
+  MI_HIP(hipMemsetAsync(counters.p, 0, sizeof(int), s));
+  R.release();
+  R.nrows = nc;
+  R.ncols = n;
+  R.ia.alloc((size_t)nc + 1);
+  air_finish_k<false><<<grc, BLK, 0, s>>>(nc, N.ia.p, N.ja.p, Y.p, c2f.p, phi, cnt.p, counters.p, nullptr, nullptr, nullptr);
+  MI_HIP(hipGetLastError());
+  exclusive_scan(cnt.p, R.ia.p, nc, s);
+  long long rnnz = 0;
+  d2h(&rnnz, R.ia.p + nc, sizeof(long long), s);
+  d2h(&info.zero_rows, counters.p, sizeof(int), s);
+  R.nnz = rnnz;
+  R.ja.alloc((size_t)rnnz);
+  R.a.alloc((size_t)rnnz);
+  air_finish_k<true><<<grc, BLK, 0, s>>>(nc, N.ia.p, N.ja.p, Y.p, c2f.p, phi, nullptr, nullptr, R.ia.p, R.ja.p, R.a.p);
+  MI_HIP(hipGetLastError());
+  MI_HIP(hipStreamSynchronize(s));  // (the temporaries are released on return)
+  info.dropped = nnz + nc - rnnz;
+  return 0;
+}
+
+void one_point_interp(const DCsr &A, const DCsr &S, DVec<int> &cf, DCsr &P, int &nc, hipStream_t s) {
+  const int n = A.nrows;
+  MI_REQUIRE(n > 0 && S.nrows == n, "device one-point interpolation: an operator with rows and its strength graph");
+  const dim3 gr = grid_for(((long long)n + BLK - 1) / BLK);
+  DVec<long long> crank;
+  nc = (int)count_c_points(cf.p, n, crank, s);
+  DVec<int> sel((size_t)n), cnt((size_t)n);
+  one_point_select_k<<<gr, BLK, 0, s>>>(n, A.ia.p, A.ja.p, A.a.p, S.ia.p, S.ja.p, cf.p, crank.p, sel.p, cnt.p);
+  MI_HIP(hipGetLastError());
+  P.release();
+  P.nrows = n;
+  P.ncols = nc;
+  P.ia.alloc((size_t)n + 1);
+  exclusive_scan(cnt.p, P.ia.p, n, s);
+  long long nnz = 0;
+  d2h(&nnz, P.ia.p + n, sizeof(long long), s);
+  P.nnz = nnz;
+  P.ja.alloc((size_t)nnz);
+  P.a.alloc((size_t)nnz);
+  one_point_fill_k<<<gr, BLK, 0, s>>>(n, sel.p, P.ia.p, P.ja.p, P.a.p);
+  sf_to_f_k<<<gr, BLK, 0, s>>>(n, cf.p);
+  MI_HIP(hipGetLastError());
+  MI_HIP(hipStreamSynchronize(s));
+}
+
 }  // namespace sk
 }  // namespace mi

@@ -73,6 +73,26 @@ int two_stage_ext(const DCsr &A, const DCsr &S, const DVec<int> &m1, DVec<int> &
 int mm_interp(const DCsr &A, const DCsr &S, DVec<int> &cf, int interp_type, double trunc_factor, int pmax, DCsr &P,
               int &nc, hipStream_t s, int lanes = 0);
 
+// Distance-1 approximate ideal restriction (restriction 1; DESIGN.md section 3, "Approximate ideal restriction") of the
+// square operator A with the final marker cf (+1 C, anything else F): row c(i) of R (|C| x n) holds (i, 1.0) and the
+// solution y of A[N_i, N_i]^T y = -A[i, N_i]^T on the F-neighbourhood N_i (|a_ij| >= theta_r * max_{k != i} |a_ik|),
+// less the entries the filter phi drops -- bit for bit hs::build_air_restriction.  A counting and a fill pass for the
+// neighbourhoods, one small dense solve per row on 16 / 32 / 64 lanes by |N_i| (the elimination of fsai_local_solve),
+// filter and compaction.  Returns 0; 1 when some |N_i| > 64 (R is not built: the caller runs the host routine; max_m
+// is set); 2 when a local system is singular (bad_row = the first such row of A; R is not built).
+struct AirInfo {
+  int max_m = 0;                    // the largest |N_i|
+  int zero_rows = 0;                // C rows with an empty N_i
+  long long dropped = 0;            // entries the filter dropped
+  int group_rows[3] = {0, 0, 0};    // rows solved by the 16-, 32- and 64-lane instantiation (the device routine only)
+  int bad_row = -1;
+};
+int air_restriction(const DCsr &A, const int *cf, double theta_r, double phi, DCsr &R, AirInfo &info, hipStream_t s);
+// One-point interpolation (interp_type 100): a C point i gets (c(i), 1.0), an F point the C point
+// of its row of S with the largest |a_ij| (the lowest column on a tie), or an empty row -- one row per lane, rows of any
+// length, bit for bit hs::build_one_point_interp.  cf is updated like the host code does (-3 -> -1); nc = number of C points.
+void one_point_interp(const DCsr &A, const DCsr &S, DVec<int> &cf, DCsr &P, int &nc, hipStream_t s);
+
 // C = A * B.  Rows of B must have ascending columns.  Entry (i, j) is the sum of
 // a_ik * b_kj taken in the stored order of A's row i (first product assigned,
 // the others added one by one) -- exactly host_spgemm (amg_setup.cpp) and the

@@ -434,6 +434,19 @@ void HypreSystem::setup_boomeramg_precond() {
     if (node["mi_cheby_eig_est"]) HYPRE_BoomerAMGSetChebyEigEst(precond_, node["mi_cheby_eig_est"].as<int>());
 #endif
   }
+  /* this library's keys for the restriction: mi_restriction 0 = the transpose of P (default), 1 = distance-1 approximate
+   * ideal restriction (AIR) with its strength threshold and the filter of its rows; an absent key leaves the solver's
+   * default (0, 0.25, 0) */
+  if (node["mi_restriction"] || node["mi_strong_threshold_r"] || node["mi_filter_threshold_r"]) {
+#ifdef MI_HOST_WITH_LIBHYPRE
+    throw std::runtime_error("Hypre Config:: mi_restriction, mi_strong_threshold_r and mi_filter_threshold_r are keys of "
+                             "libmi_hypre; this adapter does not pass them to libHYPRE");
+#else
+    if (node["mi_restriction"]) HYPRE_BoomerAMGSetRestriction(precond_, node["mi_restriction"].as<int>());
+    if (node["mi_strong_threshold_r"]) HYPRE_BoomerAMGSetStrongThresholdR(precond_, node["mi_strong_threshold_r"].as<double>());
+    if (node["mi_filter_threshold_r"]) HYPRE_BoomerAMGSetFilterThresholdR(precond_, node["mi_filter_threshold_r"].as<double>());
+#endif
+  }
   if (node["trunc_factor"]) HYPRE_BoomerAMGSetTruncFactor(precond_, node["trunc_factor"].as<double>());
   if (node["agg_p12_trunc_factor"])
     HYPRE_BoomerAMGSetAggP12TruncFactor(precond_, node["agg_p12_trunc_factor"].as<double>());
@@ -670,6 +683,16 @@ void HypreSystem::checkMemory() {
 // Timers as there: "Preconditioner setup" = SetPrecond + Setup, "Solve" = the
 // Solve calls only, all barrier-fenced.  The hierarchy is built once per matrix
 // (the reference rebuilds it for every component, :692 inside :681).
+#ifndef MI_HOST_WITH_LIBHYPRE
+// the Setup line of a hierarchy whose restriction is not the transpose of P (boomeramg_settings: mi_restriction 1)
+static void report_restriction(HYPRE_Solver amg, int step) {
+  HYPRE_Int rinfo[4] = {0, 0, 0, 0};
+  if (HYPRE_MI_BoomerAMGGetRestrictionInfo(amg, 0, rinfo) == 0 && rinfo[0] != 0)
+    printf("Setup %d : restriction AIR (approximate ideal restriction), level 0 built by the %s, largest F-neighbourhood %d\n",
+           step, rinfo[0] == 1 ? "device" : "host routine", (int)rinfo[1]);
+}
+#endif
+
 void HypreSystem::solve() {
   assemble_system();
   double setup = 0.0, write_operators = 0.0, solve_t = 0.0;
@@ -689,6 +712,9 @@ void HypreSystem::solve() {
         HYPRE_DescribeError(setup_rc, what);
         throw std::runtime_error(std::string("solver / preconditioner setup failed: ") + what);
       }
+#ifndef MI_HOST_WITH_LIBHYPRE
+      if (iproc_ == 0 && usePrecond_ && precond_ && precondSetupPtr_ == &HYPRE_BoomerAMGSetup) report_restriction(precond_, 0);
+#endif
       checkMemory();
     }
     MPI_Barrier(comm_);
@@ -947,6 +973,7 @@ void HypreSystem::update_step(int step, double &setup, double &solve_t) {
     else if (iproc_ == 0)
       printf("Setup %d : AMG hierarchy rebuilt (%s), %.3f s (solver setup %.3f s)\n", step,
              HYPRE_MI_SetupReuseReasonText(reason), amg_seconds, s1.seconds());
+    if (iproc_ == 0) report_restriction(precond_, step);
   }
 #endif
   Stopwatch s3;

@@ -286,6 +286,10 @@ class BoomerAMG:
                               ("agg_p12_max_elmts", "HYPRE_BoomerAMGSetAggP12MaxElmts", int),
                               ("agg_p12_trunc_factor", "HYPRE_BoomerAMGSetAggP12TruncFactor", float),
                               ("trunc_factor", "HYPRE_BoomerAMGSetTruncFactor", float),
+                              # restriction 0 = P^T, 1 = approximate ideal restriction
+                              ("restriction", "HYPRE_BoomerAMGSetRestriction", int),
+                              ("strong_threshold_r", "HYPRE_BoomerAMGSetStrongThresholdR", float),
+                              ("filter_threshold_r", "HYPRE_BoomerAMGSetFilterThresholdR", float),
                               ("keep_transpose", "HYPRE_BoomerAMGSetKeepTranspose", int),
                               ("rap2", "HYPRE_BoomerAMGSetRAP2", int),
                               ("smooth_type", "HYPRE_BoomerAMGSetSmoothType", int),  # HypreSystem.cpp:235-320
@@ -427,6 +431,13 @@ class BoomerAMG:
         d = {k: int(v) for k, v in zip(names, out)}
         d["fell_back"], d["host"] = bool(out[7] & 1), bool(out[7] & 2)
         return d
+
+    def restriction_info(self, level):
+        """How the level's R was made: kind 0 the transpose of P / 1 approximate ideal restriction built by the device /
+        2 by the host routine, the largest F-neighbourhood, the C rows with an empty one, the entries the filter dropped."""
+        out = np.zeros(4, dtype=np.int32)
+        call("HYPRE_MI_BoomerAMGGetRestrictionInfo", self.h, level, out)
+        return {k: int(v) for k, v in zip(("kind", "max_m", "zero_rows", "dropped"), out)}
 
     def level_perm(self, level):
         """perm[new local row] = old local row of the level's C-first ordering."""
@@ -1106,6 +1117,64 @@ def mm_interp_op(interp_type, A, S, cf, trunc_factor=0.0, pmax=0, lanes=0):
     for ptr in (pia, pja, pa):
         lib().HYPRE_MI_Free(ptr)
     return ia, ja, a, (n, nc.value)
+
+
+def _csr_from_caller(nrows, pia, pja, pa):
+    """Copies of malloc'ed CSR arrays (released here): (ia int64, ja int32, a f64)."""
+    ia = np.ctypeslib.as_array(C.cast(pia, C.POINTER(c_big)), shape=(nrows + 1,)).copy()
+    nnz = int(ia[-1])
+    ja = np.ctypeslib.as_array(C.cast(pja, C.POINTER(c_int)), shape=(max(nnz, 1),)).copy()[:nnz]
+    a = np.ctypeslib.as_array(C.cast(pa, C.POINTER(c_dbl)), shape=(max(nnz, 1),)).copy()[:nnz]
+    for ptr in (pia, pja, pa):
+        lib().HYPRE_MI_Free(ptr)
+    return ia, ja, a
+
+
+AIR_INFO_NAMES = ("status", "max_m", "zero_rows", "dropped", "rows16", "rows32", "rows64", "bad_row")
+
+
+def air_restriction_op(A, cf, strong_threshold_r=0.25, filter_threshold_r=0.0, host=False):
+    """The approximate ideal restriction (HYPRE_MI_AIRRestrictionOp) of a scipy CSR operator A (ascending columns) with
+    the marker cf (+1 C, -1 F), by the device routine or -- host=True, no GPU needed -- the host routine.  Returns
+    (R, info): R = (ia int64, ja int32, a f64, shape) exactly as the library stores it, or None when the device routine
+    did not build it (info["status"] == 1: a neighbourhood above 64 entries).  Raises HypreError with `info` set when a
+    local system is singular."""
+    n = A.shape[0]
+    aia = np.ascontiguousarray(A.indptr, dtype=np.int64)
+    aja = np.ascontiguousarray(A.indices, dtype=np.int32)
+    aa = np.ascontiguousarray(A.data, dtype=np.float64)
+    m = np.ascontiguousarray(cf, dtype=np.int32)
+    nr = c_int()
+    out = np.full(8, -2, dtype=np.int32)
+    pia, pja, pa = vp(), vp(), vp()
+    try:
+        call("HYPRE_MI_AIRRestrictionOp", int(bool(host)), n, aia, aja, aa, m, float(strong_threshold_r),
+             float(filter_threshold_r), C.byref(nr), C.byref(pia), C.byref(pja), C.byref(pa), out)
+    except HypreError as e:
+        e.info = {k: int(v) for k, v in zip(AIR_INFO_NAMES, out)}
+        raise
+    info = {k: int(v) for k, v in zip(AIR_INFO_NAMES, out)}
+    if info["status"] != 0:
+        return None, info
+    return _csr_from_caller(nr.value, pia, pja, pa) + ((nr.value, n),), info
+
+
+def one_point_interp_op(A, S, cf, host=False):
+    """One-point interpolation (HYPRE_MI_OnePointInterpOp) of a scipy CSR operator A with the pattern of the scipy CSR
+    strength graph S and the marker cf (+1 C, -1 F, -3 special F), by the device routine or -- host=True -- the host
+    routine.  Returns P as (ia int64, ja int32, a f64, shape)."""
+    n = A.shape[0]
+    aia = np.ascontiguousarray(A.indptr, dtype=np.int64)
+    aja = np.ascontiguousarray(A.indices, dtype=np.int32)
+    aa = np.ascontiguousarray(A.data, dtype=np.float64)
+    sia = np.ascontiguousarray(S.indptr, dtype=np.int64)
+    sja = np.ascontiguousarray(S.indices, dtype=np.int32)
+    m = np.ascontiguousarray(cf, dtype=np.int32)
+    nc = c_int()
+    pia, pja, pa = vp(), vp(), vp()
+    call("HYPRE_MI_OnePointInterpOp", int(bool(host)), n, aia, aja, aa, sia, sja, m, C.byref(nc), C.byref(pia),
+         C.byref(pja), C.byref(pa))
+    return _csr_from_caller(n, pia, pja, pa) + ((n, nc.value),)
 
 
 VEC_MASS_DOT, VEC_MASS_AXPY, VEC_LIN_COMB, VEC_AXPY_DOT, VEC_SCALE_POST = range(5)

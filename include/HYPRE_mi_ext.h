@@ -176,13 +176,37 @@ HYPRE_Int HYPRE_MI_MMInterpOp(HYPRE_Int type, HYPRE_Int n, const HYPRE_BigInt *a
                               HYPRE_Real trunc_factor, HYPRE_Int pmax, HYPRE_Int lanes, HYPRE_Int *p_ncols,
                               HYPRE_BigInt **p_ia, HYPRE_Int **p_ja, HYPRE_Complex **p_a, HYPRE_Int *bad_row);
 
+/* ---- the approximate ideal restriction (HYPRE_BoomerAMGSetRestriction 1) on caller (host) arrays:
+ * the n x n operator A as CSR with ascending columns and the final marker cf (+1 C, -1 F).  on_host = 0 runs the device
+ * routine, 1 the host routine (which needs no device); both give the same bits.  R (*r_nrows x n, rows = the C points in
+ * order, columns ascending) is malloc'ed: release with HYPRE_MI_Free.  info[0] = 0 built / 1 not built (a neighbourhood
+ * above 64 entries: the device routine leaves such a level to the host routine; R stays NULL and the call succeeds) /
+ * 2 a singular local system (the call fails with HYPRE_ERROR_ARG); info[1] = the largest neighbourhood, info[2] = the C
+ * rows with an empty one, info[3] = the entries the filter dropped, info[4..6] = the rows the 16-, 32- and 64-lane
+ * instantiation solved (device routine), info[7] = the first singular row or -1. */
+HYPRE_Int HYPRE_MI_AIRRestrictionOp(HYPRE_Int on_host, HYPRE_Int n, const HYPRE_BigInt *a_ia, const HYPRE_Int *a_ja,
+                                    const HYPRE_Complex *a_a, const HYPRE_Int *cf, HYPRE_Real strong_threshold_r,
+                                    HYPRE_Real filter_threshold_r, HYPRE_Int *r_nrows, HYPRE_BigInt **r_ia, HYPRE_Int **r_ja,
+                                    HYPRE_Complex **r_a, HYPRE_Int info[8]);
+/* ---- one-point interpolation (interp_type 100) on caller (host) arrays: A, the pattern of the
+ * strength graph S and the marker cf (+1 C, -1 F, -3 special F); on_host as above.  P (n x *p_ncols) is malloc'ed. */
+HYPRE_Int HYPRE_MI_OnePointInterpOp(HYPRE_Int on_host, HYPRE_Int n, const HYPRE_BigInt *a_ia, const HYPRE_Int *a_ja,
+                                    const HYPRE_Complex *a_a, const HYPRE_BigInt *s_ia, const HYPRE_Int *s_ja,
+                                    const HYPRE_Int *cf, HYPRE_Int *p_ncols, HYPRE_BigInt **p_ia, HYPRE_Int **p_ja,
+                                    HYPRE_Complex **p_a);
+/* how R of `level` was made: out[0] = 0 the transpose of P / 1 approximate ideal restriction built by the device / 2 by
+ * the host routine; out[1] = the largest neighbourhood, out[2] = the C rows with an empty one, out[3] = the entries the
+ * filter dropped */
+HYPRE_Int HYPRE_MI_BoomerAMGGetRestrictionInfo(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int out[4]);
+
 /* ---- setup reuse: mode 0 (default) = every Setup builds from scratch; 1 = a Setup on a handle that holds a finished
  * hierarchy of the same matrix object and pattern, built by the same entry point with the same structural settings on
  * one rank, keeps the splittings, orderings, P, R and all patterns and recomputes the values.  A Setup that cannot
  * refresh rebuilds, and says so.  Any other mode is HYPRE_ERROR_ARG.
  * GetSetupKind: kind 0 never set up, 1 built from scratch, 2 refreshed; reason (kind 1): 0 reuse is off, 1 first Setup
  * of this handle or the previous one failed, 2 another matrix object or pattern, 3 a setting the structure depends on
- * changed, 4 a setting the refresh does not cover is on (non-Galerkin tolerances, value storage), 5 more than one rank,
+ * changed, 4 a setting the refresh does not cover is on (non-Galerkin tolerances, value storage,
+ * restriction 1, interp_type 100), 5 more than one rank,
  * 6 the other setup entry point built the hierarchy.  Counters: "amg_setups_full", "amg_setups_refreshed". */
 HYPRE_Int HYPRE_MI_BoomerAMGSetSetupReuse(HYPRE_Solver solver, HYPRE_Int mode);
 HYPRE_Int HYPRE_MI_BoomerAMGGetSetupKind(HYPRE_Solver solver, HYPRE_Int *kind, HYPRE_Int *reason);

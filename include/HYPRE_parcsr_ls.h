@@ -32,8 +32,15 @@ HYPRE_Int HYPRE_BoomerAMGSetMaxLevels(HYPRE_Solver solver, HYPRE_Int max_levels)
 HYPRE_Int HYPRE_BoomerAMGSetStrongThreshold(HYPRE_Solver solver, HYPRE_Real theta);     /* :158 */
 HYPRE_Int HYPRE_BoomerAMGSetMaxRowSum(HYPRE_Solver solver, HYPRE_Real max_row_sum);
 HYPRE_Int HYPRE_BoomerAMGSetInterpType(HYPRE_Solver solver, HYPRE_Int interp_type);     /* :196; 6 ext+i, 3 direct, 0 classical, 4 multipass,
-                                                                                           * 16 / 17 extended / ext+i in matrix-matrix form;
+                                                                                           * 16 / 17 extended / ext+i in matrix-matrix form,
+                                                                                           * 100 one-point;
                                                                                            * any other value is refused at Setup */
+/* restriction: 0 = the transpose of P (default), 1 = distance-1 approximate ideal restriction (AIR; one rank, no
+ * aggressive levels); any other value is refused at Setup.  Its strength threshold theta_R (default 0.25, absolute
+ * values, no row-sum test) and the filter of its rows (default 0 = none) */
+HYPRE_Int HYPRE_BoomerAMGSetRestriction(HYPRE_Solver solver, HYPRE_Int restr_par);
+HYPRE_Int HYPRE_BoomerAMGSetStrongThresholdR(HYPRE_Solver solver, HYPRE_Real strong_threshold);
+HYPRE_Int HYPRE_BoomerAMGSetFilterThresholdR(HYPRE_Solver solver, HYPRE_Real filter_threshold);
 HYPRE_Int HYPRE_BoomerAMGSetTruncFactor(HYPRE_Solver solver, HYPRE_Real trunc_factor);  /* :231 */
 HYPRE_Int HYPRE_BoomerAMGSetPMaxElmts(HYPRE_Solver solver, HYPRE_Int pmax);
 HYPRE_Int HYPRE_BoomerAMGSetMinCoarseSize(HYPRE_Solver solver, HYPRE_Int n);            /* :201 */
