@@ -46,9 +46,12 @@ struct AmgParams {
   // iterative ILU(0) setup of the ILU smoothers (IluSolver::iter_*; 0 = the exact factorisation)
   int ilu_iter_type = 0, ilu_iter_option = 0, ilu_iter_max_iter = 100;
   double ilu_iter_tol = 1e-3;
-  // smooth_type 4 = FSAI with the static pattern (algo type 3, the only one built), one step per sweep
+  // smooth_type 4 = FSAI, one step per sweep: algo type 3 = static pattern (num_levels, threshold), 4 = adaptive pattern
+  // on the device (max_steps, max_step_size, kap_tolerance; this library's number)
   int fsai_algo_type = 3, fsai_num_levels = 1, fsai_eig_max_iters = 5;
   double fsai_threshold = 0.01;
+  int fsai_max_steps = 3, fsai_max_step_size = 5;
+  double fsai_kap_tolerance = 1e-3;
   // relax type 16 = Chebyshev: steps per sweep (1 ... 4), where the smoothed interval starts between
   // the eigenvalue bounds of D^-1 A, CG-Lanczos steps of the estimate (0 = Gershgorin); only variant 0 with scale 1 is built
   int cheby_order = 2, cheby_eig_est = 10, cheby_variant = 0, cheby_scale = 1;

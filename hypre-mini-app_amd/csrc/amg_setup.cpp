@@ -12,7 +12,9 @@
 #include <atomic>
 #include <thread>
 #include <cmath>
+#include <climits>
 #include <cstring>
+#include <mutex>
 
 #include "amg.hpp"
 #include "amg_setup_internal.hpp"
@@ -1198,6 +1200,182 @@ int build_air_restriction(const HostCSR &D, const std::vector<int> &cf, double t
   return -1;
 }
 
+// FSAI with the adaptive pattern (fsai_algo_type 4; DESIGN.md section 3, "FSAI (adaptive pattern)"), bit for bit
+// sk::fsai_adaptive.  Row i starts from P = (i); a step solves B[P, P]^T y = e_last (the elimination of the static
+// path: partial pivoting, the lowest row on a tie, rows not moved, back substitution by columns, descending), tests
+// psi = 1 / y_last against the previous one, sums phi_j = sum_{r in P ascending, i last} b_rj y_r over the stored columns
+// j < i outside P -- one `acc = acc + b * y` per entry, from 0.0 --, and moves the up to T columns with the largest
+// |phi_j| > 0 (the lower column on a tie) into P.  Row i of G = y / sqrt(y_last) on P.  Returns 0, or 2 when a row
+// fails (info.bad_row = the smallest such row; G is not built).
+int build_fsai_adaptive(const HostCSR &B, int S, int T, double tau, HostCSR &G, sk::FsaiAdaptiveInfo &info) {
+  const int n = B.nrows;
+  info = sk::FsaiAdaptiveInfo();
+  struct Part {
+    int64_t b = 0;
+    std::vector<int> ja;
+    std::vector<double> a;
+  };
+  std::vector<Part> parts;
+  std::vector<int> len((size_t)n, 0);
+  std::mutex mu;
+  auto entry = [&](int r, int c) {
+    const int *r0 = B.ja.data() + B.ia[(size_t)r], *r1 = B.ja.data() + B.ia[(size_t)r + 1];
+    const int *it = std::lower_bound(r0, r1, c);
+    return (it != r1 && *it == c) ? B.a[(size_t)(it - B.ja.data())] : 0.0;
+  };
+  parallel_for(n, [&](int64_t b, int64_t e, int) {
+    Part part;
+    part.b = b;
+    sk::FsaiAdaptiveInfo loc;
+    std::vector<int> pos((size_t)n, -1);  // column -> its candidate; -2: in the pattern
+    std::vector<int> P, cj, piv, step, chosen;
+    std::vector<double> M, y, cv;
+    std::vector<char> used, taken;
+    for (int64_t i64 = b; i64 < e; i64++) {
+      const int i = (int)i64;
+      P.assign(1, i);
+      int stop = 0, failed = 0;
+      double psi = 0.0;
+      for (int st = 0; st <= S && !stop; st++) {
+        const int m = (int)P.size(), ld = m + 1;
+        M.assign((size_t)m * (size_t)ld, 0.0);
+        for (int t = 0; t < m; t++) {
+          for (int q = 0; q < m; q++) M[(size_t)t * ld + q] = entry(P[(size_t)q], P[(size_t)t]);
+          M[(size_t)t * ld + m] = (t == m - 1) ? 1.0 : 0.0;
+        }
+        used.assign((size_t)m, 0);
+        step.assign((size_t)m, m);
+        piv.assign((size_t)m, 0);
+        for (int k = 0; k < m && !failed; k++) {
+          int idx = -1;
+          double v = -1.0;
+          for (int t = 0; t < m; t++)
+            if (!used[(size_t)t] && std::fabs(M[(size_t)t * ld + k]) > v) v = std::fabs(M[(size_t)t * ld + k]), idx = t;
+          if (!(v > 0.0)) {
+            failed = 1;
+            break;
+          }
+          piv[(size_t)k] = idx;
+          used[(size_t)idx] = 1;
+          step[(size_t)idx] = k;
+          const double *Mp = &M[(size_t)idx * ld];
+          for (int t = 0; t < m; t++) {
+            if (used[(size_t)t]) continue;
+            double *Mt = &M[(size_t)t * ld];
+            const double l = Mt[k] / Mp[k];
+            for (int q = k + 1; q < m; q++) Mt[q] = Mt[q] - l * Mp[q];
+            Mt[m] = Mt[m] - l * Mp[m];
+          }
+        }
+        if (failed) break;
+        y.assign((size_t)m, 0.0);
+        for (int q = m - 1; q >= 0; q--) {
+          const double *Mp = &M[(size_t)piv[(size_t)q] * ld];
+          y[(size_t)q] = Mp[m] / Mp[q];
+          for (int t = 0; t < m; t++)
+            if (step[(size_t)t] < q) M[(size_t)t * ld + m] = M[(size_t)t * ld + m] - M[(size_t)t * ld + q] * y[(size_t)q];
+        }
+        const double ylast = y[(size_t)m - 1];
+        if (!(ylast > 0.0)) {
+          failed = 2;
+          break;
+        }
+        const double psin = 1.0 / ylast;
+        if (st > 0 && psi - psin < tau * psi)
+          stop = 1;
+        else if (st == S)
+          stop = 3;
+        else
+          psi = psin;
+        if (stop) break;
+        // the gradient on the stored columns j < i outside P
+        cj.clear();
+        cv.clear();
+        for (int q = 0; q < m; q++) pos[(size_t)P[(size_t)q]] = -2;
+        for (int q = 0; q < m; q++) {
+          const int r = P[(size_t)q];
+          for (int64_t k = B.ia[(size_t)r]; k < B.ia[(size_t)r + 1]; k++) {
+            const int j = B.ja[(size_t)k];
+            if (j >= i) break;
+            int &pj = pos[(size_t)j];
+            if (pj == -2) continue;
+            if (pj < 0) {
+              pj = (int)cj.size();
+              cj.push_back(j);
+              cv.push_back(0.0);
+            }
+            cv[(size_t)pj] = cv[(size_t)pj] + B.a[(size_t)k] * y[(size_t)q];
+          }
+        }
+        int nc = 0;
+        for (double v : cv) nc += std::fabs(v) > 0.0;
+        loc.max_candidates = std::max(loc.max_candidates, nc);
+        taken.assign(cj.size(), 0);
+        chosen.clear();
+        for (int round = 0; round < T; round++) {
+          double bv = -1.0;
+          int bj = INT_MAX, bs = -1;
+          for (size_t u = 0; u < cj.size(); u++) {
+            const double v = std::fabs(cv[u]);
+            if (taken[u] || !(v > 0.0)) continue;
+            if (v > bv || (v == bv && cj[u] < bj)) bv = v, bj = cj[u], bs = (int)u;
+          }
+          if (bs < 0) break;
+          taken[(size_t)bs] = 1;
+          chosen.push_back(bj);
+        }
+        for (int j : cj) pos[(size_t)j] = -1;
+        for (int q = 0; q < m; q++) pos[(size_t)P[(size_t)q]] = -1;
+        if (chosen.empty()) {
+          stop = 2;
+          break;
+        }
+        P.pop_back();
+        P.insert(P.end(), chosen.begin(), chosen.end());
+        std::sort(P.begin(), P.end());
+        P.push_back(i);
+      }
+      if (failed) {
+        std::lock_guard<std::mutex> lock(mu);
+        if (info.bad_row < 0 || i < info.bad_row) info.bad_row = i, info.bad_kind = failed;
+        continue;
+      }
+      const int m = (int)P.size();
+      const double d = std::sqrt(y[(size_t)m - 1]);
+      for (int q = 0; q < m; q++) {
+        part.ja.push_back(P[(size_t)q]);
+        part.a.push_back(y[(size_t)q] / d);
+      }
+      len[(size_t)i] = m;
+      loc.max_row = std::max(loc.max_row, m);
+      (stop == 1 ? loc.stop_tolerance : (stop == 2 ? loc.stop_no_candidate : loc.stop_max_steps))++;
+    }
+    std::lock_guard<std::mutex> lock(mu);
+    info.max_row = std::max(info.max_row, loc.max_row);
+    info.max_candidates = std::max(info.max_candidates, loc.max_candidates);
+    info.stop_tolerance += loc.stop_tolerance;
+    info.stop_no_candidate += loc.stop_no_candidate;
+    info.stop_max_steps += loc.stop_max_steps;
+    parts.push_back(std::move(part));
+  });
+  if (info.bad_row >= 0) {
+    info.status = 2;
+    return 2;
+  }
+  G.nrows = n;
+  G.ncols = B.ncols;
+  G.ia.assign((size_t)n + 1, 0);
+  for (int i = 0; i < n; i++) G.ia[(size_t)i + 1] = G.ia[(size_t)i] + len[(size_t)i];
+  G.ja.resize((size_t)G.nnz());
+  G.a.resize((size_t)G.nnz());
+  for (const Part &part : parts) {
+    if (part.ja.empty()) continue;
+    memcpy(G.ja.data() + G.ia[(size_t)part.b], part.ja.data(), part.ja.size() * sizeof(int));
+    memcpy(G.a.data() + G.ia[(size_t)part.b], part.a.data(), part.a.size() * sizeof(double));
+  }
+  return 0;
+}
+
 // One-point interpolation (interp_type 100), bit for bit sk::one_point_interp: a C point i gets
 // (c(i), 1.0); an F point i the C point j of its row of S with the largest |a_ij|, the lowest column on a tie, as
 // (c(j), 1.0) -- or an empty row.  Truncation does not apply.  cf is handed on with special F -> F.
@@ -2009,10 +2187,12 @@ void BoomerAMG::validate_settings() const {
   if (p.smooth_num_levels > 0 && p.smooth_type != 5 && p.smooth_type != 4)
     fail(4, "BoomerAMGSetup: smooth_type " + std::to_string(p.smooth_type) + " on " + std::to_string(p.smooth_num_levels) +
                 " level(s) is not implemented (4 = FSAI and 5 = ILU are); refusing to smooth with something else");
-  if (p.smooth_num_levels > 0 && p.smooth_type == 4 && p.fsai_algo_type != 3)
+  if (p.smooth_num_levels > 0 && p.smooth_type == 4 && p.fsai_algo_type != 3 && p.fsai_algo_type != 4)
     fail(4, "BoomerAMGSetup: FSAI algo_type " + std::to_string(p.fsai_algo_type) +
-                " is not implemented (3 = static pattern is); refusing to substitute another one");
-  if (p.smooth_num_levels > 0 && p.smooth_type == 4 && (p.fsai_num_levels < 1 || p.fsai_num_levels > 3))
+                " is not implemented (3 = static pattern and 4 = adaptive pattern are); refusing to substitute another one");
+  if (p.smooth_num_levels > 0 && p.smooth_type == 4 && p.fsai_algo_type == 4)
+    FsaiSolver::check_adaptive("BoomerAMGSetup", p.fsai_max_steps, p.fsai_max_step_size, p.fsai_kap_tolerance);
+  if (p.smooth_num_levels > 0 && p.smooth_type == 4 && p.fsai_algo_type == 3 && (p.fsai_num_levels < 1 || p.fsai_num_levels > 3))
     fail(4, "BoomerAMGSetup: FSAI num_levels " + std::to_string(p.fsai_num_levels) + " is not implemented (1, 2 and 3 are)");
   if (p.smooth_num_levels > 0 && p.smooth_type == 5 && (p.ilu_type != 0 || p.ilu_level < 0))
     fail(4, "BoomerAMGSetup: ILU smoother type " + std::to_string(p.ilu_type) + " / level of fill " +
@@ -2920,6 +3100,9 @@ void BoomerAMG::build_smoothers() {
       fs->num_levels = p.fsai_num_levels;
       fs->threshold = p.fsai_threshold;
       fs->eig_max_iters = p.fsai_eig_max_iters;
+      fs->max_steps = p.fsai_max_steps;
+      fs->max_step_size = p.fsai_max_step_size;
+      fs->kap_tolerance = p.fsai_kap_tolerance;
       fs->print_level = (p.print_level > 0 && comm.rank == 0) ? 1 : 0;
       fs->setup(*Lv.A, comm, "BoomerAMGSetup: level " + std::to_string(li));
       Lv.smoother = std::move(fs);
@@ -3108,7 +3291,7 @@ std::vector<double> BoomerAMG::current_fsai_signature() const {
             p.ilu_iter_tol};
   if (p.smooth_type != 4 || p.smooth_num_levels <= 0) return {};
   return {(double)p.smooth_num_levels, (double)p.fsai_algo_type, (double)p.fsai_num_levels, p.fsai_threshold,
-          (double)p.fsai_eig_max_iters};
+          (double)p.fsai_eig_max_iters, (double)p.fsai_max_steps, (double)p.fsai_max_step_size, p.fsai_kap_tolerance};
 }
 
 // Value storage: the hierarchy is built as in mode 0; here, as the last step, the values of A, P

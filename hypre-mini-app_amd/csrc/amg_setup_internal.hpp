@@ -60,6 +60,10 @@ void build_interp(const ParCSR &A, const Strength &S, std::vector<int> &cf, int 
 // smallest C row with a singular local system (R is then not built); neighbourhoods of any size
 int build_air_restriction(const HostCSR &D, const std::vector<int> &cf, double theta_r, double phi, HostCSR &R,
                           sk::AirInfo &info);
+// FSAI with the adaptive pattern (fsai_algo_type 4) of a square block B, on the host threads: 0, or 2 when a row fails
+// (info.bad_row = the smallest such row, info.bad_kind; G is then not built) -- bit for bit sk::fsai_adaptive
+int build_fsai_adaptive(const HostCSR &B, int max_steps, int max_step_size, double kap_tolerance, HostCSR &G,
+                        sk::FsaiAdaptiveInfo &info);
 // one-point interpolation (interp_type 100); cf is handed on with special F -> F
 void build_one_point_interp(const HostCSR &D, const Strength &S, std::vector<int> &cf, HostCSR &P, int &nc_out);
 

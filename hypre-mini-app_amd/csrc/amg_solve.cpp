@@ -408,6 +408,9 @@ void BoomerAMG::cycle(int level, bool u_is_zero) {
       tail->p.fsai_num_levels = p.fsai_num_levels;
       tail->p.fsai_threshold = p.fsai_threshold;
       tail->p.fsai_eig_max_iters = p.fsai_eig_max_iters;
+      tail->p.fsai_max_steps = p.fsai_max_steps;
+      tail->p.fsai_max_step_size = p.fsai_max_step_size;
+      tail->p.fsai_kap_tolerance = p.fsai_kap_tolerance;
       tail->p.ilu_iter_type = p.ilu_iter_type;
       tail->p.ilu_iter_option = p.ilu_iter_option;
       tail->p.ilu_iter_max_iter = p.ilu_iter_max_iter;

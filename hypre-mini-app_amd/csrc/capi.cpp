@@ -896,6 +896,47 @@ HYPRE_Int HYPRE_MI_AIRRestrictionOp(HYPRE_Int on_host, HYPRE_Int n, const HYPRE_
   if (status == 0) csr_to_caller(hr, nc, r_ia, r_ja, r_a);
   API_END
 }
+// FSAI with the adaptive pattern (fsai_algo_type 4) on caller (host) arrays: the device routine sk::fsai_adaptive
+// (on_host = 0) or the host routine hs::build_fsai_adaptive (on_host = 1, no device needed).  table_slots: the slots of a
+// row's candidate table in LDS (0 = the library's choice; a small power of two sends rows through the global-memory
+// table; the result never depends on it).  info[8]: status (0 built, 2 a row failed), the largest row of G, the
+// largest candidate count met, the rows that took the global-memory table, the rows stopped by the tolerance / for
+// want of candidates / by max_steps, the first failing row (-1).  Status 2 fails the call and names the row.
+HYPRE_Int HYPRE_MI_FSAIAdaptiveOp(HYPRE_Int on_host, HYPRE_Int n, const HYPRE_BigInt *b_ia, const HYPRE_Int *b_ja,
+                                  const HYPRE_Complex *b_a, HYPRE_Int max_steps, HYPRE_Int max_step_size,
+                                  HYPRE_Real kap_tolerance, HYPRE_Int table_slots, HYPRE_BigInt **g_ia, HYPRE_Int **g_ja,
+                                  HYPRE_Complex **g_a, HYPRE_Int info[8]) {
+  API_BEGIN
+  const std::string who = "FSAIAdaptiveOp";
+  if (!b_ia || !g_ia || !g_ja || !g_a || !info) fail(HYPRE_ERROR_ARG, who + ": NULL argument");
+  if (n < 1 || b_ia[0] != 0) fail(HYPRE_ERROR_ARG, who + ": bad dimensions");
+  if (b_ia[n] > 0 && !b_a) fail(HYPRE_ERROR_ARG, who + ": NULL values of B");
+  if (table_slots < 0 || (table_slots & (table_slots - 1)) != 0)
+    fail(HYPRE_ERROR_ARG, who + ": table_slots must be 0 or a power of two");
+  FsaiSolver::check_adaptive(who, max_steps, max_step_size, kap_tolerance);
+  const HostCSR hB = square_csr_of(who, "B", n, b_ia, b_ja, b_a);
+  *g_ia = nullptr, *g_ja = nullptr, *g_a = nullptr;
+  sk::FsaiAdaptiveInfo ai;
+  HostCSR hg;
+  if (on_host) {
+    hs::build_fsai_adaptive(hB, max_steps, max_step_size, kap_tolerance, hg, ai);
+  } else {
+    ensure_init();
+    hipStream_t s = ctx().stream;
+    sk::DCsr dB, dG;
+    dB.upload(hB, s);
+    if (sk::fsai_adaptive(dB, max_steps, max_step_size, kap_tolerance, table_slots, dG, ai, s) == 0) dG.download(hg, s);
+  }
+  const HYPRE_Int v[8] = {ai.status, ai.max_row, ai.max_candidates, ai.overflow_rows, ai.stop_tolerance,
+                          ai.stop_no_candidate, ai.stop_max_steps, ai.bad_row};
+  for (int i = 0; i < 8; i++) info[i] = v[i];
+  if (ai.status == 2)
+    fail(HYPRE_ERROR_GENERIC, who + ": FSAI local solve failed in row " + std::to_string(ai.bad_row) +
+                                  (ai.bad_kind == 1 ? " (singular local matrix)"
+                                                    : " (y_last <= 0: the diagonal block is not positive definite there)"));
+  csr_to_caller(hg, n, g_ia, g_ja, g_a);
+  API_END
+}
 // One-point interpolation (interp_type 100) on caller (host) arrays: the device routine sk::one_point_interp (on_host = 0)
 // or the host routine hs::build_one_point_interp (on_host = 1, no device needed).  The marker: +1 C, -1 F, -3 special F.
 HYPRE_Int HYPRE_MI_OnePointInterpOp(HYPRE_Int on_host, HYPRE_Int n, const HYPRE_BigInt *a_ia, const HYPRE_Int *a_ja,
@@ -1342,12 +1383,13 @@ AMG_SET(ILUIterSetupTolerance, HYPRE_Real, p.ilu_iter_tol = v)
 AMG_SET(ILUTriSolve, HYPRE_Int, p.ilu_tri_solve = v)
 AMG_SET(ILULowerJacobiIters, HYPRE_Int, p.ilu_lower_it = v)
 AMG_SET(ILUUpperJacobiIters, HYPRE_Int, p.ilu_upper_it = v)
-AMG_SET(FSAIAlgoType, HYPRE_Int, p.fsai_algo_type = v)  /* only 3 (static pattern) is built: others are refused at Setup */
+AMG_SET(FSAIAlgoType, HYPRE_Int, p.fsai_algo_type = v)  /* 3 (static pattern) and 4 (adaptive pattern, this library's number) are built: others are refused at Setup */
 AMG_SET(FSAILocalSolveType, HYPRE_Int, (void)v)
 AMG_SET(FSAINumLevels, HYPRE_Int, p.fsai_num_levels = v)
 AMG_SET(FSAIThreshold, HYPRE_Real, if (v < 0.0) fail(HYPRE_ERROR_ARG, "fsai_threshold < 0"); p.fsai_threshold = v)
 AMG_SET(FSAIEigMaxIters, HYPRE_Int, if (v < 0) fail(HYPRE_ERROR_ARG, "fsai_eig_max_iters < 0"); p.fsai_eig_max_iters = v)
-AMG_SET(FSAIMaxSteps, HYPRE_Int, warn_ignored("fsai_max_steps", v))
+/* the adaptive pattern's values (algo type 4), checked at Setup; with the static pattern they still do nothing, which is said once */
+AMG_SET(FSAIMaxSteps, HYPRE_Int, p.fsai_max_steps = v; if (p.fsai_algo_type != 4) warn_ignored("fsai_max_steps", v))
 /* relax type 16: stored here, checked at Setup like every other choice (order 1 ... 4, fraction in (0, 1), eig_est >= 0,
  * variant 0 and scale 1 are built) */
 AMG_SET(ChebyOrder, HYPRE_Int, p.cheby_order = v)
@@ -1355,9 +1397,9 @@ AMG_SET(ChebyFraction, HYPRE_Real, p.cheby_fraction = v)
 AMG_SET(ChebyEigEst, HYPRE_Int, p.cheby_eig_est = v)
 AMG_SET(ChebyVariant, HYPRE_Int, p.cheby_variant = v)
 AMG_SET(ChebyScale, HYPRE_Int, p.cheby_scale = v)
-AMG_SET(FSAIMaxStepSize, HYPRE_Int, warn_ignored("fsai_max_step_size", v))
+AMG_SET(FSAIMaxStepSize, HYPRE_Int, p.fsai_max_step_size = v; if (p.fsai_algo_type != 4) warn_ignored("fsai_max_step_size", v))
 AMG_SET(FSAIMaxNnzRow, HYPRE_Int, warn_ignored("fsai_max_nnz_row", v))
-AMG_SET(FSAIKapTolerance, HYPRE_Real, warn_ignored("fsai_kap_tolerance", v))
+AMG_SET(FSAIKapTolerance, HYPRE_Real, p.fsai_kap_tolerance = v; if (p.fsai_algo_type != 4) warn_ignored("fsai_kap_tolerance", v))
 #undef AMG_SET
 HYPRE_Int HYPRE_BoomerAMGSetLevelNonGalerkinTol(HYPRE_Solver solver, HYPRE_Real tol, HYPRE_Int level) {
   API_BEGIN
@@ -1703,7 +1745,7 @@ HYPRE_Int HYPRE_FSAISolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVe
     STMT;                                                     \
     API_END                                                   \
   }
-FSAI_SET(AlgoType, HYPRE_Int, o->algo_type = v)  /* only 3 (static pattern) is built: others are refused at Setup */
+FSAI_SET(AlgoType, HYPRE_Int, o->algo_type = v)  /* 3 (static pattern) and 4 (adaptive pattern) are built: others are refused at Setup */
 FSAI_SET(LocalSolveType, HYPRE_Int, (void)v)
 FSAI_SET(NumLevels, HYPRE_Int, o->num_levels = v)
 FSAI_SET(Threshold, HYPRE_Real, if (v < 0.0) fail(HYPRE_ERROR_ARG, "FSAI threshold < 0"); o->threshold = v)
@@ -1713,11 +1755,19 @@ FSAI_SET(MaxIterations, HYPRE_Int, if (v < 0) fail(HYPRE_ERROR_ARG, "FSAI max_it
 FSAI_SET(Tolerance, HYPRE_Real, o->tol = v)
 FSAI_SET(ZeroGuess, HYPRE_Int, o->zero_guess = v != 0)
 FSAI_SET(PrintLevel, HYPRE_Int, o->print_level = v)
-FSAI_SET(MaxSteps, HYPRE_Int, warn_ignored("fsai_max_steps", v))
-FSAI_SET(MaxStepSize, HYPRE_Int, warn_ignored("fsai_max_step_size", v))
+FSAI_SET(MaxSteps, HYPRE_Int, o->max_steps = v; if (o->algo_type != 4) warn_ignored("fsai_max_steps", v))
+FSAI_SET(MaxStepSize, HYPRE_Int, o->max_step_size = v; if (o->algo_type != 4) warn_ignored("fsai_max_step_size", v))
 FSAI_SET(MaxNnzRow, HYPRE_Int, warn_ignored("fsai_max_nnz_row", v))
-FSAI_SET(KapTolerance, HYPRE_Real, warn_ignored("fsai_kap_tolerance", v))
+FSAI_SET(KapTolerance, HYPRE_Real, o->kap_tolerance = v; if (o->algo_type != 4) warn_ignored("fsai_kap_tolerance", v))
 #undef FSAI_SET
+HYPRE_Int HYPRE_MI_FSAIGetSetupInfo(HYPRE_Solver solver, HYPRE_Int out[8]) {
+  API_BEGIN
+  FsaiSolver *o = FSAI(solver);
+  if (!out) fail(HYPRE_ERROR_ARG, "FSAIGetSetupInfo: no buffer");
+  if (!o->is_setup) fail(HYPRE_ERROR_GENERIC, "FSAIGetSetupInfo: the solver is not set up");
+  for (int q = 0; q < 8; q++) out[q] = o->setup_info[q];
+  API_END
+}
 
 // ------------------------------------------------------------------ AMG internals used by the driver's level dump
 static thread_local std::vector<hypre_ParCSRMatrix *> g_level_ptrs;
@@ -2530,6 +2580,14 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetLevelFSAI(HYPRE_Solver solver, HYPRE_Int level, H
   if (ja && !g.ja.empty()) memcpy(ja, g.ja.data(), g.ja.size() * sizeof(int));
   if (a && !g.a.empty()) memcpy(a, g.a.data(), g.a.size() * sizeof(double));
   if (omega) *omega = fs->omega;
+  API_END
+}
+HYPRE_Int HYPRE_MI_BoomerAMGGetLevelFSAIInfo(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int out[8]) {
+  API_BEGIN
+  FsaiSolver *fs = level_fsai_or_null(solver, level);
+  if (!fs) fail(HYPRE_ERROR_ARG, "GetLevelFSAIInfo: the level has no FSAI smoother");
+  if (!out) fail(HYPRE_ERROR_ARG, "GetLevelFSAIInfo: no buffer");
+  for (int q = 0; q < 8; q++) out[q] = fs->setup_info[q];
   API_END
 }
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCheby(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Real *out) {

@@ -1,8 +1,10 @@
-// Factorized sparse approximate inverse with a static pattern (HYPRE_FSAI, algo type 3): the preconditioner / solver
-// of HYPRE_FSAI* and BoomerAMG's complex smoother smooth_type 4.  Every rank works on its own
-// diagonal block B (block Jacobi across ranks): G is sparse lower triangular with G B G^T ~ I, and one step is
-// u += omega G^T G (f - A u).  Setup: filtered pattern, its symbolic k-th power (device SpGEMM), one small dense
-// solve per row (sk::fsai_local_solve), G^T by the device transpose, omega by power iteration on G B G^T.
+// Factorized sparse approximate inverse (HYPRE_FSAI): the preconditioner / solver of HYPRE_FSAI* and BoomerAMG's
+// complex smoother smooth_type 4.  Every rank works on its own diagonal block B (block Jacobi
+// across ranks): G is sparse lower triangular with G B G^T ~ I, and one step is u += omega G^T G (f - A u).
+// Setup, algo type 3 (static pattern): filtered pattern, its symbolic k-th power (device SpGEMM), one small dense
+// solve per row (sk::fsai_local_solve).  Algo type 4 (adaptive pattern, this library's number): every row grows its
+// pattern from the Kaporin gradient inside one kernel (sk::fsai_adaptive).  Both: G^T by the device transpose, omega
+// by power iteration on G B G^T.
 #include <cmath>
 
 #include "kernels.hpp"
@@ -10,22 +12,36 @@
 
 namespace mi {
 
+void FsaiSolver::check_adaptive(const std::string &where, int max_steps, int max_step_size, double kap_tolerance) {
+  if (max_steps < 1 || max_step_size < 1)
+    fail(4, where + ": FSAI max_steps " + std::to_string(max_steps) + " / max_step_size " + std::to_string(max_step_size) +
+                " is not implemented: both must be >= 1");
+  if ((long long)max_steps * max_step_size + 1 > 64)
+    fail(4, where + ": FSAI max_steps " + std::to_string(max_steps) + " x max_step_size " + std::to_string(max_step_size) +
+                " + 1 entries in a row is not implemented: the row bound must be <= 64");
+  if (!(kap_tolerance >= 0.0) || !std::isfinite(kap_tolerance))
+    fail(4, where + ": FSAI kap_tolerance is not implemented for this value: it must be finite and >= 0");
+}
+
 void FsaiSolver::setup(ParCSR &A, Comm &comm, const std::string &where) {
   ensure_init();
   hipStream_t s = ctx().stream;
   is_setup = false;
-  if (algo_type != 3)
+  if (algo_type != 3 && algo_type != 4)
     fail(4, where + ": FSAI algo_type " + std::to_string(algo_type) +
-                " is not implemented (3 = static pattern is); refusing to substitute another one");
-  if (num_levels < 1 || num_levels > 3)
+                " is not implemented (3 = static pattern and 4 = adaptive pattern are); refusing to substitute another one");
+  const bool adaptive = algo_type == 4;
+  if (adaptive) check_adaptive(where, max_steps, max_step_size, kap_tolerance);
+  if (!adaptive && (num_levels < 1 || num_levels > 3))
     fail(4, where + ": FSAI num_levels " + std::to_string(num_levels) + " is not implemented (1, 2 and 3 are)");
-  if (!(threshold >= 0.0)) fail(4, where + ": FSAI threshold must be >= 0");
+  if (!adaptive && !(threshold >= 0.0)) fail(4, where + ": FSAI threshold must be >= 0");
   if (eig_max_iters < 0) fail(4, where + ": FSAI eig_max_iters must be >= 0");
   MI_REQUIRE(A.on_device, (where + ": the matrix is not on the device").c_str());
   n = A.nrows;
   sk::DCsr B, P, Gd, Gtd;
   int rc = 0, bad_row = -1, bad_kind = 0;
   max_row = 0;
+  sk::FsaiAdaptiveInfo ai;
   if (n == 0) {  // a rank without rows: empty factors, but it takes part in every collective below
     sk::fsai_local_solve(B, P, Gd, max_row, bad_row, bad_kind, s);
   } else {
@@ -35,6 +51,11 @@ void FsaiSolver::setup(ParCSR &A, Comm &comm, const std::string &where) {
       MI_REQUIRE(!A.host_diag_stale, (where + ": the matrix has no host arrays").c_str());
       B.upload(A.diag, s);
     }
+  }
+  if (n > 0 && adaptive) {
+    rc = sk::fsai_adaptive(B, max_steps, max_step_size, kap_tolerance, 0, Gd, ai, s);
+    max_row = ai.max_row, bad_row = ai.bad_row, bad_kind = ai.bad_kind;
+  } else if (n > 0) {
     // pattern: lower triangle of the k-th power of the filtered graph (values 1: no product cancels)
     sk::DCsr S;
     sk::fsai_select(B, threshold, true, num_levels == 1, S, s);
@@ -62,6 +83,9 @@ void FsaiSolver::setup(ParCSR &A, Comm &comm, const std::string &where) {
     fail(1, where + ": FSAI local solve failed in row " + std::to_string(bad_row) +
                 (bad_kind == 1 ? " (singular local matrix)" : " (y_last <= 0: the diagonal block is not positive definite there)"));
   if (rc == 3) fail(1, where + ": FSAI local solve failed on another rank");
+  const int si[8] = {0, max_row, ai.max_candidates, ai.overflow_rows, ai.stop_tolerance, ai.stop_no_candidate,
+                     ai.stop_max_steps, -1};
+  for (int q = 0; q < 8; q++) setup_info[q] = si[q];
   P.release();
   B.release();
   sk::transpose(Gd, Gtd, s);

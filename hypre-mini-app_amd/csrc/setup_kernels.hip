@@ -16,6 +16,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cstdlib>
 
 #include "kernels.hpp"
 #include "parcsr.hpp"
@@ -3677,6 +3678,432 @@ int fsai_local_solve(const DCsr &B, const DCsr &P, DCsr &G, int &max_row, int &b
 void fsai_random_vector(int n, long long gid0, int seed, double *v, hipStream_t s) {
   if (n) fsai_random_k<<<grid_for(((long long)n + BLK - 1) / BLK), BLK, 0, s>>>(n, gid0, seed, v);
   MI_HIP(hipGetLastError());
+}
+
+
+// ---------------------------------------------------------------- FSAI with the adaptive pattern (fsai_algo_type 4;
+// fsai.cpp, amg_setup.cpp build_fsai_adaptive, DESIGN.md section 3 "FSAI (adaptive pattern)")
+namespace {
+constexpr unsigned FA_EMPTY = 0xffffffffu, FA_TAKEN = 0x80000000u;  // a free slot; the column has moved into the pattern
+// how a row ended: 0 still growing; 1 - 3 finished (tolerance, no candidate, max_steps); 4 singular, 5 y_last <= 0;
+// 6 its candidates outgrew the table (the row is computed again with the table in global memory)
+enum { FA_RUN = 0, FA_TOL = 1, FA_NOCAND = 2, FA_MAXSTEPS = 3, FA_SINGULAR = 4, FA_YLAST = 5, FA_OVERFLOW = 6 };
+
+__device__ __forceinline__ unsigned fa_hash(int j) {
+  const unsigned x = (unsigned)j * 2654435761u;
+  return x ^ (x >> 15);
+}
+
+// One row of G per group of GS lanes (64 / GS rows per one-wave workgroup): the row grows its pattern pat (ascending, i
+// last; at most bound = S * T + 1 <= GS entries) in up to S steps without leaving the kernel.  A step is (1) the local
+// solve of B[pat, pat]^T y = e_last -- the layout and the elimination of fsai_local_solve_k --, (2) the stop tests on
+// psi = 1 / y_last, (3) the gradient phi_j = sum_{r in pat, ascending} b_rj y_r over the stored columns j < i outside
+// pat, in a table keyed by column (open addressing, linear probing; `ts` slots, a power of two): the pattern's rows are
+// walked one after the other with a barrier between them, the lanes take distinct entries of a row, and a row's
+// columns are distinct, so every slot has one writer per pass and every phi_j is summed in the stated order whatever
+// slot the column landed in; (4) T rounds of a group-wide argmax by (|phi| descending, column ascending) -- the chosen
+// slot is marked FA_TAKEN by the lane that scans it and keeps its place in the probe sequences --, (5) the merge of the
+// chosen columns into pat by rank.  The table lives in LDS (gkey == null) or in global memory (the rows of `rows`
+// whose candidates did not fit; keys preset to FA_EMPTY by the caller): same code, same bits.  Groups of one wave stop
+// at different steps: every trip count with a barrier inside is the wave's largest, and a finished group idles.
+// Output at position p = i - r0: pattern and g = y / sqrt(y_last) padded to `bound` entries, cnt[i] = the row's length
+// (0 for a row that failed or overflowed), meta[p] = how it ended, ncand[p] = the most candidates it met at a step.
+template <int GS>
+__global__ __launch_bounds__(64) void fsai_adaptive_k(const int *__restrict__ rows, int r0, int nlist,
+                                                      const long long *__restrict__ Bia, const int *__restrict__ Bja,
+                                                      const double *__restrict__ Ba, int S, int T, double tau, int bound,
+                                                      int ts, unsigned *__restrict__ gkey, double *__restrict__ gval,
+                                                      int *__restrict__ oja, double *__restrict__ oa, int *__restrict__ cnt,
+                                                      int *__restrict__ meta, int *__restrict__ ncand) {
+  constexpr int RPB = 64 / GS, LD = GS + 1, LTS = 16 * GS;
+  __shared__ double M[RPB][GS][LD];
+  __shared__ double y[RPB][GS];
+  __shared__ double lval[RPB][LTS];
+  __shared__ unsigned lkey[RPB][LTS];
+  __shared__ int piv[RPB][GS];
+  __shared__ int pat[RPB][GS];
+  __shared__ int full[RPB];
+  const int g = threadIdx.x / GS, t = threadIdx.x % GS;
+  const long long q = bid() * RPB + g;
+  const bool live = q < nlist;
+  const int i = live ? (rows ? rows[q] : r0 + (int)q) : 0;
+  unsigned *tk = gkey ? gkey + q * ts : &lkey[g][0];
+  double *tv = gkey ? gval + q * ts : &lval[g][0];
+  const unsigned mask = (unsigned)ts - 1u;
+  if (live && !gkey)
+    for (int u = t; u < ts; u += GS) tk[u] = FA_EMPTY;
+  if (t == 0) pat[g][0] = i, full[g] = 0;
+  int m = live ? 1 : 0, state = live ? FA_RUN : FA_MAXSTEPS, most = 0;
+  double psi = 0.0;
+  double *Mt = &M[g][t][0];
+  __syncthreads();
+  for (int step = 0; step <= S; step++) {
+    if (!__ballot(state == FA_RUN)) break;  // one wave per workgroup: uniform
+    // ---- (1) local solve on the current pattern
+    const int ma = state == FA_RUN ? m : 0;
+    if (t < ma) {
+      const int col = pat[g][t];
+      for (int c = 0; c < ma; c++) {
+        const int r = pat[g][c];
+        long long lo = Bia[r];
+        const long long end = Bia[r + 1];
+        long long hi = end;
+        while (lo < hi) {
+          const long long mid = (lo + hi) >> 1;
+          if (Bja[mid] < col)
+            lo = mid + 1;
+          else
+            hi = mid;
+        }
+        Mt[c] = (lo < end && Bja[lo] == col) ? Ba[lo] : 0.0;
+      }
+      Mt[GS] = (t == ma - 1) ? 1.0 : 0.0;
+    }
+    int mb = ma;
+    for (int off = 32; off > 0; off >>= 1) mb = max(mb, __shfl_xor(mb, off, 64));
+    __syncthreads();
+    bool used = false, singular = false;
+    int pstep = GS;  // the elimination step this lane's row was the pivot of
+    for (int k = 0; k < mb; k++) {
+      double v = (t < ma && !used && k < ma) ? fabs(Mt[k]) : -1.0;
+      int idx = t;
+      for (int off = GS / 2; off > 0; off >>= 1) {
+        const double ov = __shfl_xor(v, off, GS);
+        const int oi = __shfl_xor(idx, off, GS);
+        if (ov > v || (ov == v && oi < idx)) v = ov, idx = oi;
+      }
+      if (k < ma && !singular) {
+        if (!(v > 0.0)) singular = true;
+        if (t == 0) piv[g][k] = idx;
+        if (t == idx) used = true, pstep = k;
+        if (!singular && t < ma && !used) {
+          const double *Mp = &M[g][idx][0];
+          const double l = Mt[k] / Mp[k];
+          for (int c = k + 1; c < ma; c++) Mt[c] = Mt[c] - l * Mp[c];
+          Mt[GS] = Mt[GS] - l * Mp[GS];
+        }
+      }
+      __syncthreads();
+    }
+    for (int c = mb - 1; c >= 0; c--) {
+      if (c < ma && !singular && t == piv[g][c]) y[g][c] = Mt[GS] / Mt[c];
+      __syncthreads();
+      if (c < ma && !singular && t < ma && pstep < c) Mt[GS] = Mt[GS] - Mt[c] * y[g][c];
+    }
+    __syncthreads();
+    // ---- (2) the stop tests (every lane of the group computes the same)
+    if (state == FA_RUN) {
+      const double ylast = singular ? 0.0 : y[g][m - 1];
+      if (singular) {
+        state = FA_SINGULAR;
+      } else if (!(ylast > 0.0)) {
+        state = FA_YLAST;
+      } else {
+        const double psin = 1.0 / ylast;
+        if (step > 0 && psi - psin < tau * psi)
+          state = FA_TOL;
+        else if (step == S)
+          state = FA_MAXSTEPS;
+        else
+          psi = psin;
+      }
+    }
+    // ---- (3) the gradient of the rows that go on
+    const int mg = state == FA_RUN ? m : 0;
+    if (mg)
+      for (int u = t; u < ts; u += GS) tv[u] = 0.0;
+    int mgb = mg;
+    for (int off = 32; off > 0; off >>= 1) mgb = max(mgb, __shfl_xor(mgb, off, 64));
+    __syncthreads();
+    for (int c = 0; c < mgb; c++) {
+      if (c < mg) {
+        const int r = pat[g][c];
+        const double yr = y[g][c];
+        const long long e = Bia[r + 1];
+        for (long long k = Bia[r] + t; k < e; k += GS) {
+          const int j = Bja[k];
+          if (j >= i) break;
+          unsigned h = fa_hash(j) & mask;
+          bool found = false;
+          for (int probe = 0; probe < ts; probe++, h = (h + 1u) & mask) {
+            unsigned cur = __atomic_load_n(&tk[h], __ATOMIC_RELAXED);
+            if (cur == FA_EMPTY) {
+              cur = atomicCAS(&tk[h], FA_EMPTY, (unsigned)j);
+              if (cur == FA_EMPTY) cur = (unsigned)j;
+            }
+            if ((cur & ~FA_TAKEN) == (unsigned)j) {
+              if (!(cur & FA_TAKEN)) tv[h] = tv[h] + Ba[k] * yr;
+              found = true;
+              break;
+            }
+          }
+          if (!found) full[g] = 1;
+        }
+      }
+      __syncthreads();
+    }
+    if (state == FA_RUN && full[g]) state = FA_OVERFLOW;
+    // ---- (4) selection: up to T columns, one per round
+    const bool sel = state == FA_RUN;
+    int chosen = 0;
+    for (int round = 0; round < T; round++) {
+      double bv = -1.0;
+      int bj = 0x7fffffff, bs = -1, nc = 0;
+      if (sel)
+        for (int u = t; u < ts; u += GS) {
+          const unsigned key = tk[u];
+          if (key & FA_TAKEN) continue;  // FA_EMPTY has the bit too
+          const double v = fabs(tv[u]);
+          if (!(v > 0.0)) continue;
+          nc++;
+          if (v > bv || (v == bv && (int)key < bj)) bv = v, bj = (int)key, bs = u;
+        }
+      for (int off = GS / 2; off > 0; off >>= 1) {
+        const double ov = __shfl_xor(bv, off, GS);
+        const int oj = __shfl_xor(bj, off, GS);
+        const int os = __shfl_xor(bs, off, GS);
+        if (ov > bv || (ov == bv && oj < bj)) bv = ov, bj = oj, bs = os;
+        if (round == 0) nc += __shfl_xor(nc, off, GS);
+      }
+      if (round == 0) most = max(most, nc);
+      if (sel && bv > 0.0) {
+        if ((bs % GS) == t) tk[bs] = (unsigned)bj | FA_TAKEN;
+        if (t == 0) pat[g][m - 1 + chosen] = bj;
+        chosen++;
+      }
+    }
+    if (sel && chosen == 0) state = FA_NOCAND;
+    __syncthreads();
+    // ---- (5) merge: pat[0 .. m-2] (ascending) and the chosen columns at pat[m-1 ..] go to their ranks, i stays last
+    const int tot = state == FA_RUN ? m - 1 + chosen : 0;
+    int mycol = 0, rank = 0;
+    if (t < tot) {
+      mycol = pat[g][t];
+      for (int u = 0; u < tot; u++) rank += pat[g][u] < mycol;
+    }
+    __syncthreads();
+    if (t < tot) pat[g][rank] = mycol;
+    if (tot && t == 0) pat[g][tot] = i;
+    if (tot) m = tot + 1;
+    __syncthreads();
+  }
+  if (!live) return;
+  const bool ok = state >= FA_TOL && state <= FA_MAXSTEPS;
+  const long long p = (long long)i - r0;
+  if (ok && t < m) {
+    oja[p * bound + t] = pat[g][t];
+    oa[p * bound + t] = y[g][t] / sqrt(y[g][m - 1]);
+  }
+  if (t == 0) cnt[i] = ok ? m : 0, meta[p] = state, ncand[p] = most;
+}
+
+// The census of a batch's rows [r0, r0 + nb) -- or of the nlist rows of `rows` --: counters[0..2] += the rows finished
+// by the tolerance / for want of candidates / by max_steps, [3] = max row length, [4] = max candidates, [5] = min
+// failed row, [6] += rows that overflowed (appended to over, when given; their order is immaterial).  One atomic per
+// wave and counter.
+__global__ __launch_bounds__(BLK) void fsai_adaptive_census_k(const int *__restrict__ rows, int r0, int nlist,
+                                                              const int *__restrict__ cnt, const int *__restrict__ meta,
+                                                              const int *__restrict__ ncand, int *__restrict__ counters,
+                                                              int *__restrict__ over) {
+  const long long q = bid() * BLK + threadIdx.x;
+  const int lane = (int)(threadIdx.x & 63);
+  const bool live = q < nlist;
+  const int i = live ? (rows ? rows[q] : r0 + (int)q) : 0;
+  const int st = live ? meta[i - r0] : -1;
+  int len = live ? cnt[i] : 0, nc = live ? ncand[i - r0] : 0;
+  if (st == FA_OVERFLOW) nc = 0;
+  for (int off = 32; off > 0; off >>= 1) {
+    len = max(len, __shfl_xor(len, off, 64));
+    nc = max(nc, __shfl_xor(nc, off, 64));
+  }
+  if (lane == 0 && len > 0) atomicMax(&counters[3], len);
+  if (lane == 0 && nc > 0) atomicMax(&counters[4], nc);
+  for (int k = FA_TOL; k <= FA_MAXSTEPS; k++) {
+    const unsigned long long b = __ballot(st == k);
+    if (lane == 0 && b) atomicAdd(&counters[k - 1], __popcll(b));
+  }
+  if (st == FA_SINGULAR || st == FA_YLAST) atomicMin(&counters[5], i);
+  const unsigned long long ob = __ballot(st == FA_OVERFLOW);
+  if (ob) {
+    int base = 0;
+    const int leader = __ffsll((long long)ob) - 1;
+    if (lane == leader) base = atomicAdd(&counters[6], __popcll(ob));
+    base = __shfl(base, leader, 64);
+    if (st == FA_OVERFLOW && over) over[base + __popcll(ob & ((1ULL << lane) - 1ULL))] = i;
+  }
+}
+
+// rows padded to `bound` entries -> the batch's compact arrays at the scanned offsets
+__global__ __launch_bounds__(BLK) void fsai_adaptive_compact_k(long long total, int bound, const int *__restrict__ cnt,
+                                                               const long long *__restrict__ lia,
+                                                               const int *__restrict__ oja, const double *__restrict__ oa,
+                                                               int *__restrict__ cja, double *__restrict__ ca) {
+  const long long x = bid() * BLK + threadIdx.x;
+  if (x >= total) return;
+  const long long p = x / bound;
+  const int e = (int)(x - p * bound);
+  if (e >= cnt[p]) return;
+  cja[lia[p] + e] = oja[x];
+  ca[lia[p] + e] = oa[x];
+}
+
+__global__ __launch_bounds__(BLK) void row_length_max_k(int n, const long long *__restrict__ ia, int *__restrict__ out) {
+  const long long i = bid() * BLK + threadIdx.x;
+  int len = i < n ? (int)(ia[i + 1] - ia[i]) : 0;
+  for (int off = 32; off > 0; off >>= 1) len = max(len, __shfl_xor(len, off, 64));
+  if ((threadIdx.x & 63) == 0 && len > 0) atomicMax(out, len);
+}
+
+template <int GS>
+void fsai_adaptive_launch(const int *rows, int r0, int nlist, const DCsr &B, int S, int T, double tau, int bound, int ts,
+                          unsigned *gkey, double *gval, int *oja, double *oa, int *cnt, int *meta, int *ncand,
+                          hipStream_t s) {
+  constexpr int RPB = 64 / GS;
+  fsai_adaptive_k<GS><<<grid_for(((long long)nlist + RPB - 1) / RPB), 64, 0, s>>>(rows, r0, nlist, B.ia.p, B.ja.p, B.a.p, S, T,
+                                                                              tau, bound, ts, gkey, gval, oja, oa, cnt,
+                                                                              meta, ncand);
+}
+void fsai_adaptive_run(int gs, const int *rows, int r0, int nlist, const DCsr &B, int S, int T, double tau, int bound,
+                       int ts, unsigned *gkey, double *gval, int *oja, double *oa, int *cnt, int *meta, int *ncand,
+                       hipStream_t s) {
+  if (gs == 16)
+    fsai_adaptive_launch<16>(rows, r0, nlist, B, S, T, tau, bound, ts, gkey, gval, oja, oa, cnt, meta, ncand, s);
+  else if (gs == 32)
+    fsai_adaptive_launch<32>(rows, r0, nlist, B, S, T, tau, bound, ts, gkey, gval, oja, oa, cnt, meta, ncand, s);
+  else
+    fsai_adaptive_launch<64>(rows, r0, nlist, B, S, T, tau, bound, ts, gkey, gval, oja, oa, cnt, meta, ncand, s);
+  MI_HIP(hipGetLastError());
+}
+}  // namespace
+
+int fsai_adaptive_lds_slots(int bound) { return 16 * (bound <= 16 ? 16 : (bound <= 32 ? 32 : 64)); }
+
+long long fsai_adaptive_batch_rows(int bound) {
+  if (const char *e = getenv("MI_HYPRE_FSAI_BATCH_ROWS"))
+    if (atoll(e) > 0) return atoll(e);
+  return std::max<long long>(1, (256LL << 20) / (12LL * bound));
+}
+
+int fsai_adaptive(const DCsr &B, int max_steps, int max_step_size, double kap_tolerance, int table_slots, DCsr &G,
+                  FsaiAdaptiveInfo &info, hipStream_t s) {
+  const int n = B.nrows;
+  info = FsaiAdaptiveInfo();
+  const int bound = max_steps * max_step_size + 1;
+  MI_REQUIRE(max_steps >= 1 && max_step_size >= 1 && bound <= 64, "device adaptive FSAI: max_steps * max_step_size + 1 in 2 ... 64");
+  MI_REQUIRE(table_slots >= 0 && (table_slots & (table_slots - 1)) == 0, "device adaptive FSAI: table_slots is 0 or a power of two");
+  G.release();
+  G.nrows = n;
+  G.ncols = B.ncols;
+  G.ia.alloc((size_t)n + 1);
+  if (n == 0) {  // a rank without rows: an empty G with its one row pointer
+    MI_HIP(hipMemsetAsync(G.ia.p, 0, sizeof(long long), s));
+    G.ja.alloc(0);
+    G.a.alloc(0);
+    return 0;
+  }
+  const int gs = bound <= 16 ? 16 : (bound <= 32 ? 32 : 64);
+  const int lds_slots = table_slots ? std::min(table_slots, fsai_adaptive_lds_slots(bound)) : fsai_adaptive_lds_slots(bound);
+  const long long batch = std::min<long long>(n, fsai_adaptive_batch_rows(bound));
+  DVec<int> cnt((size_t)n), meta((size_t)batch), ncand((size_t)batch), over((size_t)batch), counters(8);
+  DVec<int> oja((size_t)(batch * bound));
+  DVec<double> oa((size_t)(batch * bound));
+  DVec<long long> lia((size_t)batch + 1);
+  DVec<unsigned> gkey;  // the overflow route's tables, on first use
+  DVec<double> gval;
+  long long gslots = 0, gcap = 0;
+  struct Chunk {
+    DVec<int> ja;
+    DVec<double> a;
+    long long nnz = 0;
+  };
+  std::vector<Chunk> chunks;
+  long long nnz = 0;
+  for (long long r0 = 0; r0 < n; r0 += batch) {
+    const int nb = (int)std::min<long long>(batch, n - r0);
+    const dim3 grb = grid_for(((long long)nb + BLK - 1) / BLK);
+    int hc[8] = {0, 0, 0, 0, 0, 0x7fffffff, 0, 0};
+    MI_HIP(hipMemcpyAsync(counters.p, hc, sizeof(hc), hipMemcpyHostToDevice, s));
+    MI_HIP(hipStreamSynchronize(s));  // hc is reused below
+    fsai_adaptive_run(gs, nullptr, (int)r0, nb, B, max_steps, max_step_size, kap_tolerance, bound, lds_slots, nullptr, nullptr,
+                      oja.p, oa.p, cnt.p, meta.p, ncand.p, s);
+    fsai_adaptive_census_k<<<grb, BLK, 0, s>>>(nullptr, (int)r0, nb, cnt.p, meta.p, ncand.p, counters.p, over.p);
+    MI_HIP(hipGetLastError());
+    d2h(hc, counters.p, sizeof(hc), s);
+    const int nover = hc[6];
+    if (nover > 0) {  // the same code with the table in global memory, as many rows at a time as the scratch holds
+      if (!gslots) {
+        MI_HIP(hipMemsetAsync(counters.p + 7, 0, sizeof(int), s));
+        row_length_max_k<<<grid_for(((long long)n + BLK - 1) / BLK), BLK, 0, s>>>(n, B.ia.p, counters.p + 7);
+        int maxlen = 0;
+        d2h(&maxlen, counters.p + 7, sizeof(int), s);
+        const long long keys = std::min<long long>((long long)bound * maxlen, n);  // distinct columns a row can meet
+        gslots = 64;
+        while (gslots < 2 * keys) gslots <<= 1;
+        MI_REQUIRE(gslots <= (1LL << 30), "device adaptive FSAI: a row's candidate table exceeds 2^30 slots");
+        gcap = std::max<long long>(1, std::min<long long>(batch, (8LL << 20) / gslots));
+        gkey.alloc((size_t)(gcap * gslots));
+        gval.alloc((size_t)(gcap * gslots));
+      }
+      for (long long o = 0; o < nover; o += gcap) {
+        const int ns = (int)std::min<long long>(gcap, nover - o);
+        MI_HIP(hipMemsetAsync(gkey.p, 0xff, (size_t)ns * (size_t)gslots * sizeof(unsigned), s));
+        fsai_adaptive_run(gs, over.p + o, (int)r0, ns, B, max_steps, max_step_size, kap_tolerance, bound, (int)gslots, gkey.p,
+                          gval.p, oja.p, oa.p, cnt.p, meta.p, ncand.p, s);
+      }
+      MI_HIP(hipMemsetAsync(counters.p + 6, 0, sizeof(int), s));
+      fsai_adaptive_census_k<<<grid_for(((long long)nover + BLK - 1) / BLK), BLK, 0, s>>>(over.p, (int)r0, nover, cnt.p, meta.p,
+                                                                                       ncand.p, counters.p, nullptr);
+      MI_HIP(hipGetLastError());
+      d2h(hc, counters.p, sizeof(hc), s);
+      MI_REQUIRE(hc[6] == 0, "device adaptive FSAI: a row outgrew its table in global memory");
+      info.overflow_rows += nover;
+    }
+    info.stop_tolerance += hc[0];
+    info.stop_no_candidate += hc[1];
+    info.stop_max_steps += hc[2];
+    info.max_row = std::max(info.max_row, hc[3]);
+    info.max_candidates = std::max(info.max_candidates, hc[4]);
+    if (hc[5] < n) {  // batches ascend: the first failing row of this batch is the first of all
+      int kind = 0;
+      d2h(&kind, meta.p + (hc[5] - r0), sizeof(int), s);
+      info.status = 2;
+      info.bad_row = hc[5];
+      info.bad_kind = kind == FA_SINGULAR ? 1 : 2;
+      G.release();
+      return 2;
+    }
+    // scan and compact this batch
+    exclusive_scan(cnt.p + r0, lia.p, nb, s);
+    Chunk ch;
+    d2h(&ch.nnz, lia.p + nb, sizeof(long long), s);
+    ch.ja.alloc((size_t)ch.nnz);
+    ch.a.alloc((size_t)ch.nnz);
+    const long long total = (long long)nb * bound;
+    fsai_adaptive_compact_k<<<grid_for((total + BLK - 1) / BLK), BLK, 0, s>>>(total, bound, cnt.p + r0, lia.p, oja.p, oa.p,
+                                                                            ch.ja.p, ch.a.p);
+    MI_HIP(hipGetLastError());
+    nnz += ch.nnz;
+    chunks.push_back(std::move(ch));
+  }
+  exclusive_scan(cnt.p, G.ia.p, n, s);
+  G.nnz = nnz;
+  if (chunks.size() == 1) {
+    G.ja = std::move(chunks[0].ja);
+    G.a = std::move(chunks[0].a);
+  } else {
+    G.ja.alloc((size_t)nnz);
+    G.a.alloc((size_t)nnz);
+    long long o = 0;
+    for (Chunk &ch : chunks) {
+      if (ch.nnz) {
+        MI_HIP(hipMemcpyAsync(G.ja.p + o, ch.ja.p, (size_t)ch.nnz * sizeof(int), hipMemcpyDeviceToDevice, s));
+        MI_HIP(hipMemcpyAsync(G.a.p + o, ch.a.p, (size_t)ch.nnz * sizeof(double), hipMemcpyDeviceToDevice, s));
+      }
+      o += ch.nnz;
+    }
+  }
+  MI_HIP(hipStreamSynchronize(s));  // (the temporaries are released on return)
+  return 0;
 }
 
 

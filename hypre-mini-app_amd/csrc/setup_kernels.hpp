@@ -264,6 +264,26 @@ int fsai_local_solve(const DCsr &B, const DCsr &P, DCsr &G, int &max_row, int &b
 // v[i] = element gid0 + i of the global Park-Miller stream seeded with `seed` (the PMIS measures' stream) / (2^31 - 1)
 void fsai_random_vector(int n, long long gid0, int seed, double *v, hipStream_t s);
 
+// ---- FSAI with the adaptive pattern (fsai_algo_type 4; DESIGN.md section 3, "FSAI (adaptive pattern)"), on a rank's
+// diagonal block B (columns ascending in every row): every row grows its pattern from the Kaporin gradient in up to
+// max_steps steps of up to max_step_size columns (max_steps * max_step_size + 1 <= 64), one row per 16 / 32 / 64 lanes
+// by that bound, without leaving the kernel -- bit for bit hs::build_fsai_adaptive.  The candidate table of a row has
+// table_slots slots in LDS (a power of two; 0 or above fsai_adaptive_lds_slots: that many); the rows whose candidates
+// do not fit are computed again by the same code with the table in global memory.  Rows are written padded to the bound
+// and compacted, fsai_adaptive_batch_rows rows at a time.  Returns 0, or 2 when a row fails (info.bad_row = the first,
+// info.bad_kind 1 singular, 2 y_last <= 0; G is not built).
+struct FsaiAdaptiveInfo {
+  int status = 0;                                                   // 0 built, 2 a row failed
+  int max_row = 0, max_candidates = 0;                              // the largest row of G / candidate count at a step
+  int overflow_rows = 0;                                            // rows that took the global-memory table (device only)
+  int stop_tolerance = 0, stop_no_candidate = 0, stop_max_steps = 0;  // rows by the reason they stopped growing
+  int bad_row = -1, bad_kind = 0;
+};
+int fsai_adaptive(const DCsr &B, int max_steps, int max_step_size, double kap_tolerance, int table_slots, DCsr &G,
+                  FsaiAdaptiveInfo &info, hipStream_t s);
+int fsai_adaptive_lds_slots(int bound);         // LDS table slots per row for a row bound (16 x the lane-group size)
+long long fsai_adaptive_batch_rows(int bound);  // rows per batch: 256 MiB of padded rows (MI_HYPRE_FSAI_BATCH_ROWS overrides)
+
 // ---- distributed setup on the device (amg_setup_dist.cpp: BoomerAMG::build_distributed_device)
 // Column map between two extended index spaces [remote below | own range | remote above] (ascending global ids):
 // column c of the source becomes below[c] (c < nb_old), own_tab[c - nb_old] or own_new0 + (c - nb_old) (own range,

@@ -113,12 +113,20 @@ struct IluSolver : SolverBase {
   int solve(ParCSR &A, ParVector &b, ParVector &x);     // x += M^-1 (b - A x), max_iter times or to tol
 };
 
-// HYPRE_FSAI with the static pattern (algo type 3): G lower triangular on the lower triangle of
+// HYPRE_FSAI.  Algo type 3, the static pattern: G lower triangular on the lower triangle of
 // the k-th power (k = num_levels) of the threshold-filtered graph of this rank's diagonal block, one dense local solve
-// per row; one step is x += omega G^T G (b - A x).  Also the complex smoother smooth_type 4 of BoomerAMG.
+// per row.  Algo type 4, the adaptive pattern: every row grows its own pattern from the Kaporin gradient (max_steps
+// steps of max_step_size columns, stopped by kap_tolerance).  One step is x += omega G^T G (b - A x).  Also the
+// complex smoother smooth_type 4 of BoomerAMG.
 struct FsaiSolver : SolverBase {
   int algo_type = 3, num_levels = 1, eig_max_iters = 5, max_iter = 20, print_level = 0;
   double threshold = 0.01, tol = 1e-6;
+  int max_steps = 3, max_step_size = 5;  // algo type 4 only
+  double kap_tolerance = 1e-3;
+  // how G was built (HYPRE_MI_FSAIGetSetupInfo): 0 built, largest row, largest candidate count, rows that took the
+  // global-memory table, rows stopped by the tolerance / for want of candidates / by max_steps, -1 (type 3: the
+  // adaptive entries are 0)
+  int setup_info[8] = {0, 0, 0, 0, 0, 0, 0, -1};
   double omega_user = 0.0;  // > 0: HYPRE_FSAISetOmega, no eigenvalue estimate
   bool zero_guess = false;
   bool is_setup = false;
@@ -132,6 +140,9 @@ struct FsaiSolver : SolverBase {
   double final_rel_res = 0.0;
   FsaiSolver() : SolverBase(K_FSAI) {}
   void setup(ParCSR &A, Comm &comm, const std::string &where);
+  // the adaptive parameters a Setup refuses: max_steps < 1, max_step_size < 1, max_steps * max_step_size + 1 > 64,
+  // kap_tolerance negative or not finite
+  static void check_adaptive(const std::string &where, int max_steps, int max_step_size, double kap_tolerance);
   // u += omega G^T G res (zero: u = omega G^T G res): two launches, the update fused into the G^T product
   void apply_add(const double *res, double *u, bool zero, int prof = -1);
   int solve(ParCSR &A, ParVector &b, ParVector &x);  // x += omega G^T G (b - A x), max_iter times or to tol

@@ -447,6 +447,25 @@ void HypreSystem::setup_boomeramg_precond() {
     if (node["mi_filter_threshold_r"]) HYPRE_BoomerAMGSetFilterThresholdR(precond_, node["mi_filter_threshold_r"].as<double>());
 #endif
   }
+  /* this library's keys for the FSAI smoother (smooth_type 4): mi_fsai_algo_type 3 = static pattern (mi_fsai_num_levels,
+   * mi_fsai_threshold), 4 = adaptive pattern built on the device (mi_fsai_max_steps, mi_fsai_max_step_size,
+   * mi_fsai_kap_tolerance); an absent key leaves the solver's default (3; 1, 0.01; 3, 5, 1e-3).  The type goes first:
+   * the adaptive values are said to have no effect while the type is 3 */
+  if (node["mi_fsai_algo_type"] || node["mi_fsai_num_levels"] || node["mi_fsai_threshold"] || node["mi_fsai_max_steps"] ||
+      node["mi_fsai_max_step_size"] || node["mi_fsai_kap_tolerance"]) {
+#ifdef MI_HOST_WITH_LIBHYPRE
+    throw std::runtime_error("Hypre Config:: mi_fsai_* are keys of libmi_hypre (its algo type 4 is not a libHYPRE value); "
+                             "this adapter does not pass them to libHYPRE");
+#else
+    if (node["mi_fsai_algo_type"]) HYPRE_BoomerAMGSetFSAIAlgoType(precond_, node["mi_fsai_algo_type"].as<int>());
+    if (node["mi_fsai_num_levels"]) HYPRE_BoomerAMGSetFSAINumLevels(precond_, node["mi_fsai_num_levels"].as<int>());
+    if (node["mi_fsai_threshold"] && HYPRE_BoomerAMGSetFSAIThreshold(precond_, node["mi_fsai_threshold"].as<double>()))
+      throw std::runtime_error(std::string("Hypre Config:: mi_fsai_threshold: ") + HYPRE_MI_LastErrorMessage());
+    if (node["mi_fsai_max_steps"]) HYPRE_BoomerAMGSetFSAIMaxSteps(precond_, node["mi_fsai_max_steps"].as<int>());
+    if (node["mi_fsai_max_step_size"]) HYPRE_BoomerAMGSetFSAIMaxStepSize(precond_, node["mi_fsai_max_step_size"].as<int>());
+    if (node["mi_fsai_kap_tolerance"]) HYPRE_BoomerAMGSetFSAIKapTolerance(precond_, node["mi_fsai_kap_tolerance"].as<double>());
+#endif
+  }
   if (node["trunc_factor"]) HYPRE_BoomerAMGSetTruncFactor(precond_, node["trunc_factor"].as<double>());
   if (node["agg_p12_trunc_factor"])
     HYPRE_BoomerAMGSetAggP12TruncFactor(precond_, node["agg_p12_trunc_factor"].as<double>());

@@ -501,7 +501,10 @@ class BoomerAMG:
         names = {"fsai_algo_type": ("HYPRE_BoomerAMGSetFSAIAlgoType", int),
                  "fsai_num_levels": ("HYPRE_BoomerAMGSetFSAINumLevels", int),
                  "fsai_threshold": ("HYPRE_BoomerAMGSetFSAIThreshold", float),
-                 "fsai_eig_max_iters": ("HYPRE_BoomerAMGSetFSAIEigMaxIters", int)}
+                 "fsai_eig_max_iters": ("HYPRE_BoomerAMGSetFSAIEigMaxIters", int),
+                 "fsai_max_steps": ("HYPRE_BoomerAMGSetFSAIMaxSteps", int),
+                 "fsai_max_step_size": ("HYPRE_BoomerAMGSetFSAIMaxStepSize", int),
+                 "fsai_kap_tolerance": ("HYPRE_BoomerAMGSetFSAIKapTolerance", float)}
         for k, v in kw.items():
             fn, conv = names[k]
             call(fn, self.h, conv(v))
@@ -538,6 +541,12 @@ class BoomerAMG:
         om = c_dbl()
         call("HYPRE_MI_BoomerAMGGetLevelFSAI", self.h, level, ia, ja, a, C.byref(om))
         return ia, ja[: nnz.value], a[: nnz.value], om.value
+
+    def level_fsai_info(self, level):
+        """How the level's FSAI factor was built (HYPRE_MI_BoomerAMGGetLevelFSAIInfo): dict with FSAI_INFO_NAMES."""
+        out = np.full(8, -2, dtype=np.int32)
+        call("HYPRE_MI_BoomerAMGGetLevelFSAIInfo", self.h, level, out)
+        return {k: int(v) for k, v in zip(FSAI_INFO_NAMES, out)}
 
     def smooth_level(self, level, f, u=None):
         """One complex-smoother step of the level on host arrays; u None = zero guess."""
@@ -638,13 +647,20 @@ class ILU:
 
 
 class FSAI:
-    """HYPRE_FSAI, static pattern (algo type 3): x += omega G^T G (b - A x); a preconditioner (set_precond) or a solver."""
+    """HYPRE_FSAI, static pattern (algo type 3; num_levels, threshold) or adaptive pattern (algo type 4; max_steps,
+    max_step_size, kap_tolerance): x += omega G^T G (b - A x); a preconditioner (set_precond) or a solver."""
 
     def __init__(self, max_iterations=1, tolerance=0.0, zero_guess=1, algo_type=3, num_levels=1, threshold=0.01,
-                 eig_max_iters=5, omega=None, print_level=0):
+                 eig_max_iters=5, omega=None, print_level=0, max_steps=None, max_step_size=None, kap_tolerance=None):
         self.h = vp()
         call("HYPRE_FSAICreate", C.byref(self.h))
         call("HYPRE_FSAISetAlgoType", self.h, int(algo_type))
+        if max_steps is not None:
+            call("HYPRE_FSAISetMaxSteps", self.h, int(max_steps))
+        if max_step_size is not None:
+            call("HYPRE_FSAISetMaxStepSize", self.h, int(max_step_size))
+        if kap_tolerance is not None:
+            call("HYPRE_FSAISetKapTolerance", self.h, float(kap_tolerance))
         call("HYPRE_FSAISetNumLevels", self.h, int(num_levels))
         call("HYPRE_FSAISetThreshold", self.h, float(threshold))
         call("HYPRE_FSAISetEigMaxIters", self.h, int(eig_max_iters))
@@ -661,6 +677,12 @@ class FSAI:
 
     def solve(self, A, b, x):
         return call("HYPRE_FSAISolve", self.h, A.par, b.par, x.par)
+
+    def setup_info(self):
+        """How G was built (HYPRE_MI_FSAIGetSetupInfo): dict with FSAI_INFO_NAMES."""
+        out = np.full(8, -2, dtype=np.int32)
+        call("HYPRE_MI_FSAIGetSetupInfo", self.h, out)
+        return {k: int(v) for k, v in zip(FSAI_INFO_NAMES, out)}
 
     def destroy(self):
         if self.h:
@@ -1157,6 +1179,32 @@ def air_restriction_op(A, cf, strong_threshold_r=0.25, filter_threshold_r=0.0, h
     if info["status"] != 0:
         return None, info
     return _csr_from_caller(nr.value, pia, pja, pa) + ((nr.value, n),), info
+
+
+FSAI_INFO_NAMES = ("status", "max_row", "max_candidates", "overflow_rows", "stop_tolerance", "stop_no_candidate",
+                   "stop_max_steps", "bad_row")
+
+
+def fsai_adaptive_op(B, max_steps=3, max_step_size=5, kap_tolerance=1e-3, table_slots=0, host=False):
+    """FSAI with the adaptive pattern (HYPRE_MI_FSAIAdaptiveOp, fsai_algo_type 4) of a scipy CSR block B (ascending
+    columns), by the device routine or -- host=True, no GPU needed -- the host routine.  table_slots: 0 = the library's
+    LDS table, a small power of two forces rows through the table in global memory (same result).  Returns (G, info):
+    G = (ia int64, ja int32, a f64, shape) exactly as the library stores it.  Raises HypreError with `info` set when a
+    row fails."""
+    n = B.shape[0]
+    bia = np.ascontiguousarray(B.indptr, dtype=np.int64)
+    bja = np.ascontiguousarray(B.indices, dtype=np.int32)
+    ba = np.ascontiguousarray(B.data, dtype=np.float64)
+    out = np.full(8, -2, dtype=np.int32)
+    pia, pja, pa = vp(), vp(), vp()
+    try:
+        call("HYPRE_MI_FSAIAdaptiveOp", int(bool(host)), n, bia, bja, ba, int(max_steps), int(max_step_size),
+             float(kap_tolerance), int(table_slots), C.byref(pia), C.byref(pja), C.byref(pa), out)
+    except HypreError as e:
+        e.info = {k: int(v) for k, v in zip(FSAI_INFO_NAMES, out)}
+        raise
+    info = {k: int(v) for k, v in zip(FSAI_INFO_NAMES, out)}
+    return _csr_from_caller(n, pia, pja, pa) + ((n, n),), info
 
 
 def one_point_interp_op(A, S, cf, host=False):

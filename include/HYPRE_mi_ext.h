@@ -188,6 +188,22 @@ HYPRE_Int HYPRE_MI_AIRRestrictionOp(HYPRE_Int on_host, HYPRE_Int n, const HYPRE_
                                     const HYPRE_Complex *a_a, const HYPRE_Int *cf, HYPRE_Real strong_threshold_r,
                                     HYPRE_Real filter_threshold_r, HYPRE_Int *r_nrows, HYPRE_BigInt **r_ia, HYPRE_Int **r_ja,
                                     HYPRE_Complex **r_a, HYPRE_Int info[8]);
+/* ---- FSAI with the adaptive pattern (fsai_algo_type 4 -- this library's number, not HYPRE's, whose adaptive types 1 and
+ * 2 are host threading schemes and stay refused) on caller (host) arrays: the n x n block B as CSR
+ * with ascending columns.  on_host = 0 runs the device routine, 1 the host routine (which needs no device); both give
+ * the same bits.  table_slots = 0: the library's choice of a row's candidate table in LDS; a small power of two sends
+ * the rows whose candidates do not fit through the table in global memory -- the result never depends on it.  G (n x n,
+ * lower triangular, columns ascending) is malloc'ed: release with HYPRE_MI_Free.  info[0] = 0 built / 2 a row failed
+ * (the call fails and names the row), info[1] = the largest row of G, info[2] = the largest candidate count met,
+ * info[3] = the rows that took the global-memory table (device routine), info[4..6] = the rows stopped by the tolerance
+ * / for want of candidates / by max_steps, info[7] = the first failing row or -1.  Refused: max_steps < 1,
+ * max_step_size < 1, max_steps * max_step_size + 1 > 64, kap_tolerance negative or not finite. */
+HYPRE_Int HYPRE_MI_FSAIAdaptiveOp(HYPRE_Int on_host, HYPRE_Int n, const HYPRE_BigInt *b_ia, const HYPRE_Int *b_ja,
+                                  const HYPRE_Complex *b_a, HYPRE_Int max_steps, HYPRE_Int max_step_size,
+                                  HYPRE_Real kap_tolerance, HYPRE_Int table_slots, HYPRE_BigInt **g_ia, HYPRE_Int **g_ja,
+                                  HYPRE_Complex **g_a, HYPRE_Int info[8]);
+/* the same eight numbers for the G of a HYPRE_FSAI solver that is set up (static pattern: entries 2 ... 6 are 0) */
+HYPRE_Int HYPRE_MI_FSAIGetSetupInfo(HYPRE_Solver solver, HYPRE_Int out[8]);
 /* ---- one-point interpolation (interp_type 100) on caller (host) arrays: A, the pattern of the
  * strength graph S and the marker cf (+1 C, -1 F, -3 special F); on_host as above.  P (n x *p_ncols) is malloc'ed. */
 HYPRE_Int HYPRE_MI_OnePointInterpOp(HYPRE_Int on_host, HYPRE_Int n, const HYPRE_BigInt *a_ia, const HYPRE_Int *a_ja,
@@ -297,6 +313,8 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetGSSweepPaths(HYPRE_Solver solver, HYPRE_Int level
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelFSAISize(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int *nrows, HYPRE_BigInt *nnz);
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelFSAI(HYPRE_Solver solver, HYPRE_Int level, HYPRE_BigInt *ia, HYPRE_Int *ja,
                                          HYPRE_Complex *a, HYPRE_Real *omega);
+/* how that G was built: the info[8] of HYPRE_MI_FSAIAdaptiveOp (static pattern: entries 2 ... 6 are 0) */
+HYPRE_Int HYPRE_MI_BoomerAMGGetLevelFSAIInfo(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int out[8]);
 /* Chebyshev data of a level (relax type 16 in some slot at Setup): out[0 .. 5] = the estimated
  * smallest and largest eigenvalue of D^-1 A, the interval [lower, upper] the polynomial is built for, its centre theta
  * and half width delta.  An error when the level has none. */

@@ -84,9 +84,13 @@ HYPRE_Int HYPRE_BoomerAMGSetILUIterSetupTolerance(HYPRE_Solver solver, HYPRE_Rea
 HYPRE_Int HYPRE_BoomerAMGSetILUTriSolve(HYPRE_Solver solver, HYPRE_Int v);              /* :311 */
 HYPRE_Int HYPRE_BoomerAMGSetILULowerJacobiIters(HYPRE_Solver solver, HYPRE_Int v);      /* :316 */
 HYPRE_Int HYPRE_BoomerAMGSetILUUpperJacobiIters(HYPRE_Solver solver, HYPRE_Int v);      /* :320 */
-/* FSAI smoother (smooth_type 4; names as remembered from HYPRE >= 2.25): only the static pattern, algo type 3, is built
- * -- any other algo type is refused at Setup.  The adaptive-only settings are accepted and warned once (no effect on a
- * static pattern); the local solve type is accepted and has no effect */
+/* FSAI smoother (smooth_type 4; names as remembered from HYPRE >= 2.25): algo type 3, the static pattern (the default),
+ * and algo type 4, the adaptive pattern built on the device, are built.  4 is THIS library's number, not HYPRE's:
+ * HYPRE's adaptive types 1 and 2 are host threading schemes that do not exist here and stay refused at Setup, like every
+ * other value.  MaxSteps (default 3), MaxStepSize (5) and KapTolerance (1e-3) act with type 4 -- refused at Setup:
+ * either below 1, MaxSteps * MaxStepSize + 1 > 64, a tolerance negative or not finite -- and are warned once as having
+ * no effect while the type is 3; NumLevels and Threshold act with type 3 only.  MaxNnzRow and the local solve type are
+ * accepted and have no effect */
 HYPRE_Int HYPRE_BoomerAMGSetFSAIAlgoType(HYPRE_Solver solver, HYPRE_Int v);
 HYPRE_Int HYPRE_BoomerAMGSetFSAILocalSolveType(HYPRE_Solver solver, HYPRE_Int v);
 HYPRE_Int HYPRE_BoomerAMGSetFSAINumLevels(HYPRE_Solver solver, HYPRE_Int v);           /* 1, 2 or 3 */
@@ -100,10 +104,10 @@ HYPRE_Int HYPRE_BoomerAMGSetChebyFraction(HYPRE_Solver solver, HYPRE_Real v);
 HYPRE_Int HYPRE_BoomerAMGSetChebyEigEst(HYPRE_Solver solver, HYPRE_Int v);
 HYPRE_Int HYPRE_BoomerAMGSetChebyVariant(HYPRE_Solver solver, HYPRE_Int v);
 HYPRE_Int HYPRE_BoomerAMGSetChebyScale(HYPRE_Solver solver, HYPRE_Int v);
-HYPRE_Int HYPRE_BoomerAMGSetFSAIMaxSteps(HYPRE_Solver solver, HYPRE_Int v);            /* adaptive only */
-HYPRE_Int HYPRE_BoomerAMGSetFSAIMaxStepSize(HYPRE_Solver solver, HYPRE_Int v);         /* adaptive only */
-HYPRE_Int HYPRE_BoomerAMGSetFSAIMaxNnzRow(HYPRE_Solver solver, HYPRE_Int v);           /* adaptive only */
-HYPRE_Int HYPRE_BoomerAMGSetFSAIKapTolerance(HYPRE_Solver solver, HYPRE_Real v);       /* adaptive only */
+HYPRE_Int HYPRE_BoomerAMGSetFSAIMaxSteps(HYPRE_Solver solver, HYPRE_Int v);            /* algo type 4 */
+HYPRE_Int HYPRE_BoomerAMGSetFSAIMaxStepSize(HYPRE_Solver solver, HYPRE_Int v);         /* algo type 4 */
+HYPRE_Int HYPRE_BoomerAMGSetFSAIMaxNnzRow(HYPRE_Solver solver, HYPRE_Int v);           /* accepted, no effect */
+HYPRE_Int HYPRE_BoomerAMGSetFSAIKapTolerance(HYPRE_Solver solver, HYPRE_Real v);       /* algo type 4 */
 
 /* ---------------------------------------------------------------- ParCSR GMRES
  * src/HypreSystem.cpp:390-404; right-preconditioned restarted GMRES(k), MGS */
@@ -206,7 +210,8 @@ HYPRE_Int HYPRE_ILUSetTriSolve(HYPRE_Solver solver, HYPRE_Int v);               
 HYPRE_Int HYPRE_ILUSetLowerJacobiIters(HYPRE_Solver solver, HYPRE_Int v);
 HYPRE_Int HYPRE_ILUSetUpperJacobiIters(HYPRE_Solver solver, HYPRE_Int v);
 
-/* FSAI (factorized sparse approximate inverse; names as remembered from HYPRE >= 2.25): static pattern (algo type 3) on
+/* FSAI (factorized sparse approximate inverse; names as remembered from HYPRE >= 2.25): static pattern (algo type 3) or
+ * adaptive pattern (algo type 4 -- this library's number, see the BoomerAMG FSAI setters above) on
  * the rank's diagonal block, x += omega G^T G (b - A x) per iteration; omega = 1 / (power-iteration estimate of
  * lambda_max(G A G^T)) unless SetOmega gives one.  Usable as a preconditioner through the Krylov SetPrecond calls
  * (then: MaxIterations 1, Tolerance 0, ZeroGuess 1) */
@@ -224,10 +229,10 @@ HYPRE_Int HYPRE_FSAISetMaxIterations(HYPRE_Solver solver, HYPRE_Int v);
 HYPRE_Int HYPRE_FSAISetTolerance(HYPRE_Solver solver, HYPRE_Real v);
 HYPRE_Int HYPRE_FSAISetZeroGuess(HYPRE_Solver solver, HYPRE_Int v);
 HYPRE_Int HYPRE_FSAISetPrintLevel(HYPRE_Solver solver, HYPRE_Int v);
-HYPRE_Int HYPRE_FSAISetMaxSteps(HYPRE_Solver solver, HYPRE_Int v);       /* adaptive only: accepted, no effect */
-HYPRE_Int HYPRE_FSAISetMaxStepSize(HYPRE_Solver solver, HYPRE_Int v);    /* adaptive only: accepted, no effect */
-HYPRE_Int HYPRE_FSAISetMaxNnzRow(HYPRE_Solver solver, HYPRE_Int v);      /* adaptive only: accepted, no effect */
-HYPRE_Int HYPRE_FSAISetKapTolerance(HYPRE_Solver solver, HYPRE_Real v);  /* adaptive only: accepted, no effect */
+HYPRE_Int HYPRE_FSAISetMaxSteps(HYPRE_Solver solver, HYPRE_Int v);       /* algo type 4 (default 3); no effect with type 3 */
+HYPRE_Int HYPRE_FSAISetMaxStepSize(HYPRE_Solver solver, HYPRE_Int v);    /* algo type 4 (default 5); no effect with type 3 */
+HYPRE_Int HYPRE_FSAISetMaxNnzRow(HYPRE_Solver solver, HYPRE_Int v);      /* accepted, no effect */
+HYPRE_Int HYPRE_FSAISetKapTolerance(HYPRE_Solver solver, HYPRE_Real v);  /* algo type 4 (default 1e-3); no effect with type 3 */
 
 #ifdef __cplusplus
 }

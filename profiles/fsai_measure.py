@@ -4,7 +4,10 @@
              level's down and up sweep) with FSAI on levels 0-1 against the default l1-hybrid-GS (relax_type 8);
   solve   -- GMRES(50) to 1e-8 with BoomerAMG: the default, FSAI on levels 0-1, FSAI on every level (refused when a
              coarse level's pattern exceeds 64 entries in a row): iterations, setup, solve.
-Usage: python profiles/fsai_measure.py [--sizes 256 512] [--skip-solve] [--out results.json]"""
+With --adaptive the same for the adaptive pattern (fsai_algo_type 4) at its defaults -- setup beside the static k = 1,
+the three solves, G's size and the rows that took the table in global memory (HYPRE_MI_FSAIGetSetupInfo /
+HYPRE_MI_BoomerAMGGetLevelFSAIInfo).
+Usage: python profiles/fsai_measure.py [--sizes 256 512] [--skip-solve] [--adaptive] [--out results.json]"""
 import argparse
 import json
 import os
@@ -35,6 +38,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", type=int, nargs="+", default=[256, 512])
     ap.add_argument("--skip-solve", action="store_true")
+    ap.add_argument("--adaptive", action="store_true", help="also measure fsai_algo_type 4 at its defaults")
     ap.add_argument("--out", default=None, help="also write the results as JSON to this file")
     args = ap.parse_args()
     mi = ge.load_binding()
@@ -52,9 +56,23 @@ def main():
                 times.append(time.perf_counter() - t0)
                 fs.destroy()
             rec[f"fsai_setup_s_k{k}"] = times
+        if args.adaptive:
+            times = []
+            for rep in range(2):
+                fs = mi.FSAI(algo_type=4)
+                t0 = time.perf_counter()
+                fs.setup(A)
+                times.append(time.perf_counter() - t0)
+                rec["fsai_adaptive_info"] = fs.setup_info()
+                fs.destroy()
+            rec["fsai_setup_s_adaptive"] = times
         if not args.skip_solve:
-            for name, kw in (("default", {}), ("fsai_levels_0_1", dict(smooth_type=4, smooth_num_levels=2)),
-                             ("fsai_all_levels", dict(smooth_type=4, smooth_num_levels=50))):
+            configs = [("default", {}), ("fsai_levels_0_1", dict(smooth_type=4, smooth_num_levels=2)),
+                       ("fsai_all_levels", dict(smooth_type=4, smooth_num_levels=50))]
+            if args.adaptive:
+                configs += [("adaptive_levels_0_1", dict(smooth_type=4, smooth_num_levels=2, fsai_algo_type=4)),
+                            ("adaptive_all_levels", dict(smooth_type=4, smooth_num_levels=50, fsai_algo_type=4))]
+            for name, kw in configs:
                 amg = mi.BoomerAMG(print_level=0, **kw)
                 try:
                     gm, ts, tsol = gmres(mi, A, b, x, amg)
@@ -64,6 +82,9 @@ def main():
                     amg.destroy()
                     continue
                 r = dict(iterations=gm.num_iterations, setup_s=ts, solve_s=tsol, rel_res=gm.final_rel_res)
+                if kw.get("fsai_algo_type") == 4:
+                    r["level_fsai_info"] = [amg.level_fsai_info(lev)
+                                            for lev in range(min(kw["smooth_num_levels"], amg.num_levels - 1))]
                 for lev in (0, 1):
                     mi.profile_enable(20 + lev, 1 << 16)
                 mi.profile_reset()
