@@ -669,6 +669,7 @@ void BoomerAMG::solve(ParCSR &A, ParVector &b, ParVector &x) {
         k::gather(xc, L0.d_perm.p, L0.u.p, n, s);
       else
         k::copy(xc, L0.u.p, n, s);
+      if (ctx().krylov_precond_depth > 0) ctx().n_precond_cycles++;  // HYPRE_MI_GetCounter "precond_cycles"
       cycle(0, zero);
       if (permuted)
         k::scatter_set(xc, L0.d_perm.p, L0.u.p, n, s);

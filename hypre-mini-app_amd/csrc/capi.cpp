@@ -2005,6 +2005,10 @@ HYPRE_Int HYPRE_MI_GetCounter(const char *name, long long *value) {
     *value = ctx().n_allgather;
   else if (n == "value_storage_row_mapped")
     *value = ctx().n_value_row_mapped;
+  else if (n == "precond_cycles")
+    *value = ctx().n_precond_cycles;
+  else if (n == "gmres_direction_vectors")
+    *value = ctx().n_gmres_z_allocated;
   else if (setup_reuse_counter(n.c_str()) >= 0)
     *value = setup_reuse_counter(n.c_str());
   else if (dist_setup_counter(n.c_str()) >= 0)
@@ -2209,6 +2213,16 @@ HYPRE_Int HYPRE_MI_ArenaSelfTest(HYPRE_Int seed, HYPRE_Int rounds, HYPRE_BigInt 
 HYPRE_Int HYPRE_MI_SetValueDictionary(HYPRE_Int on) {
   API_BEGIN
   k::set_value_dictionary(on != 0);
+  API_END
+}
+HYPRE_Int HYPRE_MI_SetGmresKeepDirections(HYPRE_Int on) {
+  API_BEGIN
+  gmres_keep_directions() = on != 0;
+  API_END
+}
+HYPRE_Int HYPRE_MI_TestGmresDirectionAllocFailsAt(HYPRE_Int at) {
+  API_BEGIN
+  gmres_keep_fail_at() = at < 0 ? -1 : (int)at;
   API_END
 }
 HYPRE_Int HYPRE_MI_GetGSChunk(HYPRE_Int *rows) {

@@ -25,11 +25,31 @@ void KrylovSolver::run_precond_setup(ParCSR &A, ParVector &b, ParVector &x) {
 }
 
 
+namespace {
+// BoomerAMG cycles started while one of these lives are counted as "precond_cycles" (HYPRE_MI_GetCounter)
+struct PrecondScope {
+  PrecondScope() { ctx().krylov_precond_depth++; }
+  ~PrecondScope() { ctx().krylov_precond_depth--; }
+};
+}  // namespace
+
+// MI_HYPRE_GMRES_KEEP_DIRECTIONS=0 / HYPRE_MI_SetGmresKeepDirections(0): GMRES and COGMRES recompute the solution
+// update with one more preconditioner cycle, as gmres.c does (see GmresSolver::solve)
+bool &gmres_keep_directions() {
+  static bool on = !(getenv("MI_HYPRE_GMRES_KEEP_DIRECTIONS") && atoi(getenv("MI_HYPRE_GMRES_KEEP_DIRECTIONS")) == 0);
+  return on;
+}
+int &gmres_keep_fail_at() {
+  static int at = -1;
+  return at;
+}
+
 void KrylovSolver::apply_precond(ParCSR &A, ParVector &rhs, ParVector &out) {
   hipStream_t s = ctx().stream;
   if (precond_solve) {
     k::fill(out.all(), out.len(), 0.0, s);
     zero_guess_hint() = true;
+    PrecondScope scope;
     precond_solve(precond_data, &A, &rhs, &out);
     zero_guess_hint() = false;
   } else {
@@ -117,6 +137,7 @@ const double *KrylovSolver::precond_in_order(BoomerAMG *amg, ParCSR &A, ParVecto
     const size_t o = (size_t)c * (size_t)n;
     L0.f.p = rhs.all() + o;  // read-only inside the cycle
     if (!amg->zero_cycle_ignores_u(0)) k::fill(L0.u.p, n, 0.0, s);
+    ctx().n_precond_cycles++;
     try {
       amg->cycle(0, true);
     } catch (...) {
@@ -172,8 +193,32 @@ int GmresSolver::solve(ParCSR &A_in, ParVector &b_in, ParVector &x_in) {
       std::unique_ptr<ParVector> v(new ParVector());
       v->init(b_in.start, b_in.end, nc);
       z.push_back(std::move(v));
+      c.n_gmres_z_allocated++;
     }
     return *z[(size_t)i];
+  };
+  // the same for the kept directions below: a vector the device has no room for is no error there.  N > 1: the ranks
+  // agree on every new vector (one host all-reduce per allocation, none once the vectors exist) -- a rank that went back
+  // to the recomputed update alone would run a cycle, a collective, that the others skip -- and a rank that had room
+  // gives its vector back, so that every rank holds the same number of them in the next solve
+  auto try_zvec = [&](int i) -> ParVector * {
+    if ((int)z.size() > i) return z[(size_t)i].get();
+    int ok = !(gmres_keep_fail_at() >= 0 && i >= gmres_keep_fail_at());  // (test hook)
+    if (ok) {
+      try {
+        zvec(i);
+      } catch (const Error &e) {
+        if (e.code != 2) throw;  // 2: dev_alloc found no memory
+        ok = 0;
+      }
+    }
+    if (comm.size > 1) {
+      int all = ok;
+      comm.allreduce_host(&all, 1, CommDType::I32, CommOp::MIN);
+      if (ok && !all) z.pop_back();
+      ok = all;
+    }
+    return ok ? z[(size_t)i].get() : nullptr;
   };
   std::vector<double> cs((size_t)kd + 1, 0.0), sn((size_t)kd + 1, 0.0), rs((size_t)kd + 1, 0.0);
   std::vector<std::vector<double>> hh((size_t)kd + 1, std::vector<double>((size_t)kd, 0.0));
@@ -189,6 +234,24 @@ int GmresSolver::solve(ParCSR &A_in, ParVector &b_in, ParVector &x_in) {
   auto precond = [&](ParVector &rhs, ParVector &out, bool need_copy) -> const double * {
     return precond_in_order(amg, A, rhs, out, need_copy);
   };
+  // Kept directions.  In level order M^-1 is one BoomerAMG cycle from a zero guess, a fixed linear map, so the update
+  // x += M^-1 sum_j y_j p_j of gmres.c equals x += sum_j y_j z_j with the z_j = M^-1 p_j every Arnoldi step has computed
+  // already: GMRES and COGMRES keep them, as FlexGMRES does, and the cycle of the update goes (same Krylov space, same
+  // Hessenberg matrix, same y; x differs in rounding).  One component: z_j ADOPTS the level-0 solution buffer of the
+  // cycle -- the storage pointers of L[0].u and z_j are swapped, no copy; the next cycle starts from a zero guess and
+  // either ignores u or fills it, so what the buffer handed back holds does not matter, and nothing keeps L[0].u.p
+  // across cycles.  Copied instead: the components of a multivector (one cycle each, into z_j + o) and a z_j whose
+  // allocation does not have the size of L[0].u.  A z_j the device has no room for ends the keeping for this solve:
+  // the restart cycle under way finishes with the recomputed update.
+  // N > 1: all ranks or none.  amg_in_level_order() decides per rank (a rank without rows has no level ordering), and
+  // a rank that recomputed its update alone would run one cycle more than the others
+  bool keep = amg && !flexible && gmres_keep_directions();
+  if (comm.size > 1 && !flexible && gmres_keep_directions() &&
+      precond_solve == reinterpret_cast<ParSolverFcn>(&HYPRE_BoomerAMGSolve)) {
+    int all = keep ? 1 : 0;
+    comm.allreduce_host(&all, 1, CommDType::I32, CommOp::MIN);
+    keep = all != 0;
+  }
 
   auto mv = [&](double alpha, const double *xv, double beta, const double *bv, double *yv) {
     matvec_all(A, alpha, xv, beta, bv, yv, nloc, nc, k::PROF_SPMV_L0);
@@ -259,17 +322,22 @@ int GmresSolver::solve(ParCSR &A_in, ParVector &b_in, ParVector &x_in) {
     }
     k::scale(1.0 / r_norm, basis(0).data(), n, s);
     int i = 0;
+    bool kept = keep;  // every z_j of this restart cycle so far is in zvec(j)
     while (i < kd && iter < max_iter) {
       i++;
       iter++;
       ParVector &pi = basis(i);
       ParVector &pim1 = basis(i - 1);
-      ParVector &dir = flexible ? zvec(i - 1) : r;  // M^-1 p_{i-1}
+      ParVector *zk = kept ? try_zvec(i - 1) : nullptr;
+      if (kept && !zk) keep = kept = false;
+      const bool adopt = zk && nc == 1 && amg->L[0].u.n == zk->d.n;
+      ParVector &dir = flexible ? zvec(i - 1) : (zk ? *zk : r);  // M^-1 p_{i-1}
       const double *mp;
       {
         TraceRange tr("precond (BoomerAMG cycle)");
-        mp = precond(pim1, dir, flexible);
+        mp = precond(pim1, dir, flexible || (zk && !adopt));
       }
+      if (adopt) std::swap(amg->L[0].u.p, zk->d.p);  // mp is z_{i-1} now
       mv(1.0, mp, 0.0, nullptr, pi.data());
       TraceRange trace_ortho("Gram-Schmidt + Givens");
       if (ortho == 0) {
@@ -346,6 +414,16 @@ int GmresSolver::solve(ParCSR &A_in, ParVector &b_in, ParVector &x_in) {
     if (flexible) {
       // x += sum_j y_j z_j
       for (int j = i - 1; j >= 0; j--) k::axpy(y[(size_t)j], zvec(j).data(), x.all(), n, s);
+    } else if (kept) {
+      // the same sum in the same order from the kept directions, in one or a few passes (k::lin_comb without init is
+      // the axpy chain bit for bit)
+      std::vector<const double *> vp((size_t)i);
+      std::vector<double> cf((size_t)i);
+      for (int j = i - 1, q = 0; j >= 0; j--, q++) {
+        vp[(size_t)q] = zvec(j).data();
+        cf[(size_t)q] = y[(size_t)j];
+      }
+      k::lin_comb(vp.data(), cf.data(), i, false, x.all(), n, s);
     } else {
       // w = sum_j y_j p_j ; x += M^-1 w   (y_{i-1} p_{i-1} first, then the others in descending j, as gmres.c's
       // copy / scale / axpy chain does -- in one or a few passes over the basis instead of i)

@@ -358,6 +358,10 @@ struct Ctx {
   // exchange groups (one per halo update), all-gathers (coarsest / redundant levels)
   long long n_allreduce = 0, n_halo_exchange = 0, n_allgather = 0;
   long long n_value_row_mapped = 0;  // row-mapped restriction operators that took fp32-rounded values (tests)
+  // BoomerAMG cycles a Krylov solver asked for as its preconditioner (cycle(0, ..) while krylov_precond_depth > 0), and
+  // the vectors GMRES allocated to keep its preconditioned directions (krylov.cpp, "kept directions")
+  long long n_precond_cycles = 0, n_gmres_z_allocated = 0;
+  int krylov_precond_depth = 0;
 };
 Ctx &ctx();
 void ensure_init();

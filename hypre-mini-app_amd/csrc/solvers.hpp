@@ -46,6 +46,11 @@ struct KrylovSolver : SolverBase {
   const double *precond_in_order(BoomerAMG *amg, ParCSR &A, ParVector &rhs, ParVector &out, bool need_copy);
 };
 
+// GMRES / COGMRES behind a level-ordered BoomerAMG keep z_j = M^-1 p_j and update x from them (krylov.cpp; the
+// switch, and a test hook: the allocation of kept vector number `at` and beyond counts as failed, -1 = never)
+bool &gmres_keep_directions();
+int &gmres_keep_fail_at();
+
 struct GmresSolver : KrylovSolver {
   std::vector<std::unique_ptr<ParVector>> p;
   // FlexGMRES (krylov/flexgmres.c): the preconditioned directions z_j = M^-1 p_j are kept and the
@@ -55,6 +60,8 @@ struct GmresSolver : KrylovSolver {
   // two passes, every pass one block of inner products (ONE all-reduce) and one block update (COGMRES,
   // krylov/cogmres.c; src/HypreSystem.cpp:372-388)
   int ortho = 0;
+  // also the kept directions of GMRES / COGMRES in level order; those of one component own what was a level-0
+  // solution buffer of the preconditioner (same size, swapped in after the cycle)
   std::vector<std::unique_ptr<ParVector>> z;
   ParVector r, w;
   GmresSolver() : KrylovSolver(K_GMRES) {}

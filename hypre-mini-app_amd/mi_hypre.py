@@ -859,6 +859,12 @@ def set_value_dictionary(on):
     call("HYPRE_MI_SetValueDictionary", 1 if on else 0)
 
 
+def set_gmres_keep_directions(on):
+    """GMRES / COGMRES behind BoomerAMG update x from the kept directions z_j (on, the default) or apply the
+    preconditioner once more, as gmres.c does (off); process-wide, for the solves started afterwards"""
+    call("HYPRE_MI_SetGmresKeepDirections", 1 if on else 0)
+
+
 def parcsr_value_kind(A):
     """0: the device diag block streams plain fp64 values, 8: through a value dictionary"""
     par = A.par if hasattr(A, "par") else A

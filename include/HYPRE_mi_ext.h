@@ -117,6 +117,17 @@ HYPRE_Int HYPRE_MI_ArenaSelfTest(HYPRE_Int seed, HYPRE_Int rounds, HYPRE_BigInt 
  * general (variable-coefficient) operator gets anyway; applies to hierarchies set up afterwards (env
  * MI_HYPRE_VALUE_DICT).  bench.py uses it to report the general-operator roofline beside the headline. */
 HYPRE_Int HYPRE_MI_SetValueDictionary(HYPRE_Int on);
+/* GMRES and COGMRES preconditioned by this library's BoomerAMG (one cycle, zero tolerance, the matrix of its Setup) keep
+ * the preconditioned directions z_j = M^-1 p_j of the Arnoldi steps and update x += sum_j y_j z_j, where gmres.c applies
+ * the preconditioner once more to sum_j y_j p_j: the cycle is a fixed linear map, so the two are the same update with
+ * other rounding, and a solve of m iterations runs m cycles instead of m + 1 per restart cycle.  Cost: one more vector
+ * per basis vector in use, allocated step by step; without room for one the solve goes on with the recomputed update.
+ * on = 0 restores the recomputed update (env MI_HYPRE_GMRES_KEEP_DIRECTIONS=0); applies to solves started afterwards.
+ * N > 1 ranks: set it alike on every rank (the ranks agree per solve on whether all of them can keep). */
+HYPRE_Int HYPRE_MI_SetGmresKeepDirections(HYPRE_Int on);
+/* test hook: the allocation of the kept direction number `at` (from 0) and of every later one counts as failed in the
+ * solves started afterwards; at < 0 = off */
+HYPRE_Int HYPRE_MI_TestGmresDirectionAllocFailsAt(HYPRE_Int at);
 /* Counters of the multi-rank choreography since the library was loaded: "matvec_overlapped" (SpMVs whose
  * neighbour exchange ran beside the diag-block product), "gs_overlapped" / "gs_in_order" (relaxation passes that
  * swept their halo-free rows while the halo travelled / that waited for it first); collectives of the solve phase
@@ -130,7 +141,10 @@ HYPRE_Int HYPRE_MI_SetValueDictionary(HYPRE_Int on);
  * were assembled there; MI_HYPRE_DEVICE_ASSEMBLY=0 turns the path off), "ij_entries_fetched_to_host" (entries of matrix
  * batches and vector indices copied device -> host: zero for a device assembly), "ij_host_mirror_bytes" (host mirrors
  * downloaded by device assemblies), "ij_device_sort_lds_capacity" (rows with more entries are sorted by the any-length
- * path), "ij_last_kernels_us" / "ij_last_mirror_us" / "ij_last_format_us" (phases of the last device assembly). */
+ * path), "ij_last_kernels_us" / "ij_last_mirror_us" / "ij_last_format_us" (phases of the last device assembly).
+ * Krylov solvers: "precond_cycles" (BoomerAMG cycles run as a Krylov solver's preconditioner, one per component of a
+ * multivector), "gmres_direction_vectors" (vectors allocated for the directions z_j of FlexGMRES and of
+ * HYPRE_MI_SetGmresKeepDirections). */
 HYPRE_Int HYPRE_MI_GetCounter(const char *name, long long *value);
 /* One rank's block keeps 32-bit local row ids in the solve format; the entry offsets of its diagonal block are 64-bit
  * (the reference's 27-point operator at 512^3 -- 3.6e9 entries, /root/reference/src/laplace_3d_weak_scaling.hpp:558,600
