@@ -46,6 +46,7 @@ struct AmgParams {
   // iterative ILU(0) setup of the ILU smoothers (IluSolver::iter_*; 0 = the exact factorisation)
   int ilu_iter_type = 0, ilu_iter_option = 0, ilu_iter_max_iter = 100;
   double ilu_iter_tol = 1e-3;
+  int ilu_reordering = 0;  // IluSolver::reordering of the ILU smoothers: 2 = multicolour ordering, otherwise none
   // smooth_type 4 = FSAI, one step per sweep: algo type 3 = static pattern (num_levels, threshold), 4 = adaptive pattern
   // on the device (max_steps, max_step_size, kap_tolerance; this library's number)
   int fsai_algo_type = 3, fsai_num_levels = 1, fsai_eig_max_iters = 5;

@@ -3121,6 +3121,7 @@ void BoomerAMG::build_smoothers() {
     ilu->iter_option = p.ilu_iter_option;
     ilu->iter_max_iter = p.ilu_iter_max_iter;
     ilu->iter_tol = p.ilu_iter_tol;
+    ilu->reordering = p.ilu_reordering;
     ilu->print_level = (p.print_level > 0 && comm.rank == 0) ? 1 : 0;
     ilu->setup(*Lv.A, comm);
     Lv.smoother = std::move(ilu);

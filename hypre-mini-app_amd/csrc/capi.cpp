@@ -1372,7 +1372,8 @@ AMG_SET(SmoothType, HYPRE_Int, p.smooth_type = v)  /* acts through smooth_num_le
 AMG_SET(SmoothNumLevels, HYPRE_Int, p.smooth_num_levels = v)
 AMG_SET(ILUType, HYPRE_Int, p.ilu_type = v)
 AMG_SET(ILULevel, HYPRE_Int, p.ilu_level = v)
-AMG_SET(ILULocalReordering, HYPRE_Int, if (v != 0) warn_ignored("ilu_reordering_type", v))
+/* 2 = multicolour ordering (this library's number); HYPRE's 1 = RCM and anything else is ignored */
+AMG_SET(ILULocalReordering, HYPRE_Int, if (v != 0 && v != 2) warn_ignored("ilu_reordering_type", v); p.ilu_reordering = v)
 AMG_SET(ILUMaxRowNnz, HYPRE_Int, warn_ignored("ilu_max_row_nnz", v))
 AMG_SET(ILUMaxIter, HYPRE_Int, if (v < 1) fail(HYPRE_ERROR_ARG, "ilu_max_iter < 1"); p.ilu_max_iter = v)
 AMG_SET(ILUDroptol, HYPRE_Real, if (v != 0.0) warn_ignored("ilu_droptol", v))
@@ -1648,7 +1649,7 @@ HYPRE_Int HYPRE_ILUGetFinalRelativeResidualNorm(HYPRE_Solver solver, HYPRE_Real 
 ILU_SET(Type, HYPRE_Int, o->ilu_type = v)
 ILU_SET(MaxIter, HYPRE_Int, o->max_iter = v)
 ILU_SET(Tol, HYPRE_Real, o->tol = v)
-ILU_SET(LocalReordering, HYPRE_Int, (void)v)
+ILU_SET(LocalReordering, HYPRE_Int, o->reordering = v)  /* 2 = multicolour ordering; every other value: none */
 ILU_SET(PrintLevel, HYPRE_Int, o->print_level = v)
 ILU_SET(LevelOfFill, HYPRE_Int, o->level_of_fill = v)
 ILU_SET(MaxNnzPerRow, HYPRE_Int, (void)v)        /* ILUT only */
@@ -1703,6 +1704,21 @@ HYPRE_Int HYPRE_MI_ILUGetFactors(HYPRE_Solver solver, HYPRE_BigInt *ia, HYPRE_In
     for (int i = 0; i <= h.nrows; i++) ia[i] = h.ia.empty() ? 0 : h.ia[(size_t)i];
   if (ja && !h.ja.empty()) memcpy(ja, h.ja.data(), h.ja.size() * sizeof(int));
   if (a && !h.a.empty()) memcpy(a, h.a.data(), h.a.size() * sizeof(double));
+  API_END
+}
+// info[5]: the reordering in force (0 or 2), colours, colouring rounds, lower and upper level sets; perm / colour: n
+// entries each, left untouched without the ordering
+static void ilu_ordering_out(IluSolver *o, HYPRE_Int *info, HYPRE_Int *perm, HYPRE_Int *colour) {
+  if (!o->is_setup) fail(HYPRE_ERROR_GENERIC, "ILUGetOrdering: the ILU is not set up");
+  if (info)
+    for (int q = 0; q < 5; q++) info[q] = o->ordering_info[q];
+  if (o->ordering_info[0] != 2 || o->n == 0) return;
+  if (perm) memcpy(perm, o->perm_h.data(), (size_t)o->n * sizeof(int));
+  if (colour) o->colour.download(colour, (size_t)o->n);
+}
+HYPRE_Int HYPRE_MI_ILUGetOrdering(HYPRE_Solver solver, HYPRE_Int info[5], HYPRE_Int *perm, HYPRE_Int *colour) {
+  API_BEGIN
+  ilu_ordering_out(ILU(solver), info, perm, colour);
   API_END
 }
 
@@ -2602,6 +2618,16 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetLevelFSAIInfo(HYPRE_Solver solver, HYPRE_Int leve
   if (!fs) fail(HYPRE_ERROR_ARG, "GetLevelFSAIInfo: the level has no FSAI smoother");
   if (!out) fail(HYPRE_ERROR_ARG, "GetLevelFSAIInfo: no buffer");
   for (int q = 0; q < 8; q++) out[q] = fs->setup_info[q];
+  API_END
+}
+HYPRE_Int HYPRE_MI_BoomerAMGGetLevelILUOrdering(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int info[5], HYPRE_Int *perm,
+                                                HYPRE_Int *colour) {
+  API_BEGIN
+  AmgSolver *a = AMG(solver);
+  if (!a->amg.is_setup) fail(HYPRE_ERROR_GENERIC, "GetLevelILUOrdering: AMG is not set up");
+  IluSolver *ilu = level_ilu(level_ref(a, level));
+  if (!ilu) fail(HYPRE_ERROR_ARG, "GetLevelILUOrdering: the level has no ILU smoother");
+  ilu_ordering_out(ilu, info, perm, colour);
   API_END
 }
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCheby(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Real *out) {

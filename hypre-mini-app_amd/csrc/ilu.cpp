@@ -71,7 +71,66 @@ void ilu_symbolic(const HostCSR &B, int fill, HostCSR &F) {
     F.ia[(size_t)i + 1] = (int64_t)F.ja.size();
   }
 }
+
+// B = P D P^T for perm[q] = the row of D that becomes row q of B (inv its inverse), columns ascending in every row
+void permute_block(const HostCSR &D, const std::vector<int> &perm, const std::vector<int> &inv, HostCSR &B) {
+  const int n = D.nrows;
+  B.nrows = n;
+  B.ncols = D.ncols;
+  B.ia.assign((size_t)n + 1, 0);
+  B.ja.resize((size_t)D.nnz());
+  B.a.resize((size_t)D.nnz());
+  std::vector<std::pair<int, double>> row;
+  for (int q = 0; q < n; q++) {
+    const int i = perm[(size_t)q];
+    row.clear();
+    for (int64_t k = D.ia[(size_t)i]; k < D.ia[(size_t)i + 1]; k++)
+      row.emplace_back(inv[(size_t)D.ja[(size_t)k]], D.a[(size_t)k]);
+    std::sort(row.begin(), row.end(), [](const std::pair<int, double> &x, const std::pair<int, double> &y) {
+      return x.first < y.first;
+    });
+    int64_t o = B.ia[(size_t)q];
+    for (const auto &e : row) B.ja[(size_t)o] = e.first, B.a[(size_t)o] = e.second, o++;
+    B.ia[(size_t)q + 1] = o;
+  }
+}
 }  // namespace
+
+// Multicolour ordering of the block D: the colouring runs on the device; the colours come back
+// once, perm lists the rows by (colour, original index), and the host mirror is permuted for the serial passes of the
+// setup (symbolic ILU(k), level sets) that follow.
+void IluSolver::multicolour_order(const HostCSR &D, HostCSR &B) {
+  hipStream_t s = ctx().stream;
+  const int nr = D.nrows;
+  int rounds = 0;
+  {
+    sk::DCsr Dd;
+    Dd.upload(D, s);
+    // Thrown before the setup's failure all-reduce, which the other ranks would then wait in: every round colours at
+    // least the first uncoloured row in priority order, so no input reaches this -- it guards the loop against a defect
+    // of the kernel, not against data, and is therefore not an outcome the ranks agree on.
+    if (sk::ilu_multicolour(Dd, colour, rounds, s) != 0)
+      fail(1, "HYPRE_ILUSetup: the multicolour ordering left rows uncoloured after " + std::to_string(nr) +
+                  " rounds, one per row");
+  }
+  const std::vector<int> col = colour.to_host();
+  int ncol = 0;
+  for (int c : col) ncol = std::max(ncol, c + 1);
+  std::vector<int> start((size_t)ncol + 1, 0), inv((size_t)nr);
+  for (int c : col) start[(size_t)c + 1]++;
+  for (int c = 0; c < ncol; c++) start[(size_t)c + 1] += start[(size_t)c];
+  perm_h.resize((size_t)nr);
+  for (int i = 0; i < nr; i++) {  // ascending i inside a colour
+    const int q = start[(size_t)col[(size_t)i]]++;
+    perm_h[(size_t)q] = i;
+    inv[(size_t)i] = q;
+  }
+  perm.upload(perm_h);
+  permute_block(D, perm_h, inv, B);
+  ordering_info[0] = 2;
+  ordering_info[1] = ncol;
+  ordering_info[2] = rounds;
+}
 
 void IluSolver::setup(ParCSR &A, Comm &comm) {
   ensure_init();
@@ -92,9 +151,18 @@ void IluSolver::setup(ParCSR &A, Comm &comm) {
   }
   MI_REQUIRE(!A.host_diag_stale, "HYPRE_ILUSetup: the matrix has no host arrays");
   is_setup = false;
-  HostCSR filled;
-  if (level_of_fill > 0) ilu_symbolic(A.diag, level_of_fill, filled);  // the factors live on the ILU(k) pattern
-  const HostCSR &D = level_of_fill > 0 ? filled : A.diag;
+  for (int &v : ordering_info) v = 0;
+  perm.release();
+  colour.release();
+  xp.release();
+  perm_h.clear();
+  HostCSR reordered, filled;
+  if (reordering == 2) multicolour_order(A.diag, reordered);  // before the symbolic pass: the fill is that of B
+  const HostCSR &B = reordering == 2 ? reordered : A.diag;
+  if (level_of_fill > 0) ilu_symbolic(B, level_of_fill, filled);  // the factors live on the ILU(k) pattern
+  const HostCSR &D = level_of_fill > 0 ? filled : B;
+  // a refusal names the row in the caller's numbering
+  auto caller_row = [&](long long row) { return perm_h.empty() ? row : (long long)perm_h[(size_t)row]; };
   n = D.nrows;
   // the Jacobi triangular solves of an iteratively built factor need no level set: no serial pass over the block
   levels_built = iter_type == 0 || tri_solve != 0;
@@ -154,6 +222,7 @@ void IluSolver::setup(ParCSR &A, Comm &comm) {
       MI_HIP(hipGetLastError());
       bad_row = sk::ilu_zero_pivot(LU, dpos.p, s);
     }
+    if (bad_row >= 0) bad_row = caller_row(bad_row);
     double err = bad_row >= 0 ? 1.0 : 0.0;
     comm.allreduce_host(&err, 1, CommDType::F64, CommOp::MAX);
     if (bad_row >= 0)
@@ -170,10 +239,15 @@ void IluSolver::setup(ParCSR &A, Comm &comm) {
   t.alloc((size_t)n);
   r.alloc((size_t)n);
   z.alloc((size_t)n);
+  if (reordering == 2) xp.alloc((size_t)n);
+  ordering_info[3] = nl;
+  ordering_info[4] = nu;
   zero_on_stream(y.p, (size_t)n * sizeof(double));
   zero_on_stream(t.p, (size_t)n * sizeof(double));
   MI_HIP(hipStreamSynchronize(s));
   is_setup = true;
+  if (print_level > 0 && comm.rank == 0 && reordering == 2)
+    printf("mi_hypre ILU multicolour ordering: %d colours in %d rounds\n", ordering_info[1], ordering_info[2]);
   if (print_level > 0 && comm.rank == 0 && levels_built)
     printf("mi_hypre ILU(%d): %d rows, %lld entries, %d lower / %d upper level sets, %s triangular solves\n", level_of_fill, n,
            (long long)LU.nnz, nl, nu, tri_solve ? "exact" : "Jacobi");
@@ -269,6 +343,7 @@ void IluSolver::iterative_factor(Comm &comm, long long row0) {
   }
   double v[4] = {(double)err, (double)iter_sweeps, iter_correction, iter_residual};
   comm.allreduce_host(v, 4, CommDType::F64, CommOp::MAX);
+  if (err == 1 && !perm_h.empty()) bad_row = perm_h[(size_t)bad_row];  // the caller's row
   if (err == 1)
     fail(1, "HYPRE_ILUSetup: iterative ILU(0) setup: zero pivot u_jj in row " + std::to_string(bad_row) +
                 " of this rank's block (global row " + std::to_string(row0 + bad_row) + ")");
@@ -285,29 +360,34 @@ void IluSolver::apply(const double *rhs, double *out) {
   hipStream_t s = ctx().stream;
   MI_REQUIRE(!tri_solve || levels_built,
              "HYPRE_ILUSolve: exact triangular solves need the level sets, which a setup with trisolve 0 did not build");
+  // reordering 2: LU holds the factors of B = P D P^T.  The lower substitution gathers rhs through perm, the upper one
+  // leaves its result in B's numbering (xp), and one pass scatters it into out.
+  const int *pm = perm.p;  // null without the ordering
+  double *const res = pm ? xp.p : out;
   if (tri_solve) {
     const int nl = (int)lptr.size() - 1, nu = (int)uptr.size() - 1;
     for (int l = 0; l < nl; l++)
-      sk::ilu_lower_level(LU, dpos.p, order_l.p + lptr[(size_t)l], lptr[(size_t)l + 1] - lptr[(size_t)l], rhs, y.p, s);
+      sk::ilu_lower_level(LU, dpos.p, order_l.p + lptr[(size_t)l], lptr[(size_t)l + 1] - lptr[(size_t)l], pm, rhs, y.p, s);
     for (int l = 0; l < nu; l++)
-      sk::ilu_upper_level(LU, dpos.p, order_u.p + uptr[(size_t)l], uptr[(size_t)l + 1] - uptr[(size_t)l], y.p, out, s);
+      sk::ilu_upper_level(LU, dpos.p, order_u.p + uptr[(size_t)l], uptr[(size_t)l + 1] - uptr[(size_t)l], y.p, res, s);
   } else {
     // y <- rhs - L_strict y (lower_it times from y = rhs); out <- D^-1 (y - U_strict out) (upper_it times from D^-1 y)
     double *a = y.p, *b2 = t.p;
-    sk::ilu_lower_jacobi(LU, dpos.p, rhs, nullptr, a, s);
+    sk::ilu_lower_jacobi(LU, dpos.p, pm, rhs, nullptr, a, s);
     for (int it = 0; it < lower_it; it++) {
-      sk::ilu_lower_jacobi(LU, dpos.p, rhs, a, b2, s);
+      sk::ilu_lower_jacobi(LU, dpos.p, pm, rhs, a, b2, s);
       std::swap(a, b2);
     }
-    // a holds y; use b2 and out alternately, finishing in out
-    double *zi = (upper_it % 2 == 0) ? out : b2, *zo = (upper_it % 2 == 0) ? b2 : out;
+    // a holds y; use b2 and res alternately, finishing in res
+    double *zi = (upper_it % 2 == 0) ? res : b2, *zo = (upper_it % 2 == 0) ? b2 : res;
     sk::ilu_upper_jacobi(LU, dpos.p, a, nullptr, zi, s);
     for (int it = 0; it < upper_it; it++) {
       sk::ilu_upper_jacobi(LU, dpos.p, a, zi, zo, s);
       std::swap(zi, zo);
     }
-    if (zi != out) k::copy(zi, out, n, s);
+    if (zi != res) k::copy(zi, res, n, s);
   }
+  if (pm) sk::ilu_unpermute(pm, xp.p, out, n, s);
   MI_HIP(hipGetLastError());
 }
 

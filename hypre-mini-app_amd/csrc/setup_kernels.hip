@@ -1529,6 +1529,85 @@ __global__ __launch_bounds__(BLK) void ilu_dpos_k(int n, const long long *__rest
   dpos[i] = d;
 }
 
+// ---- multicolour ordering (local_reordering 2)
+// priority of row i: the MurmurHash3 32-bit finaliser of i + 1; j comes before i when its weight is larger, the smaller
+// index first among equal weights
+__device__ __forceinline__ unsigned ilu_colour_weight(int i) {
+  unsigned h = (unsigned)i + 1u;
+  h ^= h >> 16;
+  h *= 0x85ebca6bu;
+  h ^= h >> 13;
+  h *= 0xc2b2ae35u;
+  h ^= h >> 16;
+  return h;
+}
+__device__ __forceinline__ bool ilu_colour_precedes(int j, int i) {
+  const unsigned wj = ilu_colour_weight(j), wi = ilu_colour_weight(i);
+  return wj > wi || (wj == wi && j < i);
+}
+
+// One Jones-Plassmann round on the graph of D + D^T (row i of D and row i of T = D^T, diagonal skipped; an edge stored
+// in both is simply seen twice), G lanes per row.  cin holds the colours of the earlier rounds (-1: none yet) and is
+// only read; cout receives every row's colour after this round, so the result does not depend on scheduling.  An
+// uncoloured row none of whose uncoloured neighbours comes before it takes the smallest colour no coloured neighbour
+// holds: 64 colours per scan of the neighbours, the next window of 64 when all of a window are taken.  left: rows still
+// uncoloured after the round (one atomic per block).  Every thread reaches every shuffle and the barrier.
+template <int G>
+__global__ __launch_bounds__(BLK) void ilu_colour_round_k(int n, const long long *__restrict__ ia,
+                                                          const int *__restrict__ ja, const long long *__restrict__ tia,
+                                                          const int *__restrict__ tja, const int *__restrict__ cin,
+                                                          int *__restrict__ cout, int *__restrict__ left) {
+  const long long i = (bid() * BLK + threadIdx.x) / G;
+  const int sub = threadIdx.x % G;
+  const bool live = i < n;
+  const int mine = live ? cin[i] : 0;
+  const bool open = live && mine < 0;
+  const long long k0 = open ? ia[i] : 0, k1 = open ? ia[i + 1] : 0, t0 = open ? tia[i] : 0, t1 = open ? tia[i + 1] : 0;
+  int blocked = 0;
+  for (long long k = k0 + sub; k < k1; k += G) {
+    const int j = ja[k];
+    if (j != i && cin[j] < 0 && ilu_colour_precedes(j, (int)i)) blocked = 1;
+  }
+  for (long long k = t0 + sub; k < t1; k += G) {
+    const int j = tja[k];
+    if (j != i && cin[j] < 0 && ilu_colour_precedes(j, (int)i)) blocked = 1;
+  }
+  for (int m = 1; m < G; m <<= 1) blocked |= __shfl_xor(blocked, m, 64);
+  const bool take = open && !blocked;
+  int colour = -1, base = 0;
+  while (__any(take && colour < 0)) {
+    const bool scan = take && colour < 0;
+    unsigned long long used = 0ull;
+    if (scan) {
+      for (long long k = k0 + sub; k < k1; k += G) {
+        const int j = ja[k], c = cin[j];
+        if (j != i && c >= base && c < base + 64) used |= 1ull << (c - base);
+      }
+      for (long long k = t0 + sub; k < t1; k += G) {
+        const int j = tja[k], c = cin[j];
+        if (j != i && c >= base && c < base + 64) used |= 1ull << (c - base);
+      }
+    }
+    for (int m = 1; m < G; m <<= 1) used |= __shfl_xor(used, m, 64);
+    if (scan) {
+      if (~used)
+        colour = base + __ffsll((long long)~used) - 1;
+      else
+        base += 64;
+    }
+  }
+  if (live && sub == 0) cout[i] = open ? colour : mine;
+  const int still = __syncthreads_count(open && sub == 0 && colour < 0);
+  if (threadIdx.x == 0 && still) atomicAdd(left, still);
+}
+
+// out[perm[q]] = in[q]: the result of the substitutions on B = P D P^T back in the caller's numbering
+__global__ __launch_bounds__(BLK) void ilu_unpermute_k(int n, const int *__restrict__ perm, const double *__restrict__ in,
+                                                       double *__restrict__ out) {
+  const long long q = bid() * BLK + threadIdx.x;
+  if (q < n) out[perm[q]] = in[q];
+}
+
 // Every kernel below but ilu_dpos_k relies on a stored diagonal in every row (dpos[i] >= 0): IluSolver::setup refuses a
 // pattern without one before it launches any of them.
 // one thread per row of the level: the oracle's IKJ loop, same operation order
@@ -1557,12 +1636,12 @@ __global__ __launch_bounds__(BLK) void ilu_factor_k(int nrows, const int *__rest
 
 __global__ __launch_bounds__(BLK) void ilu_lower_k(int nrows, const int *__restrict__ rows,
                                                    const long long *__restrict__ ia, const int *__restrict__ ja,
-                                                   const double *__restrict__ a, const double *__restrict__ b,
-                                                   double *__restrict__ y) {
+                                                   const double *__restrict__ a, const int *__restrict__ perm,
+                                                   const double *__restrict__ b, double *__restrict__ y) {
   const long long t = bid() * BLK + threadIdx.x;
   if (t >= nrows) return;
   const int i = rows ? rows[t] : (int)t;
-  double s = b[i];
+  double s = b[perm ? perm[i] : i];  // perm: the right-hand side is in the caller's numbering, row i of B is its perm[i]
   for (long long k = ia[i]; k < ia[i + 1] && ja[k] < i; k++) s -= a[k] * y[ja[k]];
   y[i] = s;
 }
@@ -1583,11 +1662,11 @@ __global__ __launch_bounds__(BLK) void ilu_upper_k(int nrows, const int *__restr
 // Jacobi sweeps: every row reads the previous iterate
 __global__ __launch_bounds__(BLK) void ilu_lower_jac_k(int n, const long long *__restrict__ ia,
                                                        const int *__restrict__ ja, const double *__restrict__ a,
-                                                       const double *__restrict__ b, const double *__restrict__ in,
-                                                       double *__restrict__ out) {
+                                                       const int *__restrict__ perm, const double *__restrict__ b,
+                                                       const double *__restrict__ in, double *__restrict__ out) {
   const long long i = bid() * BLK + threadIdx.x;
   if (i >= n) return;
-  double s = b[i];
+  double s = b[perm ? perm[i] : i];
   if (in)
     for (long long k = ia[i]; k < ia[i + 1] && ja[k] < i; k++) s -= a[k] * in[ja[k]];
   out[i] = s;
@@ -2891,26 +2970,58 @@ void ilu_diag_positions(const DCsr &A, long long *dpos, hipStream_t s) {
 void ilu_factor_level(DCsr &LU, const long long *dpos, const int *rows, int nrows, hipStream_t s) {
   if (nrows) ilu_factor_k<<<(unsigned)((nrows + BLK - 1) / BLK), BLK, 0, s>>>(nrows, rows, LU.ia.p, LU.ja.p, LU.a.p, dpos);
 }
-void ilu_lower_level(const DCsr &LU, const long long *dpos, const int *rows, int nrows, const double *b, double *y,
-                     hipStream_t s) {
+void ilu_lower_level(const DCsr &LU, const long long *dpos, const int *rows, int nrows, const int *perm, const double *b,
+                     double *y, hipStream_t s) {
   (void)dpos;
-  if (nrows) ilu_lower_k<<<(unsigned)((nrows + BLK - 1) / BLK), BLK, 0, s>>>(nrows, rows, LU.ia.p, LU.ja.p, LU.a.p, b, y);
+  if (nrows)
+    ilu_lower_k<<<(unsigned)((nrows + BLK - 1) / BLK), BLK, 0, s>>>(nrows, rows, LU.ia.p, LU.ja.p, LU.a.p, perm, b, y);
 }
 void ilu_upper_level(const DCsr &LU, const long long *dpos, const int *rows, int nrows, const double *y, double *x,
                      hipStream_t s) {
   if (nrows)
     ilu_upper_k<<<(unsigned)((nrows + BLK - 1) / BLK), BLK, 0, s>>>(nrows, rows, LU.ia.p, LU.ja.p, LU.a.p, dpos, y, x);
 }
-void ilu_lower_jacobi(const DCsr &LU, const long long *dpos, const double *b, const double *in, double *out,
-                      hipStream_t s) {
+void ilu_lower_jacobi(const DCsr &LU, const long long *dpos, const int *perm, const double *b, const double *in,
+                      double *out, hipStream_t s) {
   (void)dpos;
   const int n = LU.nrows;
-  if (n) ilu_lower_jac_k<<<(unsigned)((n + BLK - 1) / BLK), BLK, 0, s>>>(n, LU.ia.p, LU.ja.p, LU.a.p, b, in, out);
+  if (n) ilu_lower_jac_k<<<(unsigned)((n + BLK - 1) / BLK), BLK, 0, s>>>(n, LU.ia.p, LU.ja.p, LU.a.p, perm, b, in, out);
 }
 void ilu_upper_jacobi(const DCsr &LU, const long long *dpos, const double *b, const double *in, double *out,
                       hipStream_t s) {
   const int n = LU.nrows;
   if (n) ilu_upper_jac_k<<<(unsigned)((n + BLK - 1) / BLK), BLK, 0, s>>>(n, LU.ia.p, LU.ja.p, LU.a.p, dpos, b, in, out);
+}
+
+void ilu_unpermute(const int *perm, const double *in, double *out, int n, hipStream_t s) {
+  if (n) ilu_unpermute_k<<<grid_for(((long long)n + BLK - 1) / BLK), BLK, 0, s>>>(n, perm, in, out);
+}
+
+int ilu_multicolour(const DCsr &D, DVec<int> &colour, int &rounds, hipStream_t s) {
+  const int n = D.nrows;
+  rounds = 0;
+  colour.alloc((size_t)n);
+  if (n == 0) return 0;
+  DCsr T;
+  transpose(D, T, s);
+  DVec<int> other((size_t)n), left(1);
+  MI_HIP(hipMemsetAsync(colour.p, 0xff, (size_t)n * sizeof(int), s));  // -1: no colour yet
+  int *cin = colour.p, *cout = other.p;
+  const int rg = row_group(2 * D.nnz, n);  // a row of D + D^T is scanned through D's row and D^T's row
+  const dim3 grid = grid_for(((long long)n * rg + BLK - 1) / BLK);
+  int open = n;
+  while (open > 0) {
+    // every round colours at least the first uncoloured row in priority order: n rounds are the most a correct run takes
+    if (rounds >= n) return -1;
+    MI_HIP(hipMemsetAsync(left.p, 0, sizeof(int), s));
+    MI_ROW_GROUP_DISPATCH(rg, (ilu_colour_round_k<G><<<grid, BLK, 0, s>>>(n, D.ia.p, D.ja.p, T.ia.p, T.ja.p, cin, cout, left.p)))
+    MI_HIP(hipGetLastError());
+    d2h(&open, left.p, sizeof(int), s);
+    std::swap(cin, cout);
+    rounds++;
+  }
+  if (cin != colour.p) std::swap(colour, other);
+  return 0;
 }
 
 long long ilu_zero_pivot(const DCsr &LU, const long long *dpos, hipStream_t s) {

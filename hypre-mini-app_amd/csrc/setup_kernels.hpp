@@ -198,6 +198,15 @@ int value_lookup(DevCSR &dst, const int *rowmap, const int *colmap, const DevCSR
 // level_norms of an operator in the solve format (one rank)
 void level_norms(const DevCSR &A, const int *cf, int chunk, double *diag, double *l1gs, double *l1jac, hipStream_t s);
 
+// ---- multicolour ordering of the ILU (local_reordering 2): the first-fit greedy colouring of the
+// graph of D + D^T (diagonal excluded) taken in the order of the rows' hashed priorities, found by Jones-Plassmann
+// rounds -- one launch and one small download (the rows still uncoloured) per round, no waiting inside a launch.
+// colour: n entries on return; rounds: launches run.  Returns 0, or -1 when n rounds left rows uncoloured (which a
+// correct run cannot do: the caller fails).
+int ilu_multicolour(const DCsr &D, DVec<int> &colour, int &rounds, hipStream_t s);
+// out[perm[q]] = in[q]
+void ilu_unpermute(const int *perm, const double *in, double *out, int n, hipStream_t s);
+
 // ---- ILU(0) of a single-rank block (HYPRE_ILU type 0, fill 0), level-scheduled
 // position of the diagonal entry of every row (-1: none)
 void ilu_diag_positions(const DCsr &A, long long *dpos, hipStream_t s);
@@ -208,13 +217,16 @@ long long ilu_zero_pivot(const DCsr &LU, const long long *dpos, hipStream_t s);
 void ilu_factor_level(DCsr &LU, const long long *dpos, const int *rows, int nrows, hipStream_t s);
 // forward / backward substitution for one level set: y[i] = b[i] - sum_{k<i} l_ik y_k ;
 // x[i] = (y[i] - sum_{j>i} u_ij x_j) / u_ii
-void ilu_lower_level(const DCsr &LU, const long long *dpos, const int *rows, int nrows, const double *b, double *y,
-                     hipStream_t s);
+// perm (nullable, here and in ilu_lower_jacobi): the lower substitution reads b[perm[i]] for row i -- the gather of a
+// right-hand side in the caller's numbering when LU holds the factors of the reordered block P D P^T
+void ilu_lower_level(const DCsr &LU, const long long *dpos, const int *rows, int nrows, const int *perm, const double *b,
+                     double *y, hipStream_t s);
 void ilu_upper_level(const DCsr &LU, const long long *dpos, const int *rows, int nrows, const double *y, double *x,
                      hipStream_t s);
 // Jacobi sweeps on the triangular factors (HYPRE's iterative triangular solve):
 // out = b - L_strict in   /   out = D^-1 (b - U_strict in) ; in == nullptr: out = b resp. D^-1 b
-void ilu_lower_jacobi(const DCsr &LU, const long long *dpos, const double *b, const double *in, double *out, hipStream_t s);
+void ilu_lower_jacobi(const DCsr &LU, const long long *dpos, const int *perm, const double *b, const double *in,
+                      double *out, hipStream_t s);
 void ilu_upper_jacobi(const DCsr &LU, const long long *dpos, const double *b, const double *in, double *out, hipStream_t s);
 
 // ---- iterative ILU(0) setup (ilu.cpp; DESIGN.md section 3, "Iterative ILU(0) setup"): fixed-point sweeps on the

@@ -101,6 +101,15 @@ struct IluSolver : SolverBase {
   int iter_sweeps = 0;
   double iter_correction = -1.0, iter_residual = -1.0;
   std::vector<double> iter_corr_hist, iter_res_hist;
+  // local reordering (HYPRE_ILUSetLocalReordering): 2 = multicolour ordering of the diagonal block (DESIGN.md section 3;
+  // this library's own number); every other value factorises in the caller's ordering
+  int reordering = 0;
+  // what the last setup did: the reordering in force (0 or 2), colours and colouring rounds (0 without the ordering),
+  // level sets of the lower and of the upper factor (0 when no level sets were built)
+  int ordering_info[5] = {0, 0, 0, 0, 0};
+  DVec<int> perm, colour;    // reordering 2: row q of the factorised block B = P D P^T is the caller's row perm[q]
+  std::vector<int> perm_h;   // perm on the host (empty without the ordering): refusals name the caller's row
+  DVec<double> xp;           // reordering 2: the result of the substitutions in B's numbering
   bool is_setup = false, levels_built = false;
   int n = 0;
   sk::DCsr LU;
@@ -116,7 +125,8 @@ struct IluSolver : SolverBase {
   // A row without a stored diagonal or an exactly zero pivot u_jj ends it with an error that names the row.
   void setup(ParCSR &A, Comm &comm);
   void iterative_factor(Comm &comm, long long row0);
-  void apply(const double *rhs, double *out);           // out = U^-1 L^-1 rhs
+  void multicolour_order(const HostCSR &D, HostCSR &B);  // reordering 2: colour, perm, ordering_info[0..2]; B = P D P^T
+  void apply(const double *rhs, double *out);           // out = U^-1 L^-1 rhs (reordering 2: P^T U^-1 L^-1 P rhs)
   int solve(ParCSR &A, ParVector &b, ParVector &x);     // x += M^-1 (b - A x), max_iter times or to tol
 };
 

@@ -299,6 +299,7 @@ class BoomerAMG:
                               ("ilu_level", "HYPRE_BoomerAMGSetILULevel", int),
                               ("ilu_max_iter", "HYPRE_BoomerAMGSetILUMaxIter", int),
                               ("ilu_tri_solve", "HYPRE_BoomerAMGSetILUTriSolve", int),
+                              ("ilu_reordering_type", "HYPRE_BoomerAMGSetILULocalReordering", int),  # 2 = multicolour
                               ("ilu_lower_jacobi_iters", "HYPRE_BoomerAMGSetILULowerJacobiIters", int),
                               ("ilu_upper_jacobi_iters", "HYPRE_BoomerAMGSetILUUpperJacobiIters", int),
                               ("iterative_ilu_algorithm_type", "HYPRE_BoomerAMGSetILUIterSetupType", int),
@@ -548,6 +549,13 @@ class BoomerAMG:
         call("HYPRE_MI_BoomerAMGGetLevelFSAIInfo", self.h, level, out)
         return {k: int(v) for k, v in zip(FSAI_INFO_NAMES, out)}
 
+    def level_ilu_ordering(self, level):
+        """ILU.ordering() of the level's ILU smoother (smooth_type 5), rows in level_csr's numbering; raises without
+        one."""
+        nr, nc, nnz = c_int(), c_int(), c_big()
+        call("HYPRE_MI_BoomerAMGGetLevelCSRSize", self.h, level, 0, C.byref(nr), C.byref(nc), C.byref(nnz))
+        return _ilu_ordering("HYPRE_MI_BoomerAMGGetLevelILUOrdering", nr.value, self.h, level)
+
     def smooth_level(self, level, f, u=None):
         """One complex-smoother step of the level on host arrays; u None = zero guess."""
         f = dbl(f)
@@ -568,16 +576,33 @@ class BoomerAMG:
             pass
 
 
+ILU_ORDERING_NAMES = ("reordering", "colours", "rounds", "lower_levels", "upper_levels")
+
+
+def _ilu_ordering(fn, n, *handle):
+    """dict with ILU_ORDERING_NAMES, perm and colour (int32, n entries: by block row / by the caller's local row; None
+    when no ordering is in force) from HYPRE_MI_ILUGetOrdering or its per-level counterpart."""
+    info = np.zeros(5, dtype=np.int32)
+    perm = np.zeros(max(n, 1), dtype=np.int32)
+    colour = np.zeros(max(n, 1), dtype=np.int32)
+    call(fn, *handle, info, perm, colour)
+    out = {k: int(v) for k, v in zip(ILU_ORDERING_NAMES, info)}
+    on = out["reordering"] != 0
+    out["perm"], out["colour"] = (perm[:n], colour[:n]) if on else (None, None)
+    return out
+
+
 class ILU:
     """HYPRE_ILU: block-Jacobi ILU(k) (type 0); usable as a preconditioner (set_precond) or a solver.
     iterative_algorithm_type 1-4 (fill 0): the factors come from fixed-point sweeps."""
 
     def __init__(self, max_iterations=1, tolerance=0.0, trisolve=1, lower_jacobi_iters=5, upper_jacobi_iters=5,
                  print_level=0, ilu_type=0, fill=0, iterative_algorithm_type=0, iterative_setup_option=0,
-                 iterative_max_iterations=100, iterative_tolerance=1e-3):
+                 iterative_max_iterations=100, iterative_tolerance=1e-3, local_reordering=0):
         self.h = vp()
         call("HYPRE_ILUCreate", C.byref(self.h))
         call("HYPRE_ILUSetType", self.h, ilu_type)
+        call("HYPRE_ILUSetLocalReordering", self.h, int(local_reordering))  # 2 = multicolour ordering
         call("HYPRE_ILUSetLevelOfFill", self.h, fill)
         call("HYPRE_ILUSetIterativeSetupType", self.h, int(iterative_algorithm_type))
         call("HYPRE_ILUSetIterativeSetupOption", self.h, int(iterative_setup_option))
@@ -624,8 +649,16 @@ class ILU:
         call("HYPRE_MI_ILUGetIterativeSetupHistory", self.h, C.byref(nc), c, C.byref(nr), r)
         return c[: nc.value], r[: nr.value]
 
+    def ordering(self):
+        """dict(reordering, colours, rounds, lower_levels, upper_levels, perm, colour) of the last setup; perm and
+        colour (int32, by block row / by the caller's local row) are None when no ordering is in force."""
+        nr, nnz = c_int(), c_big()
+        call("HYPRE_MI_ILUGetFactorsSize", self.h, C.byref(nr), C.byref(nnz))
+        return _ilu_ordering("HYPRE_MI_ILUGetOrdering", nr.value, self.h)
+
     def factors(self):
-        """(ia int64, ja int32, a f64): L (unit diagonal not stored) and U of this rank's block as one CSR."""
+        """(ia int64, ja int32, a f64): L (unit diagonal not stored) and U of this rank's block as one CSR -- of the
+        reordered block P D P^T when local_reordering 2 is in force (ordering())."""
         nr, nnz = c_int(), c_big()
         call("HYPRE_MI_ILUGetFactorsSize", self.h, C.byref(nr), C.byref(nnz))
         ia = np.zeros(nr.value + 1, dtype=np.int64)

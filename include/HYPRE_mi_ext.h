@@ -343,6 +343,16 @@ HYPRE_Int HYPRE_MI_ILUGetIterativeSetupHistory(HYPRE_Solver solver, HYPRE_Int *n
                                                HYPRE_Real *res);
 HYPRE_Int HYPRE_MI_ILUGetFactorsSize(HYPRE_Solver solver, HYPRE_Int *nrows, HYPRE_BigInt *nnz);
 HYPRE_Int HYPRE_MI_ILUGetFactors(HYPRE_Solver solver, HYPRE_BigInt *ia, HYPRE_Int *ja, HYPRE_Complex *a);
+/* Multicolour ordering (HYPRE_ILUSetLocalReordering / HYPRE_BoomerAMGSetILULocalReordering value 2, this library's own
+ * number): the block that is factorised is B = P D P^T, row q of B being the caller's local row
+ * perm[q], rows sorted by (colour, local index).  With the ordering on, HYPRE_MI_ILUGetFactors returns the factors of
+ * B, in B's numbering.  info[5]: the reordering in force (0 or 2), the number of colours, the colouring rounds, the
+ * level sets of the lower and of the upper factor (0 when the setup built none).  perm, colour: n entries each, colour
+ * by the caller's local row; either may be null, and neither is written when no ordering is in force. */
+HYPRE_Int HYPRE_MI_ILUGetOrdering(HYPRE_Solver solver, HYPRE_Int info[5], HYPRE_Int *perm, HYPRE_Int *colour);
+/* the same of the ILU smoother of a level (smooth_type 5), rows in GetLevelCSR's numbering; an error without one */
+HYPRE_Int HYPRE_MI_BoomerAMGGetLevelILUOrdering(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int info[5], HYPRE_Int *perm,
+                                                HYPRE_Int *colour);
 /* one complex-smoother step of a level on HOST arrays (the counterpart of RelaxLevel): u <- u + M (f - A u) with the
  * level's smoother M; zero_guess != 0 takes u = 0 on entry (the mat-vec is skipped, as on a cycle's down leg) */
 HYPRE_Int HYPRE_MI_BoomerAMGSmoothLevel(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int zero_guess,
