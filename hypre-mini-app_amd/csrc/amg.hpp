@@ -172,6 +172,8 @@ struct AmgLevel {
   bool dense = false;
 };
 
+struct LevelBuild;  // what build_natural knows about the level it is building (amg_setup.cpp)
+
 struct BoomerAMG {
   AmgParams p;
   std::vector<AmgLevel> L;
@@ -281,6 +283,11 @@ struct BoomerAMG {
   // hierarchy construction: host only (threads + host collectives)
   void setup_host(ParCSR &A);
   void build_natural(ParCSR &A);      // strength / PMIS / interpolation / Galerkin loop, natural ordering
+  // its steps on the state of the level being built (amg_setup.cpp; DESIGN.md section 3, "The level build")
+  void level_strength_and_coarsening(LevelBuild &b);
+  void level_interpolation(LevelBuild &b);
+  void level_restriction(LevelBuild &b);
+  void level_galerkin_and_adopt(LevelBuild &b);
   void build_replicated(ParCSR &A);   // N > 1: global hierarchy on every rank, then this rank's row slices
   // N > 1: the same hierarchy built with O(N_global / P) per rank (amg_setup_dist.cpp); PMIS without aggressive
   // levels (the Ruge-Stueben family is sequential on the global graph: replicated path)
@@ -328,6 +335,8 @@ struct BoomerAMG {
   void local_entry_counts(double &tot, double &base) const;  // this rank's share (redundant levels: 1 / size of them)
   // fill the host arrays of a level's A / P / R from the device (inspection API, coarse solve)
   void ensure_host(int level);
+  // one operator: host_diag_stale -> download from `dev` (or from the solve format) -> ensure_offd_rows
+  static void fetch_operator(ParCSR *M, sk::DCsr &dev);
 };
 
 // MI_HYPRE_GS_ZERO_SKIP: 0 = sweeps on a zero guess read like any other sweep, 1 = they skip the gathers of

@@ -103,22 +103,11 @@ void build_interp(const ParCSR &A, const Strength &S, std::vector<int> &cf, int 
                   int pmax, HostCSR &P, int &nc_out, const std::vector<char> *want_rows) {
   const HostCSR &D = A.diag, &O = A.offd;
   const int n = D.nrows;
-  std::vector<int> f2c((size_t)n, -1);
-  int nc = 0;
-  for (int i = 0; i < n; i++)
-    if (cf[(size_t)i] == C_PT) f2c[(size_t)i] = nc++;
-  nc_out = nc;
-  const int nt = host_threads();
-  std::vector<std::vector<int>> tj((size_t)nt);
-  std::vector<std::vector<double>> ta((size_t)nt);
-  std::vector<int> rowlen((size_t)n, 0);
-  std::vector<int64_t> tbeg((size_t)nt + 1, 0);
-  std::vector<char> used((size_t)nt, 0);
+  std::vector<int> f2c;
+  const int nc = nc_out = coarse_numbering(cf, f2c);
+  RowCollector<int> rows(n);
   parallel_for(n, [&](int64_t b, int64_t e, int t) {
-    used[(size_t)t] = 1;
-    tbeg[(size_t)t] = b;
-    std::vector<int> &oj = tj[(size_t)t];
-    std::vector<double> &oa = ta[(size_t)t];
+    auto &out = rows.begin(t, b);
     std::vector<int> rc, sf;  // interpolatory set (fine ids, discovery order), strong F neighbours
     std::vector<double> rv;
     std::vector<char> keep;
@@ -238,23 +227,15 @@ void build_interp(const ParCSR &A, const Strength &S, std::vector<int> &cf, int 
         rc[(size_t)bb + 1] = c;
         rv[(size_t)bb + 1] = v;
       }
-      rowlen[(size_t)i] = len;
-      oj.insert(oj.end(), rc.begin(), rc.end());
-      oa.insert(oa.end(), rv.begin(), rv.end());
+      rows.len[(size_t)i] = len;
+      out.j.insert(out.j.end(), rc.begin(), rc.end());
+      out.a.insert(out.a.end(), rv.begin(), rv.end());
     }
   });
   P.nrows = n;
   P.ncols = nc;
-  P.ia.assign((size_t)n + 1, 0);
-  for (int i = 0; i < n; i++) P.ia[(size_t)i + 1] = P.ia[(size_t)i] + rowlen[(size_t)i];
-  P.ja.resize((size_t)P.nnz());
-  P.a.resize((size_t)P.nnz());
-  for (int t = 0; t < nt; t++) {
-    if (!used[(size_t)t] || tj[(size_t)t].empty()) continue;
-    const int64_t off = P.ia[(size_t)tbeg[(size_t)t]];
-    memcpy(P.ja.data() + off, tj[(size_t)t].data(), tj[(size_t)t].size() * sizeof(int));
-    memcpy(P.a.data() + off, ta[(size_t)t].data(), ta[(size_t)t].size() * sizeof(double));
-  }
+  P.ia.assign(1, 0);
+  rows.assemble(P.ia, P.ja, &P.a);
   if (!want_rows)
     for (int i = 0; i < n; i++)
       if (cf[(size_t)i] == SF_PT) cf[(size_t)i] = F_PT;
@@ -477,23 +458,14 @@ void coarsen_by_type(int type, int n, const Strength &S, std::vector<int> &cf) {
 // hypre_BoomerAMGCreate2ndS, num_paths 1: graph on the C points of the first coarsening; C point i depends on
 // C point j != i iff j is in S_i or in S_k for some k in S_i.  Coarse indices, columns ascending.
 void second_strength(int n, const Strength &S, const std::vector<int> &cf, Strength &S2, int &nc_out) {
-  std::vector<int> f2c((size_t)n, -1);
-  int nc = 0;
-  for (int i = 0; i < n; i++)
-    if (cf[(size_t)i] == C_PT) f2c[(size_t)i] = nc++;
-  nc_out = nc;
+  std::vector<int> f2c;
+  const int nc = nc_out = coarse_numbering(cf, f2c);
   std::vector<int> crow((size_t)nc);
   for (int i = 0; i < n; i++)
     if (f2c[(size_t)i] >= 0) crow[(size_t)f2c[(size_t)i]] = i;
-  const int nt = host_threads();
-  std::vector<std::vector<int>> tj((size_t)nt);
-  std::vector<int> rowlen((size_t)nc, 0);
-  std::vector<int64_t> tbeg((size_t)nt, 0);
-  std::vector<char> used((size_t)nt, 0);
+  RowCollector<int> rows(nc);  // (the pattern alone)
   parallel_for(nc, [&](int64_t b, int64_t e, int t) {
-    used[(size_t)t] = 1;
-    tbeg[(size_t)t] = b;
-    std::vector<int> &out = tj[(size_t)t];
+    std::vector<int> &out = rows.begin(t, b).j;
     std::vector<int> row;
     for (int64_t ci = b; ci < e; ci++) {
       const int i = crow[(size_t)ci];
@@ -509,16 +481,12 @@ void second_strength(int n, const Strength &S, const std::vector<int> &cf, Stren
       }
       std::sort(row.begin(), row.end());
       row.erase(std::unique(row.begin(), row.end()), row.end());
-      rowlen[(size_t)ci] = (int)row.size();
+      rows.len[(size_t)ci] = (int)row.size();
       out.insert(out.end(), row.begin(), row.end());
     }
   });
-  S2.ia.assign((size_t)nc + 1, 0);
-  for (int q = 0; q < nc; q++) S2.ia[(size_t)q + 1] = S2.ia[(size_t)q] + rowlen[(size_t)q];
-  S2.ja.resize((size_t)S2.ia[(size_t)nc]);
-  for (int t = 0; t < nt; t++)
-    if (used[(size_t)t] && !tj[(size_t)t].empty())
-      memcpy(S2.ja.data() + S2.ia[(size_t)tbeg[(size_t)t]], tj[(size_t)t].data(), tj[(size_t)t].size() * sizeof(int));
+  S2.ia.assign(1, 0);
+  rows.assemble(S2.ia, S2.ja);
 }
 
 // aggressive coarsening of one level (par_amg_setup.c, level < agg_num_levels; src/HypreSystem.cpp:215-219):
@@ -547,11 +515,8 @@ void build_multipass(const ParCSR &A, const Strength &S, std::vector<int> &cf, d
                      HostCSR &P, int &nc_out) {
   const HostCSR &D = A.diag;
   const int n = D.nrows;
-  std::vector<int> f2c((size_t)n, -1);
-  int nc = 0;
-  for (int i = 0; i < n; i++)
-    if (cf[(size_t)i] == C_PT) f2c[(size_t)i] = nc++;
-  nc_out = nc;
+  std::vector<int> f2c;
+  const int nc = nc_out = coarse_numbering(cf, f2c);
   std::vector<int> assigned((size_t)n, -1), rlen((size_t)n, 0);
   std::vector<int64_t> rstart((size_t)n, 0);
   std::vector<int> pool_c;  // rows in the order they were built: coarse columns / weights in discovery order
@@ -584,35 +549,24 @@ void build_multipass(const ParCSR &A, const Strength &S, std::vector<int> &cf, d
     }
     const int64_t nl = (int64_t)list.size();
     if (nl == 0) break;
-    std::vector<std::vector<int>> tc((size_t)nt);
-    std::vector<std::vector<double>> tv((size_t)nt);
-    std::vector<int> newlen((size_t)nl, 0);
-    std::vector<int64_t> tbeg((size_t)nt, 0);
-    std::vector<char> used((size_t)nt, 0);
+    RowCollector<int> rows(nl);
     parallel_for(nl, [&](int64_t b, int64_t e, int t) {
-      used[(size_t)t] = 1;
-      tbeg[(size_t)t] = b;
       std::vector<int> &pos = cpos[(size_t)t];
       if (pos.size() != (size_t)nc) pos.assign((size_t)nc, -1);
-      std::vector<int> &oc = tc[(size_t)t];
-      std::vector<double> &ov = tv[(size_t)t];
+      auto &out = rows.begin(t, b);
+      std::vector<int> &oc = out.j;
+      std::vector<double> &ov = out.a;
       for (int64_t q = b; q < e; q++) {
         const int i = list[(size_t)q];
         const size_t base = oc.size();
         double diagonal = 0.0, sum_N = 0.0, sum_J = 0.0;
-        int64_t ks = S.ia[(size_t)i];
-        const int64_t kse = S.ia[(size_t)i + 1];
-        for (int64_t k = D.ia[(size_t)i]; k < D.ia[(size_t)i + 1]; k++) {
-          const int j = D.ja[(size_t)k];
+        for_each_entry_strong(D, S, i, [&](int64_t k, int j, bool strong) {
           if (j == i) {
             diagonal = D.a[(size_t)k];
-            continue;
+            return;
           }
           sum_N += D.a[(size_t)k];
-          // S_i is a subsequence of A's row: two-pointer membership test
-          while (ks < kse && S.ja[(size_t)ks] < j) ks++;
-          const bool strong = ks < kse && S.ja[(size_t)ks] == j;
-          if (!strong || assigned[(size_t)j] != pass - 1) continue;
+          if (!strong || assigned[(size_t)j] != pass - 1) return;
           sum_J += D.a[(size_t)k];
           const int64_t r0 = rstart[(size_t)j];
           for (int w = 0; w < rlen[(size_t)j]; w++) {
@@ -624,7 +578,7 @@ void build_multipass(const ParCSR &A, const Strength &S, std::vector<int> &cf, d
             }
             ov[base + (size_t)pos[(size_t)c]] += D.a[(size_t)k] * pool_v[(size_t)(r0 + w)];
           }
-        }
+        });
         for (int64_t k = A.offd.ia[(size_t)i]; k < A.offd.ia[(size_t)i + 1]; k++) sum_N += A.offd.a[(size_t)k];
         const double alfa = (sum_J * diagonal != 0.0) ? -sum_N / (sum_J * diagonal) : 0.0;
         const int len = (int)(oc.size() - base);
@@ -632,25 +586,17 @@ void build_multipass(const ParCSR &A, const Strength &S, std::vector<int> &cf, d
           ov[base + (size_t)w] *= alfa;
           pos[(size_t)oc[base + (size_t)w]] = -1;
         }
-        newlen[(size_t)q] = len;
+        rows.len[(size_t)q] = len;
       }
     });
     // append the pass's rows to the pool (list order) -- only now do its points count as reached
-    int64_t at = (int64_t)pool_c.size();
+    std::vector<int64_t> at(1, (int64_t)pool_c.size());
+    rows.assemble(at, pool_c, &pool_v);
     for (int64_t q = 0; q < nl; q++) {
-      rstart[(size_t)list[(size_t)q]] = at;
-      rlen[(size_t)list[(size_t)q]] = newlen[(size_t)q];
-      at += newlen[(size_t)q];
+      rstart[(size_t)list[(size_t)q]] = at[(size_t)q];
+      rlen[(size_t)list[(size_t)q]] = rows.len[(size_t)q];
+      assigned[(size_t)list[(size_t)q]] = pass;
     }
-    pool_c.resize((size_t)at);
-    pool_v.resize((size_t)at);
-    for (int t = 0; t < nt; t++)
-      if (used[(size_t)t] && !tc[(size_t)t].empty()) {
-        const int64_t off = rstart[(size_t)list[(size_t)tbeg[(size_t)t]]];
-        memcpy(pool_c.data() + off, tc[(size_t)t].data(), tc[(size_t)t].size() * sizeof(int));
-        memcpy(pool_v.data() + off, tv[(size_t)t].data(), tv[(size_t)t].size() * sizeof(double));
-      }
-    for (int64_t q = 0; q < nl; q++) assigned[(size_t)list[(size_t)q]] = pass;
     remaining -= nl;
   }
   // truncation and sort row by row (in place in the pool), then compaction into P
@@ -694,21 +640,13 @@ void build_multipass(const ParCSR &A, const Strength &S, std::vector<int> &cf, d
     if (cf[(size_t)i] == SF_PT) cf[(size_t)i] = F_PT;
 }
 
-// Extended interpolation E(A, S, m) of the two-stage interpolation (DESIGN.md section 3, "Two-stage extended
-// interpolation"), in matrix-matrix form: numerators N = Lo * M by host_spgemm, then w_ij = -n_ij / d_i, then the
-// truncation.  rows (optional): build these rows only (the C1 rows of the second stage); columns: C points of m in
-// fine order.  Every row is one thread's, every sum runs in stored order.
-static void two_stage_ext_operands(const HostCSR &D, const Strength &S, const std::vector<int> &m,
-                                   const std::vector<int> *rows, HostCSR &Lo, HostCSR &M, std::vector<double> &d,
-                                   int &nc_out) {
+// The right operand of the interpolations in matrix-matrix form, and beta_k = the sum of a_kl over the strong C
+// neighbours l of k (stored order): row k of M is e_k for a C point, else the strong C entries of row k -- each divided
+// by beta_k when `scaled` -- and nothing when beta_k = 0.  Columns: C points of m in fine order (f2c).
+static void strong_c_operand(const HostCSR &D, const Strength &S, const std::vector<int> &m, const std::vector<int> &f2c,
+                             int nc, bool scaled, std::vector<double> &beta, HostCSR &M) {
   const int n = D.nrows;
-  std::vector<int> f2c((size_t)n, -1);
-  int nc = 0;
-  for (int i = 0; i < n; i++)
-    if (m[(size_t)i] == C_PT) f2c[(size_t)i] = nc++;
-  nc_out = nc;
-  // beta_k = sum of a_kl over the strong C neighbours of k, and the length of M's row k
-  std::vector<double> beta((size_t)n, 0.0);
+  beta.assign((size_t)n, 0.0);
   std::vector<int> mlen((size_t)n, 0);
   parallel_for(n, [&](int64_t b, int64_t e, int) {
     for (int64_t k = b; k < e; k++) {
@@ -718,16 +656,12 @@ static void two_stage_ext_operands(const HostCSR &D, const Strength &S, const st
       }
       double bk = 0.0;
       int cnt = 0;
-      int64_t ks = S.ia[(size_t)k];
-      const int64_t kse = S.ia[(size_t)k + 1];
-      for (int64_t q = D.ia[(size_t)k]; q < D.ia[(size_t)k + 1] && ks < kse; q++) {
-        const int l = D.ja[(size_t)q];
-        while (ks < kse && S.ja[(size_t)ks] < l) ks++;
-        if (ks < kse && S.ja[(size_t)ks] == l && m[(size_t)l] == C_PT) {
+      for_each_strong_entry(D, S, k, [&](int64_t q, int l) {
+        if (m[(size_t)l] == C_PT) {
           bk += D.a[(size_t)q];
           cnt++;
         }
-      }
+      });
       beta[(size_t)k] = bk;
       mlen[(size_t)k] = bk != 0.0 ? cnt : 0;
     }
@@ -747,19 +681,29 @@ static void two_stage_ext_operands(const HostCSR &D, const Strength &S, const st
         continue;
       }
       if (!mlen[(size_t)k]) continue;
-      int64_t ks = S.ia[(size_t)k];
-      const int64_t kse = S.ia[(size_t)k + 1];
-      for (int64_t q = D.ia[(size_t)k]; q < D.ia[(size_t)k + 1] && ks < kse; q++) {
-        const int l = D.ja[(size_t)q];
-        while (ks < kse && S.ja[(size_t)ks] < l) ks++;
-        if (ks < kse && S.ja[(size_t)ks] == l && m[(size_t)l] == C_PT) {
+      for_each_strong_entry(D, S, k, [&](int64_t q, int l) {
+        if (m[(size_t)l] == C_PT) {
           M.ja[(size_t)w] = f2c[(size_t)l];
-          M.a[(size_t)w] = D.a[(size_t)q] / beta[(size_t)k];
+          M.a[(size_t)w] = scaled ? D.a[(size_t)q] / beta[(size_t)k] : D.a[(size_t)q];
           w++;
         }
-      }
+      });
     }
   });
+}
+
+// Extended interpolation E(A, S, m) of the two-stage interpolation (DESIGN.md section 3, "Two-stage extended
+// interpolation"), in matrix-matrix form: numerators N = Lo * M by host_spgemm, then w_ij = -n_ij / d_i, then the
+// truncation.  rows (optional): build these rows only (the C1 rows of the second stage); columns: C points of m in
+// fine order.  Every row is one thread's, every sum runs in stored order.
+static void two_stage_ext_operands(const HostCSR &D, const Strength &S, const std::vector<int> &m,
+                                   const std::vector<int> *rows, HostCSR &Lo, HostCSR &M, std::vector<double> &d,
+                                   int &nc_out) {
+  const int n = D.nrows;
+  std::vector<int> f2c;
+  const int nc = nc_out = coarse_numbering(m, f2c);
+  std::vector<double> beta;
+  strong_c_operand(D, S, m, f2c, nc, true, beta, M);
   // left operand: C row -> (i, 1) (the unit row comes out of the product as 1 * 1), F row -> its strong entries,
   // special F row -> nothing; d_i of the F rows
   const int nr = rows ? (int)rows->size() : n;
@@ -785,12 +729,7 @@ static void two_stage_ext_operands(const HostCSR &D, const Strength &S, const st
       }
       if (m[(size_t)i] != F_PT) continue;
       double di = 0.0;
-      int64_t ks = S.ia[(size_t)i];
-      const int64_t kse = S.ia[(size_t)i + 1];
-      for (int64_t q = D.ia[(size_t)i]; q < D.ia[(size_t)i + 1]; q++) {
-        const int j = D.ja[(size_t)q];
-        while (ks < kse && S.ja[(size_t)ks] < j) ks++;
-        const bool strong = ks < kse && S.ja[(size_t)ks] == j;
+      for_each_entry_strong(D, S, i, [&](int64_t q, int j, bool strong) {
         if (strong) {
           Lo.ja[(size_t)w] = j;
           Lo.a[(size_t)w] = D.a[(size_t)q];
@@ -798,7 +737,7 @@ static void two_stage_ext_operands(const HostCSR &D, const Strength &S, const st
           if (m[(size_t)j] != C_PT && beta[(size_t)j] == 0.0) di += D.a[(size_t)q];
         } else
           di += D.a[(size_t)q];  // the diagonal and the weak entries
-      }
+      });
       d[(size_t)r] = di;
     }
   });
@@ -860,10 +799,9 @@ static int two_stage_finish_rows(HostCSR &N, const std::vector<int> *rows, const
 // Two-stage extended interpolation of an aggressive level (agg_interp_type 5; Yang 2010, in the matrix-matrix form of
 // Li, Sjogreen, Yang 2021): P = P1 * P2 with P1 = E(A, S, m1) (n x |C1|) and P2 = the C1 rows of E(A, S, m2)
 // (|C1| x |C2|); P1 and P2 truncated by the P12 parameters, P by the aggressive ones.  m2 is handed on as multipass
-// hands it on (special F -> F).
-void build_two_stage_ext(const ParCSR &A, const Strength &S, const std::vector<int> &m1, std::vector<int> &m2,
-                         double p12_trunc_factor, int p12_max, double trunc_factor, int pmax, int level, HostCSR &P,
-                         int &nc_out) {
+// hands it on (special F -> F).  Returns -1, or the row with a zero denominator (P is then not built).
+int build_two_stage_ext(const ParCSR &A, const Strength &S, const std::vector<int> &m1, std::vector<int> &m2,
+                        double p12_trunc_factor, int p12_max, double trunc_factor, int pmax, HostCSR &P, int &nc_out) {
   const HostCSR &D = A.diag;
   const int n = D.nrows;
   std::vector<int> c1;
@@ -875,15 +813,16 @@ void build_two_stage_ext(const ParCSR &A, const Strength &S, const std::vector<i
   two_stage_ext_operands(D, S, m1, nullptr, Lo, M, d, nc1);
   host_spgemm(Lo, M, N);
   int bad = two_stage_finish_rows(N, nullptr, &m1, &d, p12_trunc_factor, p12_max, P1);
-  if (bad >= 0) two_stage_zero_denominator(level, bad);
+  if (bad >= 0) return bad;
   two_stage_ext_operands(D, S, m2, &c1, Lo, M, d, nc_out);
   host_spgemm(Lo, M, N);
   bad = two_stage_finish_rows(N, &c1, &m2, &d, p12_trunc_factor, p12_max, P2);
-  if (bad >= 0) two_stage_zero_denominator(level, bad);
+  if (bad >= 0) return bad;
   host_spgemm(P1, P2, N);
   two_stage_finish_rows(N, nullptr, nullptr, nullptr, trunc_factor, pmax, P);
   for (int i = 0; i < n; i++)
     if (m2[(size_t)i] == SF_PT) m2[(size_t)i] = F_PT;
+  return -1;
 }
 
 // Operands of the extended+i interpolation in matrix-matrix form (interp_type 17; DESIGN.md section 3, "Matrix-matrix
@@ -895,63 +834,10 @@ void build_two_stage_ext(const ParCSR &A, const Strength &S, const std::vector<i
 static void mm_extpi_operands(const HostCSR &D, const Strength &S, const std::vector<int> &m, HostCSR &B, HostCSR &Ah,
                               std::vector<double> &d, int &nc_out) {
   const int n = D.nrows;
-  std::vector<int> f2c((size_t)n, -1);
-  int nc = 0;
-  for (int i = 0; i < n; i++)
-    if (m[(size_t)i] == C_PT) f2c[(size_t)i] = nc++;
-  nc_out = nc;
-  std::vector<double> beta((size_t)n, 0.0);
-  std::vector<int> len((size_t)n, 0);
-  parallel_for(n, [&](int64_t b, int64_t e, int) {
-    for (int64_t k = b; k < e; k++) {
-      if (m[(size_t)k] == C_PT) {
-        len[(size_t)k] = 1;
-        continue;
-      }
-      double bk = 0.0;
-      int cnt = 0;
-      int64_t ks = S.ia[(size_t)k];
-      const int64_t kse = S.ia[(size_t)k + 1];
-      for (int64_t q = D.ia[(size_t)k]; q < D.ia[(size_t)k + 1] && ks < kse; q++) {
-        const int l = D.ja[(size_t)q];
-        while (ks < kse && S.ja[(size_t)ks] < l) ks++;
-        if (ks < kse && S.ja[(size_t)ks] == l && m[(size_t)l] == C_PT) {
-          bk += D.a[(size_t)q];
-          cnt++;
-        }
-      }
-      beta[(size_t)k] = bk;
-      len[(size_t)k] = bk != 0.0 ? cnt : 0;
-    }
-  });
-  Ah.nrows = n;
-  Ah.ncols = nc;
-  Ah.ia.assign((size_t)n + 1, 0);
-  for (int k = 0; k < n; k++) Ah.ia[(size_t)k + 1] = Ah.ia[(size_t)k] + len[(size_t)k];
-  Ah.ja.resize((size_t)Ah.nnz());
-  Ah.a.resize((size_t)Ah.nnz());
-  parallel_for(n, [&](int64_t b, int64_t e, int) {
-    for (int64_t k = b; k < e; k++) {
-      int64_t w = Ah.ia[(size_t)k];
-      if (m[(size_t)k] == C_PT) {
-        Ah.ja[(size_t)w] = f2c[(size_t)k];
-        Ah.a[(size_t)w] = 1.0;
-        continue;
-      }
-      if (!len[(size_t)k]) continue;
-      int64_t ks = S.ia[(size_t)k];
-      const int64_t kse = S.ia[(size_t)k + 1];
-      for (int64_t q = D.ia[(size_t)k]; q < D.ia[(size_t)k + 1] && ks < kse; q++) {
-        const int l = D.ja[(size_t)q];
-        while (ks < kse && S.ja[(size_t)ks] < l) ks++;
-        if (ks < kse && S.ja[(size_t)ks] == l && m[(size_t)l] == C_PT) {
-          Ah.ja[(size_t)w] = f2c[(size_t)l];
-          Ah.a[(size_t)w] = D.a[(size_t)q];
-          w++;
-        }
-      }
-    }
-  });
+  std::vector<int> f2c;
+  const int nc = nc_out = coarse_numbering(m, f2c);
+  std::vector<double> beta;
+  strong_c_operand(D, S, m, f2c, nc, false, beta, Ah);
   // a_ki: the stored entry (k, i), or 0
   auto entry = [&](int k, int i) {
     const int *r0 = D.ja.data() + D.ia[(size_t)k], *r1 = D.ja.data() + D.ia[(size_t)k + 1];
@@ -960,13 +846,9 @@ static void mm_extpi_operands(const HostCSR &D, const Strength &S, const std::ve
   };
   // one walk of F row i: what(j, kind, b, term) -- kind 0: term goes to d_i; 1: (j, b) goes to B; 2: both
   auto walk = [&](int i, auto &&what) {
-    int64_t ks = S.ia[(size_t)i];
-    const int64_t kse = S.ia[(size_t)i + 1];
-    for (int64_t q = D.ia[(size_t)i]; q < D.ia[(size_t)i + 1]; q++) {
-      const int j = D.ja[(size_t)q];
+    for_each_entry_strong(D, S, i, [&](int64_t q, int j, bool strong) {
       const double v = D.a[(size_t)q];
-      while (ks < kse && S.ja[(size_t)ks] < j) ks++;
-      if (!(ks < kse && S.ja[(size_t)ks] == j)) {
+      if (!strong) {
         what(j, 0, 0.0, v);  // the diagonal and the weak entries
       } else if (m[(size_t)j] == C_PT) {
         what(j, 1, v, 0.0);
@@ -983,7 +865,7 @@ static void mm_extpi_operands(const HostCSR &D, const Strength &S, const std::ve
           what(j, 2, bik, prod);
         }
       }
-    }
+    });
   };
   B.nrows = n;
   B.ncols = n;
@@ -1033,9 +915,10 @@ void mm_interp_zero_denominator(int interp_type, int level, int row) {
 
 // Extended (16) and extended+i (17) interpolation in matrix-matrix form (Li, Sjogreen, Yang 2021):
 // numerators N = B * Ah by host_spgemm, w_ij = -n_ij / d_i, truncation.  Type 16 is E(A, S, cf) of the two-stage
-// interpolation on the level's own marker.  cf is handed on with special F -> F.
-void build_mm_interp(const ParCSR &A, const Strength &S, std::vector<int> &cf, int interp_type, double trunc_factor,
-                     int pmax, int level, HostCSR &P, int &nc_out) {
+// interpolation on the level's own marker.  cf is handed on with special F -> F.  Returns -1, or the row with a zero
+// denominator (P is then not built).
+int build_mm_interp(const ParCSR &A, const Strength &S, std::vector<int> &cf, int interp_type, double trunc_factor,
+                    int pmax, HostCSR &P, int &nc_out) {
   const HostCSR &D = A.diag;
   HostCSR B, Ah, N;
   std::vector<double> d;
@@ -1045,9 +928,10 @@ void build_mm_interp(const ParCSR &A, const Strength &S, std::vector<int> &cf, i
     mm_extpi_operands(D, S, cf, B, Ah, d, nc_out);
   host_spgemm(B, Ah, N);
   const int bad = two_stage_finish_rows(N, nullptr, &cf, &d, trunc_factor, pmax, P);
-  if (bad >= 0) mm_interp_zero_denominator(interp_type, level, bad);
+  if (bad >= 0) return bad;
   for (size_t i = 0; i < cf.size(); i++)
     if (cf[i] == SF_PT) cf[i] = F_PT;
+  return -1;
 }
 
 void air_singular_system(int level, int row) {
@@ -1381,11 +1265,8 @@ int build_fsai_adaptive(const HostCSR &B, int S, int T, double tau, HostCSR &G, 
 // (c(j), 1.0) -- or an empty row.  Truncation does not apply.  cf is handed on with special F -> F.
 void build_one_point_interp(const HostCSR &D, const Strength &S, std::vector<int> &cf, HostCSR &P, int &nc_out) {
   const int n = D.nrows;
-  std::vector<int> f2c((size_t)n, -1), sel((size_t)n, -1);
-  int nc = 0;
-  for (int i = 0; i < n; i++)
-    if (cf[(size_t)i] == C_PT) f2c[(size_t)i] = nc++;
-  nc_out = nc;
+  std::vector<int> f2c, sel((size_t)n, -1);
+  const int nc = nc_out = coarse_numbering(cf, f2c);
   parallel_for(n, [&](int64_t b, int64_t e, int) {
     for (int64_t i = b; i < e; i++) {
       if (cf[(size_t)i] == C_PT) {
@@ -1393,14 +1274,10 @@ void build_one_point_interp(const HostCSR &D, const Strength &S, std::vector<int
         continue;
       }
       double best = -1.0;
-      int64_t ks = S.ia[(size_t)i];
-      const int64_t kse = S.ia[(size_t)i + 1];
-      for (int64_t k = D.ia[(size_t)i]; k < D.ia[(size_t)i + 1] && ks < kse; k++) {
-        const int j = D.ja[(size_t)k];
-        while (ks < kse && S.ja[(size_t)ks] < j) ks++;
-        if (ks < kse && S.ja[(size_t)ks] == j && cf[(size_t)j] == C_PT && std::fabs(D.a[(size_t)k]) > best)
+      for_each_strong_entry(D, S, i, [&](int64_t k, int j) {
+        if (cf[(size_t)j] == C_PT && std::fabs(D.a[(size_t)k]) > best)
           best = std::fabs(D.a[(size_t)k]), sel[(size_t)i] = f2c[(size_t)j];
-      }
+      });
     }
   });
   P.nrows = n;
@@ -1582,22 +1459,9 @@ long long BoomerAMG::effective_redundant_rows() const {
 void BoomerAMG::ensure_host(int level) {
   if (level < 0 || level >= (int)L.size()) return;
   AmgLevel &Lv = L[(size_t)level];
-  auto fetch = [&](ParCSR *M, sk::DCsr &dev) {
-    if (!M || !M->host_diag_stale) return;
-    hipStream_t s = ctx().stream;
-    const int nr = M->diag.nrows, ncl = M->diag.ncols;
-    if (dev.nrows == M->nrows && dev.ia.p)
-      dev.download(M->diag, s);
-    else
-      sk::solve_format_to_host(M->d_diag, M->diag, s);
-    M->diag.nrows = nr;
-    M->diag.ncols = ncl;
-    M->host_diag_stale = false;
-    M->ensure_offd_rows();
-  };
-  fetch(Lv.A, Lv.oA);
-  fetch(Lv.Pm.get(), Lv.oP);
-  fetch(Lv.Rm.get(), Lv.oR);
+  fetch_operator(Lv.A, Lv.oA);
+  fetch_operator(Lv.Pm.get(), Lv.oP);
+  fetch_operator(Lv.Rm.get(), Lv.oR);
 }
 
 int BoomerAMG::chunk() const { return p.gs_chunk > 0 ? p.gs_chunk : ctx().gs_chunk; }
@@ -1765,15 +1629,8 @@ void BoomerAMG::apply_cf_ordering() {
       }
     } level_timer{timing && l < 4, l, tl0};
     TraceRange trace_lv(("C-first: level " + std::to_string(l)).c_str());
-    if (!has_pos[l] && Lv.A->host_diag_stale && Lv.sA.nrows == Lv.A->nrows) {
-      // a level without C/F splitting (the coarsest) keeps its ordering: fetch it before sA goes away
-      const int nr = Lv.A->diag.nrows, ncl = Lv.A->diag.ncols;
-      Lv.sA.download(Lv.A->diag, ctx().stream);
-      Lv.A->diag.nrows = nr;
-      Lv.A->diag.ncols = ncl;
-      Lv.A->host_diag_stale = false;
-      Lv.A->ensure_offd_rows();
-    }
+    // a level without C/F splitting (the coarsest) keeps its ordering: fetch it before sA goes away
+    if (!has_pos[l] && Lv.sA.nrows == Lv.A->nrows) fetch_operator(Lv.A, Lv.sA);
     if (has_pos[l]) {
       ParCSR &A = *Lv.A;
       std::unique_ptr<ParCSR> An(new ParCSR());
@@ -2336,6 +2193,316 @@ void BoomerAMG::setup_host(ParCSR &A0) {
            t_phase[0], t_phase[1], t_phase[2], t_phase[3], t_phase[4], t_phase[5]);
 }
 
+// ---- the single-rank level build ("The level build") --------------------------------------------
+// which routine makes a level's P: resolved once per level, switched on by the device and by the host dispatch
+enum class InterpKind { classical, multipass, two_stage, mm_ext, one_point };
+static InterpKind interp_kind(bool aggressive, const AmgParams &p) {
+  // aggressive levels: multipass (agg_interp_type 4) or the two-stage extended interpolation (5; validate_settings)
+  if (aggressive) return p.agg_interp_type == 5 ? InterpKind::two_stage : InterpKind::multipass;
+  switch (p.interp_type) {
+    case 4: return InterpKind::multipass;  // on an ordinary splitting its first pass is all there is, unless F points
+                                           // lack a strong C point
+    case 16:
+    case 17: return InterpKind::mm_ext;  // the matrix-matrix extended interpolations
+    case 100: return InterpKind::one_point;
+    default: return InterpKind::classical;  // 0, 6 (sk::interp on a device level) and 3: build_interp
+  }
+}
+
+// A C/F marker of the level being built: on the host, on the device, or -- the same contents -- on both.  host() / dev()
+// copy across when only the other side holds it; a routine that rewrites the marker asks for its side alone.
+struct LevelMarker {
+  std::vector<int> h;
+  DVec<int> d;
+  bool host_ok = false, dev_ok = false;
+  std::vector<int> &fill_host() { return host_ok = true, dev_ok = false, h; }
+  DVec<int> &fill_dev() { return dev_ok = true, host_ok = false, d; }
+  std::vector<int> &host() {
+    if (!host_ok) h = d.to_host();
+    return host_ok = true, h;
+  }
+  DVec<int> &dev() {
+    if (!dev_ok) d.upload(h);
+    return dev_ok = true, d;
+  }
+  std::vector<int> &host_only() {
+    host();
+    d.release();
+    return dev_ok = false, h;
+  }
+  DVec<int> &dev_only() {
+    dev();
+    return host_ok = false, d;
+  }
+};
+
+// What build_natural knows about the level it is building: the strength graph and the marker(s) with the side that
+// holds them, where P and R ended up, and the clock of the phase accounting.
+struct LevelBuild {
+  const int l, n;
+  ParCSR &A;
+  AmgLevel &Lv;
+  const bool on_device, aggressive;
+  const InterpKind kind;
+  // aggressive coarsening and the Ruge-Stueben family are host algorithms: on a level the device builds, the strength
+  // graph still comes from the device and the Galerkin product stays there.  (With the two-stage interpolation and PMIS
+  // the aggressive level stays on the device: second graph, second PMIS, marker correction, the sparse products.)
+  const bool host_coarsen;
+  Strength S;  // the strength graph: the device builds dS and S is its copy, the host builds S alone
+  sk::DCsr dS;
+  bool S_on_host = false;
+  LevelMarker cf, cf1;  // cf1: the marker after the first coarsening of an aggressive level (two-stage interpolation)
+  bool p_on_device = false;
+  int nc = 0;
+  sk::DCsr dR_local, *dR = nullptr;  // the device's R for the Galerkin product (Lv.sR where it is kept)
+  double tp0 = 0.0;
+  std::unique_ptr<TraceRange> trace;
+
+  LevelBuild(int level, AmgLevel &lv, const AmgParams &p, long long device_min_rows)
+      : l(level), n(lv.A->nrows), A(*lv.A), Lv(lv), on_device(device_min_rows >= 0 && n >= device_min_rows),
+        aggressive(level < p.agg_num_levels), kind(interp_kind(aggressive, p)),
+        host_coarsen(!on_device || !(p.coarsen_type == 8 || p.coarsen_type == 9) ||
+                     (aggressive && kind != InterpKind::two_stage)) {}
+  void begin(const char *what) {
+    trace.reset(), trace.reset(new TraceRange(("level " + std::to_string(l) + ": " + what).c_str()));
+  }
+  double lap() {  // seconds since the last lap
+    const double t = wall_time(), dt = t - tp0;
+    return tp0 = t, dt;
+  }
+  const Strength &strength_to_host() {
+    if (!S_on_host) {
+      hipStream_t s = ctx().stream;
+      S.ia.resize((size_t)n + 1);
+      S.ja.resize((size_t)dS.nnz);
+      d2h(S.ia.data(), dS.ia.p, ((size_t)n + 1) * sizeof(int64_t), s);
+      if (dS.nnz) d2h(S.ja.data(), dS.ja.p, (size_t)dS.nnz * sizeof(int), s);
+      MI_HIP(hipStreamSynchronize(s));
+      S_on_host = true;
+    }
+    return S;
+  }
+  long long count_c_points() {
+    if (!cf.host_ok) {
+      DVec<long long> crank;
+      return sk::count_c_points(cf.d.p, n, crank, ctx().stream);
+    }
+    std::atomic<long long> acc{0};
+    parallel_for(n, [&](int64_t b, int64_t e, int) {
+      long long c = 0;
+      for (int64_t i = b; i < e; i++) c += (cf.h[(size_t)i] == C_PT);
+      acc += c;
+    });
+    return acc.load();
+  }
+};
+
+// the host arrays of an operator only the device holds (dev: its plain CSR copy, else the solve format is read back)
+void BoomerAMG::fetch_operator(ParCSR *M, sk::DCsr &dev) {
+  if (!M || !M->host_diag_stale) return;
+  hipStream_t s = ctx().stream;
+  const int nr = M->diag.nrows, ncl = M->diag.ncols;
+  if (dev.nrows == M->nrows && dev.ia.p)
+    dev.download(M->diag, s);
+  else
+    sk::solve_format_to_host(M->d_diag, M->diag, s);
+  M->diag.nrows = nr;
+  M->diag.ncols = ncl;
+  M->host_diag_stale = false;
+  M->ensure_offd_rows();
+}
+
+// step 1: the strength graph and the splitting; leaves the level's marker in b.cf (and b.cf1)
+void BoomerAMG::level_strength_and_coarsening(LevelBuild &b) {
+  if (b.on_device) {
+    // strength graph and PMIS splitting on the device (integer/compare work, identical results)
+    hipStream_t s = ctx().stream;
+    if (b.Lv.sA.nrows != b.n) b.Lv.sA.upload(b.A.diag, s);
+    sk::strength(b.Lv.sA, p.strong_threshold, p.max_row_sum, b.dS, s);
+  } else {
+    strength(b.A, p.strong_threshold, p.max_row_sum, b.S);
+    b.S_on_host = true;
+  }
+  t_phase[0] += b.lap();
+  const bool two_stage = b.kind == InterpKind::two_stage;
+  if (b.host_coarsen) {
+    const Strength &S = b.strength_to_host();
+    if (b.aggressive)
+      coarsen_aggressive(p.coarsen_type, b.n, S, b.cf.fill_host(), two_stage ? &b.cf1.fill_host() : nullptr);
+    else
+      coarsen_by_type(p.coarsen_type, b.n, S, b.cf.fill_host());
+    if (b.on_device) b.cf.dev();
+  } else {
+    hipStream_t s = ctx().stream;
+    sk::pmis(b.dS, 2747, b.cf.fill_dev(), s);  // (the marks stay on the device: LazyInts)
+    if (b.aggressive) {
+      b.cf1.fill_dev().alloc((size_t)b.n);
+      MI_HIP(hipMemcpyAsync(b.cf1.d.p, b.cf.d.p, (size_t)b.n * sizeof(int), hipMemcpyDeviceToDevice, s));
+      sk::aggressive_second_stage(b.dS, b.cf.d, 2747, s);
+    }
+  }
+  t_phase[1] += b.lap();
+}
+
+// step 2: P of the level by the routine of its kind, on the device where the level lives there; the final marker goes
+// to Lv.cf
+void BoomerAMG::level_interpolation(LevelBuild &b) {
+  AmgLevel &Lv = b.Lv;
+  ParCSR &A = b.A;
+  const int n = b.n;
+  if (b.kind == InterpKind::two_stage && p.keep_agg_markers) {
+    // (inspection, HYPRE_MI_BoomerAMGGetLevelAggMarkers: natural order, before the interpolation rewrites -3)
+    const std::vector<int> &h1 = b.cf1.host(), &h2 = b.cf.host();
+    Lv.agg_m1.assign(h1.begin(), h1.end());
+    Lv.agg_m2.assign(h2.begin(), h2.end());
+  }
+  int bad = -1;  // a row with a zero denominator (two_stage, mm_ext)
+  if (b.on_device) {
+    hipStream_t s = ctx().stream;
+    switch (b.kind) {
+      case InterpKind::classical:
+        if (p.interp_type == 6 || p.interp_type == 0) {  // (declines a row whose interpolatory set outgrows its tables)
+          b.p_on_device = sk::interp(Lv.sA, b.dS, b.cf.dev(), p.interp_type, p.trunc_factor, p.pmax_elmts, Lv.sP, b.nc, s,
+                                     &Lv.interp_census);
+          Lv.interp_by_host = false;
+        }
+        break;
+      case InterpKind::multipass: break;  // a host routine
+      case InterpKind::two_stage:  // (after a coarsening the host ran, too: the interpolation is the device's all the same)
+        bad = sk::two_stage_ext(Lv.sA, b.dS, b.cf1.dev(), b.cf.dev(), p.agg_p12_trunc_factor, p.agg_p12_max_elmts,
+                                p.agg_trunc_factor, p.agg_pmax_elmts, Lv.sP, b.nc, s);
+        b.cf1 = LevelMarker();  // (the first stage's marker has served)
+        b.p_on_device = true;
+        break;
+      case InterpKind::mm_ext:  // two operand builders and sk::spgemm: rows of any length stay on the device
+        bad = sk::mm_interp(Lv.sA, b.dS, b.cf.dev(), p.interp_type, p.trunc_factor, p.pmax_elmts, Lv.sP, b.nc, s);
+        b.p_on_device = true;
+        break;
+      case InterpKind::one_point:  // one row per lane: rows of any length stay on the device
+        sk::one_point_interp(Lv.sA, b.dS, b.cf.dev(), Lv.sP, b.nc, s);
+        b.p_on_device = true;
+        break;
+    }
+    if (b.p_on_device) {
+      // stays on the device; the dimensions are all the host needs
+      Lv.P = HostCSR();
+      Lv.P.nrows = n;
+      Lv.P.ncols = b.nc;
+    } else {
+      // the host routine runs on the host's copies of the operator, the graph and the marker
+      fetch_operator(&A, Lv.sA);
+      b.strength_to_host();
+      b.cf.host_only();
+    }
+    b.dS.release();
+  }
+  if (!b.p_on_device) {
+    std::vector<int> &cf = b.cf.host();
+    switch (b.kind) {
+      case InterpKind::classical: build_interp(A, b.S, cf, p.interp_type, p.trunc_factor, p.pmax_elmts, Lv.P, b.nc); break;
+      case InterpKind::multipass:
+        build_multipass(A, b.S, cf, b.aggressive ? p.agg_trunc_factor : p.trunc_factor,
+                        b.aggressive ? p.agg_pmax_elmts : p.pmax_elmts, Lv.P, b.nc);
+        break;
+      case InterpKind::two_stage:
+        bad = build_two_stage_ext(A, b.S, b.cf1.host(), cf, p.agg_p12_trunc_factor, p.agg_p12_max_elmts, p.agg_trunc_factor,
+                                  p.agg_pmax_elmts, Lv.P, b.nc);
+        break;
+      case InterpKind::mm_ext: bad = build_mm_interp(A, b.S, cf, p.interp_type, p.trunc_factor, p.pmax_elmts, Lv.P, b.nc); break;
+      case InterpKind::one_point: build_one_point_interp(A.diag, b.S, cf, Lv.P, b.nc); break;
+    }
+  }
+  if (bad >= 0 && b.kind == InterpKind::two_stage) two_stage_zero_denominator(b.l, bad);
+  if (bad >= 0) mm_interp_zero_denominator(p.interp_type, b.l, bad);
+  if (b.p_on_device)
+    Lv.cf.adopt_device(std::move(b.cf.dev_only()), (size_t)n);  // (interpolation has updated the marks there: -3 -> -1)
+  else
+    Lv.cf = std::move(b.cf.host_only());
+  Lv.has_cf = true;
+}
+
+// step 3: R where the Galerkin product reads it -- Lv.R on a host level, *b.dR on a device level.  The transpose of P,
+// or (restriction 1) the approximate ideal restriction, which the device leaves to the host routine when a
+// neighbourhood outgrows its 64-lane solve
+void BoomerAMG::level_restriction(LevelBuild &b) {
+  AmgLevel &Lv = b.Lv;
+  const bool air = p.restriction == 1;
+  Lv.restriction_kind = 0;
+  Lv.air_info = sk::AirInfo();
+  if (!b.on_device) {
+    if (air) {
+      build_air_restriction(b.A.diag, Lv.cf.host(), p.strong_threshold_r, p.filter_threshold_r, Lv.R, Lv.air_info);
+      Lv.restriction_kind = 2;
+    } else {
+      host_transpose(Lv.P, Lv.R);
+    }
+  } else {
+    hipStream_t s = ctx().stream;
+    if (!b.p_on_device) Lv.sP.upload(Lv.P, s);  // (a host routine's P: the transpose and the products read the device's copy)
+    // the replicated setup slices R on the device later; an approximate ideal restriction is renumbered, not rebuilt
+    b.dR = (keep_natural_R || air) ? &Lv.sR : &b.dR_local;
+    if (air) {
+      const int rc = sk::air_restriction(Lv.sA, Lv.cf.dev(), p.strong_threshold_r, p.filter_threshold_r, *b.dR, Lv.air_info, s);
+      Lv.restriction_kind = 1;
+      if (rc == 1) {
+        fetch_operator(&b.A, Lv.sA);
+        HostCSR Rh;
+        if (build_air_restriction(b.A.diag, Lv.cf.host(), p.strong_threshold_r, p.filter_threshold_r, Rh, Lv.air_info) < 0)
+          b.dR->upload(Rh, s);
+        Lv.restriction_kind = 2;
+      }
+    } else {
+      sk::transpose(Lv.sP, *b.dR, s);
+    }
+  }
+  if (Lv.air_info.bad_row >= 0) air_singular_system(b.l, Lv.air_info.bad_row);
+}
+
+// step 4: A_c = R (A P), its non-Galerkin sparsification, and the coarse level's entry in L
+void BoomerAMG::level_galerkin_and_adopt(LevelBuild &b) {
+  AmgLevel &Lv = b.Lv;
+  const int l = b.l, nc = b.nc;
+  std::unique_ptr<ParCSR> An(new ParCSR());
+  if (b.on_device) {
+    // same arithmetic, same order (setup_kernels.hip); the natural-order device copies stay for the
+    // C-first renumbering
+    hipStream_t s = ctx().stream;
+    sk::DCsr dAP;
+    sk::spgemm(Lv.sA, Lv.sP, dAP, s);
+    L.emplace_back();  // the coarse operator is born on the device (L was reserved: references stay valid)
+    sk::DCsr &dAc = L[(size_t)l + 1].sA;
+    sk::spgemm(*b.dR, dAP, dAc, s);
+    if (p.non_galerkin_tol_for(l) > 0.0) sk::sparsify_non_galerkin(dAc, p.non_galerkin_tol_for(l), s);
+    if (nc < device_min_rows) {
+      dAc.download(An->diag, s);  // the next level is built by the host routines
+    } else {
+      An->diag.nrows = An->diag.ncols = nc;
+      An->host_diag_stale = true;
+      An->dev_diag_nnz = dAc.nnz;
+    }
+    if (getenv("MI_HYPRE_SETUP_TIMING"))
+      printf("   level %d: n %d  device Galerkin %.2f s (nnz A %lld, P %lld, AP %lld, A_c %lld)\n", l, b.n, wall_time() - b.tp0,
+             (long long)Lv.sA.nnz, (long long)Lv.sP.nnz, (long long)dAP.nnz, (long long)dAc.nnz);
+  } else {
+    HostCSR AP;
+    host_spgemm(b.A.diag, Lv.P, AP);
+    host_spgemm(Lv.R, AP, An->diag);
+    if (p.non_galerkin_tol_for(l) > 0.0) sparsify_non_galerkin(An->diag, p.non_galerkin_tol_for(l));
+    L.emplace_back();
+  }
+  An->nrows = nc;
+  An->row_start = 0;
+  An->row_end = nc;
+  An->row_starts = {0, (gidx)nc};
+  An->offd.nrows = nc;
+  An->offd.ncols = 0;
+  if (!An->host_diag_stale) An->offd.ia.assign((size_t)nc + 1, 0);  // (device-resident: ParCSR::ensure_offd_rows)
+  An->build_halo_plan(my_comm());
+  t_phase[3] += b.lap();
+  L[(size_t)l + 1].A_own = std::move(An);
+  L[(size_t)l + 1].A = L[(size_t)l + 1].A_own.get();
+}
+
 // the coarsening loop in natural ordering (single communicator rank, or the
 // global operator in the replicated multi-rank setup)
 void BoomerAMG::build_natural(ParCSR &A0) {
@@ -2355,243 +2522,24 @@ void BoomerAMG::build_natural(ParCSR &A0) {
       stopped_by_rows = true;  // the caller continues from here with a redundant hierarchy
       break;
     }
-    ParCSR &A = *L[(size_t)l].A;
-    const int n = A.nrows;
-    AmgLevel &Lv = L[(size_t)l];
-    const bool on_device = device_min_rows >= 0 && n >= device_min_rows;
-    // aggressive coarsening (level < agg_num_levels) and the Ruge-Stueben family are host algorithms: on a level
-    // the device builds, the strength graph still comes from the device and the Galerkin product stays there
-    const bool aggressive = l < p.agg_num_levels;
-    // (with the two-stage interpolation, agg_interp_type 5, and PMIS the aggressive level stays on the device: second
-    // graph, second PMIS, marker correction and the interpolation's sparse products)
-    const bool two_stage = aggressive && p.agg_interp_type == 5;
-    // (interp_type 16 / 17: the matrix-matrix extended interpolation of the levels that are not aggressive)
-    const bool mm_interp = !aggressive && (p.interp_type == 16 || p.interp_type == 17);
-    // (interp_type 100: one-point interpolation; restriction 1: R is the approximate ideal restriction, not P^T)
-    const bool one_point = !aggressive && p.interp_type == 100;
-    const bool air = p.restriction == 1;
-    const bool pmis_type = p.coarsen_type == 8 || p.coarsen_type == 9;
-    const bool host_coarsen = (aggressive && !(two_stage && pmis_type)) || !pmis_type;
-    Strength S;
-    std::vector<int> cf, cf1;  // cf1: the marker after the first coarsening of an aggressive level (two-stage interpolation)
-    sk::DCsr dS;
-    DVec<int> dcf, dcf1;  // dcf1: the first coarsening's marker on the device (two-stage interpolation)
-    const std::string lname = "level " + std::to_string(l) + ": ";
-    std::unique_ptr<TraceRange> trace_level(new TraceRange((lname + "strength + coarsening").c_str()));
-    double tp0 = wall_time();
-    auto strength_to_host = [&](hipStream_t s) {
-      S.ia.resize((size_t)n + 1);
-      S.ja.resize((size_t)dS.nnz);
-      d2h(S.ia.data(), dS.ia.p, ((size_t)n + 1) * sizeof(int64_t), s);
-      if (dS.nnz) d2h(S.ja.data(), dS.ja.p, (size_t)dS.nnz * sizeof(int), s);
-      MI_HIP(hipStreamSynchronize(s));
-    };
-    if (on_device) {
-      // strength graph and PMIS splitting on the device (integer/compare work, identical results)
-      hipStream_t s = ctx().stream;
-      if (Lv.sA.nrows != n) Lv.sA.upload(A.diag, s);
-      sk::strength(Lv.sA, p.strong_threshold, p.max_row_sum, dS, s);
-      t_phase[0] += wall_time() - tp0;
-      tp0 = wall_time();
-      if (host_coarsen) {
-        strength_to_host(s);
-        if (aggressive)
-          coarsen_aggressive(p.coarsen_type, n, S, cf, two_stage ? &cf1 : nullptr);
-        else
-          coarsen_by_type(p.coarsen_type, n, S, cf);
-        dcf.upload(cf);
-      } else {
-        sk::pmis(dS, 2747, dcf, s);  // (the marks stay on the device: LazyInts)
-        if (aggressive) {
-          dcf1.alloc((size_t)n);
-          MI_HIP(hipMemcpyAsync(dcf1.p, dcf.p, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, s));
-          sk::aggressive_second_stage(dS, dcf, 2747, s);
-        }
-      }
-      t_phase[1] += wall_time() - tp0;
-    } else {
-      strength(A, p.strong_threshold, p.max_row_sum, S);
-      t_phase[0] += wall_time() - tp0;
-      tp0 = wall_time();
-      if (aggressive)
-        coarsen_aggressive(p.coarsen_type, n, S, cf, two_stage ? &cf1 : nullptr);
-      else
-        coarsen_by_type(p.coarsen_type, n, S, cf);
-      t_phase[1] += wall_time() - tp0;
-    }
-    long long nc_loc = 0;
-    if (on_device && cf.empty() && dcf.p) {
-      DVec<long long> crank;
-      nc_loc = sk::count_c_points(dcf.p, n, crank, ctx().stream);
-    } else {
-      std::atomic<long long> acc{0};
-      parallel_for(n, [&](int64_t b, int64_t e, int) {
-        long long c = 0;
-        for (int64_t i = b; i < e; i++) c += (cf[(size_t)i] == C_PT);
-        acc += c;
-      });
-      nc_loc = acc.load();
-    }
-    long long nc_glob = nc_loc;
+    LevelBuild b(l, L[(size_t)l], p, device_min_rows);
+    b.begin("strength + coarsening");
+    b.lap();
+    level_strength_and_coarsening(b);
+    long long nc_glob = b.count_c_points();
     comm.allreduce_host(&nc_glob, 1, CommDType::I64, CommOp::SUM);
-    if (nc_glob == 0 || nc_glob == A.global_rows() || nc_glob < p.min_coarse_size) break;
+    if (nc_glob == 0 || nc_glob == b.A.global_rows() || nc_glob < p.min_coarse_size) break;
 
-    int nc = 0;
-    tp0 = wall_time();
-    trace_level.reset(), trace_level.reset(new TraceRange((lname + "interpolation").c_str()));
-    bool p_on_device = false;
-    if (on_device) {
-      hipStream_t s = ctx().stream;
-      if (!aggressive && (p.interp_type == 6 || p.interp_type == 0)) {
-        p_on_device = sk::interp(Lv.sA, dS, dcf, p.interp_type, p.trunc_factor, p.pmax_elmts, Lv.sP, nc, s, &Lv.interp_census);
-        Lv.interp_by_host = false;
-      }
-      if (two_stage) {
-        if (!dcf1.p) dcf1.upload(cf1);  // (a coarsening the host ran: the interpolation is the device's all the same)
-        if (p.keep_agg_markers) {  // (inspection: both markers to the host before the interpolation rewrites -3)
-          const std::vector<int> h1 = dcf1.to_host(), h2 = dcf.to_host();
-          Lv.agg_m1.assign(h1.begin(), h1.end());
-          Lv.agg_m2.assign(h2.begin(), h2.end());
-        }
-        const int bad = sk::two_stage_ext(Lv.sA, dS, dcf1, dcf, p.agg_p12_trunc_factor, p.agg_p12_max_elmts,
-                                          p.agg_trunc_factor, p.agg_pmax_elmts, Lv.sP, nc, s);
-        if (bad >= 0) two_stage_zero_denominator(l, bad);
-        dcf1.release();
-        p_on_device = true;
-      }
-      if (mm_interp) {  // two operand builders and sk::spgemm: rows of any length stay on the device
-        const int bad = sk::mm_interp(Lv.sA, dS, dcf, p.interp_type, p.trunc_factor, p.pmax_elmts, Lv.sP, nc, s);
-        if (bad >= 0) mm_interp_zero_denominator(p.interp_type, l, bad);
-        p_on_device = true;
-      }
-      if (one_point) {  // one row per lane: rows of any length stay on the device
-        sk::one_point_interp(Lv.sA, dS, dcf, Lv.sP, nc, s);
-        p_on_device = true;
-      }
-      if (p_on_device) {
-        // stays on the device; the dimensions are all the host needs
-        Lv.P = HostCSR();
-        Lv.P.nrows = n;
-        Lv.P.ncols = nc;
-      } else {
-        // multipass or direct interpolation, or a row whose interpolatory set outgrows the kernels' tables:
-        // host routine
-        if (A.host_diag_stale) {
-          Lv.sA.download(A.diag, s);
-          A.host_diag_stale = false;
-          A.ensure_offd_rows();
-        }
-        if (!host_coarsen) strength_to_host(s);
-        if (cf.empty() && dcf.p) {
-          cf.resize((size_t)n);
-          d2h(cf.data(), dcf.p, (size_t)n * sizeof(int), nullptr);
-        }
-        dcf.release();
-      }
-      dS.release();
-    }
-    if (!p_on_device) {
-      if (two_stage) {
-        if (p.keep_agg_markers) {  // (inspection, HYPRE_MI_BoomerAMGGetLevelAggMarkers: natural order)
-          Lv.agg_m1.assign(cf1.begin(), cf1.end());
-          Lv.agg_m2.assign(cf.begin(), cf.end());
-        }
-        build_two_stage_ext(A, S, cf1, cf, p.agg_p12_trunc_factor, p.agg_p12_max_elmts, p.agg_trunc_factor,
-                            p.agg_pmax_elmts, l, Lv.P, nc);
-      } else if (aggressive)
-        build_multipass(A, S, cf, p.agg_trunc_factor, p.agg_pmax_elmts, Lv.P, nc);
-      else if (mm_interp)
-        build_mm_interp(A, S, cf, p.interp_type, p.trunc_factor, p.pmax_elmts, l, Lv.P, nc);
-      else if (one_point)
-        build_one_point_interp(A.diag, S, cf, Lv.P, nc);
-      else if (p.interp_type == 4)  // multipass interpolation on an ordinary splitting (its first pass is all there is
-        build_multipass(A, S, cf, p.trunc_factor, p.pmax_elmts, Lv.P, nc);  // unless F points lack a strong C point)
-      else
-        build_interp(A, S, cf, p.interp_type, p.trunc_factor, p.pmax_elmts, Lv.P, nc);
-    }
-    if (p_on_device)
-      Lv.cf.adopt_device(std::move(dcf), (size_t)n);  // (interpolation has updated the marks there: -3 -> -1)
-    else
-      Lv.cf = cf;
-    Lv.has_cf = true;
-    Lv.restriction_kind = 0;
-    Lv.air_info = sk::AirInfo();
-    if (!on_device && air) {
-      if (build_air_restriction(A.diag, cf, p.strong_threshold_r, p.filter_threshold_r, Lv.R, Lv.air_info) >= 0)
-        air_singular_system(l, Lv.air_info.bad_row);
-      Lv.restriction_kind = 2;
-    } else if (!on_device) {
-      host_transpose(Lv.P, Lv.R);
-    }
-    t_phase[2] += wall_time() - tp0;
-    tp0 = wall_time();
-    trace_level.reset(), trace_level.reset(new TraceRange((lname + "Galerkin product").c_str()));
-
-    // Galerkin product on the (single-rank) operator: A_c = R (A P)
-    std::unique_ptr<ParCSR> An(new ParCSR());
-    if (on_device) {
-      // same arithmetic, same order (setup_kernels.hip); the natural-order device copies stay for the
-      // C-first renumbering
-      hipStream_t s = ctx().stream;
-      if (!p_on_device) Lv.sP.upload(Lv.P, s);
-      sk::DCsr dR_local, dAP;
-      // the replicated setup slices R on the device later; an approximate ideal restriction is renumbered, not rebuilt
-      sk::DCsr &dR = (keep_natural_R || air) ? Lv.sR : dR_local;
-      if (air) {
-        const int rc = sk::air_restriction(Lv.sA, Lv.cf.dev(), p.strong_threshold_r, p.filter_threshold_r, dR, Lv.air_info, s);
-        Lv.restriction_kind = 1;
-        if (rc == 1) {  // a neighbourhood outgrows the 64-lane solve: the host routine builds this level's R
-          if (A.host_diag_stale) {
-            Lv.sA.download(A.diag, s);
-            A.host_diag_stale = false;
-            A.ensure_offd_rows();
-          }
-          HostCSR Rh;
-          if (build_air_restriction(A.diag, Lv.cf.host(), p.strong_threshold_r, p.filter_threshold_r, Rh, Lv.air_info) < 0)
-            dR.upload(Rh, s);
-          Lv.restriction_kind = 2;
-        }
-        if (Lv.air_info.bad_row >= 0) air_singular_system(l, Lv.air_info.bad_row);
-      } else {
-        sk::transpose(Lv.sP, dR, s);
-      }
-      sk::spgemm(Lv.sA, Lv.sP, dAP, s);
-      L.emplace_back();  // the coarse operator is born on the device (L was reserved: references stay valid)
-      sk::DCsr &dAc = L[(size_t)l + 1].sA;
-      sk::spgemm(dR, dAP, dAc, s);
-      if (p.non_galerkin_tol_for(l) > 0.0) sk::sparsify_non_galerkin(dAc, p.non_galerkin_tol_for(l), s);
-      if (nc < device_min_rows) {
-        dAc.download(An->diag, s);  // the next level is built by the host routines
-      } else {
-        An->diag.nrows = An->diag.ncols = nc;
-        An->host_diag_stale = true;
-        An->dev_diag_nnz = dAc.nnz;
-      }
-      if (getenv("MI_HYPRE_SETUP_TIMING"))
-        printf("   level %d: n %d  device Galerkin %.2f s (nnz A %lld, P %lld, AP %lld, A_c %lld)\n", l, n, wall_time() - tp0,
-               (long long)Lv.sA.nnz, (long long)Lv.sP.nnz, (long long)dAP.nnz, (long long)dAc.nnz);
-    } else {
-      HostCSR AP;
-      host_spgemm(A.diag, Lv.P, AP);
-      host_spgemm(Lv.R, AP, An->diag);
-      if (p.non_galerkin_tol_for(l) > 0.0) sparsify_non_galerkin(An->diag, p.non_galerkin_tol_for(l));
-      L.emplace_back();
-    }
-    An->nrows = nc;
-    An->row_start = 0;
-    An->row_end = nc;
-    An->row_starts = {0, (gidx)nc};
-    An->offd.nrows = nc;
-    An->offd.ncols = 0;
-    if (!An->host_diag_stale) An->offd.ia.assign((size_t)nc + 1, 0);  // (device-resident: ParCSR::ensure_offd_rows)
-    An->build_halo_plan(comm);
-    t_phase[3] += wall_time() - tp0;
-    L[(size_t)l + 1].A_own = std::move(An);
-    L[(size_t)l + 1].A = L[(size_t)l + 1].A_own.get();
-    trace_level.reset();
+    b.begin("interpolation");
+    b.lap();
+    level_interpolation(b);
+    if (!b.on_device) level_restriction(b);  // a host level's R is charged to the interpolation phase,
+    t_phase[2] += b.lap();
+    b.begin("Galerkin product");
+    if (b.on_device) level_restriction(b);  // a device level's to the Galerkin phase, beside the products that read it
+    level_galerkin_and_adopt(b);
     l++;
   }
-
 }
 
 // l1 norms and the coarsest-level dense inverse, on the finished (C-first ordered, per-rank) levels
@@ -3039,14 +2987,7 @@ void BoomerAMG::build_replicated(ParCSR &A0) {
     MI_REQUIRE(tail_A != nullptr, "replicated setup: the redundant level was not kept");
     // levels nlev-1 .. : one single-rank hierarchy per rank, built by the ordinary pipeline on the
     // (global, natural-order) operator of the first redundant level
-    if (tail_A->host_diag_stale) {
-      const int nr = tail_A->diag.nrows, ncl = tail_A->diag.ncols;
-      g.L.back().sA.download(tail_A->diag, ctx().stream);
-      tail_A->diag.nrows = nr;
-      tail_A->diag.ncols = ncl;
-      tail_A->host_diag_stale = false;
-      tail_A->ensure_offd_rows();
-    }
+    fetch_operator(tail_A.get(), g.L.back().sA);
     g.L.back().sA.release();
     tail.reset(new BoomerAMG());
     tail->p = p;

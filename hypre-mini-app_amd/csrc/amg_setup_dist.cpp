@@ -1343,7 +1343,6 @@ void dist_multipass(Comm &comm, const std::vector<gidx> &starts, const GlobCSR &
       hpool_c.push_back(cgid_h[(size_t)q]);
       hpool_v.push_back(1.0);
     }
-  const int nt = host_threads();
   std::vector<int> list;
   for (int pass = 1;; pass++) {
     list.clear();
@@ -1362,16 +1361,11 @@ void dist_multipass(Comm &comm, const std::vector<gidx> &starts, const GlobCSR &
     long long nl_glob = nl;
     comm.allreduce_host(&nl_glob, 1, CommDType::I64, CommOp::SUM);
     if (nl_glob == 0) break;  // the rest cannot be reached along strong connections
-    std::vector<std::vector<gidx>> tc((size_t)nt);
-    std::vector<std::vector<double>> tv((size_t)nt);
-    std::vector<int> newlen((size_t)nl, 0);
-    std::vector<int64_t> tbeg((size_t)nt, 0);
-    std::vector<char> used((size_t)nt, 0);
+    RowCollector<gidx> rows(nl);
     parallel_for(nl, [&](int64_t b, int64_t e, int t) {
-      used[(size_t)t] = 1;
-      tbeg[(size_t)t] = b;
-      std::vector<gidx> &oc = tc[(size_t)t];
-      std::vector<double> &ov = tv[(size_t)t];
+      auto &out = rows.begin(t, b);
+      std::vector<gidx> &oc = out.j;
+      std::vector<double> &ov = out.a;
       std::vector<std::pair<gidx, int>> seen;  // coarse id -> position in the row (rows are short: sorted insert)
       for (int64_t q = b; q < e; q++) {
         const int i = list[(size_t)q];
@@ -1415,25 +1409,17 @@ void dist_multipass(Comm &comm, const std::vector<gidx> &starts, const GlobCSR &
         const double alfa = (sum_J * diagonal != 0.0) ? -sum_N / (sum_J * diagonal) : 0.0;
         const int len = (int)(oc.size() - base);
         for (int w = 0; w < len; w++) ov[base + (size_t)w] *= alfa;
-        newlen[(size_t)q] = len;
+        rows.len[(size_t)q] = len;
       }
     });
     // append the pass's rows to the pool (list order) -- only now do its points count as reached
-    int64_t at = (int64_t)pool_c.size();
+    std::vector<int64_t> at(1, (int64_t)pool_c.size());
+    rows.assemble(at, pool_c, &pool_v);
     for (int64_t q = 0; q < nl; q++) {
-      rstart[(size_t)list[(size_t)q]] = at;
-      rlen[(size_t)list[(size_t)q]] = newlen[(size_t)q];
-      at += newlen[(size_t)q];
+      rstart[(size_t)list[(size_t)q]] = at[(size_t)q];
+      rlen[(size_t)list[(size_t)q]] = rows.len[(size_t)q];
+      assigned[(size_t)list[(size_t)q]] = pass;
     }
-    pool_c.resize((size_t)at);
-    pool_v.resize((size_t)at);
-    for (int t = 0; t < nt; t++)
-      if (used[(size_t)t] && !tc[(size_t)t].empty()) {
-        const int64_t off = rstart[(size_t)list[(size_t)tbeg[(size_t)t]]];
-        memcpy(pool_c.data() + off, tc[(size_t)t].data(), tc[(size_t)t].size() * sizeof(gidx));
-        memcpy(pool_v.data() + off, tv[(size_t)t].data(), tv[(size_t)t].size() * sizeof(double));
-      }
-    for (int64_t q = 0; q < nl; q++) assigned[(size_t)list[(size_t)q]] = pass;
     // the halo points reached in this pass, with their rows
     assigned_h = ring.forward(comm, assigned);
     const std::vector<std::vector<char>> rec = ring.forward_records(comm, [&](int row, std::vector<char> &buf) {

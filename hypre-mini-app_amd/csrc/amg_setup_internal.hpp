@@ -3,6 +3,7 @@
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 
 #include "amg.hpp"
 
@@ -50,6 +51,72 @@ inline StrengthRule strength_rule(const double *a, int64_t len, int64_t dpos, do
   r.thr = theta * scale;
   return r;
 }
+
+// ---- three idioms of the host builders, stated once --------------------------------------------------------------
+// coarse numbering: f2c[i] = the rank of C point i among the C points of the marker, -1 elsewhere; returns their number
+inline int coarse_numbering(const std::vector<int> &marker, std::vector<int> &f2c) {
+  f2c.assign(marker.size(), -1);
+  int nc = 0;
+  for (size_t i = 0; i < marker.size(); i++)
+    if (marker[i] == C_PT) f2c[i] = nc++;
+  return nc;
+}
+
+// Row i of D against S_i, which is a subsequence of the row's ascending columns: f(q, j, strong) for every stored entry
+// q with column j, in stored order (the diagonal and the weak entries come with strong = false)
+template <class F>
+inline void for_each_entry_strong(const HostCSR &D, const Strength &S, int64_t i, F &&f) {
+  int64_t ks = S.ia[(size_t)i];
+  const int64_t kse = S.ia[(size_t)i + 1];
+  for (int64_t q = D.ia[(size_t)i]; q < D.ia[(size_t)i + 1]; q++) {
+    const int j = D.ja[(size_t)q];
+    while (ks < kse && S.ja[(size_t)ks] < j) ks++;
+    f(q, j, ks < kse && S.ja[(size_t)ks] == j);
+  }
+}
+// the strong entries alone, f(q, j): the walk ends with S_i
+template <class F>
+inline void for_each_strong_entry(const HostCSR &D, const Strength &S, int64_t i, F &&f) {
+  int64_t ks = S.ia[(size_t)i];
+  const int64_t kse = S.ia[(size_t)i + 1];
+  for (int64_t q = D.ia[(size_t)i]; q < D.ia[(size_t)i + 1] && ks < kse; q++) {
+    const int j = D.ja[(size_t)q];
+    while (ks < kse && S.ja[(size_t)ks] < j) ks++;
+    if (ks < kse && S.ja[(size_t)ks] == j) f(q, j);
+  }
+}
+
+// Rows that a parallel_for builds, collected per thread: a thread takes its part with begin(t, b), appends the entries of
+// its rows [b, e) in row order to part.j (and part.a) and notes each row's length in len; assemble() lays the rows out by
+// a prefix sum and one block copy per thread.  Col: int, or gidx in the distributed setup.
+template <class Col>
+struct RowCollector {
+  struct Part {
+    std::vector<Col> j;
+    std::vector<double> a;
+    int64_t first = -1;  // the thread's first row
+  };
+  std::vector<Part> part;
+  std::vector<int> len;
+  explicit RowCollector(int64_t nrows) : part((size_t)host_threads()), len((size_t)nrows, 0) {}
+  Part &begin(int t, int64_t first_row) {
+    part[(size_t)t].first = first_row;
+    return part[(size_t)t];
+  }
+  // ia[0] is the caller's: 0, or the end of what ja (and a) hold already -- the rows are appended there
+  void assemble(std::vector<int64_t> &ia, std::vector<Col> &ja, std::vector<double> *a = nullptr) const {
+    const size_t n = len.size();
+    ia.resize(n + 1);
+    for (size_t i = 0; i < n; i++) ia[i + 1] = ia[i] + len[i];
+    ja.resize((size_t)ia[n]);
+    if (a) a->resize((size_t)ia[n]);
+    for (const Part &p : part) {
+      if (p.first < 0 || p.j.empty()) continue;
+      memcpy(ja.data() + ia[(size_t)p.first], p.j.data(), p.j.size() * sizeof(Col));
+      if (a) memcpy(a->data() + ia[(size_t)p.first], p.a.data(), p.a.size() * sizeof(double));
+    }
+  }
+};
 
 // interpolation rows of the single-rank operator A (diag block).  want_rows (optional): rows with a zero flag
 // are left empty and the special-F markers of cf are kept (the caller owns them)

@@ -15,6 +15,7 @@
 #include "profile.hpp"
 #include "solvers.hpp"
 #include "amg_setup_internal.hpp"
+#include "capi_marshal.hpp"
 
 using namespace mi;
 
@@ -697,39 +698,21 @@ HYPRE_Int HYPRE_MI_CSRReuseOp(HYPRE_Int op, HYPRE_Int a_nrows, HYPRE_Int a_ncols
                               HYPRE_Int lanes, HYPRE_Int c_nrows, HYPRE_Int c_ncols, const HYPRE_BigInt *c_ia,
                               const HYPRE_Int *c_ja, HYPRE_Complex *c_a, HYPRE_Int *bad_row) {
   API_BEGIN
-  if (!a_ia || !c_ia || !c_a || !bad_row) fail(HYPRE_ERROR_ARG, "CSRReuseOp: NULL argument");
-  if (lanes < 0 || lanes > 64 || (lanes & (lanes - 1))) fail(HYPRE_ERROR_ARG, "CSRReuseOp: lanes must be 0 or a power of two up to 64");
+  const std::string who = "CSRReuseOp";
+  if (!a_ia || !c_ia || !c_a || !bad_row) fail(HYPRE_ERROR_ARG, who + ": NULL argument");
+  check_lanes(who, lanes);
   ensure_init();
   hipStream_t s = ctx().stream;
-  auto to_host = [](const char *what, HYPRE_Int nr, HYPRE_Int nc, const HYPRE_BigInt *ia, const HYPRE_Int *ja, const HYPRE_Complex *a) {
-    HostCSR h;
-    if (nr < 0 || nc < 0 || ia[0] != 0) fail(HYPRE_ERROR_ARG, std::string("CSRReuseOp: bad dimensions of ") + what);
-    h.nrows = nr;
-    h.ncols = nc;
-    h.ia.assign(ia, ia + nr + 1);
-    for (HYPRE_Int i = 0; i < nr; i++)
-      if (ia[i + 1] < ia[i]) fail(HYPRE_ERROR_ARG, std::string("CSRReuseOp: row pointers of ") + what + " decrease");
-    h.ja.assign(ja, ja + ia[nr]);
-    for (HYPRE_Int i = 0; i < nr; i++)
-      for (HYPRE_BigInt k = ia[i]; k < ia[i + 1]; k++)
-        if (ja[k] < 0 || ja[k] >= nc || (k > ia[i] && ja[k] <= ja[k - 1]))
-          fail(HYPRE_ERROR_ARG, std::string("CSRReuseOp: columns of ") + what + " out of range or not ascending");
-    if (a)
-      h.a.assign(a, a + ia[nr]);
-    else
-      h.a.assign((size_t)ia[nr], 0.0);
-    return h;
-  };
   sk::DCsr dA, dC;
-  dA.upload(to_host("A", a_nrows, a_ncols, a_ia, a_ja, a_a), s);
-  dC.upload(to_host("C", c_nrows, c_ncols, c_ia, c_ja, nullptr), s);
+  dA.upload(csr_of(who, "A", a_nrows, a_ncols, a_ia, a_ja, a_a), s);
+  dC.upload(csr_of(who, "C", c_nrows, c_ncols, c_ia, c_ja, nullptr), s);
   int bad = -1;
   if (op == 0) {
     if (!b_ia) fail(HYPRE_ERROR_ARG, "CSRReuseOp: the product needs P");
     if (a_ncols != b_nrows || a_nrows != b_nrows || c_nrows != b_ncols || c_ncols != b_ncols)
       fail(HYPRE_ERROR_ARG, "CSRReuseOp: the dimensions of A, P and C do not fit");
     sk::DCsr dP, dR;
-    dP.upload(to_host("P", b_nrows, b_ncols, b_ia, b_ja, b_a), s);
+    dP.upload(csr_of(who, "P", b_nrows, b_ncols, b_ia, b_ja, b_a), s);
     sk::transpose(dP, dR, s);
     bad = sk::galerkin_values(sk::ref_of(dA), sk::ref_of(dP), sk::ref_of(dR), nullptr, sk::ref_of(dC), dC.a.p, lanes, s);
   } else if (op == 1) {
@@ -759,33 +742,14 @@ HYPRE_Int HYPRE_MI_MMInterpOp(HYPRE_Int type, HYPRE_Int n, const HYPRE_BigInt *a
                               HYPRE_Real trunc_factor, HYPRE_Int pmax, HYPRE_Int lanes, HYPRE_Int *p_ncols,
                               HYPRE_BigInt **p_ia, HYPRE_Int **p_ja, HYPRE_Complex **p_a, HYPRE_Int *bad_row) {
   API_BEGIN
-  if (!a_ia || !s_ia || !p_ncols || !p_ia || !p_ja || !p_a || !bad_row) fail(HYPRE_ERROR_ARG, "MMInterpOp: NULL argument");
-  if (type != 16 && type != 17) fail(HYPRE_ERROR_ARG, "MMInterpOp: type must be 16 (extended) or 17 (extended+i)");
-  if (lanes < 0 || lanes > 64 || (lanes & (lanes - 1))) fail(HYPRE_ERROR_ARG, "MMInterpOp: lanes must be 0 or a power of two up to 64");
-  if (n < 0 || a_ia[0] != 0 || s_ia[0] != 0) fail(HYPRE_ERROR_ARG, "MMInterpOp: bad dimensions");
-  if (n > 0 && !cf) fail(HYPRE_ERROR_ARG, "MMInterpOp: NULL marker");
-  auto to_host = [n](const char *what, const HYPRE_BigInt *ia, const HYPRE_Int *ja, const HYPRE_Complex *a) {
-    HostCSR h;
-    h.nrows = h.ncols = n;
-    h.ia.assign(ia, ia + n + 1);
-    for (HYPRE_Int i = 0; i < n; i++)
-      if (ia[i + 1] < ia[i]) fail(HYPRE_ERROR_ARG, std::string("MMInterpOp: row pointers of ") + what + " decrease");
-    if (ia[n] > 0 && !ja) fail(HYPRE_ERROR_ARG, std::string("MMInterpOp: NULL columns of ") + what);
-    h.ja.assign(ja, ja + ia[n]);
-    for (HYPRE_Int i = 0; i < n; i++)
-      for (HYPRE_BigInt k = ia[i]; k < ia[i + 1]; k++)
-        if (ja[k] < 0 || ja[k] >= n || (k > ia[i] && ja[k] <= ja[k - 1]))
-          fail(HYPRE_ERROR_ARG, std::string("MMInterpOp: columns of ") + what + " out of range or not ascending");
-    if (a)
-      h.a.assign(a, a + ia[n]);
-    else
-      h.a.assign((size_t)ia[n], 0.0);
-    return h;
-  };
-  if (a_ia[n] > 0 && !a_a) fail(HYPRE_ERROR_ARG, "MMInterpOp: NULL values of A");
-  for (HYPRE_Int i = 0; i < n; i++)
-    if (cf[i] != 1 && cf[i] != -1 && cf[i] != -3) fail(HYPRE_ERROR_ARG, "MMInterpOp: the marker holds a value other than 1, -1, -3");
-  const HostCSR hA = to_host("A", a_ia, a_ja, a_a), hS = to_host("S", s_ia, s_ja, nullptr);
+  const std::string who = "MMInterpOp";
+  if (!a_ia || !s_ia || !p_ncols || !p_ia || !p_ja || !p_a || !bad_row) fail(HYPRE_ERROR_ARG, who + ": NULL argument");
+  if (type != 16 && type != 17) fail(HYPRE_ERROR_ARG, who + ": type must be 16 (extended) or 17 (extended+i)");
+  check_lanes(who, lanes);
+  if (n < 0 || a_ia[0] != 0 || s_ia[0] != 0) fail(HYPRE_ERROR_ARG, who + ": bad dimensions");
+  if (a_ia[n] > 0 && !a_a) fail(HYPRE_ERROR_ARG, who + ": NULL values of A");
+  check_marker(who, cf, n, true);
+  const HostCSR hA = csr_of(who, "A", n, n, a_ia, a_ja, a_a), hS = csr_of(who, "S", n, n, s_ia, s_ja, nullptr);
   ensure_init();
   hipStream_t s = ctx().stream;
   sk::DCsr dA, dS, dP;
@@ -797,58 +761,14 @@ HYPRE_Int HYPRE_MI_MMInterpOp(HYPRE_Int type, HYPRE_Int n, const HYPRE_BigInt *a
   const int bad = sk::mm_interp(dA, dS, dcf, type, trunc_factor, pmax, dP, nc, s, lanes);
   *bad_row = bad;
   if (bad >= 0)
-    fail(HYPRE_ERROR_ARG, "MMInterpOp: interp_type " + std::to_string(type) + ": row " + std::to_string(bad) +
+    fail(HYPRE_ERROR_ARG, who + ": interp_type " + std::to_string(type) + ": row " + std::to_string(bad) +
                               " has a zero denominator d_i with a non-empty numerator");
   HostCSR hp;
   if (n > 0) dP.download(hp, s);
   *p_ncols = nc;
-  *p_ia = (HYPRE_BigInt *)malloc(sizeof(HYPRE_BigInt) * ((size_t)n + 1));
-  *p_ja = (HYPRE_Int *)malloc(sizeof(HYPRE_Int) * std::max<size_t>(1, hp.ja.size()));
-  *p_a = (HYPRE_Complex *)malloc(sizeof(HYPRE_Complex) * std::max<size_t>(1, hp.a.size()));
-  (*p_ia)[0] = 0;
-  for (int i = 1; i <= n; i++) (*p_ia)[i] = hp.ia[(size_t)i];
-  if (!hp.ja.empty()) {
-    memcpy(*p_ja, hp.ja.data(), hp.ja.size() * sizeof(int));
-    memcpy(*p_a, hp.a.data(), hp.a.size() * sizeof(double));
-  }
+  csr_to_caller(hp, n, p_ia, p_ja, p_a);
   API_END
 }
-extern "C++" {
-namespace {
-// caller arrays of an n x n CSR with ascending columns, checked (a == null: a pattern, values 0)
-HostCSR square_csr_of(const std::string &who, const char *what, HYPRE_Int n, const HYPRE_BigInt *ia, const HYPRE_Int *ja,
-                      const HYPRE_Complex *a) {
-  HostCSR h;
-  h.nrows = h.ncols = n;
-  h.ia.assign(ia, ia + n + 1);
-  for (HYPRE_Int i = 0; i < n; i++)
-    if (ia[i + 1] < ia[i]) fail(HYPRE_ERROR_ARG, who + ": row pointers of " + what + " decrease");
-  if (ia[n] > 0 && !ja) fail(HYPRE_ERROR_ARG, who + ": NULL columns of " + what);
-  h.ja.assign(ja, ja + ia[n]);
-  for (HYPRE_Int i = 0; i < n; i++)
-    for (HYPRE_BigInt k = ia[i]; k < ia[i + 1]; k++)
-      if (ja[k] < 0 || ja[k] >= n || (k > ia[i] && ja[k] <= ja[k - 1]))
-        fail(HYPRE_ERROR_ARG, who + ": columns of " + what + " out of range or not ascending");
-  if (a)
-    h.a.assign(a, a + ia[n]);
-  else
-    h.a.assign((size_t)ia[n], 0.0);
-  return h;
-}
-// a HostCSR as malloc'ed caller arrays (HYPRE_MI_Free)
-void csr_to_caller(const HostCSR &h, int nrows, HYPRE_BigInt **ia, HYPRE_Int **ja, HYPRE_Complex **a) {
-  *ia = (HYPRE_BigInt *)malloc(sizeof(HYPRE_BigInt) * ((size_t)nrows + 1));
-  *ja = (HYPRE_Int *)malloc(sizeof(HYPRE_Int) * std::max<size_t>(1, h.ja.size()));
-  *a = (HYPRE_Complex *)malloc(sizeof(HYPRE_Complex) * std::max<size_t>(1, h.a.size()));
-  (*ia)[0] = 0;
-  for (int i = 1; i <= nrows; i++) (*ia)[i] = h.ia[(size_t)i];
-  if (!h.ja.empty()) {
-    memcpy(*ja, h.ja.data(), h.ja.size() * sizeof(int));
-    memcpy(*a, h.a.data(), h.a.size() * sizeof(double));
-  }
-}
-}  // namespace
-}  // extern "C++"
 // The approximate ideal restriction (restriction 1) on caller (host) arrays: the device routine sk::air_restriction
 // (on_host = 0) or the host routine hs::build_air_restriction (on_host = 1, no device needed).  info[8]: status (0 built,
 // 1 not built -- a neighbourhood above 64 entries, the device routine only --, 2 singular local system), the largest
@@ -864,13 +784,9 @@ HYPRE_Int HYPRE_MI_AIRRestrictionOp(HYPRE_Int on_host, HYPRE_Int n, const HYPRE_
   if (n < 1 || a_ia[0] != 0) fail(HYPRE_ERROR_ARG, who + ": bad dimensions");
   if (a_ia[n] > 0 && !a_a) fail(HYPRE_ERROR_ARG, who + ": NULL values of A");
   if (!(strong_threshold_r >= 0.0) || !(filter_threshold_r >= 0.0)) fail(HYPRE_ERROR_ARG, who + ": thresholds must be >= 0");
-  int nc = 0;
-  for (HYPRE_Int i = 0; i < n; i++) {
-    if (cf[i] != 1 && cf[i] != -1) fail(HYPRE_ERROR_ARG, who + ": the marker holds a value other than 1, -1");
-    nc += cf[i] == 1;
-  }
+  const int nc = check_marker(who, cf, n, false);
   if (nc == 0) fail(HYPRE_ERROR_ARG, who + ": the marker has no C point");
-  const HostCSR hA = square_csr_of(who, "A", n, a_ia, a_ja, a_a);
+  const HostCSR hA = csr_of(who, "A", n, n, a_ia, a_ja, a_a);
   *r_nrows = nc;
   *r_ia = nullptr, *r_ja = nullptr, *r_a = nullptr;
   sk::AirInfo ai;
@@ -914,7 +830,7 @@ HYPRE_Int HYPRE_MI_FSAIAdaptiveOp(HYPRE_Int on_host, HYPRE_Int n, const HYPRE_Bi
   if (table_slots < 0 || (table_slots & (table_slots - 1)) != 0)
     fail(HYPRE_ERROR_ARG, who + ": table_slots must be 0 or a power of two");
   FsaiSolver::check_adaptive(who, max_steps, max_step_size, kap_tolerance);
-  const HostCSR hB = square_csr_of(who, "B", n, b_ia, b_ja, b_a);
+  const HostCSR hB = csr_of(who, "B", n, n, b_ia, b_ja, b_a);
   *g_ia = nullptr, *g_ja = nullptr, *g_a = nullptr;
   sk::FsaiAdaptiveInfo ai;
   HostCSR hg;
@@ -948,9 +864,8 @@ HYPRE_Int HYPRE_MI_OnePointInterpOp(HYPRE_Int on_host, HYPRE_Int n, const HYPRE_
   if (!a_ia || !s_ia || !cf || !p_ncols || !p_ia || !p_ja || !p_a) fail(HYPRE_ERROR_ARG, who + ": NULL argument");
   if (n < 1 || a_ia[0] != 0 || s_ia[0] != 0) fail(HYPRE_ERROR_ARG, who + ": bad dimensions");
   if (a_ia[n] > 0 && !a_a) fail(HYPRE_ERROR_ARG, who + ": NULL values of A");
-  for (HYPRE_Int i = 0; i < n; i++)
-    if (cf[i] != 1 && cf[i] != -1 && cf[i] != -3) fail(HYPRE_ERROR_ARG, who + ": the marker holds a value other than 1, -1, -3");
-  const HostCSR hA = square_csr_of(who, "A", n, a_ia, a_ja, a_a), hS = square_csr_of(who, "S", n, s_ia, s_ja, nullptr);
+  check_marker(who, cf, n, true);
+  const HostCSR hA = csr_of(who, "A", n, n, a_ia, a_ja, a_a), hS = csr_of(who, "S", n, n, s_ia, s_ja, nullptr);
   HostCSR hp;
   int nc = 0;
   if (on_host) {
@@ -981,23 +896,17 @@ HYPRE_Int HYPRE_MI_CSRDeviceOp(HYPRE_Int op, HYPRE_Int a_nrows, HYPRE_Int a_ncol
                                const HYPRE_Int *perm, const HYPRE_Int *colpos, HYPRE_Int *c_nrows, HYPRE_Int *c_ncols,
                                HYPRE_BigInt **c_ia, HYPRE_Int **c_ja, HYPRE_Complex **c_a) {
   API_BEGIN
+  const std::string who = "CSRDeviceOp";
+  if (!a_ia || !c_nrows || !c_ncols || !c_ia || !c_ja || !c_a) fail(HYPRE_ERROR_ARG, who + ": NULL argument");
+  const HostCSR hA = csr_of(who, "A", a_nrows, a_ncols, a_ia, a_ja, a_a);
   ensure_init();
   hipStream_t s = ctx().stream;
-  auto to_host = [](HYPRE_Int nr, HYPRE_Int nc, const HYPRE_BigInt *ia, const HYPRE_Int *ja, const HYPRE_Complex *a) {
-    HostCSR h;
-    h.nrows = nr;
-    h.ncols = nc;
-    h.ia.assign(ia, ia + nr + 1);
-    h.ja.assign(ja, ja + ia[nr]);
-    h.a.assign(a, a + ia[nr]);
-    return h;
-  };
   sk::DCsr dA, dB, dC;
-  dA.upload(to_host(a_nrows, a_ncols, a_ia, a_ja, a_a), s);
+  dA.upload(hA, s);
   switch (op) {
     case 0:
       if (!b_ia) fail(HYPRE_ERROR_ARG, "CSRDeviceOp: product needs B");
-      dB.upload(to_host(b_nrows, b_ncols, b_ia, b_ja, b_a), s);
+      dB.upload(csr_of(who, "B", b_nrows, b_ncols, b_ia, b_ja, b_a), s);
       sk::spgemm(dA, dB, dC, s);
       break;
     case 1: sk::transpose(dA, dC, s); break;
@@ -1014,14 +923,7 @@ HYPRE_Int HYPRE_MI_CSRDeviceOp(HYPRE_Int op, HYPRE_Int a_nrows, HYPRE_Int a_ncol
   dC.download(hc, s);
   *c_nrows = hc.nrows;
   *c_ncols = hc.ncols;
-  *c_ia = (HYPRE_BigInt *)malloc(sizeof(HYPRE_BigInt) * ((size_t)hc.nrows + 1));
-  *c_ja = (HYPRE_Int *)malloc(sizeof(HYPRE_Int) * std::max<size_t>(1, hc.ja.size()));
-  *c_a = (HYPRE_Complex *)malloc(sizeof(HYPRE_Complex) * std::max<size_t>(1, hc.a.size()));
-  for (int i = 0; i <= hc.nrows; i++) (*c_ia)[i] = hc.ia[(size_t)i];
-  if (!hc.ja.empty()) {
-    memcpy(*c_ja, hc.ja.data(), hc.ja.size() * sizeof(int));
-    memcpy(*c_a, hc.a.data(), hc.a.size() * sizeof(double));
-  }
+  csr_to_caller(hc, hc.nrows, c_ia, c_ja, c_a);
   API_END
 }
 HYPRE_Int HYPRE_MI_ParCSRGetHaloPlan(HYPRE_ParCSRMatrix A, HYPRE_Int *nsend_peers, HYPRE_Int *send_peers,

@@ -157,10 +157,12 @@ HYPRE_Int HYPRE_MI_CheckBlockRowPointers(HYPRE_BigInt nrows, const HYPRE_BigInt 
 HYPRE_Int HYPRE_MI_KrylovGetResidualHistory(HYPRE_Solver solver, HYPRE_Real *norms, HYPRE_Int max_n, HYPRE_Int *n);
 HYPRE_Int HYPRE_MI_KrylovGetSolveSeconds(HYPRE_Solver solver, HYPRE_Real *seconds);
 
-/* ---- the setup phase's device sparse kernels on caller (host) CSR arrays: op 0 C = A*B (B rows sorted),
+/* ---- the setup phase's device sparse kernels on caller (host) CSR arrays: op 0 C = A*B,
  * 1 C = A^T, 2 C = rows of A in perm order (perm[new] = old, NULL = identity) with columns mapped through
- * colpos (NULL = identity) and re-sorted.  Bit-identical to the host/oracle arithmetic.  Results are
- * malloc'ed: release with HYPRE_MI_Free. */
+ * colpos (NULL = identity) and re-sorted.  Bit-identical to the host/oracle arithmetic.  A and B are checked as
+ * the other ...Op hooks check theirs (row pointers from 0 that do not decrease, columns in range and strictly
+ * ascending within a row; NULL values = zeros): anything else is HYPRE_ERROR_ARG.  Results are malloc'ed: release
+ * with HYPRE_MI_Free. */
 HYPRE_Int HYPRE_MI_CSRDeviceOp(HYPRE_Int op, HYPRE_Int a_nrows, HYPRE_Int a_ncols, const HYPRE_BigInt *a_ia,
                                const HYPRE_Int *a_ja, const HYPRE_Complex *a_a, HYPRE_Int b_nrows, HYPRE_Int b_ncols,
                                const HYPRE_BigInt *b_ia, const HYPRE_Int *b_ja, const HYPRE_Complex *b_a,
