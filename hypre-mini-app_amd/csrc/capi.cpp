@@ -1997,6 +1997,11 @@ HYPRE_Int HYPRE_MI_TileScheduleCheck(HYPRE_Int n, const HYPRE_BigInt *row_ptr, H
 //   op 4  k::scale_inv_sqrt_post w *= 1 / sqrt(coef[0]) when coef[0] > 0; the m slots coef[0 .. m) are posted into
 //         pinned host memory, then the sequence number: out[0 .. m) = the posted doubles, out[m] = the flag word after
 //         the kernel, out[m + 1] = the sequence number the kernel was given                    (1 <= m <= 255)
+//   op 5  k::mgs_block_pass      one pass of the blocked MGS step with NB = k::MGS_NB: scale = m_prev, the first m_prev
+//         vectors are the block subtracted, the other m - m_prev the block measured (none when init != 0, the last pass);
+//         coef = NB raw inner products c, then NB raw Gram rows of NB + 1 doubles.  out[0 .. NB] = the pass's sums,
+//         out[NB + 1 .. 2 NB] = the coefficients h (0 beyond m_prev), out[2 NB + 1] = the last pass's second copy of
+//         ||w||^2 (else 0); w is updated                                                        (1 <= m <= 2 NB)
 HYPRE_Int HYPRE_MI_VectorKernelOp(HYPRE_Int op, HYPRE_Int m, HYPRE_ParVector *vecs, const HYPRE_Real *coef,
                                   HYPRE_Real scale, HYPRE_ParVector w, HYPRE_ParVector xd, HYPRE_Int init,
                                   HYPRE_Real *out) {
@@ -2005,8 +2010,8 @@ HYPRE_Int HYPRE_MI_VectorKernelOp(HYPRE_Int op, HYPRE_Int m, HYPRE_ParVector *ve
   Ctx &c = ctx();
   hipStream_t s = c.stream;
   MI_REQUIRE(w, "VectorKernelOp: NULL vector w");
-  MI_REQUIRE(op >= 0 && op <= 4, "VectorKernelOp: op must be 0 .. 4");
-  const int mmax = (op <= 1) ? 120 : (op == 2 ? 250 : (op == 3 ? 1 : 255));
+  MI_REQUIRE(op >= 0 && op <= 5, "VectorKernelOp: op must be 0 .. 5");
+  const int mmax = (op <= 1) ? 120 : (op == 2 ? 250 : (op == 3 ? 1 : (op == 4 ? 255 : 2 * k::MGS_NB)));
   MI_REQUIRE(m >= 1 && m <= mmax, "VectorKernelOp: m out of range for this op");
   MI_REQUIRE(op == 0 || coef, "VectorKernelOp: NULL coefficients");
   MI_REQUIRE(op == 1 || op == 2 || out, "VectorKernelOp: NULL output");
@@ -2035,6 +2040,20 @@ HYPRE_Int HYPRE_MI_VectorKernelOp(HYPRE_Int op, HYPRE_Int m, HYPRE_ParVector *ve
       k::axpy_dot(slots, scale, vp[0], PV(w)->all(), xd ? PV(xd)->all() : nullptr, n, slots + 1, s);
       d2h(out, slots + 1, sizeof(double), s);
       break;
+    case 5: {
+      constexpr int NB = k::MGS_NB;
+      const int m_prev = (int)scale, m_next = init ? 0 : m - m_prev;
+      MI_REQUIRE(m_prev >= 0 && m_prev <= NB && m_prev <= m && m - m_prev <= NB && (!init || m_prev == m),
+                 "VectorKernelOp: op 5 takes at most MGS_NB vectors per block, and none to measure in the last pass");
+      DVec<double> buf((size_t)NB * (NB + 2) + 3 * (NB + 1));  // c, Gram rows | sums, h, ||w||^2
+      double *sums = buf.p + NB * (NB + 2), *h = sums + NB + 1;
+      MI_HIP(hipMemcpyAsync(buf.p, coef, (size_t)NB * (NB + 2) * sizeof(double), hipMemcpyHostToDevice, s));
+      MI_HIP(hipMemsetAsync(sums, 0, (size_t)3 * (NB + 1) * sizeof(double), s));
+      k::mgs_block_pass(vp.data(), m_prev, vp.data() + m_prev, m_next, init != 0, buf.p, buf.p + NB, h, PV(w)->all(), n,
+                        sums, init ? h + NB : nullptr, s);
+      d2h(out, sums, (size_t)(2 * NB + 2) * sizeof(double), s);
+      break;
+    }
     default: {
       const unsigned long long seq = ++c.post_seq;
       k::scale_inv_sqrt_post(slots, PV(w)->all(), n, slots, m, c.h_pinned + 256, c.h_post_flag, seq, s);

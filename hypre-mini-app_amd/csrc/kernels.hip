@@ -1356,6 +1356,146 @@ __global__ __launch_bounds__(256) void mass_axpy_k(MassPtrs P, int m, const doub
   }
 }
 
+// ---- blocked modified Gram-Schmidt (single-rank GMRES): one pass of the scheme of DESIGN.md section 5.
+// finish_reduction for NOUT sums per block: partial o of block b lies at partials[o * gridDim.x + b].  Lanes 0 .. NOUT-1
+// (one wave) leave the block's partials by exchanges whose returns the wave waits for, then lane 0 draws the ticket;
+// the last block adds every output up in finish_reduction's fixed order.  ws: NOUT x 4 wave sums on entry.
+template <int NOUT>
+__device__ __forceinline__ void finish_reduction_multi(double (*ws)[4], double *__restrict__ partials,
+                                                       unsigned *__restrict__ ticket, double *__restrict__ out,
+                                                       double *__restrict__ out_last) {
+  static_assert(NOUT <= 64, "the partials are left by one wave");
+  __shared__ unsigned s_last;
+  const int tid = threadIdx.x;
+  const int nb = (int)gridDim.x;
+  if (tid < NOUT) {
+    const double block_sum = (ws[tid][0] + ws[tid][1]) + (ws[tid][2] + ws[tid][3]);
+    unsigned long long *slot = reinterpret_cast<unsigned long long *>(partials + (size_t)tid * nb + blockIdx.x);
+    const unsigned long long old =
+        __hip_atomic_exchange(slot, (unsigned long long)__double_as_longlong(block_sum), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::"v"(old) : "memory");
+  }
+  if (tid == 0) {
+    const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = (t == gridDim.x - 1) ? 1u : 0u;
+  }
+  __syncthreads();
+  if (!s_last) return;
+#pragma unroll
+  for (int o = 0; o < NOUT; o++) {
+    double s = 0.0;
+    for (int i = tid; i < nb; i += 256)
+      s += __hip_atomic_load(partials + (size_t)o * nb + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s = wave_sum(s);
+    if ((tid & 63) == 0) ws[o][tid >> 6] = s;  // the block sums were read before the barrier above
+  }
+  __syncthreads();
+  if (tid < NOUT) {
+    const double v = (ws[tid][0] + ws[tid][1]) + (ws[tid][2] + ws[tid][3]);
+    out[tid] = v;
+    if (out_last && tid == NOUT - 1) out_last[0] = v;
+  }
+  if (tid == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <int B>
+struct MgsPtrs {
+  const double *prev[B];
+  const double *next[B];
+};
+
+// Prologue (every thread, at most B(B-1)/2 FMAs): the MGS coefficients of the block `prev` from the raw inner products
+// c_prev[j] = <prev_j, w> (all taken against the same w) and the block's raw Gram rows -- row j = B + 1 doubles,
+// <prev_k, w_j> for k < j and, last, ||w_j||^2 of the vector w_j that became prev_j = w_j / ||w_j|| --
+//   h_j = c_j - sum_{k < j} h_k g_jk,  g_jk = <prev_k, w_j> / sqrt(||w_j||^2)  (0 where the norm is not positive).
+// Block 0 stores them at h_out.  Body: w -= sum_j h_j prev_j (ascending j), and off the new w
+//   !LAST: out[j] = <next_j, w>, j < m_next (the raw c of the next block);
+//   LAST:  out[j] = <prev_j, w>, j < m_prev, out[B] = ||w||^2 (also at out_norm): the raw Gram row of w.
+// Streaming as axpy_dot_partial_k: every operand once, non-temporal.  Outputs beyond the counts are 0.
+template <int B, bool LAST>
+__global__ __launch_bounds__(256) void mgs_block_pass_k(MgsPtrs<B> P, int m_prev, int m_next,
+                                                        const double *__restrict__ c_prev,
+                                                        const double *__restrict__ gram_prev, double *__restrict__ h_out,
+                                                        double *__restrict__ w, int n, double *__restrict__ partials,
+                                                        unsigned *__restrict__ ticket, double *__restrict__ out,
+                                                        double *__restrict__ out_norm) {
+  __shared__ double ws[B + 1][4];
+  const int tid = threadIdx.x;
+  double a[B];  // -h_j
+#pragma unroll
+  for (int j = 0; j < B; j++) {
+    a[j] = 0.0;
+    if (j < m_prev) {
+      const double nrm = j > 0 ? gram_prev[j * (B + 1) + B] : 0.0;  // row 0 has no entries: never read
+      const double inv = nrm > 0.0 ? 1.0 / sqrt(nrm) : 0.0;
+      double h = c_prev[j];
+#pragma unroll
+      for (int k = 0; k < j; k++) h += a[k] * (gram_prev[j * (B + 1) + k] * inv);
+      a[j] = -h;
+      if (blockIdx.x == 0 && tid == 0) h_out[j] = h;
+    }
+  }
+  double acc[B + 1];
+#pragma unroll
+  for (int j = 0; j <= B; j++) acc[j] = 0.0;
+  const long long stride = (long long)gridDim.x * 512;
+  long long i = ((long long)blockIdx.x * 256 + tid) * 2;
+  for (; i + 1 < n; i += stride) {
+    // all loads first, then the arithmetic: the branches on the (uniform) counts hold no wait between two loads
+    d2_t wv = nt_load(reinterpret_cast<const d2_t *>(w + i));
+    d2_t pv[B], qv[B];
+#pragma unroll
+    for (int j = 0; j < B; j++)
+      if (j < m_prev) pv[j] = nt_load(reinterpret_cast<const d2_t *>(P.prev[j] + i));
+    if (!LAST) {
+#pragma unroll
+      for (int j = 0; j < B; j++)
+        if (j < m_next) qv[j] = nt_load(reinterpret_cast<const d2_t *>(P.next[j] + i));
+    }
+#pragma unroll
+    for (int j = 0; j < B; j++)
+      if (j < m_prev) {
+        wv.x += a[j] * pv[j].x;
+        wv.y += a[j] * pv[j].y;
+      }
+    if (m_prev > 0) __builtin_nontemporal_store(wv, reinterpret_cast<d2_t *>(w + i));
+    if (LAST) {
+#pragma unroll
+      for (int j = 0; j < B; j++)
+        if (j < m_prev) acc[j] += pv[j].x * wv.x + pv[j].y * wv.y;
+      acc[B] += wv.x * wv.x + wv.y * wv.y;
+    } else {
+#pragma unroll
+      for (int j = 0; j < B; j++)
+        if (j < m_next) acc[j] += qv[j].x * wv.x + qv[j].y * wv.y;
+    }
+  }
+  if (i < n) {
+    double v = w[i];
+#pragma unroll
+    for (int j = 0; j < B; j++)
+      if (j < m_prev) v += a[j] * P.prev[j][i];
+    if (m_prev > 0) w[i] = v;
+    if (LAST) {
+#pragma unroll
+      for (int j = 0; j < B; j++)
+        if (j < m_prev) acc[j] += P.prev[j][i] * v;
+      acc[B] += v * v;
+    } else {
+#pragma unroll
+      for (int j = 0; j < B; j++)
+        if (j < m_next) acc[j] += P.next[j][i] * v;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j <= B; j++) {
+    const double v = wave_sum(acc[j]);
+    if ((tid & 63) == 0) ws[j][tid >> 6] = v;
+  }
+  __syncthreads();
+  finish_reduction_multi<B + 1>(ws, partials, ticket, out, LAST ? out_norm : nullptr);
+}
+
 // w = c_0 p_0 (INIT) or w += c_0 p_0, then += c_1 p_1, ... in this order: the chain copy / scale / axpy / axpy ... of the
 // GMRES solution update in one pass over up to MASS_NV vectors (same operations per element in the same order)
 struct MassCoef {
@@ -2239,6 +2379,29 @@ void axpy_dot(const double *alpha_dev, double scale_, const double *xa, double *
   prof_begin(PROF_DOT, s);
   hipLaunchKernelGGL(axpy_dot_partial_k, dim3(g), dim3(256), 0, s, alpha_dev, scale_, xa, y, xd, n, partials,
                      ctx().red_ticket.p, out_dev);
+  prof_end(PROF_DOT, s);
+  MI_HIP(hipGetLastError());
+}
+
+void mgs_block_pass(const double *const *prev, int m_prev, const double *const *next, int m_next, bool last,
+                    const double *c_prev, const double *gram_prev, double *h_out, double *w, int n, double *out_dev,
+                    double *out_norm, hipStream_t s) {
+  MI_REQUIRE(m_prev >= 0 && m_prev <= MGS_NB && m_next >= 0 && m_next <= MGS_NB, "mgs_block_pass: block too large");
+  // MGS_NB + 1 partial sums per workgroup in the slots the reductions share
+  const int g = std::min(dot_grid(n), RED_MAX_BLOCKS * MASS_NV / (MGS_NB + 1));
+  MgsPtrs<MGS_NB> P;
+  for (int j = 0; j < MGS_NB; j++) {
+    P.prev[j] = j < m_prev ? prev[j] : nullptr;
+    P.next[j] = (!last && j < m_next) ? next[j] : nullptr;
+  }
+  double *partials = ctx().red_partials.p;
+  prof_begin(PROF_DOT, s);
+  if (last)
+    hipLaunchKernelGGL((mgs_block_pass_k<MGS_NB, true>), dim3(g), dim3(256), 0, s, P, m_prev, 0, c_prev, gram_prev, h_out,
+                       w, n, partials, ctx().red_ticket.p, out_dev, out_norm);
+  else
+    hipLaunchKernelGGL((mgs_block_pass_k<MGS_NB, false>), dim3(g), dim3(256), 0, s, P, m_prev, m_next, c_prev, gram_prev,
+                       h_out, w, n, partials, ctx().red_ticket.p, out_dev, out_norm);
   prof_end(PROF_DOT, s);
   MI_HIP(hipGetLastError());
 }

@@ -17,6 +17,12 @@ constexpr int SPMV_BLOCK_WIDE = 512;
 constexpr int SPMV_TILE_WIDE = 4096;
 constexpr int RED_MAX_BLOCKS = 2048;
 constexpr int MASS_NV = 8;        // vectors per pass of the block inner product / block update
+// basis vectors per block of the blocked modified Gram-Schmidt of single-rank GMRES (mgs_block_pass); -DMI_MGS_NB=4 / 16
+// build the other sizes that profiles/gmres_blocked_mgs.txt compares
+#ifndef MI_MGS_NB
+#define MI_MGS_NB MASS_NV
+#endif
+constexpr int MGS_NB = MI_MGS_NB;
 constexpr int GS_BLOCK = 256;     // chunks (lanes) per workgroup
 constexpr int GS_MAX_CHUNK = 32;
 
@@ -226,6 +232,15 @@ void dot(const double *x, const double *y, int n, double *out_dev, hipStream_t s
 // fused MGS step: y += scale*(*alpha_dev)*xa, then out_dev = <xd, y> (xd == nullptr: <y, y>), local sum
 void axpy_dot(const double *alpha_dev, double scale, const double *xa, double *y, const double *xd, int n,
               double *out_dev, hipStream_t s);
+// one pass of the blocked MGS step over w: h_out[j] = the MGS coefficients of the m_prev
+// vectors `prev` by forward substitution from their raw inner products c_prev[j] = <prev_j, w> and raw Gram rows
+// gram_prev (row j: MGS_NB + 1 doubles, <prev_k, w_j> for k < j, then ||w_j||^2, w_j = prev_j before its scaling);
+// w -= sum_j h_j prev_j; then out_dev[0 .. MGS_NB] = <next_j, w> for j < m_next (raw c of the next block), or, in the
+// last pass of a step, <prev_j, w> for j < m_prev and ||w||^2 at [MGS_NB] and at out_norm: the raw Gram row of w.
+// Entries beyond the counts are 0.  One launch; local sums in a fixed order
+void mgs_block_pass(const double *const *prev, int m_prev, const double *const *next, int m_next, bool last,
+                    const double *c_prev, const double *gram_prev, double *h_out, double *w, int n, double *out_dev,
+                    double *out_norm, hipStream_t s);
 // block Gram-Schmidt (COGMRES): out_dev[j] = <vecs[j], w> for j < m (local sums), and w += scale * sum_j coef_dev[j] vecs[j]
 void mass_dot(const double *const *vecs, int m, const double *w, int n, double *out_dev, hipStream_t s);
 void mass_axpy(const double *const *vecs, int m, const double *coef_dev, double scale, double *w, int n, hipStream_t s);

@@ -340,7 +340,30 @@ int GmresSolver::solve(ParCSR &A_in, ParVector &b_in, ParVector &x_in) {
       if (adopt) std::swap(amg->L[0].u.p, zk->d.p);  // mp is z_{i-1} now
       mv(1.0, mp, 0.0, nullptr, pi.data());
       TraceRange trace_ortho("Gram-Schmidt + Givens");
-      if (ortho == 0) {
+      if (ortho == 0 && comm.size == 1) {
+        // blocked modified Gram-Schmidt over aligned blocks of NB basis vectors, ceil(i / NB) + 1 passes over w = p_i:
+        // pass 0 takes the raw inner products of block 0; pass k turns those of block k-1 into MGS coefficients (forward
+        // substitution with the block's Gram rows), subtracts, and takes the raw products of block k off the new w; the
+        // last pass subtracts the last block and leaves ||w||^2 and the Gram row of p_i
+        constexpr int NB = k::MGS_NB;
+        const size_t rows = ((size_t)kd + 1) * (NB + 1);
+        if (mgs_gram.n < rows + 2 * (NB + 1)) mgs_gram.alloc(rows + 2 * (NB + 1));
+        double *gram = mgs_gram.p, *cbuf = mgs_gram.p + rows;
+        const double *vp[NB], *vn[NB];
+        const int nblk = (i + NB - 1) / NB;
+        for (int kb = 0; kb <= nblk; kb++) {
+          const int jp = (kb - 1) * NB, jn = kb * NB;  // first vector of the block subtracted / measured
+          const int m_prev = kb ? std::min(NB, i - jp) : 0, m_next = kb < nblk ? std::min(NB, i - jn) : 0;
+          for (int j = 0; j < m_prev; j++) vp[j] = basis(jp + j).data();
+          for (int j = 0; j < m_next; j++) vn[j] = basis(jn + j).data();
+          const bool last = kb == nblk;
+          k::mgs_block_pass(vp, m_prev, vn, m_next, last, kb ? cbuf + ((kb - 1) & 1) * (NB + 1) : nullptr,
+                            kb ? gram + (size_t)jp * (NB + 1) : nullptr, kb ? slots + jp : nullptr, pi.data(), n,
+                            last ? gram + (size_t)i * (NB + 1) : cbuf + (kb & 1) * (NB + 1), last ? slots + i : nullptr, s);
+        }
+        fetch_column(slots + i, pi.data(), i + 1);
+        for (int j = 0; j < i; j++) hh[(size_t)j][(size_t)i - 1] = c.h_pinned[j];
+      } else if (ortho == 0) {
         // modified Gram-Schmidt with the axpy of step j-1 fused into the dot of step j
         // (and the last axpy into the norm): h_j = <p_j, w>, w -= h_j p_j, one pass each
         par_dot(comm, basis(0).data(), pi.data(), n, slots, s);

@@ -64,6 +64,9 @@ struct GmresSolver : KrylovSolver {
   // solution buffer of the preconditioner (same size, swapped in after the cycle)
   std::vector<std::unique_ptr<ParVector>> z;
   ParVector r, w;
+  // blocked MGS (one rank, ortho 0): row i = the raw Gram row of p_i, k::MGS_NB + 1 doubles
+  // written by the pass that made p_i; after the k_dim + 1 rows, two alternating sets of k::MGS_NB + 1 raw inner products
+  DVec<double> mgs_gram;
   GmresSolver() : KrylovSolver(K_GMRES) {}
   void setup(ParCSR &A, ParVector &b, ParVector &x);
   int solve(ParCSR &A, ParVector &b, ParVector &x);

@@ -1284,3 +1284,23 @@ def vector_kernel_op(op, vecs, coef, w, scale=1.0, xd=None, init=False):
     if op == VEC_SCALE_POST:
         return out[:m].copy(), int(out[m]), int(out[m + 1])
     return None
+
+
+VEC_MGS_BLOCK = 5
+MGS_NB = 8
+
+
+def mgs_block_pass(prev, nxt, last, c, gram, w):
+    """One pass of the blocked modified Gram-Schmidt step (k::mgs_block_pass through the test hook): the vectors `prev`
+    are subtracted from w with the coefficients the kernel derives from their raw inner products c (MGS_NB doubles)
+    and raw Gram rows gram (MGS_NB x (MGS_NB + 1)); then the inner products of the new w with the vectors `nxt`, or,
+    in the last pass (nxt empty), with `prev`, and its squared norm.  Returns (sums, h, norm copy): MGS_NB + 1 sums,
+    MGS_NB coefficients, the squared norm where the last pass leaves it a second time.  w is changed on the device."""
+    vecs = list(prev) + ([] if last else list(nxt))
+    arr = (vp * max(len(vecs), 1))(*[v.par for v in vecs])
+    cf = dbl(np.concatenate([np.asarray(c, dtype=np.float64).ravel(), np.asarray(gram, dtype=np.float64).ravel()]))
+    assert len(cf) == MGS_NB * (MGS_NB + 2)
+    out = np.zeros(2 * MGS_NB + 2)
+    call("HYPRE_MI_VectorKernelOp", VEC_MGS_BLOCK, len(vecs), arr, cf, c_dbl(float(len(prev))), w.par, None,
+         1 if last else 0, out)
+    return out[:MGS_NB + 1].copy(), out[MGS_NB + 1:2 * MGS_NB + 1].copy(), float(out[2 * MGS_NB + 1])

@@ -103,7 +103,11 @@ HYPRE_Int HYPRE_MI_TileScheduleCheck(HYPRE_Int n, const HYPRE_BigInt *row_ptr, H
  * vecs[j] (m <= 250); 3 fused update and inner product w += (scale * coef[0]) vecs[0], out[0] = <xd, w> (xd NULL:
  * <w, w>), m = 1; 4 the scaling kernel that posts an Arnoldi step's Hessenberg column to the host: w *= 1 / sqrt(coef[0])
  * when coef[0] > 0, out[0 .. m) = the m posted doubles (coef as the slots held them), out[m] = the flag word after the
- * kernel, out[m + 1] = the sequence number it was given (m <= 255).  The block kernels work in passes of 8 vectors. */
+ * kernel, out[m + 1] = the sequence number it was given (m <= 255); 5 one pass of the blocked modified Gram-Schmidt
+ * step over blocks of NB = 8 vectors: scale = m_prev, vecs = the m_prev vectors subtracted, then the m - m_prev
+ * vectors measured (init != 0: the last pass, m = m_prev), coef = NB raw inner products, then NB raw Gram rows of
+ * NB + 1 doubles; out[0 .. NB] = the pass's sums, out[NB + 1 .. 2 NB] = the coefficients, out[2 NB + 1] = the last pass's
+ * second copy of the squared norm (m <= 2 NB).  The block kernels work in passes of 8 vectors. */
 HYPRE_Int HYPRE_MI_VectorKernelOp(HYPRE_Int op, HYPRE_Int m, HYPRE_ParVector *vecs, const HYPRE_Real *coef,
                                   HYPRE_Real scale, HYPRE_ParVector w, HYPRE_ParVector xd, HYPRE_Int init,
                                   HYPRE_Real *out);
