@@ -12,6 +12,9 @@ struct AmgParams {
   int interp_type = 6;            // extended+i
   double strong_threshold = 0.25; // the app sets 0.57 (HypreSystem.cpp:159)
   double max_row_sum = 0.9;
+  // unknown-based systems AMG ("Systems of PDEs"): the rows belong to num_functions unknowns;
+  // strength, splitting and interpolation of every level are those of the same-function operator.  1 = a scalar problem
+  int num_functions = 1;
   // restriction: 0 = P^T, 1 = distance-1 approximate ideal restriction with its own strength
   // threshold theta_R and the filter phi of its rows (HYPRE_BoomerAMGSetRestriction / StrongThresholdR / FilterThresholdR)
   int restriction = 0;
@@ -127,6 +130,9 @@ struct AmgLevel {
   bool halo_rows_ready = false;
   std::vector<InteriorRange> interior_cache;
   LazyInts cf;  // +1 C, -1 F (empty on the coarsest level)
+  // num_functions > 1: the unknown every row belongs to -- natural order while the hierarchy is built, the level's
+  // C-first order afterwards (HYPRE_MI_BoomerAMGGetLevelDofFunc); empty otherwise
+  LazyInts dof;
   // aggressive level with the two-stage interpolation (agg_interp_type 5): the markers after the first coarsening and
   // after the second one (+1 C, -1 F, -3 special F), natural order of the level; kept only when
   // AmgParams::keep_agg_markers asks for them (inspection)
@@ -198,6 +204,11 @@ struct BoomerAMG {
   std::unique_ptr<ParCSR> Aq_own;
   sk::DCsr pending_sA0;  // Q A Q^T built on the device by setup_host, handed to level 0 by build_natural
   bool use_locality_order(const ParCSR &A) const;
+  // num_functions > 1: the caller's dof_func (host or device memory, read and copied at every Setup, never freed here;
+  // null = global row mod num_functions), and level 0's copy in the internal numbering on its way to build_natural
+  const int *dof_func_user = nullptr;
+  std::vector<int> pending_dof;
+  void read_dof_func(const ParCSR &A);
   // the matrix HYPRE_BoomerAMGSetup was called with (and its assembly stamp): a Krylov solver may run on the
   // hierarchy's own level-0 copy only when it is handed that very matrix (krylov.cpp amg_in_level_order)
   const ParCSR *source_matrix = nullptr;
@@ -284,6 +295,7 @@ struct BoomerAMG {
   void setup_host(ParCSR &A);
   void build_natural(ParCSR &A);      // strength / PMIS / interpolation / Galerkin loop, natural ordering
   // its steps on the state of the level being built (amg_setup.cpp; DESIGN.md section 3, "The level build")
+  void level_same_function_operator(LevelBuild &b);
   void level_strength_and_coarsening(LevelBuild &b);
   void level_interpolation(LevelBuild &b);
   void level_restriction(LevelBuild &b);

@@ -61,6 +61,34 @@ void strength(const ParCSR &A, double theta, double max_row_sum, Strength &S) {
   });
 }
 
+void filter_same_function(const HostCSR &A, const std::vector<int> &dof, HostCSR &F) {
+  const int n = A.nrows;
+  F.nrows = n;
+  F.ncols = A.ncols;
+  F.ia.assign((size_t)n + 1, 0);
+  auto kept = [&](int64_t i, int64_t k) { return A.ja[(size_t)k] == i || dof[(size_t)A.ja[(size_t)k]] == dof[(size_t)i]; };
+  parallel_for(n, [&](int64_t b, int64_t e, int) {
+    for (int64_t i = b; i < e; i++) {
+      int64_t c = 0;
+      for (int64_t k = A.ia[(size_t)i]; k < A.ia[(size_t)i + 1]; k++) c += kept(i, k);
+      F.ia[(size_t)i + 1] = c;
+    }
+  });
+  for (int i = 0; i < n; i++) F.ia[(size_t)i + 1] += F.ia[(size_t)i];
+  F.ja.resize((size_t)F.ia[(size_t)n]);
+  F.a.resize((size_t)F.ia[(size_t)n]);
+  parallel_for(n, [&](int64_t b, int64_t e, int) {
+    for (int64_t i = b; i < e; i++) {
+      int64_t q = F.ia[(size_t)i];
+      for (int64_t k = A.ia[(size_t)i]; k < A.ia[(size_t)i + 1]; k++)
+        if (kept(i, k)) {
+          F.ja[(size_t)q] = A.ja[(size_t)k];
+          F.a[(size_t)q++] = A.a[(size_t)k];
+        }
+    }
+  });
+}
+
 // keep entries >= trunc_factor*max|p|, then the pmax largest by (|p| desc,
 // position asc), rescale to the original row sum; stored order is kept
 int truncate_row(int len, int *cols, double *vals, double trunc_factor, int pmax, std::vector<char> &keep) {
@@ -1690,6 +1718,18 @@ void BoomerAMG::apply_cf_ordering() {
         });
         Lv.cf = std::move(cf2);
       }
+      if (!Lv.dof.empty() && Lv.dof.on_device() && Lv.perm.on_device()) {  // (num_functions > 1) dof_func follows the rows
+        const size_t n = Lv.dof.size();
+        DVec<int> d2(n);
+        sk::gather_elems(Lv.dof.dev(), Lv.perm.dev(), 0, (int)n, 4, d2.p, ctx().stream);
+        MI_HIP(hipStreamSynchronize(ctx().stream));
+        Lv.dof.adopt_device(std::move(d2), n);
+      } else if (!Lv.dof.empty()) {
+        const std::vector<int> &dh = Lv.dof.host(), &permh = Lv.perm.host();
+        std::vector<int> d2(dh.size());
+        for (size_t q = 0; q < d2.size(); q++) d2[q] = dh[(size_t)permh[q]];
+        Lv.dof = std::move(d2);
+      }
     }
     if (Lv.P.nrows > 0 && (has_pos[l] || (l + 1 < nlev && has_pos[l + 1]))) {
       const bool map_cols = l + 1 < nlev && has_pos[l + 1];
@@ -2041,6 +2081,18 @@ void BoomerAMG::validate_settings() const {
       fail(4, "BoomerAMGSetup: restriction 1 (approximate ideal restriction) is not implemented on more than one rank (" +
                   std::to_string(my_comm().size) + " ranks); refusing to restrict with the transpose of P");
   }
+  if (p.num_functions < 1)
+    fail(4, "BoomerAMGSetup: num_functions " + std::to_string(p.num_functions) +
+                " is not implemented (a value >= 1 is); refusing to treat the system as a scalar problem");
+  if (p.num_functions > 1) {
+    if (p.restriction == 1)
+      fail(4, "BoomerAMGSetup: restriction 1 (approximate ideal restriction) with num_functions " +
+                  std::to_string(p.num_functions) + " is not implemented (it is with num_functions 1); refusing to restrict "
+                  "with the transpose of P");
+    if (my_comm().size > 1)
+      fail(4, "BoomerAMGSetup: num_functions " + std::to_string(p.num_functions) + " is not implemented on more than one rank (" +
+                  std::to_string(my_comm().size) + " ranks); refusing to treat the system as a scalar problem");
+  }
   if (p.smooth_num_levels > 0 && p.smooth_type != 5 && p.smooth_type != 4)
     fail(4, "BoomerAMGSetup: smooth_type " + std::to_string(p.smooth_type) + " on " + std::to_string(p.smooth_num_levels) +
                 " level(s) is not implemented (4 = FSAI and 5 = ILU are); refusing to smooth with something else");
@@ -2060,6 +2112,26 @@ void BoomerAMG::validate_settings() const {
                 std::to_string(p.ilu_level) + ", option " + std::to_string(p.ilu_iter_option) + ", max iterations " +
                 std::to_string(p.ilu_iter_max_iter) +
                 " is not implemented (types 0 ... 4 with ILU(0), option bits 1 ... 32, max iterations >= 1 are)");
+}
+
+// num_functions > 1: the caller's dof_func (or the interleaved default) of this rank's rows, copied and checked
+void BoomerAMG::read_dof_func(const ParCSR &A0) {
+  const size_t n = (size_t)A0.nrows;
+  const int k = p.num_functions;
+  pending_dof.resize(n);
+  if (!dof_func_user) {
+    for (size_t i = 0; i < n; i++) pending_dof[i] = (int)((A0.row_start + (gidx)i) % (gidx)k);
+    return;
+  }
+  if (n && is_device_pointer(dof_func_user))
+    d2h(pending_dof.data(), dof_func_user, n * sizeof(int), nullptr);
+  else if (n)
+    memcpy(pending_dof.data(), dof_func_user, n * sizeof(int));
+  for (size_t i = 0; i < n; i++)
+    if (pending_dof[i] < 0 || pending_dof[i] >= k)
+      fail(4, "BoomerAMGSetup: dof_func[" + std::to_string(i) + "] = " + std::to_string(pending_dof[i]) +
+                  " (local row " + std::to_string(i) + ") is outside [0, num_functions = " + std::to_string(k) +
+                  "); refusing to guess the row's unknown");
 }
 
 void BoomerAMG::setup_host(ParCSR &A0) {
@@ -2142,6 +2214,16 @@ void BoomerAMG::setup_host(ParCSR &A0) {
       Q.build_halo_plan(comm);
       Ain = Aq_own.get();
       if (getenv("MI_HYPRE_SETUP_TIMING")) printf("   locality numbering of the input: %.2f s\n", wall_time() - tq0);
+    }
+    pending_dof.clear();
+    if (p.num_functions > 1) {
+      read_dof_func(A0);
+      if (!input_order.empty()) {  // the hierarchy is built on Q A Q^T: row q of it is the caller's row input_order[q]
+        const std::vector<int> &oh = input_order.host();
+        std::vector<int> q(pending_dof.size());
+        for (size_t i = 0; i < q.size(); i++) q[i] = pending_dof[(size_t)oh[i]];
+        pending_dof.swap(q);
+      }
     }
     build_natural(*Ain);
     const double tp0 = wall_time();
@@ -2252,17 +2334,45 @@ struct LevelBuild {
   sk::DCsr dS;
   bool S_on_host = false;
   LevelMarker cf, cf1;  // cf1: the marker after the first coarsening of an aggressive level (two-stage interpolation)
+  // num_functions > 1: the same-function operator F(A) that steps 1 and 2 read in A's place -- dF on a device level, F
+  // for the host routines (made from dF when a device level hands its interpolation to one); gone after step 2
+  const bool systems;
+  sk::DCsr dF;
+  std::unique_ptr<ParCSR> F;
+  LazyInts dof_coarse;  // the coarse level's dof_func (end of step 2), handed to the new level by build_natural
   bool p_on_device = false;
   int nc = 0;
   sk::DCsr dR_local, *dR = nullptr;  // the device's R for the Galerkin product (Lv.sR where it is kept)
-  double tp0 = 0.0;
+  double tp0 = 0.0, t_filter = 0.0;
   std::unique_ptr<TraceRange> trace;
 
   LevelBuild(int level, AmgLevel &lv, const AmgParams &p, long long device_min_rows)
       : l(level), n(lv.A->nrows), A(*lv.A), Lv(lv), on_device(device_min_rows >= 0 && n >= device_min_rows),
         aggressive(level < p.agg_num_levels), kind(interp_kind(aggressive, p)),
         host_coarsen(!on_device || !(p.coarsen_type == 8 || p.coarsen_type == 9) ||
-                     (aggressive && kind != InterpKind::two_stage)) {}
+                     (aggressive && kind != InterpKind::two_stage)),
+        systems(p.num_functions > 1) {}
+  // the operator whose strength graph, splitting and interpolation the level gets
+  const sk::DCsr &graph_operator_dev() const { return systems ? dF : Lv.sA; }
+  ParCSR &graph_operator_host() {
+    if (!systems) return A;
+    if (!F) {
+      F.reset(new ParCSR());
+      if (on_device)
+        dF.download(F->diag, ctx().stream);
+      else
+        filter_same_function(A.diag, Lv.dof.host(), F->diag);
+      F->diag.nrows = F->diag.ncols = n;
+      F->nrows = n;
+      F->row_start = 0;
+      F->row_end = n;
+      F->row_starts = {0, (gidx)n};
+      F->offd.nrows = n;
+      F->offd.ncols = 0;
+      F->offd.ia.assign((size_t)n + 1, 0);
+    }
+    return *F;
+  }
   void begin(const char *what) {
     trace.reset(), trace.reset(new TraceRange(("level " + std::to_string(l) + ": " + what).c_str()));
   }
@@ -2312,18 +2422,43 @@ void BoomerAMG::fetch_operator(ParCSR *M, sk::DCsr &dev) {
   M->ensure_offd_rows();
 }
 
+// step 0 (num_functions > 1 only): the same-function operator F(A) of the level, from the level's dof_func
+void BoomerAMG::level_same_function_operator(LevelBuild &b) {
+  if (!b.systems) return;
+  MI_REQUIRE(b.Lv.dof.size() == (size_t)b.n, "level build: the level has no dof_func");
+  double t0 = wall_time();
+  if (b.on_device) {
+    hipStream_t s = ctx().stream;
+    if (b.Lv.sA.nrows != b.n) b.Lv.sA.upload(b.A.diag, s);  // (what step 1 would upload; not the filter's time)
+    const int *dof = b.Lv.dof.dev();
+    t0 = wall_time();
+    sk::same_function_filter(b.Lv.sA, dof, b.dF, s);
+  } else {
+    b.graph_operator_host();
+  }
+  b.t_filter = wall_time() - t0;
+}
+
 // step 1: the strength graph and the splitting; leaves the level's marker in b.cf (and b.cf1)
 void BoomerAMG::level_strength_and_coarsening(LevelBuild &b) {
+  double t_strength = 0.0;
   if (b.on_device) {
     // strength graph and PMIS splitting on the device (integer/compare work, identical results)
     hipStream_t s = ctx().stream;
     if (b.Lv.sA.nrows != b.n) b.Lv.sA.upload(b.A.diag, s);
-    sk::strength(b.Lv.sA, p.strong_threshold, p.max_row_sum, b.dS, s);
+    const double ts0 = wall_time();
+    sk::strength(b.graph_operator_dev(), p.strong_threshold, p.max_row_sum, b.dS, s);
+    t_strength = wall_time() - ts0;
   } else {
-    strength(b.A, p.strong_threshold, p.max_row_sum, b.S);
+    const double ts0 = wall_time();
+    strength(b.graph_operator_host(), p.strong_threshold, p.max_row_sum, b.S);
+    t_strength = wall_time() - ts0;
     b.S_on_host = true;
   }
   t_phase[0] += b.lap();
+  if (b.systems && getenv("MI_HYPRE_SETUP_TIMING"))  // (both routines are complete on return: wall time is their time)
+    printf("   level %d: n %d  same-function filter %.4f s, strength %.4f s%s\n", b.l, b.n, b.t_filter, t_strength,
+           b.on_device ? "" : "  (host routines)");
   const bool two_stage = b.kind == InterpKind::two_stage;
   if (b.host_coarsen) {
     const Strength &S = b.strength_to_host();
@@ -2348,7 +2483,6 @@ void BoomerAMG::level_strength_and_coarsening(LevelBuild &b) {
 // to Lv.cf
 void BoomerAMG::level_interpolation(LevelBuild &b) {
   AmgLevel &Lv = b.Lv;
-  ParCSR &A = b.A;
   const int n = b.n;
   if (b.kind == InterpKind::two_stage && p.keep_agg_markers) {
     // (inspection, HYPRE_MI_BoomerAMGGetLevelAggMarkers: natural order, before the interpolation rewrites -3)
@@ -2359,27 +2493,28 @@ void BoomerAMG::level_interpolation(LevelBuild &b) {
   int bad = -1;  // a row with a zero denominator (two_stage, mm_ext)
   if (b.on_device) {
     hipStream_t s = ctx().stream;
+    const sk::DCsr &dA = b.graph_operator_dev();
     switch (b.kind) {
       case InterpKind::classical:
         if (p.interp_type == 6 || p.interp_type == 0) {  // (declines a row whose interpolatory set outgrows its tables)
-          b.p_on_device = sk::interp(Lv.sA, b.dS, b.cf.dev(), p.interp_type, p.trunc_factor, p.pmax_elmts, Lv.sP, b.nc, s,
+          b.p_on_device = sk::interp(dA, b.dS, b.cf.dev(), p.interp_type, p.trunc_factor, p.pmax_elmts, Lv.sP, b.nc, s,
                                      &Lv.interp_census);
           Lv.interp_by_host = false;
         }
         break;
       case InterpKind::multipass: break;  // a host routine
       case InterpKind::two_stage:  // (after a coarsening the host ran, too: the interpolation is the device's all the same)
-        bad = sk::two_stage_ext(Lv.sA, b.dS, b.cf1.dev(), b.cf.dev(), p.agg_p12_trunc_factor, p.agg_p12_max_elmts,
+        bad = sk::two_stage_ext(dA, b.dS, b.cf1.dev(), b.cf.dev(), p.agg_p12_trunc_factor, p.agg_p12_max_elmts,
                                 p.agg_trunc_factor, p.agg_pmax_elmts, Lv.sP, b.nc, s);
         b.cf1 = LevelMarker();  // (the first stage's marker has served)
         b.p_on_device = true;
         break;
       case InterpKind::mm_ext:  // two operand builders and sk::spgemm: rows of any length stay on the device
-        bad = sk::mm_interp(Lv.sA, b.dS, b.cf.dev(), p.interp_type, p.trunc_factor, p.pmax_elmts, Lv.sP, b.nc, s);
+        bad = sk::mm_interp(dA, b.dS, b.cf.dev(), p.interp_type, p.trunc_factor, p.pmax_elmts, Lv.sP, b.nc, s);
         b.p_on_device = true;
         break;
       case InterpKind::one_point:  // one row per lane: rows of any length stay on the device
-        sk::one_point_interp(Lv.sA, b.dS, b.cf.dev(), Lv.sP, b.nc, s);
+        sk::one_point_interp(dA, b.dS, b.cf.dev(), Lv.sP, b.nc, s);
         b.p_on_device = true;
         break;
     }
@@ -2390,7 +2525,7 @@ void BoomerAMG::level_interpolation(LevelBuild &b) {
       Lv.P.ncols = b.nc;
     } else {
       // the host routine runs on the host's copies of the operator, the graph and the marker
-      fetch_operator(&A, Lv.sA);
+      if (!b.systems) fetch_operator(&b.A, Lv.sA);
       b.strength_to_host();
       b.cf.host_only();
     }
@@ -2398,6 +2533,7 @@ void BoomerAMG::level_interpolation(LevelBuild &b) {
   }
   if (!b.p_on_device) {
     std::vector<int> &cf = b.cf.host();
+    ParCSR &A = b.graph_operator_host();
     switch (b.kind) {
       case InterpKind::classical: build_interp(A, b.S, cf, p.interp_type, p.trunc_factor, p.pmax_elmts, Lv.P, b.nc); break;
       case InterpKind::multipass:
@@ -2419,6 +2555,23 @@ void BoomerAMG::level_interpolation(LevelBuild &b) {
   else
     Lv.cf = std::move(b.cf.host_only());
   Lv.has_cf = true;
+  if (b.systems) {
+    // F(A) has served (the Galerkin product allocates next); the coarse level's dof_func is this one's at the C points
+    b.dF.release();
+    b.F.reset();
+    if (Lv.cf.on_device()) {
+      DVec<int> dc;
+      sk::gather_at_c_points(Lv.cf.dev(), Lv.dof.dev(), n, dc, ctx().stream);
+      b.dof_coarse.adopt_device(std::move(dc), (size_t)b.nc);
+    } else {
+      const std::vector<int> &cfh = Lv.cf.host(), &dh = Lv.dof.host();
+      std::vector<int> dc;
+      dc.reserve((size_t)b.nc);
+      for (int i = 0; i < n; i++)
+        if (cfh[(size_t)i] == C_PT) dc.push_back(dh[(size_t)i]);
+      b.dof_coarse = std::move(dc);
+    }
+  }
 }
 
 // step 3: R where the Galerkin product reads it -- Lv.R on a host level, *b.dR on a device level.  The transpose of P,
@@ -2514,6 +2667,8 @@ void BoomerAMG::build_natural(ParCSR &A0) {
   L[0].A = &A0;
   if (pending_sA0.nrows == A0.nrows && pending_sA0.nrows > 0 && A0.host_diag_stale) L[0].sA = std::move(pending_sA0);
   pending_sA0.release();
+  if (p.num_functions > 1) L[0].dof = std::move(pending_dof);
+  pending_dof = std::vector<int>();
 
   int l = 0;
   stopped_by_rows = false;
@@ -2525,6 +2680,7 @@ void BoomerAMG::build_natural(ParCSR &A0) {
     LevelBuild b(l, L[(size_t)l], p, device_min_rows);
     b.begin("strength + coarsening");
     b.lap();
+    level_same_function_operator(b);  // (charged to the strength phase)
     level_strength_and_coarsening(b);
     long long nc_glob = b.count_c_points();
     comm.allreduce_host(&nc_glob, 1, CommDType::I64, CommOp::SUM);
@@ -2538,6 +2694,7 @@ void BoomerAMG::build_natural(ParCSR &A0) {
     b.begin("Galerkin product");
     if (b.on_device) level_restriction(b);  // a device level's to the Galerkin phase, beside the products that read it
     level_galerkin_and_adopt(b);
+    if (b.systems) L[(size_t)l + 1].dof = std::move(b.dof_coarse);
     l++;
   }
 }
@@ -3487,9 +3644,16 @@ void BoomerAMG::setup_device() {
       int loc = 0;
       BoomerAMG &o = owner_of(li, loc);
       const AmgLevel &Lv = o.L[(size_t)loc];
-      printf("   level %2d: local rows %10d  global rows %12lld  local nnz %12lld%s\n", li, Lv.n,
+      std::string per_function;  // num_functions > 1: the level's rows by the unknown they belong to
+      if (p.num_functions > 1 && Lv.dof.size() == (size_t)Lv.n) {
+        std::vector<long long> rows((size_t)p.num_functions, 0);
+        for (int d : Lv.dof.host()) rows[(size_t)d]++;
+        per_function = "  rows per function";
+        for (size_t f = 0; f < rows.size(); f++) per_function += (f ? " / " : " ") + std::to_string(rows[f]);
+      }
+      printf("   level %2d: local rows %10d  global rows %12lld  local nnz %12lld%s%s\n", li, Lv.n,
              (long long)Lv.A->global_rows(), (long long)(Lv.A->diag_nnz() + Lv.A->offd.nnz()),
-             &o != this ? "  (whole level on every rank)" : "");
+             &o != this ? "  (whole level on every rank)" : "", per_function.c_str());
     }
   }
 }
@@ -3517,8 +3681,8 @@ const char *const REBUILD_REASON[7] = {"reuse is off",
                                        "first Setup of this handle, or the previous one failed",
                                        "another matrix object or another pattern",
                                        "a setting the structure depends on changed since the last Setup",
-                                       "a setting the refresh does not cover is on (non-Galerkin tolerances, value storage, restriction 1 or "
-                                       "one-point interpolation)",
+                                       "a setting the refresh does not cover is on (non-Galerkin tolerances, value storage, restriction 1, "
+                                       "one-point interpolation or num_functions > 1)",
                                        "more than one rank",
                                        "the other setup entry point built the hierarchy"};
 }  // namespace
@@ -3547,6 +3711,7 @@ std::vector<double> BoomerAMG::current_structure_signature(const ParCSR &A) cons
   v.push_back((t0 == 3 || t0 == 4 || t0 == 6 || t0 == 8 || t0 == 13 || t0 == 14) ? 1.0 : 0.0);
   v.push_back(p.relax_type[2] == 9 ? 1.0 : 0.0);
   v.push_back((double)default_device_min_rows());
+  v.push_back((double)p.num_functions);
   return v;
 }
 
@@ -3560,6 +3725,7 @@ int BoomerAMG::refresh_verdict(const ParCSR &A, bool entry_host_only) const {
   // (the neighbourhoods and the filter of an approximate ideal restriction and the choice of one-point interpolation
   // depend on the values: their patterns are not kept)
   if (p.restriction != 0 || p.interp_type == 100) return 4;
+  if (p.num_functions > 1) return 4;  // (the refresh has no same-function operator, and dof_func may have changed)
   if (structure_signature != current_structure_signature(A)) return 3;
   return -1;
 }

@@ -20,6 +20,11 @@ struct Strength {
 
 void strength(const ParCSR &A, double theta, double max_row_sum, Strength &S);
 
+// the same-function operator F(A) of a square block (num_functions > 1; DESIGN.md section 3, "Systems of PDEs"): row i
+// keeps the entries a_ij with dof[j] == dof[i] and its diagonal, in stored order -- the host twin of
+// sk::same_function_filter
+void filter_same_function(const HostCSR &A, const std::vector<int> &dof, HostCSR &F);
+
 // The strength rule of ONE row (par_strength.c), stated once for the single-rank and the distributed setup: `a` = the
 // row's values, dpos = position of the diagonal among them (-1: none), `more` = further off-diagonal values that only
 // count for the row sum and the row scale (the halo block of a rank-local operator).  An entry v off the diagonal is

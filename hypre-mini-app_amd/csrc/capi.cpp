@@ -889,6 +889,33 @@ HYPRE_Int HYPRE_MI_OnePointInterpOp(HYPRE_Int on_host, HYPRE_Int n, const HYPRE_
   csr_to_caller(hp, n, p_ia, p_ja, p_a);
   API_END
 }
+// The same-function operator of a system with several unknowns on caller (host) arrays: the device kernel
+// sk::same_function_filter (on_host = 0) or the host routine hs::filter_same_function (on_host = 1, no device needed)
+HYPRE_Int HYPRE_MI_SameFunctionFilterOp(HYPRE_Int on_host, HYPRE_Int n, const HYPRE_BigInt *a_ia, const HYPRE_Int *a_ja,
+                                        const HYPRE_Complex *a_a, const HYPRE_Int *dof, HYPRE_BigInt **out_ia,
+                                        HYPRE_Int **out_ja, HYPRE_Complex **out_a) {
+  API_BEGIN
+  const std::string who = "SameFunctionFilterOp";
+  if (!a_ia || !dof || !out_ia || !out_ja || !out_a) fail(HYPRE_ERROR_ARG, who + ": NULL argument");
+  if (n < 1 || a_ia[0] != 0) fail(HYPRE_ERROR_ARG, who + ": bad dimensions");
+  if (a_ia[n] > 0 && !a_a) fail(HYPRE_ERROR_ARG, who + ": NULL values of A");
+  const HostCSR hA = csr_of(who, "A", n, n, a_ia, a_ja, a_a);
+  HostCSR hf;
+  if (on_host) {
+    hs::filter_same_function(hA, std::vector<int>(dof, dof + n), hf);
+  } else {
+    ensure_init();
+    hipStream_t s = ctx().stream;
+    sk::DCsr dA, dF;
+    dA.upload(hA, s);
+    DVec<int> ddof;
+    ddof.upload(std::vector<int>(dof, dof + n));
+    sk::same_function_filter(dA, ddof.p, dF, s);
+    dF.download(hf, s);
+  }
+  csr_to_caller(hf, n, out_ia, out_ja, out_a);
+  API_END
+}
 // setup-phase sparse kernels on caller (host) CSR arrays; results are malloc'ed (HYPRE_MI_Free)
 HYPRE_Int HYPRE_MI_CSRDeviceOp(HYPRE_Int op, HYPRE_Int a_nrows, HYPRE_Int a_ncols, const HYPRE_BigInt *a_ia,
                                const HYPRE_Int *a_ja, const HYPRE_Complex *a_a, HYPRE_Int b_nrows, HYPRE_Int b_ncols,
@@ -1243,6 +1270,20 @@ AMG_SET(RelaxOrder, HYPRE_Int, p.relax_order = v)
 AMG_SET(MaxLevels, HYPRE_Int, if (v < 1) fail(HYPRE_ERROR_ARG, "max_levels < 1"); p.max_levels = v)
 AMG_SET(StrongThreshold, HYPRE_Real, p.strong_threshold = v)
 AMG_SET(MaxRowSum, HYPRE_Real, p.max_row_sum = v)
+/* num_functions < 1 is refused at Setup, like the combinations unknown-based AMG is not built for */
+AMG_SET(NumFunctions, HYPRE_Int, p.num_functions = v)
+HYPRE_Int HYPRE_BoomerAMGGetNumFunctions(HYPRE_Solver solver, HYPRE_Int *num_functions) {
+  API_BEGIN
+  if (!num_functions) fail(HYPRE_ERROR_ARG, "BoomerAMGGetNumFunctions: NULL argument");
+  *num_functions = AMG(solver)->amg.p.num_functions;
+  API_END
+}
+/* host or device memory, read and copied at every Setup with num_functions > 1; never freed here (NULL: the default) */
+HYPRE_Int HYPRE_BoomerAMGSetDofFunc(HYPRE_Solver solver, HYPRE_Int *dof_func) {
+  API_BEGIN
+  AMG(solver)->amg.dof_func_user = dof_func;
+  API_END
+}
 AMG_SET(InterpType, HYPRE_Int, p.interp_type = v)  /* unknown types are refused at Setup, like every other choice */
 /* restriction: values the library does not build (2 and above, negative thresholds) are refused at Setup, by name */
 AMG_SET(Restriction, HYPRE_Int, p.restriction = v)
@@ -2343,6 +2384,17 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCF(HYPRE_Solver solver, HYPRE_Int level, HYP
   AmgSolver *a = AMG(solver);
   const auto &v = level_ref(a, level).cf;
   for (size_t i = 0; i < v.size(); i++) cf[i] = v[i];
+  API_END
+}
+HYPRE_Int HYPRE_MI_BoomerAMGGetLevelDofFunc(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int *dof) {
+  API_BEGIN
+  AmgSolver *a = AMG(solver);
+  AmgLevel &Lv = level_ref(a, level);
+  if (!dof) fail(HYPRE_ERROR_ARG, "GetLevelDofFunc: NULL argument");
+  if (Lv.dof.size() != (size_t)Lv.A->nrows)
+    fail(HYPRE_ERROR_ARG, "GetLevelDofFunc: the hierarchy was built with num_functions 1 and keeps no dof_func");
+  const std::vector<int> &v = Lv.dof.host();
+  std::copy(v.begin(), v.end(), dof);
   API_END
 }
 // diagonal and signed l1 norms of a level as the smoothers divide by them: from the host vectors of a level set up on

@@ -1985,6 +1985,59 @@ __global__ __launch_bounds__(BLK) void zero_guess_rows_k(int n, int nc, int chun
   if (!FILL && live && sub == 0) cnt[i] = c;
 }
 
+// ---------------------------------------------------------------- same-function operator (num_functions > 1)
+// Row i of F(A): the entries a_ij with dof[j] == dof[i], and the diagonal whatever dof says; stored order kept.
+// G lanes per row: coalesced reads of ja / a, dof[ja[k]] a 4-byte gather, kept entries written in stored order through
+// a ballot prefix (see strength_k).  FILL = false: count per row; FILL = true: write columns and values
+template <bool FILL, int G>
+__global__ __launch_bounds__(BLK) void same_function_rows_k(int n, const long long *__restrict__ ia,
+                                                            const int *__restrict__ ja, const double *__restrict__ a,
+                                                            const int *__restrict__ dof, int *__restrict__ cnt,
+                                                            const long long *__restrict__ fia, int *__restrict__ fja,
+                                                            double *__restrict__ fa) {
+  const long long i = (bid() * BLK + threadIdx.x) / G;
+  const int sub = threadIdx.x % G, lane = threadIdx.x & 63, gbase = lane - sub;
+  const bool live = i < n;
+  const long long k0 = live ? ia[i] : 0, k1 = live ? ia[i + 1] : 0;
+  const int mine_dof = live ? dof[i] : 0;
+  long long o = (FILL && live) ? fia[i] : 0;
+  int c = 0;
+  // the longest row of the wave decides the trip count (the ballot needs every lane)
+  long long len = k1 - k0;
+  for (int m = G; m < 64; m <<= 1) len = max(len, (long long)__shfl_xor((int)len, m, 64));
+  for (long long t = 0; t < len; t += G) {
+    const long long k = k0 + t + sub;
+    bool keep = false;
+    int j = -1;
+    if (k < k1) {
+      j = ja[k];
+      keep = (j == i) || dof[j] == mine_dof;
+    }
+    if (G == 1) {
+      if (keep) {
+        if (FILL) {
+          fja[o] = j;
+          fa[o] = a[k];
+        }
+        o++;
+        c++;
+      }
+    } else {
+      const unsigned long long bal = __ballot(keep);
+      const unsigned long long mine = (G == 64) ? bal : ((bal >> gbase) & ((1ull << G) - 1ull));
+      if (FILL && keep) {
+        const long long w = o + __popcll(mine & ((1ull << sub) - 1ull));
+        fja[w] = j;
+        fa[w] = a[k];
+      }
+      const int add = __popcll(mine);
+      o += add;
+      c += add;
+    }
+  }
+  if (!FILL && live && sub == 0) cnt[i] = c;
+}
+
 // lanes per row for the row-cooperative setup kernels: the power of two next to half the mean row length
 inline int row_group(long long nnz, long long n) {
   const double avg = n > 0 ? (double)nnz / (double)n : 0.0;
@@ -3552,6 +3605,48 @@ void mark_used_columns(const DCsr &A, DVec<unsigned char> &used, hipStream_t s) 
 void add_to_ints(int *v, int n, int add, hipStream_t s) {
   if (n && add) add_const_k<<<grid_for(((long long)n + BLK - 1) / BLK), BLK, 0, s>>>(n, v, add);
   MI_HIP(hipGetLastError());
+}
+
+void same_function_filter(const DCsr &A, const int *dof, DCsr &F, hipStream_t s) {
+  const int n = A.nrows;
+  F.release();
+  F.nrows = n;
+  F.ncols = A.ncols;
+  F.ia.alloc((size_t)n + 1);
+  DVec<int> cnt((size_t)n);
+  const int rg = row_group(A.nnz, n);
+  const dim3 grid = grid_for(((long long)n * rg + BLK - 1) / BLK);
+  if (n) {
+    MI_ROW_GROUP_DISPATCH(rg, (same_function_rows_k<false, G><<<grid, BLK, 0, s>>>(n, A.ia.p, A.ja.p, A.a.p, dof, cnt.p, nullptr, nullptr, nullptr)))
+  }
+  exclusive_scan(cnt.p, F.ia.p, n, s);
+  long long total = 0;
+  d2h(&total, F.ia.p + n, sizeof(long long), s);
+  MI_HIP(hipStreamSynchronize(s));
+  F.nnz = total;
+  F.ja.alloc((size_t)total);
+  F.a.alloc((size_t)total);
+  if (n && total) {
+    MI_ROW_GROUP_DISPATCH(rg, (same_function_rows_k<true, G><<<grid, BLK, 0, s>>>(n, A.ia.p, A.ja.p, A.a.p, dof, nullptr, F.ia.p, F.ja.p, F.a.p)))
+  }
+  MI_HIP(hipGetLastError());
+  MI_HIP(hipStreamSynchronize(s));
+}
+
+void gather_at_c_points(const int *cf, const int *v, int n, DVec<int> &out, hipStream_t s) {
+  DVec<long long> pos((size_t)n + 1);
+  DVec<int> flag((size_t)n);
+  if (n) is_c_k<<<grid_for(((long long)n + BLK - 1) / BLK), BLK, 0, s>>>(n, cf, flag.p);
+  exclusive_scan(flag.p, pos.p, n, s);
+  long long nc = 0;
+  d2h(&nc, pos.p + n, sizeof(long long), s);
+  MI_HIP(hipStreamSynchronize(s));
+  out.alloc((size_t)nc);
+  if (nc == 0) return;
+  DVec<int> list((size_t)nc);
+  compact_fill_k<<<grid_for(((long long)n + BLK - 1) / BLK), BLK, 0, s>>>(n, flag.p, pos.p, list.p);
+  gather_elems(v, list.p, 0, (int)nc, 4, out.p, s);
+  MI_HIP(hipStreamSynchronize(s));  // list is released on return
 }
 
 

@@ -32,6 +32,14 @@ struct DCsr {
 // keep nothing.  S has no values (S.a stays empty).
 void strength(const DCsr &A, double theta, double max_row_sum, DCsr &S, hipStream_t s);
 
+// The same-function operator F(A) of a system with several unknowns (num_functions > 1; DESIGN.md section 3, "Systems
+// of PDEs"): row i keeps the entries a_ij with dof[j] == dof[i] and its diagonal, in stored order -- bit for bit
+// hs::filter_same_function.  A is square, dof has A.nrows entries (device).  A count pass, a scan and a fill pass, the
+// lanes per row chosen by the mean row length like strength().
+void same_function_filter(const DCsr &A, const int *dof, DCsr &F, hipStream_t s);
+// out = v at the C points of cf (+1), in their order: the dof_func of the coarse level
+void gather_at_c_points(const int *cf, const int *v, int n, DVec<int> &out, hipStream_t s);
+
 // PMIS on the graph S: measure = |S^T row| + Park-Miller(seed) drawn in row order (hypre_Rand; element i is
 // computed directly as seed * 16807^(i+1) mod 2^31-1).  cf: +1 C, -1 F, -3 F without strong connections.
 void pmis(const DCsr &S, int seed, DVec<int> &cf, hipStream_t s);

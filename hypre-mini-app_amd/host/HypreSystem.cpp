@@ -375,6 +375,9 @@ void HypreSystem::setup_boomeramg_precond() {
       {"rap2", HYPRE_BoomerAMGSetRAP2},
       {"keep_transpose", HYPRE_BoomerAMGSetKeepTranspose},
       {"interp_type", HYPRE_BoomerAMGSetInterpType},
+      /* unknown-based systems AMG: the rows belong to num_functions unknowns, interleaved (dof_func = global row mod
+       * num_functions, HYPRE's default; the driver sets no other) */
+      {"num_functions", HYPRE_BoomerAMGSetNumFunctions},
       {"min_coarse_size", HYPRE_BoomerAMGSetMinCoarseSize},
       {"max_coarse_size", HYPRE_BoomerAMGSetMaxCoarseSize},
       {"pmax_elmts", HYPRE_BoomerAMGSetAggPMaxElmts}, /* sic: the reference routes it there, :210-213 */

@@ -274,6 +274,7 @@ class BoomerAMG:
         call("HYPRE_BoomerAMGSetMaxLevels", s, cfg["max_levels"])
         call("HYPRE_BoomerAMGSetStrongThreshold", s, float(cfg["strong_threshold"]))
         for key, fn, conv in (("interp_type", "HYPRE_BoomerAMGSetInterpType", int),
+                              ("num_functions", "HYPRE_BoomerAMGSetNumFunctions", int),  # unknown-based systems AMG
                               ("max_row_sum", "HYPRE_BoomerAMGSetMaxRowSum", float),
                               ("min_coarse_size", "HYPRE_BoomerAMGSetMinCoarseSize", int),
                               ("max_coarse_size", "HYPRE_BoomerAMGSetMaxCoarseSize", int),
@@ -323,6 +324,12 @@ class BoomerAMG:
                               ("true_pmax_elmts", "HYPRE_BoomerAMGSetPMaxElmts", int)):
             if key in cfg:
                 call(fn, s, conv(cfg[key]))
+        # dof_func: the unknown of every local row (int32 array; default global row mod num_functions).  The library
+        # reads it at Setup and never frees it: this object keeps the array alive
+        self.dof_func = None
+        if cfg.get("dof_func") is not None:
+            self.dof_func = np.ascontiguousarray(cfg["dof_func"], dtype=np.int32)
+            call("HYPRE_BoomerAMGSetDofFunc", s, self.dof_func)
         # this library's keys: value storage of the levels >= mi_value_storage_first_level (0 fp64, 1 fp32, 2 fp64
         # holding fp32-rounded values); absent keys leave the solver's defaults (MI_HYPRE_VALUE_STORAGE*)
         if "mi_value_storage" in cfg or "mi_value_storage_first_level" in cfg:
@@ -405,6 +412,20 @@ class BoomerAMG:
         cf = np.zeros(nr.value, dtype=np.int32)
         call("HYPRE_MI_BoomerAMGGetLevelCF", self.h, level, cf)
         return cf
+
+    @property
+    def num_functions(self):
+        k = c_int()
+        call("HYPRE_BoomerAMGGetNumFunctions", self.h, C.byref(k))
+        return k.value
+
+    def level_dof_func(self, level):
+        """The unknown of every row of a level built with num_functions > 1, level_cf's rows."""
+        nr, nc, nnz = c_int(), c_int(), c_big()
+        call("HYPRE_MI_BoomerAMGGetLevelCSRSize", self.h, level, 0, C.byref(nr), C.byref(nc), C.byref(nnz))
+        dof = np.zeros(nr.value, dtype=np.int32)
+        call("HYPRE_MI_BoomerAMGGetLevelDofFunc", self.h, level, dof)
+        return dof
 
     def level_norms(self, level):
         """(diagonal, signed l1 norm of the hybrid-GS chunks, signed full l1 norm) of a level, level_csr's rows."""
@@ -1262,6 +1283,21 @@ def one_point_interp_op(A, S, cf, host=False):
     call("HYPRE_MI_OnePointInterpOp", int(bool(host)), n, aia, aja, aa, sia, sja, m, C.byref(nc), C.byref(pia),
          C.byref(pja), C.byref(pa))
     return _csr_from_caller(n, pia, pja, pa) + ((n, nc.value),)
+
+
+def same_function_filter_op(A, dof, host=False):
+    """The same-function operator (HYPRE_MI_SameFunctionFilterOp) of a square scipy CSR operator A: row i keeps the
+    entries a_ij with dof[j] == dof[i] and its diagonal, by the device kernel or -- host=True -- the host routine.
+    Returns (ia int64, ja int32, a f64, shape)."""
+    n = A.shape[0]
+    aia = np.ascontiguousarray(A.indptr, dtype=np.int64)
+    aja = np.ascontiguousarray(A.indices, dtype=np.int32)
+    aa = np.ascontiguousarray(A.data, dtype=np.float64)
+    d = np.ascontiguousarray(dof, dtype=np.int32)
+    assert d.shape == (n,)
+    pia, pja, pa = vp(), vp(), vp()
+    call("HYPRE_MI_SameFunctionFilterOp", int(bool(host)), n, aia, aja, aa, d, C.byref(pia), C.byref(pja), C.byref(pa))
+    return _csr_from_caller(n, pia, pja, pa) + ((n, n),)
 
 
 VEC_MASS_DOT, VEC_MASS_AXPY, VEC_LIN_COMB, VEC_AXPY_DOT, VEC_SCALE_POST = range(5)

@@ -230,6 +230,13 @@ HYPRE_Int HYPRE_MI_OnePointInterpOp(HYPRE_Int on_host, HYPRE_Int n, const HYPRE_
                                     const HYPRE_Complex *a_a, const HYPRE_BigInt *s_ia, const HYPRE_Int *s_ja,
                                     const HYPRE_Int *cf, HYPRE_Int *p_ncols, HYPRE_BigInt **p_ia, HYPRE_Int **p_ja,
                                     HYPRE_Complex **p_a);
+/* ---- same-function operator of a system with several unknowns (HYPRE_BoomerAMGSetNumFunctions; DESIGN.md section 3,
+ * "Systems of PDEs") on caller (host) arrays: row i of the n x n matrix A keeps the entries a_ij with dof[j] == dof[i]
+ * and its diagonal, in stored order.  on_host = 0: the device kernel, 1: the host routine (no device needed).  The
+ * result is malloc'ed (HYPRE_MI_Free). */
+HYPRE_Int HYPRE_MI_SameFunctionFilterOp(HYPRE_Int on_host, HYPRE_Int n, const HYPRE_BigInt *a_ia, const HYPRE_Int *a_ja,
+                                        const HYPRE_Complex *a_a, const HYPRE_Int *dof, HYPRE_BigInt **out_ia,
+                                        HYPRE_Int **out_ja, HYPRE_Complex **out_a);
 /* how R of `level` was made: out[0] = 0 the transpose of P / 1 approximate ideal restriction built by the device / 2 by
  * the host routine; out[1] = the largest neighbourhood, out[2] = the C rows with an empty one, out[3] = the entries the
  * filter dropped */
@@ -242,7 +249,7 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetRestrictionInfo(HYPRE_Solver solver, HYPRE_Int le
  * GetSetupKind: kind 0 never set up, 1 built from scratch, 2 refreshed; reason (kind 1): 0 reuse is off, 1 first Setup
  * of this handle or the previous one failed, 2 another matrix object or pattern, 3 a setting the structure depends on
  * changed, 4 a setting the refresh does not cover is on (non-Galerkin tolerances, value storage,
- * restriction 1, interp_type 100), 5 more than one rank,
+ * restriction 1, interp_type 100, num_functions > 1), 5 more than one rank,
  * 6 the other setup entry point built the hierarchy.  Counters: "amg_setups_full", "amg_setups_refreshed". */
 HYPRE_Int HYPRE_MI_BoomerAMGSetSetupReuse(HYPRE_Solver solver, HYPRE_Int mode);
 HYPRE_Int HYPRE_MI_BoomerAMGGetSetupKind(HYPRE_Solver solver, HYPRE_Int *kind, HYPRE_Int *reason);
@@ -266,6 +273,9 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCSRSize(HYPRE_Solver solver, HYPRE_Int level
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCSR(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int which, HYPRE_BigInt *ia,
                                         HYPRE_Int *ja, HYPRE_Complex *a);
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCF(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int *cf);
+/* the unknown (0 ... num_functions - 1) every row of `level` belongs to, in GetLevelCF's row numbering; fails on a
+ * hierarchy built with num_functions 1, which keeps none */
+HYPRE_Int HYPRE_MI_BoomerAMGGetLevelDofFunc(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int *dof);
 /* What the smoothers of a level divide by, in GetLevelCSR's row numbering: the diagonal, the l1 norm of the hybrid
  * Gauss-Seidel chunks (C/F aware, replaced by |a_ii| where it is at most 4/3 of it) and the full l1 norm of the row;
  * both norms carry the sign of the diagonal.  Any array may be NULL. */

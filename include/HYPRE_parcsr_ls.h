@@ -31,6 +31,15 @@ HYPRE_Int HYPRE_BoomerAMGSetRelaxOrder(HYPRE_Solver solver, HYPRE_Int relax_orde
 HYPRE_Int HYPRE_BoomerAMGSetMaxLevels(HYPRE_Solver solver, HYPRE_Int max_levels);       /* :157 */
 HYPRE_Int HYPRE_BoomerAMGSetStrongThreshold(HYPRE_Solver solver, HYPRE_Real theta);     /* :158 */
 HYPRE_Int HYPRE_BoomerAMGSetMaxRowSum(HYPRE_Solver solver, HYPRE_Real max_row_sum);
+/* Unknown-based systems AMG: the rows belong to num_functions unknowns (default 1 = a scalar problem); dof_func[i] in
+ * [0, num_functions) names the unknown of local row i (default: global row mod num_functions).  Strength, splitting and
+ * interpolation of every level then ignore the entries that couple different unknowns.  dof_func
+ * may be host or device memory; it is read (local rows entries) and copied at every Setup, is ignored while
+ * num_functions is 1, and -- unlike libHYPRE, which takes ownership -- is never freed by the library: it must stay
+ * valid until the last Setup, and the caller frees it.  One rank, restriction 0; anything else is refused at Setup. */
+HYPRE_Int HYPRE_BoomerAMGSetNumFunctions(HYPRE_Solver solver, HYPRE_Int num_functions);
+HYPRE_Int HYPRE_BoomerAMGGetNumFunctions(HYPRE_Solver solver, HYPRE_Int *num_functions);
+HYPRE_Int HYPRE_BoomerAMGSetDofFunc(HYPRE_Solver solver, HYPRE_Int *dof_func);
 HYPRE_Int HYPRE_BoomerAMGSetInterpType(HYPRE_Solver solver, HYPRE_Int interp_type);     /* :196; 6 ext+i, 3 direct, 0 classical, 4 multipass,
                                                                                            * 16 / 17 extended / ext+i in matrix-matrix form,
                                                                                            * 100 one-point;
