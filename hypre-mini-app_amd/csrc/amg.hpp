@@ -168,6 +168,15 @@ struct AmgLevel {
     double a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
   } cheby;
   DVec<double> cheby_d;  // the direction vector d of the sweep (step 0 writes it before any step reads it)
+  // relax types 40 / 41 / 42 (multicolour Gauss-Seidel), on every level that is smoothed when some
+  // relax_type slot holds one at Setup (BoomerAMG::apply_cf_ordering): the rows of the C block and of the F block are
+  // sorted by colour.  range_start: the first rows of the (block, colour) ranges in stored order, and n at the end;
+  // range_colour: their colours; ranges_c: how many of them lie in the C block; rounds: launches of the colouring
+  struct Colours {
+    bool ready = false;
+    int colours = 0, rounds = 0, ranges_c = 0;
+    std::vector<int> range_start, range_colour;
+  } mc;
   DVec<double> ts_work;  // second work vector of the two-stage Gauss-Seidel (relax types 11 / 12), on first use
   // coarsest level dense solve (relax type 9)
   std::vector<double> Cinv_host;
@@ -336,6 +345,9 @@ struct BoomerAMG {
   bool wants_cheby() const { return p.relax_type[0] == 16 || p.relax_type[1] == 16 || p.relax_type[2] == 16; }
   std::vector<double> cheby_signature;
   std::vector<double> current_cheby_signature() const;
+  // relax types 40 / 41 / 42 in some slot: Setup colours the levels and sorts their rows by (block, colour)
+  static bool is_mcgs(int type) { return type >= 40 && type <= 42; }
+  bool wants_mcgs() const { return is_mcgs(p.relax_type[0]) || is_mcgs(p.relax_type[1]) || is_mcgs(p.relax_type[2]); }
   void refresh_cheby();
   // cycle(level, true) never reads Lv.u before it has overwritten every row (one rank, Gauss-Seidel down sweep on
   // the zero-skipping kernels, or the dense coarsest solve): the caller need not zero-fill u first -- at 512^3 the

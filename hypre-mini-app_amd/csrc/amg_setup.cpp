@@ -1595,6 +1595,77 @@ void BoomerAMG::apply_cf_ordering() {
       }
     });
   }
+  // Relax types 40 / 41 / 42 (multicolour Gauss-Seidel): every level that is smoothed is coloured
+  // -- the graph of D + D^T, D the level operator in the C-first numbering found above -- and the rows of its C block
+  // and of its F block are sorted stably by colour; perm and the positions become those of the composed ordering, so
+  // everything below (A, P, R, the marker, dof_func, the coarse numbering through P's columns) follows it.  A level
+  // without a splitting (the coarsest) is one block.  The colouring and the sort run on the device, also for a level
+  // the host routines built (its operator is uploaded for it).
+  if (wants_mcgs()) {
+    MI_REQUIRE(comm.size == 1, "multicolour Gauss-Seidel: one rank only");
+    double t_colour = 0.0, t_sort = 0.0;
+    for (size_t l = 0; l < nlev; l++) {
+      AmgLevel &Lv = L[l];
+      Lv.mc = AmgLevel::Colours();
+      const int n = Lv.A->nrows;
+      // the coarsest level when relax type 9 will solve it densely (build_coarsest_inverse) is not smoothed
+      if (l + 1 == nlev && !tail && p.relax_type[2] == 9 && Lv.A->global_rows() <= MAX_DENSE && n > 0) continue;
+      hipStream_t s = ctx().stream;
+      double t0 = wall_time();
+      sk::DCsr uploaded, cfirst;
+      const sk::DCsr *D = &Lv.sA;
+      if (!(Lv.sA.nrows == n && Lv.sA.ia.p)) {
+        fetch_operator(Lv.A, Lv.sA);  // (an operator only the solve format holds, e.g. the caller's device-assembled matrix)
+        uploaded.upload(Lv.A->diag, s);
+        D = &uploaded;
+      }
+      if (has_pos[l]) {
+        sk::permute(*D, Lv.perm.dev(), dpos(l), cfirst, s);
+        D = &cfirst;
+      }
+      int kind = 0;
+      const long long bad = sk::mcgs_bad_diagonal(*D, kind, s);
+      if (bad >= 0) {
+        long long row = has_pos[l] ? (long long)Lv.perm.host()[(size_t)bad] : bad;
+        if (l == 0 && !input_order.empty()) row = input_order.host()[(size_t)row];
+        fail(1, "BoomerAMGSetup: relax_type 40 / 41 / 42 (multicolour Gauss-Seidel): level " + std::to_string(l) + ", row " +
+                    std::to_string(row) + " (the level's numbering before its ordering; level 0: the caller's local row) " +
+                    (kind == 0 ? "stores no diagonal entry" : "stores a zero diagonal entry") +
+                    "; refusing to smooth with something else");
+      }
+      DVec<int> colour;
+      int rounds = 0;
+      if (sk::ilu_multicolour(*D, colour, rounds, s) != 0)  // (no input reaches this: see IluSolver::multicolour_order)
+        fail(1, "BoomerAMGSetup: the multicolour ordering of level " + std::to_string(l) + " left rows uncoloured after " +
+                    std::to_string(n) + " rounds, one per row");
+      MI_HIP(hipStreamSynchronize(s));
+      t_colour += wall_time() - t0;
+      t0 = wall_time();
+      DVec<int> order;
+      sk::mcgs_order(colour.p, n, has_pos[l] ? Lv.nc : 0, order, Lv.mc.range_start, Lv.mc.range_colour, Lv.mc.colours,
+                     Lv.mc.ranges_c, s);
+      Lv.mc.rounds = rounds;
+      if (has_pos[l]) {  // stored row q is C-first row order[q], the level's row perm[order[q]]
+        DVec<int> composed((size_t)n);
+        sk::gather_elems(Lv.perm.dev(), order.p, 0, n, 4, composed.p, s);
+        order = std::move(composed);
+      } else {
+        Lv.nc = 0;
+      }
+      pos[l].clear();
+      posd[l].alloc((size_t)n);
+      sk::invert_permutation(order.p, n, posd[l].p, s);
+      MI_HIP(hipStreamSynchronize(s));
+      Lv.perm.adopt_device(std::move(order), (size_t)n);
+      has_pos[l] = 1;
+      Lv.mc.ready = true;
+      t_sort += wall_time() - t0;
+      if (timing)
+        printf("   multicolour ordering: level %zu: n %d, %d colours in %d rounds, %d + %d (block, colour) ranges\n", l, n,
+               Lv.mc.colours, rounds, Lv.mc.ranges_c, (int)Lv.mc.range_colour.size() - Lv.mc.ranges_c);
+    }
+    if (timing) printf("   multicolour ordering: colouring %.3f s, sort %.3f s\n", t_colour, t_sort);
+  }
   trace_pos.reset();
   if (timing) printf("   C-first ordering: positions %.2f s\n", wall_time() - tcf0);
   auto sort_rows = [](HostCSR &M) {
@@ -2025,10 +2096,17 @@ void BoomerAMG::validate_settings() const {
   for (int k = 0; k < 3; k++) {
     const int t = p.relax_type[k];
     const bool known = t == 0 || t == 7 || t == 18 || t == 3 || t == 4 || t == 6 || t == 8 || t == 13 || t == 14 ||
-                       t == 11 || t == 12 || t == 9 || t == 16;
+                       t == 11 || t == 12 || t == 9 || t == 16 || is_mcgs(t);
     if (!known)
       fail(4, "BoomerAMGSetup: relax_type " + std::to_string(t) +
-                  " is not implemented (0, 3, 4, 6, 7, 8, 9, 11, 12, 13, 14, 16, 18 are); refusing to smooth with something else");
+                  " is not implemented (0, 3, 4, 6, 7, 8, 9, 11, 12, 13, 14, 16, 18, 40, 41, 42 are); refusing to smooth with "
+                  "something else");
+    if (is_mcgs(t) && my_comm().size > 1)
+      fail(4, "BoomerAMGSetup: relax_type " + std::to_string(t) + " (multicolour Gauss-Seidel) is not implemented on more than "
+                  "one rank (" + std::to_string(my_comm().size) + " ranks); refusing to smooth with something else");
+    if (is_mcgs(t) && host_only)
+      fail(4, "BoomerAMGSetup: relax_type " + std::to_string(t) + " (multicolour Gauss-Seidel) is not implemented by the "
+                  "host-only setup (the colouring is device code); refusing to smooth with something else");
     if (t == 16 && host_only)
       fail(4, "BoomerAMGSetup: relax_type 16 (Chebyshev) is not implemented by the host-only setup, which has no eigenvalue "
               "estimate (that is device code); refusing to smooth with something else");
@@ -3712,6 +3790,7 @@ std::vector<double> BoomerAMG::current_structure_signature(const ParCSR &A) cons
   v.push_back(p.relax_type[2] == 9 ? 1.0 : 0.0);
   v.push_back((double)default_device_min_rows());
   v.push_back((double)p.num_functions);
+  v.push_back(wants_mcgs() ? 1.0 : 0.0);  // (the levels are coloured and ordered by colour: relax types 40 / 41 / 42)
   return v;
 }
 

@@ -42,16 +42,22 @@ int relax_prof_id(int level, bool zero_guess) {
   if (level == 0 && t && t->enabled[k::PROF_RELAX_L0]) return k::PROF_RELAX_L0;
   return k::prof_level(k::PROF_LVL_RELAX, level);
 }
+// the colour passes of relax types 40 / 41 / 42: bench.py's level-0 class when relax_prof_id chose it, else their own
+int mcgs_prof_id(int level, int relax_prof) {
+  return relax_prof == k::PROF_RELAX_L0 ? relax_prof : k::prof_level(k::PROF_LVL_RELAX_MC, level);
+}
 struct GsKind {
   bool jacobi, l1, fwd, bwd;
   int two_stage;  // relax types 11 / 12: inner iterations of the two-stage Gauss-Seidel
   bool cheby;     // relax type 16
+  int mcgs;       // relax types 40 / 41 / 42 (multicolour Gauss-Seidel): 1 forward, 2 backward, 3 forward then backward
 };
 GsKind classify(int type) {
   GsKind g{};
   g.two_stage = (type == 11) ? 1 : (type == 12) ? 2 : 0;
   g.cheby = type == 16;
-  if (g.two_stage || g.cheby) return g;
+  g.mcgs = BoomerAMG::is_mcgs(type) ? type - 39 : 0;
+  if (g.two_stage || g.cheby || g.mcgs) return g;
   g.jacobi = (type == 0 || type == 7 || type == 18);
   g.l1 = (type == 8 || type == 13 || type == 14 || type == 18);
   g.fwd = (type == 3 || type == 6 || type == 8 || type == 13);
@@ -224,6 +230,27 @@ void BoomerAMG::relax(int level, int type, int points, const double *f, bool u_i
     }
     return;
   }
+  if (g.mcgs) {
+    // exact Gauss-Seidel on the diag block in the stored row order, one in-place pass per (block,
+    // colour) range -- the rows of a range do not couple.  The C/F marker, relax_order, outer_weight and the l1 norms
+    // play no part; a zero guess takes the general sweep (zero_cycle_ignores_u: u was filled).
+    if (comm.size > 1)
+      fail(4, "BoomerAMG: relax type " + std::to_string(type) + " (multicolour Gauss-Seidel) is not implemented on more than one rank");
+    if (!Lv.mc.ready)
+      fail(4, "BoomerAMG: relax type " + std::to_string(type) + " (multicolour Gauss-Seidel) on level " + std::to_string(level) +
+                  ", but the level was not coloured: the relax type was set after a Setup that saw no relax_type 40 / 41 / 42 "
+                  "(or the level is solved densely); a Setup is needed -- call HYPRE_BoomerAMGSetup again");
+    const std::vector<int> &rs = Lv.mc.range_start;
+    const int nr = (int)rs.size() - 1;
+    const int mprof = mcgs_prof_id(level, prof);
+    if (g.mcgs & 1)
+      for (int r = 0; r < nr; r++)
+        k::inplace_pass(A.d_diag, u, f, nullptr, Lv.d_diag.p, p.relax_weight, rs[(size_t)r], rs[(size_t)r + 1], s, mprof);
+    if (g.mcgs & 2)
+      for (int r = nr - 1; r >= 0; r--)
+        k::inplace_pass(A.d_diag, u, f, nullptr, Lv.d_diag.p, p.relax_weight, rs[(size_t)r], rs[(size_t)r + 1], s, mprof);
+    return;
+  }
   if (g.jacobi) {
     // a zero vector has a zero halo: no exchange, no halo contribution
     const double *offc = u_is_zero ? nullptr : A.offd_contrib(comm, u, s);
@@ -256,7 +283,7 @@ void BoomerAMG::relax(int level, int type, int points, const double *f, bool u_i
 void BoomerAMG::relax_pair(int level, int type, int first, const double *f, bool u_is_zero) {
   AmgLevel &Lv = L[(size_t)level];
   const GsKind g = classify(type);
-  if (g.cheby) {  // a Chebyshev sweep is not split into a C and an F half
+  if (g.cheby || g.mcgs) {  // a Chebyshev or a multicolour Gauss-Seidel sweep is not split into a C and an F half
     relax(level, type, 0, f, u_is_zero);
     return;
   }
@@ -386,6 +413,7 @@ bool BoomerAMG::zero_cycle_ignores_u(int level) {
   if (Lv.smoother || p.num_sweeps[0] < 1 || zero_skip_mode() < 1) return false;
   const int type = p.relax_type[0];
   if (type == 9 || type == 11 || type == 12) return false;
+  if (is_mcgs(type)) return false;  // the sweep reads u in place: the general sweep on a vector of zeros
   if (type == 16) return Lv.cheby.ready;  // step 0 on a zero guess: u = d = b0 f / diag overwrites every row
   const GsKind g = classify(type);
   if (g.jacobi || !(g.fwd || g.bwd)) return false;

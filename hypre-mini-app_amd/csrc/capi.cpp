@@ -2397,6 +2397,26 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetLevelDofFunc(HYPRE_Solver solver, HYPRE_Int level
   std::copy(v.begin(), v.end(), dof);
   API_END
 }
+// the colouring of a level set up with relax type 40 / 41 / 42 in some slot: info = colours, colouring rounds, (block,
+// colour) ranges in the C block, ranges in the F block; colour (nullable): the colour of every row in stored order
+HYPRE_Int HYPRE_MI_BoomerAMGGetLevelColours(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int info[4], HYPRE_Int *colour) {
+  API_BEGIN
+  AmgSolver *a = AMG(solver);
+  const AmgLevel &Lv = level_ref(a, level);
+  if (!info) fail(HYPRE_ERROR_ARG, "GetLevelColours: NULL argument");
+  if (!Lv.mc.ready)
+    fail(HYPRE_ERROR_ARG, "GetLevelColours: the level was not coloured (Setup saw no relax_type 40 / 41 / 42, or the level is "
+                          "solved densely)");
+  const int nr = (int)Lv.mc.range_colour.size();
+  info[0] = Lv.mc.colours;
+  info[1] = Lv.mc.rounds;
+  info[2] = Lv.mc.ranges_c;
+  info[3] = nr - Lv.mc.ranges_c;
+  if (colour)
+    for (int r = 0; r < nr; r++)
+      for (int i = Lv.mc.range_start[(size_t)r]; i < Lv.mc.range_start[(size_t)r + 1]; i++) colour[i] = Lv.mc.range_colour[(size_t)r];
+  API_END
+}
 // diagonal and signed l1 norms of a level as the smoothers divide by them: from the host vectors of a level set up on
 // the host, from the device vectors of a level set up on the device
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelNorms(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Real *diag, HYPRE_Real *l1gs,
@@ -2511,6 +2531,8 @@ HYPRE_Int HYPRE_MI_BoomerAMGRelaxLevel(HYPRE_Solver solver, HYPRE_Int level, HYP
   AmgSolver *a = AMG(solver);
   if (!a->amg.is_setup) fail(HYPRE_ERROR_GENERIC, "RelaxLevel: AMG is not set up");
   if (level < 0 || level >= (int)a->amg.L.size()) fail(HYPRE_ERROR_ARG, "AMG level out of range");
+  if (BoomerAMG::is_mcgs(relax_type) && points != 0)
+    fail(HYPRE_ERROR_ARG, "RelaxLevel: relax type 40 / 41 / 42 (multicolour Gauss-Seidel) sweeps all rows: points must be 0");
   AmgLevel &Lv = a->amg.L[(size_t)level];
   const int n = Lv.n;
   DVec<double> f((size_t)n);
@@ -2671,7 +2693,8 @@ HYPRE_Int HYPRE_MI_SolveKernelChoice(HYPRE_Int family, HYPRE_Int xcache, HYPRE_I
   if (!name || max_len < 1) fail(HYPRE_ERROR_ARG, "SolveKernelChoice: no buffer");
   if (family != 0 && family != 1) fail(HYPRE_ERROR_ARG, "SolveKernelChoice: family must be 0 (SpMV / Jacobi) or 1 (hybrid GS)");
   if (tile_entries != k::SPMV_TILE && tile_entries != k::SPMV_TILE_WIDE) fail(HYPRE_ERROR_ARG, "SolveKernelChoice: tile_entries must be 2048 or 4096");
-  if (epilogue != 0 && epilogue != 1) fail(HYPRE_ERROR_ARG, "SolveKernelChoice: epilogue must be 0 or 1");
+  if (epilogue != 0 && epilogue != 1 && epilogue != 3)
+    fail(HYPRE_ERROR_ARG, "SolveKernelChoice: epilogue must be 0, 1 or 3 (the in-place colour pass)");
   if (chunk < 1 || chunk > k::GS_MAX_CHUNK) fail(HYPRE_ERROR_ARG, "SolveKernelChoice: chunk out of range");
   if (nnz < 0 || nrows < 1 || rowlen_p95 < 0) fail(HYPRE_ERROR_ARG, "SolveKernelChoice: an operator has nnz >= 0, nrows >= 1, rowlen_p95 >= 0");
   k::SolveKernelDesc d;

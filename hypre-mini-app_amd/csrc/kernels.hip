@@ -79,6 +79,11 @@ __device__ __forceinline__ int xcd_remap(int bid, int chunk) { return (bid & 7) 
 // EPI 0: y = alpha*s + beta*b          (matvec / residual / restrict / prolong)
 // EPI 1: masked Jacobi  y = x_i + w*(f - offc - s)/d on selected rows, else x_i
 // EPI 2: Chebyshev step dc_i = ca*dc_i + cb*((f - s - offc)/d), y = x_i + dc_i  (relax type 16)
+// EPI 3: in-place pass over the rows [row_begin, row_end) of one colour (relax types 40-42):
+//        u_i += w*(f - offc - s)/d.  The vector is gathered and written through EpiArgs::u alone -- the kernels'
+//        x and y, which promise not to alias, are not used -- and only the tiles from blk0 on are launched; a tile that
+//        straddles an end of the range computes all its rows and writes those inside.  The rows of the range do not
+//        couple (colouring of D + D^T), so no workgroup gathers an entry another one writes for a row it keeps.
 // ---------------------------------------------------------------------------
 struct EpiArgs {
   double alpha, beta;      // EPI 0
@@ -92,13 +97,21 @@ struct EpiArgs {
   int b_split;             //   side: BoomerAMG's residual after a zero-guess sweep, f for the C rows, f - A_FC u_C after)
   double *dc;              // EPI 2: the Chebyshev direction vector, updated in place (b = f, offc, d as for EPI 1)
   double ca, cb;           // EPI 2: the step's coefficients (ca == 0: step 0, dc is not read)
+  double *u;               // EPI 3: the vector, read and written in place (b = f, offc, d, alpha = w as for EPI 1)
+  int row_begin, row_end;  // EPI 3: the rows that are written
+  int blk0;                // EPI 3: the first tile of the launch
 };
 __device__ __forceinline__ double epi_b(const EpiArgs &e, int ro) { return ((e.b_lo && ro < e.b_split) ? e.b_lo : e.b)[ro]; }
 
 template <int EPI>
 __device__ __forceinline__ void epilogue(int r, double s, const double *__restrict__ x, double *__restrict__ y,
                                          const EpiArgs &e) {
-  if (EPI == 0) {
+  if (EPI == 3) {
+    if (r < e.row_begin || r >= e.row_end) return;
+    double res = e.b[r] - s;
+    if (e.offc) res -= e.offc[r];
+    e.u[r] = e.u[r] + e.alpha * res / e.d[r];
+  } else if (EPI == 0) {
     // y is written once and next read by another kernel: keep it out of L2's way
     const int ro = e.rowmap ? e.rowmap[r] : r;
     __builtin_nontemporal_store((e.beta == 0.0) ? e.alpha * s : e.alpha * s + e.beta * epi_b(e, ro), y + ro);
@@ -136,15 +149,18 @@ __global__ __launch_bounds__(SPMV_BLOCK) void spmv_stream(int nb, int xchunk, co
                                                           const VT *__restrict__ av, const double *__restrict__ x,
                                                           double *__restrict__ y, EpiArgs e) {
   __shared__ double prod[SPMV_TILE];
-  const int blk = xcd_remap(blockIdx.x, xchunk);
+  int blk = xcd_remap(blockIdx.x, xchunk);
   if (blk >= nb) return;
+  if (EPI == 3) blk += e.blk0;  // nb tiles from e.blk0 on
+  // the gathered vector: x, or (EPI 3) the in-place vector, a pointer that carries no promise about aliasing
+  const double *xg = (EPI == 3) ? e.u : x;
   const int tid = threadIdx.x;
   const int r0 = rb[blk], r1 = rb[blk + 1];
   const int base = ia[r0], end = ia[r1];
   if (end - base >= SPMV_TILE) {
     // one long row: every lane strides over it, two-level reduction
     double s = 0.0;
-    for (int k = base + tid; k < end; k += SPMV_BLOCK) s += (double)av[k] * x[ja[k]];
+    for (int k = base + tid; k < end; k += SPMV_BLOCK) s += (double)av[k] * xg[ja[k]];
     s = wave_sum(s);
     if ((tid & 63) == 0) prod[tid >> 6] = s;
     __syncthreads();
@@ -160,8 +176,8 @@ __global__ __launch_bounds__(SPMV_BLOCK) void spmv_stream(int nb, int xchunk, co
     const i2_t c = nt_load(reinterpret_cast<const i2_t *>(ja + base_al + k));
     const bool ok0 = (base_al + k >= base);
     const bool ok1 = (base_al + k + 1 < end);
-    const double x0 = ok0 ? x[c.x] : 0.0;
-    const double x1 = ok1 ? x[c.y] : 0.0;
+    const double x0 = ok0 ? xg[c.x] : 0.0;
+    const double x1 = ok1 ? xg[c.y] : 0.0;
     prod[k] = (double)v.x * x0;
     if (k + 1 < SPMV_TILE) prod[k + 1] = (double)v.y * x1;
   }
@@ -218,8 +234,11 @@ __global__ __launch_bounds__(BLOCK) void spmv_stream_xc(int nb, int xchunk, cons
   __shared__ double prod[TILE];
   __shared__ double slut[VAL8 ? 256 : 1];
   double *xs = prod;
-  const int blk = xcd_remap(blockIdx.x, xchunk);
+  int blk = xcd_remap(blockIdx.x, xchunk);
   if (blk >= nb) return;
+  if (EPI == 3) blk += e.blk0;  // nb tiles from e.blk0 on
+  // the gathered vector: x, or (EPI 3) the in-place vector, a pointer that carries no promise about aliasing
+  const double *xg = (EPI == 3) ? e.u : x;
   const int tid = threadIdx.x;
   if (MI_ABLATE & 128) {  // launch only
     if (tid == 0 && blk == nb + 1) y[0] = 0.0;
@@ -242,9 +261,9 @@ __global__ __launch_bounds__(BLOCK) void spmv_stream_xc(int nb, int xchunk, cons
     double s = 0.0;
     if (VAL4) {
       const float *av4 = reinterpret_cast<const float *>(av);
-      for (long long k = base64 + tid; k < base64 + len; k += BLOCK) s += (double)av4[k] * x[ja[k]];
+      for (long long k = base64 + tid; k < base64 + len; k += BLOCK) s += (double)av4[k] * xg[ja[k]];
     } else {
-      for (long long k = base64 + tid; k < base64 + len; k += BLOCK) s += av[k] * x[ja[k]];
+      for (long long k = base64 + tid; k < base64 + len; k += BLOCK) s += av[k] * xg[ja[k]];
     }
     s = wave_sum(s);
     if ((tid & 63) == 0) prod[tid >> 6] = s;
@@ -303,7 +322,7 @@ __global__ __launch_bounds__(BLOCK) void spmv_stream_xc(int nb, int xchunk, cons
   // up to eight serial round trips per tile.  Lanes beyond the list read x[0] -- uc is 0 there -- one cached sector.)
   double xv[NU];
 #pragma unroll
-  for (int q = 0; q < NU; q++) xv[q] = x[(MI_ABLATE & 1) ? min(uc[q], 63) : uc[q]];
+  for (int q = 0; q < NU; q++) xv[q] = xg[(MI_ABLATE & 1) ? min(uc[q], 63) : uc[q]];
   // the entry range of the first row a thread sums (operators that the tile Gauss-Seidel kernel also sweeps have
   // <= BLOCK rows per tile: one row per thread; SpMV-only operators with short rows -- P, R, the residual
   // sub-operator -- get up to 4 x BLOCK rows to fill their tiles)
@@ -1884,8 +1903,25 @@ KernelChoice choose_stream_kernel(const SolveKernelDesc &d) {
       MI_KERNEL(spmv_stream<2, 0, float>)};
   static const KernelEntry<StreamKernel<double>> plain[4] = {MI_KERNEL(spmv_stream<0, 1>), MI_KERNEL(spmv_stream<0, 0>),
                                                              MI_KERNEL(spmv_stream<1, 0>), MI_KERNEL(spmv_stream<2, 0>)};
-  MI_REQUIRE(d.epi >= 0 && d.epi <= 2, "choose_stream_kernel: the epilogue is 0, 1 or 2");
+  // EPI 3, the in-place colour pass of relax types 40-42: tables of their own, named after the others, so that the
+  // kernels above are emitted in the order they always were.  [ValueFormat]
+  static const KernelEntry<XcKernel> xc_wide_inplace[3] = {MI_KERNEL(spmv_stream_xc<3, 0, false, 512, true>),
+                                                           MI_KERNEL(spmv_stream_xc<3, 0, true, 512>),
+                                                           MI_KERNEL(spmv_stream_xc<3, 0, false, 512>)};
+  static const KernelEntry<XcKernel> xc_inplace[3] = {MI_KERNEL(spmv_stream_xc<3, 0, false, 256, true>),
+                                                      MI_KERNEL(spmv_stream_xc<3, 0, true, 256>),
+                                                      MI_KERNEL(spmv_stream_xc<3, 0, false, 256>)};
+  static const KernelEntry<StreamKernel<float>> plain32_inplace = MI_KERNEL(spmv_stream<3, 0, float>);
+  static const KernelEntry<StreamKernel<double>> plain_inplace = MI_KERNEL(spmv_stream<3, 0>);
+  MI_REQUIRE(d.epi >= 0 && d.epi <= 3, "choose_stream_kernel: the epilogue is 0, 1, 2 or 3");
   const int fmt = (int)d.format;
+  if (d.epi == 3) {
+    if (d.xcache)
+      return chosen(d.tile_entries == SPMV_TILE_WIDE ? xc_wide_inplace[fmt] : xc_inplace[fmt], KernelFamily::STREAM_XC,
+                    tile_block(d.tile_entries));
+    if (d.format == ValueFormat::FP32) return chosen(plain32_inplace, KernelFamily::STREAM, SPMV_BLOCK);
+    return chosen(plain_inplace, KernelFamily::STREAM, SPMV_BLOCK);
+  }
   const int epi_tag = d.epi == 2 ? 3 : d.epi == 1 ? 2 : d.level0 ? 0 : 1;
   if (d.xcache)
     return chosen(d.tile_entries == SPMV_TILE_WIDE ? xc_wide[fmt][d.epi] : xc[fmt][epi_tag], KernelFamily::STREAM_XC,
@@ -1910,13 +1946,13 @@ static void launch_on_values(const DevCSR &A, const KernelChoice &c, Launch laun
 
 // returns the name of the instantiation it launched
 static const char *launch_stream(int epi, const DevCSR &A, const double *x, double *y, const EpiArgs &e, hipStream_t s,
-                                 bool level0 = false) {
+                                 bool level0 = false, int ntiles = 0) {
   if (A.nrows == 0) return "";
   MI_REQUIRE(A.xcache || !A.big(), "an operator with 2^31 entries or more must be in the x-cache tile format");
   // (fp32 value storage, k::narrow_values: `a` is gone, the kernels stream a32)
   MI_REQUIRE(A.value_format() == ValueFormat::FP32 || A.a.p || A.nnz == 0, "SpMV: the operator holds no value array");
   const KernelChoice c = choose_stream_kernel({A.xcache, A.tile_entries, A.value_format(), epi, level0});
-  const int nb = A.nblocks;
+  const int nb = epi == 3 ? ntiles : A.nblocks;  // (EPI 3: the tiles [e.blk0, e.blk0 + ntiles))
   const int xchunk = (nb + 7) / 8;
   const dim3 grid(xchunk * 8), block(c.block);
   if (c.family == KernelFamily::STREAM_XC) {
@@ -2066,6 +2102,31 @@ void cheby_step(const DevCSR &A, const double *u_old, double *u_new, double *dc,
   e.cb = b;
   prof_begin(prof, s);
   prof_name(prof, launch_stream(2, A, u_old, u_new, e, s));
+  prof_end(prof, s);
+}
+
+void inplace_pass(const DevCSR &A, double *u, const double *f, const double *offc, const double *d, double w,
+                  int row_begin, int row_end, hipStream_t s, int prof) {
+  row_begin = std::max(row_begin, 0);
+  row_end = std::min(row_end, A.nrows);
+  if (A.nrows == 0 || row_end <= row_begin) return;
+  const std::vector<int> &rbh = A.rb_host;
+  MI_REQUIRE((int)rbh.size() == A.nblocks + 1, "in-place pass: the operator has no host copy of its tile schedule");
+  // the tiles that intersect the range: the last one that starts at or before row_begin ... the first that starts at or after row_end
+  const int b0 = (int)(std::upper_bound(rbh.begin(), rbh.end(), row_begin) - rbh.begin()) - 1;
+  const int b1 = (int)(std::lower_bound(rbh.begin(), rbh.end(), row_end) - rbh.begin());
+  MI_REQUIRE(b0 >= 0 && b1 > b0 && b1 <= A.nblocks, "in-place pass: the row range lies outside the tile schedule");
+  EpiArgs e{};
+  e.alpha = w;
+  e.b = f;
+  e.offc = offc;
+  e.d = d;
+  e.u = u;
+  e.row_begin = row_begin;
+  e.row_end = row_end;
+  e.blk0 = b0;
+  prof_begin(prof, s);
+  prof_name(prof, launch_stream(3, A, nullptr, nullptr, e, s, false, b1 - b0));
   prof_end(prof, s);
 }
 

@@ -41,7 +41,8 @@ enum ProfId {
   PROF_LVL_RESTRICT = PROF_LVL_RELAX + PROF_LEVELS,
   PROF_LVL_PROLONG = PROF_LVL_RESTRICT + PROF_LEVELS,
   PROF_LVL_RELAX0 = PROF_LVL_PROLONG + PROF_LEVELS,  // first sweep on a zero guess (runs on the sub-operator)
-  PROF_COUNT = PROF_LVL_RELAX0 + PROF_LEVELS
+  PROF_LVL_RELAX_MC = PROF_LVL_RELAX0 + PROF_LEVELS,  // colour passes of relax types 40 / 41 / 42 (one launch per range)
+  PROF_COUNT = PROF_LVL_RELAX_MC + PROF_LEVELS
 };
 inline int prof_level(int base, int level) { return level < PROF_LEVELS ? base + level : PROF_NONE; }
 
@@ -157,7 +158,7 @@ struct SolveKernelDesc {
   bool xcache = false;
   int tile_entries = SPMV_TILE;
   ValueFormat format = ValueFormat::FP64;
-  int epi = 0;          // SpMV family: 0 mat-vec, 1 masked Jacobi, 2 Chebyshev step
+  int epi = 0;          // SpMV family: 0 mat-vec, 1 masked Jacobi, 2 Chebyshev step, 3 in-place colour pass
   bool level0 = false;  // SpMV family: launched under the profiler's level-0 class
   // hybrid Gauss-Seidel family
   int chunk = 8;
@@ -194,6 +195,13 @@ void jacobi(const DevCSR &A, const double *u_old, double *u_new, const double *f
 // dc is updated in place (row i's finishing lane alone touches dc_i); u_new must not alias u_old
 void cheby_step(const DevCSR &A, const double *u_old, double *u_new, double *dc, const double *f, const double *offc,
                 const double *diag, double a, double b, hipStream_t s, int prof = PROF_NONE);
+// One colour pass of the multicolour Gauss-Seidel (relax types 40-42), the Jacobi family's data
+// path in place:   u_i += w*(f_i - offc_i - (A u)_i) / d_i   for the rows i of [row_begin, row_end), u read as it
+// stands.  The caller guarantees that no row of the range stores a column of the range but its own (the rows have one
+// colour of a colouring of D + D^T); only the tiles that intersect the range are launched, and the rows of a tile
+// outside the range are left alone.
+void inplace_pass(const DevCSR &A, double *u, const double *f, const double *offc, const double *d, double w,
+                  int row_begin, int row_end, hipStream_t s, int prof = PROF_NONE);
 // step 0 on a zero guess, no matrix pass: dc_i = b0*(f_i / diag_i), u_i = dc_i -- the bits cheby_step gives from u_old = 0
 void cheby_first(const double *f, const double *diag, double b0, double *dc, double *u, int n, hipStream_t s);
 // out = 1 / sqrt(x);  out = x .* y (out may alias either)

@@ -3077,6 +3077,107 @@ int ilu_multicolour(const DCsr &D, DVec<int> &colour, int &rounds, hipStream_t s
   return 0;
 }
 
+// ---- multicolour Gauss-Seidel (relax types 40-42): the diagonal check and the (block, colour) sort of a level
+namespace {
+// kind[0] = the smallest row without a stored diagonal entry, kind[1] = the smallest row whose stored a_ii is zero
+__global__ __launch_bounds__(BLK) void mcgs_bad_diagonal_k(int n, const long long *__restrict__ ia, const int *__restrict__ ja,
+                                                           const double *__restrict__ a, unsigned *__restrict__ bad) {
+  const int i = blockIdx.x * BLK + threadIdx.x;
+  if (i >= n) return;
+  bool stored = false, zero = false;
+  for (long long k = ia[i]; k < ia[i + 1]; k++)
+    if (ja[k] == i) stored = true, zero = a[k] == 0.0;
+  if (!stored) atomicMin(bad, (unsigned)i);
+  if (stored && zero) atomicMin(bad + 1, (unsigned)i);
+}
+__global__ __launch_bounds__(BLK) void mcgs_max_colour_k(int n, const int *__restrict__ colour, int *__restrict__ out) {
+  __shared__ int m;
+  if (threadIdx.x == 0) m = -1;
+  __syncthreads();
+  const int i = blockIdx.x * BLK + threadIdx.x;
+  if (i < n) atomicMax(&m, colour[i]);
+  __syncthreads();
+  if (threadIdx.x == 0) atomicMax(out, m);
+}
+// rows of colour c (flag, rank: their exclusive scan): those below nc go to base_c + rank, the others to base_f + rank
+// less the flagged rows below nc
+__global__ __launch_bounds__(BLK) void mcgs_place_k(int n, int nc, const int *__restrict__ flag, const long long *__restrict__ rank,
+                                                    long long base_c, long long base_f, int *__restrict__ order) {
+  const int i = blockIdx.x * BLK + threadIdx.x;
+  if (i >= n || !flag[i]) return;
+  order[i < nc ? base_c + rank[i] : base_f + (rank[i] - rank[nc])] = i;
+}
+}  // namespace
+
+long long mcgs_bad_diagonal(const DCsr &D, int &kind, hipStream_t s) {
+  const int n = D.nrows;
+  kind = 0;
+  if (n == 0) return -1;
+  DVec<unsigned> bad(2);
+  MI_HIP(hipMemsetAsync(bad.p, 0xff, 2 * sizeof(unsigned), s));
+  mcgs_bad_diagonal_k<<<(unsigned)((n + BLK - 1) / BLK), BLK, 0, s>>>(n, D.ia.p, D.ja.p, D.a.p, bad.p);
+  MI_HIP(hipGetLastError());
+  unsigned b[2] = {0, 0};
+  d2h(b, bad.p, sizeof(b), s);
+  MI_HIP(hipStreamSynchronize(s));
+  if (b[0] == ~0u && b[1] == ~0u) return -1;
+  kind = b[0] <= b[1] ? 0 : 1;
+  return (long long)std::min(b[0], b[1]);
+}
+
+void mcgs_order(const int *colour, int n, int nc, DVec<int> &order, std::vector<int> &range_start,
+                std::vector<int> &range_colour, int &ncolours, int &ranges_c, hipStream_t s) {
+  order.alloc((size_t)n);
+  range_start.assign(1, 0);
+  range_colour.clear();
+  ncolours = ranges_c = 0;
+  if (n == 0) return;
+  const unsigned gn = (unsigned)((n + BLK - 1) / BLK);
+  DVec<int> dmax(1);
+  MI_HIP(hipMemsetAsync(dmax.p, 0xff, sizeof(int), s));
+  mcgs_max_colour_k<<<gn, BLK, 0, s>>>(n, colour, dmax.p);
+  MI_HIP(hipGetLastError());
+  int mx = -1;
+  d2h(&mx, dmax.p, sizeof(int), s);
+  MI_HIP(hipStreamSynchronize(s));
+  ncolours = mx + 1;
+  // one flagged scan per colour: rank[nc] and rank[n] count the colour's rows in the C and in the F block.  A scan is
+  // n + 1 64-bit entries, so the scans are not kept: they run twice, for the counts and then for the places.
+  DVec<int> flag((size_t)n);
+  DVec<long long> rank((size_t)n + 1);
+  std::vector<long long> cnt_c((size_t)ncolours), cnt_f((size_t)ncolours);
+  for (int c = 0; c < ncolours; c++) {
+    loc_key_eq_k<<<gn, BLK, 0, s>>>(n, colour, c, flag.p);
+    exclusive_scan(flag.p, rank.p, n, s);
+    long long at_nc = 0, at_n = 0;
+    d2h(&at_nc, rank.p + nc, sizeof(long long), s);
+    d2h(&at_n, rank.p + n, sizeof(long long), s);
+    MI_HIP(hipStreamSynchronize(s));
+    cnt_c[(size_t)c] = at_nc;
+    cnt_f[(size_t)c] = at_n - at_nc;
+  }
+  std::vector<long long> base_c((size_t)ncolours), base_f((size_t)ncolours);
+  long long run = 0;
+  for (int c = 0; c < ncolours; c++) {
+    base_c[(size_t)c] = run;
+    run += cnt_c[(size_t)c];
+    if (cnt_c[(size_t)c] > 0) range_start.push_back((int)run), range_colour.push_back(c), ranges_c++;
+  }
+  for (int c = 0; c < ncolours; c++) {
+    base_f[(size_t)c] = run;
+    run += cnt_f[(size_t)c];
+    if (cnt_f[(size_t)c] > 0) range_start.push_back((int)run), range_colour.push_back(c);
+  }
+  MI_REQUIRE(run == n, "multicolour ordering: the colours do not cover the rows");
+  for (int c = 0; c < ncolours; c++) {
+    loc_key_eq_k<<<gn, BLK, 0, s>>>(n, colour, c, flag.p);
+    exclusive_scan(flag.p, rank.p, n, s);
+    mcgs_place_k<<<gn, BLK, 0, s>>>(n, nc, flag.p, rank.p, base_c[(size_t)c], base_f[(size_t)c], order.p);
+  }
+  MI_HIP(hipGetLastError());
+  MI_HIP(hipStreamSynchronize(s));
+}
+
 long long ilu_zero_pivot(const DCsr &LU, const long long *dpos, hipStream_t s) {
   const int n = LU.nrows;
   if (n == 0) return -1;

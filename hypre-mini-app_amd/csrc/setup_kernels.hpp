@@ -212,6 +212,14 @@ void level_norms(const DevCSR &A, const int *cf, int chunk, double *diag, double
 // colour: n entries on return; rounds: launches run.  Returns 0, or -1 when n rounds left rows uncoloured (which a
 // correct run cannot do: the caller fails).
 int ilu_multicolour(const DCsr &D, DVec<int> &colour, int &rounds, hipStream_t s);
+// ---- multicolour Gauss-Seidel (relax types 40-42)
+// the smallest row of the square block D that stores no diagonal entry (kind 0) or stores a_ii == 0 (kind 1); -1: none
+long long mcgs_bad_diagonal(const DCsr &D, int &kind, hipStream_t s);
+// The stable sort of the rows by (block, colour), block 0 = rows below nc, block 1 = the others: order[new] = row.  One
+// flagged scan per colour (twice: counts, then places), so the order inside a (block, colour) range is ascending.
+// range_start: the ranges' first rows and n at the end; range_colour: their colours; ranges_c: how many lie below nc.
+void mcgs_order(const int *colour, int n, int nc, DVec<int> &order, std::vector<int> &range_start,
+                std::vector<int> &range_colour, int &ncolours, int &ranges_c, hipStream_t s);
 // out[perm[q]] = in[q]
 void ilu_unpermute(const int *perm, const double *in, double *out, int n, hipStream_t s);
 

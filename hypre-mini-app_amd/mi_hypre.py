@@ -30,6 +30,7 @@ PROF_SPMV_L0, PROF_RELAX_L0, PROF_DOT, PROF_AXPY = 0, 1, 2, 3
 PROF_LEVELS = 16
 PROF_LVL_RESID, PROF_LVL_RELAX, PROF_LVL_RESTRICT, PROF_LVL_PROLONG = 4, 4 + 16, 4 + 32, 4 + 48
 PROF_LVL_RELAX0 = 4 + 64  # first sweep on a zero guess (runs on the level's zero-guess sub-operator)
+PROF_LVL_RELAX_MC = 4 + 80  # colour passes of relax types 40 / 41 / 42 (one launch per (block, colour) range)
 
 ALLREDUCE_FN = C.CFUNCTYPE(None, vp, vp, C.c_size_t, c_int, c_int)
 ALLGATHER_FN = C.CFUNCTYPE(None, vp, vp, vp, C.c_size_t)
@@ -427,6 +428,17 @@ class BoomerAMG:
         call("HYPRE_MI_BoomerAMGGetLevelDofFunc", self.h, level, dof)
         return dof
 
+    def level_colours(self, level):
+        """The colouring of a level set up with relax type 40 / 41 / 42 in some slot: (info, colour) with info =
+        (colours, colouring rounds, (block, colour) ranges in the C block, ranges in the F block) and colour the colour
+        of every row, level_csr's rows."""
+        nr, nc, nnz = c_int(), c_int(), c_big()
+        call("HYPRE_MI_BoomerAMGGetLevelCSRSize", self.h, level, 0, C.byref(nr), C.byref(nc), C.byref(nnz))
+        info = np.zeros(4, dtype=np.int32)
+        colour = np.zeros(nr.value, dtype=np.int32)
+        call("HYPRE_MI_BoomerAMGGetLevelColours", self.h, level, info, colour)
+        return tuple(int(v) for v in info), colour
+
     def level_norms(self, level):
         """(diagonal, signed l1 norm of the hybrid-GS chunks, signed full l1 norm) of a level, level_csr's rows."""
         nr, nc, nnz = c_int(), c_int(), c_big()
@@ -495,6 +507,7 @@ class BoomerAMG:
         return cm[: nc.value]
 
     def relax_level(self, level, relax_type, points, f, u):
+        """One relaxation call of the level on host arrays (relax types 40 / 41 / 42 take points 0)."""
         f = dbl(f)
         u = np.array(u, dtype=np.float64)
         call("HYPRE_MI_BoomerAMGRelaxLevel", self.h, level, relax_type, points, f, u)
@@ -984,7 +997,7 @@ def profile_kernel_name(pid):
 def solve_kernel_choice(family, xcache=False, tile_entries=2048, fp32=False, dictionary=False, epilogue=0, level0=False,
                         chunk=8, tiles=False, nnz=0, nrows=1, rowlen_p95=0):
     """instantiation the library launches for an operator with these properties (no device needed).  family 0: SpMV /
-    Jacobi (epilogue 1), family 1: hybrid Gauss-Seidel."""
+    Jacobi (epilogue 1) / the in-place colour pass of relax types 40 - 42 (epilogue 3), family 1: hybrid Gauss-Seidel."""
     buf = C.create_string_buffer(128)
     call("HYPRE_MI_SolveKernelChoice", family, int(xcache), tile_entries, int(fp32), int(dictionary), epilogue, int(level0),
          chunk, int(tiles), c_big(nnz), nrows, rowlen_p95, buf, 128)

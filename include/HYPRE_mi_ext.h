@@ -276,6 +276,11 @@ HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCF(HYPRE_Solver solver, HYPRE_Int level, HYP
 /* the unknown (0 ... num_functions - 1) every row of `level` belongs to, in GetLevelCF's row numbering; fails on a
  * hierarchy built with num_functions 1, which keeps none */
 HYPRE_Int HYPRE_MI_BoomerAMGGetLevelDofFunc(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int *dof);
+/* The colouring of `level` in a hierarchy set up with relax type 40, 41 or 42 (multicolour Gauss-Seidel, this library's
+ * own numbers) in some slot: info = { colours, rounds of the colouring, (block, colour) row ranges in the C block, ranges
+ * in the F block }; colour (may be NULL): the colour of every row, in GetLevelCSR's row numbering -- non-decreasing over
+ * the C rows and over the F rows.  Fails on a level that was not coloured. */
+HYPRE_Int HYPRE_MI_BoomerAMGGetLevelColours(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int info[4], HYPRE_Int *colour);
 /* What the smoothers of a level divide by, in GetLevelCSR's row numbering: the diagonal, the l1 norm of the hybrid
  * Gauss-Seidel chunks (C/F aware, replaced by |a_ii| where it is at most 4/3 of it) and the full l1 norm of the row;
  * both norms carry the sign of the diagonal.  Any array may be NULL. */
@@ -384,7 +389,8 @@ HYPRE_Int HYPRE_MI_ProfileReset(void);
 HYPRE_Int HYPRE_MI_ProfileKernelName(HYPRE_Int id, char *name, HYPRE_Int max_len);
 HYPRE_Int HYPRE_MI_ProfileGet(HYPRE_Int id, long long *launches, double *total_ms, double *min_ms);
 /* test hook, needs no device: the instantiation the library launches for an operator described by plain integers.
- * family 0: SpMV (epilogue 0; level0: under class 0) / masked Jacobi (epilogue 1); family 1: hybrid Gauss-Seidel with
+ * family 0: SpMV (epilogue 0; level0: under class 0) / masked Jacobi (epilogue 1) / the in-place colour pass of relax
+ * types 40 - 42 (epilogue 3; 2, the Chebyshev step, has its own entry below); family 1: hybrid Gauss-Seidel with
  * `chunk` rows per chunk, where tiles != 0 says that the operator's tiles are whole 8-row chunks and the tile mode
  * (MI_HYPRE_GS_TILE) lets it use them.  xcache: the operator has the LDS x cache (mean row length >= 3); tile_entries
  * 2048 or 4096; has_fp32 / has_dictionary: the value arrays it holds (fp32 wins); nnz, nrows, rowlen_p95 (the entry

@@ -20,7 +20,7 @@ HYPRE_Int HYPRE_BoomerAMGSetPrintLevel(HYPRE_Solver solver, HYPRE_Int print_leve
 HYPRE_Int HYPRE_BoomerAMGSetDebugFlag(HYPRE_Solver solver, HYPRE_Int debug_flag);       /* :124 */
 HYPRE_Int HYPRE_BoomerAMGSetCoarsenType(HYPRE_Solver solver, HYPRE_Int coarsen_type);   /* :125; 8 PMIS, 10 HMIS / 11 (one-pass RS), 6 Falgout / 1 / 3 (two-pass RS); any other type is refused at Setup */
 HYPRE_Int HYPRE_BoomerAMGSetCycleType(HYPRE_Solver solver, HYPRE_Int cycle_type);       /* :127; 1 V, 2 W */
-HYPRE_Int HYPRE_BoomerAMGSetRelaxType(HYPRE_Solver solver, HYPRE_Int relax_type);       /* :138; sets down/up, coarsest = 9 */
+HYPRE_Int HYPRE_BoomerAMGSetRelaxType(HYPRE_Solver solver, HYPRE_Int relax_type);       /* :138; sets down/up, coarsest = 9; 40 / 41 / 42 = forward / backward / symmetric multicolour Gauss-Seidel (this library's own numbers, one rank, device Setup) */
 HYPRE_Int HYPRE_BoomerAMGSetCycleRelaxType(HYPRE_Solver solver, HYPRE_Int relax_type, HYPRE_Int k); /* :131-136; k 1 down 2 up 3 coarsest */
 HYPRE_Int HYPRE_BoomerAMGSetNumSweeps(HYPRE_Solver solver, HYPRE_Int num_sweeps);       /* :150; down/up = n, coarsest = 1 */
 HYPRE_Int HYPRE_BoomerAMGSetCycleNumSweeps(HYPRE_Solver solver, HYPRE_Int num_sweeps, HYPRE_Int k); /* :143-148 */
