@@ -118,6 +118,10 @@ struct AmgLevel {
   bool has_Ar = false, t_valid = false;
   int t_from = 0;
   DVec<double> tvec;
+  // C-row hand-over (level 0 of a one-rank hierarchy swept by the tile kernel): the descriptors of
+  // the tiles of A->d_diag that the mat-vec after the cycle's last C pass still has to run, and the census they came from
+  DVec<int> mv_tdesc;
+  sk::HandoverCensus handover;
   // N > 1: rows with halo entries (ascending) and, per swept row range and operator, the largest halo-free
   // stretch, cut at the units the GS kernels write back -- a pass sweeps it while the halo is still travelling
   struct InteriorRange {
@@ -328,8 +332,16 @@ struct BoomerAMG {
   // Lv.u / Lv.f in the level's C-first ordering.
   // u_is_zero: the caller guarantees Lv.u == 0 on entry (its halo is then known to be zero)
   void relax(int level, int type, int points, const double *f, bool u_is_zero = false);
-  void relax_pair(int level, int type, int first, const double *f, bool u_is_zero = false);
-  void relax_sweeps(int level, int which, const double *f, bool u_is_zero = false);
+  // wout (C-row hand-over): the C pass that ends an F-then-C pair on the tile kernel also stores (A u)_i for the C rows
+  // whose only C column is their diagonal, and raises handover_done; relax_sweeps hands it to its last pair
+  void relax_pair(int level, int type, int first, const double *f, bool u_is_zero = false, double *wout = nullptr);
+  void relax_sweeps(int level, int which, const double *f, bool u_is_zero = false, double *wout = nullptr);
+  // C-row hand-over: a Krylov loop in level order sets the vector that will take A z before it asks for the cycle that
+  // computes z; cycle(0, ..) clears handover_done and raises it when the last level-0 launch was such a C pass.  Then
+  // rows of handed-over tiles of L[0] hold (A z)_i and the mat-vec runs on L[0].mv_tdesc alone.
+  double *handover_w = nullptr;
+  bool handover_done = false;
+  bool handover_wanted() const;  // the mode and level 0's census allow it
   // host-side census of the tile Gauss-Seidel kernel's sweep branches for one pass of relax / relax_pair
   bool gs_sweep_paths(int level, int points, bool u_is_zero, long long counts[5]);
   void cycle(int level, bool u_is_zero = false);
@@ -368,6 +380,10 @@ struct BoomerAMG {
 // that follows reuses the F pass's product with the C values (AmgLevel::Ar)
 int zero_skip_mode();
 void set_zero_skip_mode(int mode);  // applies to hierarchies set up afterwards (mode 2) / to every later sweep (0, 1)
+// MI_HYPRE_C_HANDOVER: 0 = the mat-vec after a cycle is always the full one, 1 (default) = C-row hand-over when at least
+// 10 % of level 0's tiles are handed over, 2 = whenever one is
+int c_handover_mode();
+void set_c_handover_mode(int mode);
 
 // set by a Krylov solver right before it calls the preconditioner with x == 0,
 // consumed (and cleared) by BoomerAMG::solve

@@ -3639,6 +3639,12 @@ void BoomerAMG::setup_device() {
         Lv.Az.prefer_gs_tiles = true;  // only the tile kernel hands the F pass's C-column product over
       }
     }
+    // C-row hand-over: the tiles of level 0 the Krylov mat-vec still runs after the cycle's last C pass
+    Lv.mv_tdesc.release();
+    Lv.handover = sk::HandoverCensus();
+    if (li == 0 && !forced_comm && comm.size == 1 && ch == 8 && Lv.has_cf && !Lv.cf.empty() && Lv.nc > 0 && Lv.nc < Lv.n &&
+        Lv.A->d_diag.nrows == Lv.n && Lv.A->d_diag.ncols == Lv.n && k::gs_uses_tiles(Lv.A->d_diag, ch))
+      sk::handover_tiles(Lv.A->d_diag, Lv.nc, Lv.mv_tdesc, Lv.handover, s);
     trace_f.reset(), trace_f.reset(new TraceRange((fname + "vectors, C/F marks, permutation").c_str()));
     if (!Lv.d_diag.p || Lv.d_diag.n != (size_t)Lv.n) {
       Lv.d_diag.upload(Lv.diag);

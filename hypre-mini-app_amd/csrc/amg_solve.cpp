@@ -34,6 +34,16 @@ int zero_skip_mode() {
 }
 void set_zero_skip_mode(int mode) { g_zero_skip = std::max(0, std::min(3, mode)); }
 
+static int g_c_handover = -1;
+int c_handover_mode() {
+  if (g_c_handover < 0) {
+    const char *e = getenv("MI_HYPRE_C_HANDOVER");
+    g_c_handover = e ? std::max(0, std::min(2, atoi(e))) : 1;
+  }
+  return g_c_handover;
+}
+void set_c_handover_mode(int mode) { g_c_handover = std::max(0, std::min(2, mode)); }
+
 namespace {
 // level 0 is timed under bench.py's id when that one is enabled, else under the per-level id
 int relax_prof_id(int level, bool zero_guess) {
@@ -138,13 +148,15 @@ bool interior_range(AmgLevel &Lv, const DevCSR &M, int ch, int row_begin, int ro
 // order).  zero_halo: the values are all zero -- no exchange at all.
 void gs_pass(BoomerAMG &amg, AmgLevel &Lv, const DevCSR &M, bool zero_halo, const double *lo, const double *hi, int split,
              double *out, const double *f, const double *d, const signed char *cf, int points, int ch, const GsKind &g,
-             double w, int row_begin, int row_end, int prof, int zero_from, double *tout = nullptr, int t_from = 0) {
+             double w, int row_begin, int row_end, int prof, int zero_from, double *tout = nullptr, int t_from = 0,
+             double *wout = nullptr) {
   ParCSR &A = *Lv.A;
   Comm &comm = amg.my_comm();
   hipStream_t s = ctx().stream;
+  MI_REQUIRE(!wout || comm.size == 1, "hybrid GS: the C-row hand-over is a one-rank path");
   if (zero_halo || comm.size == 1) {
     k::gs_hybrid(M, lo, hi, split, out, f, nullptr, d, cf, points, ch, g.fwd, g.bwd, w, row_begin, row_end, s, prof,
-                 zero_from, tout, t_from);
+                 zero_from, tout, t_from, wout);
     return;
   }
   static const bool overlap = !(getenv("MI_HYPRE_OVERLAP_HALO") && atoi(getenv("MI_HYPRE_OVERLAP_HALO")) == 0);
@@ -280,7 +292,7 @@ void BoomerAMG::relax(int level, int type, int points, const double *f, bool u_i
 
 // a C/F pair of hybrid-GS passes (first = +1: C then F, first = -1: F then C)
 // without the intermediate copy
-void BoomerAMG::relax_pair(int level, int type, int first, const double *f, bool u_is_zero) {
+void BoomerAMG::relax_pair(int level, int type, int first, const double *f, bool u_is_zero, double *wout) {
   AmgLevel &Lv = L[(size_t)level];
   const GsKind g = classify(type);
   if (g.cheby || g.mcgs) {  // a Chebyshev or a multicolour Gauss-Seidel sweep is not split into a C and an F half
@@ -323,8 +335,13 @@ void BoomerAMG::relax_pair(int level, int type, int first, const double *f, bool
     Lv.t_valid = true;
   } else if (first == 1)
     gs_pass(*this, Lv, A2, false, lo, hi, nc, sn, f, d, Lv.d_cf.p, -1, ch, g, w, nc, n, prof, z2);
-  else
-    gs_pass(*this, Lv, A2, false, lo, hi, nc, sn, f, d, Lv.d_cf.p, 1, ch, g, w, 0, nc, prof, z2);
+  else {
+    // the pair's C pass reads the final F values: for a C row without another C column, S + a_ii u_i is (A u)_i
+    const bool hand = wout && my_comm().size == 1 && k::gs_uses_tiles(A2, ch);
+    gs_pass(*this, Lv, A2, false, lo, hi, nc, sn, f, d, Lv.d_cf.p, 1, ch, g, w, 0, nc, prof, z2, nullptr, 0,
+            hand ? wout : nullptr);
+    handover_done = hand;
+  }
   std::swap(Lv.u.p, Lv.snap.p);  // snap now holds every row
 }
 
@@ -349,7 +366,7 @@ bool BoomerAMG::gs_sweep_paths(int level, int points, bool u_is_zero, long long 
 
 // which: 0 down, 1 up, 2 coarsest.  relax_order 1: C then F going down, F then
 // C going up, all points on the coarsest level (hypre_BoomerAMGRelaxIF)
-void BoomerAMG::relax_sweeps(int level, int which, const double *f, bool u_is_zero) {
+void BoomerAMG::relax_sweeps(int level, int which, const double *f, bool u_is_zero, double *wout) {
   const int type = p.relax_type[which];
   const bool has_cf = L[(size_t)level].has_cf;
   if (FsaiSolver *fs = level_fsai(L[(size_t)level]); fs && which != 2) {
@@ -395,7 +412,7 @@ void BoomerAMG::relax_sweeps(int level, int which, const double *f, bool u_is_ze
     if (which == 2 || p.relax_order != 1 || !has_cf)
       relax(level, type, 0, f, zero);
     else
-      relax_pair(level, type, which == 0 ? 1 : -1, f, zero);
+      relax_pair(level, type, which == 0 ? 1 : -1, f, zero, sw == p.num_sweeps[which] - 1 ? wout : nullptr);
   }
 }
 
@@ -458,6 +475,7 @@ void BoomerAMG::cycle(int level, bool u_is_zero) {
   if (level == 0 && collapsed_level >= 0 && collapsed_signature != cycle_signature())
     build_collapsed_tail();  // a cycle parameter changed after Setup: the tabulated map is of another cycle
   AmgLevel &Lv = L[(size_t)level];
+  if (level == 0) handover_done = false;
   if (level == collapsed_level && u_is_zero) {  // the tabulated map of this level's whole sub-cycle
     k::dense_matvec_t(collapsed_Bt.p, Lv.f.p, Lv.u.p, collapsed_n, ctx().stream);
     return;
@@ -495,7 +513,14 @@ void BoomerAMG::cycle(int level, bool u_is_zero) {
   } else {
     Lv.Pm->matvec(comm, 1.0, Ln.u.p, 1.0, Lv.u.p, Lv.u.p, s, k::prof_level(k::PROF_LVL_PROLONG, level));
   }
-  relax_sweeps(level, 1, Lv.f.p, false);
+  relax_sweeps(level, 1, Lv.f.p, false, level == 0 ? handover_w : nullptr);
+}
+
+bool BoomerAMG::handover_wanted() const {
+  const int mode = c_handover_mode();
+  if (mode == 0 || L.empty() || !L[0].mv_tdesc.p) return false;
+  const sk::HandoverCensus &c = L[0].handover;
+  return c.handed > 0 && (mode == 2 || 10LL * c.handed >= c.tiles);
 }
 
 // tabulate the map f -> u of cycle(lt, true) by cycling the unit vectors (row j of Bt = column j of the map)

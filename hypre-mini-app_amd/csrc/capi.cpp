@@ -1968,6 +1968,10 @@ HYPRE_Int HYPRE_MI_GetCounter(const char *name, long long *value) {
     *value = ctx().n_precond_cycles;
   else if (n == "gmres_direction_vectors")
     *value = ctx().n_gmres_z_allocated;
+  else if (n == "handover_matvecs")
+    *value = ctx().n_handover_matvecs;
+  else if (n == "handover_tiles_skipped")
+    *value = ctx().n_handover_tiles_skipped;
   else if (setup_reuse_counter(n.c_str()) >= 0)
     *value = setup_reuse_counter(n.c_str());
   else if (dist_setup_counter(n.c_str()) >= 0)
@@ -1980,6 +1984,67 @@ HYPRE_Int HYPRE_MI_SetZeroGuessMode(HYPRE_Int mode) {
   API_BEGIN
   if (mode < 0 || mode > 3) fail(HYPRE_ERROR_ARG, "SetZeroGuessMode: 0..3");
   set_zero_skip_mode(mode);
+  API_END
+}
+HYPRE_Int HYPRE_MI_SetCRowHandover(HYPRE_Int mode) {
+  API_BEGIN
+  if (mode < 0 || mode > 2) fail(HYPRE_ERROR_ARG, "SetCRowHandover: 0..2");
+  set_c_handover_mode(mode);
+  API_END
+}
+HYPRE_Int HYPRE_MI_BoomerAMGGetCRowHandoverCensus(HYPRE_Solver solver, HYPRE_Int level, HYPRE_BigInt *census) {
+  API_BEGIN
+  AmgSolver *a = AMG(solver);
+  if (!a->amg.is_setup) fail(HYPRE_ERROR_GENERIC, "GetCRowHandoverCensus: AMG is not set up");
+  if (level < 0 || level >= (int)a->amg.L.size()) fail(HYPRE_ERROR_ARG, "AMG level out of range");
+  const AmgLevel &Lv = a->amg.L[(size_t)level];
+  const bool built = Lv.mv_tdesc.p != nullptr;
+  census[0] = Lv.A->d_diag.nblocks;
+  census[1] = built ? Lv.handover.listed : Lv.A->d_diag.nblocks;
+  census[2] = built ? Lv.handover.handed : 0;
+  census[3] = Lv.handover.flagged_c_rows;
+  census[4] = built ? Lv.handover.w_upto : 0;
+  API_END
+}
+// One cycle from a zero guess as a Krylov loop in level order asks for it, with the hand-over target set, then the
+// mat-vec that follows it: z = M^-1 f, w = A z by the path the current mode takes (raised: the C pass handed rows over
+// and the mat-vec ran on the tile list), w_full = A z by the full mat-vec.  Host arrays in level 0's ordering.
+HYPRE_Int HYPRE_MI_BoomerAMGCycleThenMatvec(HYPRE_Solver solver, const HYPRE_Real *f_host, HYPRE_Real *z_host,
+                                            HYPRE_Real *w_host, HYPRE_Real *w_full_host, HYPRE_Int *raised) {
+  API_BEGIN
+  BoomerAMG &amg = AMG(solver)->amg;
+  if (!amg.is_setup || amg.L.empty()) fail(HYPRE_ERROR_GENERIC, "CycleThenMatvec: AMG is not set up");
+  AmgLevel &L0 = amg.L[0];
+  const int n = L0.n;
+  hipStream_t s = ctx().stream;
+  DVec<double> f((size_t)n), w((size_t)n), wf((size_t)n);
+  f.upload(f_host, (size_t)n);
+  MI_HIP(hipStreamSynchronize(s));
+  k::fill(w.p, n, std::numeric_limits<double>::quiet_NaN(), s);  // a row nobody writes shows
+  k::copy(f.p, L0.f.p, n, s);
+  if (!amg.zero_cycle_ignores_u(0)) k::fill(L0.u.p, n, 0.0, s);
+  amg.handover_w = amg.handover_wanted() ? w.p : nullptr;
+  try {
+    amg.cycle(0, true);
+  } catch (...) {
+    amg.handover_w = nullptr;
+    throw;
+  }
+  amg.handover_w = nullptr;
+  const bool handed = amg.handover_done;
+  amg.handover_done = false;
+  if (handed)
+    L0.A->matvec_listed_tiles(L0.mv_tdesc.p, L0.handover.listed, L0.u.p, w.p, s);
+  else
+    L0.A->matvec(amg.my_comm(), 1.0, L0.u.p, 0.0, nullptr, w.p, s);
+  L0.A->matvec(amg.my_comm(), 1.0, L0.u.p, 0.0, nullptr, wf.p, s);
+  MI_HIP(hipStreamSynchronize(s));
+  if (n) {
+    d2h(z_host, L0.u.p, (size_t)n * sizeof(double), nullptr);
+    d2h(w_host, w.p, (size_t)n * sizeof(double), nullptr);
+    d2h(w_full_host, wf.p, (size_t)n * sizeof(double), nullptr);
+  }
+  *raised = handed ? 1 : 0;
   API_END
 }
 // test hook (tests/test_gpu_amg.py): every level's solution and scratch vectors of the hierarchy become NaN.  A cycle from

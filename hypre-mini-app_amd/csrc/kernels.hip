@@ -968,7 +968,7 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void gs_tile_k(int blk0, int n
                                                         int row_begin, int row_end, int zero_from,
                                                         double *__restrict__ tout, int t_from,
                                                         const unsigned char *__restrict__ vidx,
-                                                        const double *__restrict__ vlut) {
+                                                        const double *__restrict__ vlut, double *__restrict__ wout) {
 #define UOLD(j) (((j) < split ? u_lo : u_hi)[(j)])
   constexpr int TILE = 8 * BLOCK;        // TILE / TILE_WIDE
   __shared__ double buf[TILE];           // x cache, then products / in-chunk coefficients
@@ -1179,6 +1179,8 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void gs_tile_k(int blk0, int n
     const double cd = has ? buf[has ? kin : 0] : 0.0;
     if (fwd) myu = myu + (myrhs - (S + cd * myu)) * wd;  // unselected rows: wd == 0
     if (bwd) myu = myu + (myrhs - (S + cd * myu)) * wd;
+    // C-row hand-over: a row whose out-of-chunk columns this pass leaves alone has its product with the new vector here
+    if (wout && rowsel && sub == 0) wout[i] = S + cd * myu;
   } else {
     double crow[8];
 #pragma unroll
@@ -1946,18 +1948,20 @@ static void launch_on_values(const DevCSR &A, const KernelChoice &c, Launch laun
 
 // returns the name of the instantiation it launched
 static const char *launch_stream(int epi, const DevCSR &A, const double *x, double *y, const EpiArgs &e, hipStream_t s,
-                                 bool level0 = false, int ntiles = 0) {
+                                 bool level0 = false, int ntiles = 0, const int *tdesc = nullptr) {
   if (A.nrows == 0) return "";
   MI_REQUIRE(A.xcache || !A.big(), "an operator with 2^31 entries or more must be in the x-cache tile format");
   // (fp32 value storage, k::narrow_values: `a` is gone, the kernels stream a32)
   MI_REQUIRE(A.value_format() == ValueFormat::FP32 || A.a.p || A.nnz == 0, "SpMV: the operator holds no value array");
   const KernelChoice c = choose_stream_kernel({A.xcache, A.tile_entries, A.value_format(), epi, level0});
-  const int nb = epi == 3 ? ntiles : A.nblocks;  // (EPI 3: the tiles [e.blk0, e.blk0 + ntiles))
+  // (EPI 3: the tiles [e.blk0, e.blk0 + ntiles); tdesc: the ntiles tiles of a descriptor list of the caller's)
+  const int nb = (epi == 3 || tdesc) ? ntiles : A.nblocks;
+  MI_REQUIRE(!tdesc || c.family == KernelFamily::STREAM_XC, "SpMV: a tile list needs the x-cache tile format");
   const int xchunk = (nb + 7) / 8;
   const dim3 grid(xchunk * 8), block(c.block);
   if (c.family == KernelFamily::STREAM_XC) {
-    hipLaunchKernelGGL((XcKernel)c.kernel, grid, block, 0, s, nb, xchunk, A.tdesc.p, A.ia.p, A.ja.p, tile_values(A),
-                       A.ucols.p, A.lcol.p, x, y, e, A.vidx.p, A.vlut.p);
+    hipLaunchKernelGGL((XcKernel)c.kernel, grid, block, 0, s, nb, xchunk, tdesc ? tdesc : A.tdesc.p, A.ia.p, A.ja.p,
+                       tile_values(A), A.ucols.p, A.lcol.p, x, y, e, A.vidx.p, A.vlut.p);
   } else {
     launch_on_values<StreamKernel>(A, c, [&](auto kernel, auto *values) {
       hipLaunchKernelGGL(kernel, grid, block, 0, s, nb, xchunk, A.rb.p, A.ia.p, A.ja.p, values, x, y, e);
@@ -2074,6 +2078,16 @@ void spmv(const DevCSR &A, const double *x, double alpha, double beta, const dou
   e.rowmap = A.rowmap.p;
   prof_begin(prof, s);
   prof_name(prof, launch_stream(0, A, x, y, e, s, prof == PROF_SPMV_L0));
+  prof_end(prof, s);
+}
+
+void spmv_listed_tiles(const DevCSR &A, const int *tdesc, int nb, const double *x, double *y, hipStream_t s, int prof) {
+  if (nb <= 0) return;
+  MI_REQUIRE(tdesc && !A.rowmap.p, "SpMV on a tile list: no list, or an operator stored in another row order");
+  EpiArgs e{};
+  e.alpha = 1.0;
+  prof_begin(prof, s);
+  prof_name(prof, launch_stream(0, A, x, y, e, s, prof == PROF_SPMV_L0, nb, tdesc));
   prof_end(prof, s);
 }
 
@@ -2372,7 +2386,7 @@ bool gs_tile_path_census(const DevCSR &A, int chunk, const int64_t *ia, const in
 void gs_hybrid(const DevCSR &A, const double *u_lo, const double *u_hi, int split, double *out, const double *f,
                const double *offc, const double *d, const signed char *cf, int points, int chunk, bool fwd, bool bwd,
                double w, int row_begin, int row_end, hipStream_t s, int prof, int zero_from, double *tout,
-               int t_from) {
+               int t_from, double *wout) {
   if (A.nrows == 0 || row_end <= row_begin) return;
   MI_REQUIRE(chunk >= 1 && chunk <= GS_MAX_CHUNK, "hybrid GS chunk out of range");
   // chunks that intersect [row_begin, row_end); pre-sweep values come from u_lo
@@ -2386,13 +2400,15 @@ void gs_hybrid(const DevCSR &A, const double *u_lo, const double *u_hi, int spli
   if (c.family == KernelFamily::GS_TILE) {
     int first_row, last_row, b0, b1;
     gs_tile_range(A, row_begin, row_end, first_row, last_row, b0, b1);
+    MI_REQUIRE(!wout || (MI_GS_SWEEP_PATHS & 2), "hybrid GS: the C-row hand-over needs the kernel's diagonal-chunk branch");
     if (b1 > b0) {
       prof_name(prof, c.name);
       hipLaunchKernelGGL((GsTileKernel)c.kernel, dim3((unsigned)(b1 - b0)), block, 0, s, b0, b1 - b0, A.tdesc.p, A.ia.p,
                          tile_values(A), A.ucols.p, A.lcol.p, cf, points, d, f, offc, u_lo, u_hi, split, out, fwd ? 1 : 0,
-                         bwd ? 1 : 0, w, first_row, last_row, zero_from, tout, t_from, A.vidx.p, A.vlut.p);
+                         bwd ? 1 : 0, w, first_row, last_row, zero_from, tout, t_from, A.vidx.p, A.vlut.p, wout);
     }
   } else {
+    MI_REQUIRE(!wout, "hybrid GS: only the tile kernel hands the C rows' products over");
     MI_REQUIRE(!A.big(), "an operator with 2^31 entries or more is swept by the tile Gauss-Seidel kernel only");
     prof_name(prof, c.name);
     if (c.family == KernelFamily::GS_HYBRID) {

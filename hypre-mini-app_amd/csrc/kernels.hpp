@@ -228,9 +228,16 @@ bool gs_ignores_zero_vector(const DevCSR &A, int chunk);
 void gs_hybrid(const DevCSR &A, const double *u_lo, const double *u_hi, int split, double *out, const double *f,
                const double *offc, const double *d, const signed char *cf, int points, int chunk, bool fwd, bool bwd,
                double w, int row_begin, int row_end, hipStream_t s, int prof = PROF_NONE, int zero_from = GS_NO_ZEROS,
-               double *tout = nullptr, int t_from = 0);
+               double *tout = nullptr, int t_from = 0, double *wout = nullptr);
 // tout (tile kernel only -- check gs_uses_tiles): every swept row i >= t_from also stores f[i] minus its
 // out-of-chunk sum there
+// wout (tile kernel only): every swept row of a wave whose chunks couple to nothing in-chunk but their own diagonals
+// also stores its out-of-chunk sum plus a_ii times its new value there -- (A u)_i for a row whose out-of-chunk
+// columns the pass does not update (C-row hand-over); other rows of wout are left alone
+// y = A x on the tiles tdesc[0 .. nb) alone (descriptors copied from A.tdesc; x-cache tile format only): the rows of
+// the other tiles are not written
+void spmv_listed_tiles(const DevCSR &A, const int *tdesc, int nb, const double *x, double *y, hipStream_t s,
+                       int prof = PROF_NONE);
 // which branches of the tile kernel's sweep phase the waves of such a pass take, counted on the host (kernels.hip)
 bool gs_tile_path_census(const DevCSR &A, int chunk, const int64_t *ia, const int *ja, const int *cf, int points,
                          int row_begin, int row_end, int zero_from, long long counts[5]);

@@ -333,12 +333,33 @@ int GmresSolver::solve(ParCSR &A_in, ParVector &b_in, ParVector &x_in) {
       const bool adopt = zk && nc == 1 && amg->L[0].u.n == zk->d.n;
       ParVector &dir = flexible ? zvec(i - 1) : (zk ? *zk : r);  // M^-1 p_{i-1}
       const double *mp;
+      // C-row hand-over: the cycle's last C pass writes the rows of p_i = A z it already holds
+      bool handed = false;
       {
         TraceRange tr("precond (BoomerAMG cycle)");
-        mp = precond(pim1, dir, flexible || (zk && !adopt));
+        const bool hand = amg && nc == 1 && comm.size == 1 && amg->handover_wanted();
+        if (hand) amg->handover_w = pi.data();
+        try {
+          mp = precond(pim1, dir, flexible || (zk && !adopt));
+        } catch (...) {
+          if (hand) amg->handover_w = nullptr;
+          throw;
+        }
+        if (hand) {
+          amg->handover_w = nullptr;
+          handed = amg->handover_done;
+          amg->handover_done = false;
+        }
       }
       if (adopt) std::swap(amg->L[0].u.p, zk->d.p);  // mp is z_{i-1} now
-      mv(1.0, mp, 0.0, nullptr, pi.data());
+      if (handed) {  // the tiles the C pass did not cover
+        const AmgLevel &L0 = amg->L[0];
+        A.matvec_listed_tiles(L0.mv_tdesc.p, L0.handover.listed, mp, pi.data(), s, k::PROF_SPMV_L0);
+        c.n_handover_matvecs++;
+        c.n_handover_tiles_skipped += L0.handover.handed;
+      } else {
+        mv(1.0, mp, 0.0, nullptr, pi.data());
+      }
       TraceRange trace_ortho("Gram-Schmidt + Givens");
       if (ortho == 0 && comm.size == 1) {
         // blocked modified Gram-Schmidt over aligned blocks of NB basis vectors, ceil(i / NB) + 1 passes over w = p_i:

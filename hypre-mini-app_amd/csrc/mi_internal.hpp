@@ -361,6 +361,8 @@ struct Ctx {
   // BoomerAMG cycles a Krylov solver asked for as its preconditioner (cycle(0, ..) while krylov_precond_depth > 0), and
   // the vectors GMRES allocated to keep its preconditioned directions (krylov.cpp, "kept directions")
   long long n_precond_cycles = 0, n_gmres_z_allocated = 0;
+  // C-row hand-over: Krylov mat-vecs that ran on level 0's tile list, and the tiles they left out
+  long long n_handover_matvecs = 0, n_handover_tiles_skipped = 0;
   int krylov_precond_depth = 0;
 };
 Ctx &ctx();

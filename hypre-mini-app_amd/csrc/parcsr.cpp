@@ -548,6 +548,12 @@ void ParCSR::matvec(Comm &comm, double alpha, const double *x, double beta, cons
   if (halo_on) k::spmv_offd_add(d_offd, halo.d_xext.p, alpha, y, s);
 }
 
+void ParCSR::matvec_listed_tiles(const int *tdesc, int nb, const double *x, double *y, hipStream_t s, int prof) {
+  MI_REQUIRE(on_device, "matrix not assembled");
+  MI_REQUIRE(d_offd.nrows_c == 0, "mat-vec on a tile list: the matrix has a halo block");
+  k::spmv_listed_tiles(d_diag, tdesc, nb, x, y, s, prof);
+}
+
 void ParCSR::matvec_ext_ready(double alpha, const double *x, double beta, const double *b, double *y, hipStream_t s) {
   MI_REQUIRE(on_device, "matrix not assembled");
   k::spmv(d_diag, x, alpha, beta, b, y, s, -1);

@@ -92,6 +92,9 @@ struct ParCSR {
   // b_lo / b_split (optional): rows < b_split read their b entry from b_lo (composite right-hand side)
   void matvec(Comm &comm, double alpha, const double *x, double beta, const double *b, double *y, hipStream_t s,
               int prof = -1, const DevCSR *diag_op = nullptr, const double *b_lo = nullptr, int b_split = 0);
+  // y = A x on the listed tiles of the diag block alone (k::spmv_listed_tiles; one rank): the rows of the other tiles
+  // keep what y holds
+  void matvec_listed_tiles(const int *tdesc, int nb, const double *x, double *y, hipStream_t s, int prof = -1);
   // the same with the halo values already in halo.d_xext (no exchange)
   void matvec_ext_ready(double alpha, const double *x, double beta, const double *b, double *y, hipStream_t s);
   // offc[halo rows] = A_offd * x_ext(x)   (used by the smoothers)

@@ -2393,6 +2393,75 @@ void zero_guess_operator(const DevCSR &A, int nc, int chunk, DCsr &Z, hipStream_
   MI_HIP(hipStreamSynchronize(s));
 }
 
+namespace {
+// one workgroup per tile: keep[b] = 0 for a handed-over tile, 1 for one the mat-vec still runs; info[0] += flagged C
+// rows, info[1] = max end row of a handed-over tile
+__global__ __launch_bounds__(BLK) void handover_flag_k(int nb, int nc, const int *__restrict__ rb,
+                                                       const long long *__restrict__ ia, const int *__restrict__ ja,
+                                                       int *__restrict__ keep, unsigned long long *__restrict__ info) {
+  __shared__ int flagged;
+  const long long b = bid();
+  if (b >= nb) return;
+  if (threadIdx.x == 0) flagged = 0;
+  __syncthreads();
+  const int r0 = rb[b], r1 = rb[b + 1];
+  int mine = 0;
+  for (int i = r0 + (int)threadIdx.x; i < min(r1, nc); i += BLK) {
+    bool coupled = false;
+    for (long long q = ia[i]; q < ia[i + 1]; q++) coupled |= ja[q] < nc && ja[q] != i;
+    mine += coupled ? 1 : 0;
+  }
+  if (mine) atomicAdd(&flagged, mine);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const bool handed = r1 <= nc && r1 > r0 && flagged == 0;
+    keep[b] = handed ? 0 : 1;
+    if (flagged) atomicAdd(info, (unsigned long long)flagged);
+    if (handed) atomicMax(info + 1, (unsigned long long)r1);
+  }
+}
+__global__ __launch_bounds__(BLK) void handover_list_k(int nb, const int *__restrict__ keep, const long long *__restrict__ pos,
+                                                       const int *__restrict__ tdesc, int *__restrict__ out) {
+  const long long b = bid() * BLK + threadIdx.x;
+  if (b >= nb || !keep[b]) return;
+  const int4 *src = reinterpret_cast<const int4 *>(tdesc) + 2 * b;
+  int4 *dst = reinterpret_cast<int4 *>(out) + 2 * pos[b];
+  dst[0] = src[0];
+  dst[1] = src[1];
+}
+}  // namespace
+
+void handover_tiles(const DevCSR &A, int nc, DVec<int> &mv_tdesc, HandoverCensus &census, hipStream_t s) {
+  census = HandoverCensus();
+  mv_tdesc.release();
+  const int nb = A.nblocks;
+  census.tiles = census.listed = nb;
+  if (nb <= 0 || !A.rb.p || !A.tdesc.p || nc <= 0) return;
+  DVec<long long> ia_tmp;
+  const long long *Aia = wide_row_pointers(A, ia_tmp, s);
+  DVec<int> keep((size_t)nb);
+  DVec<long long> pos((size_t)nb + 1);
+  DVec<unsigned long long> info(2);
+  zero_on_stream(info.p, 2 * sizeof(unsigned long long));
+  handover_flag_k<<<grid_for(nb), BLK, 0, s>>>(nb, nc, A.rb.p, Aia, A.ja.p, keep.p, info.p);
+  MI_HIP(hipGetLastError());
+  exclusive_scan(keep.p, pos.p, nb, s);
+  long long listed = 0;
+  unsigned long long h_info[2] = {0, 0};
+  d2h(&listed, pos.p + nb, sizeof(long long), s);
+  d2h(h_info, info.p, sizeof(h_info), s);
+  MI_HIP(hipStreamSynchronize(s));
+  census.listed = (int)listed;
+  census.handed = nb - (int)listed;
+  census.flagged_c_rows = (long long)h_info[0];
+  census.w_upto = (int)h_info[1];
+  if (census.handed == 0) return;
+  mv_tdesc.alloc((size_t)std::max<long long>(listed, 1) * 8);
+  handover_list_k<<<grid_for(((long long)nb + BLK - 1) / BLK), BLK, 0, s>>>(nb, keep.p, pos.p, A.tdesc.p, mv_tdesc.p);
+  MI_HIP(hipGetLastError());
+  MI_HIP(hipStreamSynchronize(s));
+}
+
 void solve_format_to_host(const DevCSR &src, HostCSR &h, hipStream_t s) {
   const int n = src.nrows;
   h.nrows = n;

@@ -150,6 +150,16 @@ void load_device_code(hipStream_t s);
 // mode 1: the operator of the residual that follows that sweep -- F rows from the first chunk boundary >= nc on
 // lose their C columns (the F pass hands over f - A_FC u_C for them), every other row stays whole.
 void zero_guess_operator(const DevCSR &A, int nc, int chunk, DCsr &Z, hipStream_t s, int mode = 0);
+// C-row hand-over: which tiles of a C-first ordered operator in the tile format (C points =
+// indices < nc) the mat-vec that follows a level-0 C pass may leave out.  A C row is FLAGGED when it has an off-diagonal
+// C column; a tile is HANDED OVER when all its rows are C rows (r1 <= nc) and none is flagged -- the C pass then holds
+// (A z)_i of every row of it.  mv_tdesc: the descriptors of the other tiles, in their order.
+struct HandoverCensus {
+  int tiles = 0, listed = 0, handed = 0;  // tiles of the operator = listed + handed
+  long long flagged_c_rows = 0;
+  int w_upto = 0;  // end of the last handed-over tile: no row from here on is handed over
+};
+void handover_tiles(const DevCSR &A, int nc, DVec<int> &mv_tdesc, HandoverCensus &census, hipStream_t s);
 // setup-phase copy (64-bit row pointers) of an operator that lives in the solve format (device-to-device)
 void from_solve_format(const DevCSR &src, DCsr &dst, hipStream_t s);
 // Rounds of the internal locality numbering (amg_setup.cpp locality_order: graph Voronoi cells) on the device:

@@ -521,6 +521,23 @@ class BoomerAMG:
         call("HYPRE_MI_BoomerAMGRelaxPairLevel", self.h, level, relax_type, first, 1 if zero else 0, f, u)
         return u
 
+    def c_row_handover_census(self, level=0):
+        """dict(tiles, listed, handed, flagged_c_rows, w_upto): the tiles of the level's operator, those the mat-vec
+        after a C-row hand-over still runs, the handed-over ones, the C rows with an off-diagonal C column, and the row
+        at which the last handed-over tile ends."""
+        out = np.zeros(5, dtype=np.int64)
+        call("HYPRE_MI_BoomerAMGGetCRowHandoverCensus", self.h, level, out)
+        return dict(zip(("tiles", "listed", "handed", "flagged_c_rows", "w_upto"), (int(v) for v in out)))
+
+    def cycle_then_matvec(self, f):
+        """(z, w, w_full, raised): one cycle from a zero guess on f with the hand-over target set, w = A z by the path
+        the current mode takes, w_full by the full mat-vec; arrays in level 0's ordering (level_csr(0, 0)'s rows)."""
+        f = dbl(f)
+        z, w, wf = np.zeros_like(f), np.zeros_like(f), np.zeros_like(f)
+        raised = c_int()
+        call("HYPRE_MI_BoomerAMGCycleThenMatvec", self.h, f, z, w, wf, C.byref(raised))
+        return z, w, wf, bool(raised.value)
+
     def gs_sweep_paths(self, level, points, zero_guess=False):
         """Host-side census of the tile GS kernel's sweep branches for one pass: None when the pass does not run on
         the tile kernel, else dict(waves, idle, diagonal, zero, general)."""
@@ -930,6 +947,12 @@ def set_gmres_keep_directions(on):
     """GMRES / COGMRES behind BoomerAMG update x from the kept directions z_j (on, the default) or apply the
     preconditioner once more, as gmres.c does (off); process-wide, for the solves started afterwards"""
     call("HYPRE_MI_SetGmresKeepDirections", 1 if on else 0)
+
+
+def set_c_row_handover(mode):
+    """C-row hand-over of the Krylov loops in BoomerAMG's level ordering: 0 off, 1 (default) when at least 10 % of level
+    0's tiles are handed over, 2 whenever one is; process-wide, for the solves started afterwards"""
+    call("HYPRE_MI_SetCRowHandover", int(mode))
 
 
 def parcsr_value_kind(A):

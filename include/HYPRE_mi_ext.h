@@ -87,6 +87,21 @@ HYPRE_Int HYPRE_MI_GetGSChunk(HYPRE_Int *rows_per_chunk);
  * (default, env MI_HYPRE_GS_ZERO_SKIP) the residual that follows also reuses the F pass's product with the C values
  * and reads the F rows without their C columns.  Same result up to summation order. */
 HYPRE_Int HYPRE_MI_SetZeroGuessMode(HYPRE_Int mode);
+/* C-row hand-over: in a Krylov loop that runs in BoomerAMG's level ordering on one rank, the C
+ * pass that ends the cycle stores (A z)_i for the level-0 C rows whose only C column is their diagonal, and the
+ * mat-vec w = A z that follows leaves out the tiles made of such rows alone.  0 off, 1 (default, env
+ * MI_HYPRE_C_HANDOVER) when at least 10 % of level 0's tiles are handed over, 2 whenever one is.  Same result up to
+ * summation order.  Counters "handover_matvecs" / "handover_tiles_skipped" (HYPRE_MI_GetCounter). */
+HYPRE_Int HYPRE_MI_SetCRowHandover(HYPRE_Int mode);
+/* census[0 .. 4] of a level after Setup: tiles of its operator, tiles the reduced mat-vec runs, handed-over tiles,
+ * C rows with an off-diagonal C column, the row at which the last handed-over tile ends.  Only level 0 of a one-rank
+ * hierarchy swept by the tile kernel has handed-over tiles. */
+HYPRE_Int HYPRE_MI_BoomerAMGGetCRowHandoverCensus(HYPRE_Solver solver, HYPRE_Int level, HYPRE_BigInt *census);
+/* test hook: one cycle from a zero guess with the hand-over as a Krylov loop asks for it, then the mat-vec: z = M^-1 f,
+ * w = A z by the path the mode takes (raised != 0: on the tile list), w_full = A z by the full mat-vec; host arrays in
+ * level 0's ordering */
+HYPRE_Int HYPRE_MI_BoomerAMGCycleThenMatvec(HYPRE_Solver solver, const HYPRE_Real *f_host, HYPRE_Real *z_host,
+                                            HYPRE_Real *w_host, HYPRE_Real *w_full_host, HYPRE_Int *raised);
 /* test hook: fill every level's solution / scratch vectors with NaN (a zero-guess cycle that skips its zero-fills must
  * not read them) */
 HYPRE_Int HYPRE_MI_BoomerAMGPoisonWorkVectors(HYPRE_Solver solver);
@@ -148,7 +163,8 @@ HYPRE_Int HYPRE_MI_TestGmresDirectionAllocFailsAt(HYPRE_Int at);
  * path), "ij_last_kernels_us" / "ij_last_mirror_us" / "ij_last_format_us" (phases of the last device assembly).
  * Krylov solvers: "precond_cycles" (BoomerAMG cycles run as a Krylov solver's preconditioner, one per component of a
  * multivector), "gmres_direction_vectors" (vectors allocated for the directions z_j of FlexGMRES and of
- * HYPRE_MI_SetGmresKeepDirections). */
+ * HYPRE_MI_SetGmresKeepDirections), "handover_matvecs" / "handover_tiles_skipped" (mat-vecs of a Krylov loop that ran
+ * on level 0's tile list after a C-row hand-over, and the tiles they left out). */
 HYPRE_Int HYPRE_MI_GetCounter(const char *name, long long *value);
 /* One rank's block keeps 32-bit local row ids in the solve format; the entry offsets of its diagonal block are 64-bit
  * (the reference's 27-point operator at 512^3 -- 3.6e9 entries, /root/reference/src/laplace_3d_weak_scaling.hpp:558,600
