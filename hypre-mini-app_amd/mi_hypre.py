@@ -277,6 +277,8 @@ class BoomerAMG:
         for key, fn, conv in (("interp_type", "HYPRE_BoomerAMGSetInterpType", int),
                               ("num_functions", "HYPRE_BoomerAMGSetNumFunctions", int),  # unknown-based systems AMG
                               ("max_row_sum", "HYPRE_BoomerAMGSetMaxRowSum", float),
+                              ("relax_weight", "HYPRE_BoomerAMGSetRelaxWt", float),
+                              ("outer_weight", "HYPRE_BoomerAMGSetOuterWt", float),
                               ("min_coarse_size", "HYPRE_BoomerAMGSetMinCoarseSize", int),
                               ("max_coarse_size", "HYPRE_BoomerAMGSetMaxCoarseSize", int),
                               ("seq_threshold", "HYPRE_BoomerAMGSetSeqThreshold", int),

@@ -14,21 +14,11 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+from tests.handover_cases import half_anisotropic
+
 pytestmark = pytest.mark.gpu
 
 _SYS = {}
-
-
-def half_anisotropic(n=16, zc=0.5):
-    T = sp.diags([-1.0, 2.0, -1.0], [-1, 0, 1], shape=(n, n))
-    I = sp.identity(n)
-    d = np.ones(n)
-    d[n // 2:] = zc
-    Tz = sp.diags(d) @ T
-    Tz = (Tz + Tz.T) * 0.5
-    M = (sp.kron(sp.kron(I, I), T) + sp.kron(sp.kron(I, T), I) + sp.kron(sp.kron(Tz, I), I)).tocsr()
-    M.sort_indices()
-    return M
 
 
 def system(mi, case, ncomp=1):
