@@ -161,6 +161,13 @@ struct AmgLevel {
   int value_kind[3] = {0, 0, 0};
   DVec<double> d_diag, d_l1gs, d_l1jac;
   DVec<double> u, f, tmp, snap;
+  // the same vectors for `cap` components of a multivector, component-major and n apart (batched cycle, DESIGN.md
+  // section 5): allocated by the first batched cycle (BoomerAMG::mv_enter), released by Setup.  While a batched cycle
+  // runs their storage pointers stand in u / f / tmp / snap / tvec above, and the level's own ones wait here.
+  struct MvVectors {
+    int cap = 0;
+    DVec<double> u, f, tmp, snap, tvec;
+  } mv;
   // relax type 16 (Chebyshev), on every level when some relax_type slot is 16 at Setup (BoomerAMG::build_cheby):
   // eigenvalue bounds of D^-1 A, the interval [lower, upper] the polynomial is built for, its centre and half width,
   // and the coefficients (a_k, b_k) of the steps of one sweep
@@ -345,6 +352,32 @@ struct BoomerAMG {
   // host-side census of the tile Gauss-Seidel kernel's sweep branches for one pass of relax / relax_pair
   bool gs_sweep_paths(int level, int points, bool u_is_zero, long long counts[5]);
   void cycle(int level, bool u_is_zero = false);
+  // what cycle(0, ..) refreshes first: smoothers, Chebyshev data and the collapsed tail after a setting changed
+  void refresh_before_cycle();
+  // ---- batched cycle on the components of a multivector (one rank).  mv_n > 1: every level's
+  // u / f / tmp / snap / tvec hold mv_n components, n apart, and relax / relax_pair / relax_sweeps / cycle work on all of
+  // them -- the mat-vecs and the hybrid Gauss-Seidel passes through k::spmv_multi / k::gs_hybrid_multi, which sweep the
+  // operator once for up to k::multivector_batch() components; every component gets the bits of the one-vector cycle.
+  int mv_n = 1;
+  // whether this hierarchy's cycle can work on a batch: one rank without a redundant tail, no complex smoother, down /
+  // up relax types of the hybrid-GS family (3, 4, 6, 8, 13, 14), coarsest type 9 or of that family.  The one place
+  // that decides; everything else cycles component by component
+  bool mv_cycle_eligible();
+  // components per pass of a multivector with ncomp components: min(ncomp, k::multivector_batch()), or 1 when the
+  // cycle is not eligible; counts the pass under "mv_batched_cycles" / "mv_fallback_cycles" per group it will run
+  int mv_cycle_width(int ncomp);
+  void mv_enter(int nvec);  // nvec <= k::MV_MAX_BATCH
+  void mv_leave();
+  struct MvScope {
+    BoomerAMG &amg;
+    const bool on;
+    MvScope(BoomerAMG &a, int nvec) : amg(a), on(nvec > 1) {
+      if (on) amg.mv_enter(nvec);
+    }
+    ~MvScope() {
+      if (on) amg.mv_leave();
+    }
+  };
   // complex smoothers of the levels < p.smooth_num_levels (end of setup_device); fsai_signature: the FSAI and
   // iterative-ILU parameters they were built with -- a change after Setup rebuilds them before the next cycle
   void build_smoothers();

@@ -3659,6 +3659,7 @@ void BoomerAMG::setup_device() {
       Lv.d_perm.alloc(Lv.perm.size());
       MI_HIP(hipMemcpyAsync(Lv.d_perm.p, Lv.perm.dev(), Lv.perm.size() * sizeof(int), hipMemcpyDeviceToDevice, s));
     }
+    Lv.mv = AmgLevel::MvVectors();  // the next batched cycle allocates its vectors again
     Lv.u.alloc((size_t)Lv.n);
     Lv.f.alloc((size_t)Lv.n);
     Lv.tmp.alloc((size_t)Lv.n);

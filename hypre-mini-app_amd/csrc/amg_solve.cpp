@@ -154,6 +154,13 @@ void gs_pass(BoomerAMG &amg, AmgLevel &Lv, const DevCSR &M, bool zero_halo, cons
   Comm &comm = amg.my_comm();
   hipStream_t s = ctx().stream;
   MI_REQUIRE(!wout || comm.size == 1, "hybrid GS: the C-row hand-over is a one-rank path");
+  if (amg.mv_n > 1) {  // the components of a batched cycle, n apart in every vector of the level
+    MI_REQUIRE(comm.size == 1 && !wout, "hybrid GS: a batched pass is a one-rank path without the C-row hand-over");
+    const long long n = Lv.n;
+    k::gs_hybrid_multi(M, amg.mv_n, k::GsMultiStrides{n, n, n, n, 0, n}, lo, hi, split, out, f, nullptr, d, cf, points, ch,
+                       g.fwd, g.bwd, w, row_begin, row_end, s, prof, zero_from, tout, t_from);
+    return;
+  }
   if (zero_halo || comm.size == 1) {
     k::gs_hybrid(M, lo, hi, split, out, f, nullptr, d, cf, points, ch, g.fwd, g.bwd, w, row_begin, row_end, s, prof,
                  zero_from, tout, t_from, wout);
@@ -199,11 +206,17 @@ void BoomerAMG::relax(int level, int type, int points, const double *f, bool u_i
   const int prof = relax_prof_id(level, u_is_zero && zero_skip_mode() > 0);
   double *u = Lv.u.p;
   if (type == 9) {
+    if (Lv.dense && mv_n > 1) {  // the dense solve of every component of a batched cycle
+      for (int c = 0; c < mv_n; c++) dense_solve(Lv, comm, f + (size_t)c * Lv.n, u + (size_t)c * Lv.n, s);
+      return;
+    }
     if (dense_solve(Lv, comm, f, u, s)) return;
     type = p.relax_type[0];  // coarsest level too large for a dense solve
   }
   Lv.t_valid = false;
   const GsKind g = classify(type);
+  MI_REQUIRE(mv_n == 1 || !(g.two_stage || g.cheby || g.mcgs || g.jacobi),
+             "BoomerAMG: only the hybrid Gauss-Seidel family relaxes a batch of components (mv_cycle_eligible)");
   const double w = p.relax_weight * p.outer_weight;
   const bool has_cf = Lv.has_cf && !Lv.cf.empty();
   const signed char *cf = has_cf ? Lv.d_cf.p : nullptr;
@@ -286,7 +299,7 @@ void BoomerAMG::relax(int level, int type, int points, const double *f, bool u_i
   } else {  // lone C or F pass: only the swept chunks were written
     const long long r0 = (long long)(row_begin / ch) * ch;
     const long long r1 = std::min<long long>(((long long)row_end + ch - 1) / ch * ch, Lv.n);
-    k::copy(Lv.snap.p + r0, u + r0, (int)(r1 - r0), s);
+    for (int c = 0; c < mv_n; c++) k::copy(Lv.snap.p + (size_t)c * Lv.n + r0, u + (size_t)c * Lv.n + r0, (int)(r1 - r0), s);
   }
 }
 
@@ -369,6 +382,8 @@ bool BoomerAMG::gs_sweep_paths(int level, int points, bool u_is_zero, long long 
 void BoomerAMG::relax_sweeps(int level, int which, const double *f, bool u_is_zero, double *wout) {
   const int type = p.relax_type[which];
   const bool has_cf = L[(size_t)level].has_cf;
+  MI_REQUIRE(mv_n == 1 || which == 2 || !L[(size_t)level].smoother,
+             "BoomerAMG: a complex smoother does not relax a batch of components (mv_cycle_eligible)");
   if (FsaiSolver *fs = level_fsai(L[(size_t)level]); fs && which != 2) {
     // FSAI (smooth_type 4): per sweep one step u += omega G^T G (f - A u), 3 launches; on a zero guess u = omega G^T G f
     AmgLevel &Lv = L[(size_t)level];
@@ -443,10 +458,12 @@ bool BoomerAMG::zero_cycle_ignores_u(int level) {
   return k::gs_ignores_zero_vector(M, ch);
 }
 
-// one cycle on the level's own f (Lv.f) and u (Lv.u)
-void BoomerAMG::cycle(int level, bool u_is_zero) {
-  const int nlev = (int)L.size();
-  if (level == 0 && fsai_signature != current_fsai_signature()) {
+void BoomerAMG::refresh_before_cycle() {
+  // (a batched cycle has been through here before its vectors were swapped in: BoomerAMG::mv_cycle_eligible)
+  MI_REQUIRE(mv_n == 1 || (fsai_signature == current_fsai_signature() &&
+                           (collapsed_level < 0 || collapsed_signature == cycle_signature())),
+             "BoomerAMG: a setting changed inside a batched cycle");
+  if (fsai_signature != current_fsai_signature()) {
     build_smoothers();  // an FSAI or iterative-ILU parameter changed after Setup: the smoothers are rebuilt
     if (tail) {         // the redundant tail rebuilds its own at its next cycle
       tail->p.fsai_algo_type = p.fsai_algo_type;
@@ -462,24 +479,30 @@ void BoomerAMG::cycle(int level, bool u_is_zero) {
       tail->p.ilu_iter_tol = p.ilu_iter_tol;
     }
   }
-  if (level == 0) {
-    if (tail) {  // the redundant tail rebuilds its own at its next cycle
-      tail->p.cheby_order = p.cheby_order;
-      tail->p.cheby_fraction = p.cheby_fraction;
-      tail->p.cheby_eig_est = p.cheby_eig_est;
-      tail->p.cheby_variant = p.cheby_variant;
-      tail->p.cheby_scale = p.cheby_scale;
-    }
-    refresh_cheby();  // a Chebyshev parameter changed after Setup
+  if (tail) {  // the redundant tail rebuilds its own at its next cycle
+    tail->p.cheby_order = p.cheby_order;
+    tail->p.cheby_fraction = p.cheby_fraction;
+    tail->p.cheby_eig_est = p.cheby_eig_est;
+    tail->p.cheby_variant = p.cheby_variant;
+    tail->p.cheby_scale = p.cheby_scale;
   }
-  if (level == 0 && collapsed_level >= 0 && collapsed_signature != cycle_signature())
+  refresh_cheby();  // a Chebyshev parameter changed after Setup
+  if (collapsed_level >= 0 && collapsed_signature != cycle_signature())
     build_collapsed_tail();  // a cycle parameter changed after Setup: the tabulated map is of another cycle
+}
+
+// one cycle on the level's own f (Lv.f) and u (Lv.u); mv_n > 1: on the mv_n components these vectors hold, n apart
+void BoomerAMG::cycle(int level, bool u_is_zero) {
+  const int nlev = (int)L.size();
+  if (level == 0) refresh_before_cycle();
   AmgLevel &Lv = L[(size_t)level];
   if (level == 0) handover_done = false;
   if (level == collapsed_level && u_is_zero) {  // the tabulated map of this level's whole sub-cycle
-    k::dense_matvec_t(collapsed_Bt.p, Lv.f.p, Lv.u.p, collapsed_n, ctx().stream);
+    for (int c = 0; c < mv_n; c++)
+      k::dense_matvec_t(collapsed_Bt.p, Lv.f.p + (size_t)c * Lv.n, Lv.u.p + (size_t)c * Lv.n, collapsed_n, ctx().stream);
     return;
   }
+  MI_REQUIRE(mv_n == 1 || !tail, "BoomerAMG: a redundant tail does not cycle a batch of components (mv_cycle_eligible)");
   if (level == nlev - 1) {
     if (tail)
       tail_cycle(u_is_zero);
@@ -491,15 +514,26 @@ void BoomerAMG::cycle(int level, bool u_is_zero) {
   Comm &comm = my_comm();
   hipStream_t s = ctx().stream;
   relax_sweeps(level, 0, Lv.f.p, u_is_zero && p.num_sweeps[0] > 0);
+  // one vector, or the mv_n components of a batched cycle (xs / bs / ys: their strides, this level's n or the next one's)
+  auto matvec = [&](ParCSR &M, double alpha, const double *x, long long xs, double beta, const double *b, long long bs,
+                    double *y, long long ys, int prof, const DevCSR *diag_op = nullptr, const double *b_lo = nullptr,
+                    int b_split = 0) {
+    if (mv_n == 1)
+      M.matvec(comm, alpha, x, beta, b, y, s, prof, diag_op, b_lo, b_split);
+    else
+      M.matvec_multi(comm, mv_n, alpha, x, xs, beta, b, bs, y, ys, s, prof, diag_op, b_lo, bs, b_split);
+  };
+  const long long n = Lv.n, nn = Ln.n;
   // r = f - A u ; f_c = P^T r ; u_c = 0
   if (Lv.t_valid && Lv.has_Ar)  // F rows: f - A_FC u_C is in tvec already, only their F columns are left
-    Lv.A->matvec(comm, -1.0, Lv.u.p, 1.0, Lv.tvec.p, Lv.tmp.p, s, k::prof_level(k::PROF_LVL_RESID, level), &Lv.Ar, Lv.f.p,
-                 std::min(Lv.t_from, Lv.n));
+    matvec(*Lv.A, -1.0, Lv.u.p, n, 1.0, Lv.tvec.p, n, Lv.tmp.p, n, k::prof_level(k::PROF_LVL_RESID, level), &Lv.Ar, Lv.f.p,
+           std::min(Lv.t_from, Lv.n));
   else
-    Lv.A->matvec(comm, -1.0, Lv.u.p, 1.0, Lv.f.p, Lv.tmp.p, s, k::prof_level(k::PROF_LVL_RESID, level));
+    matvec(*Lv.A, -1.0, Lv.u.p, n, 1.0, Lv.f.p, n, Lv.tmp.p, n, k::prof_level(k::PROF_LVL_RESID, level));
   Lv.t_valid = false;
-  Lv.Rm->matvec(comm, 1.0, Lv.tmp.p, 0.0, nullptr, Ln.f.p, s, k::prof_level(k::PROF_LVL_RESTRICT, level));
-  if (!zero_cycle_ignores_u(level + 1)) k::fill(Ln.u.p, Ln.n, 0.0, s);
+  matvec(*Lv.Rm, 1.0, Lv.tmp.p, n, 0.0, nullptr, 0, Ln.f.p, nn, k::prof_level(k::PROF_LVL_RESTRICT, level));
+  if (!zero_cycle_ignores_u(level + 1))
+    for (int c = 0; c < mv_n; c++) k::fill(Ln.u.p + (size_t)c * Ln.n, Ln.n, 0.0, s);
   // the coarsest level is visited once per cycle; with a redundant tail the count continues into the tail
   const bool tail_next = tail && level + 1 == nlev - 1;
   const bool next_is_coarsest = tail_next ? tail->L.size() == 1 : level + 1 == nlev - 1;
@@ -511,9 +545,64 @@ void BoomerAMG::cycle(int level, bool u_is_zero) {
     if (next) k::gather(tail_e.p, tail_pcol.p, Lv.Pm->halo.d_xext.p, next, s);
     Lv.Pm->matvec_ext_ready(1.0, Ln.u.p, 1.0, Lv.u.p, Lv.u.p, s);
   } else {
-    Lv.Pm->matvec(comm, 1.0, Ln.u.p, 1.0, Lv.u.p, Lv.u.p, s, k::prof_level(k::PROF_LVL_PROLONG, level));
+    matvec(*Lv.Pm, 1.0, Ln.u.p, nn, 1.0, Lv.u.p, n, Lv.u.p, n, k::prof_level(k::PROF_LVL_PROLONG, level));
   }
-  relax_sweeps(level, 1, Lv.f.p, false, level == 0 ? handover_w : nullptr);
+  relax_sweeps(level, 1, Lv.f.p, false, (level == 0 && mv_n == 1) ? handover_w : nullptr);
+}
+
+bool BoomerAMG::mv_cycle_eligible() {
+  if (L.empty() || my_comm().size != 1 || tail) return false;
+  refresh_before_cycle();  // the smoothers as the cycle will find them
+  const int nlev = (int)L.size();
+  if (p.smooth_num_levels > 0)
+    for (int l = 0; l + 1 < nlev; l++)
+      if (L[(size_t)l].smoother) return false;
+  auto gs_family = [](int t) { return t == 3 || t == 4 || t == 6 || t == 8 || t == 13 || t == 14; };
+  if (nlev > 1 && !(gs_family(p.relax_type[0]) && gs_family(p.relax_type[1]))) return false;
+  // (a coarsest level too large for its dense solve takes the down type: BoomerAMG::relax)
+  return p.relax_type[2] == 9 ? (L.back().dense || gs_family(p.relax_type[0])) : gs_family(p.relax_type[2]);
+}
+
+int BoomerAMG::mv_cycle_width(int ncomp) {
+  if (ncomp <= 1) return 1;
+  const int width = std::min(ncomp, k::multivector_batch());
+  const bool batch = width > 1 && mv_cycle_eligible();
+  (batch ? ctx().n_mv_batched_cycles : ctx().n_mv_fallback_cycles) += batch ? (ncomp + width - 1) / width : 1;
+  return batch ? width : 1;
+}
+
+void BoomerAMG::mv_enter(int nvec) {
+  MI_REQUIRE(mv_n == 1 && nvec >= 2 && nvec <= k::MV_MAX_BATCH, "BoomerAMG: a batch holds 2 to 4 components, one batch at a time");
+  for (AmgLevel &Lv : L) {
+    if (Lv.mv.cap >= nvec) continue;
+    const size_t len = (size_t)nvec * (size_t)Lv.n;
+    DVec<double> *v[5] = {&Lv.mv.u, &Lv.mv.f, &Lv.mv.tmp, &Lv.mv.snap, &Lv.mv.tvec};
+    for (int q = 0; q < 5; q++) {
+      if (q == 4 && !Lv.tvec.p) continue;
+      v[q]->alloc(len);
+      // zeroed, as Setup leaves the level's own vectors (so MI_HYPRE_POISON_ALLOC does not reach them either).  The
+      // components lie n apart: with an odd n a component starts on an 8-byte boundary only, like the components of a
+      // Krylov multivector, which the pairwise vector kernels (k::fill, k::copy, k::dot) have always been handed
+      if (len) zero_on_stream(v[q]->p, len * sizeof(double));
+    }
+    Lv.mv.cap = nvec;
+  }
+  for (AmgLevel &Lv : L) {
+    std::swap(Lv.u.p, Lv.mv.u.p), std::swap(Lv.f.p, Lv.mv.f.p), std::swap(Lv.tmp.p, Lv.mv.tmp.p);
+    std::swap(Lv.snap.p, Lv.mv.snap.p), std::swap(Lv.tvec.p, Lv.mv.tvec.p);
+    Lv.t_valid = false;
+  }
+  mv_n = nvec;
+}
+
+void BoomerAMG::mv_leave() {
+  // (a sweep may have swapped u and snap: the two batch buffers have one size, whichever comes back as which)
+  for (AmgLevel &Lv : L) {
+    std::swap(Lv.u.p, Lv.mv.u.p), std::swap(Lv.f.p, Lv.mv.f.p), std::swap(Lv.tmp.p, Lv.mv.tmp.p);
+    std::swap(Lv.snap.p, Lv.mv.snap.p), std::swap(Lv.tvec.p, Lv.mv.tvec.p);
+    Lv.t_valid = false;
+  }
+  mv_n = 1;
 }
 
 bool BoomerAMG::handover_wanted() const {
@@ -537,6 +626,7 @@ bool any_profile_class_on() {
 }  // namespace
 
 void BoomerAMG::tabulate_cycle(int lt, DVec<double> &Bt) {
+  MI_REQUIRE(mv_n == 1, "BoomerAMG: the collapsed tail is tabulated outside a batched cycle");
   AmgLevel &Lv = L[(size_t)lt];
   const int n = Lv.n;
   hipStream_t s = ctx().stream;
@@ -696,7 +786,9 @@ void BoomerAMG::solve(ParCSR &A, ParVector &b, ParVector &x) {
   hipStream_t s = ctx().stream;
   AmgLevel &L0 = L[0];
   const bool permuted = !L0.perm.empty();
-  const int n = L0.n, nc = b.ncomp;  // a multivector is cycled component by component
+  // a multivector is cycled `width` components per pass where the cycle is eligible (mv_cycle_eligible), else
+  // component by component
+  const int n = L0.n, nc = b.ncomp;
   int it = 0;
   double rel = 0.0, bn = 0.0;
   if (p.tol > 0.0) bn = std::sqrt(par_dot_host(comm, b.all(), b.all(), b.len(), s));
@@ -706,36 +798,57 @@ void BoomerAMG::solve(ParCSR &A, ParVector &b, ParVector &x) {
   zero_guess_hint() = false;
   while (it < p.max_iter) {
     const bool zero = zero_first && it == 0;
-    for (int c = 0; c < nc; c++) {
-      const double *bc = b.all() + (size_t)c * (size_t)n;
-      double *xc = x.all() + (size_t)c * (size_t)n;
-      // caller order -> level-0 (C-first) order
-      if (it == 0 || nc > 1) {
-        if (permuted)
-          k::gather(bc, L0.d_perm.p, L0.f.p, n, s);
+    const int width = mv_cycle_width(nc);
+    for (int c0 = 0; c0 < nc;) {
+      const int nv = std::min(width, nc - c0);
+      MvScope batch(*this, nv);  // nv > 1: L0.f / L0.u hold nv components from here on
+      for (int j = 0; j < nv; j++) {
+        const double *bc = b.all() + (size_t)(c0 + j) * (size_t)n;
+        const double *xc = x.all() + (size_t)(c0 + j) * (size_t)n;
+        double *fj = L0.f.p + (size_t)j * (size_t)n, *uj = L0.u.p + (size_t)j * (size_t)n;
+        // caller order -> level-0 (C-first) order
+        if (it == 0 || nc > 1) {
+          if (permuted)
+            k::gather(bc, L0.d_perm.p, fj, n, s);
+          else
+            k::copy(bc, fj, n, s);
+        }
+        if (zero) {
+          if (!zero_cycle_ignores_u(0)) k::fill(uj, n, 0.0, s);
+        } else if (permuted)
+          k::gather(xc, L0.d_perm.p, uj, n, s);
         else
-          k::copy(bc, L0.f.p, n, s);
+          k::copy(xc, uj, n, s);
       }
-      if (zero) {
-        if (!zero_cycle_ignores_u(0)) k::fill(L0.u.p, n, 0.0, s);
-      } else if (permuted)
-        k::gather(xc, L0.d_perm.p, L0.u.p, n, s);
-      else
-        k::copy(xc, L0.u.p, n, s);
-      if (ctx().krylov_precond_depth > 0) ctx().n_precond_cycles++;  // HYPRE_MI_GetCounter "precond_cycles"
+      if (ctx().krylov_precond_depth > 0) ctx().n_precond_cycles += nv;  // HYPRE_MI_GetCounter "precond_cycles"
       cycle(0, zero);
-      if (permuted)
-        k::scatter_set(xc, L0.d_perm.p, L0.u.p, n, s);
-      else
-        k::copy(L0.u.p, xc, n, s);
+      for (int j = 0; j < nv; j++) {
+        double *xc = x.all() + (size_t)(c0 + j) * (size_t)n;
+        const double *uj = L0.u.p + (size_t)j * (size_t)n;
+        if (permuted)
+          k::scatter_set(xc, L0.d_perm.p, uj, n, s);
+        else
+          k::copy(uj, xc, n, s);
+      }
+      c0 += nv;
     }
     it++;
     if (p.tol > 0.0) {
+      // the residual of every component, `width` of them per pass over A; their squared norms add up in component order
       double rr = 0.0;
-      for (int c = 0; c < nc; c++) {
-        const size_t o = (size_t)c * (size_t)n;
-        A.matvec(comm, -1.0, x.all() + o, 1.0, b.all() + o, L0.tmp.p, s);
-        rr += par_dot_host(comm, L0.tmp.p, L0.tmp.p, n, s);
+      for (int c0 = 0; c0 < nc;) {
+        const int nv = std::min(width, nc - c0);
+        const size_t o = (size_t)c0 * (size_t)n;
+        MvScope batch(*this, nv);  // nv > 1: L0.tmp holds nv components
+        if (nv == 1)
+          A.matvec(comm, -1.0, x.all() + o, 1.0, b.all() + o, L0.tmp.p, s);
+        else
+          A.matvec_multi(comm, nv, -1.0, x.all() + o, n, 1.0, b.all() + o, n, L0.tmp.p, n, s);
+        for (int j = 0; j < nv; j++) {
+          const double *rj = L0.tmp.p + (size_t)j * (size_t)n;
+          rr += par_dot_host(comm, rj, rj, n, s);
+        }
+        c0 += nv;
       }
       const double rn = std::sqrt(rr);
       rel = (bn > 0.0) ? rn / bn : rn;

@@ -1127,6 +1127,20 @@ HYPRE_Int HYPRE_ParCSRMatrixMatvec(HYPRE_Complex alpha, HYPRE_ParCSRMatrix A, HY
   MI_HIP(hipStreamSynchronize(ctx().stream));
   API_END
 }
+HYPRE_Int HYPRE_MI_ParCSRMatrixMatvecMulti(HYPRE_Complex alpha, HYPRE_ParCSRMatrix A, HYPRE_ParVector x, HYPRE_Complex beta,
+                                           HYPRE_ParVector y) {
+  API_BEGIN
+  if (!A || !x || !y) fail(HYPRE_ERROR_ARG, "ParCSRMatrixMatvecMulti: NULL argument");
+  ParCSR *a = PM(A);
+  if (PV(x)->n != a->nrows || PV(y)->n != a->nrows) fail(HYPRE_ERROR_ARG, "ParCSRMatrixMatvecMulti: size mismatch");
+  if (PV(x)->ncomp != PV(y)->ncomp) fail(HYPRE_ERROR_ARG, "ParCSRMatrixMatvecMulti: x and y differ in their number of components");
+  if (PV(x) == PV(y)) fail(HYPRE_ERROR_ARG, "ParCSRMatrixMatvecMulti: x and y are the same vector");
+  const long long n = a->nrows;
+  a->matvec_multi(current_comm(), PV(x)->ncomp, alpha, PV(x)->all(), n, beta, PV(y)->all(), n, PV(y)->all(), n, ctx().stream,
+                  k::PROF_SPMV_L0);
+  MI_HIP(hipStreamSynchronize(ctx().stream));
+  API_END
+}
 HYPRE_Int HYPRE_ParCSRMatrixGetDims(HYPRE_ParCSRMatrix A, HYPRE_BigInt *Mr, HYPRE_BigInt *Nc) {
   API_BEGIN
   if (!A) fail(HYPRE_ERROR_ARG, "ParCSRMatrixGetDims: NULL handle");
@@ -1972,6 +1986,12 @@ HYPRE_Int HYPRE_MI_GetCounter(const char *name, long long *value) {
     *value = ctx().n_handover_matvecs;
   else if (n == "handover_tiles_skipped")
     *value = ctx().n_handover_tiles_skipped;
+  else if (n == "mv_batched_cycles")
+    *value = ctx().n_mv_batched_cycles;
+  else if (n == "mv_batched_matvecs")
+    *value = ctx().n_mv_batched_matvecs;
+  else if (n == "mv_fallback_cycles")
+    *value = ctx().n_mv_fallback_cycles;
   else if (setup_reuse_counter(n.c_str()) >= 0)
     *value = setup_reuse_counter(n.c_str());
   else if (dist_setup_counter(n.c_str()) >= 0)
@@ -2256,6 +2276,19 @@ HYPRE_Int HYPRE_MI_ArenaSelfTest(HYPRE_Int seed, HYPRE_Int rounds, HYPRE_BigInt 
 HYPRE_Int HYPRE_MI_SetValueDictionary(HYPRE_Int on) {
   API_BEGIN
   k::set_value_dictionary(on != 0);
+  API_END
+}
+HYPRE_Int HYPRE_MI_SetMultivectorBatch(HYPRE_Int width) {
+  API_BEGIN
+  if (width < 1 || width > k::MV_MAX_BATCH)
+    fail(HYPRE_ERROR_ARG, "SetMultivectorBatch: the width is 1 (component by component), 2, 3 or 4 components per pass");
+  k::set_multivector_batch(width);
+  API_END
+}
+HYPRE_Int HYPRE_MI_GetMultivectorBatch(HYPRE_Int *width) {
+  API_BEGIN
+  if (!width) fail(HYPRE_ERROR_ARG, "GetMultivectorBatch: NULL argument");
+  *width = k::multivector_batch();
   API_END
 }
 HYPRE_Int HYPRE_MI_SetGmresKeepDirections(HYPRE_Int on) {
@@ -2634,6 +2667,58 @@ HYPRE_Int HYPRE_MI_BoomerAMGRelaxPairLevel(HYPRE_Solver solver, HYPRE_Int level,
   if (n) d2h(u_host, Lv.u.p, (size_t)n * sizeof(double), nullptr);
   API_END
 }
+// the two hooks above on nvec component-major vectors at once (n apart): the passes of a batched cycle
+static void relax_multi_check(AmgSolver *a, int level, int relax_type, int nvec, const char *who) {
+  if (!a->amg.is_setup) fail(HYPRE_ERROR_GENERIC, std::string(who) + ": AMG is not set up");
+  if (level < 0 || level >= (int)a->amg.L.size()) fail(HYPRE_ERROR_ARG, "AMG level out of range");
+  if (nvec < 2 || nvec > k::MV_MAX_BATCH) fail(HYPRE_ERROR_ARG, std::string(who) + ": nvec is 2, 3 or 4");
+  if (relax_type != 3 && relax_type != 4 && relax_type != 6 && relax_type != 8 && relax_type != 13 && relax_type != 14)
+    fail(HYPRE_ERROR_ARG, std::string(who) + ": only the hybrid Gauss-Seidel relax types 3, 4, 6, 8, 13, 14 work on a batch");
+  if (current_comm().size != 1) fail(HYPRE_ERROR_GENERIC, std::string(who) + ": a batched pass is a one-rank path");
+}
+HYPRE_Int HYPRE_MI_BoomerAMGRelaxLevelMulti(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int relax_type, HYPRE_Int points,
+                                            HYPRE_Int nvec, const HYPRE_Real *f_host, HYPRE_Real *u_host) {
+  API_BEGIN
+  AmgSolver *a = AMG(solver);
+  relax_multi_check(a, level, relax_type, nvec, "RelaxLevelMulti");
+  AmgLevel &Lv = a->amg.L[(size_t)level];
+  const size_t len = (size_t)nvec * (size_t)Lv.n;
+  BoomerAMG::MvScope batch(a->amg, nvec);
+  DVec<double> f(len);
+  if (len) {
+    f.upload(f_host, len);
+    MI_HIP(hipStreamSynchronize(ctx().stream));
+    MI_HIP(hipMemcpy(Lv.u.p, u_host, len * sizeof(double), hipMemcpyHostToDevice));
+  }
+  a->amg.relax(level, relax_type, points, f.p);
+  MI_HIP(hipStreamSynchronize(ctx().stream));
+  if (len) d2h(u_host, Lv.u.p, len * sizeof(double), nullptr);
+  API_END
+}
+HYPRE_Int HYPRE_MI_BoomerAMGRelaxPairLevelMulti(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int relax_type, HYPRE_Int first,
+                                                HYPRE_Int zero_guess, HYPRE_Int nvec, const HYPRE_Real *f_host,
+                                                HYPRE_Real *u_host) {
+  API_BEGIN
+  AmgSolver *a = AMG(solver);
+  relax_multi_check(a, level, relax_type, nvec, "RelaxPairLevelMulti");
+  if (first != 1 && first != -1) fail(HYPRE_ERROR_ARG, "RelaxPairLevelMulti: first is +1 (C then F) or -1 (F then C)");
+  AmgLevel &Lv = a->amg.L[(size_t)level];
+  const size_t len = (size_t)nvec * (size_t)Lv.n;
+  BoomerAMG::MvScope batch(a->amg, nvec);
+  DVec<double> f(len);
+  if (len) {
+    f.upload(f_host, len);
+    MI_HIP(hipStreamSynchronize(ctx().stream));
+    if (zero_guess)
+      MI_HIP(hipMemset(Lv.u.p, 0, len * sizeof(double)));
+    else
+      MI_HIP(hipMemcpy(Lv.u.p, u_host, len * sizeof(double), hipMemcpyHostToDevice));
+  }
+  a->amg.relax_pair(level, relax_type, first, f.p, zero_guess != 0);
+  MI_HIP(hipStreamSynchronize(ctx().stream));
+  if (len) d2h(u_host, Lv.u.p, len * sizeof(double), nullptr);
+  API_END
+}
 HYPRE_Int HYPRE_MI_BoomerAMGGetGSSweepPaths(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int points, HYPRE_Int zero_guess,
                                             HYPRE_Int *on_tiles, HYPRE_BigInt *counts) {
   API_BEGIN
@@ -2774,6 +2859,36 @@ HYPRE_Int HYPRE_MI_SolveKernelChoice(HYPRE_Int family, HYPRE_Int xcache, HYPRE_I
   d.nrows = nrows;
   d.rowlen_p95 = rowlen_p95;
   snprintf(name, (size_t)max_len, "%s", (family == 0 ? k::choose_stream_kernel(d) : k::choose_gs_kernel(d)).name);
+  API_END
+}
+HYPRE_Int HYPRE_MI_SolveKernelChoiceMulti(HYPRE_Int nvec, HYPRE_Int family, HYPRE_Int xcache, HYPRE_Int tile_entries,
+                                          HYPRE_Int has_fp32, HYPRE_Int has_dictionary, HYPRE_Int epilogue, HYPRE_Int level0,
+                                          HYPRE_Int chunk, HYPRE_Int tiles, HYPRE_BigInt nnz, HYPRE_Int nrows,
+                                          HYPRE_Int rowlen_p95, char *name, HYPRE_Int max_len, HYPRE_Int *batched) {
+  API_BEGIN
+  if (!name || max_len < 1 || !batched) fail(HYPRE_ERROR_ARG, "SolveKernelChoiceMulti: no buffer");
+  if (nvec < 1 || nvec > k::MV_MAX_BATCH) fail(HYPRE_ERROR_ARG, "SolveKernelChoiceMulti: nvec is 1, 2, 3 or 4 components per pass");
+  if (family != 0 && family != 1) fail(HYPRE_ERROR_ARG, "SolveKernelChoiceMulti: family must be 0 (SpMV / Jacobi) or 1 (hybrid GS)");
+  if (tile_entries != k::SPMV_TILE && tile_entries != k::SPMV_TILE_WIDE) fail(HYPRE_ERROR_ARG, "SolveKernelChoiceMulti: tile_entries must be 2048 or 4096");
+  if (epilogue != 0 && epilogue != 1 && epilogue != 3)
+    fail(HYPRE_ERROR_ARG, "SolveKernelChoiceMulti: epilogue must be 0, 1 or 3 (the in-place colour pass)");
+  if (chunk < 1 || chunk > k::GS_MAX_CHUNK) fail(HYPRE_ERROR_ARG, "SolveKernelChoiceMulti: chunk out of range");
+  if (nnz < 0 || nrows < 1 || rowlen_p95 < 0) fail(HYPRE_ERROR_ARG, "SolveKernelChoiceMulti: an operator has nnz >= 0, nrows >= 1, rowlen_p95 >= 0");
+  k::SolveKernelDesc d;
+  d.xcache = xcache != 0;
+  d.tile_entries = tile_entries;
+  d.format = value_format_of(has_fp32 != 0, has_dictionary != 0);
+  d.epi = epilogue;
+  d.level0 = level0 != 0;
+  d.chunk = chunk;
+  d.tiles = tiles != 0;
+  d.nnz = nnz;
+  d.nrows = nrows;
+  d.rowlen_p95 = rowlen_p95;
+  d.nvec = nvec;
+  const k::KernelChoice c = family == 0 ? k::choose_stream_kernel(d) : k::choose_gs_kernel(d);
+  snprintf(name, (size_t)max_len, "%s", c.name);
+  *batched = c.batched ? 1 : 0;
   API_END
 }
 HYPRE_Int HYPRE_MI_ChebyKernelChoice(HYPRE_Int xcache, HYPRE_Int tile_entries, HYPRE_Int has_fp32, HYPRE_Int has_dictionary,

@@ -404,6 +404,205 @@ __global__ __launch_bounds__(BLOCK) void spmv_stream_xc(int nb, int xchunk, cons
   }
 }
 
+// ---------------------------------------------------------------------------
+// spmv_stream_xc, epilogue 0, for the NV components of a multivector in one pass over the operator:
+//   y_c = alpha A x_c + beta b_c,   c = 0 .. NV-1
+// The part of spmv_stream_xc that does not depend on the vector -- descriptor, column list, column words, value
+// stream, the rows' entry ranges and their place in y -- is requested once per tile and stays in registers (the values
+// as doubles, whatever the storage format: the dictionary is looked up and the floats are widened once).  The part that
+// does -- gather -> LDS x cache -> products -> product buffer -> row sums -> store -- runs once per component, with
+// that kernel's operands in that kernel's order, so every component gets the bits the single-vector kernel gives it
+// (tests/test_gpu_multivector_batch.py).  The gathers of component c + 1 are issued as soon as the x cache of
+// component c stands, and land while its products and row sums are formed.
+// Every vector carries its own component stride (MvStrides, in doubles): Krylov multivectors are component-major
+// with the local row count as stride, level vectors with the level's.
+// ---------------------------------------------------------------------------
+struct MvStrides {
+  long long x, y, b, b_lo;
+};
+template <int NV, int TAG, bool VAL8, int BLOCK, bool VAL4 = false>
+__global__ __launch_bounds__(BLOCK) void spmv_stream_xc_mv(int nb, int xchunk, const int *__restrict__ tdesc,
+                                                           const int *__restrict__ ia, const int *__restrict__ ja,
+                                                           const double *__restrict__ av,
+                                                           const int *__restrict__ ucols,
+                                                           const unsigned short *__restrict__ lcol,
+                                                           const double *__restrict__ x, double *__restrict__ y,
+                                                           EpiArgs e, MvStrides st,
+                                                           const unsigned char *__restrict__ vidx,
+                                                           const double *__restrict__ vlut) {
+  static_assert(!(VAL8 && VAL4), "one value format per instantiation");
+  static_assert(NV >= 2 && NV <= 4, "2, 3 or 4 components per pass");
+  constexpr int TILE = 8 * BLOCK;
+  __shared__ double prod[TILE];
+  __shared__ double slut[VAL8 ? 256 : 1];
+  double *xs = prod;
+  const int blk = xcd_remap(blockIdx.x, xchunk);
+  if (blk >= nb) return;
+  const int tid = threadIdx.x;
+  double lutv = 0.0;
+  if (VAL8 && tid < 256) lutv = vlut[tid];
+  const int4 d0 = reinterpret_cast<const int4 *>(tdesc)[2 * blk];
+  const int4 d1 = reinterpret_cast<const int4 *>(tdesc)[2 * blk + 1];
+  const int r0 = d0.x, r1 = d0.y, len = d0.w, u0 = d1.x, nu = d1.y;
+  const long long base64 = ((long long)d1.z << 32) | (long long)(unsigned)d0.z;
+  if (len >= TILE) {
+    // one row longer than the tile: one pass over it, one accumulator per component
+    double s[NV];
+#pragma unroll
+    for (int c = 0; c < NV; c++) s[c] = 0.0;
+    for (long long k = base64 + tid; k < base64 + len; k += BLOCK) {
+      const double a = VAL4 ? (double)reinterpret_cast<const float *>(av)[k] : av[k];
+      const int j = ja[k];
+#pragma unroll
+      for (int c = 0; c < NV; c++) s[c] += a * x[c * st.x + j];
+    }
+#pragma unroll
+    for (int c = 0; c < NV; c++) {
+      const double sc = wave_sum(s[c]);
+      if ((tid & 63) == 0) prod[c * (BLOCK / 64) + (tid >> 6)] = sc;
+    }
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+      for (int c = 0; c < NV; c++) {
+        const double *pc = prod + c * (BLOCK / 64);
+        double tot = pc[0] + pc[1] + pc[2] + pc[3];
+        for (int wv = 4; wv < BLOCK / 64; wv++) tot += pc[wv];
+        EpiArgs ec = e;
+        ec.b = e.b + c * st.b;
+        ec.b_lo = e.b_lo ? e.b_lo + c * st.b_lo : nullptr;
+        epilogue<0>(r0, tot, x + c * st.x, y + c * st.y, ec);
+      }
+    }
+    return;
+  }
+  constexpr int NU = TILE / BLOCK;
+  int uc[NU];
+#pragma unroll
+  for (int q = 0; q < NU; q++) {
+    const int k = tid + q * BLOCK;
+    uc[q] = 0;  // (a select, see spmv_stream_xc)
+    if (k < nu) uc[q] = LIST_LOAD(ucols + u0 + k);
+  }
+  const long long base_al64 = base64 & ~1LL;
+  const int base = (int)(base64 - base_al64);  // tile-local: the aligned start is 0, the first entry 0 or 1
+  const int end = base + len;
+  const int cnt = end;
+  const unsigned ia_off = (unsigned)base_al64;
+  const float *av4 = reinterpret_cast<const float *>(av) + base_al64;
+  av += base_al64;
+  lcol += base_al64;
+  if (VAL8) vidx += base_al64;
+  constexpr int NIT = TILE / (2 * BLOCK);
+  d2_t vv[NIT];      // the values: as loaded (fp64), or from the first barrier on (dictionary, fp32)
+  f2_t vf[NIT];
+  unsigned cw[NIT], vw[NIT];
+#pragma unroll
+  for (int it = 0; it < NIT; it++) {
+    const int k = 2 * tid + it * 2 * BLOCK;
+    cw[it] = 0;
+    vw[it] = 0;
+    vv[it] = d2_t{0.0, 0.0};
+    if (k < cnt) {
+      if (VAL8)
+        vw[it] = STREAM_LOAD(reinterpret_cast<const unsigned short *>(vidx + k));
+      else if (VAL4)
+        vf[it] = STREAM_LOAD(reinterpret_cast<const f2_t *>(av4 + k));
+      else
+        vv[it] = STREAM_LOAD(reinterpret_cast<const d2_t *>(av + k));
+      cw[it] = STREAM_LOAD(reinterpret_cast<const unsigned *>(lcol + k));
+    }
+  }
+  double xv[NU];
+#pragma unroll
+  for (int q = 0; q < NU; q++) xv[q] = x[uc[q]];
+  const int nr = r1 - r0;
+  int G = 1;
+  while (G < 64 && nr * G * 2 <= BLOCK) G <<= 1;
+  const int lane = tid & (G - 1);
+  const int rr = tid / G;
+  int s0 = 0, s1 = 0;
+  int ro = r0 + rr;
+  if (rr < nr) {
+    s0 = (int)((unsigned)ia[r0 + rr] - ia_off);
+    s1 = (int)((unsigned)ia[r0 + rr + 1] - ia_off);
+    if (e.rowmap && lane == 0) ro = e.rowmap[r0 + rr];
+  }
+  if (VAL8 && tid < 256) slut[tid] = lutv;  // visible after the first barrier
+#pragma unroll 1
+  for (int c = 0; c < NV; c++) {
+    const double *bc = e.b + c * st.b;
+    const double *bloc = e.b_lo ? e.b_lo + c * st.b_lo : nullptr;
+    double *yc = y + c * st.y;
+    double bpre = 0.0;
+    if (rr < nr && e.beta != 0.0 && lane == 0) bpre = ((bloc && ro < e.b_split) ? bloc : bc)[ro];
+#pragma unroll
+    for (int q = 0; q < NU; q++) {
+      const int k = tid + q * BLOCK;
+      if (k < nu) xs[k] = xv[q];
+    }
+    __syncthreads();
+    if (c + 1 < NV) {  // the next component's gathers, in flight through the rest of this one
+      const double *xn = x + (c + 1) * st.x;
+#pragma unroll
+      for (int q = 0; q < NU; q++) xv[q] = xn[uc[q]];
+    }
+    if (c == 0 && (VAL8 || VAL4)) {
+#pragma unroll
+      for (int it = 0; it < NIT; it++) {
+        if (VAL8) {
+          vv[it].x = slut[vw[it] & 0xffu];
+          vv[it].y = slut[vw[it] >> 8];
+        } else {
+          vv[it].x = (double)vf[it].x;
+          vv[it].y = (double)vf[it].y;
+        }
+      }
+    }
+    d2_t pv[NIT];
+#pragma unroll
+    for (int it = 0; it < NIT; it++) {
+      const int k = 2 * tid + it * 2 * BLOCK;
+      pv[it] = d2_t{0.0, 0.0};
+      if (k < cnt) {
+        const bool ok0 = (k >= base);
+        const bool ok1 = (k + 1 < end);
+        pv[it].x = ok0 ? vv[it].x * xs[cw[it] & XC_ID_MASK] : 0.0;
+        pv[it].y = ok1 ? vv[it].y * xs[(cw[it] >> 16) & XC_ID_MASK] : 0.0;
+      }
+    }
+    __syncthreads();  // every x-cache read is done: the array becomes the product buffer
+#pragma unroll
+    for (int it = 0; it < NIT; it++) {
+      const int k = 2 * tid + it * 2 * BLOCK;
+      if (k < cnt) {
+        prod[k] = pv[it].x;
+        prod[k + 1] = pv[it].y;
+      }
+    }
+    __syncthreads();
+    if (rr < nr) {
+      double s = 0.0;
+      for (int k = s0 + lane; k < s1; k += G) s += prod[k];
+      for (int off = G >> 1; off > 0; off >>= 1) s += __shfl_down(s, off, G);
+      if (lane == 0)
+        __builtin_nontemporal_store((e.beta == 0.0) ? e.alpha * s : e.alpha * s + e.beta * bpre, yc + ro);
+    }
+    if (nr > BLOCK) {  // tiles with more rows than threads (G == 1 there): the remaining rows, one lane each
+      EpiArgs ec = e;
+      ec.b = bc;
+      ec.b_lo = bloc;
+      for (int r2 = tid + BLOCK; r2 < nr; r2 += BLOCK) {
+        const int a0 = (int)((unsigned)ia[r0 + r2] - ia_off), a1 = (int)((unsigned)ia[r0 + r2 + 1] - ia_off);
+        double s = 0.0;
+        for (int k = a0; k < a1; k++) s += prod[k];
+        epilogue<0>(r0 + r2, s, x, yc, ec);
+      }
+    }
+    if (c + 1 < NV) __syncthreads();  // the row sums are done: the array becomes the next component's x cache
+  }
+}
+
 __global__ __launch_bounds__(256) void tile_desc_k(int nb, const int *__restrict__ rb, const long long *__restrict__ ia,
                                                    const int *__restrict__ uptr, int *__restrict__ desc) {
   const int b = blockIdx.x * 256 + threadIdx.x;
@@ -1197,6 +1396,242 @@ __global__ __launch_bounds__(BLOCK, 2048 / BLOCK) void gs_tile_k(int blk0, int n
 }
 
 // ---------------------------------------------------------------------------
+// gs_tile_k for the NV components of a multivector in one pass over the operator (no C-row hand-over: `wout` stays
+// with the single-vector kernel).  As in spmv_stream_xc_mv, what does not depend on the vector is requested once per
+// tile -- descriptor, column list, column words, values (held as doubles), the rows' marks, divisors and entry ranges,
+// and the `code` words in LDS -- and the gather -> x cache -> products -> out-of-chunk sums -> 8x8 sweep -> store part
+// of gs_tile_k runs once per component, on that kernel's operands in that kernel's order, through the same
+// gs_tile_sweep and the same three uniform branches.  The value dictionary shares its LDS bytes with `code`, so it is
+// looked up once, before the first component's code words are written.
+// Holding the values through the component loop costs registers this kernel cannot have at gs_tile_k's 8 waves per
+// SIMD; it is built without that bound (profiles/mv_batch_resources.txt has the figures: no scratch).
+// ---------------------------------------------------------------------------
+template <int NV, bool VAL8, int BLOCK, bool VAL4 = false>
+__global__ __launch_bounds__(BLOCK) void gs_tile_mv_k(int blk0, int nblk, const int *__restrict__ tdesc,
+                                                      const int *__restrict__ ia, const double *__restrict__ av,
+                                                      const int *__restrict__ ucols,
+                                                      const unsigned short *__restrict__ lcol,
+                                                      const signed char *__restrict__ cf, int points,
+                                                      const double *__restrict__ dd, const double *__restrict__ f_all,
+                                                      const double *__restrict__ offc_all,
+                                                      const double *__restrict__ u_lo_all,
+                                                      const double *__restrict__ u_hi_all, int split,
+                                                      double *__restrict__ u_new_all, int fwd, int bwd, double w,
+                                                      int row_begin, int row_end, int zero_from,
+                                                      double *__restrict__ tout_all, int t_from, GsMultiStrides st,
+                                                      const unsigned char *__restrict__ vidx,
+                                                      const double *__restrict__ vlut) {
+#define UOLD(j) (((j) < split ? u_lo : u_hi)[(j)])
+  static_assert(NV >= 2 && NV <= 4, "2, 3 or 4 components per pass");
+  constexpr int TILE = 8 * BLOCK;
+  __shared__ double buf[TILE];
+  __shared__ __attribute__((aligned(8))) unsigned char code_bytes[TILE * sizeof(unsigned short)];
+  static_assert(TILE * sizeof(unsigned short) >= 256 * sizeof(double), "the value table must fit the code array");
+  unsigned short *code = reinterpret_cast<unsigned short *>(code_bytes);
+  double *slut = reinterpret_cast<double *>(code_bytes);
+  if ((int)blockIdx.x >= nblk) return;
+  const int blk = blk0 + blockIdx.x;
+  const int tid = threadIdx.x;
+  double lutv = 0.0;
+  if (VAL8 && tid < 256) lutv = vlut[tid];
+  const int4 d0 = reinterpret_cast<const int4 *>(tdesc)[2 * blk];
+  const int4 d1 = reinterpret_cast<const int4 *>(tdesc)[2 * blk + 1];
+  const int r0 = d0.x, r1 = d0.y, len = d0.w, u0 = d1.x, nu = d1.y;
+  const long long base64 = ((long long)d1.z << 32) | (long long)(unsigned)d0.z;
+  const bool all_zero = zero_from <= 0;
+  constexpr int NU = TILE / BLOCK;
+  int ucid[NU];
+#pragma unroll
+  for (int q = 0; q < NU; q++) {
+    const int k = tid + q * BLOCK;
+    ucid[q] = 0;
+    if (!all_zero && k < nu) ucid[q] = LIST_LOAD(ucols + u0 + k);
+  }
+  const long long base_al64 = base64 & ~1LL;
+  const int base = (int)(base64 - base_al64);  // tile-local from here on
+  const int end = base + len;
+  const int cnt = end;
+  const unsigned ia_off = (unsigned)base_al64;
+  const float *av4 = reinterpret_cast<const float *>(av) + base_al64;
+  av += base_al64;
+  lcol += base_al64;
+  if (VAL8) vidx += base_al64;
+  constexpr int NIT = TILE / (2 * BLOCK);
+  d2_t vv[NIT];  // the values: as loaded (fp64), or from the first barrier on (dictionary, fp32)
+  f2_t vf[NIT];
+  unsigned cw[NIT], vw[NIT];
+#pragma unroll
+  for (int it = 0; it < NIT; it++) {
+    const int k = 2 * tid + it * 2 * BLOCK;
+    cw[it] = 0;
+    vw[it] = 0;
+    vv[it] = d2_t{0.0, 0.0};
+    if (k < cnt) {
+      if (VAL8)
+        vw[it] = STREAM_LOAD(reinterpret_cast<const unsigned short *>(vidx + k));
+      else if (VAL4)
+        vf[it] = STREAM_LOAD(reinterpret_cast<const f2_t *>(av4 + k));
+      else
+        vv[it] = STREAM_LOAD(reinterpret_cast<const d2_t *>(av + k));
+      cw[it] = STREAM_LOAD(reinterpret_cast<const unsigned *>(lcol + k));
+    }
+  }
+  // the two-batch gather of the fp64 form, as in gs_tile_k
+  constexpr int GB = (VAL8 || VAL4) ? NU : NU / 2;
+  // per row, once for all components: is it swept, its divisor and its entry range
+  const int nr = r1 - r0;
+  const int LPR = nr <= BLOCK / 8 ? 8 : nr <= BLOCK / 4 ? 4 : nr <= BLOCK / 2 ? 2 : 1;
+  const int rl = tid / LPR, sub = tid % LPR;
+  const int i = r0 + rl;
+  double wd = 0.0;
+  bool rowsel = false;
+  int s0 = 0, s1 = 0;
+  if (rl < nr) {
+    const int mark = (points != 0 && cf != nullptr) ? (int)cf[i] : points;
+    rowsel = (mark == points) && i >= row_begin && i < row_end;
+    if (rowsel) {
+      const double myd = dd[i];
+      if (myd != 0.0) wd = w / myd;
+      s0 = (int)((unsigned)ia[i] - ia_off);
+      s1 = (int)((unsigned)ia[i + 1] - ia_off);
+    }
+  }
+  const int lane = tid & 63;
+  const int g = (lane / LPR) & 7;
+  const int gbase = lane & ~(8 * LPR - 1);
+  const bool zero_tile = (MI_GS_SWEEP_PATHS & 1) && r0 >= zero_from;
+  if (VAL8 && tid < 256) slut[tid] = lutv;
+#pragma unroll 1
+  for (int c = 0; c < NV; c++) {
+    const double *u_lo = u_lo_all + c * st.u_lo;
+    const double *u_hi = u_hi_all + c * st.u_hi;
+    const double *f = f_all + c * st.f;
+    const double *offc = offc_all ? offc_all + c * st.offc : nullptr;
+    double *u_new = u_new_all + c * st.out;
+    double *tout = tout_all ? tout_all + c * st.tout : nullptr;
+    double xv[GB];
+    if (!all_zero) {
+#pragma unroll
+      for (int q = 0; q < GB; q++) {
+        const int j = (ucid[q] >= zero_from) ? 0 : ucid[q];
+        xv[q] = UOLD(j);
+      }
+    }
+    double myu = 0.0, myrhs = 0.0;
+    if (rl < nr) {
+      myu = (i >= zero_from) ? 0.0 : UOLD(i);
+      if (rowsel) {
+        myrhs = f[i];
+        if (offc) myrhs -= offc[i];
+      }
+    }
+    if (!all_zero) {
+#pragma unroll
+      for (int q = 0; q < GB; q++) {
+        const int k = tid + q * BLOCK;
+        if (k < nu) buf[k] = (ucid[q] >= zero_from) ? 0.0 : xv[q];
+      }
+      if (GB < NU && nu > GB * BLOCK) {  // (uniform) more unique columns than the first batch holds
+#pragma unroll
+        for (int q = GB; q < NU; q++) {
+          const int j = (ucid[q] >= zero_from) ? 0 : ucid[q];
+          xv[q - GB] = UOLD(j);
+        }
+#pragma unroll
+        for (int q = GB; q < NU; q++) {
+          const int k = tid + q * BLOCK;
+          if (k < nu) buf[k] = (ucid[q] >= zero_from) ? 0.0 : xv[q - GB];
+        }
+      }
+    }
+    __syncthreads();
+    if (c == 0 && (VAL8 || VAL4)) {
+#pragma unroll
+      for (int it = 0; it < NIT; it++) {
+        if (VAL8) {
+          vv[it].x = slut[vw[it] & 0xffu];
+          vv[it].y = slut[vw[it] >> 8];
+        } else {
+          vv[it].x = (double)vf[it].x;
+          vv[it].y = (double)vf[it].y;
+        }
+      }
+    }
+    d2_t pv[NIT];
+#pragma unroll
+    for (int it = 0; it < NIT; it++) {
+      const int k = 2 * tid + it * 2 * BLOCK;
+      pv[it] = d2_t{0.0, 0.0};
+      if (k < cnt) {
+        const bool ok0 = (k >= base);
+        const bool ok1 = (k + 1 < end);
+        const unsigned c0 = cw[it] & 0xffffu, c1 = cw[it] >> 16;
+        // out-of-chunk: product with the snapshot value; in-chunk: the coefficient itself
+        const double x0 = all_zero ? 0.0 : buf[c0 & XC_ID_MASK], x1 = all_zero ? 0.0 : buf[c1 & XC_ID_MASK];
+        pv[it].x = ok0 ? ((c0 & XC_INCH) ? vv[it].x : vv[it].x * x0) : 0.0;
+        pv[it].y = ok1 ? ((c1 & XC_INCH) ? vv[it].y : vv[it].y * x1) : 0.0;
+      }
+    }
+    __syncthreads();  // every x-cache read (and, c == 0, every dictionary lookup) is done
+#pragma unroll
+    for (int it = 0; it < NIT; it++) {
+      const int k = 2 * tid + it * 2 * BLOCK;
+      if (k < cnt) {
+        buf[k] = pv[it].x;
+        buf[k + 1] = pv[it].y;
+        if (c == 0) {
+          code[k] = (unsigned short)(cw[it] & 0xffffu);
+          code[k + 1] = (unsigned short)(cw[it] >> 16);
+        }
+      }
+    }
+    __syncthreads();
+    double S = 0.0;
+    unsigned inmask = 0;
+    int kin = TILE;
+    if (rowsel) {
+      for (int k = s0 + sub; k < s1; k += LPR) {
+        const unsigned cc = code[k];
+        const double v = buf[k];
+        const bool in = (cc & XC_INCH) != 0;
+        S += in ? 0.0 : v;
+        inmask |= in ? (1u << ((cc >> XC_OFF_SHIFT) & 7)) : 0u;
+        kin = in ? min(kin, k) : kin;
+      }
+    }
+    for (int m = 1; m < LPR; m <<= 1) {
+      S += __shfl_xor(S, m, 64);
+      inmask |= (unsigned)__shfl_xor((int)inmask, m, 64);
+      kin = min(kin, __shfl_xor(kin, m, 64));
+    }
+    if (tout && rowsel && sub == 0 && i >= t_from) tout[i] = f[i] - S;
+    const bool wave_idle = (MI_GS_SWEEP_PATHS & 4) && __ballot(rowsel) == 0;
+    const bool wave_diag = (MI_GS_SWEEP_PATHS & 2) && __ballot((inmask & ~(1u << g)) != 0u) == 0;
+    if (wave_idle) {
+      // nothing to sweep: myu is the row's value
+    } else if (wave_diag) {
+      const bool has = (inmask >> g) & 1u;
+      const double cd = has ? buf[has ? kin : 0] : 0.0;
+      if (fwd) myu = myu + (myrhs - (S + cd * myu)) * wd;  // unselected rows: wd == 0
+      if (bwd) myu = myu + (myrhs - (S + cd * myu)) * wd;
+    } else {
+      double crow[8];
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        const bool has = (inmask >> j) & 1u;
+        const int pos = kin + __popc(inmask & ((1u << j) - 1u));
+        crow[j] = has ? buf[has ? pos : 0] : 0.0;
+      }
+      double uc[8];
+      gs_tile_sweep(crow, uc, myu, S, myrhs, wd, g, gbase, LPR, fwd, bwd, zero_tile);
+    }
+    if (rl < nr && sub == 0) u_new[i] = myu;
+    if (c + 1 < NV) __syncthreads();  // the sums and coefficients are read: the array becomes the next x cache
+  }
+#undef UOLD
+}
+
+// ---------------------------------------------------------------------------
 // BLAS-1
 // ---------------------------------------------------------------------------
 // Second stage of the two-stage reductions inside the first-stage kernel: every block leaves its partial sum, takes a
@@ -1866,6 +2301,8 @@ struct KernelEntry {
 #define MI_KERNEL(...) {&__VA_ARGS__, #__VA_ARGS__}
 using XcKernel = decltype(&spmv_stream_xc<0, 0, false, SPMV_BLOCK>);
 using GsTileKernel = decltype(&gs_tile_k<false, SPMV_BLOCK>);
+using XcMvKernel = decltype(&spmv_stream_xc_mv<2, 0, false, SPMV_BLOCK>);  // NV = 2, 3, 4 share the signature
+using GsTileMvKernel = decltype(&gs_tile_mv_k<2, false, SPMV_BLOCK>);
 template <class VT>
 using StreamKernel = decltype(&spmv_stream<0, 0, VT>);
 template <class VT>
@@ -1877,8 +2314,8 @@ static_assert(SPMV_BLOCK == 256 && SPMV_BLOCK_WIDE == 512, "the tables below spe
 static int tile_block(int tile_entries) { return tile_entries == SPMV_TILE_WIDE ? SPMV_BLOCK_WIDE : SPMV_BLOCK; }
 
 template <class Fn>
-static KernelChoice chosen(const KernelEntry<Fn> &e, KernelFamily family, int block, int lpc = 0) {
-  return KernelChoice{(const void *)e.kernel, e.name, family, block, lpc};
+static KernelChoice chosen(const KernelEntry<Fn> &e, KernelFamily family, int block, int lpc = 0, bool batched = false) {
+  return KernelChoice{(const void *)e.kernel, e.name, family, block, lpc, batched};
 }
 
 // EPI: 0 mat-vec, 1 masked Jacobi, 2 Chebyshev step.  TAG 1 names the mat-vec of the level-0 class; the wide tiles have no such instantiation.
@@ -1915,8 +2352,23 @@ KernelChoice choose_stream_kernel(const SolveKernelDesc &d) {
                                                       MI_KERNEL(spmv_stream_xc<3, 0, false, 256>)};
   static const KernelEntry<StreamKernel<float>> plain32_inplace = MI_KERNEL(spmv_stream<3, 0, float>);
   static const KernelEntry<StreamKernel<double>> plain_inplace = MI_KERNEL(spmv_stream<3, 0>);
+  // the batched mat-vec of a multivector (x cache, EPI 0): [NV - 2][ValueFormat][wide / TAG 1 / TAG 0]; tables named
+  // after the others, as above
+#define MI_MV_XC(NV)                                                                                                   \
+  {{MI_KERNEL(spmv_stream_xc_mv<NV, 0, false, 512, true>), MI_KERNEL(spmv_stream_xc_mv<NV, 1, false, 256, true>),     \
+    MI_KERNEL(spmv_stream_xc_mv<NV, 0, false, 256, true>)},                                                            \
+   {MI_KERNEL(spmv_stream_xc_mv<NV, 0, true, 512>), MI_KERNEL(spmv_stream_xc_mv<NV, 1, true, 256>),                   \
+    MI_KERNEL(spmv_stream_xc_mv<NV, 0, true, 256>)},                                                                   \
+   {MI_KERNEL(spmv_stream_xc_mv<NV, 0, false, 512>), MI_KERNEL(spmv_stream_xc_mv<NV, 1, false, 256>),                 \
+    MI_KERNEL(spmv_stream_xc_mv<NV, 0, false, 256>)}}
+  static const KernelEntry<XcMvKernel> xc_mv[MV_MAX_BATCH - 1][3][3] = {MI_MV_XC(2), MI_MV_XC(3), MI_MV_XC(4)};
+#undef MI_MV_XC
   MI_REQUIRE(d.epi >= 0 && d.epi <= 3, "choose_stream_kernel: the epilogue is 0, 1, 2 or 3");
+  MI_REQUIRE(d.nvec >= 1 && d.nvec <= MV_MAX_BATCH, "choose_stream_kernel: 1 to 4 components per pass");
   const int fmt = (int)d.format;
+  if (d.nvec > 1 && d.xcache && d.epi == 0)
+    return chosen(xc_mv[d.nvec - 2][fmt][d.tile_entries == SPMV_TILE_WIDE ? 0 : d.level0 ? 1 : 2], KernelFamily::STREAM_XC,
+                  tile_block(d.tile_entries), 0, true);
   if (d.epi == 3) {
     if (d.xcache)
       return chosen(d.tile_entries == SPMV_TILE_WIDE ? xc_wide_inplace[fmt] : xc_inplace[fmt], KernelFamily::STREAM_XC,
@@ -2079,6 +2531,61 @@ void spmv(const DevCSR &A, const double *x, double alpha, double beta, const dou
   prof_begin(prof, s);
   prof_name(prof, launch_stream(0, A, x, y, e, s, prof == PROF_SPMV_L0));
   prof_end(prof, s);
+}
+
+static int g_mv_batch = 0;
+int multivector_batch() {
+  if (g_mv_batch == 0) {
+    const int v = getenv("MI_HYPRE_MV_BATCH") ? atoi(getenv("MI_HYPRE_MV_BATCH")) : MV_BATCH_DEFAULT;
+    g_mv_batch = (v >= 1 && v <= MV_MAX_BATCH) ? v : MV_BATCH_DEFAULT;
+  }
+  return g_mv_batch;
+}
+void set_multivector_batch(int width) {
+  MI_REQUIRE(width >= 1 && width <= MV_MAX_BATCH, "multivector batch: the width is 1, 2, 3 or 4");
+  g_mv_batch = width;
+}
+
+int spmv_multi(const DevCSR &A, int nvec, const double *x, long long x_stride, double alpha, double beta, const double *b,
+               long long b_stride, double *y, long long y_stride, hipStream_t s, int prof, const double *b_lo,
+               long long b_lo_stride, int b_split) {
+  const int width = multivector_batch();
+  // the batched form exists for the x-cache tile format alone (choose_stream_kernel); one component needs none
+  const bool batch = nvec > 1 && width > 1 && A.nrows > 0 && A.xcache;
+  int passes = 0;
+  for (int c0 = 0; c0 < nvec;) {
+    const int nv = batch ? std::min(width, nvec - c0) : 1;
+    const double *xc = x + c0 * x_stride, *bc = b ? b + c0 * b_stride : nullptr;
+    const double *bloc = b_lo ? b_lo + c0 * b_lo_stride : nullptr;
+    double *yc = y + c0 * y_stride;
+    if (nv == 1) {
+      spmv(A, xc, alpha, beta, bc, yc, s, prof, bloc, b_split);
+    } else {
+      MI_REQUIRE(A.value_format() == ValueFormat::FP32 || A.a.p || A.nnz == 0, "SpMV: the operator holds no value array");
+      SolveKernelDesc d{A.xcache, A.tile_entries, A.value_format(), 0, prof == PROF_SPMV_L0};
+      d.nvec = nv;
+      const KernelChoice c = choose_stream_kernel(d);
+      MI_REQUIRE(c.batched, "SpMV: no batched instantiation for an operator in the x-cache tile format");
+      EpiArgs e{};
+      e.alpha = alpha;
+      e.beta = beta;
+      e.b = bc;
+      e.b_lo = bloc;
+      e.b_split = b_split;
+      e.rowmap = A.rowmap.p;
+      const MvStrides st{x_stride, y_stride, b_stride, b_lo_stride};
+      const int nb = A.nblocks, xchunk = (nb + 7) / 8;
+      prof_begin(prof, s);
+      hipLaunchKernelGGL((XcMvKernel)c.kernel, dim3(xchunk * 8), dim3(c.block), 0, s, nb, xchunk, A.tdesc.p, A.ia.p, A.ja.p,
+                         tile_values(A), A.ucols.p, A.lcol.p, xc, yc, e, st, A.vidx.p, A.vlut.p);
+      MI_HIP(hipGetLastError());
+      prof_name(prof, c.name);
+      prof_end(prof, s);
+    }
+    if (batch) passes++;
+    c0 += nv;
+  }
+  return passes;
 }
 
 void spmv_listed_tiles(const DevCSR &A, const int *tdesc, int nb, const double *x, double *y, hipStream_t s, int prof) {
@@ -2278,6 +2785,18 @@ void spmv_offd_set(const DevOffd &B, const double *xext, double *out, hipStream_
 //   longer rows: the dense-chunk kernel wins 10-18 %; for means up to 32 two chunks per wave (32 lanes
 //   each, rows beyond 32 entries finished in the pre-sweep loop) beat one chunk per wave.
 KernelChoice choose_gs_kernel(const SolveKernelDesc &d) {
+  MI_REQUIRE(d.nvec >= 1 && d.nvec <= MV_MAX_BATCH, "choose_gs_kernel: 1 to 4 components per pass");
+  if (d.nvec > 1 && d.chunk == 8 && d.tiles && d.xcache) {
+    // the batched tile kernel of a multivector: [NV - 2][ValueFormat][2048-entry tiles]
+#define MI_MV_GS(NV)                                                                            \
+  {{MI_KERNEL(gs_tile_mv_k<NV, false, 512, true>), MI_KERNEL(gs_tile_mv_k<NV, false, 256, true>)}, \
+   {MI_KERNEL(gs_tile_mv_k<NV, true, 512>), MI_KERNEL(gs_tile_mv_k<NV, true, 256>)},             \
+   {MI_KERNEL(gs_tile_mv_k<NV, false, 512>), MI_KERNEL(gs_tile_mv_k<NV, false, 256>)}}
+    static const KernelEntry<GsTileMvKernel> tile_mv[MV_MAX_BATCH - 1][3][2] = {MI_MV_GS(2), MI_MV_GS(3), MI_MV_GS(4)};
+#undef MI_MV_GS
+    return chosen(tile_mv[d.nvec - 2][(int)d.format][d.tile_entries != SPMV_TILE_WIDE], KernelFamily::GS_TILE,
+                  tile_block(d.tile_entries), 0, true);
+  }
   if (d.chunk == 8 && d.tiles && d.xcache) {
     // [ValueFormat][2048-entry tiles]
     static const KernelEntry<GsTileKernel> tile[3][2] = {
@@ -2323,9 +2842,9 @@ KernelChoice choose_gs_kernel(const SolveKernelDesc &d) {
 }
 #undef MI_KERNEL
 
-static KernelChoice gs_choice(const DevCSR &A, int chunk) {
+static KernelChoice gs_choice(const DevCSR &A, int chunk, int nvec = 1) {
   return choose_gs_kernel({A.xcache, A.tile_entries, A.value_format(), 0, false, chunk, A.gs_tiles && gs_tile_mode(A), A.nnz,
-                           A.nrows, A.rowlen_p95});
+                           A.nrows, A.rowlen_p95, nvec});
 }
 
 bool gs_uses_tiles(const DevCSR &A, int chunk) { return gs_choice(A, chunk).family == KernelFamily::GS_TILE; }
@@ -2429,6 +2948,43 @@ void gs_hybrid(const DevCSR &A, const double *u_lo, const double *u_hi, int spli
   }
   MI_HIP(hipGetLastError());
   prof_end(prof, s);
+}
+
+int gs_hybrid_multi(const DevCSR &A, int nvec, const GsMultiStrides &st, const double *u_lo, const double *u_hi, int split,
+                    double *out, const double *f, const double *offc, const double *d, const signed char *cf, int points,
+                    int chunk, bool fwd, bool bwd, double w, int row_begin, int row_end, hipStream_t s, int prof,
+                    int zero_from, double *tout, int t_from) {
+  if (A.nrows == 0 || row_end <= row_begin) return 0;
+  const int width = multivector_batch();
+  const bool batch = nvec > 1 && width > 1 && gs_uses_tiles(A, chunk);
+  int passes = 0;
+  for (int c0 = 0; c0 < nvec;) {
+    const int nv = batch ? std::min(width, nvec - c0) : 1;
+    const double *ulo = u_lo + c0 * st.u_lo, *uhi = u_hi + c0 * st.u_hi, *fc = f + c0 * st.f;
+    const double *oc = offc ? offc + c0 * st.offc : nullptr;
+    double *outc = out + c0 * st.out, *tc = tout ? tout + c0 * st.tout : nullptr;
+    if (nv == 1) {
+      gs_hybrid(A, ulo, uhi, split, outc, fc, oc, d, cf, points, chunk, fwd, bwd, w, row_begin, row_end, s, prof,
+                zero_from, tc, t_from);
+    } else {
+      const KernelChoice c = gs_choice(A, chunk, nv);
+      MI_REQUIRE(c.batched && c.family == KernelFamily::GS_TILE, "hybrid GS: no batched instantiation for a tile operator");
+      int first_row, last_row, b0, b1;
+      gs_tile_range(A, row_begin, row_end, first_row, last_row, b0, b1);
+      prof_begin(prof, s);
+      if (b1 > b0) {
+        prof_name(prof, c.name);
+        hipLaunchKernelGGL((GsTileMvKernel)c.kernel, dim3((unsigned)(b1 - b0)), dim3(c.block), 0, s, b0, b1 - b0, A.tdesc.p,
+                           A.ia.p, tile_values(A), A.ucols.p, A.lcol.p, cf, points, d, fc, oc, ulo, uhi, split, outc,
+                           fwd ? 1 : 0, bwd ? 1 : 0, w, first_row, last_row, zero_from, tc, t_from, st, A.vidx.p, A.vlut.p);
+      }
+      MI_HIP(hipGetLastError());
+      prof_end(prof, s);
+    }
+    if (batch) passes++;
+    c0 += nv;
+  }
+  return passes;
 }
 
 // workgroups of the inner-product kernels (MI_HYPRE_DOT_BLOCKS, at most RED_MAX_BLOCKS * MASS_NV partial slots)

@@ -166,6 +166,9 @@ struct SolveKernelDesc {
   int64_t nnz = 0;
   int nrows = 0;
   int rowlen_p95 = 0;
+  // components of a multivector the launch serves (spmv_multi / gs_hybrid_multi): 2 .. 4 select the batched
+  // instantiation where the family has one
+  int nvec = 1;
 };
 enum class KernelFamily { STREAM, STREAM_XC, GS_TILE, GS_GROUP, GS_DENSE, GS_HYBRID };
 struct KernelChoice {
@@ -174,6 +177,9 @@ struct KernelChoice {
   KernelFamily family;
   int block;  // threads per workgroup
   int lpc;    // GS_GROUP / GS_DENSE: lanes per chunk
+  // nvec > 1: whether `kernel` is the batched instantiation for nvec components (other signature: MvStrides /
+  // GsMvStrides after the scalars); false: the single-vector kernel, which the launcher runs once per component
+  bool batched = false;
 };
 KernelChoice choose_stream_kernel(const SolveKernelDesc &d);
 KernelChoice choose_gs_kernel(const SolveKernelDesc &d);
@@ -182,6 +188,27 @@ KernelChoice choose_gs_kernel(const SolveKernelDesc &d);
 // b_lo (optional): rows < b_split take their b entry from b_lo instead of b
 void spmv(const DevCSR &A, const double *x, double alpha, double beta, const double *b, double *y, hipStream_t s,
           int prof = PROF_NONE, const double *b_lo = nullptr, int b_split = 0);
+// ---- multivectors: the same operations on the nvec components of component-major vectors, each
+// vector with its own stride between components (in doubles).  At most multivector_batch() (and never more than
+// MV_MAX_BATCH) components share one pass over the operator, in order (5 = 4 + 1); where the chosen family has no batched
+// instantiation, or the width is 1, the single-vector kernel runs once per component.  Either way every component
+// gets the bits of the single-vector call on it.
+constexpr int GS_NO_ZEROS = 0x7fffffff;  // gs_hybrid's zero_from: no column is known to hold zero
+constexpr int MV_MAX_BATCH = 4;
+constexpr int MV_BATCH_DEFAULT = 1;  // opt-in: see README (round notes) for why
+int multivector_batch();             // MI_HYPRE_MV_BATCH / HYPRE_MI_SetMultivectorBatch: 1 .. MV_MAX_BATCH
+void set_multivector_batch(int width);
+// returns the number of passes when the batched kernels ran (a trailing single component counts as a pass), else 0
+int spmv_multi(const DevCSR &A, int nvec, const double *x, long long x_stride, double alpha, double beta, const double *b,
+               long long b_stride, double *y, long long y_stride, hipStream_t s, int prof = PROF_NONE,
+               const double *b_lo = nullptr, long long b_lo_stride = 0, int b_split = 0);
+struct GsMultiStrides {
+  long long u_lo, u_hi, out, f, offc, tout;
+};
+int gs_hybrid_multi(const DevCSR &A, int nvec, const GsMultiStrides &st, const double *u_lo, const double *u_hi, int split,
+                    double *out, const double *f, const double *offc, const double *d, const signed char *cf, int points,
+                    int chunk, bool fwd, bool bwd, double w, int row_begin, int row_end, hipStream_t s,
+                    int prof = PROF_NONE, int zero_from = GS_NO_ZEROS, double *tout = nullptr, int t_from = 0);
 // y[rows[k]] += alpha * (B*xext)[k]
 void spmv_offd_add(const DevOffd &B, const double *xext, double alpha, double *y, hipStream_t s);
 // out[rows[k]] = (B*xext)[k]   (other entries of out untouched)
@@ -219,7 +246,6 @@ void gershgorin(const DevCSR &A, const DevOffd &B, const double *diag, double *w
 // pair reads the first pass's output without a copy); the swept chunks' rows are
 // written to out.  zero_from: the caller guarantees that every pre-sweep value with index >= zero_from is
 // zero (first sweep on a zero guess); kernels may then skip those gathers -- same result, less traffic.
-constexpr int GS_NO_ZEROS = 0x7fffffff;
 // whether gs_hybrid sweeps A tile by tile (A.rb_host boundaries) rather than chunk by chunk: a caller that
 // splits one pass into several launches must cut at the unit the kernel writes back
 bool gs_uses_tiles(const DevCSR &A, int chunk);

@@ -5,6 +5,7 @@
 // Modified Gram-Schmidt keeps its coefficients on the device: every <p_j,p_i>
 // lands in a device slot that the following axpy reads, so one Arnoldi step
 // costs a single host synchronisation (the Hessenberg column copy).
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -63,10 +64,10 @@ void KrylovSolver::matvec_all(ParCSR &A, double alpha, const double *x, double b
                               int ncomp, int prof) {
   Comm &comm = current_comm();
   hipStream_t s = ctx().stream;
-  for (int c = 0; c < ncomp; c++) {
-    const size_t o = (size_t)c * (size_t)nloc;
-    A.matvec(comm, alpha, x + o, beta, b ? b + o : nullptr, y + o, s, prof);
-  }
+  if (ncomp == 1)
+    A.matvec(comm, alpha, x, beta, b, y, s, prof);
+  else  // one pass over the operator for up to k::multivector_batch() components (one rank), the same bits
+    A.matvec_multi(comm, ncomp, alpha, x, nloc, beta, b, nloc, y, nloc, s, prof);
 }
 
 // The BoomerAMG preconditioner works in its own (C-first) ordering of level 0 and gathers / scatters its
@@ -132,13 +133,19 @@ const double *KrylovSolver::precond_in_order(BoomerAMG *amg, ParCSR &A, ParVecto
   hipStream_t s = ctx().stream;
   AmgLevel &L0 = amg->L[0];
   const int n = L0.n, nc = rhs.ncomp;
-  double *own_f = L0.f.p;
-  for (int c = 0; c < nc; c++) {  // one cycle per component of a multivector
-    const size_t o = (size_t)c * (size_t)n;
+  // a multivector: one cycle per `width` components where the cycle can work on a batch (BoomerAMG::mv_cycle_eligible),
+  // else one cycle per component
+  const int width = amg->mv_cycle_width(nc);
+  for (int c0 = 0; c0 < nc;) {
+    const int nv = std::min(width, nc - c0);
+    const size_t o = (size_t)c0 * (size_t)n;
+    BoomerAMG::MvScope batch(*amg, nv);  // nv > 1: L0.u holds nv components, n apart as the Krylov vectors' are
+    double *own_f = L0.f.p;
     L0.f.p = rhs.all() + o;  // read-only inside the cycle
-    if (!amg->zero_cycle_ignores_u(0)) k::fill(L0.u.p, n, 0.0, s);
-    ctx().n_precond_cycles++;
+    ctx().n_precond_cycles += nv;
     try {
+      if (!amg->zero_cycle_ignores_u(0))
+        for (int j = 0; j < nv; j++) k::fill(L0.u.p + (size_t)j * (size_t)n, n, 0.0, s);
       amg->cycle(0, true);
     } catch (...) {
       L0.f.p = own_f;
@@ -146,7 +153,8 @@ const double *KrylovSolver::precond_in_order(BoomerAMG *amg, ParCSR &A, ParVecto
     }
     L0.f.p = own_f;
     if (nc == 1 && !need_copy) return L0.u.p;
-    k::copy(L0.u.p, out.all() + o, n, s);
+    for (int j = 0; j < nv; j++) k::copy(L0.u.p + (size_t)j * (size_t)n, out.all() + o + (size_t)j * (size_t)n, n, s);
+    c0 += nv;
   }
   return out.all();
 }

@@ -363,6 +363,8 @@ struct Ctx {
   long long n_precond_cycles = 0, n_gmres_z_allocated = 0;
   // C-row hand-over: Krylov mat-vecs that ran on level 0's tile list, and the tiles they left out
   long long n_handover_matvecs = 0, n_handover_tiles_skipped = 0;
+  // multivectors: cycle passes / mat-vec passes that ran batched, multivector cycles that looped over the components
+  long long n_mv_batched_cycles = 0, n_mv_batched_matvecs = 0, n_mv_fallback_cycles = 0;
   int krylov_precond_depth = 0;
 };
 Ctx &ctx();

@@ -548,6 +548,20 @@ void ParCSR::matvec(Comm &comm, double alpha, const double *x, double beta, cons
   if (halo_on) k::spmv_offd_add(d_offd, halo.d_xext.p, alpha, y, s);
 }
 
+void ParCSR::matvec_multi(Comm &comm, int nvec, double alpha, const double *x, long long x_stride, double beta,
+                          const double *b, long long b_stride, double *y, long long y_stride, hipStream_t s, int prof,
+                          const DevCSR *diag_op, const double *b_lo, long long b_lo_stride, int b_split) {
+  MI_REQUIRE(on_device, "matrix not assembled");
+  if (comm.size == 1 && d_offd.nrows_c == 0) {
+    ctx().n_mv_batched_matvecs += k::spmv_multi(diag_op ? *diag_op : d_diag, nvec, x, x_stride, alpha, beta, b, b_stride, y,
+                                                y_stride, s, prof, b_lo, b_lo_stride, b_split);
+    return;
+  }
+  for (int c = 0; c < nvec; c++)
+    matvec(comm, alpha, x + c * x_stride, beta, b ? b + c * b_stride : nullptr, y + c * y_stride, s, prof, diag_op,
+           b_lo ? b_lo + c * b_lo_stride : nullptr, b_split);
+}
+
 void ParCSR::matvec_listed_tiles(const int *tdesc, int nb, const double *x, double *y, hipStream_t s, int prof) {
   MI_REQUIRE(on_device, "matrix not assembled");
   MI_REQUIRE(d_offd.nrows_c == 0, "mat-vec on a tile list: the matrix has a halo block");

@@ -92,6 +92,14 @@ struct ParCSR {
   // b_lo / b_split (optional): rows < b_split read their b entry from b_lo (composite right-hand side)
   void matvec(Comm &comm, double alpha, const double *x, double beta, const double *b, double *y, hipStream_t s,
               int prof = -1, const DevCSR *diag_op = nullptr, const double *b_lo = nullptr, int b_split = 0);
+  // the same for the nvec components of component-major multivectors, each vector with its own stride between
+  // components (doubles): on one rank one pass over the operator serves up to k::multivector_batch() components
+  // (k::spmv_multi; counted as "mv_batched_matvecs"), on N > 1 ranks the components take matvec() one by one.  Every
+  // component gets the bits matvec() gives it
+  void matvec_multi(Comm &comm, int nvec, double alpha, const double *x, long long x_stride, double beta, const double *b,
+                    long long b_stride, double *y, long long y_stride, hipStream_t s, int prof = -1,
+                    const DevCSR *diag_op = nullptr, const double *b_lo = nullptr, long long b_lo_stride = 0,
+                    int b_split = 0);
   // y = A x on the listed tiles of the diag block alone (k::spmv_listed_tiles; one rank): the rows of the other tiles
   // keep what y holds
   void matvec_listed_tiles(const int *tdesc, int nb, const double *x, double *y, hipStream_t s, int prof = -1);

@@ -272,6 +272,17 @@ void HypreSystem::setup_precon_and_solver() {
   if (iproc_ == 0)
     printf("%s : Using %s solver with %s preconditioner\n", __FUNCTION__, method.c_str(), preconditioner.c_str());
 
+  /* this library's key: mi_multivector_batch = components of a multivector (num_components > 1, segregated_solve: 0) that
+   * share one pass over an operator: 1 component by component, 2 .. 4 at most that many; absent = the library's setting */
+  if (solver["mi_multivector_batch"]) {
+#ifdef MI_HOST_WITH_LIBHYPRE
+    throw std::runtime_error("Hypre Config:: mi_multivector_batch is a key of libmi_hypre; libHYPRE has no such setting");
+#else
+    if (HYPRE_MI_SetMultivectorBatch(solver["mi_multivector_batch"].as<int>()))
+      throw std::runtime_error(std::string("Hypre Config:: mi_multivector_batch: ") + HYPRE_MI_LastErrorMessage());
+#endif
+  }
+
   if (preconditioner == "boomeramg")
     setup_boomeramg_precond();
   else if (preconditioner == "ilu")

@@ -19,6 +19,7 @@ HYPRE_PARCSR = 5555
 HYPRE_MEMORY_DEVICE = 1
 HYPRE_EXEC_DEVICE = 1
 HYPRE_ERROR_GENERIC = 1
+HYPRE_ERROR_ARG = 4
 HYPRE_ERROR_CONV = 256
 
 c_big = C.c_longlong
@@ -523,6 +524,24 @@ class BoomerAMG:
         call("HYPRE_MI_BoomerAMGRelaxPairLevel", self.h, level, relax_type, first, 1 if zero else 0, f, u)
         return u
 
+    def relax_level_multi(self, level, relax_type, points, f, u):
+        """relax_level on nvec = 2 .. 4 vectors at once, as a batched cycle does: f and u of shape (nvec, n)."""
+        f = dbl(f)
+        u = np.array(u, dtype=np.float64)
+        assert f.ndim == 2 and f.shape == u.shape
+        call("HYPRE_MI_BoomerAMGRelaxLevelMulti", self.h, level, relax_type, points, f.shape[0], f, u)
+        return u
+
+    def relax_pair_level_multi(self, level, relax_type, first, f, u=None):
+        """relax_pair_level on nvec = 2 .. 4 vectors at once: f (and u) of shape (nvec, n); u None = zero guess."""
+        f = dbl(f)
+        assert f.ndim == 2
+        zero = u is None
+        u = np.zeros_like(f) if zero else np.array(u, dtype=np.float64)
+        assert u.shape == f.shape
+        call("HYPRE_MI_BoomerAMGRelaxPairLevelMulti", self.h, level, relax_type, first, 1 if zero else 0, f.shape[0], f, u)
+        return u
+
     def c_row_handover_census(self, level=0):
         """dict(tiles, listed, handed, flagged_c_rows, w_upto): the tiles of the level's operator, those the mat-vec
         after a C-row hand-over still runs, the handed-over ones, the C rows with an off-diagonal C column, and the row
@@ -945,6 +964,23 @@ def set_value_dictionary(on):
     call("HYPRE_MI_SetValueDictionary", 1 if on else 0)
 
 
+def set_multivector_batch(width):
+    """components of a multivector that share one pass over an operator (mat-vecs, BoomerAMG cycles; one rank): 1 =
+    component by component, 2 .. 4 = at most that many; process-wide.  The results are the same bits for every width."""
+    call("HYPRE_MI_SetMultivectorBatch", int(width))
+
+
+def multivector_batch():
+    v = c_int()
+    call("HYPRE_MI_GetMultivectorBatch", C.byref(v))
+    return v.value
+
+
+def parcsr_matvec_multi(alpha, A, x, beta, y):
+    """y_c = alpha A x_c + beta y_c for every component of the multivectors x and y (IJVector with ncomp > 1)"""
+    call("HYPRE_MI_ParCSRMatrixMatvecMulti", float(alpha), A.par if hasattr(A, "par") else A, x.par, float(beta), y.par)
+
+
 def set_gmres_keep_directions(on):
     """GMRES / COGMRES behind BoomerAMG update x from the kept directions z_j (on, the default) or apply the
     preconditioner once more, as gmres.c does (off); process-wide, for the solves started afterwards"""
@@ -1027,6 +1063,17 @@ def solve_kernel_choice(family, xcache=False, tile_entries=2048, fp32=False, dic
     call("HYPRE_MI_SolveKernelChoice", family, int(xcache), tile_entries, int(fp32), int(dictionary), epilogue, int(level0),
          chunk, int(tiles), c_big(nnz), nrows, rowlen_p95, buf, 128)
     return buf.value.decode()
+
+
+def solve_kernel_choice_multi(nvec, family, xcache=False, tile_entries=2048, fp32=False, dictionary=False, epilogue=0,
+                              level0=False, chunk=8, tiles=False, nnz=0, nrows=1, rowlen_p95=0):
+    """(name, batched): solve_kernel_choice for a pass that serves nvec components of a multivector; batched False = the
+    single-vector instantiation, run once per component"""
+    buf = C.create_string_buffer(128)
+    batched = c_int(-1)
+    call("HYPRE_MI_SolveKernelChoiceMulti", nvec, family, int(xcache), tile_entries, int(fp32), int(dictionary), epilogue,
+         int(level0), chunk, int(tiles), c_big(nnz), nrows, rowlen_p95, buf, 128, C.byref(batched))
+    return buf.value.decode(), bool(batched.value)
 
 
 def cheby_kernel_choice(xcache=False, tile_entries=2048, fp32=False, dictionary=False):

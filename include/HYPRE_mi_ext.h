@@ -136,6 +136,18 @@ HYPRE_Int HYPRE_MI_ArenaSelfTest(HYPRE_Int seed, HYPRE_Int rounds, HYPRE_BigInt 
  * general (variable-coefficient) operator gets anyway; applies to hierarchies set up afterwards (env
  * MI_HYPRE_VALUE_DICT).  bench.py uses it to report the general-operator roofline beside the headline. */
 HYPRE_Int HYPRE_MI_SetValueDictionary(HYPRE_Int on);
+/* Multivectors (HYPRE_IJVectorSetNumComponents > 1): how many components share one pass over an
+ * operator in the mat-vecs and BoomerAMG cycles of a solve on one rank.  1 (the default; environment MI_HYPRE_MV_BATCH):
+ * component by component; 2, 3, 4: at most that many per pass, more components in groups, in order.  Any other width
+ * is refused (HYPRE_ERROR_ARG).  The results are the same bits for every width.  Counters (HYPRE_MI_GetCounter):
+ * "mv_batched_cycles" / "mv_batched_matvecs" passes that ran batched, "mv_fallback_cycles" multivector cycles that
+ * looped over the components (width 1, more than one rank, a smoother outside the hybrid Gauss-Seidel family). */
+HYPRE_Int HYPRE_MI_SetMultivectorBatch(HYPRE_Int width);
+HYPRE_Int HYPRE_MI_GetMultivectorBatch(HYPRE_Int *width);
+/* y_c = alpha A x_c + beta y_c for every component c of two multivectors with the same number of components (batched
+ * as set above; HYPRE_ParCSRMatrixMatvec acts on the current component alone).  x and y must be different vectors */
+HYPRE_Int HYPRE_MI_ParCSRMatrixMatvecMulti(HYPRE_Complex alpha, HYPRE_ParCSRMatrix A, HYPRE_ParVector x, HYPRE_Complex beta,
+                                           HYPRE_ParVector y);
 /* GMRES and COGMRES preconditioned by this library's BoomerAMG (one cycle, zero tolerance, the matrix of its Setup) keep
  * the preconditioned directions z_j = M^-1 p_j of the Arnoldi steps and update x += sum_j y_j z_j, where gmres.c applies
  * the preconditioner once more to sum_j y_j p_j: the cycle is a fixed linear map, so the two are the same update with
@@ -352,6 +364,14 @@ HYPRE_Int HYPRE_MI_BoomerAMGRelaxLevel(HYPRE_Solver solver, HYPRE_Int level, HYP
  * zero_guess != 0 takes u = 0 on entry (u_host is then output only) and sweeps as the first sweep of a down leg does */
 HYPRE_Int HYPRE_MI_BoomerAMGRelaxPairLevel(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int relax_type, HYPRE_Int first,
                                            HYPRE_Int zero_guess, const HYPRE_Real *f_host, HYPRE_Real *u_host);
+/* the two hooks above on nvec = 2, 3 or 4 vectors at once, as a batched cycle runs them: f_host and
+ * u_host hold the components one after the other, each of the level's local length.  Relax types 3, 4, 6, 8, 13, 14; one
+ * rank.  Every component comes back with the bits of the single-vector hook on it */
+HYPRE_Int HYPRE_MI_BoomerAMGRelaxLevelMulti(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int relax_type, HYPRE_Int points,
+                                            HYPRE_Int nvec, const HYPRE_Real *f_host, HYPRE_Real *u_host);
+HYPRE_Int HYPRE_MI_BoomerAMGRelaxPairLevelMulti(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int relax_type, HYPRE_Int first,
+                                                HYPRE_Int zero_guess, HYPRE_Int nvec, const HYPRE_Real *f_host,
+                                                HYPRE_Real *u_host);
 /* which branch of the tile Gauss-Seidel kernel's in-chunk sweep the waves of one pass take, counted on the host from
  * the level's pattern (points 0: an all-point pass; +1 / -1: the C / F pass of a C-then-F pair; zero_guess: the first
  * sweep on a zero guess).  counts[5]: waves launched, waves without a selected row (no sweep), waves whose chunks
@@ -415,6 +435,13 @@ HYPRE_Int HYPRE_MI_SolveKernelChoice(HYPRE_Int family, HYPRE_Int xcache, HYPRE_I
                                      HYPRE_Int has_dictionary, HYPRE_Int epilogue, HYPRE_Int level0, HYPRE_Int chunk,
                                      HYPRE_Int tiles, HYPRE_BigInt nnz, HYPRE_Int nrows, HYPRE_Int rowlen_p95, char *name,
                                      HYPRE_Int max_len);
+/* the same for a pass that serves nvec components of a multivector (1 ... 4): the batched instantiation and
+ * *batched = 1 where the family has one (x-cache SpMV with epilogue 0, tile Gauss-Seidel), else the single-vector
+ * instantiation, which the launcher then runs once per component, and *batched = 0.  nvec = 1 is SolveKernelChoice */
+HYPRE_Int HYPRE_MI_SolveKernelChoiceMulti(HYPRE_Int nvec, HYPRE_Int family, HYPRE_Int xcache, HYPRE_Int tile_entries,
+                                          HYPRE_Int has_fp32, HYPRE_Int has_dictionary, HYPRE_Int epilogue, HYPRE_Int level0,
+                                          HYPRE_Int chunk, HYPRE_Int tiles, HYPRE_BigInt nnz, HYPRE_Int nrows,
+                                          HYPRE_Int rowlen_p95, char *name, HYPRE_Int max_len, HYPRE_Int *batched);
 /* the same for the Chebyshev step (relax type 16), the third epilogue of the SpMV family */
 HYPRE_Int HYPRE_MI_ChebyKernelChoice(HYPRE_Int xcache, HYPRE_Int tile_entries, HYPRE_Int has_fp32, HYPRE_Int has_dictionary,
                                      char *name, HYPRE_Int max_len);
