@@ -198,6 +198,42 @@ struct AmgLevel {
   bool dense = false;
 };
 
+// Cycle trace (test hook, HYPRE_MI_BoomerAMGTraceCycle): what one cycle left in its vectors after
+// each of its steps, copied to the host where the cycle runs them.  BoomerAMG::trace is null outside that hook, and
+// every call site is `if (trace) ...`: a solve launches, synchronises and allocates what it did without it.
+struct CycleTrace {
+  enum Step {
+    F_IN = 0,       // the level's right-hand side on entry (for a level > 0: the restricted residual)
+    U_IN = 1,       // its guess on entry, when that is not zero
+    U_DOWN = 2,     // u after the down sweeps
+    RESID = 3,      // r = f - A u (Lv.tmp)
+    U_SUB = 4,      // the next level's u after its sub-cycle(s): the correction e
+    U_PROLONG = 5,  // u + P e
+    U_UP = 6,       // u after the up sweeps
+    U_COARSE = 7,   // the coarsest level's u after its solve
+    U_COLLAPSED = 8,  // the collapsed level's u = B f
+    U_SWEEP = 9     // u after one sweep of relax_sweeps (flags: which and the sweep's number)
+  };
+  enum Flag {
+    COMPOSITE = 1,     // RESID: the mat-vec ran on Ar with tvec / f as its composite right-hand side
+    FILL_SKIPPED = 2,  // F_IN: the level's u was not zero-filled before this zero-guess visit
+    DENSE = 4,         // U_COARSE: the dense solve ran
+    SWEPT = 8,         // U_COARSE: relaxation sweeps ran
+    COLLAPSED = 16,    // F_IN / U_COLLAPSED: the visit applied the tabulated map
+    ZERO_GUESS = 32,   // F_IN: the visit started from a zero guess
+    SWEEP_ZERO = 64    // U_SWEEP: the sweep was told its u is zero
+    // U_SWEEP: bits 8-9 = which (0 down, 1 up, 2 coarsest), bits 10.. = the sweep's number
+  };
+  struct Record {
+    int level, visit, step, flags;
+    std::vector<double> values;  // mv_n components, the level's n apart
+  };
+  std::vector<Record> records;
+  std::vector<int> visits;    // per level: cycle() entries so far
+  bool fill_skipped = false;  // set where the next level's zero-fill is decided, read by that level's F_IN
+  bool dense_ran = false;     // set by relax() when the dense solve took the coarsest level
+};
+
 struct LevelBuild;  // what build_natural knows about the level it is building (amg_setup.cpp)
 
 struct BoomerAMG {
@@ -352,6 +388,13 @@ struct BoomerAMG {
   // host-side census of the tile Gauss-Seidel kernel's sweep branches for one pass of relax / relax_pair
   bool gs_sweep_paths(int level, int points, bool u_is_zero, long long counts[5]);
   void cycle(int level, bool u_is_zero = false);
+  // the recorder of the cycle trace (test hook): null but inside trace_cycle.  trace_step waits for the stream and copies
+  // the level's mv_n * n values at `dev` to the host
+  CycleTrace *trace = nullptr;
+  void trace_step(int level, int step, const double *dev, int flags);
+  // one cycle(level, u0 == null) on host arrays of nvec * n values in the level's ordering, every step recorded in `out`;
+  // nvec 2..4: inside mv_enter / mv_leave; collapse false: the collapsed level cycles like any other.  One rank, no tail.
+  void trace_cycle(int level, const double *f_host, const double *u0_host, int nvec, bool collapse, CycleTrace &out);
   // what cycle(0, ..) refreshes first: smoothers, Chebyshev data and the collapsed tail after a setting changed
   void refresh_before_cycle();
   // ---- batched cycle on the components of a multivector (one rank).  mv_n > 1: every level's

@@ -208,9 +208,13 @@ void BoomerAMG::relax(int level, int type, int points, const double *f, bool u_i
   if (type == 9) {
     if (Lv.dense && mv_n > 1) {  // the dense solve of every component of a batched cycle
       for (int c = 0; c < mv_n; c++) dense_solve(Lv, comm, f + (size_t)c * Lv.n, u + (size_t)c * Lv.n, s);
+      if (trace) trace->dense_ran = true;
       return;
     }
-    if (dense_solve(Lv, comm, f, u, s)) return;
+    if (dense_solve(Lv, comm, f, u, s)) {
+      if (trace) trace->dense_ran = true;
+      return;
+    }
     type = p.relax_type[0];  // coarsest level too large for a dense solve
   }
   Lv.t_valid = false;
@@ -428,6 +432,8 @@ void BoomerAMG::relax_sweeps(int level, int which, const double *f, bool u_is_ze
       relax(level, type, 0, f, zero);
     else
       relax_pair(level, type, which == 0 ? 1 : -1, f, zero, sw == p.num_sweeps[which] - 1 ? wout : nullptr);
+    if (trace)
+      trace_step(level, CycleTrace::U_SWEEP, L[(size_t)level].u.p, (zero ? CycleTrace::SWEEP_ZERO : 0) | (which << 8) | (sw << 10));
   }
 }
 
@@ -491,6 +497,78 @@ void BoomerAMG::refresh_before_cycle() {
     build_collapsed_tail();  // a cycle parameter changed after Setup: the tabulated map is of another cycle
 }
 
+// ---- cycle trace (test hook; CycleTrace in amg.hpp).  Only reached with a recorder set.
+void BoomerAMG::trace_step(int level, int step, const double *dev, int flags) {
+  AmgLevel &Lv = L[(size_t)level];
+  CycleTrace::Record r;
+  r.level = level;
+  r.visit = trace->visits[(size_t)level];
+  r.step = step;
+  r.flags = flags;
+  r.values.resize((size_t)mv_n * (size_t)Lv.n);
+  MI_HIP(hipStreamSynchronize(ctx().stream));
+  if (!r.values.empty()) d2h(r.values.data(), dev, r.values.size() * sizeof(double), nullptr);
+  trace->records.push_back(std::move(r));
+}
+
+namespace {
+// a visit of a level begins: its number, f on entry and -- unless the guess is zero -- u on entry
+void trace_enter(BoomerAMG &amg, int level, bool u_is_zero, int flags) {
+  CycleTrace &t = *amg.trace;
+  t.visits[(size_t)level]++;
+  AmgLevel &Lv = amg.L[(size_t)level];
+  flags |= (u_is_zero ? CycleTrace::ZERO_GUESS : 0) | ((u_is_zero && t.fill_skipped) ? CycleTrace::FILL_SKIPPED : 0);
+  t.fill_skipped = false;
+  amg.trace_step(level, CycleTrace::F_IN, Lv.f.p, flags);
+  if (!u_is_zero) amg.trace_step(level, CycleTrace::U_IN, Lv.u.p, 0);
+}
+}  // namespace
+
+void BoomerAMG::trace_cycle(int level, const double *f_host, const double *u0_host, int nvec, bool collapse, CycleTrace &out) {
+  MI_REQUIRE(is_setup && !host_only, "TraceCycle: the hierarchy is not set up on the device");
+  MI_REQUIRE(my_comm().size == 1 && !tail, "TraceCycle: one rank only");
+  MI_REQUIRE(level >= 0 && level < (int)L.size(), "TraceCycle: level out of range");
+  MI_REQUIRE(nvec >= 1 && nvec <= k::MV_MAX_BATCH, "TraceCycle: nvec is 1 to 4");
+  MI_REQUIRE(mv_n == 1 && !trace, "TraceCycle: a cycle is running");
+  refresh_before_cycle();  // a collapsed tail that has to be tabulated again is tabulated here, without a recorder
+  MI_REQUIRE(nvec == 1 || mv_cycle_eligible(), "TraceCycle: this hierarchy's cycle does not run on a batch of components");
+  hipStream_t s = ctx().stream;
+  // what the trace changes in the solver, put back whatever happens
+  struct Restore {
+    BoomerAMG &a;
+    int collapsed_level;
+    double *handover_w;
+    ~Restore() {
+      a.trace = nullptr;
+      a.collapsed_level = collapsed_level;
+      a.handover_w = handover_w;
+    }
+  } restore{*this, collapsed_level, handover_w};
+  handover_w = nullptr;
+  if (!collapse) collapsed_level = -1;  // as tabulate_cycle finds it: the level cycles like any other
+  MvScope batch(*this, nvec);
+  AmgLevel &Lv = L[(size_t)level];
+  const size_t len = (size_t)nvec * (size_t)Lv.n;
+  const bool zero = u0_host == nullptr;
+  out.records.clear();
+  out.visits.assign(L.size(), -1);
+  out.dense_ran = false;
+  out.fill_skipped = false;
+  if (len) {
+    MI_HIP(hipStreamSynchronize(s));
+    MI_HIP(hipMemcpy(Lv.f.p, f_host, len * sizeof(double), hipMemcpyHostToDevice));
+    if (!zero)
+      MI_HIP(hipMemcpy(Lv.u.p, u0_host, len * sizeof(double), hipMemcpyHostToDevice));
+    else if (!zero_cycle_ignores_u(level))  // as every caller of cycle(level, true) does
+      for (int c = 0; c < nvec; c++) k::fill(Lv.u.p + (size_t)c * Lv.n, Lv.n, 0.0, s);
+    else
+      out.fill_skipped = true;
+  }
+  trace = &out;
+  cycle(level, zero);
+  MI_HIP(hipStreamSynchronize(s));
+}
+
 // one cycle on the level's own f (Lv.f) and u (Lv.u); mv_n > 1: on the mv_n components these vectors hold, n apart
 void BoomerAMG::cycle(int level, bool u_is_zero) {
   const int nlev = (int)L.size();
@@ -500,20 +578,30 @@ void BoomerAMG::cycle(int level, bool u_is_zero) {
   if (level == collapsed_level && u_is_zero) {  // the tabulated map of this level's whole sub-cycle
     for (int c = 0; c < mv_n; c++)
       k::dense_matvec_t(collapsed_Bt.p, Lv.f.p + (size_t)c * Lv.n, Lv.u.p + (size_t)c * Lv.n, collapsed_n, ctx().stream);
+    if (trace) {
+      trace_enter(*this, level, true, CycleTrace::COLLAPSED);
+      trace_step(level, CycleTrace::U_COLLAPSED, Lv.u.p, CycleTrace::COLLAPSED);
+    }
     return;
   }
+  if (trace) trace_enter(*this, level, u_is_zero, 0);
   MI_REQUIRE(mv_n == 1 || !tail, "BoomerAMG: a redundant tail does not cycle a batch of components (mv_cycle_eligible)");
   if (level == nlev - 1) {
     if (tail)
       tail_cycle(u_is_zero);
     else
       relax_sweeps(level, 2, Lv.f.p, u_is_zero);
+    if (trace) {
+      trace_step(level, CycleTrace::U_COARSE, Lv.u.p, trace->dense_ran ? CycleTrace::DENSE : CycleTrace::SWEPT);
+      trace->dense_ran = false;
+    }
     return;
   }
   AmgLevel &Ln = L[(size_t)level + 1];
   Comm &comm = my_comm();
   hipStream_t s = ctx().stream;
   relax_sweeps(level, 0, Lv.f.p, u_is_zero && p.num_sweeps[0] > 0);
+  if (trace) trace_step(level, CycleTrace::U_DOWN, Lv.u.p, 0);
   // one vector, or the mv_n components of a batched cycle (xs / bs / ys: their strides, this level's n or the next one's)
   auto matvec = [&](ParCSR &M, double alpha, const double *x, long long xs, double beta, const double *b, long long bs,
                     double *y, long long ys, int prof, const DevCSR *diag_op = nullptr, const double *b_lo = nullptr,
@@ -525,20 +613,25 @@ void BoomerAMG::cycle(int level, bool u_is_zero) {
   };
   const long long n = Lv.n, nn = Ln.n;
   // r = f - A u ; f_c = P^T r ; u_c = 0
-  if (Lv.t_valid && Lv.has_Ar)  // F rows: f - A_FC u_C is in tvec already, only their F columns are left
+  const bool composite = Lv.t_valid && Lv.has_Ar;
+  if (composite)  // F rows: f - A_FC u_C is in tvec already, only their F columns are left
     matvec(*Lv.A, -1.0, Lv.u.p, n, 1.0, Lv.tvec.p, n, Lv.tmp.p, n, k::prof_level(k::PROF_LVL_RESID, level), &Lv.Ar, Lv.f.p,
            std::min(Lv.t_from, Lv.n));
   else
     matvec(*Lv.A, -1.0, Lv.u.p, n, 1.0, Lv.f.p, n, Lv.tmp.p, n, k::prof_level(k::PROF_LVL_RESID, level));
   Lv.t_valid = false;
+  if (trace) trace_step(level, CycleTrace::RESID, Lv.tmp.p, composite ? CycleTrace::COMPOSITE : 0);
   matvec(*Lv.Rm, 1.0, Lv.tmp.p, n, 0.0, nullptr, 0, Ln.f.p, nn, k::prof_level(k::PROF_LVL_RESTRICT, level));
-  if (!zero_cycle_ignores_u(level + 1))
+  const bool fill_next = !zero_cycle_ignores_u(level + 1);
+  if (fill_next)
     for (int c = 0; c < mv_n; c++) k::fill(Ln.u.p + (size_t)c * Ln.n, Ln.n, 0.0, s);
+  if (trace) trace->fill_skipped = !fill_next;
   // the coarsest level is visited once per cycle; with a redundant tail the count continues into the tail
   const bool tail_next = tail && level + 1 == nlev - 1;
   const bool next_is_coarsest = tail_next ? tail->L.size() == 1 : level + 1 == nlev - 1;
   const int ncyc = (p.cycle_type == 2 && !next_is_coarsest) ? 2 : 1;
   for (int c = 0; c < ncyc; c++) cycle(level + 1, c == 0);
+  if (trace) trace_step(level + 1, CycleTrace::U_SUB, Ln.u.p, 0);
   // u += P e
   if (tail_next) {  // every rank holds the whole coarse correction: halo values without an exchange
     const int next = (int)Lv.Pm->col_map_offd.size();
@@ -547,7 +640,9 @@ void BoomerAMG::cycle(int level, bool u_is_zero) {
   } else {
     matvec(*Lv.Pm, 1.0, Ln.u.p, nn, 1.0, Lv.u.p, n, Lv.u.p, n, k::prof_level(k::PROF_LVL_PROLONG, level));
   }
+  if (trace) trace_step(level, CycleTrace::U_PROLONG, Lv.u.p, 0);
   relax_sweeps(level, 1, Lv.f.p, false, (level == 0 && mv_n == 1) ? handover_w : nullptr);
+  if (trace) trace_step(level, CycleTrace::U_UP, Lv.u.p, 0);
 }
 
 bool BoomerAMG::mv_cycle_eligible() {

@@ -2719,6 +2719,59 @@ HYPRE_Int HYPRE_MI_BoomerAMGRelaxPairLevelMulti(HYPRE_Solver solver, HYPRE_Int l
   if (len) d2h(u_host, Lv.u.p, len * sizeof(double), nullptr);
   API_END
 }
+// test hooks (tests/test_gpu_cycle_steps.py): one cycle with every step recorded where the cycle runs it
+HYPRE_Int HYPRE_MI_BoomerAMGTraceCycle(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int nvec, HYPRE_Int collapse,
+                                       const HYPRE_Real *f_host, const HYPRE_Real *u0_host, HYPRE_Int *nrecords) {
+  API_BEGIN
+  AmgSolver *a = AMG(solver);
+  if (!f_host || !nrecords) fail(HYPRE_ERROR_ARG, "TraceCycle: NULL argument");
+  if (!a->amg.is_setup) fail(HYPRE_ERROR_GENERIC, "TraceCycle: AMG is not set up");
+  if (current_comm().size != 1 || a->amg.tail) fail(HYPRE_ERROR_GENERIC, "TraceCycle: one rank only");
+  if (level < 0 || level >= (int)a->amg.L.size()) fail(HYPRE_ERROR_ARG, "AMG level out of range");
+  if (nvec < 1 || nvec > k::MV_MAX_BATCH) fail(HYPRE_ERROR_ARG, "TraceCycle: nvec is 1, 2, 3 or 4");
+  *nrecords = 0;
+  a->amg.trace_cycle(level, f_host, u0_host, nvec, collapse != 0, a->last_trace);
+  *nrecords = (HYPRE_Int)a->last_trace.records.size();
+  API_END
+}
+HYPRE_Int HYPRE_MI_BoomerAMGGetTraceRecord(HYPRE_Solver solver, HYPRE_Int i, HYPRE_Int info[5], HYPRE_Real *values) {
+  API_BEGIN
+  AmgSolver *a = AMG(solver);
+  if (!info) fail(HYPRE_ERROR_ARG, "GetTraceRecord: NULL argument");
+  if (i < 0 || i >= (HYPRE_Int)a->last_trace.records.size()) fail(HYPRE_ERROR_ARG, "GetTraceRecord: no such record");
+  const CycleTrace::Record &r = a->last_trace.records[(size_t)i];
+  info[0] = r.level, info[1] = r.visit, info[2] = r.step, info[3] = r.flags, info[4] = (HYPRE_Int)r.values.size();
+  if (values) std::copy(r.values.begin(), r.values.end(), values);
+  API_END
+}
+HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCycleInfo(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int out[6]) {
+  API_BEGIN
+  AmgSolver *a = AMG(solver);
+  if (!out) fail(HYPRE_ERROR_ARG, "GetLevelCycleInfo: NULL argument");
+  if (level < 0 || level >= (int)a->amg.L.size()) fail(HYPRE_ERROR_ARG, "AMG level out of range");
+  const AmgLevel &Lv = a->amg.L[(size_t)level];
+  out[0] = (Lv.Rm && Lv.Rm->d_diag.rowmap.p) ? 1 : 0;
+  out[1] = Lv.t_from;
+  out[2] = Lv.has_Ar ? 1 : 0;
+  out[3] = Lv.has_Az ? 1 : 0;
+  out[4] = Lv.nc;
+  out[5] = a->amg.collapsed_level;
+  API_END
+}
+HYPRE_Int HYPRE_MI_BoomerAMGGetCollapsedTail(HYPRE_Solver solver, HYPRE_Int *level, HYPRE_Int *n, HYPRE_Real *Bt_host) {
+  API_BEGIN
+  BoomerAMG &amg = AMG(solver)->amg;
+  if (!level || !n) fail(HYPRE_ERROR_ARG, "GetCollapsedTail: NULL argument");
+  if (amg.is_setup && !amg.host_only && amg.mv_n == 1) amg.refresh_before_cycle();  // the map of the cycle's current settings
+  *level = amg.collapsed_level;
+  *n = amg.collapsed_level >= 0 ? amg.collapsed_n : 0;
+  const size_t len = (size_t)*n * (size_t)*n;
+  if (Bt_host && len) {
+    MI_HIP(hipStreamSynchronize(ctx().stream));
+    d2h(Bt_host, amg.collapsed_Bt.p, len * sizeof(double), nullptr);
+  }
+  API_END
+}
 HYPRE_Int HYPRE_MI_BoomerAMGGetGSSweepPaths(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int points, HYPRE_Int zero_guess,
                                             HYPRE_Int *on_tiles, HYPRE_BigInt *counts) {
   API_BEGIN

@@ -15,6 +15,7 @@ typedef int (*ParSolverFcn)(void *, void *, void *, void *);
 
 struct AmgSolver : SolverBase {
   BoomerAMG amg;
+  CycleTrace last_trace;  // the records of the last HYPRE_MI_BoomerAMGTraceCycle (test hook)
   AmgSolver() : SolverBase(K_AMG) {}
 };
 

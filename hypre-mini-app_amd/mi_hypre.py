@@ -542,6 +542,54 @@ class BoomerAMG:
         call("HYPRE_MI_BoomerAMGRelaxPairLevelMulti", self.h, level, relax_type, first, 1 if zero else 0, f.shape[0], f, u)
         return u
 
+    # ---- cycle trace (test hooks)
+    TRACE_STEPS = ("f_in", "u_in", "u_down", "resid", "u_sub", "u_prolong", "u_up", "u_coarse", "u_collapsed", "u_sweep")
+    TRACE_COMPOSITE, TRACE_FILL_SKIPPED, TRACE_DENSE, TRACE_SWEPT, TRACE_COLLAPSED, TRACE_ZERO_GUESS, TRACE_SWEEP_ZERO = \
+        1, 2, 4, 8, 16, 32, 64
+
+    def trace_cycle(self, level, f, u0=None, nvec=1, collapse=True):
+        """One cycle(level, zero guess iff u0 is None) on host arrays in level_csr's numbering, every step recorded where
+        the cycle runs it.  nvec 2 .. 4: f (and u0) of shape (nvec, n), run as a batched cycle.  collapse False: the
+        collapsed level cycles like any other.  Returns records (level, visit, step name, values, flags), values of
+        shape (n_level,) or (nvec, n_level); a u_sweep record's flags carry which leg (bits 8-9) and sweep (bits 10..)."""
+        f = dbl(f)
+        assert f.shape[0] == nvec if nvec > 1 else f.ndim == 1
+        if u0 is not None:
+            u0 = dbl(u0)
+            assert u0.shape == f.shape
+        nrec = c_int()
+        call("HYPRE_MI_BoomerAMGTraceCycle", self.h, level, nvec, 1 if collapse else 0, f, u0, C.byref(nrec))
+        out = []
+        for i in range(nrec.value):
+            info = np.zeros(5, dtype=np.int32)
+            call("HYPRE_MI_BoomerAMGGetTraceRecord", self.h, i, info, None)
+            vals = np.zeros(max(int(info[4]), 1), dtype=np.float64)
+            call("HYPRE_MI_BoomerAMGGetTraceRecord", self.h, i, info, vals)
+            vals = vals[: int(info[4])]
+            if nvec > 1:
+                vals = vals.reshape(nvec, -1)
+            out.append((int(info[0]), int(info[1]), self.TRACE_STEPS[int(info[2])], vals, int(info[3])))
+        return out
+
+    def level_cycle_info(self, level):
+        """dict(r_row_mapped, t_from, has_Ar, has_Az, nc, collapsed_level): the state of a level the cycle's steps
+        depend on."""
+        out = np.zeros(6, dtype=np.int32)
+        call("HYPRE_MI_BoomerAMGGetLevelCycleInfo", self.h, level, out)
+        return dict(r_row_mapped=bool(out[0]), t_from=int(out[1]), has_Ar=bool(out[2]), has_Az=bool(out[3]),
+                    nc=int(out[4]), collapsed_level=int(out[5]))
+
+    def collapsed_tail(self):
+        """(level, B): the tabulated map u = B f of the collapsed coarse tail (n x n, level's numbering); (-1, None)
+        without one."""
+        level, n = c_int(), c_int()
+        call("HYPRE_MI_BoomerAMGGetCollapsedTail", self.h, C.byref(level), C.byref(n), None)
+        if level.value < 0:
+            return -1, None
+        Bt = np.zeros((n.value, n.value), dtype=np.float64)
+        call("HYPRE_MI_BoomerAMGGetCollapsedTail", self.h, C.byref(level), C.byref(n), Bt)
+        return level.value, np.ascontiguousarray(Bt.T)
+
     def c_row_handover_census(self, level=0):
         """dict(tiles, listed, handed, flagged_c_rows, w_upto): the tiles of the level's operator, those the mat-vec
         after a C-row hand-over still runs, the handed-over ones, the C rows with an off-diagonal C column, and the row

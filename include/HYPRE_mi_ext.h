@@ -372,6 +372,35 @@ HYPRE_Int HYPRE_MI_BoomerAMGRelaxLevelMulti(HYPRE_Solver solver, HYPRE_Int level
 HYPRE_Int HYPRE_MI_BoomerAMGRelaxPairLevelMulti(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int relax_type, HYPRE_Int first,
                                                 HYPRE_Int zero_guess, HYPRE_Int nvec, const HYPRE_Real *f_host,
                                                 HYPRE_Real *u_host);
+/* ---- cycle trace: TEST HOOKS (tests/test_gpu_cycle_steps.py).  No solve path calls them, and a
+ * solver that was never traced launches, synchronises and allocates exactly what it did before they existed.
+ *
+ * TraceCycle runs ONE cycle(level, zero guess iff u0_host == NULL) of the hierarchy on HOST arrays of nvec times the
+ * level's local length, in GetLevelCSR's numbering, and records what the cycle's vectors hold after each of its steps,
+ * where the cycle runs them (the state a step depends on -- a composite right-hand side, a skipped zero-fill -- is the
+ * cycle's own).  nvec 2, 3 or 4 runs it as a batched cycle does (components one after the other); collapse == 0 makes
+ * the cycle descend through the level whose sub-cycle is otherwise applied as a tabulated map.  One rank only.
+ * *nrecords = the records kept in the solver until the next TraceCycle; GetTraceRecord copies record i:
+ *   info[0] level, info[1] visit (0, 1, ... per level within this cycle), info[2] step, info[3] flags, info[4] the
+ *   number of values (nvec x that level's rows); values may be NULL to query info.
+ * steps: 0 f on entry; 1 u on entry (non-zero guess only); 2 u after the down sweeps; 3 the residual f - A u; 4 (level
+ *   l + 1's record) the correction after the sub-cycle(s); 5 u after the prolongation; 6 u after the up sweeps; 7 u of the
+ *   coarsest level after its solve; 8 u of the collapsed level (the map applied); 9 u after one sweep of a leg
+ *   (flags bits 8-9: 0 down / 1 up / 2 coarsest, bits 10 and up: the sweep's number, bit 6: the sweep took u as zero).
+ * flags: 1 (step 3) the residual ran on the reduced operator with the F pass's product as a composite right-hand side;
+ *   2 (step 0) the level's zero-fill was skipped; 4 / 8 (step 7) the dense solve / relaxation sweeps ran; 16 (steps 0, 8)
+ *   the visit applied the collapsed map; 32 (step 0) the visit started from a zero guess. */
+HYPRE_Int HYPRE_MI_BoomerAMGTraceCycle(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int nvec, HYPRE_Int collapse,
+                                       const HYPRE_Real *f_host, const HYPRE_Real *u0_host, HYPRE_Int *nrecords);
+HYPRE_Int HYPRE_MI_BoomerAMGGetTraceRecord(HYPRE_Solver solver, HYPRE_Int i, HYPRE_Int info[5], HYPRE_Real *values);
+/* test hook: the state of a level the cycle's steps depend on.  out[0] = 1 when R's rows are stored in another order
+ * and written through a row map, out[1] = t_from (the first F row whose product with the C values the F pass hands to
+ * the residual), out[2] = 1 when the level has the reduced residual operator, out[3] = 1 when it has the zero-guess
+ * sub-operator, out[4] = the number of C rows, out[5] = the level whose sub-cycle is collapsed (-1: none) */
+HYPRE_Int HYPRE_MI_BoomerAMGGetLevelCycleInfo(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Int out[6]);
+/* test hook: the tabulated map of the collapsed coarse tail.  *level = -1 and *n = 0 without one; else *n <= 1024 rows
+ * and row j of Bt_host (n x n, row-major) is column j of the map f -> u.  Bt_host may be NULL to query the size */
+HYPRE_Int HYPRE_MI_BoomerAMGGetCollapsedTail(HYPRE_Solver solver, HYPRE_Int *level, HYPRE_Int *n, HYPRE_Real *Bt_host);
 /* which branch of the tile Gauss-Seidel kernel's in-chunk sweep the waves of one pass take, counted on the host from
  * the level's pattern (points 0: an all-point pass; +1 / -1: the C / F pass of a C-then-F pair; zero_guess: the first
  * sweep on a zero guess).  counts[5]: waves launched, waves without a selected row (no sweep), waves whose chunks
