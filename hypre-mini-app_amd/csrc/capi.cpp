@@ -1982,6 +1982,10 @@ HYPRE_Int HYPRE_MI_GetCounter(const char *name, long long *value) {
     *value = ctx().n_precond_cycles;
   else if (n == "gmres_direction_vectors")
     *value = ctx().n_gmres_z_allocated;
+  else if (n == "krylov_basis_fp32_vectors")
+    *value = ctx().n_krylov_basis_fp32;
+  else if (n == "krylov_basis_bytes")
+    *value = ctx().krylov_basis_bytes;
   else if (n == "handover_matvecs")
     *value = ctx().n_handover_matvecs;
   else if (n == "handover_tiles_skipped")
@@ -2193,6 +2197,97 @@ HYPRE_Int HYPRE_MI_VectorKernelOp(HYPRE_Int op, HYPRE_Int m, HYPRE_ParVector *ve
   API_END
 }
 
+// The same hook for the kernels' instantiations on float basis vectors (Krylov basis storage mode 1): `vecs` are
+// converted to float storage (round to nearest even, on the host) and ops 0, 1, 2 and 5 run the float instantiation on
+// them; w, the coefficients and every result stay double.  Op 4 runs the rounding variant of the posting scaling:
+// w = rd(w / sqrt(coef[0])), and the float slot the kernel also writes starts as xd's values converted and comes back
+// widened in xd (xd NULL: the slot starts as zeros and is dropped).  Op 3 has no float instantiation.
+HYPRE_Int HYPRE_MI_VectorKernelOpF32(HYPRE_Int op, HYPRE_Int m, HYPRE_ParVector *vecs, const HYPRE_Real *coef,
+                                     HYPRE_Real scale, HYPRE_ParVector w, HYPRE_ParVector xd, HYPRE_Int init,
+                                     HYPRE_Real *out) {
+  API_BEGIN
+  ensure_init();
+  Ctx &c = ctx();
+  hipStream_t s = c.stream;
+  MI_REQUIRE(w, "VectorKernelOpF32: NULL vector w");
+  MI_REQUIRE(op >= 0 && op <= 5 && op != 3, "VectorKernelOpF32: op must be 0, 1, 2, 4 or 5");
+  const int mmax = (op <= 1) ? 120 : (op == 2 ? 250 : (op == 4 ? 255 : 2 * k::MGS_NB));
+  MI_REQUIRE(m >= 1 && m <= mmax, "VectorKernelOpF32: m out of range for this op");
+  MI_REQUIRE(op == 0 || coef, "VectorKernelOpF32: NULL coefficients");
+  MI_REQUIRE(op == 1 || op == 2 || out, "VectorKernelOpF32: NULL output");
+  const int n = PV(w)->len();
+  MI_HIP(hipStreamSynchronize(s));
+  // device doubles -> a float copy on the device, converted on the host
+  auto narrowed = [&](const double *dev) {
+    std::vector<double> h((size_t)n);
+    if (n) d2h(h.data(), dev, (size_t)n * sizeof(double), s);
+    std::vector<float> f((size_t)n);
+    for (int i = 0; i < n; i++) f[(size_t)i] = (float)h[(size_t)i];
+    DVec<float> d((size_t)n);
+    if (n) d.upload(f.data(), (size_t)n);
+    return d;
+  };
+  std::vector<DVec<float>> store;
+  std::vector<const float *> vp;
+  if (op != 4) {
+    MI_REQUIRE(vecs, "VectorKernelOpF32: NULL vector list");
+    for (int j = 0; j < m; j++) {
+      MI_REQUIRE(vecs[j] && PV(vecs[j])->len() == n, "VectorKernelOpF32: vecs[j] is NULL or differs from w in length");
+      MI_REQUIRE(vecs[j] != w, "VectorKernelOpF32: w among vecs");
+      store.push_back(narrowed(PV(vecs[j])->all()));
+      vp.push_back(store.back().p);
+    }
+  }
+  MI_REQUIRE(!xd || (op == 4 && PV(xd)->len() == n && xd != w), "VectorKernelOpF32: xd goes with op 4 and has w's length");
+  double *slots = c.red_out.p;
+  if (op == 1 || op == 4) MI_HIP(hipMemcpyAsync(slots, coef, (size_t)m * sizeof(double), hipMemcpyHostToDevice, s));
+  switch (op) {
+    case 0:
+      k::mass_dot(vp.data(), m, PV(w)->all(), n, slots, s);
+      d2h(out, slots, (size_t)m * sizeof(double), s);
+      break;
+    case 1: k::mass_axpy(vp.data(), m, slots, scale, PV(w)->all(), n, s); break;
+    case 2: k::lin_comb(vp.data(), coef, m, init != 0, PV(w)->all(), n, s); break;
+    case 5: {
+      constexpr int NB = k::MGS_NB;
+      const int m_prev = (int)scale, m_next = init ? 0 : m - m_prev;
+      MI_REQUIRE(m_prev >= 0 && m_prev <= NB && m_prev <= m && m - m_prev <= NB && (!init || m_prev == m),
+                 "VectorKernelOpF32: op 5 takes at most MGS_NB vectors per block, and none to measure in the last pass");
+      DVec<double> buf((size_t)NB * (NB + 2) + 3 * (NB + 1));  // c, Gram rows | sums, h, ||w||^2
+      double *sums = buf.p + NB * (NB + 2), *h = sums + NB + 1;
+      MI_HIP(hipMemcpyAsync(buf.p, coef, (size_t)NB * (NB + 2) * sizeof(double), hipMemcpyHostToDevice, s));
+      MI_HIP(hipMemsetAsync(sums, 0, (size_t)3 * (NB + 1) * sizeof(double), s));
+      k::mgs_block_pass(vp.data(), m_prev, vp.data() + m_prev, m_next, init != 0, buf.p, buf.p + NB, h, PV(w)->all(), n,
+                        sums, init ? h + NB : nullptr, s);
+      d2h(out, sums, (size_t)(2 * NB + 2) * sizeof(double), s);
+      break;
+    }
+    default: {
+      DVec<float> slot;
+      if (xd) {
+        slot = narrowed(PV(xd)->all());
+      } else {
+        slot.alloc((size_t)n);
+        if (n) MI_HIP(hipMemsetAsync(slot.p, 0, (size_t)n * sizeof(float), s));
+      }
+      const unsigned long long seq = ++c.post_seq;
+      k::scale_inv_sqrt_post_round(slots, PV(w)->all(), slot.p, n, slots, m, c.h_pinned + 256, c.h_post_flag, seq, s);
+      MI_HIP(hipStreamSynchronize(s));
+      for (int j = 0; j < m; j++) out[j] = c.h_pinned[256 + j];
+      out[m] = (double)__atomic_load_n(c.h_post_flag, __ATOMIC_ACQUIRE);
+      out[m + 1] = (double)seq;
+      if (xd && n) {
+        std::vector<float> f((size_t)n);
+        d2h(f.data(), slot.p, (size_t)n * sizeof(float), s);
+        std::vector<double> h(f.begin(), f.end());
+        MI_HIP(hipMemcpy(PV(xd)->all(), h.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+      }
+    }
+  }
+  MI_HIP(hipStreamSynchronize(s));
+  API_END
+}
+
 HYPRE_Int HYPRE_MI_ArenaSelfTest(HYPRE_Int seed, HYPRE_Int rounds, HYPRE_BigInt max_block_bytes, HYPRE_BigInt *verified,
                                  HYPRE_BigInt *peak_bytes) {
   API_BEGIN
@@ -2294,6 +2389,19 @@ HYPRE_Int HYPRE_MI_GetMultivectorBatch(HYPRE_Int *width) {
 HYPRE_Int HYPRE_MI_SetGmresKeepDirections(HYPRE_Int on) {
   API_BEGIN
   gmres_keep_directions() = on != 0;
+  API_END
+}
+HYPRE_Int HYPRE_MI_SetKrylovBasisStorage(HYPRE_Int mode) {
+  API_BEGIN
+  if (mode < 0 || mode > 2)
+    fail(HYPRE_ERROR_ARG, "SetKrylovBasisStorage: the mode is 0 (fp64), 1 (float) or 2 (fp64 storage of float-rounded values)");
+  krylov_basis_storage() = (int)mode;
+  API_END
+}
+HYPRE_Int HYPRE_MI_GetKrylovBasisStorage(HYPRE_Int *mode) {
+  API_BEGIN
+  if (!mode) fail(HYPRE_ERROR_ARG, "GetKrylovBasisStorage: NULL argument");
+  *mode = krylov_basis_storage();
   API_END
 }
 HYPRE_Int HYPRE_MI_TestGmresDirectionAllocFailsAt(HYPRE_Int at) {

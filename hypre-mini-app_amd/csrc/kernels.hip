@@ -41,6 +41,29 @@ template <class T>
 __device__ __forceinline__ T nt_load(const T *p) {
   return __builtin_nontemporal_load(p);
 }
+// Two consecutive elements of a Krylov basis vector stored as T = double or float (basis storage mode 1, DESIGN.md
+// section 3), as the doubles the arithmetic takes: one 16-byte or one 8-byte load per lane, the same elements on the same
+// lane either way, and float -> double is exact -- a kernel instantiated on float gives the bits its double instantiation
+// gives on the same values.  NT: non-temporal, where the fp64 kernel's load is.
+template <class T>
+struct BasisPair;
+template <>
+struct BasisPair<double> {
+  typedef d2_t type;
+};
+template <>
+struct BasisPair<float> {
+  typedef f2_t type;
+};
+template <bool NT, class T>
+__device__ __forceinline__ d2_t load_pair(const T *p) {
+  typedef typename BasisPair<T>::type V;
+  const V v = NT ? nt_load(reinterpret_cast<const V *>(p)) : *reinterpret_cast<const V *>(p);
+  d2_t r;
+  r.x = (double)v.x;
+  r.y = (double)v.y;
+  return r;
+}
 
 // The tile kernels (spmv_stream_xc, gs_tile_k) read their matrix stream (values or value indices, 16-bit column words)
 // and their column lists exactly once, in whole lines per load instruction: non-temporal loads too, so that what stays
@@ -1735,11 +1758,13 @@ __global__ __launch_bounds__(256) void axpy_dot_partial_k(const double *__restri
 // ---- block Gram-Schmidt pieces of COGMRES: up to MASS_NV inner products off one vector in one pass, and the
 // matching block update.  The per-thread accumulation pattern is dot_partial_k's, so every result equals the
 // separate dot's bit for bit; the update adds the terms in ascending j like repeated axpys.
+template <class T>
 struct MassPtrs {
-  const double *p[MASS_NV];
+  const T *p[MASS_NV];
 };
 
-__global__ __launch_bounds__(256) void mass_dot_partial_k(MassPtrs P, int m, const double *__restrict__ w, int n,
+template <class T>
+__global__ __launch_bounds__(256) void mass_dot_partial_k(MassPtrs<T> P, int m, const double *__restrict__ w, int n,
                                                           double *__restrict__ partials) {
   __shared__ double ws[MASS_NV][4];
   const int tid = threadIdx.x;
@@ -1753,14 +1778,14 @@ __global__ __launch_bounds__(256) void mass_dot_partial_k(MassPtrs P, int m, con
 #pragma unroll
     for (int j = 0; j < MASS_NV; j++)
       if (j < m) {
-        const double2 a = *reinterpret_cast<const double2 *>(P.p[j] + i);
+        const d2_t a = load_pair<false>(P.p[j] + i);
         acc[j] += a.x * b.x + a.y * b.y;
       }
   }
   if (i < n) {
 #pragma unroll
     for (int j = 0; j < MASS_NV; j++)
-      if (j < m) acc[j] += P.p[j][i] * w[i];
+      if (j < m) acc[j] += (double)P.p[j][i] * w[i];
   }
 #pragma unroll
   for (int j = 0; j < MASS_NV; j++) {
@@ -1785,7 +1810,8 @@ __global__ __launch_bounds__(256) void reduce_final_multi_k(const double *__rest
 }
 
 // w += sum_j (scale * coef[j]) * p_j, terms added in ascending j
-__global__ __launch_bounds__(256) void mass_axpy_k(MassPtrs P, int m, const double *__restrict__ coef, double scale,
+template <class T>
+__global__ __launch_bounds__(256) void mass_axpy_k(MassPtrs<T> P, int m, const double *__restrict__ coef, double scale,
                                                    double *__restrict__ w, int n) {
   double c[MASS_NV];
 #pragma unroll
@@ -1797,7 +1823,7 @@ __global__ __launch_bounds__(256) void mass_axpy_k(MassPtrs P, int m, const doub
 #pragma unroll
     for (int j = 0; j < MASS_NV; j++)
       if (j < m) {
-        const double2 a = *reinterpret_cast<const double2 *>(P.p[j] + i);
+        const d2_t a = load_pair<false>(P.p[j] + i);
         wv.x += c[j] * a.x;
         wv.y += c[j] * a.y;
       }
@@ -1807,7 +1833,7 @@ __global__ __launch_bounds__(256) void mass_axpy_k(MassPtrs P, int m, const doub
     double v = w[i];
 #pragma unroll
     for (int j = 0; j < MASS_NV; j++)
-      if (j < m) v += c[j] * P.p[j][i];
+      if (j < m) v += c[j] * (double)P.p[j][i];
     w[i] = v;
   }
 }
@@ -1854,10 +1880,10 @@ __device__ __forceinline__ void finish_reduction_multi(double (*ws)[4], double *
   if (tid == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int B>
+template <int B, class T>
 struct MgsPtrs {
-  const double *prev[B];
-  const double *next[B];
+  const T *prev[B];
+  const T *next[B];
 };
 
 // Prologue (every thread, at most B(B-1)/2 FMAs): the MGS coefficients of the block `prev` from the raw inner products
@@ -1868,8 +1894,8 @@ struct MgsPtrs {
 //   !LAST: out[j] = <next_j, w>, j < m_next (the raw c of the next block);
 //   LAST:  out[j] = <prev_j, w>, j < m_prev, out[B] = ||w||^2 (also at out_norm): the raw Gram row of w.
 // Streaming as axpy_dot_partial_k: every operand once, non-temporal.  Outputs beyond the counts are 0.
-template <int B, bool LAST>
-__global__ __launch_bounds__(256) void mgs_block_pass_k(MgsPtrs<B> P, int m_prev, int m_next,
+template <int B, bool LAST, class T>
+__global__ __launch_bounds__(256) void mgs_block_pass_k(MgsPtrs<B, T> P, int m_prev, int m_next,
                                                         const double *__restrict__ c_prev,
                                                         const double *__restrict__ gram_prev, double *__restrict__ h_out,
                                                         double *__restrict__ w, int n, double *__restrict__ partials,
@@ -1902,11 +1928,11 @@ __global__ __launch_bounds__(256) void mgs_block_pass_k(MgsPtrs<B> P, int m_prev
     d2_t pv[B], qv[B];
 #pragma unroll
     for (int j = 0; j < B; j++)
-      if (j < m_prev) pv[j] = nt_load(reinterpret_cast<const d2_t *>(P.prev[j] + i));
+      if (j < m_prev) pv[j] = load_pair<true>(P.prev[j] + i);
     if (!LAST) {
 #pragma unroll
       for (int j = 0; j < B; j++)
-        if (j < m_next) qv[j] = nt_load(reinterpret_cast<const d2_t *>(P.next[j] + i));
+        if (j < m_next) qv[j] = load_pair<true>(P.next[j] + i);
     }
 #pragma unroll
     for (int j = 0; j < B; j++)
@@ -1930,17 +1956,17 @@ __global__ __launch_bounds__(256) void mgs_block_pass_k(MgsPtrs<B> P, int m_prev
     double v = w[i];
 #pragma unroll
     for (int j = 0; j < B; j++)
-      if (j < m_prev) v += a[j] * P.prev[j][i];
+      if (j < m_prev) v += a[j] * (double)P.prev[j][i];
     if (m_prev > 0) w[i] = v;
     if (LAST) {
 #pragma unroll
       for (int j = 0; j < B; j++)
-        if (j < m_prev) acc[j] += P.prev[j][i] * v;
+        if (j < m_prev) acc[j] += (double)P.prev[j][i] * v;
       acc[B] += v * v;
     } else {
 #pragma unroll
       for (int j = 0; j < B; j++)
-        if (j < m_next) acc[j] += P.next[j][i] * v;
+        if (j < m_next) acc[j] += (double)P.next[j][i] * v;
     }
   }
 #pragma unroll
@@ -1957,14 +1983,14 @@ __global__ __launch_bounds__(256) void mgs_block_pass_k(MgsPtrs<B> P, int m_prev
 struct MassCoef {
   double c[MASS_NV];
 };
-template <bool INIT>
-__global__ __launch_bounds__(256) void lin_comb_k(MassPtrs P, int m, MassCoef C, double *__restrict__ w, int n) {
+template <bool INIT, class T>
+__global__ __launch_bounds__(256) void lin_comb_k(MassPtrs<T> P, int m, MassCoef C, double *__restrict__ w, int n) {
   const long long stride = (long long)gridDim.x * 512;
   long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 2;
   for (; i + 1 < n; i += stride) {
     double2 wv;
     if (INIT) {
-      const d2_t a = nt_load(reinterpret_cast<const d2_t *>(P.p[0] + i));
+      const d2_t a = load_pair<true>(P.p[0] + i);
       wv.x = C.c[0] * a.x;
       wv.y = C.c[0] * a.y;
     } else {
@@ -1973,17 +1999,17 @@ __global__ __launch_bounds__(256) void lin_comb_k(MassPtrs P, int m, MassCoef C,
 #pragma unroll
     for (int j = INIT ? 1 : 0; j < MASS_NV; j++)
       if (j < m) {
-        const d2_t a = nt_load(reinterpret_cast<const d2_t *>(P.p[j] + i));
+        const d2_t a = load_pair<true>(P.p[j] + i);
         wv.x += C.c[j] * a.x;
         wv.y += C.c[j] * a.y;
       }
     *reinterpret_cast<double2 *>(w + i) = wv;
   }
   if (i < n) {
-    double v = INIT ? C.c[0] * P.p[0][i] : w[i];
+    double v = INIT ? C.c[0] * (double)P.p[0][i] : w[i];
 #pragma unroll
     for (int j = INIT ? 1 : 0; j < MASS_NV; j++)
-      if (j < m) v += C.c[j] * P.p[j][i];
+      if (j < m) v += C.c[j] * (double)P.p[j][i];
     w[i] = v;
   }
 }
@@ -3016,13 +3042,16 @@ void axpy_dot(const double *alpha_dev, double scale_, const double *xa, double *
   MI_HIP(hipGetLastError());
 }
 
-void mgs_block_pass(const double *const *prev, int m_prev, const double *const *next, int m_next, bool last,
-                    const double *c_prev, const double *gram_prev, double *h_out, double *w, int n, double *out_dev,
-                    double *out_norm, hipStream_t s) {
+// The Gram-Schmidt and update launchers below exist for basis vectors stored as double and as float (Krylov basis
+// storage mode 1): one body each, instantiated on the element type, the same grid and the same kernel body either way.
+template <class T>
+static void mgs_block_pass_t(const T *const *prev, int m_prev, const T *const *next, int m_next, bool last,
+                             const double *c_prev, const double *gram_prev, double *h_out, double *w, int n, double *out_dev,
+                             double *out_norm, hipStream_t s) {
   MI_REQUIRE(m_prev >= 0 && m_prev <= MGS_NB && m_next >= 0 && m_next <= MGS_NB, "mgs_block_pass: block too large");
   // MGS_NB + 1 partial sums per workgroup in the slots the reductions share
   const int g = std::min(dot_grid(n), RED_MAX_BLOCKS * MASS_NV / (MGS_NB + 1));
-  MgsPtrs<MGS_NB> P;
+  MgsPtrs<MGS_NB, T> P;
   for (int j = 0; j < MGS_NB; j++) {
     P.prev[j] = j < m_prev ? prev[j] : nullptr;
     P.next[j] = (!last && j < m_next) ? next[j] : nullptr;
@@ -3030,62 +3059,97 @@ void mgs_block_pass(const double *const *prev, int m_prev, const double *const *
   double *partials = ctx().red_partials.p;
   prof_begin(PROF_DOT, s);
   if (last)
-    hipLaunchKernelGGL((mgs_block_pass_k<MGS_NB, true>), dim3(g), dim3(256), 0, s, P, m_prev, 0, c_prev, gram_prev, h_out,
+    hipLaunchKernelGGL((mgs_block_pass_k<MGS_NB, true, T>), dim3(g), dim3(256), 0, s, P, m_prev, 0, c_prev, gram_prev, h_out,
                        w, n, partials, ctx().red_ticket.p, out_dev, out_norm);
   else
-    hipLaunchKernelGGL((mgs_block_pass_k<MGS_NB, false>), dim3(g), dim3(256), 0, s, P, m_prev, m_next, c_prev, gram_prev,
+    hipLaunchKernelGGL((mgs_block_pass_k<MGS_NB, false, T>), dim3(g), dim3(256), 0, s, P, m_prev, m_next, c_prev, gram_prev,
                        h_out, w, n, partials, ctx().red_ticket.p, out_dev, out_norm);
   prof_end(PROF_DOT, s);
   MI_HIP(hipGetLastError());
 }
+void mgs_block_pass(const double *const *prev, int m_prev, const double *const *next, int m_next, bool last,
+                    const double *c_prev, const double *gram_prev, double *h_out, double *w, int n, double *out_dev,
+                    double *out_norm, hipStream_t s) {
+  mgs_block_pass_t(prev, m_prev, next, m_next, last, c_prev, gram_prev, h_out, w, n, out_dev, out_norm, s);
+}
+void mgs_block_pass(const float *const *prev, int m_prev, const float *const *next, int m_next, bool last,
+                    const double *c_prev, const double *gram_prev, double *h_out, double *w, int n, double *out_dev,
+                    double *out_norm, hipStream_t s) {
+  mgs_block_pass_t(prev, m_prev, next, m_next, last, c_prev, gram_prev, h_out, w, n, out_dev, out_norm, s);
+}
 
-void mass_dot(const double *const *vecs, int m, const double *w, int n, double *out_dev, hipStream_t s) {
+template <class T>
+static void mass_dot_t(const T *const *vecs, int m, const double *w, int n, double *out_dev, hipStream_t s) {
   const int g = vec_grid(n);
   double *partials = ctx().red_partials.p;
   prof_begin(PROF_DOT, s);
   for (int j0 = 0; j0 < m; j0 += MASS_NV) {
     const int mm = std::min(MASS_NV, m - j0);
-    MassPtrs P;
+    MassPtrs<T> P;
     for (int j = 0; j < MASS_NV; j++) P.p[j] = vecs[j0 + (j < mm ? j : 0)];
-    hipLaunchKernelGGL(mass_dot_partial_k, dim3(g), dim3(256), 0, s, P, mm, w, n, partials);
+    hipLaunchKernelGGL(mass_dot_partial_k<T>, dim3(g), dim3(256), 0, s, P, mm, w, n, partials);
     hipLaunchKernelGGL(reduce_final_multi_k, dim3(mm), dim3(256), 0, s, partials, g, out_dev + j0);
   }
   prof_end(PROF_DOT, s);
   MI_HIP(hipGetLastError());
 }
 
-void mass_axpy(const double *const *vecs, int m, const double *coef_dev, double scale_, double *w, int n,
-               hipStream_t s) {
+void mass_dot(const double *const *vecs, int m, const double *w, int n, double *out_dev, hipStream_t s) {
+  mass_dot_t(vecs, m, w, n, out_dev, s);
+}
+void mass_dot(const float *const *vecs, int m, const double *w, int n, double *out_dev, hipStream_t s) {
+  mass_dot_t(vecs, m, w, n, out_dev, s);
+}
+
+template <class T>
+static void mass_axpy_t(const T *const *vecs, int m, const double *coef_dev, double scale_, double *w, int n,
+                        hipStream_t s) {
   if (n == 0) return;
   prof_begin(PROF_AXPY, s);
   for (int j0 = 0; j0 < m; j0 += MASS_NV) {
     const int mm = std::min(MASS_NV, m - j0);
-    MassPtrs P;
+    MassPtrs<T> P;
     for (int j = 0; j < MASS_NV; j++) P.p[j] = vecs[j0 + (j < mm ? j : 0)];
-    hipLaunchKernelGGL(mass_axpy_k, dim3(vec_grid(n)), dim3(256), 0, s, P, mm, coef_dev + j0, scale_, w, n);
+    hipLaunchKernelGGL(mass_axpy_k<T>, dim3(vec_grid(n)), dim3(256), 0, s, P, mm, coef_dev + j0, scale_, w, n);
   }
   prof_end(PROF_AXPY, s);
   MI_HIP(hipGetLastError());
 }
 
-void lin_comb(const double *const *vecs, const double *coef_host, int m, bool init, double *w, int n, hipStream_t s) {
+void mass_axpy(const double *const *vecs, int m, const double *coef_dev, double scale_, double *w, int n,
+               hipStream_t s) {
+  mass_axpy_t(vecs, m, coef_dev, scale_, w, n, s);
+}
+void mass_axpy(const float *const *vecs, int m, const double *coef_dev, double scale_, double *w, int n, hipStream_t s) {
+  mass_axpy_t(vecs, m, coef_dev, scale_, w, n, s);
+}
+
+template <class T>
+static void lin_comb_t(const T *const *vecs, const double *coef_host, int m, bool init, double *w, int n, hipStream_t s) {
   if (n == 0 || m == 0) return;
   prof_begin(PROF_AXPY, s);
   for (int j0 = 0; j0 < m; j0 += MASS_NV) {
     const int mm = std::min(MASS_NV, m - j0);
-    MassPtrs P;
+    MassPtrs<T> P;
     MassCoef C;
     for (int j = 0; j < MASS_NV; j++) {
       P.p[j] = vecs[j0 + (j < mm ? j : 0)];
       C.c[j] = j < mm ? coef_host[j0 + j] : 0.0;
     }
     if (init && j0 == 0)
-      hipLaunchKernelGGL(lin_comb_k<true>, dim3(vec_grid(n)), dim3(256), 0, s, P, mm, C, w, n);
+      hipLaunchKernelGGL((lin_comb_k<true, T>), dim3(vec_grid(n)), dim3(256), 0, s, P, mm, C, w, n);
     else
-      hipLaunchKernelGGL(lin_comb_k<false>, dim3(vec_grid(n)), dim3(256), 0, s, P, mm, C, w, n);
+      hipLaunchKernelGGL((lin_comb_k<false, T>), dim3(vec_grid(n)), dim3(256), 0, s, P, mm, C, w, n);
   }
   prof_end(PROF_AXPY, s);
   MI_HIP(hipGetLastError());
+}
+
+void lin_comb(const double *const *vecs, const double *coef_host, int m, bool init, double *w, int n, hipStream_t s) {
+  lin_comb_t(vecs, coef_host, m, init, w, n, s);
+}
+void lin_comb(const float *const *vecs, const double *coef_host, int m, bool init, double *w, int n, hipStream_t s) {
+  lin_comb_t(vecs, coef_host, m, init, w, n, s);
 }
 
 void axpy(double alpha, const double *x, double *y, int n, hipStream_t s) {
@@ -3145,6 +3209,83 @@ void scale_inv_sqrt_post(const double *sumsq_dev, double *x, int n, const double
 void scale_inv_sqrt_dev(const double *sumsq_dev, double *x, int n, hipStream_t s) {
   if (n == 0) return;
   hipLaunchKernelGGL(scale_k<1>, dim3(vec_grid(n)), dim3(256), 0, s, sumsq_dev, 1.0, x, n);
+  MI_HIP(hipGetLastError());
+}
+// ---- the rounding variants of the three scalings (Krylov basis storage modes 1 and 2): the
+// product x_i * a of the plain kernel first, then its rounding to float; x_i = rd(x_i * a) = (double)(float)(x_i * a),
+// and with SLOT the float itself goes into slot_i (mode 1's basis vector).  Same element-to-lane mapping as the plain
+// kernels; the float pair of a lane is one 8-byte store.
+template <bool SLOT>
+__device__ __forceinline__ void scale_round_body(double a, double *__restrict__ x, float *__restrict__ slot, int n) {
+  const long long stride = (long long)gridDim.x * 512;
+  long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 2;
+  for (; i + 1 < n; i += stride) {
+    double2 v = *reinterpret_cast<double2 *>(x + i);
+    f2_t f;
+    f.x = (float)(v.x * a);
+    f.y = (float)(v.y * a);
+    v.x = (double)f.x;
+    v.y = (double)f.y;
+    *reinterpret_cast<double2 *>(x + i) = v;
+    if (SLOT) *reinterpret_cast<f2_t *>(slot + i) = f;
+  }
+  if (i < n) {
+    const float f = (float)(x[i] * a);
+    x[i] = (double)f;
+    if (SLOT) slot[i] = f;
+  }
+}
+// MODE as scale_k
+template <int MODE, bool SLOT>
+__global__ __launch_bounds__(256) void scale_round_k(const double *__restrict__ sumsq_dev, double scale,
+                                                     double *__restrict__ x, float *__restrict__ slot, int n) {
+  double a = scale;
+  if (MODE == 1) {
+    const double t = sumsq_dev[0];
+    if (!(t > 0.0)) return;
+    a = 1.0 / sqrt(t);
+  }
+  scale_round_body<SLOT>(a, x, slot, n);
+}
+// scale_post_k with the rounding: the posting is that kernel's
+template <bool SLOT>
+__global__ __launch_bounds__(256) void scale_post_round_k(const double *__restrict__ sumsq_dev, double *__restrict__ x,
+                                                          float *__restrict__ slot, int n, const double *__restrict__ slots,
+                                                          int count, double *__restrict__ host_out,
+                                                          unsigned long long *__restrict__ host_flag, unsigned long long seq) {
+  if (blockIdx.x == 0 && threadIdx.x < 64) {
+    for (int j = threadIdx.x; j < count; j += 64)
+      __hip_atomic_store(host_out + j, slots[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    if (threadIdx.x == 0) __hip_atomic_store(host_flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  const double t = sumsq_dev[0];
+  if (!(t > 0.0)) return;
+  scale_round_body<SLOT>(1.0 / sqrt(t), x, slot, n);
+}
+void scale_round(double alpha, double *x, float *slot, int n, hipStream_t s) {
+  if (n == 0) return;
+  if (slot)
+    hipLaunchKernelGGL((scale_round_k<0, true>), dim3(vec_grid(n)), dim3(256), 0, s, (const double *)nullptr, alpha, x, slot, n);
+  else
+    hipLaunchKernelGGL((scale_round_k<0, false>), dim3(vec_grid(n)), dim3(256), 0, s, (const double *)nullptr, alpha, x, slot, n);
+  MI_HIP(hipGetLastError());
+}
+void scale_inv_sqrt_dev_round(const double *sumsq_dev, double *x, float *slot, int n, hipStream_t s) {
+  if (n == 0) return;
+  if (slot)
+    hipLaunchKernelGGL((scale_round_k<1, true>), dim3(vec_grid(n)), dim3(256), 0, s, sumsq_dev, 1.0, x, slot, n);
+  else
+    hipLaunchKernelGGL((scale_round_k<1, false>), dim3(vec_grid(n)), dim3(256), 0, s, sumsq_dev, 1.0, x, slot, n);
+  MI_HIP(hipGetLastError());
+}
+void scale_inv_sqrt_post_round(const double *sumsq_dev, double *x, float *slot, int n, const double *slots, int count,
+                               double *host_out, unsigned long long *host_flag, unsigned long long seq, hipStream_t s) {
+  const dim3 g(n ? vec_grid(n) : 1);
+  if (slot)
+    hipLaunchKernelGGL(scale_post_round_k<true>, g, dim3(256), 0, s, sumsq_dev, x, slot, n, slots, count, host_out, host_flag, seq);
+  else
+    hipLaunchKernelGGL(scale_post_round_k<false>, g, dim3(256), 0, s, sumsq_dev, x, slot, n, slots, count, host_out, host_flag, seq);
   MI_HIP(hipGetLastError());
 }
 // Tabulation of a linear map column by column inside ONE captured graph (BoomerAMG::tabulate_cycle): the column number

@@ -282,6 +282,16 @@ void axpy_dot(const double *alpha_dev, double scale, const double *xa, double *y
 void mgs_block_pass(const double *const *prev, int m_prev, const double *const *next, int m_next, bool last,
                     const double *c_prev, const double *gram_prev, double *h_out, double *w, int n, double *out_dev,
                     double *out_norm, hipStream_t s);
+// Krylov basis storage mode 1: the same kernels instantiated on basis vectors stored as float --
+// mgs_block_pass, mass_dot, mass_axpy and lin_comb below take `const float *const *` too.  w, the sums and every output
+// stay double; elements map to lanes and sums run as in the double instantiation, so a float call gives the bits of the
+// double call on the same (float-representable) values.
+void mgs_block_pass(const float *const *prev, int m_prev, const float *const *next, int m_next, bool last,
+                    const double *c_prev, const double *gram_prev, double *h_out, double *w, int n, double *out_dev,
+                    double *out_norm, hipStream_t s);
+void mass_dot(const float *const *vecs, int m, const double *w, int n, double *out_dev, hipStream_t s);
+void mass_axpy(const float *const *vecs, int m, const double *coef_dev, double scale, double *w, int n, hipStream_t s);
+void lin_comb(const float *const *vecs, const double *coef_host, int m, bool init, double *w, int n, hipStream_t s);
 // block Gram-Schmidt (COGMRES): out_dev[j] = <vecs[j], w> for j < m (local sums), and w += scale * sum_j coef_dev[j] vecs[j]
 void mass_dot(const double *const *vecs, int m, const double *w, int n, double *out_dev, hipStream_t s);
 void mass_axpy(const double *const *vecs, int m, const double *coef_dev, double scale, double *w, int n, hipStream_t s);
@@ -295,6 +305,12 @@ void scale(double alpha, double *x, int n, hipStream_t s);
 void scale_inv_sqrt_post(const double *sumsq_dev, double *x, int n, const double *slots, int count, double *host_out,
                          unsigned long long *host_flag, unsigned long long seq, hipStream_t s);
 void scale_inv_sqrt_dev(const double *sumsq_dev, double *x, int n, hipStream_t s);
+// the three scalings with the rounding of basis storage modes 1 and 2: x_i = rd(x_i * a), rd(v) = (double)(float)v (the
+// product first, then the rounding); slot (mode 1; NULL in mode 2) also receives (float)(x_i * a).  Posting as above.
+void scale_round(double alpha, double *x, float *slot, int n, hipStream_t s);
+void scale_inv_sqrt_post_round(const double *sumsq_dev, double *x, float *slot, int n, const double *slots, int count,
+                               double *host_out, unsigned long long *host_flag, unsigned long long seq, hipStream_t s);
+void scale_inv_sqrt_dev_round(const double *sumsq_dev, double *x, float *slot, int n, hipStream_t s);
 void load_device_code(hipStream_t s);
 void fill(double *x, int n, double v, hipStream_t s);
 void copy(const double *x, double *y, int n, hipStream_t s);

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #include "HYPRE_parcsr_ls.h"
 #include "kernels.hpp"
@@ -43,6 +44,20 @@ bool &gmres_keep_directions() {
 int &gmres_keep_fail_at() {
   static int at = -1;
   return at;
+}
+// MI_HYPRE_BASIS_STORAGE / HYPRE_MI_SetKrylovBasisStorage; a value the environment gives that is
+// not a mode leaves the default and is reported once on stderr (the setter refuses such a value)
+int &krylov_basis_storage() {
+  static int mode = [] {
+    const char *e = getenv("MI_HYPRE_BASIS_STORAGE");
+    if (!e || !*e) return 0;
+    char *end = nullptr;
+    const long v = strtol(e, &end, 10);
+    if (*end == '\0' && v >= 0 && v <= 2) return (int)v;
+    fprintf(stderr, "mi_hypre: MI_HYPRE_BASIS_STORAGE=%s is not a mode (0, 1 or 2): the Krylov basis stays fp64 (mode 0)\n", e);
+    return 0;
+  }();
+  return mode;
 }
 
 void KrylovSolver::apply_precond(ParCSR &A, ParVector &rhs, ParVector &out) {
@@ -170,7 +185,22 @@ void GmresSolver::setup(ParCSR &A, ParVector &b, ParVector &x) {
   // Solve, src/HypreSystem.cpp:692 inside the loop at :681); another shape starts afresh
   if (!p.empty() && (p[0]->n != b.n || p[0]->ncomp != b.ncomp || p[0]->start != b.start)) p.clear();
   if (!z.empty() && (z[0]->n != b.n || z[0]->ncomp != b.ncomp || z[0]->start != b.start)) z.clear();
+  keep_or_drop_basis(b);
   run_precond_setup(A, b, x);
+}
+
+// the basis also goes when the storage mode is no longer the one it was made under (fp64 vectors, fp64 vectors of
+// rounded values and float slots do not stand in for each other), and mode 1's vectors when the shape changed
+void GmresSolver::keep_or_drop_basis(const ParVector &b) {
+  const int mode = krylov_basis_storage();
+  const bool reshaped = work[0].d.p && (work[0].n != b.n || work[0].ncomp != b.ncomp || work[0].start != b.start);
+  if (mode != basis_mode || reshaped) {
+    if (mode != basis_mode) p.clear();
+    p32.clear();
+    work[0] = ParVector();
+    work[1] = ParVector();
+  }
+  basis_mode = mode;
 }
 
 int GmresSolver::solve(ParCSR &A_in, ParVector &b_in, ParVector &x_in) {
@@ -186,8 +216,30 @@ int GmresSolver::solve(ParCSR &A_in, ParVector &b_in, ParVector &x_in) {
   const int kd = k_dim < 1 ? 1 : k_dim;
   MI_REQUIRE(kd + 2 <= (ortho > 1 ? 120 : 250), "GMRES: k_dim too large for the device scalar slots");
   MI_REQUIRE(ortho >= 0 && ortho <= 2, "GMRES: orthogonalisation must be 0 (MGS), 1 or 2 (classical passes)");
-  if (r.n != nloc || r.ncomp != nc) setup(A_in, b_in, x_in);
+  // basis storage: 1 = float slots and two rotating fp64 work vectors, 2 = fp64 vectors of
+  // float-rounded values; both restart from b - A x.  One rank: the fused dot of N > 1 ranks has no float instantiation
+  const int bmode = krylov_basis_storage();
+  const bool f32 = bmode == 1;
+  if (bmode != 0 && comm.size > 1)
+    fail(HYPRE_ERROR_ARG,
+         "GMRES: Krylov basis storage mode " + std::to_string(bmode) +
+             " (HYPRE_MI_SetKrylovBasisStorage / MI_HYPRE_BASIS_STORAGE) runs on one rank only; N > 1 ranks take mode 0");
+  if (r.n != nloc || r.ncomp != nc)
+    setup(A_in, b_in, x_in);
+  else
+    keep_or_drop_basis(b_in);
+  if (f32 && !work[0].d.p)
+    for (ParVector &v : work) v.init(b_in.start, b_in.end, nc);
   const double epsmac = 1.e-16;
+  auto slot32 = [&](int i) -> float * {
+    while ((int)p32.size() <= i) {
+      p32.emplace_back();
+      p32.back().alloc((size_t)n);
+      c.n_krylov_basis_fp32++;
+    }
+    return p32[(size_t)i].p;
+  };
+  int cur = 0;  // mode 1: work[cur] holds p_{i-1}, work[1 - cur] takes A z
   auto basis = [&](int i) -> ParVector & {
     while ((int)p.size() <= i) {
       std::unique_ptr<ParVector> v(new ParVector());
@@ -269,15 +321,22 @@ int GmresSolver::solve(ParCSR &A_in, ParVector &b_in, ParVector &x_in) {
   // number -- Givens rotations, the convergence test and the launches of the next cycle happen while that kernel still
   // runs, and no copy kernel or stream synchronisation stands between two steps (MI_HYPRE_GMRES_POLL=0: the round-3 way)
   static const bool poll = !(getenv("MI_HYPRE_GMRES_POLL") && atoi(getenv("MI_HYPRE_GMRES_POLL")) == 0);
-  auto fetch_column = [&](const double *norm_slot, double *vec, int count) {
+  // (modes 1 and 2: the rounding variants; slot = the float basis slot of mode 1, else null)
+  auto fetch_column = [&](const double *norm_slot, double *vec, float *slot, int count) {
     if (!poll || count > 255) {
-      k::scale_inv_sqrt_dev(norm_slot, vec, n, s);
+      if (bmode)
+        k::scale_inv_sqrt_dev_round(norm_slot, vec, slot, n, s);
+      else
+        k::scale_inv_sqrt_dev(norm_slot, vec, n, s);
       MI_HIP(hipMemcpyAsync(c.h_pinned, slots, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, s));
       MI_HIP(hipStreamSynchronize(s));
       return;
     }
     const unsigned long long seq = ++c.post_seq;
-    k::scale_inv_sqrt_post(norm_slot, vec, n, slots, count, c.h_pinned + 256, c.h_post_flag, seq, s);
+    if (bmode)
+      k::scale_inv_sqrt_post_round(norm_slot, vec, slot, n, slots, count, c.h_pinned + 256, c.h_post_flag, seq, s);
+    else
+      k::scale_inv_sqrt_post(norm_slot, vec, n, slots, count, c.h_pinned + 256, c.h_post_flag, seq, s);
     const double t0 = wall_time();
     unsigned spins = 0;
     while (__atomic_load_n(c.h_post_flag, __ATOMIC_ACQUIRE) != seq) {
@@ -289,7 +348,8 @@ int GmresSolver::solve(ParCSR &A_in, ParVector &b_in, ParVector &x_in) {
     }
     memcpy(c.h_pinned, c.h_pinned + 256, (size_t)count * sizeof(double));
   };
-  ParVector &p0 = basis(0);
+  // the fp64 vector the (restart) residual is built in: p_0 itself, or mode 1's first work vector
+  ParVector &p0 = f32 ? work[0] : basis(0);
   mv(-1.0, x.all(), 1.0, b.all(), p0.data());
   const double b_norm = std::sqrt(par_dot_host(comm, b.all(), b.all(), n, s));
   double r_norm = std::sqrt(par_dot_host(comm, p0.data(), p0.data(), n, s));
@@ -328,14 +388,18 @@ int GmresSolver::solve(ParCSR &A_in, ParVector &b_in, ParVector &x_in) {
       }
       if (chatty) printf("false convergence 1\n");
     }
-    k::scale(1.0 / r_norm, basis(0).data(), n, s);
+    if (bmode)
+      k::scale_round(1.0 / r_norm, p0.data(), f32 ? slot32(0) : nullptr, n, s);
+    else
+      k::scale(1.0 / r_norm, basis(0).data(), n, s);
+    cur = 0;
     int i = 0;
     bool kept = keep;  // every z_j of this restart cycle so far is in zvec(j)
     while (i < kd && iter < max_iter) {
       i++;
       iter++;
-      ParVector &pi = basis(i);
-      ParVector &pim1 = basis(i - 1);
+      ParVector &pi = f32 ? work[1 - cur] : basis(i);
+      ParVector &pim1 = f32 ? work[cur] : basis(i - 1);
       ParVector *zk = kept ? try_zvec(i - 1) : nullptr;
       if (kept && !zk) keep = kept = false;
       const bool adopt = zk && nc == 1 && amg->L[0].u.n == zk->d.n;
@@ -369,60 +433,76 @@ int GmresSolver::solve(ParCSR &A_in, ParVector &b_in, ParVector &x_in) {
         mv(1.0, mp, 0.0, nullptr, pi.data());
       }
       TraceRange trace_ortho("Gram-Schmidt + Givens");
-      if (ortho == 0 && comm.size == 1) {
-        // blocked modified Gram-Schmidt over aligned blocks of NB basis vectors, ceil(i / NB) + 1 passes over w = p_i:
-        // pass 0 takes the raw inner products of block 0; pass k turns those of block k-1 into MGS coefficients (forward
-        // substitution with the block's Gram rows), subtracts, and takes the raw products of block k off the new w; the
-        // last pass subtracts the last block and leaves ||w||^2 and the Gram row of p_i
-        constexpr int NB = k::MGS_NB;
-        const size_t rows = ((size_t)kd + 1) * (NB + 1);
-        if (mgs_gram.n < rows + 2 * (NB + 1)) mgs_gram.alloc(rows + 2 * (NB + 1));
-        double *gram = mgs_gram.p, *cbuf = mgs_gram.p + rows;
-        const double *vp[NB], *vn[NB];
-        const int nblk = (i + NB - 1) / NB;
-        for (int kb = 0; kb <= nblk; kb++) {
-          const int jp = (kb - 1) * NB, jn = kb * NB;  // first vector of the block subtracted / measured
-          const int m_prev = kb ? std::min(NB, i - jp) : 0, m_next = kb < nblk ? std::min(NB, i - jn) : 0;
-          for (int j = 0; j < m_prev; j++) vp[j] = basis(jp + j).data();
-          for (int j = 0; j < m_next; j++) vn[j] = basis(jn + j).data();
-          const bool last = kb == nblk;
-          k::mgs_block_pass(vp, m_prev, vn, m_next, last, kb ? cbuf + ((kb - 1) & 1) * (NB + 1) : nullptr,
-                            kb ? gram + (size_t)jp * (NB + 1) : nullptr, kb ? slots + jp : nullptr, pi.data(), n,
-                            last ? gram + (size_t)i * (NB + 1) : cbuf + (kb & 1) * (NB + 1), last ? slots + i : nullptr, s);
+      // bvec(j): basis vector j as the kernels read it -- doubles, or the float slots of mode 1 (the kernels'
+      // instantiations on float, same sums in the same order)
+      auto orthogonalise = [&](auto bvec) {
+        typedef typename std::remove_const<typename std::remove_pointer<decltype(bvec(0))>::type>::type T;
+        float *const slot = f32 ? slot32(i) : nullptr;
+        if (ortho == 0 && comm.size == 1) {
+          // blocked modified Gram-Schmidt over aligned blocks of NB basis vectors, ceil(i / NB) + 1 passes over w = p_i:
+          // pass 0 takes the raw inner products of block 0; pass k turns those of block k-1 into MGS coefficients (forward
+          // substitution with the block's Gram rows), subtracts, and takes the raw products of block k off the new w; the
+          // last pass subtracts the last block and leaves ||w||^2 and the Gram row of p_i
+          constexpr int NB = k::MGS_NB;
+          const size_t rows = ((size_t)kd + 1) * (NB + 1);
+          if (mgs_gram.n < rows + 2 * (NB + 1)) mgs_gram.alloc(rows + 2 * (NB + 1));
+          double *gram = mgs_gram.p, *cbuf = mgs_gram.p + rows;
+          const T *vp[NB], *vn[NB];
+          const int nblk = (i + NB - 1) / NB;
+          for (int kb = 0; kb <= nblk; kb++) {
+            const int jp = (kb - 1) * NB, jn = kb * NB;  // first vector of the block subtracted / measured
+            const int m_prev = kb ? std::min(NB, i - jp) : 0, m_next = kb < nblk ? std::min(NB, i - jn) : 0;
+            for (int j = 0; j < m_prev; j++) vp[j] = bvec(jp + j);
+            for (int j = 0; j < m_next; j++) vn[j] = bvec(jn + j);
+            const bool last = kb == nblk;
+            k::mgs_block_pass(vp, m_prev, vn, m_next, last, kb ? cbuf + ((kb - 1) & 1) * (NB + 1) : nullptr,
+                              kb ? gram + (size_t)jp * (NB + 1) : nullptr, kb ? slots + jp : nullptr, pi.data(), n,
+                              last ? gram + (size_t)i * (NB + 1) : cbuf + (kb & 1) * (NB + 1), last ? slots + i : nullptr, s);
+          }
+          fetch_column(slots + i, pi.data(), slot, i + 1);
+          for (int j = 0; j < i; j++) hh[(size_t)j][(size_t)i - 1] = c.h_pinned[j];
+        } else if (ortho == 0) {
+          if constexpr (std::is_same<T, double>::value) {  // (N > 1 ranks: fp64 basis only)
+            // modified Gram-Schmidt with the axpy of step j-1 fused into the dot of step j
+            // (and the last axpy into the norm): h_j = <p_j, w>, w -= h_j p_j, one pass each
+            par_dot(comm, basis(0).data(), pi.data(), n, slots, s);
+            for (int j = 1; j <= i; j++) {
+              k::axpy_dot(slots + j - 1, -1.0, basis(j - 1).data(), pi.data(), j < i ? basis(j).data() : nullptr, n,
+                          slots + j, s);
+              if (comm.size > 1) comm.allreduce_dev(slots + j, 1, CommDType::F64, CommOp::SUM, s), c.n_allreduce++;
+            }
+            fetch_column(slots + i, pi.data(), slot, i + 1);
+            for (int j = 0; j < i; j++) hh[(size_t)j][(size_t)i - 1] = c.h_pinned[j];
+          } else {
+            fail(1, "GMRES: the chain Gram-Schmidt of N > 1 ranks has no float instantiation");  // refused at the top of solve()
+          }
+        } else {
+          // classical Gram-Schmidt: per pass ONE block of inner products (one all-reduce of i values) and one
+          // block update; coefficients of the passes add up.  Slots: pass q at [128 q, 128 q + i), norm^2 at [i].
+          std::vector<const T *> vecs((size_t)i);
+          for (int j = 0; j < i; j++) vecs[(size_t)j] = bvec(j);
+          for (int q = 0; q < ortho; q++) {
+            double *cs_dev = slots + 128 * q;
+            k::mass_dot(vecs.data(), i, pi.data(), n, cs_dev, s);
+            if (comm.size > 1) comm.allreduce_dev(cs_dev, (size_t)i, CommDType::F64, CommOp::SUM, s), c.n_allreduce++;
+            k::mass_axpy(vecs.data(), i, cs_dev, -1.0, pi.data(), n, s);
+          }
+          double *nrm = (ortho == 1) ? slots + i : slots + 128 + i;  // adjacent to the last pass: one copy below
+          par_dot(comm, pi.data(), pi.data(), n, nrm, s);
+          fetch_column(nrm, pi.data(), slot, 128 * (ortho - 1) + i + 1);
+          for (int j = 0; j < i; j++) {
+            double hsum = c.h_pinned[j];
+            if (ortho > 1) hsum += c.h_pinned[128 + j];
+            hh[(size_t)j][(size_t)i - 1] = hsum;
+          }
+          c.h_pinned[i] = c.h_pinned[128 * (ortho - 1) + i];
         }
-        fetch_column(slots + i, pi.data(), i + 1);
-        for (int j = 0; j < i; j++) hh[(size_t)j][(size_t)i - 1] = c.h_pinned[j];
-      } else if (ortho == 0) {
-        // modified Gram-Schmidt with the axpy of step j-1 fused into the dot of step j
-        // (and the last axpy into the norm): h_j = <p_j, w>, w -= h_j p_j, one pass each
-        par_dot(comm, basis(0).data(), pi.data(), n, slots, s);
-        for (int j = 1; j <= i; j++) {
-          k::axpy_dot(slots + j - 1, -1.0, basis(j - 1).data(), pi.data(), j < i ? basis(j).data() : nullptr, n,
-                      slots + j, s);
-          if (comm.size > 1) comm.allreduce_dev(slots + j, 1, CommDType::F64, CommOp::SUM, s), c.n_allreduce++;
-        }
-        fetch_column(slots + i, pi.data(), i + 1);
-        for (int j = 0; j < i; j++) hh[(size_t)j][(size_t)i - 1] = c.h_pinned[j];
+      };
+      if (f32) {
+        orthogonalise([&](int j) -> const float * { return slot32(j); });
+        cur = 1 - cur;  // the scaled vector is p_i, rounded: the next step's right-hand side
       } else {
-        // classical Gram-Schmidt: per pass ONE block of inner products (one all-reduce of i values) and one
-        // block update; coefficients of the passes add up.  Slots: pass q at [128 q, 128 q + i), norm^2 at [i].
-        std::vector<const double *> vecs((size_t)i);
-        for (int j = 0; j < i; j++) vecs[(size_t)j] = basis(j).data();
-        for (int q = 0; q < ortho; q++) {
-          double *cs_dev = slots + 128 * q;
-          k::mass_dot(vecs.data(), i, pi.data(), n, cs_dev, s);
-          if (comm.size > 1) comm.allreduce_dev(cs_dev, (size_t)i, CommDType::F64, CommOp::SUM, s), c.n_allreduce++;
-          k::mass_axpy(vecs.data(), i, cs_dev, -1.0, pi.data(), n, s);
-        }
-        double *nrm = (ortho == 1) ? slots + i : slots + 128 + i;  // adjacent to the last pass: one copy below
-        par_dot(comm, pi.data(), pi.data(), n, nrm, s);
-        fetch_column(nrm, pi.data(), 128 * (ortho - 1) + i + 1);
-        for (int j = 0; j < i; j++) {
-          double hsum = c.h_pinned[j];
-          if (ortho > 1) hsum += c.h_pinned[128 + j];
-          hh[(size_t)j][(size_t)i - 1] = hsum;
-        }
-        c.h_pinned[i] = c.h_pinned[128 * (ortho - 1) + i];
+        orthogonalise([&](int j) -> const double * { return basis(j).data(); });
       }
       const double t = std::sqrt(c.h_pinned[i] > 0.0 ? c.h_pinned[i] : 0.0);
       hh[(size_t)i][(size_t)i - 1] = t;
@@ -481,12 +561,19 @@ int GmresSolver::solve(ParCSR &A_in, ParVector &b_in, ParVector &x_in) {
       // copy / scale / axpy chain does -- in one or a few passes over the basis instead of i)
       {
         std::vector<const double *> vp((size_t)i);
+        std::vector<const float *> vp32((size_t)i);
         std::vector<double> cf((size_t)i);
         for (int j = i - 1, q = 0; j >= 0; j--, q++) {
-          vp[(size_t)q] = basis(j).data();
+          if (f32)
+            vp32[(size_t)q] = slot32(j);
+          else
+            vp[(size_t)q] = basis(j).data();
           cf[(size_t)q] = y[(size_t)j];
         }
-        k::lin_comb(vp.data(), cf.data(), i, true, w.data(), n, s);
+        if (f32)
+          k::lin_comb(vp32.data(), cf.data(), i, true, w.data(), n, s);
+        else
+          k::lin_comb(vp.data(), cf.data(), i, true, w.data(), n, s);
       }
       const double *mw = precond(w, r, false);
       k::axpy(1.0, mw, x.all(), n, s);
@@ -499,14 +586,15 @@ int GmresSolver::solve(ParCSR &A_in, ParVector &b_in, ParVector &x_in) {
         break;
       }
       if (chatty) printf("false convergence 2\n");
-      k::copy(r.data(), basis(0).data(), n, s);
+      k::copy(r.data(), p0.data(), n, s);
       i = 0;
     }
-    if (flexible) {
-      // flexgmres.c restarts from the explicitly recomputed residual
+    if (flexible || bmode) {
+      // flexgmres.c restarts from the explicitly recomputed residual; so do basis storage modes 1 and 2 (the residual
+      // rebuilt from the Givens data and the stored basis would carry the float error into the next cycle)
       if (i) {
-        mv(-1.0, x.all(), 1.0, b.all(), basis(0).data());
-        r_norm = std::sqrt(par_dot_host(comm, basis(0).data(), basis(0).data(), n, s));
+        mv(-1.0, x.all(), 1.0, b.all(), p0.data());
+        r_norm = std::sqrt(par_dot_host(comm, p0.data(), p0.data(), n, s));
       }
       continue;
     }
@@ -535,6 +623,8 @@ int GmresSolver::solve(ParCSR &A_in, ParVector &b_in, ParVector &x_in) {
   num_iterations = iter;
   rel_residual_norm = (b_norm > 0.0) ? r_norm / b_norm : r_norm;
   solve_seconds = wall_time() - t_start;
+  c.krylov_basis_bytes = f32 ? (long long)sizeof(float) * n * (long long)p32.size()
+                             : (long long)sizeof(double) * n * (long long)p.size();
   if (chatty) {
     printf("\n\nFinal L2 norm of residual: %e\n\n", r_norm);
     (void)r_norm_0;

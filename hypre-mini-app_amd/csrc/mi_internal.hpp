@@ -361,6 +361,9 @@ struct Ctx {
   // BoomerAMG cycles a Krylov solver asked for as its preconditioner (cycle(0, ..) while krylov_precond_depth > 0), and
   // the vectors GMRES allocated to keep its preconditioned directions (krylov.cpp, "kept directions")
   long long n_precond_cycles = 0, n_gmres_z_allocated = 0;
+  // Krylov basis storage: float basis slots allocated so far (mode 1), and the bytes the basis
+  // vectors of the last GMRES / COGMRES / FlexGMRES solve hold (mode 1's two fp64 work vectors are not basis vectors)
+  long long n_krylov_basis_fp32 = 0, krylov_basis_bytes = 0;
   // C-row hand-over: Krylov mat-vecs that ran on level 0's tile list, and the tiles they left out
   long long n_handover_matvecs = 0, n_handover_tiles_skipped = 0;
   // multivectors: cycle passes / mat-vec passes that ran batched, multivector cycles that looped over the components

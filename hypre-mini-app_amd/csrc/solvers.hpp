@@ -51,6 +51,10 @@ struct KrylovSolver : SolverBase {
 // switch, and a test hook: the allocation of kept vector number `at` and beyond counts as failed, -1 = never)
 bool &gmres_keep_directions();
 int &gmres_keep_fail_at();
+// How GMRES, COGMRES and FlexGMRES store their Krylov basis (MI_HYPRE_BASIS_STORAGE / HYPRE_MI_SetKrylovBasisStorage;
+// DESIGN.md section 3): 0 fp64; 1 float; 2 fp64 vectors holding the float-rounded values (mode 1's reference).
+// Process-wide, read at the start of a solve; one rank only.
+int &krylov_basis_storage();
 
 struct GmresSolver : KrylovSolver {
   std::vector<std::unique_ptr<ParVector>> p;
@@ -65,6 +69,14 @@ struct GmresSolver : KrylovSolver {
   // solution buffer of the preconditioner (same size, swapped in after the cycle)
   std::vector<std::unique_ptr<ParVector>> z;
   ParVector r, w;
+  // basis storage mode 1: the basis vectors as floats (p stays empty), and the two fp64 work vectors that rotate --
+  // one holds p_{i-1} widened (the preconditioner's right-hand side), the other receives A z, is orthogonalised in
+  // place and scaled into the next float slot.  basis_mode: the mode the vectors held were made under
+  std::vector<DVec<float>> p32;
+  ParVector work[2];
+  int basis_mode = 0;
+  // a basis of another shape or another storage mode is dropped (Setup and Solve)
+  void keep_or_drop_basis(const ParVector &b);
   // blocked MGS (one rank, ortho 0): row i = the raw Gram row of p_i, k::MGS_NB + 1 doubles
   // written by the pass that made p_i; after the k_dim + 1 rows, two alternating sets of k::MGS_NB + 1 raw inner products
   DVec<double> mgs_gram;

@@ -282,6 +282,16 @@ void HypreSystem::setup_precon_and_solver() {
       throw std::runtime_error(std::string("Hypre Config:: mi_multivector_batch: ") + HYPRE_MI_LastErrorMessage());
 #endif
   }
+  /* this library's key: mi_basis_storage = how GMRES / COGMRES / FlexGMRES store their Krylov basis: 0 fp64, 1 float,
+   * 2 fp64 vectors of the float-rounded values (mode 1's reference); absent = the library's setting */
+  if (solver["mi_basis_storage"]) {
+#ifdef MI_HOST_WITH_LIBHYPRE
+    throw std::runtime_error("Hypre Config:: mi_basis_storage is a key of libmi_hypre; libHYPRE has no such setting");
+#else
+    if (HYPRE_MI_SetKrylovBasisStorage(solver["mi_basis_storage"].as<int>()))
+      throw std::runtime_error(std::string("Hypre Config:: mi_basis_storage: ") + HYPRE_MI_LastErrorMessage());
+#endif
+  }
 
   if (preconditioner == "boomeramg")
     setup_boomeramg_precond();

@@ -1035,6 +1035,19 @@ def set_gmres_keep_directions(on):
     call("HYPRE_MI_SetGmresKeepDirections", 1 if on else 0)
 
 
+def set_basis_storage(mode):
+    """how GMRES / COGMRES / FlexGMRES store their Krylov basis: 0 fp64 (default), 1 float, 2 fp64 vectors of the
+    float-rounded values (mode 1's bit-exact reference); process-wide, for the solves started afterwards, one rank.
+    Another mode raises (HYPRE_ERROR_ARG) and leaves the setting."""
+    call("HYPRE_MI_SetKrylovBasisStorage", int(mode))
+
+
+def get_basis_storage():
+    v = c_int()
+    call("HYPRE_MI_GetKrylovBasisStorage", C.byref(v))
+    return v.value
+
+
 def set_c_row_handover(mode):
     """C-row hand-over of the Krylov loops in BoomerAMG's level ordering: 0 off, 1 (default) when at least 10 % of level
     0's tiles are handed over, 2 whenever one is; process-wide, for the solves started afterwards"""
@@ -1436,16 +1449,18 @@ def same_function_filter_op(A, dof, host=False):
 VEC_MASS_DOT, VEC_MASS_AXPY, VEC_LIN_COMB, VEC_AXPY_DOT, VEC_SCALE_POST = range(5)
 
 
-def vector_kernel_op(op, vecs, coef, w, scale=1.0, xd=None, init=False):
+def vector_kernel_op(op, vecs, coef, w, scale=1.0, xd=None, init=False, f32=False):
     """One of the Krylov loops' vector kernels on IJVectors (HYPRE_MI_VectorKernelOp, test hook): returns the scalar
     results -- m inner products (VEC_MASS_DOT), one (VEC_AXPY_DOT), (posted doubles, flag word, sequence number) for
-    VEC_SCALE_POST, None for the updates.  w (and nothing else) is changed in place on the device."""
+    VEC_SCALE_POST, None for the updates.  w (and nothing else) is changed in place on the device.
+    f32: the kernel's instantiation on float basis vectors (HYPRE_MI_VectorKernelOpF32: vecs are converted to float
+    inside the call; VEC_SCALE_POST rounds w to float values and, given xd, leaves the float basis slot, widened, there)."""
     m = len(coef) if op == VEC_SCALE_POST else len(vecs)
     arr = (vp * max(len(vecs), 1))(*[v.par for v in vecs])
     cf = None if coef is None else dbl(coef)
     out = np.zeros(m + 2)
-    call("HYPRE_MI_VectorKernelOp", op, m, arr, cf, c_dbl(scale), w.par, xd.par if xd is not None else None,
-         1 if init else 0, out)
+    call("HYPRE_MI_VectorKernelOpF32" if f32 else "HYPRE_MI_VectorKernelOp", op, m, arr, cf, c_dbl(scale), w.par,
+         xd.par if xd is not None else None, 1 if init else 0, out)
     if op == VEC_MASS_DOT:
         return out[:m].copy()
     if op == VEC_AXPY_DOT:
@@ -1459,7 +1474,7 @@ VEC_MGS_BLOCK = 5
 MGS_NB = 8
 
 
-def mgs_block_pass(prev, nxt, last, c, gram, w):
+def mgs_block_pass(prev, nxt, last, c, gram, w, f32=False):
     """One pass of the blocked modified Gram-Schmidt step (k::mgs_block_pass through the test hook): the vectors `prev`
     are subtracted from w with the coefficients the kernel derives from their raw inner products c (MGS_NB doubles)
     and raw Gram rows gram (MGS_NB x (MGS_NB + 1)); then the inner products of the new w with the vectors `nxt`, or,
@@ -1470,6 +1485,6 @@ def mgs_block_pass(prev, nxt, last, c, gram, w):
     cf = dbl(np.concatenate([np.asarray(c, dtype=np.float64).ravel(), np.asarray(gram, dtype=np.float64).ravel()]))
     assert len(cf) == MGS_NB * (MGS_NB + 2)
     out = np.zeros(2 * MGS_NB + 2)
-    call("HYPRE_MI_VectorKernelOp", VEC_MGS_BLOCK, len(vecs), arr, cf, c_dbl(float(len(prev))), w.par, None,
-         1 if last else 0, out)
+    call("HYPRE_MI_VectorKernelOpF32" if f32 else "HYPRE_MI_VectorKernelOp", VEC_MGS_BLOCK, len(vecs), arr, cf,
+         c_dbl(float(len(prev))), w.par, None, 1 if last else 0, out)
     return out[:MGS_NB + 1].copy(), out[MGS_NB + 1:2 * MGS_NB + 1].copy(), float(out[2 * MGS_NB + 1])

@@ -126,6 +126,14 @@ HYPRE_Int HYPRE_MI_TileScheduleCheck(HYPRE_Int n, const HYPRE_BigInt *row_ptr, H
 HYPRE_Int HYPRE_MI_VectorKernelOp(HYPRE_Int op, HYPRE_Int m, HYPRE_ParVector *vecs, const HYPRE_Real *coef,
                                   HYPRE_Real scale, HYPRE_ParVector w, HYPRE_ParVector xd, HYPRE_Int init,
                                   HYPRE_Real *out);
+/* test hook: the same kernels instantiated on float basis vectors (HYPRE_MI_SetKrylovBasisStorage mode 1).  `vecs` are
+ * converted to float storage (round to nearest even) inside the call; w, the coefficients and all results stay double.
+ * Ops 0, 1, 2 and 5 as above.  Op 4 runs the rounding variant of the posting scaling: w = rd(w / sqrt(coef[0])) with
+ * rd(v) = (double)(float)v, and the float basis slot the kernel also writes starts as xd's values converted and comes back
+ * widened in xd (xd may be NULL); the posted doubles and the flag are as above.  Op 3 is refused. */
+HYPRE_Int HYPRE_MI_VectorKernelOpF32(HYPRE_Int op, HYPRE_Int m, HYPRE_ParVector *vecs, const HYPRE_Real *coef,
+                                     HYPRE_Real scale, HYPRE_ParVector w, HYPRE_ParVector xd, HYPRE_Int init,
+                                     HYPRE_Real *out);
 /* test hook: a seeded storm of device allocations / releases of every size through the library's allocator (arena, block
  * cache or plain, whatever MI_HYPRE_POOL says), every block pattern-filled and checked before its release */
 HYPRE_Int HYPRE_MI_ArenaSelfTest(HYPRE_Int seed, HYPRE_Int rounds, HYPRE_BigInt max_block_bytes, HYPRE_BigInt *verified,
@@ -156,6 +164,18 @@ HYPRE_Int HYPRE_MI_ParCSRMatrixMatvecMulti(HYPRE_Complex alpha, HYPRE_ParCSRMatr
  * on = 0 restores the recomputed update (env MI_HYPRE_GMRES_KEEP_DIRECTIONS=0); applies to solves started afterwards.
  * N > 1 ranks: set it alike on every rank (the ranks agree per solve on whether all of them can keep). */
 HYPRE_Int HYPRE_MI_SetGmresKeepDirections(HYPRE_Int on);
+/* How GMRES, COGMRES and FlexGMRES store their Krylov basis (compressed-basis GMRES).  0 (the
+ * default; environment MI_HYPRE_BASIS_STORAGE): fp64.  1: the basis vectors are stored as float -- half the traffic of
+ * the Gram-Schmidt passes and half the basis memory; every sum, the Hessenberg matrix, the preconditioner, the kept
+ * directions and x stay fp64.  2: fp64 vectors that hold the float-rounded values: the same iteration count, residual
+ * history, x and final residual as mode 1, bit for bit (its reference).  Modes 1 and 2 restart from b - A x.  One restart
+ * cycle cannot gain more than about 7 digits under them: leave the setting off for tight tolerances asked of a single
+ * cycle.  Any other mode is refused (HYPRE_ERROR_ARG) and the setting stays.  Process-wide, applies to solves started
+ * afterwards; BiCGSTAB and PCG ignore it.  One rank: a solve on N > 1 ranks under mode 1 or 2 is refused.  Counters
+ * (HYPRE_MI_GetCounter): "krylov_basis_fp32_vectors" (float basis vectors allocated), "krylov_basis_bytes" (bytes the
+ * basis vectors of the last solve hold). */
+HYPRE_Int HYPRE_MI_SetKrylovBasisStorage(HYPRE_Int mode);
+HYPRE_Int HYPRE_MI_GetKrylovBasisStorage(HYPRE_Int *mode);
 /* test hook: the allocation of the kept direction number `at` (from 0) and of every later one counts as failed in the
  * solves started afterwards; at < 0 = off */
 HYPRE_Int HYPRE_MI_TestGmresDirectionAllocFailsAt(HYPRE_Int at);
